@@ -5,7 +5,14 @@ A "step" is one compute_cost-equivalent pass (cross_entropy_bilevel_optimization
 1024 theta-samples: 1024 complete iLEQG solves (initialize! + iterations with line search) on the synthetic LQ-plus-noise
 problem of SURVEY.md section 8(d).  theta, x0, u0 and the problem tables are resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--spec-eps E] [--no-cpu] [--no-second]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--spec-eps E] [--dump-outputs DIR] [--full [--no-cpu] [--no-second]]
+
+A plain run does what the headline needs: set-up, 0.3 s of conditioning, W warm-up steps, EXACTLY K timed steps, the result line
+(`value`, `ms_per_step`, `strong`, `config`).  --full adds everything else the line used to carry: the CPU baseline, the per-kernel
+breakdown and the `roofline` object (event-timed passes of their own), the secondaries (other widths, sizes, paths and entry points) and,
+for N > 1, `weak` and `strong_spec_eps8`; --no-cpu / --no-second drop parts of it.
+--dump-outputs DIR writes what the last timed step computed for the global batch -- DIR/cost.npy, status.npy, iters.npy, ls_evals.npy,
+float64 -- so that two builds can be compared output for output (the inputs are seeded: identical from run to run).
 
 N > 1 (one process per GPU over RCCL):
   * started by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (WORLD_SIZE is set), or
@@ -13,8 +20,8 @@ N > 1 (one process per GPU over RCCL):
     exits with their exit code; it fails (non-zero) when fewer than N devices are visible.
   `value` is the BASELINE.json configuration: the ONE CE batch of 1024 samples sharded over the N ranks in contiguous theta blocks
   (1024 / N solves per GPU) followed by the RCCL all-gather of the per-sample costs, i.e. STRONG scaling ("scaling": "strong").
-  The same JSON line carries `weak` (1024 samples per GPU) and `strong_spec_eps8` (BASELINE config 3: 8 speculative line-search step
-  sizes per sample) measured in the same run.
+  With --full the same JSON line carries `weak` (1024 samples per GPU) and `strong_spec_eps8` (BASELINE config 3: 8 speculative
+  line-search step sizes per sample) measured in the same run.
 """
 import argparse
 import hashlib
@@ -103,6 +110,19 @@ def shard_bounds(B, world, rank):
     base, rem = divmod(B, world)
     lo = rank * base + min(rank, rem)
     return lo, lo + base + (1 if rank < rem else 0)
+
+
+def dump_outputs(path, arrays, max_bytes=64 << 20):
+    """--dump-outputs: one DIR/<name>.npy per array, all of one length (one entry per sample of the global batch), as float64 (the
+    counters are small integers: exact).  Beyond `max_bytes` in all, a fixed seeded sample of the entries is written, its indices in
+    DIR/index.npy."""
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    if 8 * n * len(arrays) > max_bytes:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=max_bytes // (8 * (len(arrays) + 1)), replace=False))
+        arrays = {**{k: np.asarray(v)[idx] for k, v in arrays.items()}, "index": idx}
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.asarray(v, dtype=np.float64))
 
 
 def kernel_source_hash():
@@ -481,6 +501,8 @@ def dry_rank(args, D):
 
     elapsed = D.timed(step, K, W)
     assert np.array_equal(gathered["all"].numpy(), 0.1 / theta), "gathered costs are not the global batch in order"
+    if D.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cost": gathered["all"].numpy()})
     if D.rank == 0:
         print(json.dumps({"metric": "iLEQG solves/sec (N=50, n=12, m=4) at CE batch=1024", "value": G * K / elapsed, "unit": "solves/s",
                           "n_gpus": D.world, "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3, "higher_is_better": True,
@@ -505,9 +527,9 @@ def rank_main(args):
     prob, x0, u0 = rat.synthetic_lq_problem(n=12, m=4, N=50, seed=0)
     theta_global = draw_theta(G, seed=1000)                  # the ONE CE batch every rank knows (same N(0,1) stream on every rank)
     lo, hi = shard_bounds(G, world, rank)
-    # The CPU baseline runs FIRST (rank 0, N = 1): the GPU legs then form one contiguous stretch at the end of the run, long enough for
-    # an external utilisation sampler to see the device at work.
-    cpu = cpu_baseline(prob, x0, u0, args.cpu_seconds) if (rank == 0 and world == 1 and not args.no_cpu) else None
+    # With --full the CPU baseline runs FIRST (rank 0, N = 1): the GPU legs then form one contiguous stretch at the end of the run, long
+    # enough for an external utilisation sampler to see the device at work.
+    cpu = cpu_baseline(prob, x0, u0, args.cpu_seconds) if (args.full and rank == 0 and world == 1 and not args.no_cpu) else None
 
     # ---- primary: the BASELINE configuration -- one CE batch of G = 1024 samples over all ranks (strong scaling) -------------
     dbg = tuple((kv.split("=")[0], int(kv.split("=")[1])) for kv in args.debug)
@@ -517,42 +539,54 @@ def rank_main(args):
     # same batches first; the timed region is still EXACTLY `steps` batches.
     # (every rank must issue the SAME number of collectives: the number of conditioning blocks is fixed from one block timed on all
     #  ranks and max-reduced, never from a rank-local clock)
-    if args.condition_seconds > 0:
-        t_blk = D.timed(w.step, 16, 0)
-        for _ in range(max(0, min(2000, int(math.ceil(args.condition_seconds / max(t_blk, 1e-6))) - 1))):
-            for _ in range(16):
-                w.step()
+    def condition():
+        if args.condition_seconds > 0:
+            t_blk = D.timed(w.step, 16, 0)
+            for _ in range(max(0, min(2000, int(math.ceil(args.condition_seconds / max(t_blk, 1e-6))) - 1))):
+                for _ in range(16):
+                    w.step()
+            D.sync()
+        for _ in range(W):
+            w.step()
         D.sync()
-    for _ in range(W):
-        w.step()
-    D.sync()
-    # untimed pass with HIP events around every kernel kind: per-kernel breakdown (events perturb the stream, so the timed region
-    # below only brackets the dominant kernel, whose duration feeds the roofline object)
-    w.ctx.profile(True)
-    w.ctx.profile_reset()
-    n_all = max(2, min(K, 5))
-    for _ in range(n_all):
-        w.step()
-    D.sync()
-    prof_all = w.ctx.profile_get()
-    main_kind = next((k for k in ("solve_fused", "solve_block") if prof_all[k]["launches"] > 0), "sweep_eval")
-    fused = main_kind != "sweep_eval"
-    w.ctx.profile(True, kinds=[main_kind])
-    w.ctx.profile_reset()
+
+    condition()
+    # the headline: EXACTLY K steps, no profiling events on the stream
     elapsed = D.timed(w.step, K, 0)
-    prof = w.ctx.profile_get()
-    w.ctx.profile(False)
-    v_h, st_h, it_h, ls_h = w.outputs()
-    w.check_gather()
-    # statistics of the WHOLE batch, from what the timed step's own all-gather left on this rank (not from this rank's shard)
-    _, st_g, it_g, ls_g = w.gathered()
+    # what the last timed step left on this rank: the WHOLE batch's costs and counters from its own all-gather (not this rank's shard)
+    cost_g, st_g, it_g, ls_g = w.gathered()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cost": cost_g, "status": st_g, "iters": it_g, "ls_evals": ls_g})
     feasible = float(np.mean((st_g == 0) | (st_g == 3))) if st_g.size else 1.0
     strong = {"value": G * K / elapsed, "unit": "solves/s", "ms_per_step": elapsed / K * 1e3, "global_batch": G,
               "solves_per_gpu": [shard_bounds(G, world, r)[1] - shard_bounds(G, world, r)[0] for r in range(world)], "spec_eps": E}
+    fused = w.ctx.get_path(max(w.nloc, 1)) in ("fused", "block")
+    if args.full:
+        # untimed pass with HIP events around every kernel kind: per-kernel breakdown; then K steps of their own with events around the
+        # dominant kernel only, whose duration feeds the roofline object (events perturb the stream: the headline above runs without them).
+        # The host work since the headline left the device idle long enough to leave its clocks: conditioned again first.
+        condition()
+        w.ctx.profile(True)
+        w.ctx.profile_reset()
+        n_all = max(2, min(K, 5))
+        for _ in range(n_all):
+            w.step()
+        D.sync()
+        prof_all = w.ctx.profile_get()
+        main_kind = next((k for k in ("solve_fused", "solve_block") if prof_all[k]["launches"] > 0), "sweep_eval")
+        fused = main_kind != "sweep_eval"
+        w.ctx.profile(True, kinds=[main_kind])
+        w.ctx.profile_reset()
+        D.timed(w.step, K, 0)
+        prof = w.ctx.profile_get()
+        w.ctx.profile(False)
+        v_h, st_h, it_h, ls_h = w.outputs()
+        w.check_gather()
+    full_second = args.full and not args.no_second
 
     # ---- weak scaling and BASELINE config 3 (E = 8) in the same run, N > 1 ---------------------------------------------------------
     weak = strong8 = None
-    if world > 1:
+    if world > 1 and args.full:
         ww = Workload(D, prob, x0, u0, draw_theta(G, seed=1000 + rank), G * world, E)
         ew = D.timed(ww.step, K, W)
         weak = {"value": world * G * K / ew, "unit": "solves/s", "ms_per_step": ew / K * 1e3, "global_batch": world * G,
@@ -571,11 +605,11 @@ def rank_main(args):
 
     # ---- single-GPU secondaries ---------------------------------------------------------------------------------------------------
     second = nonlin = unfused = steady = large = None
-    value = w.value_t
+    value = w.value_t if args.full else None
     theta = w.theta
     B = w.nloc
     dev = D.dev
-    if world == 1 and not args.no_second:
+    if world == 1 and full_second:
         # steady state: >= 1 s of back-to-back batches, one HIP event per batch on the handle's stream
         n_ss = int(min(40000, max(200, args.steady_seconds / max(elapsed / K, 1e-5))))
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_ss + 1)]
@@ -596,7 +630,7 @@ def rank_main(args):
                           "is the driver-contract figure over `steps` batches"}
         del evs
 
-    if world == 1 and E != 8 and not args.no_second:
+    if world == 1 and E != 8 and full_second:
         # E = 8 speculative step sizes per sample (BASELINE config 3's "x 8 line-search eps"); identical results, 8x the candidate
         # work on this problem (every first candidate is accepted).
         ctx8 = rat.Context(prob, max_batch=B, spec_eps=8, device=D.local_rank)
@@ -665,7 +699,7 @@ def rank_main(args):
                                   "ms_per_step": e8f / K8 * 1e3, "values_identical_to_primary": bool(torch.equal(v8, value))}
         del ctx8
 
-    if world == 1 and not args.no_second:
+    if world == 1 and full_second:
         # a nonlinear workload (cubic drift kappa x^3 on the same tables): more iterations per solve and theta-dependent
         # iteration counts, i.e. divergent per-sample control flow inside one launch
         probn, x0n, u0n = rat.synthetic_lq_problem(n=12, m=4, N=50, seed=0, kappa=0.05)
@@ -712,7 +746,7 @@ def rank_main(args):
             del ctxl
 
     contract = ce_sec = host_sec = e8_shard = None
-    if world == 1 and fused and E == 1 and not args.no_second:
+    if world == 1 and fused and E == 1 and full_second:
         # SURVEY 8(d) to the letter: "tiles must be materialised per trajectory per step" and every sample runs its own initialize! --
         # the same batch on the same kernel with its tile records put back (rollouts write 3.4 KB per step, sweeps load them) and the
         # shared initial trajectory switched off.  Bit-identical costs; the number the headline's tile-free / shared-init form is an
@@ -728,7 +762,7 @@ def rank_main(args):
                     "traffic": trc, "hbm_real_frac": (trc / (ec / K) / 1e9 / HBM_PEAK_GBS) if trc else None}
         del wc
 
-    if world == 1 and not args.no_second:
+    if world == 1 and full_second:
         # The user-facing calls, host buffers in and out (what the reference's signatures are):
         #  * compute_cost (cross_entropy...jl:173-195): theta[1024] on the host -> cost[1024] on the host;
         #  * one RAT iLQR solve! (:364-415): 5 CE iterations of 1024 samples (draws, elite selection, mu / sigma update) + the final
@@ -772,7 +806,7 @@ def rank_main(args):
                   "solves_per_s_equivalent": (5 * B + 1) / float(np.median(ts)), "theta_opt": float(out_ce[0])}
         del ces, n_solves_ce
 
-    if world == 1 and E != 8 and not args.no_second:
+    if world == 1 and E != 8 and full_second:
         # BASELINE config 3's shard on 8 GPUs: 128 samples x 8 speculative step sizes in one launch
         c8s = rat.Context(prob, max_batch=128, spec_eps=8, device=D.local_rank)
         c8s.set_initial(x0, u0)
@@ -805,7 +839,7 @@ def rank_main(args):
         del c8s
 
     shard_lat = pets_sec = nm_sec = wide_sec = None
-    if world == 1 and not args.no_second:
+    if world == 1 and full_second:
         # What each rank of an N-GPU run of the BASELINE metric executes: ONE launch over 1024 / N samples.  A strong-scaling shard costs
         # one solve's latency whatever its size, so these driver-timed figures are the scaling curve's proxy when no multi-GPU node is
         # available: value(N) ~ 1024 / (shard_latency_ms(1024 / N) + all-gather).
@@ -950,7 +984,7 @@ def rank_main(args):
         wide_sec["value"] = wide_sec["runs"]["16x4"]["solves_per_s"]
         wide_sec["unit"] = "solves/s (n = 16, m = 4)"
 
-    if fused and world == 1 and not args.no_second:
+    if fused and world == 1 and full_second:
         # per-phase breakdown of the same batch on the round-based path (one launch per phase; what the fused kernel replaces)
         ctxu = rat.Context(prob, max_batch=B, spec_eps=E, device=D.local_rank)
         ctxu.set_path("rounds")
@@ -1012,9 +1046,10 @@ def rank_main(args):
                 "path": w.ctx.get_path(max(w.nloc, 1)),
             },
             "strong": strong,
-            "roofline": roofline_of(w, prof[main_kind], main_kind, it_h, ls_h),
-            "kernel_ms_per_step": {k: v["ms"] / n_all for k, v in prof_all.items()},
         }
+        if args.full:
+            out["roofline"] = roofline_of(w, prof[main_kind], main_kind, it_h, ls_h)
+            out["kernel_ms_per_step"] = {k: v["ms"] / n_all for k, v in prof_all.items()}
         # one scalar per secondary at the top level (a parser that keeps only scalars still sees every leg)
         flat = {
             "contract_solves_per_s": contract["value"] if contract else None,
@@ -1041,25 +1076,26 @@ def rank_main(args):
             "batch8192_solves_per_s": large["8192"]["value"] if large else None,
         }
         out.update({k: v for k, v in flat.items() if v is not None})
-        # ... and inside `roofline`, which the driver's record keeps whole: the SURVEY 8(d)-to-the-letter contract figure
-        # with its fraction, the strong-scaling shard latencies and the user-facing calls; `frac_of_bound` = the fraction of the roofline
-        # `bound` names (fp64), beside `frac` = SURVEY 8(d)'s algorithmic-bytes figure against the HBM peak
-        rf = out["roofline"]
-        rf["frac_of_bound"] = rf.get("fp64_frac") if rf.get("bound") == "fp64" else rf.get("frac")
-        rf["frac_is"] = "SURVEY 8(d) contract: algorithmic bytes / launch time / HBM peak (NOT bytes moved); the binding roofline's fraction is frac_of_bound"
-        if contract:
-            rf["contract_frac"] = contract["frac_of_hbm_peak_on_algorithmic_bytes"]
-            rf["contract_hbm_real_frac"] = contract["hbm_real_frac"]
-        rf.update({k: v for k, v in flat.items() if v is not None})
-        # key ORDER: the driver's record keeps the first 24 keys of `roofline` -- the contract's six, then the scalars a
-        # reader of BENCH_rNN.json needs; the prose (`bound_is`, `traffic_source`, `frac_is`, `kernel`) goes last
-        front = ("bound", "achieved", "peak", "unit", "frac", "traffic", "frac_of_bound", "contract_solves_per_s", "contract_frac",
-                 "shard128_ms", "shard256_ms", "shard512_ms", "ce_solve_ms", "e8_solves_per_s", "e8_shard128_ms", "nm_ms_per_solve",
-                 "fp64_frac", "issue_frac", "hbm_real_frac", "avg_launch_ms", "batch4096_solves_per_s", "wide_32x32_solves_per_s",
-                 "pets_solve_ms", "contract_hbm_real_frac")
-        prose = ("kernel", "bound_is", "frac_is", "traffic_source")
-        out["roofline"] = rf = {**{k: rf[k] for k in front if k in rf}, **{k: v for k, v in rf.items() if k not in front and k not in prose},
-                                **{k: rf[k] for k in prose if k in rf}}
+        if args.full:
+            # ... and inside `roofline`, which the driver's record keeps whole: the SURVEY 8(d)-to-the-letter contract figure
+            # with its fraction, the strong-scaling shard latencies and the user-facing calls; `frac_of_bound` = the fraction of the roofline
+            # `bound` names (fp64), beside `frac` = SURVEY 8(d)'s algorithmic-bytes figure against the HBM peak
+            rf = out["roofline"]
+            rf["frac_of_bound"] = rf.get("fp64_frac") if rf.get("bound") == "fp64" else rf.get("frac")
+            rf["frac_is"] = "SURVEY 8(d) contract: algorithmic bytes / launch time / HBM peak (NOT bytes moved); the binding roofline's fraction is frac_of_bound"
+            if contract:
+                rf["contract_frac"] = contract["frac_of_hbm_peak_on_algorithmic_bytes"]
+                rf["contract_hbm_real_frac"] = contract["hbm_real_frac"]
+            rf.update({k: v for k, v in flat.items() if v is not None})
+            # key ORDER: the driver's record keeps the first 24 keys of `roofline` -- the contract's six, then the scalars a
+            # reader of BENCH_rNN.json needs; the prose (`bound_is`, `traffic_source`, `frac_is`, `kernel`) goes last
+            front = ("bound", "achieved", "peak", "unit", "frac", "traffic", "frac_of_bound", "contract_solves_per_s", "contract_frac",
+                     "shard128_ms", "shard256_ms", "shard512_ms", "ce_solve_ms", "e8_solves_per_s", "e8_shard128_ms", "nm_ms_per_solve",
+                     "fp64_frac", "issue_frac", "hbm_real_frac", "avg_launch_ms", "batch4096_solves_per_s", "wide_32x32_solves_per_s",
+                     "pets_solve_ms", "contract_hbm_real_frac")
+            prose = ("kernel", "bound_is", "frac_is", "traffic_source")
+            out["roofline"] = rf = {**{k: rf[k] for k in front if k in rf}, **{k: v for k, v in rf.items() if k not in front and k not in prose},
+                                    **{k: rf[k] for k in prose if k in rf}}
         if weak is not None:
             out["weak"] = weak
         if strong8 is not None:
@@ -1093,8 +1129,12 @@ def parse(argv):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024, help="the CE batch (global: sharded over the ranks)")
     ap.add_argument("--spec-eps", type=int, default=1, help="E speculative line-search step sizes per sample")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-second", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: CPU baseline, per-kernel breakdown, roofline, secondaries, weak scaling (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-sample cost / status / iters / ls_evals of the global batch as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-second", action="store_true", help="with --full: skip the secondary measurements")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--debug", action="append", default=[], metavar="KEY=VALUE",
                     help="execution switch of the primary workload's handle (rat_debug_set), e.g. --debug materialize=1 --debug init_share=0")
@@ -1108,6 +1148,8 @@ def main(argv=None):
     args = parse(argv)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args, argv))             # (nothing has touched the GPU in this process)
     rank_main(args)

@@ -10,6 +10,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 spec = importlib.util.spec_from_file_location("bench", BENCH)
@@ -98,3 +100,29 @@ def test_traffic_is_null_when_the_kernels_changed(tmp_path, monkeypatch):
     (src / "kernels.hip").write_text("// edited")
     val, why = bench.traffic_for("solve_fused_E1_B1024")
     assert val is None and sha in why
+
+
+def test_dry_run_dumps_the_gathered_costs(tmp_path):
+    """--dump-outputs writes what the last timed step left for the global batch (here the stand-in's costs, gathered over two ranks)."""
+    d = _json(_run(["--gpus", "2", "--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path / "out")],
+                   {"RATILQR_BENCH_DRY": "1", "RATILQR_BENCH_BACKEND": "gloo"}))
+    assert d["steps"] == 2
+    cost = np.load(tmp_path / "out" / "cost.npy")
+    assert cost.dtype == np.float64 and np.array_equal(cost, 0.1 / bench.draw_theta(1024, seed=1000))
+
+
+def test_dump_outputs_samples_beyond_the_cap(tmp_path):
+    a = {"cost": np.arange(1000, dtype=np.float64), "status": np.zeros(1000, dtype=np.int32)}
+    bench.dump_outputs(str(tmp_path / "small"), a)
+    assert sorted(os.listdir(tmp_path / "small")) == ["cost.npy", "status.npy"]
+    assert np.load(tmp_path / "small" / "status.npy").dtype == np.float64
+    bench.dump_outputs(str(tmp_path / "a"), a, max_bytes=4800)
+    bench.dump_outputs(str(tmp_path / "b"), a, max_bytes=4800)
+    idx = np.load(tmp_path / "a" / "index.npy")
+    assert idx.size == 200 and np.all(np.diff(idx) > 0) and sum(os.path.getsize(p) - 128 for p in (tmp_path / "a").iterdir()) <= 4800
+    assert np.array_equal(np.load(tmp_path / "a" / "cost.npy"), idx) and np.array_equal(idx, np.load(tmp_path / "b" / "index.npy"))
+
+
+def test_zero_steps_are_refused():
+    out = _run(["--gpus", "1", "--steps", "0"], {"RATILQR_BENCH_DRY": "1"})
+    assert out.returncode != 0 and "--steps" in out.stderr and "{" not in out.stdout

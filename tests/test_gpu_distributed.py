@@ -121,7 +121,8 @@ def _run_bench(nproc, extra_env, *args, launcher=True):
 def test_bench_collective_path_over_rccl_on_the_solver_stream():
     """The N > 1 step of bench.py -- batch enqueued on the handle's HIP stream, RCCL all-gather ordered behind it on that stream, next
     batch ordered behind the gather -- run with a one-rank RCCL communicator (test hook), costs checked by bench.py itself."""
-    d = _run_bench(1, {"RATILQR_BENCH_FORCE_DIST": "1"}, "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu", "--no-second", "--batch", "512")
+    d = _run_bench(1, {"RATILQR_BENCH_FORCE_DIST": "1"}, "--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--no-cpu", "--no-second",
+                   "--batch", "512")
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["value"] > 0 and d["roofline"]["launches"] == 4
     assert d["rccl_ranks"] == 1 and d["collective_backend"].startswith("rccl")
 
@@ -132,7 +133,7 @@ def test_bench_self_launches_two_ranks():
     rank 0 prints the JSON line with `weak` and `strong_spec_eps8` beside it.  Two ranks share this box's single GPU and the collective
     is host-staged (test hooks of bench.py; on a multi-GPU node the same flow runs one rank per GPU over RCCL)."""
     d = _run_bench(2, {"RATILQR_BENCH_BACKEND": "gloo", "RATILQR_BENCH_ONE_DEVICE": "1"}, "--gpus", "2", "--steps", "3", "--warmup", "1",
-                   "--no-cpu", "--batch", "256", launcher=False)
+                   "--full", "--no-cpu", "--batch", "256", launcher=False)
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["self_launched"] is True and d["scaling"] == "strong" and d["steps"] == 3
     assert d["config"]["global_batch"] == 256 and d["strong"]["solves_per_gpu"] == [128, 128]
     assert d["value"] == d["strong"]["value"] > 0 and abs(d["value"] - 256 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
@@ -145,3 +146,25 @@ def test_bench_runs_as_two_ranks_under_the_drivers_launcher():
     d = _run_bench(2, {"RATILQR_BENCH_BACKEND": "gloo", "RATILQR_BENCH_ONE_DEVICE": "1"}, "--gpus", "2", "--steps", "2", "--warmup", "1",
                    "--no-cpu", "--no-second", "--batch", "64")
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["self_launched"] is False and d["strong"]["solves_per_gpu"] == [32, 32]
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run: the headline alone (no roofline, CPU baseline or secondary in the line), exactly --steps timed
+    steps, and with --dump-outputs the last timed step's per-sample cost and counters of the whole batch, as float64 .npy files that
+    equal a direct solve of the same seeded batch."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    d = _run_bench(1, {}, "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path), launcher=False)
+    assert d["steps"] == 3 and d["value"] > 0 and abs(d["value"] - 1024 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    assert not {"roofline", "kernel_ms_per_step", "cpu_baseline", "steady_state", "secondary_contract"} & set(d)
+    out = {k: np.load(tmp_path / f"{k}.npy") for k in ("cost", "status", "iters", "ls_evals")}
+    assert all(v.dtype == np.float64 and v.shape == (1024,) for v in out.values())
+    theta = bench.draw_theta(1024, seed=1000)
+    prob, x0, u0 = rat.synthetic_lq_problem(n=12, m=4, N=50, seed=0)
+    val, st, it, ls = rat.Context(prob, max_batch=1024, device=0).solve_batch(x0, u0, theta)
+    assert np.array_equal(out["status"], st) and np.array_equal(out["iters"], it) and np.array_equal(out["ls_evals"], ls)
+    assert np.allclose(out["cost"], val + 0.1 / theta, rtol=1e-12, atol=0.0)
+    assert d["config"]["feasible_fraction"] == float(np.mean((st == 0) | (st == 3)))

@@ -7,7 +7,7 @@ timeout 2000 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo 
 tail -3 $O/pytest_gpu.log; t1=$(date +%s); echo "pytest wall $((t1-t0)) s"
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -4 $O/smoke.log
 t2=$(date +%s)
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 t3=$(date +%s); echo "bench wall $((t3-t2)) s"
 python3 - <<PY
 import json

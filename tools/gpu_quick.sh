@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r03; mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests/test_gpu_block.py tests/test_gpu_parity.py tests/test_gpu_multi.py tests/test_gpu_ce.py -m gpu -x -q > $O/pytest_quick.log 2>&1; echo "pytest rc=$?" >> $O/pytest_quick.log
 tail -3 $O/pytest_quick.log
-B="--steps 20 --warmup 5 --no-cpu --no-second"
+B="--steps 20 --warmup 5 --full --no-cpu --no-second"
 run() { name=$1; shift; env "$@" > $O/bench_$name.json 2> $O/bench_$name.err
 python3 - <<PY
 import json

@@ -8,7 +8,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r02/prof; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 cd $R
-B="--steps 10 --warmup 2 --no-cpu --no-second --condition-seconds 0.05"
+B="--steps 10 --warmup 2 --full --no-cpu --no-second --condition-seconds 0.05"
 run() {  # name, bench args
   local name=$1; shift
   timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt_$name -o runc --output-format csv -- python3 bench.py $B "$@" > $O/bench_${name}_under_rocprof.log 2>&1

@@ -53,7 +53,7 @@ def by_kind(per, counter, how=max):
 traffic = {"kernels_sha": bench.kernel_source_hash(), "round": RND, "sq": {}}
 md = [f"# {RND} rocprofv3 summaries (tools/profile_{RND}.sh; one MI355X, ROCm 7.2)\n",
       "Commands: `rocprofv3 --kernel-trace --stats` / `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` / two `--pmc SQ_*` passes (each its own run, no trace",
-      "domains with counters) around `python3 bench.py --steps 10 --warmup 2 --no-cpu --no-second [--batch B] [--spec-eps E]`.\n",
+      "domains with counters) around `python3 bench.py --steps 10 --warmup 2 --full --no-cpu --no-second [--batch B] [--spec-eps E]`.\n",
       "## Kernel duration (kernel-trace stats) and HBM traffic per launch (2 x FETCH_SIZE + WRITE_SIZE: gfx950 tallies 128-B read requests at 64 B)\n",
       "| configuration | kernel | launches | avg duration (us) | HBM traffic per launch (MB) | algorithmic bytes per launch (MB) |", "|---|---|---|---|---|---|"]
 a = bench.algo_bytes()

@@ -13,10 +13,10 @@ STEPS=${1:-20}
 OUT=${R}/gpurun_out/scale_check; mkdir -p "$OUT"
 NDEV=$(python3 -c 'import torch; print(torch.cuda.device_count())')
 echo "visible devices: $NDEV"
-python3 bench.py --gpus 1 --steps "$STEPS" --warmup 3 --no-cpu > "$OUT/n1.json" 2> "$OUT/n1.err" || { echo "N=1 failed"; tail -5 "$OUT/n1.err"; exit 1; }
+python3 bench.py --gpus 1 --steps "$STEPS" --warmup 3 --full --no-cpu > "$OUT/n1.json" 2> "$OUT/n1.err" || { echo "N=1 failed"; tail -5 "$OUT/n1.err"; exit 1; }
 for N in 1 2 4 8; do
   [ "$N" -gt "$NDEV" ] && break
-  python3 bench.py --gpus "$N" --steps "$STEPS" --warmup 3 --no-cpu --no-second > "$OUT/s$N.json" 2> "$OUT/s$N.err" || { echo "N=$N failed"; tail -5 "$OUT/s$N.err"; exit 1; }
+  python3 bench.py --gpus "$N" --steps "$STEPS" --warmup 3 --full --no-cpu --no-second > "$OUT/s$N.json" 2> "$OUT/s$N.err" || { echo "N=$N failed"; tail -5 "$OUT/s$N.err"; exit 1; }
 done
 python3 - "$OUT" "$NDEV" <<'PY'
 import json, sys, os
