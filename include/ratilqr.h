@@ -19,7 +19,7 @@
  *   - call from one host thread per handle; a handle owns one HIP device and one stream; a rat_multi owns one handle per
  *     device and is driven from one host thread as well (no callbacks, no thread-local state of the caller: @threadcall-safe);
  *   - user closures f/c/h/W cannot cross the ABI: problems are instances of compiled-in model
- *     families (rat_problem_desc.model).
+ *     families (rat_problem_desc.model), or HIP source the library compiles at run time (rat_problem_set_source).
  */
 #ifndef RATILQR_H
 #define RATILQR_H
@@ -113,6 +113,39 @@ rat_rc rat_set_ileqg_opts(rat_handle h, const rat_ileqg_opts *opts);
  * dimensions from the arrays, ileqg.jl:229) and run every entry point in general-size kernels; the power-law family beyond n = m = 4
  * and any larger problem return RAT_ERR_UNSUPPORTED. */
 rat_rc rat_problem_set(rat_handle h, const rat_problem_desc *desc);
+
+/* ---- source models: f, c, h written by the user, compiled at run time --------------------------
+ * FiniteHorizonRiskSensitiveOptimalControlProblem(f, c, h, W, N) with arbitrary f, c, h (optimal_control_problems.jl:67-73),
+ * differentiated by forward-mode AD as the reference does with ForwardDiff (ileqg.jl:265-273).  The source is plain HIP device code
+ * that defines, for RAT_N = n and RAT_M = m (compile-time constants) and the user's parameters p (kept on the device):
+ *
+ *   template <class T> __device__ void rat_user_f(const T *x, const T *u, T *xn, const double *p);   x_{k+1} = f(x_k, u_k)
+ *   template <class T> __device__ T    rat_user_c(int k, const T *x, const T *u, const double *p);   c(k, x, u), k = 0 .. N-1
+ *   template <class T> __device__ T    rat_user_h(const T *x, const double *p);                      h(x_N)
+ *
+ * T is double in rollouts, or a forward-mode AD type (rat_ad.h: a dual number for the Jacobian columns of f, a hyper-dual number per
+ * upper-triangle pair of z = (x, u) for c and its derivatives; the Hessian is mirrored from the upper triangle like Symmetric(...)).
+ * Both support + - * / with double, comparisons on the value, and sin cos tan exp log sqrt pow(T,double) pow(T,T) tanh atan atan2 fabs
+ * fmin fmax.  Optionally (the analogue of f_returns_jacobian, ileqg.jl:302-311) the source defines RAT_USER_F_JACOBIAN and
+ *
+ *   __device__ void rat_user_f_jacobian(const double *x, const double *u, double *xn, double *A, double *B, const double *p);
+ *
+ * with A n x n and B n x m column-major: exact Jacobians instead of AD for f.  A NaN in x_{t+1} or in a cost whose inputs had none is
+ * the reference's DomainError (RAT_ST_DOMAIN, value Inf).  No fast-math.
+ * Limits: n <= 12, m <= 4 (else RAT_ERR_UNSUPPORTED); batches run on the round-based path (rat_set_path FUSED / BLOCK return
+ * RAT_ERR_UNSUPPORTED); rat_rollout_noisy, PETS and rat_multi are not available for source models. */
+#define RAT_MODEL_SOURCE    3
+
+/* Compile `source` (NUL-terminated) for the handle's device and make it the handle's problem.  W: n*n column-major, N entries if W_tv
+ * (exactly as rat_problem_set takes it).  params: n_params doubles (may be 0 / NULL).  A compile error returns RAT_ERR_ARG with the
+ * compiler's log in rat_last_error(); a failed call leaves the previous problem in place.  Code objects are cached per process by
+ * (source, n, m, device architecture). */
+rat_rc rat_problem_set_source(rat_handle h, const char *source, int32_t n, int32_t m, int32_t N,
+                              const double *W, int32_t W_tv, const double *params, int64_t n_params);
+/* New values of the source problem's parameters (the same count; no recompilation). */
+rat_rc rat_problem_set_params(rat_handle h, const double *params, int64_t n_params);
+/* Compile only, for gfx950 (no device needed): RAT_OK, RAT_ERR_ARG with the log in rat_last_error(), or RAT_ERR_UNSUPPORTED. */
+rat_rc rat_source_check(const char *source, int32_t n, int32_t m);
 
 /* ---- the hot path ----------------------------------------------------------------------------- */
 
@@ -472,6 +505,8 @@ int32_t rat_get_path(rat_handle h, int64_t B);
  *                            sequential sweep to rounding (not bit for bit); values above 4 mean 4 (one wave per SIMD)             (0)
  *   psw_hop, psw_hop_e, psw_comp   its cost model in hundredths of an ordinary step -- one hop of a gain sweep, one hop of an evaluation, one
  *                            element step: where the segment cuts go                                                      (120, 140, 125)
+ *   src_tpw         16 / 32 / 64   source models: trajectories per wavefront of the rollout kernel (16: measured faster at 1024
+ *                            trajectories, profiles/source_model.md)                                                        (16)
  *   wdiag           0 / 1    diagonal time-invariant W: inv(W) folded into M^-1's operand (takes effect at the next rat_problem_set) (1) */
 rat_rc  rat_debug_set(rat_handle h, const char *key, int64_t value);
 rat_rc  rat_debug_get(rat_handle h, const char *key, int64_t *value);      /* the EFFECTIVE value on this handle */

@@ -49,7 +49,18 @@ struct LQGenerativeProblem <: OptimalControlProblem
     tw2::Float64; tmean2::Vector{Float64}; tchol2::Matrix{Float64}
 end
 
+"""Source model (RAT_MODEL_SOURCE): f, c, h written as HIP device code (rat_user_f / rat_user_c / rat_user_h, include/ratilqr.h),
+compiled by the library at run time; `params` are the doubles those functions read.  W: a matrix or an n x n x N array (time last)."""
+struct DeviceSourceProblem <: DeviceRiskSensitiveProblem
+    source::String
+    n::Int64; m::Int64; N::Int64
+    W::Array{Float64}
+    params::Vector{Float64}
+end
+DeviceSourceProblem(source, n, m, N, W; params=Float64[]) = DeviceSourceProblem(String(source), n, m, N, W, Vector{Float64}(params))
+
 dims(p::LQRiskSensitiveProblem) = (size(p.B, 1), size(p.B, 2), p.N)
+dims(p::DeviceSourceProblem) = (p.n, p.m, p.N)
 dims(p::PowerLawRiskSensitiveProblem) = (p.n, p.n, p.N)
 
 # ---- plain-data mirrors of the C structs (field order and widths are checked against include/ratilqr.h) -----------------------------
@@ -201,6 +212,14 @@ function problem_set!(h::MultiHandle, p::DeviceRiskSensitiveProblem)
     end
     h.problem = p
 end
+function problem_set!(h::Handle, p::DeviceSourceProblem)
+    check(ccall((:rat_problem_set_source, LIB), Int32, (Ptr{Cvoid}, Cstring, Int32, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int64),
+                h.ptr, p.source, p.n, p.m, p.N, p.W, ndims(p.W) == 3, p.params, length(p.params)))
+    h.problem = p
+end
+problem_set!(h::MultiHandle, p::DeviceSourceProblem) = throw(ArgumentError("rat_multi does not take source models"))
+"Compile a source model for gfx950 without a device (throws with the compiler's log)."
+source_check(source::AbstractString, n::Integer, m::Integer) = check(ccall((:rat_source_check, LIB), Int32, (Cstring, Int32, Int32), source, n, m))
 "Re-bind the handle when it is called with a problem other than the one its device tables were built from."
 bind!(h::Union{Handle,MultiHandle}, p) = (h.problem === p || problem_set!(h, p); h)
 
@@ -237,6 +256,13 @@ function ILEQGSolver(problem::DeviceRiskSensitiveProblem; μ_min=1e-6, Δ_0=2.0,
                 Vector{Float64}[], Vector{Float64}[], Matrix{Float64}[], Inf, 0, Inf, Tuple{Float64,Float64}[])
 end
 
+"""New values of a source problem's parameters on this solver's handle (same count, no recompilation).  `problem.params` is left as it
+is: other handles keep what they uploaded from it, and this handle uploads it again if it is re-bound to the problem."""
+function set_params!(s::ILEQGSolver, problem::DeviceSourceProblem, params::Vector{Float64})
+    h = bind!(s.h, problem)
+    check(ccall((:rat_problem_set_params, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64), h.ptr, params, length(params)))
+    s
+end
 "simulate_dynamics(problem, x_0, u_array) -- ileqg.jl:18-38"
 function simulate_dynamics(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_0::Vector{Float64}, u_array::Vector{Vector{Float64}})
     h = bind!(s.h, problem); n, m, N = dims(problem)
@@ -1098,7 +1124,7 @@ function solve!(s::NelderMeadBilevelOptimizationSolver, problem, x_0::Vector{Flo
     R.solve!(ref, problem, x_0, u_array; kl_bound=kl_bound, verbose=verbose)
 end
 
-export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem,
+export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check,
        simulate_dynamics, simulate_dynamics_noisy, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,

@@ -8,6 +8,7 @@ from .problems import (  # noqa: F401
     FiniteHorizonRiskSensitiveOptimalControlProblem,
     LQRiskSensitiveProblem,
     PowerLawRiskSensitiveProblem,
+    DeviceSourceProblem,
     synthetic_lq_problem,
 )
 from ._native import RatError, SO_PATH  # noqa: F401,E402

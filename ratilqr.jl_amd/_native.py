@@ -87,6 +87,7 @@ EXPORTS = [
     "rat_multi_ce_solve", "rat_multi_pets_problem_set", "rat_multi_pets_compute_cost",
     "rat_multi_ce_compute_cost_ex", "rat_multi_ileqg_solve_batch", "rat_multi_is_logical", "rat_set_path", "rat_get_path", "rat_ce_compute_cost_enqueue_ex",
     "rat_debug_set", "rat_debug_get", "rat_ce_update_dev",
+    "rat_problem_set_source", "rat_problem_set_params", "rat_source_check",
 ]
 
 _lib = None
@@ -117,6 +118,9 @@ def lib():
         _lib.rat_get_path.restype = C.c_int32
         _lib.rat_debug_set.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         _lib.rat_debug_get.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
+        _lib.rat_problem_set_source.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_int64]
+        _lib.rat_problem_set_params.argtypes = [C.c_void_p, _dp, C.c_int64]
+        _lib.rat_source_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32]
     return _lib
 
 
@@ -144,6 +148,24 @@ def cm3(a):
 
 def from_cm3(buf, T, rows, cols):
     return np.asarray(buf, dtype=np.float64).reshape(T, cols, rows).transpose(0, 2, 1).copy()
+
+
+def set_source(h, prob):
+    """rat_problem_set_source for a DeviceSourceProblem; returns the arrays the call read (kept alive by the caller)."""
+    W, p = f64(_wbuf(prob)), f64(prob.params)
+    check(lib().rat_problem_set_source(h, prob.source.encode(), int(prob.n), int(prob.m), int(prob.N), P(W), int(bool(prob.W_tv)),
+                                       P(p) if p.size else None, C.c_int64(p.size)))
+    return {"W": W, "params": p}
+
+
+def _wbuf(prob):
+    from .problems import _colmajor
+    return _colmajor(prob.Wtab)
+
+
+def source_check(source, n, m):
+    """rat_source_check: compile only (gfx950, no device needed); raises RatError with the compiler's log."""
+    check(lib().rat_source_check(str(source).encode(), int(n), int(m)))
 
 
 def make_desc(prob):

@@ -22,6 +22,8 @@
 #include "layout.h"
 #include "wide.h"
 #include "ce_device.h"
+#include "source_args.h"
+#include "source_model.h"
 
 static thread_local std::string g_err;
 static rat_rc fail(rat_rc rc, const std::string &msg) { g_err = msg; return rc; }
@@ -160,6 +162,11 @@ struct rat_handle_s {
     CeDev *d_ce = nullptr, *h_ce = nullptr;          // device record, pinned host mirror
     double *d_cez = nullptr, *h_cez = nullptr; size_t cap_cez = 0;      // standard normals: pinned host buffer and its device address (read in place)
     double *d_ce_theta = nullptr, *d_ce_cost = nullptr;
+    // runtime-compiled model family (RAT_MODEL_SOURCE): the handle's module of the two model kernels (source_kernels.h), its parameters
+    hipModule_t src_mod = nullptr;
+    hipFunction_t src_roll = nullptr, src_lin = nullptr;
+    double *d_src_p = nullptr; int64_t src_np = 0;      // (d_src_p lives in pb_allocs)
+    int src_tpw = 16;                // switch src_tpw: trajectories per wavefront of the rollout kernel (16 or 64; measured)
 };
 
 extern "C" int32_t rat_version(void) { return RAT_VERSION; }
@@ -232,6 +239,7 @@ static const DebugSwitch debug_switches[] = {
      [](rat_handle h) -> int64_t { int c = 0; if (h->d_duo_count) { (void)hipStreamSynchronize(h->stream); (void)hipMemcpy(&c, h->d_duo_count, sizeof(int), hipMemcpyDeviceToHost); } return c; }},
     {"psw_acl", [](rat_handle h, int64_t v) { h->psw_acl = (v != 0); }, [](rat_handle h) -> int64_t { return h->psw_acl; }},
     {"psw_comp", [](rat_handle h, int64_t v) { h->psw_comp = (int)std::max<int64_t>(100, v); }, [](rat_handle h) -> int64_t { return h->psw_comp; }},
+    {"src_tpw", [](rat_handle h, int64_t v) { h->src_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_tpw; }},
 };
 // what the requests amount to on this handle (speculation width, forced pairings)
 static void finish_switches(rat_handle h) {
@@ -330,6 +338,7 @@ extern "C" void rat_destroy(rat_handle h) {
     if (h->h_pstage) (void)hipHostFree(h->h_pstage);
     if (h->h_sol) (void)hipHostFree(h->h_sol);
     if (h->d_census) (void)hipFree(h->d_census);
+    if (h->src_mod) (void)hipModuleUnload(h->src_mod);
     for (void *q : {(void *)h->d_ce, (void *)h->d_ce_theta, (void *)h->d_ce_cost}) if (q) (void)hipFree(q);      // (d_cez aliases the pinned h_cez)
     if (h->h_ce) (void)hipHostFree(h->h_ce);
     if (h->h_cez) (void)hipHostFree(h->h_cez);
@@ -396,6 +405,8 @@ static bool host_inv(int n, const double *A, double *Ainv) {
     return true;
 }
 
+// one tile bundle per sample (the single-launch E = 1 kernels) or one per slot (round-based path; always for source problems)
+static bool want_alias(const rat_handle h) { return h->fused && h->pb.model != RAT_MODEL_SOURCE; }
 static rat_rc alloc_state(rat_handle h) {
     free_list(h->st_allocs);
     StateDev &st = h->st;
@@ -406,7 +417,7 @@ static rat_rc alloc_state(rat_handle h) {
     st.x_stride = (long)(N + 1) * XSTR;
     st.u_stride = (long)N * USTR;
     const size_t slots = (size_t)B * (E + 1);
-    st.tile_alias = h->fused ? 1 : 0;          // (layout.h: candidates are linearised over the dead tiles of their nominal trajectory)
+    st.tile_alias = want_alias(h) ? 1 : 0;     // (layout.h: candidates are linearised over the dead tiles of their nominal trajectory)
     rat_rc rc;
 #define AL(ptr, cnt) if ((rc = dev_alloc(h->st_allocs, &(ptr), (cnt)))) return rc
     AL(st.tiles, (st.tile_alias ? (size_t)B : slots) * st.tile_stride);
@@ -564,6 +575,52 @@ static rat_rc problem_set_wide(rat_handle h, const rat_problem_desc *d) {
     return RAT_OK;
 }
 
+// the W(k) tables of a problem (rat_problem_set, rat_problem_set_source): inverses, pivots, log-determinants and the diagonal form
+struct WTables { std::vector<double> Winv, Wp, epiv, ldw, Wdg; };
+static rat_rc build_w_tables(rat_handle h, ProblemDev &pb, const double *Wsrc, int n, int N, const char *who, WTables &wt) {
+    const int Nw = pb.W_tv ? N : 1;
+    std::vector<double> &Winv = wt.Winv, &Wp = wt.Wp, &epiv = wt.epiv, &ldw = wt.ldw, &Wdg = wt.Wdg;
+    Winv.assign((size_t)Nw * 192, 0.0); Wp.assign((size_t)Nw * 192, 0.0); epiv.assign((size_t)Nw * 16, 1.0); ldw.assign(Nw, 0.0);
+    for (int k = 0; k < Nw; ++k) {
+        const double *W = Wsrc + (size_t)k * n * n;
+        std::vector<double> wi(n * n);
+        if (!host_inv(n, W, wi.data())) return fail(RAT_ERR_ARG, std::string(who) + ": W(k) is singular (inv(W) would throw, ileqg.jl:365)");
+        double *wo = &Winv[(size_t)k * 192], *wq = &Wp[(size_t)k * 192];
+        for (int i = 0; i < RAT_NP; ++i)
+            for (int jj = 0; jj < RAT_NP; ++jj) {
+                if (i < n && jj < n) {
+                    wo[i * 16 + jj] = (i <= jj) ? wi[i + n * jj] : wi[jj + n * i];   // Symmetric(inv(W) - ...) reads the upper triangle
+                    wq[i * 16 + jj] = W[i + n * jj];
+                } else if (i == jj) wo[i * 16 + jj] = 1.0;
+            }
+        // elimination pivots e_k of the padded inv(W): logdet(W M) = sum log(d_k / e_k)
+        double a[12][12];
+        for (int i = 0; i < 12; ++i) for (int jj = 0; jj < 12; ++jj) a[i][jj] = wo[i * 16 + jj];
+        double pivs[12];
+        for (int p = 0; p < 12; ++p) {
+            const double piv = a[p][p];
+            pivs[p] = piv;
+            ldw[k] -= std::log(piv);
+            for (int i = p + 1; i < 12; ++i) {
+                const double f = a[i][p] / piv;
+                for (int jj = p; jj < 12; ++jj) a[i][jj] -= f * a[p][jj];
+            }
+        }
+        // the kernels eliminate 2x2 blocks {p, p+1}: lane p (even) multiplies det(P) by 1 / (e_p e_{p+1})
+        for (int p = 0; p < 12; p += 2) { epiv[(size_t)k * 16 + p] = 1.0 / (pivs[p] * pivs[p + 1]); epiv[(size_t)k * 16 + p + 1] = 1.0; }
+    }
+    // time-invariant diagonal W: the sweeps fold inv(W) into the inverse of M (ProblemDev.W_diag)
+    Wdg.assign(16, 1.0);
+    pb.W_diag = pb.W_tv ? 0 : 1;
+    if (!pb.W_tv) {
+        for (int i = 0; i < n; ++i)
+            for (int jj = 0; jj < n; ++jj) if (i != jj && Wsrc[i + n * jj] != 0.0) pb.W_diag = 0;
+        for (int i = 0; i < n; ++i) Wdg[i] = Winv[i * 16 + i];
+    }
+    if (!h->wdiag) pb.W_diag = 0;       // debug switch wdiag = 0: the general-W arithmetic (A/B measurements, bit-identity tests)
+    return RAT_OK;
+}
+
 extern "C" rat_rc rat_problem_set(rat_handle h, const rat_problem_desc *d) {
     if (!h || !d) return fail(RAT_ERR_ARG, "null");
     HIPCHK(hipSetDevice(h->device));
@@ -587,6 +644,7 @@ extern "C" rat_rc rat_problem_set(rat_handle h, const rat_problem_desc *d) {
     pb.q0f = d->q0f; pb.kappa = d->kappa;
     pb.pl_a = d->pl_a; pb.pl_b = d->pl_b; pb.pl_p = d->pl_p; pb.pl_pu = d->pl_pu; pb.pl_cx = d->pl_cx; pb.pl_cu = d->pl_cu; pb.pl_h = d->pl_h;
     const int Nc = pb.cost_tv ? N : 1, Nw = pb.W_tv ? N : 1;
+    rat_rc rc;
     std::vector<double> Zt(192, 0.0), Ctab((size_t)Nc * 256, 0.0), lin((size_t)Nc * 16, 0.0), q0(Nc, 0.0), Qf(144, 0.0), qvf(16, 0.0);
     if (d->model == RAT_MODEL_LQ) {
         if (!d->A || !d->B || !d->Q || !d->R || !d->P || !d->qv || !d->rv || !d->q0 || !d->Qf || !d->qvf)
@@ -614,61 +672,135 @@ extern "C" rat_rc rat_problem_set(rat_handle h, const rat_problem_desc *d) {
             qvf[i] = d->qvf[i];
         }
     }
-    std::vector<double> Winv((size_t)Nw * 192, 0.0), Wp((size_t)Nw * 192, 0.0), epiv((size_t)Nw * 16, 1.0), ldw(Nw, 0.0);
+    WTables wt;
+    if ((rc = build_w_tables(h, pb, d->W, n, N, "rat_problem_set", wt))) return rc;
     h->hW.assign(d->W, d->W + (size_t)Nw * n * n);
     h->W_tv = pb.W_tv;
-    for (int k = 0; k < Nw; ++k) {
-        const double *W = d->W + (size_t)k * n * n;
-        std::vector<double> wi(n * n);
-        if (!host_inv(n, W, wi.data())) return fail(RAT_ERR_ARG, "rat_problem_set: W(k) is singular (inv(W) would throw, ileqg.jl:365)");
-        double *wo = &Winv[(size_t)k * 192], *wq = &Wp[(size_t)k * 192];
-        for (int i = 0; i < RAT_NP; ++i)
-            for (int jj = 0; jj < RAT_NP; ++jj) {
-                if (i < n && jj < n) {
-                    wo[i * 16 + jj] = (i <= jj) ? wi[i + n * jj] : wi[jj + n * i];   // Symmetric(inv(W) - ...) reads the upper triangle
-                    wq[i * 16 + jj] = W[i + n * jj];
-                } else if (i == jj) wo[i * 16 + jj] = 1.0;
-            }
-        // elimination pivots e_k of the padded inv(W): logdet(W M) = sum log(d_k / e_k)
-        double a[12][12];
-        for (int i = 0; i < 12; ++i) for (int jj = 0; jj < 12; ++jj) a[i][jj] = wo[i * 16 + jj];
-        double pivs[12];
-        for (int p = 0; p < 12; ++p) {
-            const double piv = a[p][p];
-            pivs[p] = piv;
-            ldw[k] -= std::log(piv);
-            for (int i = p + 1; i < 12; ++i) {
-                const double f = a[i][p] / piv;
-                for (int jj = p; jj < 12; ++jj) a[i][jj] -= f * a[p][jj];
-            }
-        }
-        // the kernels eliminate 2x2 blocks {p, p+1}: lane p (even) multiplies det(P) by 1 / (e_p e_{p+1})
-        for (int p = 0; p < 12; p += 2) { epiv[(size_t)k * 16 + p] = 1.0 / (pivs[p] * pivs[p + 1]); epiv[(size_t)k * 16 + p + 1] = 1.0; }
-    }
-    // time-invariant diagonal W: the sweeps fold inv(W) into the inverse of M (ProblemDev.W_diag)
-    std::vector<double> Wdg(16, 1.0);
-    pb.W_diag = pb.W_tv ? 0 : 1;
-    if (!pb.W_tv) {
-        for (int i = 0; i < n; ++i)
-            for (int jj = 0; jj < n; ++jj) if (i != jj && d->W[i + n * jj] != 0.0) pb.W_diag = 0;
-        for (int i = 0; i < n; ++i) Wdg[i] = Winv[i * 16 + i];
-    }
-    if (!h->wdiag) pb.W_diag = 0;       // debug switch wdiag = 0: the general-W arithmetic (A/B measurements, bit-identity tests)
-    rat_rc rc;
 #define UP(field, vec) if ((rc = dev_upload(h, h->pb_allocs, &pb.field, vec))) return rc
-    UP(Wdg, Wdg);
+    UP(Wdg, wt.Wdg);
     UP(Zt, Zt); UP(Ctab, Ctab); UP(lin, lin); UP(q0, q0); UP(Qf, Qf); UP(qvf, qvf);
-    UP(Winv, Winv); UP(Wp, Wp); UP(epiv, epiv); UP(logdetW, ldw);
+    UP(Winv, wt.Winv); UP(Wp, wt.Wp); UP(epiv, wt.epiv); UP(logdetW, wt.ldw);
 #undef UP
     // The slot pools rely on their padded lanes (states n..11, controls m..3 of x / u / L / dl) being exact zeros.  A problem with the
     // same N but smaller n or m would find the previous problem's values there, so the pools are rebuilt (and re-zeroed by
     // alloc_state) whenever ANY dimension changes; a problem of the same shape (a receding-horizon caller re-setting its tables every
     // control step) keeps its buffers: every live lane is rewritten by the next solve.
-    const bool realloc_state = !h->have_problem || h->wide || h->N != N || h->n != n || h->m != m;
+    const bool realloc_state = !h->have_problem || h->wide || h->N != N || h->n != n || h->m != m || h->pb.model == RAT_MODEL_SOURCE;
     h->pb = pb; h->n = n; h->m = m; h->N = N;
     h->have_problem = true; h->have_initial = false; h->init_traj_valid = false; h->init_batches = 0; h->problem_serial++;
     if (realloc_state && (rc = alloc_state(h))) return rc;
     return RAT_OK;
+}
+
+// ---- source models (RAT_MODEL_SOURCE): user-written f, c, h compiled at run time (source_model.cpp, source_kernels.h) -------------
+static bool src_sizes_ok(int n, int m) { return n >= 1 && m >= 1 && n <= SRC_MAX_N && m <= SRC_MAX_M; }
+
+extern "C" rat_rc rat_source_check(const char *source, int32_t n, int32_t m) {
+    if (!source) return fail(RAT_ERR_ARG, "null");
+    if (n < 1 || m < 1) return fail(RAT_ERR_ARG, "rat_source_check: n, m must be positive");
+    if (!src_sizes_ok(n, m)) return fail(RAT_ERR_UNSUPPORTED, "rat_source_check: source models are compiled for n <= 12, m <= 4");
+    std::string log;
+    const rat_rc rc = src_compile(source, n, m, "gfx950", nullptr, &log);
+    if (rc) return fail(rc, log);
+    return RAT_OK;
+}
+
+extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32_t n, int32_t m, int32_t N, const double *W, int32_t W_tv,
+                                         const double *params, int64_t n_params) {
+    if (!h || !source || !W) return fail(RAT_ERR_ARG, "null");
+    if (n < 1 || m < 1 || N < 1) return fail(RAT_ERR_ARG, "rat_problem_set_source: n, m, N must be positive");
+    if (n_params < 0 || (n_params > 0 && !params)) return fail(RAT_ERR_ARG, "rat_problem_set_source: bad parameter array");
+    if (!src_sizes_ok(n, m)) return fail(RAT_ERR_UNSUPPORTED, "rat_problem_set_source: source models are compiled for n <= 12, m <= 4");
+    HIPCHK(hipSetDevice(h->device));
+    // everything that can fail comes before the handle's previous problem is touched
+    hipDeviceProp_t pr;
+    HIPCHK(hipGetDeviceProperties(&pr, h->device));
+    std::shared_ptr<const std::vector<char>> code;
+    std::string log;
+    rat_rc rc = src_compile(source, n, m, src_arch(pr.gcnArchName), &code, &log);
+    if (rc) return fail(rc, log);
+    ProblemDev pb;
+    memset(&pb, 0, sizeof(pb));
+    pb.model = RAT_MODEL_SOURCE; pb.n = n; pb.m = m; pb.N = N; pb.cost_tv = 0; pb.W_tv = W_tv ? 1 : 0;
+    WTables wt;
+    if ((rc = build_w_tables(h, pb, W, n, N, "rat_problem_set_source", wt))) return rc;
+    hipModule_t mod = nullptr;
+    hipFunction_t fr = nullptr, fl = nullptr;
+    HIPCHK(hipModuleLoadData(&mod, code->data()));
+    if (hipModuleGetFunction(&fr, mod, "rat_src_rollout") != hipSuccess || hipModuleGetFunction(&fl, mod, "rat_src_linearize") != hipSuccess) {
+        (void)hipModuleUnload(mod);
+        return fail(RAT_ERR_HIP, "rat_problem_set_source: the compiled module lacks its kernels");
+    }
+    // the new tables go to a list of their own: the previous problem's buffers are released only once every upload has succeeded
+    std::vector<void *> allocs;
+    auto undo = [&](rat_rc r) { free_list(allocs); (void)hipModuleUnload(mod); return r; };
+    // the family tables stay allocated (zero): nothing on the round-based path reads them for a source problem
+    std::vector<double> z192(192, 0.0), z256(256, 0.0), z16(16, 0.0), z1(1, 0.0), z144(144, 0.0);
+    std::vector<double> pv(params, params + n_params);
+    if (pv.empty()) pv.push_back(0.0);
+    const double *dp = nullptr;
+#define UP(field, vec) if ((rc = dev_upload(h, allocs, &pb.field, vec))) return undo(rc)
+    UP(Wdg, wt.Wdg);
+    UP(Zt, z192); UP(Ctab, z256); UP(lin, z16); UP(q0, z1); UP(Qf, z144); UP(qvf, z16);
+    UP(Winv, wt.Winv); UP(Wp, wt.Wp); UP(epiv, wt.epiv); UP(logdetW, wt.ldw);
+#undef UP
+    if ((rc = dev_upload(h, allocs, &dp, pv))) return undo(rc);
+    if (hipStreamSynchronize(h->stream) != hipSuccess || hipStreamSynchronize(h->stream2) != hipSuccess)
+        return undo(fail(RAT_ERR_HIP, "rat_problem_set_source: hipStreamSynchronize failed"));
+    free_list(h->pb_allocs);
+    h->pb_allocs.swap(allocs);
+    if (h->src_mod) (void)hipModuleUnload(h->src_mod);
+    h->src_mod = mod; h->src_roll = fr; h->src_lin = fl;
+    h->d_src_p = const_cast<double *>(dp); h->src_np = n_params;
+    h->hW.assign(W, W + (size_t)(pb.W_tv ? N : 1) * n * n);
+    h->W_tv = pb.W_tv;
+    // per-slot tile records always (want_alias): a handle that aliased them is re-laid
+    const bool realloc_state = !h->have_problem || h->wide || h->N != N || h->n != n || h->m != m || h->st.tile_alias != 0;
+    h->pb = pb; h->n = n; h->m = m; h->N = N;
+    h->have_problem = true; h->have_initial = false; h->init_traj_valid = false; h->init_batches = 0; h->problem_serial++;
+    h->x0_host.clear(); h->u0_host.clear();
+    if (realloc_state && (rc = alloc_state(h))) return rc;
+    return RAT_OK;
+}
+
+extern "C" rat_rc rat_problem_set_params(rat_handle h, const double *params, int64_t n_params) {
+    if (!h) return fail(RAT_ERR_ARG, "null");
+    if (!h->have_problem || h->pb.model != RAT_MODEL_SOURCE) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set_params: the handle has no source problem");
+    if (n_params != h->src_np) return fail(RAT_ERR_ARG, "rat_problem_set_params: the source problem has " + std::to_string(h->src_np) + " parameters");
+    if (n_params > 0 && !params) return fail(RAT_ERR_ARG, "null");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream2));
+    if (n_params > 0) HIPCHK(hipMemcpy(h->d_src_p, params, (size_t)n_params * sizeof(double), hipMemcpyHostToDevice));
+    h->init_traj_valid = false; h->problem_serial++;     // (new results: the Nelder-Mead cost table keys on the problem serial)
+    return RAT_OK;
+}
+
+// the model launches of the handle: the family kernels (kernels.hip) or the source model's two kernels
+static void model_rollout(rat_handle h, const RolloutArgs &ra, hipStream_t s) {
+    if (h->pb.model != RAT_MODEL_SOURCE) { launch_rollout(ra, s); return; }
+    const int ncand = (ra.mode == 0) ? ra.st.B : ra.st.B * ra.st.E;
+    if (ncand <= 0) return;
+    SrcRollArgs a;
+    a.st = ra.st; a.op = ra.op; a.mode = ra.mode; a.tpw = h->src_tpw; a.x0 = ra.x0; a.u0 = ra.u0; a.p = h->d_src_p;
+    void *args[] = {&a};
+    (void)hipModuleLaunchKernel(h->src_roll, (unsigned)((ncand + a.tpw - 1) / a.tpw), 1, 1, 64, 1, 1, 0, s, args, nullptr);
+}
+static void model_linearize(rat_handle h, const LinArgs &la, hipStream_t s) {
+    if (h->pb.model != RAT_MODEL_SOURCE) { launch_linearize(la, s); return; }
+    const int ntraj = (la.mode == 0) ? la.st.B : la.st.B * la.st.E;
+    if (ntraj <= 0) return;
+    SrcLinArgs a;
+    a.st = la.st; a.mode = la.mode; a.p = h->d_src_p;
+    void *args[] = {&a};
+    const unsigned nchunk = (unsigned)((la.st.N + SRC_LIN_WAVES) / SRC_LIN_WAVES);
+    (void)hipModuleLaunchKernel(h->src_lin, (unsigned)ntraj * nchunk, 1, 1, 64 * SRC_LIN_WAVES, 1, 1, 0, s, args, nullptr);
+}
+static void model_rollin(rat_handle h, const RolloutArgs &ra, hipStream_t s) {      // rollout + linearise of the solver's loop
+    if (h->pb.model != RAT_MODEL_SOURCE) { launch_rollin(ra, s); return; }
+    model_rollout(h, ra, s);
+    LinArgs la; la.st = ra.st; la.pb = ra.pb; la.mode = ra.mode;
+    model_linearize(h, la, s);
 }
 
 // ---- profiling helpers -----------------------------------------------------------------------------
@@ -856,7 +988,7 @@ static rat_rc enqueue_round(rat_handle h, const StateDev &st, int round) {
         // fused path (E = 1): the plain gain sweep only serves samples whose fused gain recursion was abandoned (H not PD)
         { SweepArgs sg0 = sweep_args(h, st, 0); sg0.fly = fly;       // (tile-free path: the plain gain sweep forms its tiles too -- nothing to materialise)
           prof_begin(h, RAT_K_SWEEP_GAIN, st.B); launch_sweep(sg0, st.B, true, false, h->stream); prof_end(h); }
-        prof_begin(h, RAT_K_ROLLOUT, nc); launch_rollin(ra, h->stream); prof_end(h);
+        prof_begin(h, RAT_K_ROLLOUT, nc); model_rollin(h, ra, h->stream); prof_end(h);
         // Speculation pruned (switch prune, tile-free candidates): candidate 0's paired wavefronts go first and say whether the line search
         // will settle on it (StateDev.acc0); the evaluations of candidates 1 .. E-1 -- on a stream of the lowest priority, so that the paired
         // launch, which holds a SIMD's register file alone, is dispatched ahead of them -- poll that word and stop: the sequential rule never
@@ -899,7 +1031,7 @@ static rat_rc enqueue_round(rat_handle h, const StateDev &st, int round) {
         SweepArgs sg0 = sweep_args(h, st, 0); sg0.fly = fly;
         prof_begin(h, RAT_K_SWEEP_GAIN, st.B); launch_sweep(sg0, st.B, true, false, h->stream); prof_end(h);
     }
-    prof_begin(h, RAT_K_ROLLOUT, nc); launch_rollin(ra, h->stream); prof_end(h);        // fused rollout + linearise
+    prof_begin(h, RAT_K_ROLLOUT, nc); model_rollin(h, ra, h->stream); prof_end(h);        // fused rollout + linearise
     if (spec) {
         HIPCHK(hipEventRecord(h->ev_a, h->stream));
         HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_a, 0));
@@ -926,6 +1058,7 @@ static rat_rc enqueue_round(rat_handle h, const StateDev &st, int round) {
 enum Path { PATH_ROUNDS, PATH_FUSED, PATH_BLOCK, PATH_WIDE };
 static Path pick_path(const rat_handle h, int B) {
     if (h->wide) return PATH_WIDE;
+    if (h->pb.model == RAT_MODEL_SOURCE) return PATH_ROUNDS;       // (the single-launch solves have the families built in)
     if (h->path_fixed == RAT_PATH_ROUNDS) return PATH_ROUNDS;      // (rat_set_path has checked that the handle's E has the kernel)
     if (h->path_fixed == RAT_PATH_FUSED) return PATH_FUSED;
     if (h->path_fixed == RAT_PATH_BLOCK) return PATH_BLOCK;
@@ -960,7 +1093,7 @@ extern "C" int32_t rat_get_path(rat_handle h, int64_t B) {
 static rat_rc alloc_state(rat_handle h);
 static rat_rc relayout_if_needed(rat_handle h, bool was_alias, int was_E = -1) {
     if (was_E < 0) was_E = h->E;
-    if (h->have_problem && !h->wide && (was_alias != h->fused || was_E != h->E)) {      // re-laid only when the aliasing mode or the speculation width really changes
+    if (h->have_problem && !h->wide && (was_alias != want_alias(h) || was_E != h->E)) {      // re-laid only when the aliasing mode or the speculation width really changes
         rat_rc rc = alloc_state(h);
         if (rc) return rc;
         h->have_initial = false; h->init_traj_valid = false; h->init_batches = 0; h->x0_host.clear(); h->u0_host.clear();
@@ -971,6 +1104,8 @@ extern "C" rat_rc rat_set_path(rat_handle h, int32_t path) {
     if (!h) return fail(RAT_ERR_ARG, "null");
     if (path < RAT_PATH_AUTO || path > RAT_PATH_BLOCK) return fail(RAT_ERR_ARG, "rat_set_path: unknown path");
     if (h->wide && path != RAT_PATH_AUTO) return fail(RAT_ERR_UNSUPPORTED, "rat_set_path: problems beyond n <= 12, m <= 4 run the general-size kernel only");
+    if (h->have_problem && h->pb.model == RAT_MODEL_SOURCE && (path == RAT_PATH_FUSED || path == RAT_PATH_BLOCK))
+        return fail(RAT_ERR_UNSUPPORTED, "rat_set_path: source models run the round-based path only");
     if (path == RAT_PATH_FUSED && h->E != 1) return fail(RAT_ERR_UNSUPPORTED, "rat_set_path: the one-wavefront-per-sample kernel exists for spec_eps = 1 only");
     if (path == RAT_PATH_BLOCK && !solve_block_supported(h->E)) return fail(RAT_ERR_UNSUPPORTED, "rat_set_path: the workgroup-per-sample kernel exists for spec_eps 1, 2, 4, 8");
     if ((path == RAT_PATH_FUSED || path == RAT_PATH_BLOCK) && (h->speculate || (h->E == 1 && h->dual)))
@@ -1019,7 +1154,7 @@ static void ensure_init_traj(rat_handle h, const RolloutArgs &ra, const double *
     si.B = 1; si.xs = h->d_init_x; si.us = h->d_init_u; si.tiles = h->d_init_t;
     launch_init_state(si, h->opd, theta_dev, h->stream);     // (sample 0's control words; the batch initialises its samples again)
     RolloutArgs ri = ra; ri.st = si; ri.mode = 0; ri.notile = 0; ri.multi = 0;
-    launch_rollin(ri, h->stream);
+    model_rollin(h, ri, h->stream);
     h->init_traj_valid = true;
 }
 
@@ -1131,7 +1266,7 @@ static rat_rc run_batch(rat_handle h, const double *theta_dev, int B, const Batc
         ensure_init_traj(h, ra, theta_dev);              // (its init_state writes to sample 0 what the batch's own has just written)
         prof_begin(h, RAT_K_ROLLOUT, B); launch_copy_initial(st, h->d_init_x, h->d_init_u, h->d_init_t, h->stream); prof_end(h);
     } else {
-        prof_begin(h, RAT_K_ROLLOUT, B); launch_rollin(ra, h->stream); prof_end(h);     // fused rollout + linearise
+        prof_begin(h, RAT_K_ROLLOUT, B); model_rollin(h, ra, h->stream); prof_end(h);     // fused rollout + linearise
     }
     if (h->dual && !spec) {
         SweepArgs s6 = sweep_args(h, st, 6); s6.fly = share0 ? 1 : 0;
@@ -1584,7 +1719,7 @@ extern "C" rat_rc rat_rollout_open(rat_handle h, const double *x0, const double 
     StateDev st;
     if ((rc = op_prepare(h, 0.0, 0.0, h->opts.delta_0, &st))) return rc;
     RolloutArgs ra; ra.st = st; ra.pb = h->pb; ra.op = h->opd; ra.dump = h->d_dump; ra.mode = 0; ra.x0 = h->d_x0; ra.u0 = h->d_u0; ra.notile = 0; ra.multi = 0;
-    launch_rollout(ra, h->stream);
+    model_rollout(h, ra, h->stream);
     HIPCHK(hipStreamSynchronize(h->stream));
     std::vector<double> xp;
     if ((rc = fetch_slot(h, 0, &xp, nullptr, nullptr))) return rc;
@@ -1617,7 +1752,7 @@ extern "C" rat_rc rat_rollout_feedback(rat_handle h, const double *xbar, const d
     const int one = 1;
     HIPCHK(hipMemcpy(st.ls_active, &one, 4, hipMemcpyHostToDevice));
     RolloutArgs ra; ra.st = st; ra.pb = h->pb; ra.op = h->opd; ra.dump = h->d_dump; ra.mode = 1; ra.x0 = h->d_x0; ra.u0 = h->d_u0; ra.notile = 0; ra.multi = 0;
-    launch_rollout(ra, h->stream);
+    model_rollout(h, ra, h->stream);
     HIPCHK(hipStreamSynchronize(h->stream));
     std::vector<double> xp, up;
     if ((rc = fetch_slot(h, 1, &xp, &up, nullptr))) return rc;        // candidate 0 of sample 0 lives in slot 1
@@ -1638,6 +1773,7 @@ extern "C" rat_rc rat_rollout_noisy(rat_handle h, const double *x_nom, const dou
     if (!h || !x_nom || !l) return fail(RAT_ERR_ARG, "null");
     if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
     if (K < 1) return fail(RAT_ERR_ARG, "K must be positive");
+    if (h->pb.model == RAT_MODEL_SOURCE) return fail(RAT_ERR_UNSUPPORTED, "rat_rollout_noisy: not available for source models");
     HIPCHK(hipSetDevice(h->device));
     const int n = h->n, m = h->m, N = h->N, Nw = h->W_tv ? N : 1;
     if (h->wide) {                       // general size: dense column-major in and out, one workgroup per rollout
@@ -1733,7 +1869,7 @@ static rat_rc linearize_slot0(rat_handle h, const double *u, const double *x, st
     if (rc) return rc;
     if ((rc = put_slot0(h, x, u))) return rc;
     LinArgs la; la.st = st; la.pb = h->pb; la.mode = 0;
-    launch_linearize(la, h->stream);
+    model_linearize(h, la, h->stream);
     HIPCHK(hipStreamSynchronize(h->stream));
     if ((rc = fetch_slot(h, 0, nullptr, nullptr, tiles))) return rc;
     int st_h = 0;

@@ -1,0 +1,27 @@
+// source_args.h -- argument blocks of the runtime-compiled model kernels (source_kernels.h), shared with the host driver.
+// No HIP include here: under hiprtc <hip/hip_runtime.h> is not found, so the JIT side reaches these definitions through this header and
+// layout.h alone.
+#pragma once
+#include "layout.h"
+
+#define SRC_MAX_N 12          /* the 12 + 4 tile of layout.h */
+#define SRC_MAX_M 4
+#define SRC_LIN_WAVES 4       /* time steps (waves) per workgroup of rat_src_linearize */
+
+// rat_src_rollout: simulate_dynamics (ileqg.jl:18-38, :62-87), one lane per trajectory
+struct SrcRollArgs {
+    StateDev st;
+    OptsDev op;
+    int mode;                 // 0 open loop from (x0, u0) into the nominal slots; 1 closed-loop line-search candidates (what rollout_kernel does)
+    int tpw;                  // trajectories per wavefront (lanes 0 .. tpw-1 of each 64-lane workgroup work)
+    const double *x0;         // [12]
+    const double *u0;         // [N*4]
+    const double *p;          // the model's parameters
+};
+
+// rat_src_linearize: approximate_model (ileqg.jl:258-322), one wavefront per (trajectory, t), t = N the terminal tile
+struct SrcLinArgs {
+    StateDev st;
+    int mode;                 // 0 nominal slots, 1 candidate slots
+    const double *p;
+};

@@ -1,0 +1,128 @@
+// source_model.cpp -- hiprtc (through dlopen: the library loads, and every other path works, where hiprtc is missing) and the process-wide
+// code-object cache of the runtime-compiled model family.
+#include "source_model.h"
+
+#include <dlfcn.h>
+
+#include <chrono>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <tuple>
+
+#include <hip/hiprtc.h>
+
+namespace {
+
+// the embedded headers (Makefile: source_embed.inc, raw string literals of the files)
+#include "source_embed.inc"
+
+struct Rtc {
+    bool tried = false, ok = false;
+    std::string why;
+    hiprtcResult (*create)(hiprtcProgram *, const char *, const char *, int, const char *const *, const char *const *) = nullptr;
+    hiprtcResult (*compile)(hiprtcProgram, int, const char *const *) = nullptr;
+    hiprtcResult (*destroy)(hiprtcProgram *) = nullptr;
+    hiprtcResult (*log_size)(hiprtcProgram, size_t *) = nullptr;
+    hiprtcResult (*log)(hiprtcProgram, char *) = nullptr;
+    hiprtcResult (*code_size)(hiprtcProgram, size_t *) = nullptr;
+    hiprtcResult (*code)(hiprtcProgram, char *) = nullptr;
+};
+
+std::mutex g_mu;
+Rtc g_rtc;
+std::map<std::tuple<std::string, int, int, std::string>, std::shared_ptr<const std::vector<char>>> g_cache;
+
+bool rtc_load(std::string *why) {           // (g_mu held)
+    if (!g_rtc.tried) {
+        g_rtc.tried = true;
+        void *so = dlopen("libhiprtc.so", RTLD_NOW | RTLD_LOCAL);
+        if (!so) so = dlopen("libhiprtc.so.7", RTLD_NOW | RTLD_LOCAL);
+        if (!so) g_rtc.why = std::string("hiprtc is not available: ") + dlerror();
+        else {
+#define SYM(field, name) g_rtc.field = reinterpret_cast<decltype(g_rtc.field)>(dlsym(so, name))
+            SYM(create, "hiprtcCreateProgram"); SYM(compile, "hiprtcCompileProgram"); SYM(destroy, "hiprtcDestroyProgram");
+            SYM(log_size, "hiprtcGetProgramLogSize"); SYM(log, "hiprtcGetProgramLog");
+            SYM(code_size, "hiprtcGetCodeSize"); SYM(code, "hiprtcGetCode");
+#undef SYM
+            g_rtc.ok = g_rtc.create && g_rtc.compile && g_rtc.destroy && g_rtc.log_size && g_rtc.log && g_rtc.code_size && g_rtc.code;
+            if (!g_rtc.ok) g_rtc.why = "hiprtc is not available: a symbol is missing from libhiprtc.so";
+        }
+    }
+    if (!g_rtc.ok) *why = g_rtc.why;
+    return g_rtc.ok;
+}
+
+}  // namespace
+
+std::string src_arch(const char *gcn_arch_name) {
+    std::string in = gcn_arch_name ? gcn_arch_name : "", out;
+    size_t pos = 0;
+    while (pos <= in.size()) {
+        size_t e = in.find(':', pos);
+        if (e == std::string::npos) e = in.size();
+        const std::string tok = in.substr(pos, e - pos);
+        if (!tok.empty() && tok != "xnack+") out += (out.empty() ? "" : ":") + tok;
+        pos = e + 1;
+    }
+    return out.empty() ? std::string("gfx950") : out;
+}
+
+rat_rc src_compile(const char *source, int n, int m, const std::string &arch, std::shared_ptr<const std::vector<char>> *code,
+                   std::string *log, double *ms, bool *cached) {
+    const auto t0 = std::chrono::steady_clock::now();
+    auto done = [&](rat_rc rc) {
+        if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return rc;
+    };
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (cached) *cached = false;
+    const auto key = std::make_tuple(std::string(source), n, m, arch);
+    auto it = g_cache.find(key);
+    if (it != g_cache.end()) {
+        if (code) *code = it->second;
+        if (cached) *cached = true;
+        return done(RAT_OK);
+    }
+    std::string why;
+    if (!rtc_load(&why)) { if (log) *log = why; return done(RAT_ERR_UNSUPPORTED); }
+    // the user's source between the AD header and the kernels; #line makes the compiler's messages name lines of the user's text
+    const std::string text = std::string("#include \"source_args.h\"\n#include \"rat_ad.h\"\n#line 1 \"model.hip\"\n") + source +
+                             "\n#line 1 \"source_kernels.h\"\n#include \"source_kernels.h\"\n";
+    const char *hdr[] = {k_embed_layout_h, k_embed_source_args_h, k_embed_rat_ad_h, k_embed_source_kernels_h};
+    const char *hdr_names[] = {"layout.h", "source_args.h", "rat_ad.h", "source_kernels.h"};
+    hiprtcProgram prog = nullptr;
+    if (g_rtc.create(&prog, text.c_str(), "model.hip", 4, hdr, hdr_names) != HIPRTC_SUCCESS) {
+        if (log) *log = "hiprtcCreateProgram failed";
+        return done(RAT_ERR_ARG);
+    }
+    const std::string dn = "-DRAT_N=" + std::to_string(n), dm = "-DRAT_M=" + std::to_string(m), oa = "--offload-arch=" + arch;
+    const char *opts[] = {"-O3", "-std=c++17", dn.c_str(), dm.c_str(), oa.c_str()};
+    const hiprtcResult rc = g_rtc.compile(prog, 5, opts);
+    size_t ls = 0;
+    std::string lg;
+    if (g_rtc.log_size(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
+        lg.resize(ls);
+        g_rtc.log(prog, &lg[0]);
+        lg.resize(strnlen(lg.c_str(), ls));
+    }
+    if (rc != HIPRTC_SUCCESS) {
+        g_rtc.destroy(&prog);
+        if (log) *log = "source model does not compile:\n" + lg;
+        return done(RAT_ERR_ARG);
+    }
+    size_t cs = 0;
+    auto obj = std::make_shared<std::vector<char>>();
+    if (g_rtc.code_size(prog, &cs) != HIPRTC_SUCCESS || cs == 0) {
+        g_rtc.destroy(&prog);
+        if (log) *log = "hiprtc produced no code object";
+        return done(RAT_ERR_ARG);
+    }
+    obj->resize(cs);
+    g_rtc.code(prog, obj->data());
+    g_rtc.destroy(&prog);
+    g_cache[key] = obj;
+    if (code) *code = obj;
+    if (log) *log = lg;
+    return done(RAT_OK);
+}

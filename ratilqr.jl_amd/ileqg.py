@@ -18,7 +18,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native as nv
-from .problems import FiniteHorizonRiskSensitiveOptimalControlProblem
+from .problems import MODEL_SOURCE, FiniteHorizonRiskSensitiveOptimalControlProblem
 
 SQRT_EPS = 1.4901161193847656e-8
 
@@ -35,8 +35,16 @@ class Context:
         nv.check(L.rat_create(C.byref(opts) if opts is not None else None, self.max_batch, self.spec_eps,
                               self.device, C.byref(self.h)))
         self._fin = weakref.finalize(self, L.rat_destroy, self.h)
-        desc, self._keep = nv.make_desc(problem)
-        nv.check(L.rat_problem_set(self.h, C.byref(desc)))
+        self._keep = self._upload(problem)
+
+    def _upload(self, problem):
+        if getattr(problem, "model", 0) == MODEL_SOURCE:            # user-written f, c, h: compiled at run time (rat_problem_set_source)
+            keep = nv.set_source(self.h, problem)
+            self.params = keep["params"].copy()                       # what this handle's kernels read (set_params changes it)
+            return keep
+        desc, keep = nv.make_desc(problem)
+        nv.check(nv.lib().rat_problem_set(self.h, C.byref(desc)))
+        return keep
 
     def set_opts(self, opts):
         nv.check(nv.lib().rat_set_ileqg_opts(self.h, C.byref(opts)))
@@ -44,10 +52,17 @@ class Context:
     def set_problem(self, problem):
         """Re-bind the handle to another problem of the same model families (rat_problem_set on the live handle: device buffers are
         kept when n, m, N are unchanged -- the receding-horizon pattern of re-setting the tables every control step)."""
-        desc, keep = nv.make_desc(problem)
-        nv.check(nv.lib().rat_problem_set(self.h, C.byref(desc)))
+        keep = self._upload(problem)
         self.problem, self._keep = problem, keep
         self.n, self.m, self.N = problem.n, problem.m, problem.N
+
+    def set_params(self, params):
+        """New parameter values of this handle's source problem (rat_problem_set_params: the same count, no recompilation).  They hold for
+        this handle only: the problem object keeps its own `params`, which every other handle -- and this one, when the problem is set
+        again -- uploads."""
+        p = nv.f64(np.atleast_1d(params))
+        nv.check(nv.lib().rat_problem_set_params(self.h, nv.P(p) if p.size else None, C.c_int64(p.size)))
+        self.params = p.copy()
 
     # ---- operator forms --------------------------------------------------------------------------
     def rollout_open(self, x0, u):

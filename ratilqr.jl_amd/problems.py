@@ -19,6 +19,7 @@ import numpy as np
 
 MODEL_LQ = 1
 MODEL_POWERLAW = 2
+MODEL_SOURCE = 3
 
 
 class OptimalControlProblem:
@@ -194,6 +195,34 @@ def synthetic_lq_problem(n=12, m=4, N=50, rho=0.9, w=1e-3, r_weight=0.1, seed=0,
     prob = LQRiskSensitiveProblem(A, B, Q=np.eye(n), R=r_weight * np.eye(m), N=N, W=w * np.eye(n), Qf=np.eye(n),
                                   kappa=kappa)
     return prob, x0, np.zeros((N, m))
+
+
+class DeviceSourceProblem(FiniteHorizonRiskSensitiveOptimalControlProblem):
+    """FiniteHorizonRiskSensitiveOptimalControlProblem(f, c, h, W, N) with f, c, h written as HIP device code (RAT_MODEL_SOURCE,
+    include/ratilqr.h "source models"): the library compiles `source` at run time and runs rollouts and linearisations on the GPU.
+
+    source: defines rat_user_f / rat_user_c / rat_user_h templated on the scalar type (RAT_N = n, RAT_M = m); params: the doubles the
+    device functions read through `p` (Context.set_params replaces them on one handle without recompiling).  W: one (n, n) matrix, an (N, n, n)
+    stack, or a callable W(k), k = 0 .. N-1."""
+
+    model = MODEL_SOURCE
+
+    def __init__(self, source, n, m, N, W, params=None):
+        self.source, self.n, self.m, self.N = str(source), int(n), int(m), int(N)
+        if callable(W):
+            W = np.stack([np.asarray(W(k), dtype=np.float64) for k in range(self.N)])
+        self.Wtab = np.asarray(W, dtype=np.float64)
+        self.W_tv = self.Wtab.ndim == 3
+        self.params = np.zeros(0) if params is None else np.ascontiguousarray(np.atleast_1d(params), dtype=np.float64)
+
+    def W(self, k):
+        return self.Wtab[k] if self.W_tv else self.Wtab
+
+    def f(self, x, u, f_returns_jacobian=False):
+        raise NotImplementedError("a source model's f runs on the device only (simulate_dynamics)")
+
+    def c_tables(self) -> dict:
+        raise NotImplementedError("a source model is uploaded with rat_problem_set_source (Context)")
 
 
 class FiniteHorizonGenerativeOptimalControlProblem(OptimalControlProblem):
