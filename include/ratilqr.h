@@ -19,7 +19,8 @@
  *   - call from one host thread per handle; a handle owns one HIP device and one stream; a rat_multi owns one handle per
  *     device and is driven from one host thread as well (no callbacks, no thread-local state of the caller: @threadcall-safe);
  *   - user closures f/c/h/W cannot cross the ABI: problems are instances of compiled-in model
- *     families (rat_problem_desc.model), or HIP source the library compiles at run time (rat_problem_set_source).
+ *     families (rat_problem_desc.model), or HIP source the library compiles at run time (rat_problem_set_source,
+ *     rat_pets_problem_set_source).
  */
 #ifndef RATILQR_H
 #define RATILQR_H
@@ -133,7 +134,8 @@ rat_rc rat_problem_set(rat_handle h, const rat_problem_desc *desc);
  * with A n x n and B n x m column-major: exact Jacobians instead of AD for f.  A NaN in x_{t+1} or in a cost whose inputs had none is
  * the reference's DomainError (RAT_ST_DOMAIN, value Inf).  No fast-math.
  * Limits: n <= 12, m <= 4 (else RAT_ERR_UNSUPPORTED); batches run on the round-based path (rat_set_path FUSED / BLOCK return
- * RAT_ERR_UNSUPPORTED); rat_rollout_noisy, PETS and rat_multi are not available for source models. */
+ * RAT_ERR_UNSUPPORTED); rat_rollout_noisy and rat_multi are not available for source models.  PETS takes generative source models
+ * of its own (rat_pets_problem_set_source, below). */
 #define RAT_MODEL_SOURCE    3
 
 /* Compile `source` (NUL-terminated) for the handle's device and make it the handle's problem.  W: n*n column-major, N entries if W_tv
@@ -377,6 +379,40 @@ rat_rc rat_pets_step(rat_handle h, rat_pets_solver *s, const double *x0, int32_t
 rat_rc rat_pets_solve(rat_handle h, rat_pets_solver *s, const double *x0, int32_t use_true_model, const double *zc,
                       const double *zn, const double *zu, uint64_t seed);
 
+/* ---- generative source models: f_stochastic, c, h written by the user, compiled at run time ------------------------------------------
+ * FiniteHorizonGenerativeOptimalControlProblem(f_stochastic, c, h, N) with user device code (pets.jl / optimal_control_problems.jl:77-131).
+ * After success, rat_pets_compute_cost / rat_pets_step / rat_pets_solve (host loop and device-resident loop) run this model;
+ * rat_pets_problem_set switches the handle back to the family.  The handle's iLEQG problem is not touched, and vice versa.
+ * The source defines, for the compile-time constants RAT_N = n, RAT_M = m, RAT_PETS_NORMALS = normals_per_step and
+ * RAT_PETS_UNIFORMS = uniforms_per_step, and the user's parameters p (kept on the device):
+ *
+ *   __device__ void rat_user_f_stochastic(const double *x, const double *u, rat_rng &rng, int use_true_model, double *xn, const double *p);
+ *   template <class T> __device__ T rat_user_c(int k, const T *x, const T *u, const double *p);   c(k, x, u), k = 0 .. N-1 (T = double)
+ *   template <class T> __device__ T rat_user_h(const T *x, const double *p);                      h(x_N)
+ *
+ * rat_rng provides double normal() (N(0,1)) and double uniform() (U[0,1)).  rat_user_f is not needed; a source that defines all four
+ * functions works with rat_problem_set_source and rat_pets_problem_set_source alike.  Each step's draws are counted, i = 0, 1, ...:
+ *   injected (zn or zu non-NULL; every stream whose count is nonzero must be given, else RAT_ERR_ARG): the i-th normal() of trajectory
+ *     j = ii*K + kk at step t reads zn[(j*N + t)*normals_per_step + i], the i-th uniform() zu[(j*N + t)*uniforms_per_step + i]; slots are
+ *     fixed per (j, t, i) -- a draw the model skips leaves its slot unread.  normals_per_step = n is the family's zn layout.
+ *   generator (zn and zu NULL): Philox4x32-10 with key (seed lo, seed hi) and g = the global trajectory index (rat_pets_enqueue's
+ *     sample0 * K + j): normal pair q = i / 2 from counter (g lo, g hi, t, q) -- two 53-bit uniforms (r0:r1, r2:r3) >> 11 * 2^-53, the
+ *     Box-Muller transform of csrc/rat_normal.h, normal 2q its cosine output, 2q + 1 its sine output; uniform pair q from counter
+ *     (g lo, g hi, t, 0x80000000 | q), uniform 2q = (r0:r1), 2q + 1 = (r2:r3).  Results do not depend on how a batch is split.
+ *   overdraw: a draw beyond the declared count is NaN and the call returns RAT_ERR_ARG naming the limits (rat_pets_solve checks once,
+ *     after its single wait).  NaN costs otherwise propagate as in the reference (PETS has no DomainError).
+ * Limits as rat_problem_set_source: n <= 12, m <= 4 (else RAT_ERR_UNSUPPORTED); negative counts RAT_ERR_ARG; a compile error RAT_ERR_ARG
+ * with the compiler's log (model.hip:LINE) and the handle's previous generative problem in place; hiprtc missing RAT_ERR_UNSUPPORTED.
+ * Code objects are cached per process by (source, kind, n, m, the two counts, device architecture).  rat_multi_pets_* take the family only. */
+rat_rc rat_pets_problem_set_source(rat_handle h, const char *source, int32_t n, int32_t m, int32_t N,
+                                   int32_t normals_per_step, int32_t uniforms_per_step,
+                                   const double *params, int64_t n_params);
+/* New values of the generative source problem's parameters (the same count; no recompilation). */
+rat_rc rat_pets_set_params(rat_handle h, const double *params, int64_t n_params);
+/* Compile only, for gfx950 (no device needed): RAT_OK, RAT_ERR_ARG with the log in rat_last_error(), or RAT_ERR_UNSUPPORTED. */
+rat_rc rat_pets_source_check(const char *source, int32_t n, int32_t m,
+                             int32_t normals_per_step, int32_t uniforms_per_step);
+
 /* ---- several devices behind one object -----------------------------------------------------------------
  * Replaces the process fan-out of compute_cost (cross_entropy_bilevel_optimization.jl:180-192: `@sync ... @async remotecall_fetch(
  * compute_value_worker, 2 + mod(i, nprocs - 1), ...)` over `addprocs` workers) and of the PETS cost (pets.jl:108-124): ONE host
@@ -507,6 +543,8 @@ int32_t rat_get_path(rat_handle h, int64_t B);
  *                            element step: where the segment cuts go                                                      (120, 140, 125)
  *   src_tpw         16 / 32 / 64   source models: trajectories per wavefront of the rollout kernel (16: measured faster at 1024
  *                            trajectories, profiles/source_model.md)                                                        (16)
+ *   src_pets_tpw    16 / 32 / 64   generative source models: trajectories per wavefront of the PETS rollout kernel (64: 3.7x 16's
+ *                            rollouts/s at 10^6 trajectories, equal at 10 k; profiles/source_pets.md)                     (64)
  *   wdiag           0 / 1    diagonal time-invariant W: inv(W) folded into M^-1's operand (takes effect at the next rat_problem_set) (1) */
 rat_rc  rat_debug_set(rat_handle h, const char *key, int64_t value);
 rat_rc  rat_debug_get(rat_handle h, const char *key, int64_t *value);      /* the EFFECTIVE value on this handle */

@@ -59,6 +59,18 @@ struct DeviceSourceProblem <: DeviceRiskSensitiveProblem
 end
 DeviceSourceProblem(source, n, m, N, W; params=Float64[]) = DeviceSourceProblem(String(source), n, m, N, W, Vector{Float64}(params))
 
+"""Generative source model (PETS): f_stochastic, c, h written as HIP device code (rat_user_f_stochastic / rat_user_c / rat_user_h,
+include/ratilqr.h "generative source models"), compiled by the library at run time; `rng.normal()` / `rng.uniform()` draw at most
+`normals_per_step` (default n) / `uniforms_per_step` values per step; `params` are the doubles those functions read."""
+struct DeviceGenerativeSourceProblem <: OptimalControlProblem
+    source::String
+    n::Int64; m::Int64; N::Int64
+    params::Vector{Float64}
+    normals_per_step::Int64; uniforms_per_step::Int64
+end
+DeviceGenerativeSourceProblem(source, n, m, N; params=Float64[], normals_per_step=n, uniforms_per_step=0) =
+    DeviceGenerativeSourceProblem(String(source), n, m, N, Vector{Float64}(params), normals_per_step, uniforms_per_step)
+
 dims(p::LQRiskSensitiveProblem) = (size(p.B, 1), size(p.B, 2), p.N)
 dims(p::DeviceSourceProblem) = (p.n, p.m, p.N)
 dims(p::PowerLawRiskSensitiveProblem) = (p.n, p.n, p.N)
@@ -844,6 +856,29 @@ function handle!(s::CrossEntropyDirectOptimizationSolver, problem::LQGenerativeP
     end
     s.h
 end
+function handle!(s::CrossEntropyDirectOptimizationSolver, problem::DeviceGenerativeSourceProblem)
+    if s.h === nothing || s.h.problem !== problem
+        s.h === nothing && (s.h = Handle(IleqgOpts(1e-6, 2.0, 0.5, 1e-2, 100, 1.0, 1e-6, 0), 1, 1, s.device))
+        check(ccall((:rat_pets_problem_set_source, LIB), Int32, (Ptr{Cvoid}, Cstring, Int32, Int32, Int32, Int32, Int32, Ptr{Float64}, Int64),
+                    s.h.ptr, problem.source, problem.n, problem.m, problem.N, problem.normals_per_step, problem.uniforms_per_step,
+                    problem.params, length(problem.params)))
+        s.h.problem = problem
+    end
+    s.h
+end
+multi_handle!(s::CrossEntropyDirectOptimizationSolver, problem::DeviceGenerativeSourceProblem) =
+    throw(ArgumentError("rat_multi does not take generative source models: use one device"))
+"""New values of a generative source problem's parameters on this solver's handle (same count, no recompilation).  `problem.params` is
+left as it is: the handle uploads it again if it is re-bound to the problem."""
+function set_params!(s::CrossEntropyDirectOptimizationSolver, problem::DeviceGenerativeSourceProblem, params::Vector{Float64})
+    h = handle!(s, problem)
+    check(ccall((:rat_pets_set_params, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64), h.ptr, params, length(params)))
+    s
+end
+"Compile a generative source model for gfx950 without a device (throws with the compiler's log)."
+pets_source_check(source::AbstractString, n::Integer, m::Integer; normals_per_step::Integer=n, uniforms_per_step::Integer=0) =
+    check(ccall((:rat_pets_source_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32), source, n, m, normals_per_step, uniforms_per_step))
+const GenerativeDeviceProblem = Union{LQGenerativeProblem,DeviceGenerativeSourceProblem}
 function multi_handle!(s::CrossEntropyDirectOptimizationSolver, problem::LQGenerativeProblem)
     if s.mh === nothing || s.mh.problem !== problem
         s.mh === nothing && (s.mh = MultiHandle(IleqgOpts(1e-6, 2.0, 0.5, 1e-2, 100, 1.0, 1e-6, 0), 1, 1, s.devices))
@@ -857,7 +892,7 @@ end
 
 """compute_cost(direct_solver, problem, x, control_sequence_array, rng, use_true_model) -- pets.jl:100-126 (all S × K stochastic rollouts in
 one launch; noise from the device generator keyed by a seed drawn from `rng`)"""
-function compute_cost(s::CrossEntropyDirectOptimizationSolver, problem::LQGenerativeProblem, x::Vector{Float64},
+function compute_cost(s::CrossEntropyDirectOptimizationSolver, problem::GenerativeDeviceProblem, x::Vector{Float64},
                       control_sequence_array::Vector{Vector{Vector{Float64}}}, rng::AbstractRNG, use_true_model=false)
     S = length(control_sequence_array)
     ctrl = cat([flat(c) for c in control_sequence_array]...; dims=3)           # m × N × S
@@ -889,7 +924,7 @@ function with_pets_state(f::Function, s::CrossEntropyDirectOptimizationSolver)
 end
 
 "step!(direct_solver, problem, x, rng, use_true_model) -- pets.jl:193-245"
-function step!(s::CrossEntropyDirectOptimizationSolver, problem::LQGenerativeProblem, x::Vector{Float64}, rng::AbstractRNG,
+function step!(s::CrossEntropyDirectOptimizationSolver, problem::GenerativeDeviceProblem, x::Vector{Float64}, rng::AbstractRNG,
                use_true_model=false, verbose=false, serial=false)
     h = handle!(s, problem); m = length(s.μ_array[1])
     zc = randn(rng, m, s.N, s.num_control_samples)
@@ -901,7 +936,7 @@ function step!(s::CrossEntropyDirectOptimizationSolver, problem::LQGenerativePro
 end
 
 "solve!(direct_solver, problem, x_0, rng; use_true_model) -- pets.jl:270-281.  Returns (μ_array, Σ_array)."
-function solve!(s::CrossEntropyDirectOptimizationSolver, problem::LQGenerativeProblem, x_0::Vector{Float64}, rng::AbstractRNG;
+function solve!(s::CrossEntropyDirectOptimizationSolver, problem::GenerativeDeviceProblem, x_0::Vector{Float64}, rng::AbstractRNG;
                 use_true_model=false, verbose=false, serial=false)
     h = handle!(s, problem); m = length(s.μ_array[1])
     zc = randn(rng, m, s.N, s.num_control_samples, s.iter_max)
@@ -1125,6 +1160,7 @@ function solve!(s::NelderMeadBilevelOptimizationSolver, problem, x_0::Vector{Flo
 end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check,
+       DeviceGenerativeSourceProblem, pets_source_check,
        simulate_dynamics, simulate_dynamics_noisy, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,

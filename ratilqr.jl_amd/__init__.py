@@ -9,6 +9,7 @@ from .problems import (  # noqa: F401
     LQRiskSensitiveProblem,
     PowerLawRiskSensitiveProblem,
     DeviceSourceProblem,
+    DeviceGenerativeSourceProblem,
     synthetic_lq_problem,
 )
 from ._native import RatError, SO_PATH  # noqa: F401,E402

@@ -88,6 +88,7 @@ EXPORTS = [
     "rat_multi_ce_compute_cost_ex", "rat_multi_ileqg_solve_batch", "rat_multi_is_logical", "rat_set_path", "rat_get_path", "rat_ce_compute_cost_enqueue_ex",
     "rat_debug_set", "rat_debug_get", "rat_ce_update_dev",
     "rat_problem_set_source", "rat_problem_set_params", "rat_source_check",
+    "rat_pets_problem_set_source", "rat_pets_set_params", "rat_pets_source_check",
 ]
 
 _lib = None
@@ -121,6 +122,9 @@ def lib():
         _lib.rat_problem_set_source.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_int64]
         _lib.rat_problem_set_params.argtypes = [C.c_void_p, _dp, C.c_int64]
         _lib.rat_source_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32]
+        _lib.rat_pets_problem_set_source.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int64]
+        _lib.rat_pets_set_params.argtypes = [C.c_void_p, _dp, C.c_int64]
+        _lib.rat_pets_source_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     return _lib
 
 
@@ -166,6 +170,21 @@ def _wbuf(prob):
 def source_check(source, n, m):
     """rat_source_check: compile only (gfx950, no device needed); raises RatError with the compiler's log."""
     check(lib().rat_source_check(str(source).encode(), int(n), int(m)))
+
+
+def pets_set_source(h, prob):
+    """rat_pets_problem_set_source for a DeviceGenerativeSourceProblem; returns the parameter array the call read."""
+    p = f64(prob.params)
+    check(lib().rat_pets_problem_set_source(h, prob.source.encode(), int(prob.n), int(prob.m), int(prob.N), int(prob.normals_per_step),
+                                            int(prob.uniforms_per_step), P(p) if p.size else None, C.c_int64(p.size)))
+    return p
+
+
+def pets_source_check(source, n, m, normals_per_step=None, uniforms_per_step=0):
+    """rat_pets_source_check: compile a generative source only (gfx950, no device needed); raises RatError with the compiler's log.
+    normals_per_step defaults to n."""
+    npn = int(n) if normals_per_step is None else int(normals_per_step)
+    check(lib().rat_pets_source_check(str(source).encode(), int(n), int(m), npn, int(uniforms_per_step)))
 
 
 def make_desc(prob):

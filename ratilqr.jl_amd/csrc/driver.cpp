@@ -167,6 +167,15 @@ struct rat_handle_s {
     hipFunction_t src_roll = nullptr, src_lin = nullptr;
     double *d_src_p = nullptr; int64_t src_np = 0;      // (d_src_p lives in pb_allocs)
     int src_tpw = 16;                // switch src_tpw: trajectories per wavefront of the rollout kernel (16 or 64; measured)
+    int src_pets_tpw = 64;           // switch src_pets_tpw: the same for the generative source models' PETS rollouts (64 measured best at
+                                     // 10 k and 10^6 trajectories, profiles/source_pets.md)
+    // generative source models (PETS, rat_pets_problem_set_source): a module of their own, apart from src_mod (the iLEQG problem's)
+    bool gsrc = false;               // the handle's PETS problem is a source model (false: the family tables of rat_pets_problem_set)
+    hipModule_t gsrc_mod = nullptr;
+    hipFunction_t gsrc_roll = nullptr;
+    double *d_gsrc_p = nullptr; int64_t gsrc_np = 0;    // (d_gsrc_p lives in gen_allocs)
+    int gsrc_npn = 0, gsrc_npu = 0;  // draws per step it declared
+    int *h_gsrc_over = nullptr;      // pinned: the overdraw flag its kernel sets with a plain store (bit 0 normals, bit 1 uniforms)
 };
 
 extern "C" int32_t rat_version(void) { return RAT_VERSION; }
@@ -240,6 +249,7 @@ static const DebugSwitch debug_switches[] = {
     {"psw_acl", [](rat_handle h, int64_t v) { h->psw_acl = (v != 0); }, [](rat_handle h) -> int64_t { return h->psw_acl; }},
     {"psw_comp", [](rat_handle h, int64_t v) { h->psw_comp = (int)std::max<int64_t>(100, v); }, [](rat_handle h) -> int64_t { return h->psw_comp; }},
     {"src_tpw", [](rat_handle h, int64_t v) { h->src_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_tpw; }},
+    {"src_pets_tpw", [](rat_handle h, int64_t v) { h->src_pets_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_pets_tpw; }},
 };
 // what the requests amount to on this handle (speculation width, forced pairings)
 static void finish_switches(rat_handle h) {
@@ -339,6 +349,8 @@ extern "C" void rat_destroy(rat_handle h) {
     if (h->h_sol) (void)hipHostFree(h->h_sol);
     if (h->d_census) (void)hipFree(h->d_census);
     if (h->src_mod) (void)hipModuleUnload(h->src_mod);
+    if (h->gsrc_mod) (void)hipModuleUnload(h->gsrc_mod);
+    if (h->h_gsrc_over) (void)hipHostFree(h->h_gsrc_over);
     for (void *q : {(void *)h->d_ce, (void *)h->d_ce_theta, (void *)h->d_ce_cost}) if (q) (void)hipFree(q);      // (d_cez aliases the pinned h_cez)
     if (h->h_ce) (void)hipHostFree(h->h_ce);
     if (h->h_cez) (void)hipHostFree(h->h_cez);
@@ -2891,7 +2903,101 @@ extern "C" rat_rc rat_pets_problem_set(rat_handle h, const rat_gen_problem_desc 
     if (d->tw2 > 0) { auto v = pack_vec(d->tmean2); UPG(tmean2, v); auto w = pack_low(d->tchol2); UPG(tchol2, w); }
 #undef UPG
     h->gen = g; h->gn = n; h->gm = m; h->gN = N; h->have_gen = true;
+    if (h->gsrc_mod) (void)hipModuleUnload(h->gsrc_mod);             // (its parameters went with gen_allocs above)
+    h->gsrc = false; h->gsrc_mod = nullptr; h->gsrc_roll = nullptr; h->d_gsrc_p = nullptr; h->gsrc_np = 0;
     return RAT_OK;
+}
+
+// ---- generative source models: f_stochastic, c, h written by the user (source_model.cpp, rat_rng.h, source_pets.h) ----------------
+static rat_rc gsrc_args_ok(const char *who, int n, int m, int npn, int npu) {
+    if (n < 1 || m < 1) return fail(RAT_ERR_ARG, std::string(who) + ": n, m must be positive");
+    if (npn < 0 || npu < 0) return fail(RAT_ERR_ARG, std::string(who) + ": normals_per_step, uniforms_per_step must not be negative");
+    if (!src_sizes_ok(n, m)) return fail(RAT_ERR_UNSUPPORTED, std::string(who) + ": source models are compiled for n <= 12, m <= 4");
+    return RAT_OK;
+}
+
+extern "C" rat_rc rat_pets_source_check(const char *source, int32_t n, int32_t m, int32_t normals_per_step, int32_t uniforms_per_step) {
+    if (!source) return fail(RAT_ERR_ARG, "null");
+    rat_rc rc = gsrc_args_ok("rat_pets_source_check", n, m, normals_per_step, uniforms_per_step);
+    if (rc) return rc;
+    std::string log;
+    if ((rc = src_compile_gen(source, n, m, normals_per_step, uniforms_per_step, "gfx950", nullptr, &log))) return fail(rc, log);
+    return RAT_OK;
+}
+
+extern "C" rat_rc rat_pets_problem_set_source(rat_handle h, const char *source, int32_t n, int32_t m, int32_t N, int32_t normals_per_step,
+                                              int32_t uniforms_per_step, const double *params, int64_t n_params) {
+    if (!h || !source) return fail(RAT_ERR_ARG, "null");
+    rat_rc rc = gsrc_args_ok("rat_pets_problem_set_source", n, m, normals_per_step, uniforms_per_step);
+    if (rc) return rc;
+    if (N < 1) return fail(RAT_ERR_ARG, "rat_pets_problem_set_source: N must be positive");
+    if (n_params < 0 || (n_params > 0 && !params)) return fail(RAT_ERR_ARG, "rat_pets_problem_set_source: bad parameter array");
+    HIPCHK(hipSetDevice(h->device));
+    // everything that can fail comes before the handle's previous generative problem is touched
+    hipDeviceProp_t pr;
+    HIPCHK(hipGetDeviceProperties(&pr, h->device));
+    std::shared_ptr<const std::vector<char>> code;
+    std::string log;
+    if ((rc = src_compile_gen(source, n, m, normals_per_step, uniforms_per_step, src_arch(pr.gcnArchName), &code, &log))) return fail(rc, log);
+    hipModule_t mod = nullptr;
+    hipFunction_t fr = nullptr;
+    HIPCHK(hipModuleLoadData(&mod, code->data()));
+    if (hipModuleGetFunction(&fr, mod, "rat_src_pets_rollout") != hipSuccess) {
+        (void)hipModuleUnload(mod);
+        return fail(RAT_ERR_HIP, "rat_pets_problem_set_source: the compiled module lacks its kernel");
+    }
+    std::vector<void *> allocs;
+    auto undo = [&](rat_rc r) { free_list(allocs); (void)hipModuleUnload(mod); return r; };
+    if (!h->h_gsrc_over && hipHostMalloc((void **)&h->h_gsrc_over, sizeof(int), hipHostMallocDefault) != hipSuccess) {
+        h->h_gsrc_over = nullptr;
+        return undo(fail(RAT_ERR_HIP, "rat_pets_problem_set_source: hipHostMalloc failed"));
+    }
+    std::vector<double> pv(params, params + n_params);
+    if (pv.empty()) pv.push_back(0.0);
+    const double *dp = nullptr;
+    if ((rc = dev_upload(h, allocs, &dp, pv))) return undo(rc);
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return undo(fail(RAT_ERR_HIP, "rat_pets_problem_set_source: hipStreamSynchronize failed"));
+    free_list(h->gen_allocs);                                          // the previous generative problem's tables (family or source)
+    h->gen_allocs.swap(allocs);
+    if (h->gsrc_mod) (void)hipModuleUnload(h->gsrc_mod);
+    h->gsrc_mod = mod; h->gsrc_roll = fr;
+    h->d_gsrc_p = const_cast<double *>(dp); h->gsrc_np = n_params;
+    h->gsrc_npn = normals_per_step; h->gsrc_npu = uniforms_per_step;
+    memset(&h->gen, 0, sizeof(h->gen));                               // (the family tables are gone; nothing reads them while gsrc holds)
+    h->gn = n; h->gm = m; h->gN = N; h->have_gen = true; h->gsrc = true;
+    return RAT_OK;
+}
+
+extern "C" rat_rc rat_pets_set_params(rat_handle h, const double *params, int64_t n_params) {
+    if (!h) return fail(RAT_ERR_ARG, "null");
+    if (!h->have_gen || !h->gsrc) return fail(RAT_ERR_NO_PROBLEM, "rat_pets_set_params: the handle has no generative source problem");
+    if (n_params != h->gsrc_np) return fail(RAT_ERR_ARG, "rat_pets_set_params: the generative source problem has " + std::to_string(h->gsrc_np) + " parameters");
+    if (n_params > 0 && !params) return fail(RAT_ERR_ARG, "null");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (n_params > 0) HIPCHK(hipMemcpy(h->d_gsrc_p, params, (size_t)n_params * sizeof(double), hipMemcpyHostToDevice));
+    return RAT_OK;
+}
+
+// the rollouts + per-sample means of one compute_cost: the family kernels (launch_pets) or the source model's kernel + pets_mean_kernel
+static void pets_rollouts(rat_handle h, const PetsArgs &a, hipStream_t s) {
+    if (!h->gsrc) { launch_pets(a, s); return; }
+    const long ntraj = a.S * a.K;
+    if (ntraj <= 0) return;
+    SrcPetsArgs sa;
+    sa.x0 = a.x0; sa.controls = a.controls; sa.S = a.S; sa.K = a.K; sa.N = h->gN; sa.use_true = a.use_true; sa.tpw = h->src_pets_tpw;
+    sa.zn = a.zn; sa.zu = a.zu; sa.seed = a.seed; sa.traj0 = a.traj0; sa.traj_cost = a.traj_cost; sa.p = h->d_gsrc_p;
+    sa.overdraw = nullptr;
+    (void)hipHostGetDevicePointer((void **)&sa.overdraw, h->h_gsrc_over, 0);
+    void *args[] = {&sa};
+    (void)hipModuleLaunchKernel(h->gsrc_roll, (unsigned)((ntraj + sa.tpw - 1) / sa.tpw), 1, 1, 64, 1, 1, 0, s, args, nullptr);
+    launch_pets_mean(a, s);
+}
+// after the wait: a step that drew more than the source declared (the flag is cleared before every launch chain)
+static rat_rc gsrc_overdraw(rat_handle h) {
+    if (!h->gsrc || *(volatile int *)h->h_gsrc_over == 0) return RAT_OK;
+    return fail(RAT_ERR_ARG, "generative source model: a step drew more than it declared (normals_per_step = " + std::to_string(h->gsrc_npn) +
+                             ", uniforms_per_step = " + std::to_string(h->gsrc_npu) + "): the overdrawn values were NaN");
 }
 
 extern "C" void rat_pets_initialize(rat_pets_solver *s) {                     // pets.jl:70-74
@@ -2968,7 +3074,23 @@ static rat_rc pets_enqueue_impl(rat_handle h, const double *x0, const double *co
     a.g = h->gen; a.x0 = h->d_pin; a.controls = h->d_pin + XSTR; a.S = S; a.K = K; a.use_true = use_true_model ? 1 : 0;
     a.zn = nullptr; a.zu = nullptr; a.seed = seed; a.traj0 = (long)(sample0 * K); a.traj_cost = h->d_ptraj; a.cost = cost_dev;
     a.wave16 = h->pets_wave16;
-    if (zn) {
+    if (h->gsrc) {                                            // generative source model: each stream it declares, injected or both from the generator
+        const size_t npn = (size_t)h->gsrc_npn, npu = (size_t)h->gsrc_npu;
+        if ((zn || zu) && ((npn > 0 && !zn) || (npu > 0 && !zu)))
+            return fail(RAT_ERR_ARG, "generative source model: injected draws need every declared stream (normals_per_step = " + std::to_string(npn) +
+                                     ", uniforms_per_step = " + std::to_string(npu) + ")");
+        if (zn && npn > 0) {
+            if ((rc = grow(&h->d_pzn, &h->cap_zn, ntraj * N * npn))) return rc;
+            HIPCHK(hipMemcpyAsync(h->d_pzn, zn, ntraj * N * npn * 8, hipMemcpyHostToDevice, h->stream));
+            a.zn = h->d_pzn;
+        }
+        if (zu && npu > 0) {
+            if ((rc = grow(&h->d_pzu, &h->cap_zu, ntraj * N * npu))) return rc;
+            HIPCHK(hipMemcpyAsync(h->d_pzu, zu, ntraj * N * npu * 8, hipMemcpyHostToDevice, h->stream));
+            a.zu = h->d_pzu;
+        }
+        *h->h_gsrc_over = 0;
+    } else if (zn) {
         if ((rc = grow(&h->d_pzn, &h->cap_zn, ntraj * N * n))) return rc;
         HIPCHK(hipMemcpyAsync(h->d_pzn, zn, ntraj * N * n * 8, hipMemcpyHostToDevice, h->stream));
         a.zn = h->d_pzn;
@@ -2979,7 +3101,7 @@ static rat_rc pets_enqueue_impl(rat_handle h, const double *x0, const double *co
         }
     }
     prof_begin(h, RAT_K_PETS, (int64_t)ntraj);
-    launch_pets(a, h->stream);
+    pets_rollouts(h, a, h->stream);
     prof_end(h);
     HIPCHK(hipGetLastError());
     if (cost) HIPCHK(hipMemcpyAsync(cost, h->d_pcost, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
@@ -2992,6 +3114,7 @@ extern "C" rat_rc rat_pets_compute_cost(rat_handle h, const double *x0, const do
     rat_rc rc = pets_enqueue_impl(h, x0, controls, S, K, use_true_model, zn, zu, seed, 0, nullptr);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = gsrc_overdraw(h))) return rc;
     memcpy(cost, h->h_pcost, (size_t)S * sizeof(double));
     return RAT_OK;
 }
@@ -3074,8 +3197,8 @@ extern "C" rat_rc rat_pets_step(rat_handle h, rat_pets_solver *s, const double *
 // enqueued as ONE chain on the handle's stream; mu, Sigma and an error word come back through pinned memory behind ONE host wait.
 // Rollout noise comes from the device generator (seed + iteration, as the host loop keys it); the control normals are the injected
 // stream (read in place from pinned memory) or, zc == nullptr, drawn on the device.  Arithmetic = the host loop's: mu / Sigma bit for bit.
-static bool pets_device_usable(rat_handle h, const rat_pets_solver *s, const double *zn) {
-    return h->pets_device && !zn && s->num_control_samples >= 1 && s->num_control_samples <= PETS_DEV_MAX_S &&
+static bool pets_device_usable(rat_handle h, const rat_pets_solver *s, const double *zn, const double *zu) {
+    return h->pets_device && !zn && !zu && s->num_control_samples >= 1 && s->num_control_samples <= PETS_DEV_MAX_S &&
            s->m <= 4 && s->N <= 1024 && s->num_elite >= 2 && s->num_elite <= s->num_control_samples && s->iter_max >= 1;
 }
 static rat_rc pets_solve_device(rat_handle h, rat_pets_solver *s, const double *x0, int32_t use_true_model, const double *zc, uint64_t seed) {
@@ -3124,6 +3247,7 @@ static rat_rc pets_solve_device(rat_handle h, rat_pets_solver *s, const double *
     PetsArgs a;
     a.g = h->gen; a.x0 = h->d_pin; a.controls = h->d_pin + XSTR; a.S = S; a.K = K; a.use_true = use_true_model ? 1 : 0;
     a.zn = nullptr; a.zu = nullptr; a.traj0 = 0; a.traj_cost = h->d_ptraj; a.cost = h->d_pcost; a.wave16 = h->pets_wave16;
+    if (h->gsrc) *h->h_gsrc_over = 0;
     // sample_1 | rollouts_1 | update_1 + sample_2 | rollouts_2 | ... | update_n : one bookkeeping launch between two rollout launches
     double *const ctrl = h->d_pin + XSTR;
     prof_begin(h, RAT_K_CE, S);
@@ -3133,7 +3257,7 @@ static rat_rc pets_solve_device(rat_handle h, rat_pets_solver *s, const double *
     for (int64_t it = 0; it < IT; ++it) {
         a.seed = seed + (uint64_t)it;
         prof_begin(h, RAT_K_PETS, (int64_t)ntraj);
-        launch_pets(a, h->stream);
+        pets_rollouts(h, a, h->stream);
         prof_end(h);
         const int more = (it + 1 < IT) ? 1 : 0;
         prof_begin(h, RAT_K_CE, S);
@@ -3157,6 +3281,7 @@ static rat_rc pets_solve_device(rat_handle h, rat_pets_solver *s, const double *
     int err = 0;
     memcpy(&err, hp + off_err, sizeof(int));
     if (err) return fail(RAT_ERR_ARG, "Sigma_t is not positive definite (MvNormal would throw)");
+    if ((rc = gsrc_overdraw(h))) return rc;
     memcpy(s->mu, hp + off_mu, nmu * 8);
     memcpy(s->Sigma, hp + off_sg, nsg * 8);
     s->iter_current = IT;
@@ -3169,16 +3294,17 @@ extern "C" rat_rc rat_pets_solve(rat_handle h, rat_pets_solver *s, const double 
     if (!h->have_gen) return fail(RAT_ERR_NO_PROBLEM, "rat_pets_problem_set was not called");
     if (s->N != h->gN || s->m != h->gm) return fail(RAT_ERR_ARG, "solver N / m do not match the problem");
     rat_pets_initialize(s);
-    if (pets_device_usable(h, s, zn)) return pets_solve_device(h, s, x0, use_true_model, zc, seed);
+    if (pets_device_usable(h, s, zn, zu)) return pets_solve_device(h, s, x0, use_true_model, zc, seed);
     if (!zc) return fail(RAT_ERR_UNSUPPORTED, "rat_pets_solve: control normals are drawn on the device only by the device-resident loop (switch pets_device, "
                                               "no injected rollout noise, <= 1024 control samples)");
     const size_t nzc = (size_t)s->num_control_samples * s->N * s->m;
     const size_t ntraj = (size_t)s->num_control_samples * s->num_trajectory_samples;
-    const size_t nzn = ntraj * s->N * h->gn, nzu = ntraj * s->N;
+    // injected draws per iteration: the family's n normals and one selector uniform per (trajectory, step), a source model's declared counts
+    const size_t nzn = ntraj * s->N * (h->gsrc ? (size_t)h->gsrc_npn : (size_t)h->gn), nzu = ntraj * s->N * (h->gsrc ? (size_t)h->gsrc_npu : 1);
     while (s->iter_current < s->iter_max) {
         const int64_t it = s->iter_current;
-        rat_rc rc = rat_pets_step(h, s, x0, use_true_model, zc + it * nzc, zn ? zn + it * nzn : nullptr, (zn && zu) ? zu + it * nzu : nullptr,
-                                  seed + (uint64_t)it, nullptr, nullptr);
+        const double *zu_it = h->gsrc ? (zu ? zu + it * nzu : nullptr) : ((zn && zu) ? zu + it * nzu : nullptr);
+        rat_rc rc = rat_pets_step(h, s, x0, use_true_model, zc + it * nzc, zn ? zn + it * nzn : nullptr, zu_it, seed + (uint64_t)it, nullptr, nullptr);
         if (rc) return rc;
     }
     return RAT_OK;

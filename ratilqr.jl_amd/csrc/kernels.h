@@ -111,6 +111,7 @@ struct PetsArgs {
 #define PETS_SPLIT_MAX_WAVES 1536
 void launch_pets(const PetsArgs &a, hipStream_t s);
 void launch_pets_stage(const double *src, double *dst, long count, hipStream_t s);
+void launch_pets_mean(const PetsArgs &a, hipStream_t s);     // pets_mean_kernel only (reads a.traj_cost, a.S, a.K; writes a.cost)
 
 struct NoisyArgs {              // Monte-Carlo rollouts under process noise (simulate_dynamics with rng)
     ProblemDev pb;

@@ -36,6 +36,7 @@
 
 #include "device_utils.h"
 #include "rat_normal.h"
+#include "rat_philox.h"
 #include "rat_pow.h"
 #include "sweep_dual.h"
 
@@ -3429,19 +3430,7 @@ void launch_gather(const StateDev &st, double *value, int *status, int *iters, i
 // PETS (pets.jl:76-157): stochastic forward rollouts with running cost, 4 trajectories per wavefront (16-lane rows).
 // Noise comes from an injected stream (parity with the oracle, serial semantics) or from Philox4x32-10 on the device.
 // =====================================================================================================
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ double u01(unsigned hi, unsigned lo) {       // 53-bit uniform in [0, 1)
-    return (double)((((unsigned long long)hi << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
-}
+// (philox4x32_10, u01: rat_philox.h)
 
 __global__ __launch_bounds__(64) void pets_rollout_kernel(PetsArgs a) {
     const int row = threadIdx.x >> 4, j = threadIdx.x & 15;
@@ -3957,6 +3946,12 @@ __global__ __launch_bounds__(64) void pets_mean_kernel(PetsArgs a) {
     for (long kk = l; kk < a.K; kk += 64) s += a.traj_cost[ii * a.K + kk];
     s = wave_sum(s);
     if (l == 0) a.cost[ii] = s / (double)a.K;
+}
+
+// the per-sample means alone: after the rollouts of a generative source model (source_pets.h), same summation order as the family's
+void launch_pets_mean(const PetsArgs &a, hipStream_t s) {
+    if (a.S <= 0) return;
+    hipLaunchKernelGGL(pets_mean_kernel, dim3((unsigned)a.S), dim3(64), 0, s, a);
 }
 
 void launch_pets(const PetsArgs &a, hipStream_t s) {

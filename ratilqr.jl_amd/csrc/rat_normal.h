@@ -21,9 +21,13 @@
 // is preserved.
 // ====================================================
 #pragma once
+#if !defined(__HIPCC_RTC__)            // (under hiprtc -- the generative source models, rat_rng.h -- the runtime's own headers provide these)
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
+#else
+typedef unsigned long long uint64_t;   // (hiprtc's runtime header keeps its own in a namespace; the same type)
+#endif
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define RATN_FN __device__ __forceinline__

@@ -25,3 +25,18 @@ struct SrcLinArgs {
     int mode;                 // 0 nominal slots, 1 candidate slots
     const double *p;
 };
+
+// rat_src_pets_rollout (source_pets.h): compute_cost_worker (pets.jl:76-98) of a generative source model, one lane per trajectory
+struct SrcPetsArgs {
+    const double *x0;         // [12]
+    const double *controls;   // [S][N][USTR] padded
+    long S, K;
+    int N, use_true;
+    int tpw;                  // trajectories per wavefront (lanes 0 .. tpw-1 of each 64-lane workgroup work)
+    const double *zn, *zu;    // injected draws ([S*K][N][normals], [S*K][N][uniforms]) or both null (Philox keyed by seed)
+    unsigned long long seed;
+    long traj0;               // global index of this launch's first trajectory (the generator's counter)
+    double *traj_cost;        // [S*K]
+    const double *p;          // the model's parameters
+    int *overdraw;            // set (plain store) when a step draws more than it declared: 1 normals, 2 uniforms
+};

@@ -31,7 +31,8 @@ struct Rtc {
 
 std::mutex g_mu;
 Rtc g_rtc;
-std::map<std::tuple<std::string, int, int, std::string>, std::shared_ptr<const std::vector<char>>> g_cache;
+// key: (source, n, m, kind (0 risk-sensitive, 1 generative), normals per step, uniforms per step, architecture)
+std::map<std::tuple<std::string, int, int, int, int, int, std::string>, std::shared_ptr<const std::vector<char>>> g_cache;
 
 bool rtc_load(std::string *why) {           // (g_mu held)
     if (!g_rtc.tried) {
@@ -68,8 +69,8 @@ std::string src_arch(const char *gcn_arch_name) {
     return out.empty() ? std::string("gfx950") : out;
 }
 
-rat_rc src_compile(const char *source, int n, int m, const std::string &arch, std::shared_ptr<const std::vector<char>> *code,
-                   std::string *log, double *ms, bool *cached) {
+static rat_rc compile_impl(const char *source, int n, int m, int kind, int npn, int npu, const std::string &arch,
+                          std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
     const auto t0 = std::chrono::steady_clock::now();
     auto done = [&](rat_rc rc) {
         if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -77,7 +78,7 @@ rat_rc src_compile(const char *source, int n, int m, const std::string &arch, st
     };
     std::lock_guard<std::mutex> lk(g_mu);
     if (cached) *cached = false;
-    const auto key = std::make_tuple(std::string(source), n, m, arch);
+    const auto key = std::make_tuple(std::string(source), n, m, kind, npn, npu, arch);
     auto it = g_cache.find(key);
     if (it != g_cache.end()) {
         if (code) *code = it->second;
@@ -86,19 +87,25 @@ rat_rc src_compile(const char *source, int n, int m, const std::string &arch, st
     }
     std::string why;
     if (!rtc_load(&why)) { if (log) *log = why; return done(RAT_ERR_UNSUPPORTED); }
-    // the user's source between the AD header and the kernels; #line makes the compiler's messages name lines of the user's text
-    const std::string text = std::string("#include \"source_args.h\"\n#include \"rat_ad.h\"\n#line 1 \"model.hip\"\n") + source +
-                             "\n#line 1 \"source_kernels.h\"\n#include \"source_kernels.h\"\n";
-    const char *hdr[] = {k_embed_layout_h, k_embed_source_args_h, k_embed_rat_ad_h, k_embed_source_kernels_h};
-    const char *hdr_names[] = {"layout.h", "source_args.h", "rat_ad.h", "source_kernels.h"};
+    // the user's source between the AD and rat_rng headers and the kernels (a source that defines all four functions compiles as either
+    // kind); #line makes the compiler's messages name lines of the user's text.  A generative source does not define rat_user_f:
+    // source_kernels.h is not part of its text
+    const std::string text = std::string("#include \"source_args.h\"\n#include \"rat_ad.h\"\n#include \"rat_rng.h\"\n#line 1 \"model.hip\"\n") +
+                             source + (kind == 0 ? "\n#line 1 \"source_kernels.h\"\n#include \"source_kernels.h\"\n"
+                                                 : "\n#line 1 \"source_pets.h\"\n#include \"source_pets.h\"\n");
+    const char *hdr[] = {k_embed_layout_h, k_embed_source_args_h, k_embed_rat_ad_h, k_embed_source_kernels_h, k_embed_rat_normal_h,
+                         k_embed_rat_philox_h, k_embed_rat_rng_h, k_embed_source_pets_h};
+    const char *hdr_names[] = {"layout.h", "source_args.h", "rat_ad.h", "source_kernels.h", "rat_normal.h", "rat_philox.h", "rat_rng.h",
+                               "source_pets.h"};
     hiprtcProgram prog = nullptr;
-    if (g_rtc.create(&prog, text.c_str(), "model.hip", 4, hdr, hdr_names) != HIPRTC_SUCCESS) {
+    if (g_rtc.create(&prog, text.c_str(), "model.hip", 8, hdr, hdr_names) != HIPRTC_SUCCESS) {
         if (log) *log = "hiprtcCreateProgram failed";
         return done(RAT_ERR_ARG);
     }
     const std::string dn = "-DRAT_N=" + std::to_string(n), dm = "-DRAT_M=" + std::to_string(m), oa = "--offload-arch=" + arch;
-    const char *opts[] = {"-O3", "-std=c++17", dn.c_str(), dm.c_str(), oa.c_str()};
-    const hiprtcResult rc = g_rtc.compile(prog, 5, opts);
+    const std::string dpn = "-DRAT_PETS_NORMALS=" + std::to_string(npn), dpu = "-DRAT_PETS_UNIFORMS=" + std::to_string(npu);
+    const char *opts[] = {"-O3", "-std=c++17", dn.c_str(), dm.c_str(), oa.c_str(), dpn.c_str(), dpu.c_str()};
+    const hiprtcResult rc = g_rtc.compile(prog, 7, opts);
     size_t ls = 0;
     std::string lg;
     if (g_rtc.log_size(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
@@ -125,4 +132,14 @@ rat_rc src_compile(const char *source, int n, int m, const std::string &arch, st
     if (code) *code = obj;
     if (log) *log = lg;
     return done(RAT_OK);
+}
+
+rat_rc src_compile(const char *source, int n, int m, const std::string &arch, std::shared_ptr<const std::vector<char>> *code,
+                   std::string *log, double *ms, bool *cached) {
+    return compile_impl(source, n, m, 0, 0, 0, arch, code, log, ms, cached);
+}
+
+rat_rc src_compile_gen(const char *source, int n, int m, int npn, int npu, const std::string &arch,
+                       std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
+    return compile_impl(source, n, m, 1, npn, npu, arch, code, log, ms, cached);
 }

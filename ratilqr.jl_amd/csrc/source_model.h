@@ -8,11 +8,15 @@
 
 #include "../../include/ratilqr.h"
 
-// Compiles the user's source behind the embedded headers (rat_ad.h, source_args.h, layout.h, source_kernels.h) for `arch` with
-// -O3 -std=c++17 -DRAT_N=n -DRAT_M=m.  RAT_OK: *code holds the code object (shared with the cache).  RAT_ERR_ARG: *log holds the
+// Compiles the user's source behind the embedded headers (rat_ad.h, rat_rng.h, source_args.h, layout.h; source_kernels.h after it) for
+// `arch` with -O3 -std=c++17 -DRAT_N=n -DRAT_M=m -DRAT_PETS_NORMALS=0 -DRAT_PETS_UNIFORMS=0.  RAT_OK: *code holds the code object (shared with the cache).  RAT_ERR_ARG: *log holds the
 // compiler's log.  RAT_ERR_UNSUPPORTED: hiprtc is not available in this process.  *ms (if not null): wall time of the call; *cached:
 // whether the code object came from the cache.
 rat_rc src_compile(const char *source, int n, int m, const std::string &arch, std::shared_ptr<const std::vector<char>> *code,
                    std::string *log, double *ms = nullptr, bool *cached = nullptr);
+// The same for a generative source (PETS): source_pets.h after it, -DRAT_PETS_NORMALS=npn -DRAT_PETS_UNIFORMS=npu.  Cached apart from
+// risk-sensitive compiles of the same text.
+rat_rc src_compile_gen(const char *source, int n, int m, int npn, int npu, const std::string &arch,
+                       std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
 // The offload-arch string for the device's reported gcnArchName (an xnack+ feature is never passed on).
 std::string src_arch(const char *gcn_arch_name);

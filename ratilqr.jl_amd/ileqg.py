@@ -27,15 +27,16 @@ class Context:
     """One rat_handle bound to one problem (device buffers sized for max_batch samples x spec_eps step sizes)."""
 
     def __init__(self, problem, opts: nv.IleqgOpts | None = None, max_batch=1, spec_eps=1, device=0):
+        """problem None: a handle without an iLEQG problem (PETS on a generative source model sets its own)."""
         L = nv.lib()
         self.problem = problem
-        self.n, self.m, self.N = problem.n, problem.m, problem.N
+        self.n, self.m, self.N = (problem.n, problem.m, problem.N) if problem is not None else (0, 0, 0)
         self.max_batch, self.spec_eps, self.device = int(max_batch), int(spec_eps), int(device)
         self.h = C.c_void_p()
         nv.check(L.rat_create(C.byref(opts) if opts is not None else None, self.max_batch, self.spec_eps,
                               self.device, C.byref(self.h)))
         self._fin = weakref.finalize(self, L.rat_destroy, self.h)
-        self._keep = self._upload(problem)
+        self._keep = self._upload(problem) if problem is not None else None
 
     def _upload(self, problem):
         if getattr(problem, "model", 0) == MODEL_SOURCE:            # user-written f, c, h: compiled at run time (rat_problem_set_source)

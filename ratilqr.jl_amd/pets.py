@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _native as nv
 from .ileqg import Context
+from .problems import DeviceGenerativeSourceProblem
 
 
 def _cm3(a):
@@ -69,11 +70,22 @@ class CrossEntropyDirectOptimizationSolver:                       # a.k.a. "PETS
 
     def context(self, problem):
         if self._ctx is None or self._ctx[0] is not problem:
-            ctx = Context(problem.lq, device=self.device)
-            g, keep = make_gen_desc(problem)
-            nv.check(nv.lib().rat_pets_problem_set(ctx.h, C.byref(g)))
+            if isinstance(problem, DeviceGenerativeSourceProblem):     # user-written f_stochastic, c, h (rat_pets_problem_set_source)
+                ctx = Context(None, device=self.device)                # (a handle without an iLEQG problem)
+                keep = nv.pets_set_source(ctx.h, problem)
+            else:
+                ctx = Context(problem.lq, device=self.device)
+                g, keep = make_gen_desc(problem)
+                nv.check(nv.lib().rat_pets_problem_set(ctx.h, C.byref(g)))
             self._ctx = (problem, ctx, keep)
         return self._ctx[1]
+
+    def set_params(self, problem, params):
+        """New parameter values of a generative source problem on this solver's handle (rat_pets_set_params: the same count, no
+        recompilation).  `problem.params` is left as it is: the handle uploads it again if it is bound to the problem anew."""
+        ctx = self.context(problem)
+        p = nv.f64(np.atleast_1d(params))
+        nv.check(nv.lib().rat_pets_set_params(ctx.h, nv.P(p) if p.size else None, C.c_int64(p.size)))
 
 
 def make_gen_desc(problem):
@@ -93,8 +105,14 @@ def initialize_(direct_solver):                                   # initialize! 
 
 
 def draw_noise(problem, rng, S, K, use_true_model=False):
-    """The N(0,1)/U[0,1) draws compute_cost_serial consumes, in its order (sample, trajectory, step, component)."""
+    """The N(0,1)/U[0,1) draws compute_cost_serial consumes, in its order (sample, trajectory, step, component).  A generative source
+    problem: S*K*N*normals_per_step normals and S*K*N*uniforms_per_step uniforms, each None where its count is 0."""
     n, N = problem.n, problem.N
+    if isinstance(problem, DeviceGenerativeSourceProblem):
+        npn, npu = problem.normals_per_step, problem.uniforms_per_step
+        zn = rng.standard_normal(S * K * N * npn) if npn > 0 else None
+        zu = rng.random(S * K * N * npu) if npu > 0 else None
+        return zn, zu
     if use_true_model and problem.tw2 > 0:
         zu = rng.random(S * K * N)
         zn = rng.standard_normal(S * K * N * n)
@@ -114,7 +132,7 @@ def compute_cost_serial(direct_solver, problem, x, control_sequence_array, rng, 
     zn = zu = None
     if seed is None:
         zn, zu = streams if streams is not None else draw_noise(problem, rng, S, K, use_true_model)
-        zn = nv.f64(zn)
+        zn = None if zn is None else nv.f64(zn)
         zu = None if zu is None else nv.f64(zu)
     cost = np.zeros(S)
     nv.check(nv.lib().rat_pets_compute_cost(ctx.h, nv.P(nv.f64(x)), nv.P(ctrl), C.c_int64(S), C.c_int64(K), int(use_true_model),
@@ -134,7 +152,7 @@ def compute_cost_worker(direct_solver, problem, x, u_array, rng, use_true_model=
     zn = zu = None
     if seed is None:
         zn, zu = streams if streams is not None else draw_noise(problem, rng, 1, K, use_true_model)
-        zn = nv.f64(zn)
+        zn = None if zn is None else nv.f64(zn)
         zu = None if zu is None else nv.f64(zu)
     cost = np.zeros(1)
     nv.check(nv.lib().rat_pets_compute_cost(ctx.h, nv.P(nv.f64(x)), nv.P(ctrl), C.c_int64(1), C.c_int64(K), int(use_true_model),
@@ -164,7 +182,7 @@ def step_(direct_solver, problem, x, rng, use_true_model=False, verbose=False, s
     zn = zu = None
     if seed is None:
         zn, zu = draw_noise(problem, rng, S, K, use_true_model)
-        zn, zu = nv.f64(zn), (None if zu is None else nv.f64(zu))
+        zn, zu = (None if zn is None else nv.f64(zn)), (None if zu is None else nv.f64(zu))
     ctrl, cost = np.zeros((S, N, m)), np.zeros(S)
     nv.check(nv.lib().rat_pets_step(ctx.h, C.byref(direct_solver.c), nv.P(nv.f64(x)), int(use_true_model), nv.P(zc), nv.P(zn), nv.P(zu),
                                     C.c_uint64(0 if seed is None else int(seed)), nv.P(ctrl), nv.P(cost)))

@@ -284,3 +284,30 @@ class LQGenerativeProblem(FiniteHorizonGenerativeOptimalControlProblem):
         t.update(l1u=self.l1u, noise_kind=self.noise_kind, nmean=_colmajor(self.nmean), nchol=_colmajor(self.nchol),
                  nlo=self.nlo, nhi=self.nhi, tw2=self.tw2, tmean2=_colmajor(self.tmean2), tchol2=_colmajor(self.tchol2))
         return t
+
+
+class DeviceGenerativeSourceProblem(FiniteHorizonGenerativeOptimalControlProblem):
+    """FiniteHorizonGenerativeOptimalControlProblem(f_stochastic, c, h, N) with f_stochastic, c, h written as HIP device code (PETS,
+    include/ratilqr.h "generative source models"): the library compiles `source` at run time and runs the stochastic rollouts on the GPU.
+
+    source: defines rat_user_f_stochastic(x, u, rng, use_true_model, xn, p), rat_user_c / rat_user_h templated on the scalar type
+    (RAT_N = n, RAT_M = m); rng.normal() / rng.uniform() draw at most normals_per_step (default n) / uniforms_per_step values per step;
+    params: the doubles the device functions read through `p` (CrossEntropyDirectOptimizationSolver.set_params replaces them on the
+    solver's handle without recompiling)."""
+
+    model = MODEL_SOURCE
+
+    def __init__(self, source, n, m, N, params=None, normals_per_step=None, uniforms_per_step=0):
+        self.source, self.n, self.m, self.N = str(source), int(n), int(m), int(N)
+        self.params = np.zeros(0) if params is None else np.ascontiguousarray(np.atleast_1d(params), dtype=np.float64)
+        self.normals_per_step = self.n if normals_per_step is None else int(normals_per_step)
+        self.uniforms_per_step = int(uniforms_per_step)
+
+    def f_stochastic(self, x, u, rng, use_true_model=False):
+        raise NotImplementedError("a source model's f_stochastic runs on the device only (compute_cost)")
+
+    def c(self, k, x, u):
+        raise NotImplementedError("a source model's c runs on the device only (compute_cost)")
+
+    def h(self, x):
+        raise NotImplementedError("a source model's h runs on the device only (compute_cost)")
