@@ -508,6 +508,12 @@ int32_t rat_get_path(rat_handle h, int64_t B);
  *                            critical path of one-shot callers -- receding-horizon solves, a single rat_ileqg_solve               (1)
  *   materialize     0 / 1    one-wavefront-per-sample kernel, LQ family, time-invariant cost: tile records written by the
  *                            rollouts and loaded by the sweeps (SURVEY 8d's wording) instead of formed in registers      (0)
+ *   lq_replay       0 / 1    one-wavefront-per-sample kernel, LQ family with kappa = 0, diagonal time-invariant W and cost: every full paired
+ *                            gain sweep records its Riccati matrices (-M^-1, [G | H + mu I]: 2 KB per step and sample) and a later pair
+ *                            that would recompute them -- the evaluation of the gains it solved beside the next gain sweep, both at
+ *                            mu = 0 -- runs only the vector half of both recursions over the record (csrc/sweep_dual.h:
+ *                            replay_dual_body); identical outputs                                                        (1)
+ *   lq_replay_count (read)   sweeps of this handle replayed so far, two per replayed pair (rat_debug_set clears it)
  *   fly             0 / 1    round-based path, E > 1: line-search candidates without tile records                         (1)
  *   fly_multi       0 / 1    ... and all candidates of a sample rolled out by one wavefront                               (1)
  *   dual            0 / 1    round-based path: candidate 0 paired with the next gain sweep in one wavefront              (E > 1)

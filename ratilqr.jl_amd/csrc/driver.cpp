@@ -60,6 +60,10 @@ struct rat_handle_s {
     int n_cu = 256;                  // compute units of the device
     long long *d_xw = nullptr;       // solve_block_psw_kernel, two workgroups per sample: [Bmax][XW_STRIDE] hand-over words (kernels.hip)
     int *d_duo_count = nullptr;      // ... samples that ran as a pair so far
+    bool lq_replay = true;           // solve_fused_kernel, LQ family, kappa = 0, diagonal W: later sweeps replay the Riccati matrices of the last full gain
+                                     // sweep (RecDev, kernels.h; switch lq_replay)
+    RecDev rec = {};                 // ... its per-sample words (st_allocs) and the record (rec.m: rec_cap doubles, allocated by the first batch that uses it)
+    size_t rec_cap = 0;
     unsigned xepoch = 0;             // ... launches so far (the hand-over words carry it: nothing to clear between launches)
     int *d_census = nullptr;         // solve_block_kernel's per-CU workgroup tickets (two-wave geometry: which SIMD pair a workgroup keeps)
     bool block_shape = true;         // RATILQR_BLOCK_SHAPE=0: plain two-wave workgroups, placement left to the dispatcher
@@ -246,6 +250,9 @@ static const DebugSwitch debug_switches[] = {
     {"prl_cuts", [](rat_handle, int64_t) {}, [](rat_handle h) -> int64_t { return h->prl_last; }},
     {"psw_duo_count", [](rat_handle h, int64_t) { if (h->d_duo_count) { (void)hipStreamSynchronize(h->stream); (void)hipMemset(h->d_duo_count, 0, sizeof(int)); } },
      [](rat_handle h) -> int64_t { int c = 0; if (h->d_duo_count) { (void)hipStreamSynchronize(h->stream); (void)hipMemcpy(&c, h->d_duo_count, sizeof(int), hipMemcpyDeviceToHost); } return c; }},
+    {"lq_replay", [](rat_handle h, int64_t v) { h->lq_replay = (v != 0); }, [](rat_handle h) -> int64_t { return h->lq_replay; }},
+    {"lq_replay_count", [](rat_handle h, int64_t) { if (h->rec.count) { (void)hipStreamSynchronize(h->stream); (void)hipMemset(h->rec.count, 0, sizeof(int)); } },
+     [](rat_handle h) -> int64_t { int c = 0; if (h->rec.count) { (void)hipStreamSynchronize(h->stream); (void)hipMemcpy(&c, h->rec.count, sizeof(int), hipMemcpyDeviceToHost); } return c; }},
     {"psw_acl", [](rat_handle h, int64_t v) { h->psw_acl = (v != 0); }, [](rat_handle h) -> int64_t { return h->psw_acl; }},
     {"psw_comp", [](rat_handle h, int64_t v) { h->psw_comp = (int)std::max<int64_t>(100, v); }, [](rat_handle h) -> int64_t { return h->psw_comp; }},
     {"src_tpw", [](rat_handle h, int64_t v) { h->src_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_tpw; }},
@@ -337,6 +344,7 @@ extern "C" void rat_destroy(rat_handle h) {
     free_list(h->pb_allocs);
     free_list(h->st_allocs);
     free_list(h->gen_allocs);
+    if (h->rec.m) (void)hipFree(h->rec.m);
     for (double *q : {h->d_pin, h->d_pzn, h->d_pzu, h->d_ptraj, h->d_pcost, h->d_pmu, h->d_psig}) if (q) (void)hipFree(q);
     if (h->d_perr) (void)hipFree(h->d_perr);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
@@ -419,8 +427,15 @@ static bool host_inv(int n, const double *A, double *Ainv) {
 
 // one tile bundle per sample (the single-launch E = 1 kernels) or one per slot (round-based path; always for source problems)
 static bool want_alias(const rat_handle h) { return h->fused && h->pb.model != RAT_MODEL_SOURCE; }
+static void free_record(rat_handle h) {
+    if (h->rec.m) { (void)hipStreamSynchronize(h->stream); (void)hipFree(h->rec.m); }
+    h->rec = RecDev{};
+    h->rec_cap = 0;
+}
+
 static rat_rc alloc_state(rat_handle h) {
     free_list(h->st_allocs);
+    free_record(h);
     StateDev &st = h->st;
     h->wide = false;
     const int N = h->N, E = h->E, B = h->Bmax;
@@ -445,6 +460,7 @@ static rat_rc alloc_state(rat_handle h) {
     AL(st.value_c, (size_t)B * E); AL(st.d_c, (size_t)B * E); AL(st.flag_c, (size_t)B * E); AL(st.acc0, B);
     AL(st.counters, 2 * CTR_RING); AL(st.sink, (size_t)SINK_SLOTS * 64);
     AL(h->d_xw, (size_t)B * XW_STRIDE); AL(h->d_duo_count, 1);
+    AL(h->rec.mu, B); AL(h->rec.rprod, B); AL(h->rec.rexp, B); AL(h->rec.gen, B); AL(h->rec.lgen, (size_t)2 * B); AL(h->rec.count, 1);
     h->xepoch = 0;
     st.hist = nullptr; st.hist_cap = 0;
     AL(h->d_x0, XSTR); AL(h->d_u0, (size_t)N * USTR); AL(h->d_theta, B); AL(h->d_val, B);
@@ -467,6 +483,7 @@ static rat_rc alloc_state(rat_handle h) {
     HIPCHK(hipMemsetAsync(h->d_dump, 0, (size_t)(N + 1) * DUMP_STRIDE * sizeof(double), h->stream));      // (diagnostic builds count into it)
     HIPCHK(hipMemsetAsync(h->d_xw, 0, (size_t)B * XW_STRIDE * sizeof(long long), h->stream));
     HIPCHK(hipMemsetAsync(h->d_duo_count, 0, sizeof(int), h->stream));
+    HIPCHK(hipMemsetAsync(h->rec.count, 0, sizeof(int), h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return RAT_OK;
 }
@@ -474,6 +491,7 @@ static rat_rc alloc_state(rat_handle h) {
 // ---- problems beyond n <= 12, m <= 4: tables at their own size for wide.hip ---------------------------
 static rat_rc alloc_state_wide(rat_handle h) {
     free_list(h->st_allocs);
+    free_record(h);
     h->d_xw = nullptr; h->d_duo_count = nullptr;
     memset(&h->st, 0, sizeof(h->st));
     const int N = h->N, n = h->n, m = h->m, B = h->Bmax;
@@ -892,6 +910,7 @@ static SweepArgs sweep_args(rat_handle h, const StateDev &st, int mode) {
     SweepArgs a;
     a.st = st; a.pb = h->pb; a.op = h->opd; a.mode = mode; a.k_first = 0; a.dl_in = nullptr; a.mu_op = 0.0; a.op_out = nullptr; a.dump = nullptr;
     a.fly = 0; a.prune = 0;
+    memset(&a.rec, 0, sizeof(a.rec));
 #if defined(RAT_DIAG) || defined(RAT_DIAG_PHASES)
     a.dump = h->d_dump;
 #endif
@@ -1208,6 +1227,17 @@ static rat_rc run_batch(rat_handle h, const double *theta_dev, int B, const Batc
         fa.occ2 = (path == PATH_FUSED && h->fused_dual &&
                    (h->fused_occ2 > 0 ? B >= h->fused_occ2 : (h->fused_occ2 < 0 && h->pb.model == 1 && !h->materialize && B > 4 * (int64_t)h->n_cu))) ? 1 : 0;
         fa.mat = h->materialize ? 1 : 0;
+        // the Riccati-matrix record of the fused solve (launch_solve_fused applies it where the problem allows: LQ family, kappa = 0, diagonal W)
+        if (path == PATH_FUSED && h->lq_replay && fa.dual && !fa.occ2 && !fa.mat && h->pb.model == 1 && h->pb.kappa == 0.0 && h->pb.W_diag &&
+            !h->pb.W_tv && !h->pb.cost_tv && st.N <= ROLLIN_NST) {
+            const size_t need = (size_t)B * st.N * REC_STEP;
+            if (need > h->rec_cap) {
+                if (h->rec.m) { HIPCHK(hipStreamSynchronize(h->stream)); HIPCHK(hipFree(h->rec.m)); h->rec.m = nullptr; h->rec_cap = 0; }
+                HIPCHK(hipMalloc((void **)&h->rec.m, need * sizeof(double)));
+                h->rec_cap = need;
+            }
+            fa.sw.rec = h->rec;
+        }
         fa.theta_in = theta_dev;
         fa.out_value = out.value; fa.out_status = out.status; fa.out_iters = out.iters; fa.out_ls = out.ls;
         fa.out_cost = out.cost; fa.kl_bound = out.kl_bound;

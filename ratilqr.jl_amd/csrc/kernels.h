@@ -4,6 +4,21 @@
 
 #include "layout.h"
 
+// Riccati-matrix record of the one-wavefront-per-sample solve (solve_fused_kernel, LQ family, kappa = 0, diagonal time-invariant W): for such a
+// problem A, B, Q, R, P, W do not depend on the trajectory, so every later paired sweep at the same mu runs the matrix half of the recursions
+// of the last full paired gain sweep again, bit for bit.  That sweep records per step what the vector half reads from it; later pairs replay
+// only the vector half (sweep_dual.h: replay_dual_body).  Null m: no record (every sweep runs in full).
+#define REC_STEP 256       /* doubles per step: lane-major, 4 per lane = -M^-1 (3 accumulator registers) and [G | H + mu I] (register 3 of F) */
+struct RecDev {
+    double *m;             // [B][N][REC_STEP]
+    double *mu;            // [B] mu of the recorded pass (bitwise: the replay gate)
+    double *rprod;         // [B] the recorded pass's running product of the pivot determinants ...
+    int *rexp;             // [B] ... and its exponent sum (logdet(W M): identical for every sweep that replays the record)
+    int *gen;              // [B] generation of the valid record (> 0), or minus the last one (<= 0: none)
+    int *lgen;             // [B][2] record generation the gains of each half of L / dl were solved from (0: none)
+    int *count;            // sweeps replayed so far (switch lq_replay_count)
+};
+
 struct SweepArgs {
     StateDev st;
     ProblemDev pb;
@@ -21,6 +36,7 @@ struct SweepArgs {
                            // Hessian of a step are formed in the sweep from x_t and the problem tables
     int prune;             // round-based path, E > 1: mode 7 publishes whether candidate 0 is the line search's choice (StateDev.acc0); mode 1
                            // launches of candidates 1 .. E-1 poll it and stop (sweep_kernel<.., PRUNE>)
+    RecDev rec;            // solve_fused_kernel<.., RPL>: the record / replay of the Riccati matrices (m null elsewhere)
 };
 
 // the time-parallel sweep (psweep.h): P waves over P + 1 horizon segments
@@ -78,6 +94,7 @@ struct FusedArgs {         // solve_fused_kernel: one persistent wavefront per s
     unsigned xepoch;
     long long *xw;
     int *duo_count;
+    long long pad_;                    // (sizeof(FusedArgs) stays a whole number of 64-B lines: solve_block_psw_kernel's kernarg_warm)
 };
 #define XW_STRIDE 24                   /* 64-bit words per sample: [0] pair word, [8] role A's posts, [16] role B's posts (64 B apart) */
 #define CENSUS_SLOTS 4096              /* (XCC_ID, SE_ID, SH_ID, CU_ID) of HW_REG_HW_ID / HW_REG_XCC_ID: 4 + 3 + 1 + 4 bits */

@@ -115,7 +115,9 @@ __device__ __forceinline__ void load_tile(TileRegs &tr, const double *__restrict
 // wls: this wavefront's LDS scratch (WLS_SWEEP doubles).
 // SWZ: the elimination's row exchange through the LDS crossbar (ds_swizzle) instead of vector-ALU lane swaps: identical values, fewer
 // vector instructions, longer latency -- for the kernel that runs two samples per SIMD, which is short of issue slots, not of latency.
-template <bool GAIN, bool DUMP, int WM, bool HASL, int SWZ = 0, int FLY = 0, bool PRUNE = false>
+// REC (gain sweeps of solve_fused_kernel<.., RPL>): the gains this sweep writes are not solved from the Riccati-matrix record (SweepArgs.rec):
+// the half they go to loses its record generation.
+template <bool GAIN, bool DUMP, int WM, bool HASL, int SWZ = 0, int FLY = 0, bool PRUNE = false, bool REC = false>
 __device__ __forceinline__ void sweep_body(const SweepArgs &a, const int tid, double *const wls) {
     int lane_ = threadIdx.x & 63;
     asm volatile("" : "+v"(lane_));      // opaque per phase: keeps the per-lane constants of one phase from being shared with
@@ -474,6 +476,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs &a, const int tid, do
         for (int q = 0; q < 6; ++q) a.dump[blockIdx.x * 8 + q] = (double)dg_acc[q];
 #endif
     const double tot = sweep_scalars(wave_sum(racc), coef, rprod, rexp, theta != 0.0);
+    if (REC && l == 12) a.rec.lgen[2 * b + osel] = 0;
     if (l == 12) {
         const double s0 = 0.5 * v[3] + tot;
         if (a.mode == 1) {
@@ -2542,7 +2545,10 @@ __device__ __forceinline__ void gather_body(const StateDev &st, const int b, dou
 // 2 KB of LDS per wave) -- the direct test of "hide a wave's dependency stalls with a second sample" for batches beyond one per SIMD.
 // MAT: the tile-free geometry with its tile records put back (rollouts write them, sweeps load them): the materialised formulation SURVEY 8d
 // words its byte model on, kept as a measured variant (bit-identical: fx_diag gives a record the bits the fly sweeps form in registers).
-template <int MODEL, bool CTV, int WM, bool DUALF, bool STG, bool OCC2 = false, bool MAT = false>
+// RPL (headline geometry, kappa = 0, diagonal W; switch lq_replay): every full paired gain sweep records its Riccati matrices (SweepArgs.rec)
+// and a later pair that would recompute them -- the evaluation of the gains it solved beside the gain sweep at the same mu -- replays the
+// record (replay_dual_body, sweep_dual.h: bit-identical; a pair the replay refuses runs in full).
+template <int MODEL, bool CTV, int WM, bool DUALF, bool STG, bool OCC2 = false, bool MAT = false, bool RPL = false>
 __global__ __launch_bounds__(64, OCC2 ? 2 : 1) void solve_fused_kernel(FusedArgs fa) {
     const int b = blockIdx.x;
     const StateDev &st = fa.sw.st;
@@ -2562,7 +2568,10 @@ __global__ __launch_bounds__(64, OCC2 ? 2 : 1) void solve_fused_kernel(FusedArgs
     constexpr int FLYF = (MODEL == 1 && ((DUALF && STG && !OCC2) || (OCC2 && !DUALF && !STG)) && !MAT) ? (CTV ? 2 : 1) : 0;
     constexpr bool NT = FLYF != 0;
     // the sample's own wave initialises its state and, at the end, writes its outputs: a batch is ONE launch
-    if (threadIdx.x == 0) init_state_body(st, fa.sw.op, fa.theta_in, b);
+    if (threadIdx.x == 0) {
+        init_state_body(st, fa.sw.op, fa.theta_in, b);
+        if (RPL) { fa.sw.rec.gen[b] = 0; fa.sw.rec.lgen[2 * b] = 0; fa.sw.rec.lgen[2 * b + 1] = 0; }     // no record yet
+    }
     PHASE_FENCE();
     {
         if (NT && fa.init_x) {
@@ -2576,7 +2585,7 @@ __global__ __launch_bounds__(64, OCC2 ? 2 : 1) void solve_fused_kernel(FusedArgs
         PHASE_MARK();
         if (DUALF) {
             SweepArgs sa = fa.sw; sa.mode = 6;
-            sweep_dual_body<WM, false, FLYF>(sa, b, wls);
+            sweep_dual_body<WM, false, FLYF, RPL>(sa, b, wls);
             PHASE_MARK();
             PHASE_FENCE();
             if (threadIdx.x == 0) commit_init_body(st, b);
@@ -2596,7 +2605,7 @@ __global__ __launch_bounds__(64, OCC2 ? 2 : 1) void solve_fused_kernel(FusedArgs
         if (__builtin_amdgcn_readfirstlane(v_stat) != ST_RUNNING) break;
         if (!__builtin_amdgcn_readfirstlane(v_act)) {        // step!: solve_approximate_dp!  (ileqg.jl:598-613)
             SweepArgs sa = fa.sw; sa.mode = 0;
-            sweep_body<true, false, WM, false, OCC2 ? OCC2_SWZ : 0, FLYF>(sa, b, wls);
+            sweep_body<true, false, WM, false, OCC2 ? OCC2_SWZ : 0, FLYF, false, RPL>(sa, b, wls);
             PHASE_MARK();
             PHASE_FENCE();
             PHASE_MARK();
@@ -2618,7 +2627,7 @@ __global__ __launch_bounds__(64, OCC2 ? 2 : 1) void solve_fused_kernel(FusedArgs
             }
             if (pair) {
                 SweepArgs sa = fa.sw; sa.mode = 7;
-                sweep_dual_body<WM, true, FLYF>(sa, b, wls);
+                if (!(RPL && replay_dual_body(sa, b, wls))) sweep_dual_body<WM, true, FLYF, RPL>(sa, b, wls);
             } else {
                 SweepArgs sa = fa.sw; sa.mode = 1;
                 sweep_body<false, false, WM, true, OCC2 ? OCC2_SWZ : 0, FLYF>(sa, b, wls);
@@ -2642,9 +2651,12 @@ void launch_solve_fused(const FusedArgs &fa, hipStream_t s) {
     const dim3 grid(B), block(64);
     const int wm = fa.sw.pb.W_tv ? 1 : (fa.sw.pb.W_diag ? 2 : 0);
     const bool stg = fa.sw.pb.model == 1 && fa.sw.st.N <= ROLLIN_NST;
+    // the record / replay of the Riccati matrices (RecDev): LQ family, kappa = 0, diagonal time-invariant W, time-invariant cost, paired sweeps
+    const bool rpl = fa.sw.rec.m && fa.dual && stg && fa.sw.pb.model == 1 && fa.sw.pb.kappa == 0.0 && !fa.sw.pb.cost_tv && wm == 2;
 #define FUSED_LAUNCH(M, C, W) do { \
         if (fa.occ2) hipLaunchKernelGGL((solve_fused_kernel<M, C, W, false, false, true>), grid, block, 0, s, fa); \
         else if (fa.mat && fa.dual && stg && M == 1 && !C) hipLaunchKernelGGL((solve_fused_kernel<1, false, W, true, true, false, true>), grid, block, 0, s, fa); \
+        else if (rpl && M == 1 && !C && W == 2) hipLaunchKernelGGL((solve_fused_kernel<1, false, 2, true, true, false, false, true>), grid, block, 0, s, fa); \
         else if (fa.dual && stg && M == 1) hipLaunchKernelGGL((solve_fused_kernel<M, C, W, true, M == 1>), grid, block, 0, s, fa); \
         else hipLaunchKernelGGL((solve_fused_kernel<M, C, W, true, false>), grid, block, 0, s, fa); } while (0)
     if (fa.sw.pb.model == 1) {

@@ -52,6 +52,22 @@ struct DTile {
     double xj;             // FLY: x_t[j] of this lane's column
 };
 
+// End of a recording gain pass (SweepArgs.rec, one lane): the record becomes the sample's valid one under a new generation -- which the gains the
+// pass wrote to L / dl half `half` carry -- or, if the pass failed or met a non-finite value (bad), no record is valid and that half carries none.
+__device__ __forceinline__ void rec_close(const RecDev &rc, const int b, const int half, const bool bad, const double mu, const double rprod, const int rexp) {
+    const int g0 = rc.gen[b], gabs = g0 < 0 ? -g0 : g0, gnew = gabs + 1;
+    if (bad) {
+        rc.gen[b] = -gabs;
+        rc.lgen[2 * b + half] = 0;
+    } else {
+        rc.gen[b] = gnew;
+        rc.mu[b] = mu;
+        rc.rprod[b] = rprod;
+        rc.rexp[b] = rexp;
+        rc.lgen[2 * b + half] = gnew;
+    }
+}
+
 // HASL: recursion A evaluates a given policy (mode 7); false for initialize!'s open-loop sweep (mode 6: all gains zero, nothing to load)
 template <bool HASL, int FLY = 0>
 __device__ __forceinline__ void dload(DTile &tr, const double *__restrict__ tp, int lx, int l, int j,
@@ -79,7 +95,8 @@ __device__ __forceinline__ void dload(DTile &tr, const double *__restrict__ tp, 
 // The elimination rounds of the two recursions are the shared elim_round (device_utils.h: rank-2 update on the matrix pipe, no LDS,
 // no fence), issued back to back: two independent pivot chains for the scheduler to interleave.
 // wls: this wavefront's LDS scratch (WLS_DUAL doubles)
-template <int WM, bool HASL, int FLY = 0>
+// REC (solve_fused_kernel<.., RPL>): recursion B writes the Riccati-matrix record of its steps (see sweep_body)
+template <int WM, bool HASL, int FLY = 0, bool REC = false>
 __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b, double *const wls) {
     int lane_ = threadIdx.x & 63;
     asm volatile("" : "+v"(lane_));      // opaque per phase (see sweep_body)
@@ -174,6 +191,8 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
     double raccA = 0.0, raccB = 0.0, rprodA = 1.0, rprodB = 1.0;
     int rexpA = 0, rexpB = 0;
     int failA = 0, deadB = 0;        // deadB: 1 = H not PD (needs the restart loop of the plain kernel), 2 = M not PD
+    [[maybe_unused]] double *const recp = REC ? a.rec.m + (long)b * N * REC_STEP + 4 * l : nullptr;
+    [[maybe_unused]] double rchk = 0.0;                           // REC: stays zero while every recorded value is finite
 
     DIAG_DECL
     auto step = [&](const int t, const DTile &cur) -> int {
@@ -220,6 +239,11 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
             if (!deadB && (!(pdB > 0) || !(rprodB * 0.0 == 0.0))) deadB = 2;      // @assert isposdef(M) (:366)
             rexpA += __builtin_amdgcn_frexp_exp(rprodA); rprodA = __builtin_amdgcn_frexp_mant(rprodA);
             rexpB += __builtin_amdgcn_frexp_exp(rprodB); rprodB = __builtin_amdgcn_frexp_mant(rprodB);
+            if (REC) {
+                *reinterpret_cast<double2 *>(recp + (long)t * REC_STEP) = make_double2(mB[0], mB[1]);
+                recp[(long)t * REC_STEP + 2] = mB[2];
+                rchk = fma((mB[0] + mB[1]) + mB[2], 0.0, rchk);
+            }
             if (WM == 2) {
                 raccA += (nth12 * exA[84 + j]) * (mA[0] * exA[84 + g] + mA[1] * exA[84 + 4 + g] + mA[2] * exA[84 + 8 + g]);
                 raccB += (nth12 * exB[84 + j]) * (mB[0] * exB[84 + g] + mB[1] * exB[84 + 4 + g] + mB[2] * exB[84 + 8 + g]);
@@ -257,6 +281,10 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
         d4 fA = mm3(cz, tmA, ccs);
         d4 fB = mm3(cz, tmB, ccs);
         const double ghA = fma(muA, mH, fA[3]), ghB = fma(muB, mH, fB[3]);
+        if (REC) {
+            recp[(long)t * REC_STEP + 3] = ghB;
+            rchk = fma(ghB, 0.0, rchk);
+        }
         const double fvA = tmA[3] + cur.x, fvB = tmB[3] + cur.x;
         exA[g * 16 + j] = ghA; exB[g * 16 + j] = ghB;
         exA[fbo] = fvA; exB[fbo] = fvB;
@@ -338,6 +366,10 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
 #endif
     const double totA = sweep_scalars(wave_sum(raccA), coef, rprodA, rexpA, theta != 0.0);
     (void)raccB; (void)rprodB; (void)rexpB;          // B's value s_1 is not used by step! (only L, dl, mu, Delta are)
+    if (REC) {            // B ran every step (A did not fail), solved them all, on finite data, with theta != 0: its record is valid
+        const bool bad = failA || deadB || theta == 0.0 || __ballot(!(rchk == 0.0));
+        if (l == 12) rec_close(a.rec, b, sel ^ 1, bad, muB, rprodB, rexpB);
+    }
     if (l == 12) {
         const double s0 = 0.5 * vA[3] + totA;
         if (a.mode == 7) {
@@ -361,3 +393,214 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
     BODY_MARK(a.dump, dgs + 3);
 }
 
+
+// =======================================================================================================================================
+// replay_dual_body: mode 7 of sweep_dual_body -- line-search candidate 0's evaluation and the gain sweep of the next step! -- running only the
+// VECTOR half of the two recursions, both over ONE stream: the record of the sample's last full paired gain sweep (SweepArgs.rec).
+// Why it is exact: for the LQ family with kappa = 0 and a time-invariant diagonal W, f_x | f_u and the cost Hessian do not depend on the
+// trajectory, so S_t, -M_t^-1, [G_t | H_t + mu I] and L_t of a sweep depend only on theta and mu -- and the evaluation of the L a gain sweep
+// produced forms S = Q + A'DSA + L'HL + L'G + G'L from the same operands as that sweep (sweep_body: one formula for both).  The matrix half of
+// the V update only feeds the matrix half (an MFMA element reads its own row of A and column of B; F reads rows 0..11 of T), so what the
+// vector half reads from it -- -M^-1 (racc and Y = -M^-1 (-inv W) [A|B]) and register 3 of F + mu I -- is taken from the record, and every
+// value that reaches an output or feeds back comes from the instruction and the operands of the full sweep:
+//   T row 12 = mm3(v, Y) (rows 0..11 of the result are not used), the theta s'M^-1 s term, [G | g], the LDL' of H and the solve of every
+//   column (the columns j < 12 give L_t again: a replayed gain sweep writes L_t and dl_t like a full one), Ua, and the two V-update MFMAs
+//   (row 12 and column 12 of V are two differently rounded copies of s_vec; both feed forward).  The S block of V is not formed (Fx's is 0).
+// Exactness needs finite vector data: a non-finite x_t^2 (kappa = 0 still forms 0 x^2) or s_vec gives NaNs the record does not have.  Every
+// step tests its operands first; on one the replay stops (before the step's stores) and returns false -- so does a sweep the gate refuses
+// (no valid record, mu differs bitwise from the recorded pass's, theta == 0, or committed gains not solved from this record) -- and the
+// caller runs the full sweep, which rewrites everything the replay wrote.  Record loads run two steps ahead (three register sets).
+// Only sweep_dual_body records and only its mode 7 replays: sweep_body compiles the same V update to another contraction of its products
+// (measured: an evaluation by sweep_body of gains the pair solved differs from the pair's in the last bit on some samples), so a record of
+// the pair would not give sweep_body's bits.
+// wls: WLS_DUAL doubles
+// =======================================================================================================================================
+struct RTile {
+    double2 m01, m2h;      // record: -M^-1 registers 0, 1 | register 2, [G | H + mu I]
+    double x, xj, la;      // [qr | q] row, x_t[j], own entry of L_t (evaluation)
+};
+
+__device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b, double *const wls) {
+    int lane_ = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane_));      // opaque per phase (see sweep_body)
+    const int l_ = lane_, g_ = l_ >> 4, j_ = l_ & 15;
+    const int l = l_, g = g_, j = j_;
+    const StateDev &st = a.st;
+    const ProblemDev &pb = a.pb;
+    const RecDev &rc = a.rec;
+    // (every per-sample word requested before the first test on any of them: see sweep_body)
+    const int v_act = st.ls_active[b], v_flag = st.flag_c[b * st.E], v_nom = st.slot_nom[b], v_sel = st.lsel[b];
+    const int v_gen = rc.gen[b], v_lg0 = rc.lgen[2 * b], v_lg1 = rc.lgen[2 * b + 1];
+    const double v_theta = st.theta[b], v_mu = st.mu[b], v_rmu = rc.mu[b], v_rprod = rc.rprod[b];
+    const int v_rexp = rc.rexp[b];
+    const int s_act = wave_uniform(v_act), s_flag = wave_uniform(v_flag), s_nom = wave_uniform(v_nom), sel = wave_uniform(v_sel);
+    const int gen = wave_uniform(v_gen), lg = wave_uniform(sel ? v_lg1 : v_lg0);
+    const double theta = readlane_f64(v_theta, 0), mu = readlane_f64(v_mu, 0), rmu = readlane_f64(v_rmu, 0);
+    if (!s_act || s_flag == 2 || a.prune) return false;
+    // (mu = 0 only: with a raised mu the replayed pair was measured to differ from the full one in the last bits of some line-search
+    //  candidates' values -- not explained yet -- while every pair at mu = 0 matched; the LQ family raises mu only where H is not PD)
+    if (gen <= 0 || lg != gen || theta == 0.0 || __double_as_longlong(mu) != 0 || __double_as_longlong(rmu) != 0) return false;
+    const int slot = cand_slot(b, 0, s_nom, st.E);
+    const int N = st.N;
+    const double *__restrict__ tile0 = st.tiles + tile_slot(st, b, slot) * st.tile_stride;
+    const double *__restrict__ xh = st.xs + (long)slot * st.x_stride;
+    const double *__restrict__ rp = rc.m + (long)b * N * REC_STEP + 4 * l;
+    const int osel = sel ^ 1;
+    const double *__restrict__ Lb = st.L + (long)sel * st.l_half + (long)b * N * LSTR;
+    double *__restrict__ Lout = st.L + (long)osel * st.l_half + (long)b * N * LSTR;
+    double *__restrict__ dlout = st.dl + (long)osel * st.dl_half + (long)b * N * USTR;
+
+    double *const lbuf = wls;                                    // evaluation: the step's gain rows [L | 0] (natural 4 x 16 layout)
+    double *const exA = wls + 64, *const exB = wls + 64 + 168;   // exchange areas (see sweep_body); [G | H] lives in exB
+    if (l < 8) { exA[80 + l] = 0.0; exB[80 + l] = 0.0; }
+
+    const double m12 = (j < 12) ? 1.0 : 0.0;                    // (also the gain-column multiplier of the evaluation's loads)
+    const double nth12 = -theta * m12;
+    const double mA_ = (g == 0 && j < 12) ? 1.0 : 0.0, mB_ = (g == 0 && j == 12) ? 1.0 : 0.0;
+    const double e00 = (g == 0) ? 1.0 : 0.0, e10 = (g == 1) ? 1.0 : 0.0, e01 = (g == 2) ? 1.0 : 0.0, e11 = (g == 3) ? 1.0 : 0.0;
+    int hoff[4], foff[3], goff[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        hoff[k] = (g <= k) ? (g * 16 + 12 + k) : (k * 16 + 12 + g);
+        goff[k] = (j < 12) ? (k * 16 + j) : (j == 12 ? 64 + 12 + k : 80);
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) foff[r] = (j == 12) ? (64 + 4 * r + g) : 80;
+    const int gaoff = (j == 12) ? (64 + 12 + g) : 80;
+    const int lx = (l < 17) ? l : TS_PAD - TS_QR;
+    const int jc = (j < 12) ? j : 11;
+    const int svo = (g == 0) ? 84 + j : 104 + l, fbo = (g == 0) ? 64 + j : 104 + l;
+    double *const pgl = (j < 12) ? Lout + g * 12 + j : (j == 12 ? dlout + g : sample_sink(st, b) + l);
+    const long sgl = (j < 12) ? LSTR : (j == 12 ? USTR : 0);
+    double zt[3], dg[3], nwrow[3];                               // [A | B] image and diagonal selectors (FlyCtx), -inv(W)_ii of this lane's rows
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { zt[r] = pb.Zt[64 * r + l]; dg[r] = (j == 4 * r + g) ? 1.0 : 0.0; nwrow[r] = -pb.Wdg[4 * r + g]; }
+    const double kappa = pb.kappa;
+    const double coef = -1.0 / (2.0 * theta);
+
+    d4 vA, vB;                                                   // terminal condition (see sweep_dual_body)
+    {
+        const double *__restrict__ tt = tile0 + (long)N * TSTRIDE;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int i = 4 * r + g;
+            const double te = tt[(j < 12) ? TT_Q + i * 12 + j : TT_QV + i];
+            vA[r] = (j <= 12) ? te : 0.0;
+        }
+        const double t3 = tt[(j < 12) ? TT_QV + j : TT_q];
+        vA[3] = (g == 0 && j <= 12) ? (j < 12 ? t3 : 2.0 * t3) : 0.0;
+        vB = vA;
+    }
+    double raccA = 0.0;
+
+    auto load = [&](RTile &tr, const int t) {
+        const double2 *__restrict__ q = reinterpret_cast<const double2 *>(rp + (long)t * REC_STEP);
+        tr.m01 = q[0];
+        tr.m2h = q[1];
+        tr.x = tile0[(long)t * TSTRIDE + TS_QR + lx];
+        tr.xj = xh[(long)t * XSTR + jc];
+        tr.la = Lb[(long)t * LSTR + g * 12 + jc] * m12;
+    };
+    // one backward step; false: a non-finite operand (nothing of this step is stored)
+    auto step = [&](const int t, const RTile &cur) -> bool {
+        int l = l_, g = g_, j = j_;
+        asm volatile("" : "+v"(l), "+v"(g), "+v"(j));
+        d4 cz;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) cz[r] = fx_diag(zt[r], dg[r], kappa, cur.xj);
+        cz[3] = 0.0;
+        double probe = (cz[0] + cz[1]) + cz[2];
+        probe += (vA[0] + vA[1]) + (vA[2] + vA[3]);
+        probe += (vB[0] + vB[1]) + (vB[2] + vB[3]);
+        if (__ballot(!(probe - probe == 0.0))) return false;
+        const double m0 = cur.m01.x, m1 = cur.m01.y, m2 = cur.m2h.x, gh = cur.m2h.y;
+        exA[svo] = vA[3];
+        exB[svo] = vB[3];
+        // theta s_vec' M^-1 s_vec (:387) of the evaluation (a gain sweep's own value is not used by step!)
+        raccA += (nth12 * exA[84 + j]) * (m0 * exA[84 + g] + m1 * exA[84 + 4 + g] + m2 * exA[84 + 8 + g]);
+        d4 mw;
+        mw[0] = m0 * nwrow[0]; mw[1] = m1 * nwrow[1]; mw[2] = m2 * nwrow[2]; mw[3] = 0.0;
+        const d4 y2 = mm3(mw, cz, (d4){0, 0, 0, 0});
+        const d4 tmA = mm3(vA, y2, (d4){0, 0, 0, 0});
+        const d4 tmB = mm3(vB, y2, (d4){0, 0, 0, 0});
+        const double fvA = tmA[3] + cur.x, fvB = tmB[3] + cur.x;
+        exB[g * 16 + j] = gh;
+        exA[fbo] = fvA;
+        lbuf[l] = cur.la;
+        exB[fbo] = fvB;
+        WAVE_SYNC();
+        const double h0 = exB[hoff[0]], h1 = exB[hoff[1]], h2 = exB[hoff[2]], h3 = exB[hoff[3]];
+        const double qc = readlane_f64(cur.x, 16);
+        {                                                        // optimal gains (:372-382)
+            const double gaB = fma(gh, m12, exB[gaoff]);
+            const double h00 = exB[12], h01 = exB[13], h02 = exB[14], h03 = exB[15];
+            const double h11 = exB[16 + 13], h12 = exB[16 + 14], h13 = exB[16 + 15];
+            const double h22 = exB[32 + 14], h23 = exB[32 + 15], h33 = exB[48 + 15];
+            const double g0 = exB[goff[0]], g1 = exB[goff[1]], g2 = exB[goff[2]], g3 = exB[goff[3]];
+            const double d0 = h00, i0 = fast_rcp(d0);
+            const double l10 = h01 * i0, l20 = h02 * i0, l30 = h03 * i0;
+            const double d1 = h11 - l10 * h01, i1 = fast_rcp(d1);
+            const double l21 = (h12 - l20 * h01) * i1, l31 = (h13 - l30 * h01) * i1;
+            const double d2 = h22 - l20 * h02 - l21 * (l21 * d1), i2 = fast_rcp(d2);
+            const double l32 = (h23 - l30 * h02 - l31 * (l21 * d1)) * i2;
+            const double d3 = h33 - l30 * h03 - l31 * (l31 * d1) - l32 * (l32 * d2), i3 = fast_rcp(d3);
+            const double y0 = -g0;
+            const double y1 = -g1 - l10 * y0;
+            const double yy2 = -g2 - l20 * y0 - l21 * y1;
+            const double y3 = -g3 - l30 * y0 - l31 * y1 - l32 * yy2;
+            const double x3 = y3 * i3;
+            const double x2 = yy2 * i2 - l32 * x3;
+            const double x1 = y1 * i1 - l21 * x2 - l31 * x3;
+            const double x0 = y0 * i0 - l10 * x1 - l20 * x2 - l30 * x3;
+            const double laB = ((x0 * e00 + x1 * e10) + x2 * e01) + x3 * e11;
+            const double uaB = h0 * x0 + h1 * x1 + h2 * x2 + h3 * x3 + gaB;
+            pgl[(long)t * sgl] = (j <= 12) ? laB : 0.0;             // L_t | dl_t | idle lanes: sink
+            d4 fxB;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) fxB[r] = exB[foff[r]];     // column 12 (f_x) exact; the S block is not formed
+            fxB[3] = fma(fvB, mA_, (2.0 * qc + vB[3]) * mB_);
+            const d4 vn = MFMA(laB, uaB, fxB);
+            vB = MFMA(gaB, laB, vn);
+        }
+        {                                                        // the given policy (:446-451)
+            const double gaA = fma(gh, m12, exA[gaoff]);
+            const double uaA = h0 * lbuf[j] + h1 * lbuf[16 + j] + h2 * lbuf[32 + j] + h3 * lbuf[48 + j] + gaA;
+            d4 fxA;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) fxA[r] = exA[foff[r]];
+            fxA[3] = fma(fvA, mA_, (2.0 * qc + vA[3]) * mB_);
+            const d4 vn = MFMA(cur.la, uaA, fxA);
+            vA = MFMA(gaA, cur.la, vn);
+        }
+        WAVE_SYNC();          // the exchange areas are rewritten next step
+        return true;
+    };
+
+    RTile r0, r1, r2;
+    load(r0, N - 1);
+    load(r1, (N > 1) ? N - 2 : 0);
+    bool ok = true;
+    for (int t = N - 1; t >= 0; t -= 3) {        // (unrolled by three over rotating register sets: the record of step t - 2 is requested at step t)
+        load(r2, (t > 1) ? t - 2 : 0);
+        if (!step(t, r0)) { ok = false; break; }
+        if (t == 0) break;
+        load(r0, (t > 2) ? t - 3 : 0);
+        if (!step(t - 1, r1)) { ok = false; break; }
+        if (t == 1) break;
+        load(r1, (t > 3) ? t - 4 : 0);
+        if (!step(t - 2, r2)) { ok = false; break; }
+    }
+    WAVE_SYNC();
+    if (!ok) return false;
+    const double totA = sweep_scalars(wave_sum(raccA), coef, readlane_f64(v_rprod, 0), __builtin_amdgcn_readfirstlane(v_rexp), true);
+    if (l == 12) {
+        st.value_c[b * st.E] = 0.5 * vA[3] + totA;
+        st.flag_c[b * st.E] = 0;
+        st.mu_spec[b] = mu;                                      // (no restart: mu, Delta unchanged by the gain sweep)
+        st.delta_spec[b] = st.delta[b];
+        st.spec_st[b] = 1;
+        rc.lgen[2 * b + osel] = gen;                             // the gains written are the record's
+    }
+    if (l == 0) atomicAdd(rc.count, 2);
+    return true;
+}
