@@ -514,6 +514,10 @@ int32_t rat_get_path(rat_handle h, int64_t B);
  *                            mu = 0 -- runs only the vector half of both recursions over the record (csrc/sweep_dual.h:
  *                            replay_dual_body); identical outputs                                                        (1)
  *   lq_replay_count (read)   sweeps of this handle replayed so far, two per replayed pair (rat_debug_set clears it)
+ *   lq_replay_last  0 / 1    ... and the evaluation that ends a solve (d < d_tol or iter_max), whose gains came from the record, runs only
+ *                            its vector half over it as well (replay_eval_body); 0 = that evaluation runs in full; identical outputs  (1)
+ *   lq_replay_last_count (read)  evaluations of this handle replayed that way so far, one each; not part of lq_replay_count
+ *                            (rat_debug_set clears it)
  *   fly             0 / 1    round-based path, E > 1: line-search candidates without tile records                         (1)
  *   fly_multi       0 / 1    ... and all candidates of a sample rolled out by one wavefront                               (1)
  *   dual            0 / 1    round-based path: candidate 0 paired with the next gain sweep in one wavefront              (E > 1)

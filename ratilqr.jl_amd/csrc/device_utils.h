@@ -177,6 +177,29 @@ __device__ __forceinline__ double cost_term(double xu, double cxu, double lin) {
     return xu * h;
 }
 
+// Ua = H [L | dl] + [G | g] of the V update (ileqg.jl:383 / :448), this lane's entry: row g of Symmetric(H) times column j of the gains, plus
+// ga.  Ua feeds every column of the update, so the S block of an evaluation equals the S block of the gain sweep that solved its gains -- and
+// a record of that sweep's Riccati matrices can stand in for the evaluation's (sweep_dual.h: replay_body) -- only while every sweep rounds
+// this sum the same way.  Left to the compiler's contraction it was not: the gain recursions got h0 x0 as the separately rounded product, the
+// evaluations (of the pair, of the replay and of sweep_body alike) h1 x1.  ONE order in source: the evaluations'.
+__device__ __forceinline__ double ua_entry(double h0, double h1, double h2, double h3, double x0, double x1, double x2, double x3, double ga) {
+#pragma clang fp contract(off)
+    const double p1 = h1 * x1;
+    const double s = __builtin_fma(h3, x3, __builtin_fma(h2, x2, __builtin_fma(h0, x0, p1)));
+    return s + ga;
+}
+
+// theta s_vec' M^-1 s_vec (ileqg.jl:387) with a diagonal W, this lane's share added to racc: (-theta s_j) sum_i (-M^-1)_ij s_i over the lane's
+// three rows i = g, 4 + g, 8 + g (nth12 = -theta on the lanes j < 12, else 0).  The sum only reaches the sweep's value; one order in source so
+// that a sweep replayed over a record gives the bits of the full one, whichever kernel runs it.
+__device__ __forceinline__ double racc_diag(double racc, double nth12, double sj, double m0, double m1, double m2, double s0, double s4, double s8) {
+#pragma clang fp contract(off)
+    const double nsj = nth12 * sj;
+    const double p1 = m1 * s4;
+    const double q = __builtin_fma(m2, s8, __builtin_fma(m0, s0, p1));
+    return __builtin_fma(nsj, q, racc);
+}
+
 // The four 16-lane rows of x, each broadcast to every row (v_permlane32_swap + v_permlane16_swap, gfx950; tools/ubench/xlane.hip checks
 // the pattern lane by lane): r[g] on lane (., j) = x of lane (g, j).
 __device__ __forceinline__ void rows_bcast(double x, double (&r)[4]) {

@@ -62,6 +62,7 @@ struct rat_handle_s {
     int *d_duo_count = nullptr;      // ... samples that ran as a pair so far
     bool lq_replay = true;           // solve_fused_kernel, LQ family, kappa = 0, diagonal W: later sweeps replay the Riccati matrices of the last full gain
                                      // sweep (RecDev, kernels.h; switch lq_replay)
+    bool lq_replay_last = true;      // ... and so does the evaluation that ends the solve (replay_eval_body; switch lq_replay_last)
     RecDev rec = {};                 // ... its per-sample words (st_allocs) and the record (rec.m: rec_cap doubles, allocated by the first batch that uses it)
     size_t rec_cap = 0;
     unsigned xepoch = 0;             // ... launches so far (the hand-over words carry it: nothing to clear between launches)
@@ -253,6 +254,9 @@ static const DebugSwitch debug_switches[] = {
     {"lq_replay", [](rat_handle h, int64_t v) { h->lq_replay = (v != 0); }, [](rat_handle h) -> int64_t { return h->lq_replay; }},
     {"lq_replay_count", [](rat_handle h, int64_t) { if (h->rec.count) { (void)hipStreamSynchronize(h->stream); (void)hipMemset(h->rec.count, 0, sizeof(int)); } },
      [](rat_handle h) -> int64_t { int c = 0; if (h->rec.count) { (void)hipStreamSynchronize(h->stream); (void)hipMemcpy(&c, h->rec.count, sizeof(int), hipMemcpyDeviceToHost); } return c; }},
+    {"lq_replay_last", [](rat_handle h, int64_t v) { h->lq_replay_last = (v != 0); }, [](rat_handle h) -> int64_t { return h->lq_replay_last; }},
+    {"lq_replay_last_count", [](rat_handle h, int64_t) { if (h->rec.count) { (void)hipStreamSynchronize(h->stream); (void)hipMemset(h->rec.count + 1, 0, sizeof(int)); } },
+     [](rat_handle h) -> int64_t { int c = 0; if (h->rec.count) { (void)hipStreamSynchronize(h->stream); (void)hipMemcpy(&c, h->rec.count + 1, sizeof(int), hipMemcpyDeviceToHost); } return c; }},
     {"psw_acl", [](rat_handle h, int64_t v) { h->psw_acl = (v != 0); }, [](rat_handle h) -> int64_t { return h->psw_acl; }},
     {"psw_comp", [](rat_handle h, int64_t v) { h->psw_comp = (int)std::max<int64_t>(100, v); }, [](rat_handle h) -> int64_t { return h->psw_comp; }},
     {"src_tpw", [](rat_handle h, int64_t v) { h->src_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_tpw; }},
@@ -460,7 +464,7 @@ static rat_rc alloc_state(rat_handle h) {
     AL(st.value_c, (size_t)B * E); AL(st.d_c, (size_t)B * E); AL(st.flag_c, (size_t)B * E); AL(st.acc0, B);
     AL(st.counters, 2 * CTR_RING); AL(st.sink, (size_t)SINK_SLOTS * 64);
     AL(h->d_xw, (size_t)B * XW_STRIDE); AL(h->d_duo_count, 1);
-    AL(h->rec.mu, B); AL(h->rec.rprod, B); AL(h->rec.rexp, B); AL(h->rec.gen, B); AL(h->rec.lgen, (size_t)2 * B); AL(h->rec.count, 1);
+    AL(h->rec.mu, B); AL(h->rec.rprod, B); AL(h->rec.rexp, B); AL(h->rec.gen, B); AL(h->rec.lgen, (size_t)2 * B); AL(h->rec.count, 2);
     h->xepoch = 0;
     st.hist = nullptr; st.hist_cap = 0;
     AL(h->d_x0, XSTR); AL(h->d_u0, (size_t)N * USTR); AL(h->d_theta, B); AL(h->d_val, B);
@@ -483,7 +487,7 @@ static rat_rc alloc_state(rat_handle h) {
     HIPCHK(hipMemsetAsync(h->d_dump, 0, (size_t)(N + 1) * DUMP_STRIDE * sizeof(double), h->stream));      // (diagnostic builds count into it)
     HIPCHK(hipMemsetAsync(h->d_xw, 0, (size_t)B * XW_STRIDE * sizeof(long long), h->stream));
     HIPCHK(hipMemsetAsync(h->d_duo_count, 0, sizeof(int), h->stream));
-    HIPCHK(hipMemsetAsync(h->rec.count, 0, sizeof(int), h->stream));
+    HIPCHK(hipMemsetAsync(h->rec.count, 0, 2 * sizeof(int), h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return RAT_OK;
 }
@@ -1237,6 +1241,7 @@ static rat_rc run_batch(rat_handle h, const double *theta_dev, int B, const Batc
                 h->rec_cap = need;
             }
             fa.sw.rec = h->rec;
+            fa.sw.rec.last = h->lq_replay_last ? 1 : 0;
         }
         fa.theta_in = theta_dev;
         fa.out_value = out.value; fa.out_status = out.status; fa.out_iters = out.iters; fa.out_ls = out.ls;

@@ -7,7 +7,7 @@
 // Riccati-matrix record of the one-wavefront-per-sample solve (solve_fused_kernel, LQ family, kappa = 0, diagonal time-invariant W): for such a
 // problem A, B, Q, R, P, W do not depend on the trajectory, so every later paired sweep at the same mu runs the matrix half of the recursions
 // of the last full paired gain sweep again, bit for bit.  That sweep records per step what the vector half reads from it; later pairs replay
-// only the vector half (sweep_dual.h: replay_dual_body).  Null m: no record (every sweep runs in full).
+// only the vector half (sweep_dual.h: replay_body), and so does the evaluation that ends the solve.  Null m: no record (every sweep runs in full).
 #define REC_STEP 256       /* doubles per step: lane-major, 4 per lane = -M^-1 (3 accumulator registers) and [G | H + mu I] (register 3 of F) */
 struct RecDev {
     double *m;             // [B][N][REC_STEP]
@@ -16,7 +16,8 @@ struct RecDev {
     int *rexp;             // [B] ... and its exponent sum (logdet(W M): identical for every sweep that replays the record)
     int *gen;              // [B] generation of the valid record (> 0), or minus the last one (<= 0: none)
     int *lgen;             // [B][2] record generation the gains of each half of L / dl were solved from (0: none)
-    int *count;            // sweeps replayed so far (switch lq_replay_count)
+    int *count;            // [2] sweeps replayed so far in pairs (switch lq_replay_count) | evaluations that end a solve replayed (lq_replay_last_count)
+    int last;              // the evaluation that ends a solve replays too (switch lq_replay_last)
 };
 
 struct SweepArgs {
@@ -94,8 +95,9 @@ struct FusedArgs {         // solve_fused_kernel: one persistent wavefront per s
     unsigned xepoch;
     long long *xw;
     int *duo_count;
-    long long pad_;                    // (sizeof(FusedArgs) stays a whole number of 64-B lines: solve_block_psw_kernel's kernarg_warm)
 };
+// solve_block_psw_kernel's kernarg_warm fetches the argument block in whole 64-B lines: a new field may need padding beside it
+static_assert(sizeof(FusedArgs) % 64 == 0, "FusedArgs: a whole number of 64-B lines");
 #define XW_STRIDE 24                   /* 64-bit words per sample: [0] pair word, [8] role A's posts, [16] role B's posts (64 B apart) */
 #define CENSUS_SLOTS 4096              /* (XCC_ID, SE_ID, SH_ID, CU_ID) of HW_REG_HW_ID / HW_REG_XCC_ID: 4 + 3 + 1 + 4 bits */
 

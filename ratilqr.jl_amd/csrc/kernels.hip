@@ -322,7 +322,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs &a, const int tid, do
                 rprod = __builtin_amdgcn_frexp_mant(rprod);
                 if (WM == 2) {
                     // theta s_vec' M^-1 s_vec (:387), per lane: (-theta s_j) sum_i (-M^-1)_ij s_i (columns >= 12 of the sweep's result are zero)
-                    racc += (nth12 * SVB(j)) * (m[0] * SVB(g) + m[1] * SVB(4 + g) + m[2] * SVB(8 + g));
+                    racc = racc_diag(racc, nth12, SVB(j), m[0], m[1], m[2], SVB(g), SVB(4 + g), SVB(8 + g));
                     // T = V M^-1 inv(W) [A|B]: rows 0..11 = (D S)[A|B], row 12 = (D s_vec)'[A|B]   (:367)
                     d4 mw;
 #pragma unroll
@@ -398,7 +398,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs &a, const int tid, do
             } else {
                 x0 = x1 = x2 = x3 = la = 0.0;
             }
-            const double ua = hg0 * x0 + hg1 * x1 + hg2 * x2 + hg3 * x3 + ga;         // H [L|dl] + [G|g]
+            const double ua = ua_entry(hg0, hg1, hg2, hg3, x0, x1, x2, x3, ga);        // H [L|dl] + [G|g]: one rounding order in every sweep
             DIAG_STAMP(4, ua);
             if (GAIN) {
                 pgl[(long)t * sgl] = (j <= 12) ? la : 0.0;      // L_t (columns 0..11) | dl_t (column 12) | idle lanes: sink
@@ -2547,7 +2547,8 @@ __device__ __forceinline__ void gather_body(const StateDev &st, const int b, dou
 // words its byte model on, kept as a measured variant (bit-identical: fx_diag gives a record the bits the fly sweeps form in registers).
 // RPL (headline geometry, kappa = 0, diagonal W; switch lq_replay): every full paired gain sweep records its Riccati matrices (SweepArgs.rec)
 // and a later pair that would recompute them -- the evaluation of the gains it solved beside the gain sweep at the same mu -- replays the
-// record (replay_dual_body, sweep_dual.h: bit-identical; a pair the replay refuses runs in full).
+// record (replay_dual_body, sweep_dual.h: bit-identical; a pair the replay refuses runs in full).  So does the evaluation that ends the solve
+// when its gains came from the record (replay_eval_body: the evaluation half of the pair alone; switch lq_replay_last).
 template <int MODEL, bool CTV, int WM, bool DUALF, bool STG, bool OCC2 = false, bool MAT = false, bool RPL = false>
 __global__ __launch_bounds__(64, OCC2 ? 2 : 1) void solve_fused_kernel(FusedArgs fa) {
     const int b = blockIdx.x;
@@ -2630,7 +2631,7 @@ __global__ __launch_bounds__(64, OCC2 ? 2 : 1) void solve_fused_kernel(FusedArgs
                 if (!(RPL && replay_dual_body(sa, b, wls))) sweep_dual_body<WM, true, FLYF, RPL>(sa, b, wls);
             } else {
                 SweepArgs sa = fa.sw; sa.mode = 1;
-                sweep_body<false, false, WM, true, OCC2 ? OCC2_SWZ : 0, FLYF>(sa, b, wls);
+                if (!(RPL && replay_eval_body(sa, b, wls))) sweep_body<false, false, WM, true, OCC2 ? OCC2_SWZ : 0, FLYF>(sa, b, wls);
             }
             PHASE_MARK();
             PHASE_FENCE();

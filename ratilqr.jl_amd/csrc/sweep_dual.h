@@ -245,8 +245,8 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
                 rchk = fma((mB[0] + mB[1]) + mB[2], 0.0, rchk);
             }
             if (WM == 2) {
-                raccA += (nth12 * exA[84 + j]) * (mA[0] * exA[84 + g] + mA[1] * exA[84 + 4 + g] + mA[2] * exA[84 + 8 + g]);
-                raccB += (nth12 * exB[84 + j]) * (mB[0] * exB[84 + g] + mB[1] * exB[84 + 4 + g] + mB[2] * exB[84 + 8 + g]);
+                raccA = racc_diag(raccA, nth12, exA[84 + j], mA[0], mA[1], mA[2], exA[84 + g], exA[84 + 4 + g], exA[84 + 8 + g]);
+                raccB = racc_diag(raccB, nth12, exB[84 + j], mB[0], mB[1], mB[2], exB[84 + g], exB[84 + 4 + g], exB[84 + 8 + g]);
                 d4 mwA, mwB;
 #pragma unroll
                 for (int r = 0; r < 3; ++r) { mwA[r] = mA[r] * nwrow[r]; mwB[r] = mB[r] * nwrow[r]; }
@@ -294,7 +294,7 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
         // ---- A: given policy (:446-451) ----
         const double hA0 = exA[hoff[0]], hA1 = exA[hoff[1]], hA2 = exA[hoff[2]], hA3 = exA[hoff[3]];
         const double gaA = fma(ghA, m12, exA[gaoff]);
-        const double uaA = HASL ? hA0 * lbufA[j] + hA1 * lbufA[16 + j] + hA2 * lbufA[32 + j] + hA3 * lbufA[48 + j] + gaA : gaA;
+        const double uaA = HASL ? ua_entry(hA0, hA1, hA2, hA3, lbufA[j], lbufA[16 + j], lbufA[32 + j], lbufA[48 + j], gaA) : gaA;
         // ---- B: optimal gains (:372-382) ----
         const double hB0 = exB[hoff[0]], hB1 = exB[hoff[1]], hB2 = exB[hoff[2]], hB3 = exB[hoff[3]];
         const double gaB = fma(ghB, m12, exB[gaoff]);
@@ -319,7 +319,7 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
         const double x1 = y1 * i1 - l21 * x2 - l31 * x3;
         const double x0 = y0 * i0 - l10 * x1 - l20 * x2 - l30 * x3;
         const double laB = ((x0 * em.e0[0] + x1 * em.e1[0]) + x2 * em.e0[1]) + x3 * em.e1[1];     // row g takes x_g (see sweep_body)
-        const double uaB = hB0 * x0 + hB1 * x1 + hB2 * x2 + hB3 * x3 + gaB;
+        const double uaB = ua_entry(hB0, hB1, hB2, hB3, x0, x1, x2, x3, gaB);
         pgl[(long)t * sgl] = (j <= 12) ? laB : 0.0;                // L_t | dl_t | idle lanes: sink
         d4 fxA, fxB;
 #pragma unroll
@@ -395,24 +395,26 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
 
 
 // =======================================================================================================================================
-// replay_dual_body: mode 7 of sweep_dual_body -- line-search candidate 0's evaluation and the gain sweep of the next step! -- running only the
-// VECTOR half of the two recursions, both over ONE stream: the record of the sample's last full paired gain sweep (SweepArgs.rec).
+// replay_body: a sweep of the one-wavefront-per-sample solve running only the VECTOR half of its recursions over ONE stream: the record of the
+// sample's last full paired gain sweep (SweepArgs.rec).
+//   GAINB = true   replay_dual_body: mode 7 of sweep_dual_body -- line-search candidate 0's evaluation and the gain sweep of the next step!
+//   GAINB = false  replay_eval_body: mode 1 of sweep_body -- the plain evaluation of candidate 0 where accepting it ends the solve (d < d_tol
+//                  or iter_max: nothing would consume the gains), the evaluation half of the pair alone
 // Why it is exact: for the LQ family with kappa = 0 and a time-invariant diagonal W, f_x | f_u and the cost Hessian do not depend on the
 // trajectory, so S_t, -M_t^-1, [G_t | H_t + mu I] and L_t of a sweep depend only on theta and mu -- and the evaluation of the L a gain sweep
-// produced forms S = Q + A'DSA + L'HL + L'G + G'L from the same operands as that sweep (sweep_body: one formula for both).  The matrix half of
-// the V update only feeds the matrix half (an MFMA element reads its own row of A and column of B; F reads rows 0..11 of T), so what the
-// vector half reads from it -- -M^-1 (racc and Y = -M^-1 (-inv W) [A|B]) and register 3 of F + mu I -- is taken from the record, and every
-// value that reaches an output or feeds back comes from the instruction and the operands of the full sweep:
-//   T row 12 = mm3(v, Y) (rows 0..11 of the result are not used), the theta s'M^-1 s term, [G | g], the LDL' of H and the solve of every
-//   column (the columns j < 12 give L_t again: a replayed gain sweep writes L_t and dl_t like a full one), Ua, and the two V-update MFMAs
-//   (row 12 and column 12 of V are two differently rounded copies of s_vec; both feed forward).  The S block of V is not formed (Fx's is 0).
+// produced forms S = Q + A'DSA + L'HL + L'G + G'L from the same operands as that sweep (sweep_body: one formula for both, Ua in one rounding
+// order everywhere: ua_entry).  The matrix half of the V update only feeds the matrix half (an MFMA element reads its own row of A and column
+// of B; F reads rows 0..11 of T), so what the vector half reads from it -- -M^-1 (racc and Y = -M^-1 (-inv W) [A|B]) and register 3 of
+// F + mu I -- is taken from the record, and every value that reaches an output or feeds back comes from the instruction and the operands of
+// the full sweep:
+//   T row 12 = mm3(v, Y) (rows 0..11 of the result are not used), the theta s'M^-1 s term (racc_diag), [G | g], the LDL' of H and the solve
+//   of every column (the columns j < 12 give L_t again: a replayed gain sweep writes L_t and dl_t like a full one), Ua, and the two V-update
+//   MFMAs (row 12 and column 12 of V are two differently rounded copies of s_vec; both feed forward).  The S block of V is not formed (Fx's is 0).
 // Exactness needs finite vector data: a non-finite x_t^2 (kappa = 0 still forms 0 x^2) or s_vec gives NaNs the record does not have.  Every
 // step tests its operands first; on one the replay stops (before the step's stores) and returns false -- so does a sweep the gate refuses
-// (no valid record, mu differs bitwise from the recorded pass's, theta == 0, or committed gains not solved from this record) -- and the
-// caller runs the full sweep, which rewrites everything the replay wrote.  Record loads run two steps ahead (three register sets).
-// Only sweep_dual_body records and only its mode 7 replays: sweep_body compiles the same V update to another contraction of its products
-// (measured: an evaluation by sweep_body of gains the pair solved differs from the pair's in the last bit on some samples), so a record of
-// the pair would not give sweep_body's bits.
+// (no valid record, mu differs bitwise from the recorded pass's, theta == 0, or committed gains not solved from this record; the evaluation
+// alone also under rec.last = 0) -- and the caller runs the full sweep, which rewrites everything the replay wrote.  Record loads run two steps
+// ahead (three register sets).
 // wls: WLS_DUAL doubles
 // =======================================================================================================================================
 struct RTile {
@@ -420,7 +422,8 @@ struct RTile {
     double x, xj, la;      // [qr | q] row, x_t[j], own entry of L_t (evaluation)
 };
 
-__device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b, double *const wls) {
+template <bool GAINB>
+__device__ __forceinline__ bool replay_body(const SweepArgs &a, const int b, double *const wls) {
     int lane_ = threadIdx.x & 63;
     asm volatile("" : "+v"(lane_));      // opaque per phase (see sweep_body)
     const int l_ = lane_, g_ = l_ >> 4, j_ = l_ & 15;
@@ -437,6 +440,7 @@ __device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b
     const int gen = wave_uniform(v_gen), lg = wave_uniform(sel ? v_lg1 : v_lg0);
     const double theta = readlane_f64(v_theta, 0), mu = readlane_f64(v_mu, 0), rmu = readlane_f64(v_rmu, 0);
     if (!s_act || s_flag == 2 || a.prune) return false;
+    if (!GAINB && !rc.last) return false;                        // switch lq_replay_last
     // (mu = 0 only: with a raised mu the replayed pair was measured to differ from the full one in the last bits of some line-search
     //  candidates' values -- not explained yet -- while every pair at mu = 0 matched; the LQ family raises mu only where H is not PD)
     if (gen <= 0 || lg != gen || theta == 0.0 || __double_as_longlong(mu) != 0 || __double_as_longlong(rmu) != 0) return false;
@@ -457,8 +461,9 @@ __device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b
     const double m12 = (j < 12) ? 1.0 : 0.0;                    // (also the gain-column multiplier of the evaluation's loads)
     const double nth12 = -theta * m12;
     const double mA_ = (g == 0 && j < 12) ? 1.0 : 0.0, mB_ = (g == 0 && j == 12) ? 1.0 : 0.0;
-    const double e00 = (g == 0) ? 1.0 : 0.0, e10 = (g == 1) ? 1.0 : 0.0, e01 = (g == 2) ? 1.0 : 0.0, e11 = (g == 3) ? 1.0 : 0.0;
-    int hoff[4], foff[3], goff[4];
+    [[maybe_unused]] const double e00 = (g == 0) ? 1.0 : 0.0, e10 = (g == 1) ? 1.0 : 0.0, e01 = (g == 2) ? 1.0 : 0.0, e11 = (g == 3) ? 1.0 : 0.0;
+    int hoff[4], foff[3];
+    [[maybe_unused]] int goff[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         hoff[k] = (g <= k) ? (g * 16 + 12 + k) : (k * 16 + 12 + g);
@@ -470,8 +475,8 @@ __device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b
     const int lx = (l < 17) ? l : TS_PAD - TS_QR;
     const int jc = (j < 12) ? j : 11;
     const int svo = (g == 0) ? 84 + j : 104 + l, fbo = (g == 0) ? 64 + j : 104 + l;
-    double *const pgl = (j < 12) ? Lout + g * 12 + j : (j == 12 ? dlout + g : sample_sink(st, b) + l);
-    const long sgl = (j < 12) ? LSTR : (j == 12 ? USTR : 0);
+    [[maybe_unused]] double *const pgl = (j < 12) ? Lout + g * 12 + j : (j == 12 ? dlout + g : sample_sink(st, b) + l);
+    [[maybe_unused]] const long sgl = (j < 12) ? LSTR : (j == 12 ? USTR : 0);
     double zt[3], dg[3], nwrow[3];                               // [A | B] image and diagonal selectors (FlyCtx), -inv(W)_ii of this lane's rows
 #pragma unroll
     for (int r = 0; r < 3; ++r) { zt[r] = pb.Zt[64 * r + l]; dg[r] = (j == 4 * r + g) ? 1.0 : 0.0; nwrow[r] = -pb.Wdg[4 * r + g]; }
@@ -511,27 +516,28 @@ __device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b
         cz[3] = 0.0;
         double probe = (cz[0] + cz[1]) + cz[2];
         probe += (vA[0] + vA[1]) + (vA[2] + vA[3]);
-        probe += (vB[0] + vB[1]) + (vB[2] + vB[3]);
+        if (GAINB) probe += (vB[0] + vB[1]) + (vB[2] + vB[3]);
         if (__ballot(!(probe - probe == 0.0))) return false;
         const double m0 = cur.m01.x, m1 = cur.m01.y, m2 = cur.m2h.x, gh = cur.m2h.y;
         exA[svo] = vA[3];
-        exB[svo] = vB[3];
+        if (GAINB) exB[svo] = vB[3];
         // theta s_vec' M^-1 s_vec (:387) of the evaluation (a gain sweep's own value is not used by step!)
-        raccA += (nth12 * exA[84 + j]) * (m0 * exA[84 + g] + m1 * exA[84 + 4 + g] + m2 * exA[84 + 8 + g]);
+        raccA = racc_diag(raccA, nth12, exA[84 + j], m0, m1, m2, exA[84 + g], exA[84 + 4 + g], exA[84 + 8 + g]);
         d4 mw;
         mw[0] = m0 * nwrow[0]; mw[1] = m1 * nwrow[1]; mw[2] = m2 * nwrow[2]; mw[3] = 0.0;
         const d4 y2 = mm3(mw, cz, (d4){0, 0, 0, 0});
         const d4 tmA = mm3(vA, y2, (d4){0, 0, 0, 0});
-        const d4 tmB = mm3(vB, y2, (d4){0, 0, 0, 0});
+        d4 tmB = {0, 0, 0, 0};
+        if (GAINB) tmB = mm3(vB, y2, (d4){0, 0, 0, 0});
         const double fvA = tmA[3] + cur.x, fvB = tmB[3] + cur.x;
         exB[g * 16 + j] = gh;
         exA[fbo] = fvA;
         lbuf[l] = cur.la;
-        exB[fbo] = fvB;
+        if (GAINB) exB[fbo] = fvB;
         WAVE_SYNC();
         const double h0 = exB[hoff[0]], h1 = exB[hoff[1]], h2 = exB[hoff[2]], h3 = exB[hoff[3]];
         const double qc = readlane_f64(cur.x, 16);
-        {                                                        // optimal gains (:372-382)
+        if (GAINB) {                                             // optimal gains (:372-382)
             const double gaB = fma(gh, m12, exB[gaoff]);
             const double h00 = exB[12], h01 = exB[13], h02 = exB[14], h03 = exB[15];
             const double h11 = exB[16 + 13], h12 = exB[16 + 14], h13 = exB[16 + 15];
@@ -553,7 +559,7 @@ __device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b
             const double x1 = y1 * i1 - l21 * x2 - l31 * x3;
             const double x0 = y0 * i0 - l10 * x1 - l20 * x2 - l30 * x3;
             const double laB = ((x0 * e00 + x1 * e10) + x2 * e01) + x3 * e11;
-            const double uaB = h0 * x0 + h1 * x1 + h2 * x2 + h3 * x3 + gaB;
+            const double uaB = ua_entry(h0, h1, h2, h3, x0, x1, x2, x3, gaB);
             pgl[(long)t * sgl] = (j <= 12) ? laB : 0.0;             // L_t | dl_t | idle lanes: sink
             d4 fxB;
 #pragma unroll
@@ -564,7 +570,7 @@ __device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b
         }
         {                                                        // the given policy (:446-451)
             const double gaA = fma(gh, m12, exA[gaoff]);
-            const double uaA = h0 * lbuf[j] + h1 * lbuf[16 + j] + h2 * lbuf[32 + j] + h3 * lbuf[48 + j] + gaA;
+            const double uaA = ua_entry(h0, h1, h2, h3, lbuf[j], lbuf[16 + j], lbuf[32 + j], lbuf[48 + j], gaA);
             d4 fxA;
 #pragma unroll
             for (int r = 0; r < 3; ++r) fxA[r] = exA[foff[r]];
@@ -596,11 +602,15 @@ __device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b
     if (l == 12) {
         st.value_c[b * st.E] = 0.5 * vA[3] + totA;
         st.flag_c[b * st.E] = 0;
-        st.mu_spec[b] = mu;                                      // (no restart: mu, Delta unchanged by the gain sweep)
-        st.delta_spec[b] = st.delta[b];
-        st.spec_st[b] = 1;
-        rc.lgen[2 * b + osel] = gen;                             // the gains written are the record's
+        if (GAINB) {
+            st.mu_spec[b] = mu;                                  // (no restart: mu, Delta unchanged by the gain sweep)
+            st.delta_spec[b] = st.delta[b];
+            st.spec_st[b] = 1;
+            rc.lgen[2 * b + osel] = gen;                         // the gains written are the record's
+        }
     }
-    if (l == 0) atomicAdd(rc.count, 2);
+    if (l == 0) atomicAdd(rc.count + (GAINB ? 0 : 1), GAINB ? 2 : 1);     // [0] sweeps replayed in pairs, [1] last evaluations replayed
     return true;
 }
+__device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b, double *const wls) { return replay_body<true>(a, b, wls); }
+__device__ __forceinline__ bool replay_eval_body(const SweepArgs &a, const int b, double *const wls) { return replay_body<false>(a, b, wls); }
