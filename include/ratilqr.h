@@ -134,8 +134,8 @@ rat_rc rat_problem_set(rat_handle h, const rat_problem_desc *desc);
  * with A n x n and B n x m column-major: exact Jacobians instead of AD for f.  A NaN in x_{t+1} or in a cost whose inputs had none is
  * the reference's DomainError (RAT_ST_DOMAIN, value Inf).  No fast-math.
  * Limits: n <= 12, m <= 4 (else RAT_ERR_UNSUPPORTED); batches run on the round-based path (rat_set_path FUSED / BLOCK return
- * RAT_ERR_UNSUPPORTED); rat_rollout_noisy and rat_multi are not available for source models.  PETS takes generative source models
- * of its own (rat_pets_problem_set_source, below). */
+ * RAT_ERR_UNSUPPORTED); rat_rollout_noisy and rat_multi are not available for source models: rat_policy_evaluate with cost_out is the way
+ * to their Monte-Carlo costs.  PETS takes generative source models of its own (rat_pets_problem_set_source, below). */
 #define RAT_MODEL_SOURCE    3
 
 /* Compile `source` (NUL-terminated) for the handle's device and make it the handle's problem.  W: n*n column-major, N entries if W_tv
@@ -191,6 +191,34 @@ rat_rc rat_integrate_cost(rat_handle h, const double *x, const double *u, double
  * (ileqg.jl:115-124; NaN where a rollout hit a DomainError), *domain_fail = 1 if any rollout did. */
 rat_rc rat_rollout_noisy(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
                          const double *z, uint64_t seed, double *x_out, double *u_out, double *cost_out, int32_t *domain_fail);
+/* Monte-Carlo policy evaluation: the K rollouts of rat_rollout_noisy (x_nom, l, L, K, z, seed mean exactly what they mean there; L == NULL
+ * is an open-loop run) for a problem of any model kind -- the LQ and power-law families, general sizes and source models -- with the
+ * statistics of the K costs formed on the device: only these doubles come back, not K of them.
+ *   stats[RAT_MC_NSTAT]  the slots below; required
+ *   theta[n_theta]       risk parameters, 0 <= n_theta <= 16, every theta[i] >= 0 (else RAT_ERR_ARG)
+ *   risk[i]              the entropic risk (1 / theta_i) log mean_k exp(theta_i J_k) that iLEQG minimises, formed as
+ *                        Jmax + log(mean_k exp(theta_i (J_k - Jmax))) / theta_i (no overflow for any theta); the mean where theta_i == 0
+ *   risk_se[i]           its delta-method standard error sd(y) / (mean(y) theta_i sqrt(N_OK)), y_k = exp(theta_i (J_k - Jmax)); SE_MEAN where
+ *                        theta_i == 0.  It is finite only where E exp(2 theta J) is.
+ *   cost_out[K]          rat_rollout_noisy's cost_out (bit for bit for the families and general sizes, with the same seed or z), NaN for a
+ *                        DomainError rollout
+ * risk, risk_se, cost_out may be NULL.  DomainError rollouts are counted and left out of every statistic; with N_OK == 0 the call returns
+ * RAT_OK and MEAN, VAR, MIN, MAX, the risks and their errors are NaN.  K < 1 or K > 2^27 is RAT_ERR_ARG, and so is a W(k) that is not
+ * positive definite.  The sums run in a fixed order without floating-point atomics: two calls with the same arguments return the same
+ * bits.  For a source model the generator is keyed as for the families: a seed names the same noise for a family problem and for the same
+ * problem written as source; its rollout kernel is compiled by the first call on the problem (cached per process like the model kernels).
+ * The device buffers of the call (8 bytes per rollout, plus 4 for the families) belong to the handle, grow with K and stay until rat_destroy. */
+#define RAT_MC_N_OK     0   /* rollouts without a DomainError, as a double */
+#define RAT_MC_N_DOMAIN 1   /* rollouts that hit one; they are left out of every statistic */
+#define RAT_MC_MEAN     2
+#define RAT_MC_VAR      3   /* unbiased; NaN when N_OK < 2 */
+#define RAT_MC_MIN      4
+#define RAT_MC_MAX      5
+#define RAT_MC_SE_MEAN  6   /* sqrt(VAR / N_OK) */
+#define RAT_MC_NSTAT    8   /* slot 7 reserved, written as 0 */
+rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
+                           const double *z, uint64_t seed, const double *theta, int32_t n_theta,
+                           double *stats, double *risk, double *risk_se, double *cost_out);
 /* approximate_model(problem, u_array, x_array)                 ileqg.jl:258-322
  * -> q[N+1], qv[n*(N+1)], Q[n*n*(N+1)], r[m*N], R[m*m*N], P[m*n*N], A[n*n*N], B[n*m*N], W[n*n*N] */
 rat_rc rat_approximate_model(rat_handle h, const double *u, const double *x,
@@ -555,6 +583,7 @@ int32_t rat_get_path(rat_handle h, int64_t B);
  *                            trajectories, profiles/source_model.md)                                                        (16)
  *   src_pets_tpw    16 / 32 / 64   generative source models: trajectories per wavefront of the PETS rollout kernel (64: 3.7x 16's
  *                            rollouts/s at 10^6 trajectories, equal at 10 k; profiles/source_pets.md)                     (64)
+ *   src_mc_tpw      16 / 32 / 64   source models: rollouts per wavefront of rat_policy_evaluate's rollout kernel (profiles/policy_mc.md) (64)
  *   wdiag           0 / 1    diagonal time-invariant W: inv(W) folded into M^-1's operand (takes effect at the next rat_problem_set) (1) */
 rat_rc  rat_debug_set(rat_handle h, const char *key, int64_t value);
 rat_rc  rat_debug_get(rat_handle h, const char *key, int64_t *value);      /* the EFFECTIVE value on this handle */

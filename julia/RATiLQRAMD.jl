@@ -319,6 +319,32 @@ function simulate_dynamics_noisy(s::ILEQGSolver, problem::DeviceRiskSensitivePro
     return L_array === nothing ? (xs, cost) : (xs, [[u[:, t, k] for t in 1:N] for k in 1:K], cost)
 end
 
+"""
+evaluate_policy(s, problem, x_nom, l_array[, L_array]; thetas, K, z, seed, want_costs): Monte-Carlo evaluation of a policy under the
+problem's process noise (rat_policy_evaluate).  The K rollouts of simulate_dynamics_noisy, for a problem of any model kind
+(DeviceSourceProblem included), with the statistics of the K costs formed on the device.  Returns a named tuple: n_ok, n_domain
+(DomainError rollouts, left out of every statistic), mean, var, min, max, se_mean, risk[i] = (1/θ_i) log mean exp(θ_i J) (the mean at
+θ_i = 0), risk_se[i] (delta method), costs (K values, NaN for a DomainError rollout; `nothing` unless want_costs).
+"""
+function evaluate_policy(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_nom, l_array::Vector{Vector{Float64}},
+                         L_array::Union{Nothing,Vector{Matrix{Float64}}}=nothing; thetas=Float64[], K::Integer=1, z=nothing,
+                         seed::Integer=0, want_costs::Bool=false)
+    h = bind!(s.h, problem)
+    z === nothing || (K = size(z, 3))
+    xn = x_nom isa Vector{Float64} ? x_nom : flat(x_nom)
+    l = flat(l_array)
+    L = L_array === nothing ? C_NULL : flat(L_array)
+    th = collect(Float64, thetas); nth = length(th)
+    stats = zeros(8); risk = zeros(nth); risk_se = zeros(nth)
+    costs = want_costs ? Vector{Float64}(undef, K) : nothing
+    check(ccall((:rat_policy_evaluate, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, UInt64, Ptr{Float64}, Int32, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, xn, l, L, K, z === nothing ? C_NULL : z, UInt64(seed), th, nth, stats, risk, risk_se, want_costs ? costs : C_NULL))
+    (n_ok=Int(stats[1]), n_domain=Int(stats[2]), mean=stats[3], var=stats[4], min=stats[5], max=stats[6], se_mean=stats[7],
+     risk=risk, risk_se=risk_se, costs=costs)
+end
+
 "integrate_cost(problem, x_array, u_array) -- ileqg.jl:115-124"
 function integrate_cost(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_array, u_array)
     h = bind!(s.h, problem); c = Ref(0.0)
@@ -1161,7 +1187,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

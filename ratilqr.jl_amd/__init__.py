@@ -21,6 +21,7 @@ from .ileqg import (  # noqa: F401,E402
     DynamicProgrammingResult,
     simulate_dynamics,
     simulate_dynamics_noisy,
+    evaluate_policy,
     integrate_cost,
     approximate_model,
     solve_approximate_dp,

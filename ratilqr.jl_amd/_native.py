@@ -89,7 +89,9 @@ EXPORTS = [
     "rat_debug_set", "rat_debug_get", "rat_ce_update_dev",
     "rat_problem_set_source", "rat_problem_set_params", "rat_source_check",
     "rat_pets_problem_set_source", "rat_pets_set_params", "rat_pets_source_check",
+    "rat_policy_evaluate",
 ]
+MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 
 _lib = None
 
@@ -125,6 +127,7 @@ def lib():
         _lib.rat_pets_problem_set_source.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int64]
         _lib.rat_pets_set_params.argtypes = [C.c_void_p, _dp, C.c_int64]
         _lib.rat_pets_source_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        _lib.rat_policy_evaluate.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, _dp, C.c_uint64, _dp, C.c_int32, _dp, _dp, _dp, _dp]
     return _lib
 
 

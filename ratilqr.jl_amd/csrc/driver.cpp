@@ -22,6 +22,7 @@
 #include "layout.h"
 #include "wide.h"
 #include "ce_device.h"
+#include "policy_mc.h"
 #include "source_args.h"
 #include "source_model.h"
 
@@ -181,6 +182,19 @@ struct rat_handle_s {
     double *d_gsrc_p = nullptr; int64_t gsrc_np = 0;    // (d_gsrc_p lives in gen_allocs)
     int gsrc_npn = 0, gsrc_npu = 0;  // draws per step it declared
     int *h_gsrc_over = nullptr;      // pinned: the overdraw flag its kernel sets with a plain store (bit 0 normals, bit 1 uniforms)
+    // Monte-Carlo policy evaluation (rat_policy_evaluate, policy_mc.hip): scratch of the handle, allocated by the first call, grown on demand
+    // Source models run rat_src_noisy_rollout (source_noisy.h): a module of its own, compiled by the first evaluation of the problem
+    std::string src_text;            // the source problem's text and architecture, kept for that compile (a copy per source handle, a few kB:
+                                     // the process-wide cache keys on the text and holds only code objects)
+    std::string src_arch_name;
+    hipModule_t src_noisy_mod = nullptr;
+    hipFunction_t src_noisy = nullptr;
+    int src_mc_tpw = 64;             // switch src_mc_tpw: rollouts per wavefront of that kernel (16 / 32 / 64)
+    double *d_mc_cost = nullptr; size_t cap_mc_cost = 0;     // [K] rollout costs
+    int *d_mc_dom = nullptr; size_t cap_mc_dom = 0;          // [K] DomainError flags of the family kernel
+    double *d_mc_z = nullptr; size_t cap_mc_z = 0;           // injected normals of one chunk
+    double *d_mc_in = nullptr; size_t cap_mc_in = 0;         // Wchol | x_nom | l | L
+    double *d_mc_red = nullptr;                              // [MC_SCRATCH] partials and results of the reduction
 };
 
 extern "C" int32_t rat_version(void) { return RAT_VERSION; }
@@ -261,6 +275,7 @@ static const DebugSwitch debug_switches[] = {
     {"psw_comp", [](rat_handle h, int64_t v) { h->psw_comp = (int)std::max<int64_t>(100, v); }, [](rat_handle h) -> int64_t { return h->psw_comp; }},
     {"src_tpw", [](rat_handle h, int64_t v) { h->src_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_tpw; }},
     {"src_pets_tpw", [](rat_handle h, int64_t v) { h->src_pets_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_pets_tpw; }},
+    {"src_mc_tpw", [](rat_handle h, int64_t v) { h->src_mc_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_mc_tpw; }},
 };
 // what the requests amount to on this handle (speculation width, forced pairings)
 static void finish_switches(rat_handle h) {
@@ -351,6 +366,8 @@ extern "C" void rat_destroy(rat_handle h) {
     if (h->rec.m) (void)hipFree(h->rec.m);
     for (double *q : {h->d_pin, h->d_pzn, h->d_pzu, h->d_ptraj, h->d_pcost, h->d_pmu, h->d_psig}) if (q) (void)hipFree(q);
     if (h->d_perr) (void)hipFree(h->d_perr);
+    for (void *q : {(void *)h->d_mc_cost, (void *)h->d_mc_dom, (void *)h->d_mc_z, (void *)h->d_mc_in, (void *)h->d_mc_red}) if (q) (void)hipFree(q);
+    if (h->src_noisy_mod) (void)hipModuleUnload(h->src_noisy_mod);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
     if (h->h_pcost) (void)hipHostFree(h->h_pcost);
     for (auto &e : h->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -785,6 +802,9 @@ extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32
     h->pb_allocs.swap(allocs);
     if (h->src_mod) (void)hipModuleUnload(h->src_mod);
     h->src_mod = mod; h->src_roll = fr; h->src_lin = fl;
+    if (h->src_noisy_mod) (void)hipModuleUnload(h->src_noisy_mod);      // (the previous problem's Monte-Carlo kernel)
+    h->src_noisy_mod = nullptr; h->src_noisy = nullptr;
+    h->src_text = source; h->src_arch_name = src_arch(pr.gcnArchName);
     h->d_src_p = const_cast<double *>(dp); h->src_np = n_params;
     h->hW.assign(W, W + (size_t)(pb.W_tv ? N : 1) * n * n);
     h->W_tv = pb.W_tv;
@@ -1812,6 +1832,7 @@ extern "C" rat_rc rat_rollout_feedback(rat_handle h, const double *xbar, const d
 }
 
 static bool host_chol_lower(int n, const double *A, double *Lo);
+template <class T> static rat_rc grow(T **p, size_t *cap, size_t need);
 
 // simulate_dynamics(problem, x_0 | x_array, u_array | (l_array, L_array), rng)  -- ileqg.jl:44-55, :94-109
 extern "C" rat_rc rat_rollout_noisy(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
@@ -1908,6 +1929,124 @@ extern "C" rat_rc rat_rollout_noisy(rat_handle h, const double *x_nom, const dou
     freeall();
     if (domain_fail) *domain_fail = any_dom;
     return rc;
+}
+
+// K rollouts as rat_rollout_noisy runs them, reduced on the device (policy_mc.hip): mean, spread, extremes and the entropic risk
+// (1/theta) log E exp(theta J) that iLEQG minimises.  Every buffer is scratch of the handle; only the statistics (and, on request, the K
+// costs) come back.  The families and general sizes run noisy_rollout_kernel / WOP_NOISY unchanged -- chunks, Philox keys and all, so
+// cost_out is rat_rollout_noisy's bit for bit -- and source models run rat_src_noisy_rollout, a module of its own (source_noisy.h) that the
+// first evaluation of the problem compiles.
+extern "C" rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K, const double *z,
+                                      uint64_t seed, const double *theta, int32_t n_theta, double *stats, double *risk, double *risk_se,
+                                      double *cost_out) {
+    if (n_theta < 0 || n_theta > MC_MAX_THETA) return fail(RAT_ERR_ARG, "rat_policy_evaluate: n_theta must be in 0 .. 16");
+    if (n_theta > 0 && !theta) return fail(RAT_ERR_ARG, "rat_policy_evaluate: theta is null");
+    for (int i = 0; i < n_theta; ++i)
+        if (!(theta[i] >= 0.0)) return fail(RAT_ERR_ARG, "rat_policy_evaluate: every theta must be >= 0");
+    if (K < 1) return fail(RAT_ERR_ARG, "rat_policy_evaluate: K must be positive");
+    if (K > ((int64_t)1 << 27)) return fail(RAT_ERR_ARG, "rat_policy_evaluate: K must be at most 2^27 (the costs stay on the device, 8 bytes each)");
+    if (!h || !x_nom || !l || !stats) return fail(RAT_ERR_ARG, "null");
+    if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
+    HIPCHK(hipSetDevice(h->device));
+    const int n = h->n, m = h->m, N = h->N, Nw = h->W_tv ? N : 1;
+    const bool source = !h->wide && h->pb.model == RAT_MODEL_SOURCE;
+    // the policy and the lower Cholesky factors of W(k), packed for one upload: Wchol | x_nom | l | L (dense column-major at general
+    // size, the padded 12 + 4 layout otherwise)
+    std::vector<double> pack;
+    size_t o_x = 0, o_l = 0, o_L = 0;
+    if (h->wide) {
+        pack.assign((size_t)Nw * n * n, 0.0);
+        for (int k = 0; k < Nw; ++k)
+            if (!host_chol_lower(n, h->hW.data() + (size_t)k * n * n, pack.data() + (size_t)k * n * n))
+                return fail(RAT_ERR_ARG, "W(k) is not positive definite (MvNormal would throw)");
+        o_x = pack.size(); pack.insert(pack.end(), x_nom, x_nom + (L ? (size_t)(N + 1) * n : (size_t)n));
+        o_l = pack.size(); pack.insert(pack.end(), l, l + (size_t)N * m);
+        o_L = pack.size(); if (L) pack.insert(pack.end(), L, L + (size_t)N * m * n);
+    } else {
+        std::vector<double> Lc((size_t)n * n), xp, up, Lp;
+        pack.assign((size_t)Nw * 192, 0.0);
+        for (int k = 0; k < Nw; ++k) {
+            if (!host_chol_lower(n, h->hW.data() + (size_t)k * n * n, Lc.data()))
+                return fail(RAT_ERR_ARG, "W(k) is not positive definite (MvNormal would throw)");
+            for (int i = 0; i < n; ++i) for (int jj = 0; jj <= i; ++jj) pack[(size_t)k * 192 + i * 16 + jj] = Lc[i + n * jj];
+        }
+        if (L) { pad_x(h, x_nom, xp); pad_L(h, L, Lp); }
+        else { xp.assign((size_t)(N + 1) * XSTR, 0.0); for (int i = 0; i < n; ++i) xp[i] = x_nom[i]; }
+        pad_u(h, l, up);
+        o_x = pack.size(); pack.insert(pack.end(), xp.begin(), xp.end());
+        o_l = pack.size(); pack.insert(pack.end(), up.begin(), up.end());
+        o_L = pack.size(); pack.insert(pack.end(), Lp.begin(), Lp.end());
+    }
+    const int64_t chunk = std::min<int64_t>(K, 1 << 16);         // (rat_rollout_noisy's chunks: injected normals are staged chunk by chunk)
+    rat_rc rc;
+    if (source && !h->src_noisy) {                                // the first evaluation of this source problem compiles its rollout kernel
+        std::shared_ptr<const std::vector<char>> code;
+        std::string log;
+        if ((rc = src_compile_noisy(h->src_text.c_str(), n, m, h->src_arch_name, &code, &log))) return fail(rc, log);
+        hipModule_t mod = nullptr;
+        hipFunction_t fn = nullptr;
+        HIPCHK(hipModuleLoadData(&mod, code->data()));
+        if (hipModuleGetFunction(&fn, mod, "rat_src_noisy_rollout") != hipSuccess) {
+            (void)hipModuleUnload(mod);
+            return fail(RAT_ERR_HIP, "rat_policy_evaluate: the compiled module lacks its kernel");
+        }
+        h->src_noisy_mod = mod; h->src_noisy = fn;
+    }
+    // the handle's scratch: allocated by the first call, grown on demand, kept until rat_destroy (a buffer that grows is freed first:
+    // every earlier call has finished, the entry point is synchronous)
+    const size_t one = 1;
+    size_t cap_red = h->d_mc_red ? MC_SCRATCH : 0;
+    if ((rc = grow(&h->d_mc_in, &h->cap_mc_in, pack.size()))) return rc;
+    if ((rc = grow(&h->d_mc_cost, &h->cap_mc_cost, std::max((size_t)K, one)))) return rc;
+    if ((rc = grow(&h->d_mc_red, &cap_red, (size_t)MC_SCRATCH))) return rc;
+    if (!source && !h->wide && (rc = grow(&h->d_mc_dom, &h->cap_mc_dom, (size_t)K))) return rc;
+    if (z && (rc = grow(&h->d_mc_z, &h->cap_mc_z, (size_t)chunk * N * n))) return rc;
+    HIPCHK(hipMemcpy(h->d_mc_in, pack.data(), pack.size() * 8, hipMemcpyHostToDevice));
+    const double *d_wc = h->d_mc_in, *d_x = h->d_mc_in + o_x, *d_l = h->d_mc_in + o_l, *d_L = L ? h->d_mc_in + o_L : nullptr;
+    int *d_dom = (source || h->wide) ? nullptr : h->d_mc_dom;
+    // general sizes with the generator: one launch, as rat_rollout_noisy runs it (the rollout index is the Philox counter)
+    const int64_t step = (h->wide && !z) ? K : chunk;
+    for (int64_t k0 = 0; k0 < K; k0 += step) {
+        const int64_t kc = std::min(step, K - k0);
+        if (z) {
+            HIPCHK(hipStreamSynchronize(h->stream));              // (the previous chunk's rollouts read the staging area)
+            HIPCHK(hipMemcpy(h->d_mc_z, z + (size_t)k0 * N * n, (size_t)kc * N * n * 8, hipMemcpyHostToDevice));
+        }
+        const uint64_t cseed = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(k0 / chunk);     // distinct Philox keys per chunk
+        if (h->wide) {
+            WideOpArgs a = wide_op_args(h, WOP_NOISY, (long)kc);
+            a.xbar = d_x; a.l = d_l; a.L = d_L; a.z = z ? h->d_mc_z : nullptr; a.seed = seed; a.Wchol = d_wc;
+            a.cost_out = h->d_mc_cost + k0;
+            HIPCHK(launch_wide_op(a, h->stream));
+        } else if (source) {
+            SrcNoisyArgs a;
+            a.Wchol = d_wc; a.xnom = d_x; a.l = d_l; a.L = d_L; a.z = z ? h->d_mc_z : nullptr; a.K = (long)kc; a.N = N; a.W_tv = h->W_tv;
+            a.tpw = h->src_mc_tpw; a.seed = cseed; a.cost = h->d_mc_cost + k0; a.p = h->d_src_p;
+            void *args[] = {&a};
+            HIPCHK(hipModuleLaunchKernel(h->src_noisy, (unsigned)((kc + a.tpw - 1) / a.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+        } else {
+            NoisyArgs a;
+            a.pb = h->pb; a.Wchol = d_wc; a.xnom = d_x; a.l = d_l; a.L = d_L; a.K = (long)kc; a.z = z ? h->d_mc_z : nullptr;
+            a.seed = cseed; a.x_out = nullptr; a.u_out = nullptr; a.cost = h->d_mc_cost + k0; a.dom = d_dom + k0;
+            launch_noisy_rollout(a, h->stream);
+        }
+    }
+    McArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.cost = h->d_mc_cost; ma.dom = d_dom; ma.K = (long)K; ma.n_theta = n_theta; ma.scratch = h->d_mc_red;
+    for (int i = 0; i < n_theta; ++i) ma.theta[i] = theta[i];
+    launch_policy_mc(ma, h->stream);
+    HIPCHK(hipGetLastError());
+    double out[MC_OUT];
+    HIPCHK(hipMemcpyAsync(out, h->d_mc_red + (MC_P1 + MC_P2) * MC_BLOCKS, sizeof(out), hipMemcpyDeviceToHost, h->stream));
+    if (cost_out) HIPCHK(hipMemcpyAsync(cost_out, h->d_mc_cost, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < RAT_MC_NSTAT; ++i) stats[i] = out[i];
+    for (int i = 0; i < n_theta; ++i) {
+        if (risk) risk[i] = out[8 + i];
+        if (risk_se) risk_se[i] = out[8 + MC_MAX_THETA + i];
+    }
+    return RAT_OK;
 }
 
 static rat_rc linearize_slot0(rat_handle h, const double *u, const double *x, std::vector<double> *tiles, int32_t *domain_fail) {
@@ -3041,11 +3180,11 @@ extern "C" void rat_pets_initialize(rat_pets_solver *s) {                     //
     memcpy(s->Sigma, s->Sigma_init, sizeof(double) * s->N * s->m * s->m);
 }
 
-static rat_rc grow(double **p, size_t *cap, size_t need) {
+template <class T> static rat_rc grow(T **p, size_t *cap, size_t need) {
     if (need <= *cap) return RAT_OK;
     if (*p) (void)hipFree(*p);
     *p = nullptr; *cap = 0;
-    HIPCHK(hipMalloc((void **)p, need * sizeof(double)));
+    HIPCHK(hipMalloc((void **)p, need * sizeof(T)));
     *cap = need;
     return RAT_OK;
 }

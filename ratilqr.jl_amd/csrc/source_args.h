@@ -40,3 +40,19 @@ struct SrcPetsArgs {
     const double *p;          // the model's parameters
     int *overdraw;            // set (plain store) when a step draws more than it declared: 1 normals, 2 uniforms
 };
+
+// rat_src_noisy_rollout (source_noisy.h): simulate_dynamics with rng (ileqg.jl:44-55, :94-109) + integrate_cost (:115-124) of a source
+// model, one lane per Monte-Carlo rollout (rat_policy_evaluate)
+struct SrcNoisyArgs {
+    const double *Wchol;      // [Nw][12][16] lower Cholesky factors of W(k), row-major, zero padded
+    const double *xnom;       // [(N+1)][12] nominal states (open loop: only row 0 is read)
+    const double *l;          // [N][4]
+    const double *L;          // [N][4][12] or null (open loop)
+    const double *z;          // [K][N][n] injected N(0,1) draws or null (Philox keyed by seed)
+    long K;
+    int N, W_tv;
+    int tpw;                  // rollouts per wavefront (lanes 0 .. tpw-1 of each 64-lane workgroup work)
+    unsigned long long seed;
+    double *cost;             // [K]; NaN where the rollout hit a DomainError
+    const double *p;          // the model's parameters
+};

@@ -18,5 +18,9 @@ rat_rc src_compile(const char *source, int n, int m, const std::string &arch, st
 // risk-sensitive compiles of the same text.
 rat_rc src_compile_gen(const char *source, int n, int m, int npn, int npu, const std::string &arch,
                        std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
+// The Monte-Carlo rollout kernel of a risk-sensitive source (rat_policy_evaluate): source_noisy.h after it.  A third kind with a cache key
+// of its own, compiled on the first evaluation of a source problem, not when the problem is set.
+rat_rc src_compile_noisy(const char *source, int n, int m, const std::string &arch, std::shared_ptr<const std::vector<char>> *code,
+                         std::string *log, double *ms = nullptr, bool *cached = nullptr);
 // The offload-arch string for the device's reported gcnArchName (an xnack+ feature is never passed on).
 std::string src_arch(const char *gcn_arch_name);

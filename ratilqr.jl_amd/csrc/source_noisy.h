@@ -1,0 +1,105 @@
+// source_noisy.h -- the Monte-Carlo rollout kernel of source models (rat_policy_evaluate, include/ratilqr.h).  Compiled by hiprtc behind the
+// user's source (rat_user_f / rat_user_c / rat_user_h; RAT_N, RAT_M from the command line) as a module of its own, on the first
+// rat_policy_evaluate of a source problem: a handle that never evaluates a policy never pays for it (as a third kernel of the model
+// module it lengthened that module's compile by 7-16 %, around and over the tenth allowed: DESIGN.md section 7, profiles/policy_mc.md).  The library embeds this header at build time (Makefile: source_embed.inc).
+#pragma once
+#include "rat_normal.h"
+#include "rat_philox.h"
+#include "source_args.h"
+
+#if !defined(RAT_N) || !defined(RAT_M)
+#error "RAT_N and RAT_M must be defined"
+#endif
+#if RAT_N > SRC_MAX_N || RAT_M > SRC_MAX_M
+#error "source models are compiled for n <= 12, m <= 4"
+#endif
+
+__device__ inline bool srcn_nan(double v) { return v != v; }
+
+// ---- noisy rollout: one lane per Monte-Carlo rollout, the state in registers ------------------------------------------------------------
+// noisy_rollout_kernel (kernels.hip) restated for a model the library does not know at build time: x_{t+1} = f(x_t, u_t) + chol_lower(W(t)) z_t
+// open loop or under u_t = l_t + L_t (x_t - xbar_t), and the realised cost c(0, x_0, u_0) + ... + c(N-1, ..) + h(x_N) of every rollout.
+// The noise is the family kernel's: injected z at (k N + t) n + j, or Philox4x32-10 with counter (k lo, k hi, t >> 1, j) and key (seed lo,
+// seed hi), both outputs of one Box-Muller transform for steps 2 i and 2 i + 1 -- a seed names the same noise for a family problem and for
+// the same problem written as source.  The products with the Cholesky factor run over its lower triangle in the family kernel's order
+// (the zeros it adds beyond the diagonal change nothing).  A DomainError rollout writes NaN.
+extern "C" __global__ __launch_bounds__(64) void rat_src_noisy_rollout(SrcNoisyArgs a) {
+    const int lane = threadIdx.x;
+    const long k = (long)blockIdx.x * a.tpw + lane;
+    if (lane >= a.tpw || k >= a.K) return;
+    const int N = a.N;
+    double x[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) x[q] = (q < RAT_N) ? a.xnom[q] : 0.0;
+    double znext[RAT_N];
+#pragma unroll
+    for (int q = 0; q < RAT_N; ++q) znext[q] = 0.0;
+    double cost = 0.0;
+    int dom = 0;
+    for (int t = 0; t < N; ++t) {
+        double u[4];
+        if (a.L) {
+            double dx[12];
+#pragma unroll
+            for (int q = 0; q < 12; ++q) dx[q] = x[q] - a.xnom[(long)t * XSTR + q];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double *Lr = a.L + (long)t * LSTR + j * 12;
+                double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {                         // L_t (x_t - xbar_t)   (ileqg.jl:104), rat_src_rollout's order (source_kernels.h)
+                    a0 = __builtin_fma(Lr[q], dx[q], a0);
+                    a1 = __builtin_fma(Lr[4 + q], dx[4 + q], a1);
+                    a2 = __builtin_fma(Lr[8 + q], dx[8 + q], a2);
+                }
+                u[j] = a.l[(long)t * USTR + j] + ((a0 + a1) + a2);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) u[j] = a.l[(long)t * USTR + j];
+        }
+        bool inok = true;
+#pragma unroll
+        for (int q = 0; q < RAT_N; ++q) inok = inok && !srcn_nan(x[q]);
+#pragma unroll
+        for (int q = 0; q < RAT_M; ++q) inok = inok && !srcn_nan(u[q]);
+        const double ct = rat_user_c<double>(t, x, u, a.p);           // integrate_cost: c(t, x_t, u_t) in order   (ileqg.jl:118-121)
+        cost += ct;
+        double xn[RAT_N];
+        rat_user_f<double>(x, u, xn, a.p);
+        bool outnan = srcn_nan(ct);
+#pragma unroll
+        for (int q = 0; q < RAT_N; ++q) outnan = outnan || srcn_nan(xn[q]);
+        if (inok && outnan) dom = 1;                                  // the reference's DomainError
+        double z[RAT_N];
+        if (a.z) {
+#pragma unroll
+            for (int q = 0; q < RAT_N; ++q) z[q] = a.z[(k * N + t) * (long)RAT_N + q];
+        } else if ((t & 1) == 0) {
+#pragma unroll
+            for (int q = 0; q < RAT_N; ++q) {
+                unsigned r[4];
+                philox4x32_10((unsigned)k, (unsigned)(k >> 32), (unsigned)(t >> 1), (unsigned)q, (unsigned)a.seed, (unsigned)(a.seed >> 32), r);
+                ratn_box_muller(u01(r[0], r[1]), u01(r[2], r[3]), &z[q], &znext[q]);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < RAT_N; ++q) z[q] = znext[q];
+        }
+        const double *__restrict__ Wc = a.Wchol + (a.W_tv ? (long)t * 192 : 0);
+#pragma unroll
+        for (int i = 0; i < RAT_N; ++i) {
+            double w = 0.0;                                           // w_t = chol_lower(W(t)) z_t
+#pragma unroll
+            for (int q = 0; q <= i; ++q) w = __builtin_fma(Wc[i * 16 + q], z[q], w);
+            x[i] = xn[i] + w;
+        }
+    }
+    bool inok = true;
+#pragma unroll
+    for (int q = 0; q < RAT_N; ++q) inok = inok && !srcn_nan(x[q]);
+    const double hc = rat_user_h<double>(x, a.p);                     // ... then h(x_N)   (ileqg.jl:122)
+    if (inok && srcn_nan(hc)) dom = 1;
+    cost += hc;
+    a.cost[k] = dom ? __builtin_nan("") : cost;
+}

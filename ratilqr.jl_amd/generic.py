@@ -181,6 +181,9 @@ class GenericContext(il.Context):
     def rollout_noisy(self, *a, **k):
         self._carrier_only("rollout_noisy (simulate_dynamics with rng)")
 
+    def policy_evaluate(self, *a, **k):
+        self._carrier_only("policy_evaluate")
+
     def solve_batch(self, *a, **k):
         self._carrier_only("solve_batch")
 

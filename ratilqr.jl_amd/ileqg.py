@@ -99,6 +99,29 @@ class Context:
                                             C.c_int64(K), nv.P(z), C.c_uint64(int(seed)), nv.P(x), nv.P(u), nv.P(cost), C.byref(dom)))
         return x, u, cost, bool(dom.value)
 
+    def policy_evaluate(self, x_nom, l, L=None, thetas=(), K=None, z=None, seed=0, want_costs=False):
+        """Monte-Carlo evaluation of a policy (rat_policy_evaluate): the K rollouts of rollout_noisy -- open loop with L=None and
+        x_nom = x_0, or under u = l + L (x - x_nom) -- for a problem of any model kind, source models included, with the statistics of
+        the K costs formed on the device.  thetas: up to 16 risk parameters >= 0.  Returns a dict: n_ok, n_domain (rollouts that hit a
+        DomainError: left out of every statistic), mean, var (unbiased), min, max, se_mean, risk[i] = (1/theta_i) log mean exp(theta_i J)
+        (the mean at theta_i = 0), risk_se[i] (delta method), costs ((K,), NaN for a DomainError rollout; None unless want_costs)."""
+        if z is not None:
+            z = nv.f64(z)
+            K = z.shape[0]
+        if K is None:
+            raise ValueError("policy_evaluate needs K= or z=")
+        K = int(K)
+        th = nv.f64(np.atleast_1d(np.asarray(thetas, dtype=np.float64))).ravel()
+        stats, risk, se = np.zeros(nv.MC_NSTAT), np.zeros(th.size), np.zeros(th.size)
+        costs = np.zeros(max(K, 0)) if want_costs else None
+        nv.check(nv.lib().rat_policy_evaluate(self.h, nv.P(nv.f64(x_nom)), nv.P(nv.f64(l)), nv.P(nv.cm3(L)) if L is not None else None,
+                                              C.c_int64(K), nv.P(z), C.c_uint64(int(seed)), nv.P(th) if th.size else None,
+                                              C.c_int32(th.size), nv.P(stats), nv.P(risk) if th.size else None,
+                                              nv.P(se) if th.size else None, nv.P(costs)))
+        return dict(n_ok=int(stats[nv.MC_N_OK]), n_domain=int(stats[nv.MC_N_DOMAIN]), mean=float(stats[nv.MC_MEAN]),
+                    var=float(stats[nv.MC_VAR]), min=float(stats[nv.MC_MIN]), max=float(stats[nv.MC_MAX]),
+                    se_mean=float(stats[nv.MC_SE_MEAN]), risk=risk, risk_se=se, costs=costs)
+
     def integrate_cost(self, x, u):
         out = C.c_double()
         nv.check(nv.lib().rat_integrate_cost(self.h, nv.P(nv.f64(x)), nv.P(nv.f64(u)), C.byref(out)))
@@ -363,6 +386,12 @@ def simulate_dynamics_noisy(problem, a, b, c=None, K=1, z=None, seed=0):
     if dom:
         raise ArithmeticError("DomainError in simulate_dynamics")
     return (x, cost) if c is None else (x, u, cost)
+
+
+def evaluate_policy(problem, x, l, L=None, thetas=(), K=None, z=None, seed=0, want_costs=False):
+    """Monte-Carlo evaluation of the policy (x, l, L) that solve_ returned -- or of an open-loop plan (x_0, u_array) with L=None -- under
+    the problem's process noise: Context.policy_evaluate on the problem's default context.  DeviceSourceProblem included."""
+    return _ctx(problem).policy_evaluate(x, l, L, thetas=thetas, K=K, z=z, seed=seed, want_costs=want_costs)
 
 
 def integrate_cost(problem, x_array, u_array):          # ileqg.jl:115-124
