@@ -133,9 +133,20 @@ rat_rc rat_problem_set(rat_handle h, const rat_problem_desc *desc);
  *
  * with A n x n and B n x m column-major: exact Jacobians instead of AD for f.  A NaN in x_{t+1} or in a cost whose inputs had none is
  * the reference's DomainError (RAT_ST_DOMAIN, value Inf).  No fast-math.
+ * Optionally, for Monte-Carlo evaluation under a disturbance of the user's own (rat_policy_evaluate_noise, below), the source defines
+ * RAT_USER_NOISE and
+ *
+ *   template <class R>
+ *   __device__ void rat_user_noise(int k, const double *x, const double *u, R &rng, double *w, const double *p);
+ *
+ * which writes w[0 .. RAT_N): the rollout is x_{k+1} = f(x_k, u_k) + w.  x and u are the state and control of step k, so the noise may
+ * depend on them; w arrives zeroed.  rng is the rat_rng of generative source models (below): rng.normal() is N(0, 1), rng.uniform() is
+ * U[0, 1), counted per step against the draw counts the caller declares, which the compile line carries as RAT_PETS_NORMALS and
+ * RAT_PETS_UNIFORMS.  A source without RAT_USER_NOISE compiles and behaves exactly as before.
  * Limits: n <= 12, m <= 4 (else RAT_ERR_UNSUPPORTED); batches run on the round-based path (rat_set_path FUSED / BLOCK return
  * RAT_ERR_UNSUPPORTED); rat_rollout_noisy and rat_multi are not available for source models: rat_policy_evaluate with cost_out is the way
- * to their Monte-Carlo costs.  PETS takes generative source models of its own (rat_pets_problem_set_source, below). */
+ * to their Monte-Carlo costs, and rat_policy_evaluate_noise with x_out / u_out the way to Monte-Carlo trajectories (under the user's
+ * sampler only).  PETS takes generative source models of its own (rat_pets_problem_set_source, below). */
 #define RAT_MODEL_SOURCE    3
 
 /* Compile `source` (NUL-terminated) for the handle's device and make it the handle's problem.  W: n*n column-major, N entries if W_tv
@@ -148,6 +159,9 @@ rat_rc rat_problem_set_source(rat_handle h, const char *source, int32_t n, int32
 rat_rc rat_problem_set_params(rat_handle h, const double *params, int64_t n_params);
 /* Compile only, for gfx950 (no device needed): RAT_OK, RAT_ERR_ARG with the log in rat_last_error(), or RAT_ERR_UNSUPPORTED. */
 rat_rc rat_source_check(const char *source, int32_t n, int32_t m);
+/* The same for the kernel of rat_policy_evaluate_noise: `source` must define RAT_USER_NOISE and rat_user_noise (else RAT_ERR_ARG, and the
+ * message says so); negative draw counts are RAT_ERR_ARG. */
+rat_rc rat_user_noise_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms);
 
 /* ---- the hot path ----------------------------------------------------------------------------- */
 
@@ -219,6 +233,27 @@ rat_rc rat_rollout_noisy(rat_handle h, const double *x_nom, const double *l, con
 rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
                            const double *z, uint64_t seed, const double *theta, int32_t n_theta,
                            double *stats, double *risk, double *risk_se, double *cost_out);
+/* rat_policy_evaluate for a source model under the user's own process noise: w_k = rat_user_noise(k, x_k, u_k, rng) ("source models"
+ * above) in place of chol_lower(W(k)) z_k.  W is not read: the sampler is the whole disturbance.  x_nom, l, L, K, theta, n_theta, stats,
+ * risk, risk_se, cost_out and the range of K mean exactly what they mean for rat_policy_evaluate, and the K costs go through the same
+ * fixed-order reduction: two calls with the same arguments return the same bits.
+ *   normals_per_step, uniforms_per_step   the most rng.normal() / rng.uniform() calls one step makes (>= 0, else RAT_ERR_ARG); the rollout
+ *                         kernel is compiled for them by the first call that names them (cached per process by source, n, m, the two
+ *                         counts and the architecture); a step that draws more gets NaN and the call returns RAT_ERR_ARG naming the
+ *                         limits (the handle stays usable)
+ *   zn, zu                injected draws: the i-th normal / uniform of rollout j at step t is zn[(j N + t) normals_per_step + i] /
+ *                         zu[(j N + t) uniforms_per_step + i]; every stream with a positive count must be given (else RAT_ERR_ARG).  Both
+ *                         NULL: the device generator, Philox4x32-10 keyed by seed with the rollout's index j in the counter (the keying
+ *                         of generative source models, below) -- a rollout's noise does not depend on K
+ *   x_out, u_out          [n x (N+1) x K], [m x N x K] dense column-major, rollout slowest (rat_rollout_noisy's layout); either may be
+ *                         NULL.  They are staged on the device 2^16 rollouts at a time.  A DomainError rollout holds what was computed
+ * The five noise fields are arguments of the call, as in rat_pets_compute_cost, not a descriptor struct.  A NaN in w whose inputs x_k, u_k
+ * had none is a DomainError, like a NaN in f or a cost.  Refusals: a problem that is not a source model RAT_ERR_UNSUPPORTED; a source
+ * without RAT_USER_NOISE, or one that does not compile, RAT_ERR_ARG with the compiler's log (model.hip:LINE) in rat_last_error(). */
+rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
+                                 int32_t normals_per_step, int32_t uniforms_per_step, const double *zn, const double *zu, uint64_t seed,
+                                 const double *theta, int32_t n_theta, double *stats, double *risk, double *risk_se, double *cost_out,
+                                 double *x_out, double *u_out);
 /* approximate_model(problem, u_array, x_array)                 ileqg.jl:258-322
  * -> q[N+1], qv[n*(N+1)], Q[n*n*(N+1)], r[m*N], R[m*m*N], P[m*n*N], A[n*n*N], B[n*m*N], W[n*n*N] */
 rat_rc rat_approximate_model(rat_handle h, const double *u, const double *x,

@@ -232,6 +232,25 @@ end
 problem_set!(h::MultiHandle, p::DeviceSourceProblem) = throw(ArgumentError("rat_multi does not take source models"))
 "Compile a source model for gfx950 without a device (throws with the compiler's log)."
 source_check(source::AbstractString, n::Integer, m::Integer) = check(ccall((:rat_source_check, LIB), Int32, (Cstring, Int32, Int32), source, n, m))
+
+"""
+UserNoise(normals_per_step, uniforms_per_step; zn, zu, seed): the disturbance of evaluate_policy(...; noise=...) for a source that defines
+RAT_USER_NOISE and rat_user_noise (include/ratilqr.h "source models"): the most rng.normal() / rng.uniform() calls of one step, and
+where the draws come from -- injected streams zn (normals_per_step×N×K) and zu (uniforms_per_step×N×K), every declared one, or the
+device generator keyed by `seed`.
+"""
+struct UserNoise
+    normals_per_step::Int32
+    uniforms_per_step::Int32
+    zn::Union{Nothing,Array{Float64}}
+    zu::Union{Nothing,Array{Float64}}
+    seed::UInt64
+end
+UserNoise(normals_per_step::Integer, uniforms_per_step::Integer=0; zn=nothing, zu=nothing, seed::Integer=0) =
+    UserNoise(Int32(normals_per_step), Int32(uniforms_per_step), zn, zu, UInt64(seed))
+"user_noise_check(source, n, m; normals_per_step, uniforms_per_step): compile the rollout kernel under the source's own sampler only (rat_user_noise_check)"
+user_noise_check(source::AbstractString, n::Integer, m::Integer; normals_per_step::Integer=0, uniforms_per_step::Integer=0) =
+    check(ccall((:rat_user_noise_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32), source, n, m, normals_per_step, uniforms_per_step))
 "Re-bind the handle when it is called with a problem other than the one its device tables were built from."
 bind!(h::Union{Handle,MultiHandle}, p) = (h.problem === p || problem_set!(h, p); h)
 
@@ -325,10 +344,13 @@ problem's process noise (rat_policy_evaluate).  The K rollouts of simulate_dynam
 (DeviceSourceProblem included), with the statistics of the K costs formed on the device.  Returns a named tuple: n_ok, n_domain
 (DomainError rollouts, left out of every statistic), mean, var, min, max, se_mean, risk[i] = (1/θ_i) log mean exp(θ_i J) (the mean at
 θ_i = 0), risk_se[i] (delta method), costs (K values, NaN for a DomainError rollout; `nothing` unless want_costs).
+With noise=UserNoise(...) (source problems only) the disturbance is the one the source's rat_user_noise draws (rat_policy_evaluate_noise;
+z and seed are then the UserNoise's own), and want_trajectories adds x (K state arrays) and u (K control arrays) to the tuple.
 """
 function evaluate_policy(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_nom, l_array::Vector{Vector{Float64}},
                          L_array::Union{Nothing,Vector{Matrix{Float64}}}=nothing; thetas=Float64[], K::Integer=1, z=nothing,
-                         seed::Integer=0, want_costs::Bool=false)
+                         seed::Integer=0, want_costs::Bool=false, noise::Union{Nothing,UserNoise}=nothing,
+                         want_trajectories::Bool=false)
     h = bind!(s.h, problem)
     z === nothing || (K = size(z, 3))
     xn = x_nom isa Vector{Float64} ? x_nom : flat(x_nom)
@@ -336,6 +358,26 @@ function evaluate_policy(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_
     L = L_array === nothing ? C_NULL : flat(L_array)
     th = collect(Float64, thetas); nth = length(th)
     stats = zeros(8); risk = zeros(nth); risk_se = zeros(nth)
+    if noise !== nothing
+        z === nothing || throw(ArgumentError("evaluate_policy: with noise the injected draws are noise.zn / noise.zu, not z"))
+        n, m, N = dims(problem)
+        noise.zn === nothing || (K = size(noise.zn, 3))
+        noise.zn === nothing && noise.zu !== nothing && (K = size(noise.zu, 3))
+        costs = want_costs ? Vector{Float64}(undef, K) : nothing
+        x = want_trajectories ? Array{Float64}(undef, n, N + 1, K) : nothing
+        u = want_trajectories ? Array{Float64}(undef, m, N, K) : nothing
+        check(ccall((:rat_policy_evaluate_noise, LIB), Int32,
+                    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, UInt64,
+                     Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    h.ptr, xn, l, L, K, noise.normals_per_step, noise.uniforms_per_step, noise.zn === nothing ? C_NULL : noise.zn,
+                    noise.zu === nothing ? C_NULL : noise.zu, noise.seed, th, nth, stats, risk, risk_se, want_costs ? costs : C_NULL,
+                    want_trajectories ? x : C_NULL, want_trajectories ? u : C_NULL))
+        return (n_ok=Int(stats[1]), n_domain=Int(stats[2]), mean=stats[3], var=stats[4], min=stats[5], max=stats[6], se_mean=stats[7],
+                risk=risk, risk_se=risk_se, costs=costs,
+                x=want_trajectories ? [[x[:, t, k] for t in 1:N+1] for k in 1:K] : nothing,
+                u=want_trajectories ? [[u[:, t, k] for t in 1:N] for k in 1:K] : nothing)
+    end
+    want_trajectories && throw(ArgumentError("evaluate_policy: trajectories come with noise=UserNoise(...) only"))
     costs = want_costs ? Vector{Float64}(undef, K) : nothing
     check(ccall((:rat_policy_evaluate, LIB), Int32,
                 (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, UInt64, Ptr{Float64}, Int32, Ptr{Float64},
@@ -1185,7 +1227,7 @@ function solve!(s::NelderMeadBilevelOptimizationSolver, problem, x_0::Vector{Flo
     R.solve!(ref, problem, x_0, u_array; kl_bound=kl_bound, verbose=verbose)
 end
 
-export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check,
+export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
        simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,

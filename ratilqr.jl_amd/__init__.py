@@ -16,6 +16,7 @@ from ._native import RatError, SO_PATH  # noqa: F401,E402
 from . import _native as native  # noqa: F401,E402
 from .ileqg import (  # noqa: F401,E402
     Context,
+    UserNoise,
     ILEQGSolver,
     ApproximationResult,
     DynamicProgrammingResult,

@@ -90,6 +90,7 @@ EXPORTS = [
     "rat_problem_set_source", "rat_problem_set_params", "rat_source_check",
     "rat_pets_problem_set_source", "rat_pets_set_params", "rat_pets_source_check",
     "rat_policy_evaluate",
+    "rat_policy_evaluate_noise", "rat_user_noise_check",
 ]
 MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 
@@ -128,6 +129,9 @@ def lib():
         _lib.rat_pets_set_params.argtypes = [C.c_void_p, _dp, C.c_int64]
         _lib.rat_pets_source_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
         _lib.rat_policy_evaluate.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, _dp, C.c_uint64, _dp, C.c_int32, _dp, _dp, _dp, _dp]
+        _lib.rat_policy_evaluate_noise.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, C.c_uint64, _dp,
+                                                   C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]
+        _lib.rat_user_noise_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     return _lib
 
 
@@ -173,6 +177,12 @@ def _wbuf(prob):
 def source_check(source, n, m):
     """rat_source_check: compile only (gfx950, no device needed); raises RatError with the compiler's log."""
     check(lib().rat_source_check(str(source).encode(), int(n), int(m)))
+
+
+def user_noise_check(source, n, m, normals_per_step=0, uniforms_per_step=0):
+    """rat_user_noise_check: compile a source's rollout kernel under its own rat_user_noise only (gfx950, no device needed); raises
+    RatError with the compiler's log, or saying that the source does not define RAT_USER_NOISE."""
+    check(lib().rat_user_noise_check(str(source).encode(), int(n), int(m), int(normals_per_step), int(uniforms_per_step)))
 
 
 def pets_set_source(h, prob):

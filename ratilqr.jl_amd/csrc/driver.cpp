@@ -195,6 +195,16 @@ struct rat_handle_s {
     double *d_mc_z = nullptr; size_t cap_mc_z = 0;           // injected normals of one chunk
     double *d_mc_in = nullptr; size_t cap_mc_in = 0;         // Wchol | x_nom | l | L
     double *d_mc_red = nullptr;                              // [MC_SCRATCH] partials and results of the reduction
+    // ... under the user's noise sampler (rat_policy_evaluate_noise): rat_src_user_noisy_rollout (source_user_noise.h), a module of its own
+    // compiled for the declared draw counts by the first call that needs it
+    hipModule_t src_un_mod = nullptr;
+    hipFunction_t src_un = nullptr;
+    int src_un_npn = -1, src_un_npu = -1;                    // the draw counts the loaded module was compiled for
+    int64_t src_un_loads = 0;                                // switch src_un_loads (read only): modules this handle compiled or fetched from the cache
+    int *h_un_over = nullptr;                                // pinned: that kernel's overdraw flag (bit 0 normals, bit 1 uniforms)
+    double *d_mc_zu = nullptr; size_t cap_mc_zu = 0;         // injected uniforms of one chunk (the normals use d_mc_z)
+    double *d_mc_xo = nullptr; size_t cap_mc_xo = 0;         // [chunk][N+1][n] trajectory staging
+    double *d_mc_uo = nullptr; size_t cap_mc_uo = 0;         // [chunk][N][m]
 };
 
 extern "C" int32_t rat_version(void) { return RAT_VERSION; }
@@ -276,6 +286,7 @@ static const DebugSwitch debug_switches[] = {
     {"src_tpw", [](rat_handle h, int64_t v) { h->src_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_tpw; }},
     {"src_pets_tpw", [](rat_handle h, int64_t v) { h->src_pets_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_pets_tpw; }},
     {"src_mc_tpw", [](rat_handle h, int64_t v) { h->src_mc_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_mc_tpw; }},
+    {"src_un_loads", [](rat_handle, int64_t) {}, [](rat_handle h) -> int64_t { return h->src_un_loads; }},
 };
 // what the requests amount to on this handle (speculation width, forced pairings)
 static void finish_switches(rat_handle h) {
@@ -368,6 +379,9 @@ extern "C" void rat_destroy(rat_handle h) {
     if (h->d_perr) (void)hipFree(h->d_perr);
     for (void *q : {(void *)h->d_mc_cost, (void *)h->d_mc_dom, (void *)h->d_mc_z, (void *)h->d_mc_in, (void *)h->d_mc_red}) if (q) (void)hipFree(q);
     if (h->src_noisy_mod) (void)hipModuleUnload(h->src_noisy_mod);
+    for (double *q : {h->d_mc_zu, h->d_mc_xo, h->d_mc_uo}) if (q) (void)hipFree(q);
+    if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
+    if (h->h_un_over) (void)hipHostFree(h->h_un_over);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
     if (h->h_pcost) (void)hipHostFree(h->h_pcost);
     for (auto &e : h->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -756,6 +770,22 @@ extern "C" rat_rc rat_source_check(const char *source, int32_t n, int32_t m) {
     return RAT_OK;
 }
 
+static rat_rc user_noise_args_ok(const char *who, int n, int m, int npn, int npu) {
+    if (n < 1 || m < 1) return fail(RAT_ERR_ARG, std::string(who) + ": n, m must be positive");
+    if (npn < 0 || npu < 0) return fail(RAT_ERR_ARG, std::string(who) + ": normals_per_step, uniforms_per_step must not be negative");
+    if (!src_sizes_ok(n, m)) return fail(RAT_ERR_UNSUPPORTED, std::string(who) + ": source models are compiled for n <= 12, m <= 4");
+    return RAT_OK;
+}
+
+extern "C" rat_rc rat_user_noise_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms) {
+    if (!source) return fail(RAT_ERR_ARG, "null");
+    rat_rc rc = user_noise_args_ok("rat_user_noise_check", n, m, normals, uniforms);
+    if (rc) return rc;
+    std::string log;
+    if ((rc = src_compile_user_noise(source, n, m, normals, uniforms, "gfx950", nullptr, &log))) return fail(rc, log);
+    return RAT_OK;
+}
+
 extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32_t n, int32_t m, int32_t N, const double *W, int32_t W_tv,
                                          const double *params, int64_t n_params) {
     if (!h || !source || !W) return fail(RAT_ERR_ARG, "null");
@@ -804,6 +834,8 @@ extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32
     h->src_mod = mod; h->src_roll = fr; h->src_lin = fl;
     if (h->src_noisy_mod) (void)hipModuleUnload(h->src_noisy_mod);      // (the previous problem's Monte-Carlo kernel)
     h->src_noisy_mod = nullptr; h->src_noisy = nullptr;
+    if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
+    h->src_un_mod = nullptr; h->src_un = nullptr; h->src_un_npn = h->src_un_npu = -1;
     h->src_text = source; h->src_arch_name = src_arch(pr.gcnArchName);
     h->d_src_p = const_cast<double *>(dp); h->src_np = n_params;
     h->hW.assign(W, W + (size_t)(pb.W_tv ? N : 1) * n * n);
@@ -2041,6 +2073,116 @@ extern "C" rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const d
     HIPCHK(hipMemcpyAsync(out, h->d_mc_red + (MC_P1 + MC_P2) * MC_BLOCKS, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     if (cost_out) HIPCHK(hipMemcpyAsync(cost_out, h->d_mc_cost, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < RAT_MC_NSTAT; ++i) stats[i] = out[i];
+    for (int i = 0; i < n_theta; ++i) {
+        if (risk) risk[i] = out[8 + i];
+        if (risk_se) risk_se[i] = out[8 + MC_MAX_THETA + i];
+    }
+    return RAT_OK;
+}
+
+// rat_policy_evaluate for a source model whose disturbance is the user's rat_user_noise (source_user_noise.h) instead of N(0, W(k)): the
+// same packing of the policy, the same reduction of the K costs (launch_policy_mc), W is not read.  Injected streams and the optional
+// trajectories are staged a chunk of 2^16 rollouts at a time; the generator counts rollouts globally, so the chunks do not show.
+extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
+                                            int32_t normals_per_step, int32_t uniforms_per_step, const double *zn, const double *zu,
+                                            uint64_t seed, const double *theta, int32_t n_theta, double *stats, double *risk,
+                                            double *risk_se, double *cost_out, double *x_out, double *u_out) {
+    if (n_theta < 0 || n_theta > MC_MAX_THETA) return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: n_theta must be in 0 .. 16");
+    if (n_theta > 0 && !theta) return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: theta is null");
+    for (int i = 0; i < n_theta; ++i)
+        if (!(theta[i] >= 0.0)) return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: every theta must be >= 0");
+    if (K < 1) return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: K must be positive");
+    if (K > ((int64_t)1 << 27)) return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: K must be at most 2^27 (the costs stay on the device, 8 bytes each)");
+    if (!h || !x_nom || !l || !stats) return fail(RAT_ERR_ARG, "null");
+    if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
+    if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
+        return fail(RAT_ERR_UNSUPPORTED, "rat_policy_evaluate_noise: the handle's problem is not a source model (only a source can define rat_user_noise)");
+    const int n = h->n, m = h->m, N = h->N;
+    const int npn = normals_per_step, npu = uniforms_per_step;
+    rat_rc rc;
+    if ((rc = user_noise_args_ok("rat_policy_evaluate_noise", n, m, npn, npu))) return rc;
+    if ((zn || zu) && ((npn > 0 && !zn) || (npu > 0 && !zu)))
+        return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: injected draws need every declared stream (normals_per_step = " + std::to_string(npn) +
+                                 ", uniforms_per_step = " + std::to_string(npu) + ")");
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->src_un || h->src_un_npn != npn || h->src_un_npu != npu) {       // the first evaluation with these draw counts compiles the kernel
+        std::shared_ptr<const std::vector<char>> code;
+        std::string log;
+        if ((rc = src_compile_user_noise(h->src_text.c_str(), n, m, npn, npu, h->src_arch_name, &code, &log))) return fail(rc, log);
+        hipModule_t mod = nullptr;
+        hipFunction_t fn = nullptr;
+        HIPCHK(hipModuleLoadData(&mod, code->data()));
+        if (hipModuleGetFunction(&fn, mod, "rat_src_user_noisy_rollout") != hipSuccess) {
+            (void)hipModuleUnload(mod);
+            return fail(RAT_ERR_HIP, "rat_policy_evaluate_noise: the compiled module lacks its kernel");
+        }
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
+        h->src_un_mod = mod; h->src_un = fn; h->src_un_npn = npn; h->src_un_npu = npu; h->src_un_loads++;
+    }
+    if (!h->h_un_over && hipHostMalloc((void **)&h->h_un_over, sizeof(int), hipHostMallocDefault) != hipSuccess) {
+        h->h_un_over = nullptr;
+        return fail(RAT_ERR_HIP, "rat_policy_evaluate_noise: hipHostMalloc failed");
+    }
+    // the policy in the padded 12 + 4 layout, one upload: x_nom | l | L
+    std::vector<double> pack, xp, up, Lp;
+    if (L) { pad_x(h, x_nom, xp); pad_L(h, L, Lp); }
+    else { xp.assign((size_t)(N + 1) * XSTR, 0.0); for (int i = 0; i < n; ++i) xp[i] = x_nom[i]; }
+    pad_u(h, l, up);
+    pack.insert(pack.end(), xp.begin(), xp.end());
+    const size_t o_l = pack.size(); pack.insert(pack.end(), up.begin(), up.end());
+    const size_t o_L = pack.size(); pack.insert(pack.end(), Lp.begin(), Lp.end());
+    const bool inject = zn || zu, traj = x_out || u_out;
+    const int64_t chunk = std::min<int64_t>(K, 1 << 16);
+    const size_t one = 1, nxo = (size_t)(N + 1) * n, nuo = (size_t)N * m;
+    size_t cap_red = h->d_mc_red ? MC_SCRATCH : 0;
+    if ((rc = grow(&h->d_mc_in, &h->cap_mc_in, pack.size()))) return rc;
+    if ((rc = grow(&h->d_mc_cost, &h->cap_mc_cost, std::max((size_t)K, one)))) return rc;
+    if ((rc = grow(&h->d_mc_red, &cap_red, (size_t)MC_SCRATCH))) return rc;
+    if (zn && npn > 0 && (rc = grow(&h->d_mc_z, &h->cap_mc_z, (size_t)chunk * N * npn))) return rc;
+    if (zu && npu > 0 && (rc = grow(&h->d_mc_zu, &h->cap_mc_zu, (size_t)chunk * N * npu))) return rc;
+    if (x_out && (rc = grow(&h->d_mc_xo, &h->cap_mc_xo, (size_t)chunk * nxo))) return rc;
+    if (u_out && (rc = grow(&h->d_mc_uo, &h->cap_mc_uo, (size_t)chunk * nuo))) return rc;
+    HIPCHK(hipMemcpy(h->d_mc_in, pack.data(), pack.size() * 8, hipMemcpyHostToDevice));
+    int *d_over = nullptr;
+    HIPCHK(hipHostGetDevicePointer((void **)&d_over, h->h_un_over, 0));
+    *h->h_un_over = 0;
+    // the generator without trajectories needs no staging: one launch (the rollout index is the Philox counter either way)
+    const int64_t step = (inject || traj) ? chunk : K;
+    for (int64_t k0 = 0; k0 < K; k0 += step) {
+        const int64_t kc = std::min(step, K - k0);
+        if (inject) {
+            HIPCHK(hipStreamSynchronize(h->stream));              // (the previous chunk's rollouts read the staging areas)
+            if (zn && npn > 0) HIPCHK(hipMemcpy(h->d_mc_z, zn + (size_t)k0 * N * npn, (size_t)kc * N * npn * 8, hipMemcpyHostToDevice));
+            if (zu && npu > 0) HIPCHK(hipMemcpy(h->d_mc_zu, zu + (size_t)k0 * N * npu, (size_t)kc * N * npu * 8, hipMemcpyHostToDevice));
+        }
+        SrcUserNoisyArgs a;
+        a.xnom = h->d_mc_in; a.l = h->d_mc_in + o_l; a.L = L ? h->d_mc_in + o_L : nullptr;
+        a.zn = (zn && npn > 0) ? h->d_mc_z : nullptr; a.zu = (zu && npu > 0) ? h->d_mc_zu : nullptr;
+        a.K = (long)kc; a.j0 = (long)k0; a.N = N; a.tpw = h->src_mc_tpw; a.seed = seed; a.cost = h->d_mc_cost + k0;
+        a.x_out = x_out ? h->d_mc_xo : nullptr; a.u_out = u_out ? h->d_mc_uo : nullptr; a.p = h->d_src_p; a.overdraw = d_over;
+        void *args[] = {&a};
+        HIPCHK(hipModuleLaunchKernel(h->src_un, (unsigned)((kc + a.tpw - 1) / a.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+        if (traj) {                                               // (the stream orders these copies behind the chunk's rollouts; they block the host)
+            if (x_out) HIPCHK(hipMemcpyAsync(x_out + (size_t)k0 * nxo, h->d_mc_xo, (size_t)kc * nxo * 8, hipMemcpyDeviceToHost, h->stream));
+            if (u_out) HIPCHK(hipMemcpyAsync(u_out + (size_t)k0 * nuo, h->d_mc_uo, (size_t)kc * nuo * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+        }
+    }
+    McArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.cost = h->d_mc_cost; ma.dom = nullptr; ma.K = (long)K; ma.n_theta = n_theta; ma.scratch = h->d_mc_red;
+    for (int i = 0; i < n_theta; ++i) ma.theta[i] = theta[i];
+    launch_policy_mc(ma, h->stream);
+    HIPCHK(hipGetLastError());
+    double out[MC_OUT];
+    HIPCHK(hipMemcpyAsync(out, h->d_mc_red + (MC_P1 + MC_P2) * MC_BLOCKS, sizeof(out), hipMemcpyDeviceToHost, h->stream));
+    if (cost_out) HIPCHK(hipMemcpyAsync(cost_out, h->d_mc_cost, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (*(volatile int *)h->h_un_over != 0)                       // after the wait: a step that drew more than the caller declared
+        return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: a step drew more than was declared (normals_per_step = " + std::to_string(npn) +
+                                 ", uniforms_per_step = " + std::to_string(npu) + "): the overdrawn values were NaN");
     for (int i = 0; i < RAT_MC_NSTAT; ++i) stats[i] = out[i];
     for (int i = 0; i < n_theta; ++i) {
         if (risk) risk[i] = out[8 + i];

@@ -56,3 +56,22 @@ struct SrcNoisyArgs {
     double *cost;             // [K]; NaN where the rollout hit a DomainError
     const double *p;          // the model's parameters
 };
+
+// rat_src_user_noisy_rollout (source_user_noise.h): rat_src_noisy_rollout with the disturbance drawn by the user's rat_user_noise from a
+// rat_rng, one lane per Monte-Carlo rollout (rat_policy_evaluate_noise)
+struct SrcUserNoisyArgs {
+    const double *xnom;       // [(N+1)][12] nominal states (open loop: only row 0 is read)
+    const double *l;          // [N][4]
+    const double *L;          // [N][4][12] or null (open loop)
+    const double *zn, *zu;    // injected draws of this launch ([K][N][normals], [K][N][uniforms]) or both null (Philox keyed by seed)
+    long K;                   // rollouts of this launch
+    long j0;                  // global index of this launch's first rollout (the generator's counter)
+    int N;
+    int tpw;                  // rollouts per wavefront (lanes 0 .. tpw-1 of each 64-lane workgroup work)
+    unsigned long long seed;
+    double *cost;             // [K]; NaN where the rollout hit a DomainError
+    double *x_out;            // [K][N+1][n] dense, or null
+    double *u_out;            // [K][N][m] dense, or null
+    const double *p;          // the model's parameters
+    int *overdraw;            // set (plain store) when a step draws more than was declared: 1 normals, 2 uniforms
+};

@@ -31,7 +31,8 @@ struct Rtc {
 
 std::mutex g_mu;
 Rtc g_rtc;
-// key: (source, n, m, kind (0 risk-sensitive, 1 generative, 2 the risk-sensitive model's Monte-Carlo rollout), normals per step, uniforms per step, architecture)
+// key: (source, n, m, kind (0 risk-sensitive, 1 generative, 2 the risk-sensitive model's Monte-Carlo rollout, 3 that rollout under the
+// user's noise sampler), normals per step, uniforms per step, architecture)
 std::map<std::tuple<std::string, int, int, int, int, int, std::string>, std::shared_ptr<const std::vector<char>>> g_cache;
 
 bool rtc_load(std::string *why) {           // (g_mu held)
@@ -93,13 +94,14 @@ static rat_rc compile_impl(const char *source, int n, int m, int kind, int npn, 
     const std::string text = std::string("#include \"source_args.h\"\n#include \"rat_ad.h\"\n#include \"rat_rng.h\"\n#line 1 \"model.hip\"\n") +
                              source + (kind == 0 ? "\n#line 1 \"source_kernels.h\"\n#include \"source_kernels.h\"\n"
                                       : kind == 2 ? "\n#line 1 \"source_noisy.h\"\n#include \"source_noisy.h\"\n"
+                                      : kind == 3 ? "\n#line 1 \"source_user_noise.h\"\n#include \"source_user_noise.h\"\n"
                                                   : "\n#line 1 \"source_pets.h\"\n#include \"source_pets.h\"\n");
     const char *hdr[] = {k_embed_layout_h, k_embed_source_args_h, k_embed_rat_ad_h, k_embed_source_kernels_h, k_embed_rat_normal_h,
-                         k_embed_rat_philox_h, k_embed_rat_rng_h, k_embed_source_pets_h, k_embed_source_noisy_h};
+                         k_embed_rat_philox_h, k_embed_rat_rng_h, k_embed_source_pets_h, k_embed_source_noisy_h, k_embed_source_user_noise_h};
     const char *hdr_names[] = {"layout.h", "source_args.h", "rat_ad.h", "source_kernels.h", "rat_normal.h", "rat_philox.h", "rat_rng.h",
-                               "source_pets.h", "source_noisy.h"};
+                               "source_pets.h", "source_noisy.h", "source_user_noise.h"};
     hiprtcProgram prog = nullptr;
-    if (g_rtc.create(&prog, text.c_str(), "model.hip", 9, hdr, hdr_names) != HIPRTC_SUCCESS) {
+    if (g_rtc.create(&prog, text.c_str(), "model.hip", 10, hdr, hdr_names) != HIPRTC_SUCCESS) {
         if (log) *log = "hiprtcCreateProgram failed";
         return done(RAT_ERR_ARG);
     }
@@ -148,4 +150,9 @@ rat_rc src_compile_gen(const char *source, int n, int m, int npn, int npu, const
 rat_rc src_compile_noisy(const char *source, int n, int m, const std::string &arch, std::shared_ptr<const std::vector<char>> *code,
                          std::string *log, double *ms, bool *cached) {
     return compile_impl(source, n, m, 2, 0, 0, arch, code, log, ms, cached);
+}
+
+rat_rc src_compile_user_noise(const char *source, int n, int m, int npn, int npu, const std::string &arch,
+                              std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
+    return compile_impl(source, n, m, 3, npn, npu, arch, code, log, ms, cached);
 }

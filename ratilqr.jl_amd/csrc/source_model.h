@@ -22,5 +22,9 @@ rat_rc src_compile_gen(const char *source, int n, int m, int npn, int npu, const
 // of its own, compiled on the first evaluation of a source problem, not when the problem is set.
 rat_rc src_compile_noisy(const char *source, int n, int m, const std::string &arch, std::shared_ptr<const std::vector<char>> *code,
                          std::string *log, double *ms = nullptr, bool *cached = nullptr);
+// That rollout under the user's noise sampler (rat_policy_evaluate_noise): source_user_noise.h after the source, which must define
+// RAT_USER_NOISE and rat_user_noise; -DRAT_PETS_NORMALS=npn -DRAT_PETS_UNIFORMS=npu.  A fourth kind, compiled on the first such evaluation.
+rat_rc src_compile_user_noise(const char *source, int n, int m, int npn, int npu, const std::string &arch,
+                              std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
 // The offload-arch string for the device's reported gcnArchName (an xnack+ feature is never passed on).
 std::string src_arch(const char *gcn_arch_name);

@@ -184,6 +184,9 @@ class GenericContext(il.Context):
     def policy_evaluate(self, *a, **k):
         self._carrier_only("policy_evaluate")
 
+    def policy_evaluate_noise(self, *a, **k):
+        self._carrier_only("policy_evaluate_noise")
+
     def solve_batch(self, *a, **k):
         self._carrier_only("solve_batch")
 

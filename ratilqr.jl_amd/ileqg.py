@@ -23,6 +23,19 @@ from .problems import MODEL_SOURCE, FiniteHorizonRiskSensitiveOptimalControlProb
 SQRT_EPS = 1.4901161193847656e-8
 
 
+class UserNoise:
+    """The disturbance of Context.policy_evaluate_noise / evaluate_policy(..., noise=): what the source's rat_user_noise draws per step
+    (normals_per_step, uniforms_per_step: the most rng.normal() / rng.uniform() calls of one step) and where the draws come from --
+    injected streams zn (K, N, normals_per_step) and zu (K, N, uniforms_per_step), every declared one, or the device generator keyed
+    by seed."""
+
+    def __init__(self, normals_per_step, uniforms_per_step=0, zn=None, zu=None, seed=0):
+        self.normals_per_step, self.uniforms_per_step = int(normals_per_step), int(uniforms_per_step)
+        self.zn = None if zn is None else nv.f64(zn)
+        self.zu = None if zu is None else nv.f64(zu)
+        self.seed = int(seed)
+
+
 class Context:
     """One rat_handle bound to one problem (device buffers sized for max_batch samples x spec_eps step sizes)."""
 
@@ -121,6 +134,38 @@ class Context:
         return dict(n_ok=int(stats[nv.MC_N_OK]), n_domain=int(stats[nv.MC_N_DOMAIN]), mean=float(stats[nv.MC_MEAN]),
                     var=float(stats[nv.MC_VAR]), min=float(stats[nv.MC_MIN]), max=float(stats[nv.MC_MAX]),
                     se_mean=float(stats[nv.MC_SE_MEAN]), risk=risk, risk_se=se, costs=costs)
+
+    def policy_evaluate_noise(self, x_nom, l, L=None, noise=None, thetas=(), K=None, want_costs=False, want_trajectories=False):
+        """policy_evaluate for a source problem under the disturbance its own rat_user_noise draws (rat_policy_evaluate_noise): noise is
+        a UserNoise.  K defaults to the rollouts an injected stream holds.  The same dict, and with want_trajectories x (K, N+1, n) and
+        u (K, N, m), rollout index first (None otherwise)."""
+        if not isinstance(noise, UserNoise):
+            raise TypeError("policy_evaluate_noise needs noise=UserNoise(...)")
+        npn, npu = noise.normals_per_step, noise.uniforms_per_step
+        if K is None:
+            for z, per in ((noise.zn, npn), (noise.zu, npu)):
+                if z is not None and per > 0 and self.N > 0:
+                    K = z.size // (self.N * per)
+                    break
+        if K is None:
+            raise ValueError("policy_evaluate_noise needs K= or an injected stream")
+        K = int(K)
+        for z, per, name in ((noise.zn, npn, "zn"), (noise.zu, npu, "zu")):
+            if z is not None and per > 0 and z.size != K * self.N * per:
+                raise ValueError(f"{name} holds {z.size} draws, K N per-step = {K * self.N * per}")
+        th = nv.f64(np.atleast_1d(np.asarray(thetas, dtype=np.float64))).ravel()
+        stats, risk, se = np.zeros(nv.MC_NSTAT), np.zeros(th.size), np.zeros(th.size)
+        costs = np.zeros(max(K, 0)) if want_costs else None
+        x = np.zeros((max(K, 0), self.N + 1, self.n)) if want_trajectories else None
+        u = np.zeros((max(K, 0), self.N, self.m)) if want_trajectories else None
+        nv.check(nv.lib().rat_policy_evaluate_noise(self.h, nv.P(nv.f64(x_nom)), nv.P(nv.f64(l)), nv.P(nv.cm3(L)) if L is not None else None,
+                                                    C.c_int64(K), C.c_int32(npn), C.c_int32(npu), nv.P(noise.zn), nv.P(noise.zu),
+                                                    C.c_uint64(noise.seed), nv.P(th) if th.size else None, C.c_int32(th.size), nv.P(stats),
+                                                    nv.P(risk) if th.size else None, nv.P(se) if th.size else None, nv.P(costs), nv.P(x),
+                                                    nv.P(u)))
+        return dict(n_ok=int(stats[nv.MC_N_OK]), n_domain=int(stats[nv.MC_N_DOMAIN]), mean=float(stats[nv.MC_MEAN]),
+                    var=float(stats[nv.MC_VAR]), min=float(stats[nv.MC_MIN]), max=float(stats[nv.MC_MAX]),
+                    se_mean=float(stats[nv.MC_SE_MEAN]), risk=risk, risk_se=se, costs=costs, x=x, u=u)
 
     def integrate_cost(self, x, u):
         out = C.c_double()
@@ -388,9 +433,18 @@ def simulate_dynamics_noisy(problem, a, b, c=None, K=1, z=None, seed=0):
     return (x, cost) if c is None else (x, u, cost)
 
 
-def evaluate_policy(problem, x, l, L=None, thetas=(), K=None, z=None, seed=0, want_costs=False):
+def evaluate_policy(problem, x, l, L=None, thetas=(), K=None, z=None, seed=0, want_costs=False, noise=None, want_trajectories=False):
     """Monte-Carlo evaluation of the policy (x, l, L) that solve_ returned -- or of an open-loop plan (x_0, u_array) with L=None -- under
-    the problem's process noise: Context.policy_evaluate on the problem's default context.  DeviceSourceProblem included."""
+    the problem's process noise: Context.policy_evaluate on the problem's default context.  DeviceSourceProblem included.  With
+    noise=UserNoise(...) the disturbance is the one the source's rat_user_noise draws (Context.policy_evaluate_noise; z and seed are then
+    the UserNoise's own), and want_trajectories returns the rollouts' x and u as well."""
+    if noise is not None:
+        if z is not None:
+            raise ValueError("evaluate_policy: with noise= the injected draws are noise.zn / noise.zu, not z")
+        return _ctx(problem).policy_evaluate_noise(x, l, L, noise=noise, thetas=thetas, K=K, want_costs=want_costs,
+                                                   want_trajectories=want_trajectories)
+    if want_trajectories:
+        raise ValueError("evaluate_policy: trajectories come with noise=UserNoise(...) only (rollout_noisy returns them for the families)")
     return _ctx(problem).policy_evaluate(x, l, L, thetas=thetas, K=K, z=z, seed=seed, want_costs=want_costs)
 
 
