@@ -254,6 +254,44 @@ rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, const double
                                  int32_t normals_per_step, int32_t uniforms_per_step, const double *zn, const double *zu, uint64_t seed,
                                  const double *theta, int32_t n_theta, double *stats, double *risk, double *risk_se, double *cost_out,
                                  double *x_out, double *u_out);
+/* The worst-case expected cost of a policy within the KL ball, from the K Monte-Carlo costs: sup { E_p[J] : KL(p || q) <= d } over the
+ * sample, the quantity rat_ce_solve / rat_nm_solve minimise as value(theta) + d / theta.  The dual is exact and one-dimensional: with
+ * y_k = exp(theta (J_k - Jmax)) over the N_OK costs, Z = mean y, m(theta) = sum y J / sum y (the mean under the exponentially tilted, worst-case
+ * distribution), KL(theta) = theta (m - Jmax) - log Z (non-decreasing from 0 to log(N_OK / n_max), n_max the rollouts with J == Jmax),
+ * bound(d) = min_theta [Jmax + log Z / theta + d / theta], attained where KL(theta*) = d, and there bound = m(theta*).  theta* is searched
+ * on the device: 12 passes of 16 points per bound (a geometric grid theta_0 4^(j - 7) around theta_0 = sqrt(2 d) / sd(J), then eleven
+ * 17-sections: the last bracket is below 1e-13 relative), no read-back between passes.
+ *   cost       NULL: the K costs the last rat_policy_evaluate / rat_policy_evaluate_noise on this handle left on the device -- or the K
+ *              costs a later call of this function uploaded; K must be 0 or that K, and RAT_ERR_ARG if no such call has been made.
+ *              Otherwise K host doubles (1 <= K <= 2^27), uploaded into the same buffer; NaN entries are DomainError rollouts and are
+ *              left out.  No problem needs to be set for this form.
+ *   kl_bound   [n_bound], 0 <= n_bound <= 16, every one >= 0 (+Inf allowed; NaN or negative RAT_ERR_ARG)
+ *   theta      [n_theta], 0 <= n_theta <= 16, every one >= 0 and finite (else RAT_ERR_ARG); n_bound + n_theta == 0 is RAT_ERR_ARG
+ *   out_bound  [n_bound][RAT_WC_NSTAT], out_theta [n_theta][RAT_WC_NSTAT]: a row of the slots below per kl_bound / per theta
+ *   weights_out[K] or NULL: y_k / sum y at kl_bound[0]'s theta* (at theta[0] when n_bound == 0), 0 for a DomainError rollout; on a
+ *              saturated row 1 / n_max on the maxima and 0 elsewhere.  The importance weights that turn rat_policy_evaluate_noise's
+ *              x_out / u_out into worst-case trajectories on the host.
+ * Flags: RAT_WC_SATURATED when kl_bound >= log(N_OK / n_max), or when theta_top = 65536 theta_0 still has KL < kl_bound: the row holds the
+ * theta -> Inf limits (THETA +Inf, KL log(N_OK / n_max), BOUND = TILT_MEAN = Jmax, TILT_VAR 0, ESS n_max, BOUND_SE NaN).  RAT_WC_EMPTY:
+ * N_OK == 0; RAT_WC_NONFINITE: a +-Inf among the costs; every other slot is NaN in both.  kl_bound == 0 is decided first: theta 0, KL 0,
+ * BOUND = TILT_MEAN = the mean, ESS N_OK, flag OK.  The sums run in rat_policy_evaluate's fixed order: the same arguments return the same
+ * bits, and a row's bits depend neither on the other rows of the call nor on where the costs came from. */
+#define RAT_WC_THETA     0   /* bound row: theta*; theta row: the given theta */
+#define RAT_WC_KL        1   /* KL(theta) */
+#define RAT_WC_BOUND     2   /* Jmax + log Z / theta + d / theta; d = kl_bound[i] on a bound row, the row's own KL on a theta row (so BOUND
+                              * equals TILT_MEAN up to rounding there) */
+#define RAT_WC_BOUND_SE  3   /* delta method, sd(y) / (mean(y) theta sqrt(N_OK)): risk_se's formula at that theta; SE_MEAN at theta == 0 */
+#define RAT_WC_TILT_MEAN 4   /* m(theta) */
+#define RAT_WC_TILT_VAR  5   /* sum y (J - m)^2 / sum y */
+#define RAT_WC_ESS       6   /* (sum y)^2 / sum y^2: the effective sample size of the tilted estimate */
+#define RAT_WC_FLAG      7   /* RAT_WC_OK ... as a double */
+#define RAT_WC_NSTAT     8
+#define RAT_WC_OK        0
+#define RAT_WC_SATURATED 1
+#define RAT_WC_EMPTY     2
+#define RAT_WC_NONFINITE 3
+rat_rc rat_policy_worst_case(rat_handle h, const double *cost, int64_t K, const double *kl_bound, int32_t n_bound,
+                             const double *theta, int32_t n_theta, double *out_bound, double *out_theta, double *weights_out);
 /* approximate_model(problem, u_array, x_array)                 ileqg.jl:258-322
  * -> q[N+1], qv[n*(N+1)], Q[n*n*(N+1)], r[m*N], R[m*m*N], P[m*n*N], A[n*n*N], B[n*m*N], W[n*n*N] */
 rat_rc rat_approximate_model(rat_handle h, const double *u, const double *x,
@@ -618,6 +656,7 @@ int32_t rat_get_path(rat_handle h, int64_t B);
  *                            trajectories, profiles/source_model.md)                                                        (16)
  *   src_pets_tpw    16 / 32 / 64   generative source models: trajectories per wavefront of the PETS rollout kernel (64: 3.7x 16's
  *                            rollouts/s at 10^6 trajectories, equal at 10 k; profiles/source_pets.md)                     (64)
+ *   mc_cost_K       read-only      costs the last rat_policy_evaluate / _noise (or rat_policy_worst_case with host costs) left on the device (0: none)
  *   src_mc_tpw      16 / 32 / 64   source models: rollouts per wavefront of rat_policy_evaluate's rollout kernel (profiles/policy_mc.md) (64)
  *   wdiag           0 / 1    diagonal time-invariant W: inv(W) folded into M^-1's operand (takes effect at the next rat_problem_set) (1) */
 rat_rc  rat_debug_set(rat_handle h, const char *key, int64_t value);

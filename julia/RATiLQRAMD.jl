@@ -387,6 +387,31 @@ function evaluate_policy(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_
      risk=risk, risk_se=risk_se, costs=costs)
 end
 
+"""
+policy_worst_case(s; kl_bounds, thetas, costs, want_weights): the worst-case expected cost sup { E_p[J] : KL(p ‖ q) ≤ d } of a sample of
+Monte-Carlo costs (rat_policy_worst_case), by its one-dimensional dual searched on the device.  costs === nothing: the costs the last
+evaluate_policy on this solver's handle left on the device; otherwise a vector of K costs (NaN = DomainError rollout, left out).
+kl_bounds: up to 16 radii d ≥ 0; thetas: up to 16 tilts θ ≥ 0.  Returns (bounds, thetas, weights): bounds and thetas are named tuples of
+vectors theta, kl, bound, bound_se, tilt_mean, tilt_var, ess, flag (0 OK, 1 saturated, 2 empty, 3 non-finite), one entry per kl_bound /
+per θ; weights = y_k / Σ y at kl_bounds[1]'s θ* (thetas[1] without bounds), `nothing` unless want_weights.
+"""
+function policy_worst_case(s::ILEQGSolver; kl_bounds=Float64[], thetas=Float64[], costs::Union{Nothing,Vector{Float64}}=nothing,
+                           want_weights::Bool=false)
+    h = s.h
+    d = collect(Float64, kl_bounds); th = collect(Float64, thetas)
+    nb = length(d); nt = length(th)
+    K = costs === nothing ? Int64(debug_get(h, "mc_cost_K")) : Int64(length(costs))
+    ob = zeros(8, nb); ot = zeros(8, nt)
+    w = want_weights ? zeros(max(K, 1)) : nothing
+    check(ccall((:rat_policy_worst_case, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, costs === nothing ? C_NULL : costs, costs === nothing ? Int64(0) : K, nb > 0 ? d : C_NULL, nb, nt > 0 ? th : C_NULL, nt,
+                nb > 0 ? ob : C_NULL, nt > 0 ? ot : C_NULL, want_weights ? w : C_NULL))
+    rows(o) = (theta=o[1, :], kl=o[2, :], bound=o[3, :], bound_se=o[4, :], tilt_mean=o[5, :], tilt_var=o[6, :], ess=o[7, :],
+               flag=Int.(o[8, :]))
+    (bounds=rows(ob), thetas=rows(ot), weights=want_weights ? w[1:K] : nothing)
+end
+
 "integrate_cost(problem, x_array, u_array) -- ileqg.jl:115-124"
 function integrate_cost(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_array, u_array)
     h = bind!(s.h, problem); c = Ref(0.0)
@@ -1229,7 +1254,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

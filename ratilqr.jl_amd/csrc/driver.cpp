@@ -195,6 +195,10 @@ struct rat_handle_s {
     double *d_mc_z = nullptr; size_t cap_mc_z = 0;           // injected normals of one chunk
     double *d_mc_in = nullptr; size_t cap_mc_in = 0;         // Wchol | x_nom | l | L
     double *d_mc_red = nullptr;                              // [MC_SCRATCH] partials and results of the reduction
+    int64_t mc_cost_K = 0;                                   // rollouts whose costs the last evaluation left in d_mc_cost (0: none are valid)
+    // the worst case over the KL ball (rat_policy_worst_case, policy_mc.hip): brackets, partials and rows; the weights
+    double *d_wc_red = nullptr;                              // [WC_SCRATCH]
+    double *d_wc_w = nullptr; size_t cap_wc_w = 0;           // [K]
     // ... under the user's noise sampler (rat_policy_evaluate_noise): rat_src_user_noisy_rollout (source_user_noise.h), a module of its own
     // compiled for the declared draw counts by the first call that needs it
     hipModule_t src_un_mod = nullptr;
@@ -285,6 +289,7 @@ static const DebugSwitch debug_switches[] = {
     {"psw_comp", [](rat_handle h, int64_t v) { h->psw_comp = (int)std::max<int64_t>(100, v); }, [](rat_handle h) -> int64_t { return h->psw_comp; }},
     {"src_tpw", [](rat_handle h, int64_t v) { h->src_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_tpw; }},
     {"src_pets_tpw", [](rat_handle h, int64_t v) { h->src_pets_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_pets_tpw; }},
+    {"mc_cost_K", [](rat_handle, int64_t) {}, [](rat_handle h) -> int64_t { return h->mc_cost_K; }},   // read-only
     {"src_mc_tpw", [](rat_handle h, int64_t v) { h->src_mc_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_mc_tpw; }},
     {"src_un_loads", [](rat_handle, int64_t) {}, [](rat_handle h) -> int64_t { return h->src_un_loads; }},
 };
@@ -380,6 +385,7 @@ extern "C" void rat_destroy(rat_handle h) {
     for (void *q : {(void *)h->d_mc_cost, (void *)h->d_mc_dom, (void *)h->d_mc_z, (void *)h->d_mc_in, (void *)h->d_mc_red}) if (q) (void)hipFree(q);
     if (h->src_noisy_mod) (void)hipModuleUnload(h->src_noisy_mod);
     for (double *q : {h->d_mc_zu, h->d_mc_xo, h->d_mc_uo}) if (q) (void)hipFree(q);
+    for (double *q : {h->d_wc_red, h->d_wc_w}) if (q) (void)hipFree(q);
     if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
@@ -2027,6 +2033,7 @@ extern "C" rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const d
     // the handle's scratch: allocated by the first call, grown on demand, kept until rat_destroy (a buffer that grows is freed first:
     // every earlier call has finished, the entry point is synchronous)
     const size_t one = 1;
+    h->mc_cost_K = 0;                                             // (d_mc_cost is about to be regrown or overwritten)
     size_t cap_red = h->d_mc_red ? MC_SCRATCH : 0;
     if ((rc = grow(&h->d_mc_in, &h->cap_mc_in, pack.size()))) return rc;
     if ((rc = grow(&h->d_mc_cost, &h->cap_mc_cost, std::max((size_t)K, one)))) return rc;
@@ -2073,6 +2080,7 @@ extern "C" rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const d
     HIPCHK(hipMemcpyAsync(out, h->d_mc_red + (MC_P1 + MC_P2) * MC_BLOCKS, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     if (cost_out) HIPCHK(hipMemcpyAsync(cost_out, h->d_mc_cost, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    h->mc_cost_K = K;
     for (int i = 0; i < RAT_MC_NSTAT; ++i) stats[i] = out[i];
     for (int i = 0; i < n_theta; ++i) {
         if (risk) risk[i] = out[8 + i];
@@ -2136,6 +2144,7 @@ extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, c
     const bool inject = zn || zu, traj = x_out || u_out;
     const int64_t chunk = std::min<int64_t>(K, 1 << 16);
     const size_t one = 1, nxo = (size_t)(N + 1) * n, nuo = (size_t)N * m;
+    h->mc_cost_K = 0;                                             // (d_mc_cost is about to be regrown or overwritten)
     size_t cap_red = h->d_mc_red ? MC_SCRATCH : 0;
     if ((rc = grow(&h->d_mc_in, &h->cap_mc_in, pack.size()))) return rc;
     if ((rc = grow(&h->d_mc_cost, &h->cap_mc_cost, std::max((size_t)K, one)))) return rc;
@@ -2183,11 +2192,68 @@ extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, c
     if (*(volatile int *)h->h_un_over != 0)                       // after the wait: a step that drew more than the caller declared
         return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: a step drew more than was declared (normals_per_step = " + std::to_string(npn) +
                                  ", uniforms_per_step = " + std::to_string(npu) + "): the overdrawn values were NaN");
+    h->mc_cost_K = K;
     for (int i = 0; i < RAT_MC_NSTAT; ++i) stats[i] = out[i];
     for (int i = 0; i < n_theta; ++i) {
         if (risk) risk[i] = out[8 + i];
         if (risk_se) risk_se[i] = out[8 + MC_MAX_THETA + i];
     }
+    return RAT_OK;
+}
+
+// The worst-case expected cost sup { E_p[J] : KL(p || q) <= d } of the sample of K costs, by its one-dimensional dual, searched on the
+// device (policy_mc.hip, launch_policy_wc): one enqueue chain on the handle's stream, one host wait.  The costs are the ones the last
+// evaluation -- or the last call of this kind with host costs -- left in d_mc_cost (cost == NULL) or K host doubles uploaded into that buffer; either way the chain starts with its own pass 1
+// over the buffer, so a row's bits do not depend on where the costs came from.
+extern "C" rat_rc rat_policy_worst_case(rat_handle h, const double *cost, int64_t K, const double *kl_bound, int32_t n_bound,
+                                        const double *theta, int32_t n_theta, double *out_bound, double *out_theta, double *weights_out) {
+    if (!h) return fail(RAT_ERR_ARG, "rat_policy_worst_case: null handle");
+    if (n_bound < 0 || n_bound > WC_MAX_BOUND) return fail(RAT_ERR_ARG, "rat_policy_worst_case: n_bound must be in 0 .. 16");
+    if (n_theta < 0 || n_theta > MC_MAX_THETA) return fail(RAT_ERR_ARG, "rat_policy_worst_case: n_theta must be in 0 .. 16");
+    if (n_bound + n_theta == 0) return fail(RAT_ERR_ARG, "rat_policy_worst_case: no kl_bound and no theta: nothing to compute");
+    if ((n_bound > 0 && (!kl_bound || !out_bound)) || (n_theta > 0 && (!theta || !out_theta)))
+        return fail(RAT_ERR_ARG, "rat_policy_worst_case: null kl_bound / theta / output");
+    for (int i = 0; i < n_bound; ++i)
+        if (!(kl_bound[i] >= 0.0)) return fail(RAT_ERR_ARG, "rat_policy_worst_case: every kl_bound must be >= 0 (+Inf is allowed, NaN is not)");
+    for (int i = 0; i < n_theta; ++i)
+        if (!(theta[i] >= 0.0) || std::isinf(theta[i])) return fail(RAT_ERR_ARG, "rat_policy_worst_case: every theta must be >= 0 and finite");
+    if (cost) {
+        if (K < 1) return fail(RAT_ERR_ARG, "rat_policy_worst_case: K must be positive when costs are given");
+        if (K > ((int64_t)1 << 27)) return fail(RAT_ERR_ARG, "rat_policy_worst_case: K must be at most 2^27 (the costs stay on the device, 8 bytes each)");
+    } else {
+        if (h->mc_cost_K == 0)
+            return fail(RAT_ERR_ARG, "rat_policy_worst_case: cost is NULL and no rat_policy_evaluate / rat_policy_evaluate_noise on this handle has left "
+                                     "its costs on the device (a call with host costs leaves those instead)");
+        if (K != 0 && K != h->mc_cost_K)
+            return fail(RAT_ERR_ARG, "rat_policy_worst_case: K = " + std::to_string(K) + ", the last evaluation left " + std::to_string(h->mc_cost_K) +
+                                     " costs on the device (pass that K, or 0)");
+        K = h->mc_cost_K;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    rat_rc rc;
+    size_t cap_red = h->d_wc_red ? WC_SCRATCH : 0;
+    if ((rc = grow(&h->d_wc_red, &cap_red, (size_t)WC_SCRATCH))) return rc;
+    if (weights_out && (rc = grow(&h->d_wc_w, &h->cap_wc_w, (size_t)K))) return rc;
+    if (cost) {
+        h->mc_cost_K = 0;                                             // (the buffer's costs are replaced; valid again after the wait)
+        if ((rc = grow(&h->d_mc_cost, &h->cap_mc_cost, (size_t)K))) return rc;
+        HIPCHK(hipMemcpyAsync(h->d_mc_cost, cost, (size_t)K * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    WcArgs a;
+    memset(&a, 0, sizeof(a));
+    a.cost = h->d_mc_cost; a.K = (long)K; a.n_bound = n_bound; a.n_theta = n_theta; a.scratch = h->d_wc_red;
+    a.weights = weights_out ? h->d_wc_w : nullptr;
+    for (int i = 0; i < n_bound; ++i) a.bound[i] = kl_bound[i];
+    for (int i = 0; i < n_theta; ++i) a.theta[i] = theta[i];
+    launch_policy_wc(a, h->stream);
+    HIPCHK(hipGetLastError());
+    double rows[WC_MAX_ROWS * WC_NSTAT];
+    HIPCHK(hipMemcpyAsync(rows, h->d_wc_red + WC_O_ROWS, (size_t)(n_bound + n_theta) * WC_NSTAT * 8, hipMemcpyDeviceToHost, h->stream));
+    if (weights_out) HIPCHK(hipMemcpyAsync(weights_out, h->d_wc_w, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->mc_cost_K = K;                                                 // (uploaded costs serve a later cost == NULL call like an evaluation's)
+    for (int i = 0; i < n_bound * WC_NSTAT; ++i) out_bound[i] = rows[i];
+    for (int i = 0; i < n_theta * WC_NSTAT; ++i) out_theta[i] = rows[n_bound * WC_NSTAT + i];
     return RAT_OK;
 }
 

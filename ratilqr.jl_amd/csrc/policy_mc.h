@@ -20,3 +20,48 @@ struct McArgs {
 };
 // enqueues pass 1, pass 2 and the final reduction on s; the results are a.scratch + (MC_P1 + MC_P2) * MC_BLOCKS
 void launch_policy_mc(const McArgs &a, hipStream_t s);
+
+// ---- rat_policy_worst_case: sup { E_p[J] : KL(p || q) <= d } on the K costs, by the one-dimensional dual (policy_mc.hip) -----------------
+#define WC_NPT 16             /* theta points a search pass evaluates per bound */
+#define WC_MAX_BOUND 16
+#define WC_MAX_ROWS 32        /* bound rows, then theta rows */
+#define WC_NSTAT 8            /* RAT_WC_NSTAT of the header */
+#define WC_GEO_BELOW 7        /* pass 0: theta_0 4^(j - 7), j = 0 .. 15; the top point theta_0 4^8 is theta_top */
+#define WC_LINEAR_PASSES 11   /* passes 1 .. 11: 17-section of the bracket; 3 / 17^11 = 8.8e-14 relative */
+#define WC_PASSES (1 + WC_LINEAR_PASSES)
+#define WC_CENTRE_MAX 32.0    /* sums are centred about the mean while theta (Jmax - mean) <= this, about Jmax beyond */
+#define WC_THETA_CAP 1e300    /* grid points are capped here: theta (J - Jmax) stays 0, not NaN, at J == Jmax */
+#define WC_FROWS 8            /* rows the final sums form per sweep over the costs */
+// states of a bound's search (doubles in the scratch, like everything there)
+#define WC_ST_SEARCH 0.0
+#define WC_ST_ZERO 1.0        /* d == 0 (or a theta row's theta == 0): the plain mean */
+#define WC_ST_SAT 2.0
+#define WC_ST_EMPTY 3.0
+#define WC_ST_NONFINITE 4.0
+// scratch, in doubles: part1 [5][B] | var [2][B] | bracket [2][16][4] | search partials [2][16][32][B] | final partials [32][5][B] |
+// row info [32][2] | rows [32][8] | aux [8]        (B = MC_BLOCKS; the brackets and the search partials alternate between passes)
+#define WC_O_P1 0
+#define WC_O_PV (MC_P1 * MC_BLOCKS)
+#define WC_O_BRK (WC_O_PV + 2 * MC_BLOCKS)
+#define WC_O_PS (WC_O_BRK + 2 * WC_MAX_BOUND * 4)
+#define WC_PS_SET (WC_MAX_BOUND * 2 * WC_NPT * MC_BLOCKS)
+#define WC_O_PF (WC_O_PS + 2 * WC_PS_SET)
+#define WC_NFIN 5              /* sums per row of the final pass */
+#define WC_O_INFO (WC_O_PF + WC_MAX_ROWS * WC_NFIN * MC_BLOCKS)
+#define WC_O_ROWS (WC_O_INFO + WC_MAX_ROWS * 2)
+#define WC_O_AUX (WC_O_ROWS + WC_MAX_ROWS * WC_NSTAT)
+#define WC_SCRATCH (WC_O_AUX + 8)
+
+struct WcArgs {
+    double *cost;             // [K] costs, NaN for a DomainError rollout
+    long K;
+    int n_bound, n_theta;
+    int pass;                 // search pass of this launch (wc_search)
+    double bound[WC_MAX_BOUND];
+    double theta[MC_MAX_THETA];
+    double *scratch;          // [WC_SCRATCH]
+    double *weights;          // [K] or null
+};
+// enqueues pass 1 (mc_pass1), the variance pass, WC_PASSES search passes, the final sums, the rows and (a.weights) the weights on s;
+// the rows are a.scratch + WC_O_ROWS
+void launch_policy_wc(const WcArgs &a, hipStream_t s);

@@ -14,6 +14,7 @@
 // y_ref = exp(theta (mean - Jmax)): mean(y) = y_ref + sum d / n and (n - 1) var(y) = sum d^2 - (sum d)^2 / n are the sums of y and y^2
 // restated so that the subtraction does not cancel as theta sd(J) -> 0 (d is centred to first order).
 #include "policy_mc.h"
+#include <cstring>
 
 namespace {
 
@@ -150,10 +151,351 @@ __global__ __launch_bounds__(MC_THREADS) void mc_final(McArgs a) {
     }
 }
 
+
+// ---- rat_policy_worst_case: sup { E_p[J] : KL(p || q) <= d } over the K costs ----------------------------------------------------------
+// The dual is one-dimensional: with y_k = exp(theta (J_k - Jmax)), Z = mean y, m = sum y J / sum y and KL(theta) = theta (m - Jmax) - log Z
+// (non-decreasing from KL(0) = 0 to log(n / n_max)), the bound is Jmax + (log Z + d) / theta at the theta* where KL(theta*) = d.  The search
+// for theta* runs on the device in a fixed number of launches ("Worst-case cost within the KL ball"):
+//   mc_pass1    as for rat_policy_evaluate                                               -> part1
+//   wc_var      sum (J - mean)^2 and n_max = #{J == Jmax}                                -> var
+//   wc_search   x WC_PASSES.  Pass p places WC_NPT thetas per bound -- pass 0 on the geometric grid theta_0 4^(j - 7) around the Gaussian
+//               answer theta_0 = sqrt(2 d) / sd(J), later passes at lo + (hi - lo) (j + 1) / 17 -- and sums, per theta,
+//               A = sum (y - y_ref) and B = sum y (J - c) over the costs.  Its head first reduces the previous pass's partials, forms
+//               KL at that pass's thetas and picks the sub-interval that contains d: the bracket lives in the scratch, nothing is read
+//               back.  Brackets and partials alternate between two sets, so that a workgroup that is ahead never overwrites what another
+//               still reads.
+//   wc_final    theta* = the middle of the last bracket; per row (every bound, then every given theta) A, sum (y - y_ref)^2, B,
+//               sum y (J - c)^2 and sum y (J - Jmax)^2                                                          -> final partials, row info
+//   wc_rows     second level of those sums; writes the rows
+//   wc_weights  y_k / sum y of the first row, elementwise
+// Every sum runs in mc_pass1's order (lane g sums elements g, g + T, ...; the LDS tree; the second level at the head of the next launch).
+// Centring: c = mean and y_ref = exp(theta (mean - Jmax)) while theta (Jmax - mean) <= WC_CENTRE_MAX -- then, with y - y_ref formed as
+// y_ref expm1(theta (J - mean)), KL = theta B / sum y - log1p(A / (n y_ref)) holds its digits as theta sd(J) -> 0, where theta (m - Jmax)
+// and log Z are each far larger than their difference -- and c = Jmax, y_ref = 0 beyond (y_ref would underflow; KL is of order one there).
+
+// block_tree<0> for NQ sums at once (the same additions in the same order, NQ per barrier): sh is [NQ][MC_THREADS]
+template <int NQ>
+__device__ __forceinline__ void block_tree_n(double (&v)[NQ], double *sh) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) sh[q * MC_THREADS + tid] = v[q];
+    __syncthreads();
+    for (int s = MC_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) sh[q * MC_THREADS + tid] = sh[q * MC_THREADS + tid] + sh[q * MC_THREADS + tid + s];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) v[q] = sh[q * MC_THREADS];
+}
+
+struct WcHead { double n, mean, Jmax, s2, nmax, sd, klmax, kind; };
+
+// what every launch after wc_var knows about the sample (kind: WC_ST_SEARCH unless the sample is empty or holds an infinity)
+__device__ __forceinline__ WcHead wc_head(const double *scr, double *sh) {
+    const McHead hd = reduce_part1(scr + WC_O_P1, sh);
+    double v[2] = {scr[WC_O_PV + threadIdx.x], scr[WC_O_PV + MC_BLOCKS + threadIdx.x]};
+    block_tree_n<2>(v, sh);
+    WcHead r;
+    r.n = hd.n_ok; r.mean = hd.sum / hd.n_ok; r.Jmax = hd.mx; r.s2 = v[0]; r.nmax = v[1];
+    r.sd = sqrt(r.s2 / r.n);
+    r.klmax = log(r.n / r.nmax);
+    r.kind = !(hd.n_ok > 0.0) ? WC_ST_EMPTY : !(hd.mn > -__builtin_inf() && hd.mx < __builtin_inf()) ? WC_ST_NONFINITE : WC_ST_SEARCH;
+    return r;
+}
+
+__device__ __forceinline__ double wc_theta0(const WcHead &h, double d) { return sqrt(2.0 * d) / h.sd; }
+
+__device__ __forceinline__ double wc_bound_state(const WcHead &h, double d) {
+    if (h.kind != WC_ST_SEARCH) return h.kind;
+    if (d == 0.0) return WC_ST_ZERO;                                  // (decided before the saturation rule: all costs equal, d = 0)
+    if (d >= h.klmax) return WC_ST_SAT;
+    const double t0 = wc_theta0(h, d);
+    return (t0 > 0.0 && t0 < __builtin_inf()) ? WC_ST_SEARCH : WC_ST_SAT;
+}
+
+// theta j of search pass `pass` in the bracket [lo, hi]
+__device__ __forceinline__ double wc_grid(int pass, int j, double lo, double hi, double theta0) {
+    const double t = (pass == 0) ? theta0 * ldexp(1.0, 2 * (j - WC_GEO_BELOW)) : lo + (hi - lo) * ((double)(j + 1) / (double)(WC_NPT + 1));
+    return t < WC_THETA_CAP ? t : WC_THETA_CAP;
+}
+
+// y_ref of a theta: exp(theta (mean - Jmax)) where the sums are centred about the mean, 0 where they are taken about Jmax
+__device__ __forceinline__ double wc_yref(double th, const WcHead &h) {
+    return (th * (h.Jmax - h.mean) <= WC_CENTRE_MAX) ? exp(th * (h.mean - h.Jmax)) : 0.0;
+}
+
+// one cost's terms at one theta: dd = y - y_ref and yc = y (J - c), from dm = J - mean and dx = J - Jmax.  Centred, y - y_ref is formed as
+// y_ref expm1(theta dm), exact to its own last digits: exp(theta dx) - y_ref would carry y's rounding, 1e-16 absolute against a sum of
+// order kl_bound per cost
+__device__ __forceinline__ void wc_term(double th, double yref, bool centred, double dm, double dx, double &dd, double &yc) {
+    if (centred) {
+        dd = yref * expm1(th * dm);
+        yc = (yref + dd) * dm;
+    } else {
+        dd = exp(th * dx);
+        yc = dd * dx;
+    }
+}
+
+// log Z - theta (c - Jmax) from A = sum (y - y_ref)
+__device__ __forceinline__ double wc_lz(double yref, double A, double n) { return (yref != 0.0) ? log1p(A / (n * yref)) : log(A / n); }
+__device__ __forceinline__ double wc_sumy(double yref, double A, double n) { return (yref != 0.0) ? n * yref + A : A; }
+__device__ __forceinline__ double wc_kl(double th, double yref, double A, double B, double n) {
+    return th * (B / wc_sumy(yref, A, n)) - wc_lz(yref, A, n);
+}
+
+// the bracket and state of bound b as search pass `pass` finds them: pass 0 decides the state from the sample alone, a later pass (and
+// wc_final, as pass WC_PASSES) reduces the partials of pass - 1 and narrows.  Every lane of every workgroup computes the same values.
+__device__ __forceinline__ void wc_bracket(const WcArgs &a, const WcHead &h, int b, int pass, double *sh, double &lo, double &hi, double &st) {
+    const double d = a.bound[b];
+    if (pass == 0) { lo = 0.0; hi = 0.0; st = wc_bound_state(h, d); return; }
+    const double *bi = a.scratch + WC_O_BRK + ((pass & 1) * WC_MAX_BOUND + b) * 4;
+    lo = bi[0]; hi = bi[1]; st = bi[2];
+    if (st != WC_ST_SEARCH) return;
+    const double *ps = a.scratch + WC_O_PS + (size_t)((pass - 1) & 1) * WC_PS_SET + (size_t)b * 2 * WC_NPT * MC_BLOCKS;
+    const double theta0 = wc_theta0(h, d);
+    double prev = lo, nlo = lo, nhi = hi;
+    bool found = false;
+    for (int q0 = 0; q0 < WC_NPT; q0 += 4) {
+        double v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = ps[(2 * q0 + q) * MC_BLOCKS + threadIdx.x];
+        block_tree_n<8>(v, sh);
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const double t = wc_grid(pass - 1, q0 + jj, lo, hi, theta0);
+            const double kl = wc_kl(t, wc_yref(t, h), v[2 * jj], v[2 * jj + 1], h.n);
+            if (!found) {
+                if (kl >= d) { found = true; nlo = prev; nhi = t; }
+                prev = t;
+            }
+        }
+    }
+    if (!found) {
+        if (pass == 1) st = WC_ST_SAT;                                // KL(theta_top) < d
+        else nlo = prev;                                              // (hi had KL >= d when it was chosen)
+    }
+    lo = nlo; hi = nhi;
+}
+
+__global__ __launch_bounds__(MC_THREADS) void wc_var(WcArgs a) {
+    __shared__ double sh[2 * MC_THREADS];
+    const McHead hd = reduce_part1(a.scratch + WC_O_P1, sh);
+    const double mean = hd.sum / hd.n_ok, Jmax = hd.mx;
+    double v[2] = {0.0, 0.0};
+    const long T = (long)MC_BLOCKS * MC_THREADS;
+    for (long k = (long)blockIdx.x * MC_THREADS + threadIdx.x; k < a.K; k += T) {
+        const double J = a.cost[k];
+        if (mc_nan(J)) continue;
+        const double dj = J - mean;
+        v[0] += dj * dj;
+        v[1] += (J == Jmax) ? 1.0 : 0.0;
+    }
+    block_tree_n<2>(v, sh);
+    if (threadIdx.x == 0) { a.scratch[WC_O_PV + blockIdx.x] = v[0]; a.scratch[WC_O_PV + MC_BLOCKS + blockIdx.x] = v[1]; }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void wc_search(WcArgs a) {
+    __shared__ double sh[8 * MC_THREADS];
+    const WcHead h = wc_head(a.scratch, sh);
+    const long T = (long)MC_BLOCKS * MC_THREADS;
+    for (int b = 0; b < a.n_bound; ++b) {                             // (bounds in turn: 16 thetas x 2 sums is what a lane holds)
+        double lo, hi, st;
+        wc_bracket(a, h, b, a.pass, sh, lo, hi, st);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            double *bo = a.scratch + WC_O_BRK + (((a.pass + 1) & 1) * WC_MAX_BOUND + b) * 4;
+            bo[0] = lo; bo[1] = hi; bo[2] = st; bo[3] = 0.0;
+        }
+        if (st != WC_ST_SEARCH) continue;                             // (uniform over the grid)
+        const double theta0 = wc_theta0(h, a.bound[b]);
+        double th[WC_NPT], yr[WC_NPT], A[WC_NPT], B[WC_NPT];
+        bool cen[WC_NPT];
+#pragma unroll
+        for (int j = 0; j < WC_NPT; ++j) {
+            th[j] = wc_grid(a.pass, j, lo, hi, theta0);
+            yr[j] = wc_yref(th[j], h);
+            cen[j] = __builtin_amdgcn_readfirstlane((int)(yr[j] != 0.0)) != 0;   // (the same in every lane: a scalar branch)
+            A[j] = 0.0; B[j] = 0.0;
+        }
+        for (long k = (long)blockIdx.x * MC_THREADS + threadIdx.x; k < a.K; k += T) {
+            const double J = a.cost[k];
+            if (mc_nan(J)) continue;
+            const double dm = J - h.mean, dx = J - h.Jmax;
+#pragma unroll
+            for (int j = 0; j < WC_NPT; ++j) {
+                double dd, yc;
+                wc_term(th[j], yr[j], cen[j], dm, dx, dd, yc);
+                A[j] += dd;
+                B[j] += yc;
+            }
+        }
+        double *ps = a.scratch + WC_O_PS + (size_t)(a.pass & 1) * WC_PS_SET + (size_t)b * 2 * WC_NPT * MC_BLOCKS;
+#pragma unroll
+        for (int q0 = 0; q0 < WC_NPT; q0 += 4) {
+            double v[8];
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) { v[2 * jj] = A[q0 + jj]; v[2 * jj + 1] = B[q0 + jj]; }
+            block_tree_n<8>(v, sh);
+            if (threadIdx.x == 0) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) ps[(2 * q0 + q) * MC_BLOCKS + blockIdx.x] = v[q];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void wc_final(WcArgs a) {
+    __shared__ double sh[8 * MC_THREADS];
+    __shared__ double s_th[WC_MAX_ROWS], s_st[WC_MAX_ROWS];
+    const WcHead h = wc_head(a.scratch, sh);
+    const int nrows = a.n_bound + a.n_theta;
+    for (int b = 0; b < a.n_bound; ++b) {
+        double lo, hi, st;
+        wc_bracket(a, h, b, WC_PASSES, sh, lo, hi, st);
+        if (threadIdx.x == 0) { s_th[b] = (st == WC_ST_SEARCH) ? 0.5 * (lo + hi) : 0.0; s_st[b] = st; }
+    }
+    if (threadIdx.x < a.n_theta) {
+        const double t = a.theta[threadIdx.x];
+        s_th[a.n_bound + threadIdx.x] = t;
+        s_st[a.n_bound + threadIdx.x] = (h.kind != WC_ST_SEARCH) ? h.kind : (t == 0.0 ? WC_ST_ZERO : WC_ST_SEARCH);
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && threadIdx.x < nrows) {
+        a.scratch[WC_O_INFO + 2 * threadIdx.x] = s_th[threadIdx.x];
+        a.scratch[WC_O_INFO + 2 * threadIdx.x + 1] = s_st[threadIdx.x];
+    }
+    const long T = (long)MC_BLOCKS * MC_THREADS;
+    for (int r0 = 0; r0 < nrows; r0 += WC_FROWS) {
+        const int ns = (nrows - r0 < WC_FROWS) ? nrows - r0 : WC_FROWS;
+        double th[WC_FROWS], yr[WC_FROWS], acc[WC_FROWS][WC_NFIN];
+        bool cen[WC_FROWS], live[WC_FROWS];                          // (live: the row needs sums; the others are written from the sample alone)
+#pragma unroll
+        for (int s = 0; s < WC_FROWS; ++s) {
+            live[s] = __builtin_amdgcn_readfirstlane((int)(s < ns && s_st[r0 + s] == WC_ST_SEARCH)) != 0;
+            th[s] = live[s] ? s_th[r0 + s] : 0.0;
+            yr[s] = wc_yref(th[s], h);
+            cen[s] = __builtin_amdgcn_readfirstlane((int)(yr[s] != 0.0)) != 0;
+            acc[s][0] = acc[s][1] = acc[s][2] = acc[s][3] = acc[s][4] = 0.0;
+        }
+        for (long k = (long)blockIdx.x * MC_THREADS + threadIdx.x; k < a.K; k += T) {
+            const double J = a.cost[k];
+            if (mc_nan(J)) continue;
+            const double dm = J - h.mean, dx = J - h.Jmax;
+#pragma unroll
+            for (int s = 0; s < WC_FROWS; ++s) {
+                if (live[s]) {                                        // (uniform)
+                    double dd, yc;
+                    wc_term(th[s], yr[s], cen[s], dm, dx, dd, yc);
+                    acc[s][0] += dd;
+                    acc[s][1] += dd * dd;
+                    acc[s][2] += yc;
+                    acc[s][3] += yc * (cen[s] ? dm : dx);
+                    acc[s][4] += (cen[s] ? yr[s] + dd : dd) * dx * dx;
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < WC_FROWS; ++s) {
+            if (s < ns) {
+                double v[WC_NFIN] = {acc[s][0], acc[s][1], acc[s][2], acc[s][3], acc[s][4]};
+                block_tree_n<WC_NFIN>(v, sh);
+                if (threadIdx.x == 0) {
+#pragma unroll
+                    for (int q = 0; q < WC_NFIN; ++q) a.scratch[WC_O_PF + ((r0 + s) * WC_NFIN + q) * MC_BLOCKS + blockIdx.x] = v[q];
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void wc_rows(WcArgs a) {
+    __shared__ double sh[WC_NFIN * MC_THREADS];
+    const WcHead h = wc_head(a.scratch, sh);
+    const int nrows = a.n_bound + a.n_theta;
+    const double nan = __builtin_nan(""), n = h.n;
+    const double se_mean = (n >= 2.0) ? sqrt(h.s2 / (n - 1.0) / n) : nan;
+    for (int r = 0; r < nrows; ++r) {
+        double v[WC_NFIN];
+#pragma unroll
+        for (int q = 0; q < WC_NFIN; ++q) v[q] = a.scratch[WC_O_PF + (r * WC_NFIN + q) * MC_BLOCKS + threadIdx.x];
+        block_tree_n<WC_NFIN>(v, sh);
+        if (threadIdx.x != 0) continue;
+        const double th = a.scratch[WC_O_INFO + 2 * r], st = a.scratch[WC_O_INFO + 2 * r + 1];
+        double o[WC_NSTAT], sumy = nan;
+        if (st == WC_ST_EMPTY || st == WC_ST_NONFINITE) {
+            for (int q = 0; q < 7; ++q) o[q] = nan;
+            o[7] = (st == WC_ST_EMPTY) ? 2.0 : 3.0;
+        } else if (st == WC_ST_ZERO) {
+            o[0] = 0.0; o[1] = 0.0; o[2] = h.mean; o[3] = se_mean; o[4] = h.mean; o[5] = h.s2 / n; o[6] = n; o[7] = 0.0;
+            sumy = n;
+        } else if (st == WC_ST_SAT) {
+            o[0] = __builtin_inf(); o[1] = h.klmax; o[2] = h.Jmax; o[3] = nan; o[4] = h.Jmax; o[5] = 0.0; o[6] = h.nmax; o[7] = 1.0;
+        } else {
+            const double A = v[0], A2 = v[1], B = v[2], B2 = v[3], B2x = v[4];
+            const double yr = wc_yref(th, h), c = (yr != 0.0) ? h.mean : h.Jmax;
+            sumy = wc_sumy(yr, A, n);
+            const double lz = wc_lz(yr, A, n), mc = B / sumy, kl = th * mc - lz;
+            const double d = (r < a.n_bound) ? a.bound[r] : kl;
+            // the tilted variance about the nearer of the two centres: E (J - c)^2 - (m - c)^2 cancels where m is far from c
+            const double mx = (yr != 0.0) ? mc + (h.mean - h.Jmax) : mc;
+            double tvar = (fabs(mc) <= fabs(mx)) ? B2 / sumy - mc * mc : B2x / sumy - mx * mx;
+            if (tvar < 0.0) tvar = 0.0;
+            double vy = (n >= 2.0) ? (A2 - A * A / n) / (n - 1.0) : nan;
+            if (vy < 0.0) vy = 0.0;
+            o[0] = th; o[1] = kl; o[2] = c + (lz + d) / th;
+            o[3] = sqrt(vy) / ((sumy / n) * th * sqrt(n));            // delta method, as mc_final's risk_se
+            o[4] = c + mc; o[5] = tvar;
+            o[6] = sumy * sumy / (A2 + 2.0 * yr * A + n * yr * yr);    // sum y^2 = sum (y - y_ref)^2 + 2 y_ref A + n y_ref^2
+            o[7] = 0.0;
+        }
+        for (int q = 0; q < WC_NSTAT; ++q) a.scratch[WC_O_ROWS + r * WC_NSTAT + q] = o[q];
+        if (r == 0) {
+            double *x = a.scratch + WC_O_AUX;
+            x[0] = th; x[1] = sumy; x[2] = h.Jmax; x[3] = st; x[4] = h.nmax; x[5] = n; x[6] = 0.0; x[7] = 0.0;
+        }
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void wc_weights(WcArgs a) {
+    const double *x = a.scratch + WC_O_AUX;
+    const double th = x[0], sumy = x[1], Jmax = x[2], st = x[3], nmax = x[4];
+    const long T = (long)gridDim.x * MC_THREADS;
+    for (long k = (long)blockIdx.x * MC_THREADS + threadIdx.x; k < a.K; k += T) {
+        const double J = a.cost[k];
+        double w;
+        if (mc_nan(J)) w = 0.0;
+        else if (st == WC_ST_SAT) w = (J == Jmax) ? 1.0 / nmax : 0.0;
+        else if (st == WC_ST_SEARCH || st == WC_ST_ZERO) w = exp(th * (J - Jmax)) / sumy;
+        else w = __builtin_nan("");
+        a.weights[k] = w;
+    }
+}
+
 }  // namespace
 
 void launch_policy_mc(const McArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(mc_pass1, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
     hipLaunchKernelGGL(mc_pass2, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
     hipLaunchKernelGGL(mc_final, dim3(1), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_policy_wc(const WcArgs &a0, hipStream_t s) {
+    WcArgs a = a0;
+    McArgs m;
+    memset(&m, 0, sizeof(m));
+    m.cost = a.cost; m.K = a.K; m.scratch = a.scratch + WC_O_P1;
+    hipLaunchKernelGGL(mc_pass1, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, m);
+    hipLaunchKernelGGL(wc_var, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
+    if (a.n_bound > 0)
+        for (a.pass = 0; a.pass < WC_PASSES; ++a.pass) hipLaunchKernelGGL(wc_search, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
+    hipLaunchKernelGGL(wc_final, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
+    hipLaunchKernelGGL(wc_rows, dim3(1), dim3(MC_THREADS), 0, s, a);
+    if (a.weights) {
+        const long nb = (a.K + MC_THREADS - 1) / MC_THREADS;
+        hipLaunchKernelGGL(wc_weights, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(MC_THREADS), 0, s, a);
+    }
 }

@@ -187,6 +187,9 @@ class GenericContext(il.Context):
     def policy_evaluate_noise(self, *a, **k):
         self._carrier_only("policy_evaluate_noise")
 
+    def policy_worst_case(self, *a, **k):
+        self._carrier_only("policy_worst_case")
+
     def solve_batch(self, *a, **k):
         self._carrier_only("solve_batch")
 

@@ -167,6 +167,36 @@ class Context:
                     var=float(stats[nv.MC_VAR]), min=float(stats[nv.MC_MIN]), max=float(stats[nv.MC_MAX]),
                     se_mean=float(stats[nv.MC_SE_MEAN]), risk=risk, risk_se=se, costs=costs, x=x, u=u)
 
+    def policy_worst_case(self, kl_bounds=(), thetas=(), costs=None, want_weights=False):
+        """The worst-case expected cost sup { E_p[J] : KL(p || q) <= d } of a sample of Monte-Carlo costs (rat_policy_worst_case), by its
+        one-dimensional dual searched on the device.  costs None: the costs the last policy_evaluate / policy_evaluate_noise on this
+        context left on the device (or the ones an earlier call uploaded); otherwise K host values (NaN = DomainError rollout, left out).  kl_bounds: up to 16 radii d >= 0;
+        thetas: up to 16 tilts >= 0.  Returns {"bounds": rows, "thetas": rows, "weights": (K,) or None}; rows is a dict of arrays keyed
+        theta, kl, bound, bound_se, tilt_mean, tilt_var, ess, flag (int: 0 OK, 1 saturated, 2 empty, 3 non-finite), one entry per
+        kl_bound / per theta.  weights: y_k / sum y at kl_bounds[0]'s theta* (thetas[0] without bounds), 0 at a DomainError rollout."""
+        d = nv.f64(np.atleast_1d(np.asarray(kl_bounds, dtype=np.float64))).ravel()
+        th = nv.f64(np.atleast_1d(np.asarray(thetas, dtype=np.float64))).ravel()
+        K = 0
+        if costs is not None:
+            costs = nv.f64(costs).ravel()
+            K = costs.size
+        ob, ot = np.zeros((d.size, nv.WC_NSTAT)), np.zeros((th.size, nv.WC_NSTAT))
+        w = None
+        if want_weights:
+            kw = K if costs is not None else int(self.debug_get("mc_cost_K"))
+            w = np.zeros(max(kw, 1))
+        nv.check(nv.lib().rat_policy_worst_case(self.h, nv.P(costs), C.c_int64(K), nv.P(d) if d.size else None, C.c_int32(d.size),
+                                                nv.P(th) if th.size else None, C.c_int32(th.size), nv.P(ob) if d.size else None,
+                                                nv.P(ot) if th.size else None, nv.P(w)))
+
+        def rows(o):
+            r = {k: o[:, i].copy() for i, k in enumerate(nv.WC_SLOTS)}
+            r["flag"] = r["flag"].astype(np.int64)
+            return r
+        if w is not None and costs is None:
+            w = w[:int(self.debug_get("mc_cost_K"))]
+        return dict(bounds=rows(ob), thetas=rows(ot), weights=w)
+
     def integrate_cost(self, x, u):
         out = C.c_double()
         nv.check(nv.lib().rat_integrate_cost(self.h, nv.P(nv.f64(x)), nv.P(nv.f64(u)), C.byref(out)))
