@@ -270,7 +270,8 @@ rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, const double
  *   out_bound  [n_bound][RAT_WC_NSTAT], out_theta [n_theta][RAT_WC_NSTAT]: a row of the slots below per kl_bound / per theta
  *   weights_out[K] or NULL: y_k / sum y at kl_bound[0]'s theta* (at theta[0] when n_bound == 0), 0 for a DomainError rollout; on a
  *              saturated row 1 / n_max on the maxima and 0 elsewhere.  The importance weights that turn rat_policy_evaluate_noise's
- *              x_out / u_out into worst-case trajectories on the host.
+ *              x_out / u_out into worst-case trajectories on the host (rat_policy_worst_case_trajectory forms their moments on the
+ *              device instead).
  * Flags: RAT_WC_SATURATED when kl_bound >= log(N_OK / n_max), or when theta_top = 65536 theta_0 still has KL < kl_bound: the row holds the
  * theta -> Inf limits (THETA +Inf, KL log(N_OK / n_max), BOUND = TILT_MEAN = Jmax, TILT_VAR 0, ESS n_max, BOUND_SE NaN).  RAT_WC_EMPTY:
  * N_OK == 0; RAT_WC_NONFINITE: a +-Inf among the costs; every other slot is NaN in both.  kl_bound == 0 is decided first: theta 0, KL 0,
@@ -292,6 +293,28 @@ rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, const double
 #define RAT_WC_NONFINITE 3
 rat_rc rat_policy_worst_case(rat_handle h, const double *cost, int64_t K, const double *kl_bound, int32_t n_bound,
                              const double *theta, int32_t n_theta, double *out_bound, double *out_theta, double *weights_out);
+/* What the worst case looks like: the mean and covariance of (x_t, u_t) at every step under the nominal distribution q (a theta = 0 row)
+ * and under the worst-case distribution p* ~ exp(theta* J) q of each kl_bound (and the tilt of each given theta), formed on the device.
+ * The call takes no policy and no noise: it REPLAYS the last rat_policy_evaluate / rat_policy_evaluate_noise of the handle -- the same
+ * rollout kernel, chunks and seeds, the trajectories staged in buffers of the handle -- and sums, per step and row, S0 = sum y,
+ * S1 = sum y D and S2 = sum y D D' of D = (x_t, u_t) - c_t with y = exp(theta (J - Jmax)) from the stored costs (one f64 MFMA per four
+ * rollouts, step and row).  c_t is (x_nom[t], l[t]) under a policy and the noise-free open-loop trajectory with L == NULL.  Fixed
+ * summation order, no floating-point atomics: the same call returns the same bits, and a row's bits do not depend on the other rows.
+ *   kl_bound, theta   as rat_policy_worst_case's (the same refusals)
+ *   rows_out  [(n_bound + n_theta)][RAT_WC_NSTAT]: rat_policy_worst_case's rows of the same arguments, bit for bit (bounds, then thetas)
+ *   mean_out  [(n_bound + n_theta)][N+1][n+m]: E (x_t, u_t); the u part of step N is 0
+ *   cov_out   [(n_bound + n_theta)][N+1][(n+m)^2] column-major, the population form sum y (z - mean)(z - mean)' / sum y (as RAT_WC_TILT_VAR);
+ *             rows and columns of u at step N are 0
+ * A RAT_WC_SATURATED row holds the moments of the rollouts that attain Jmax; RAT_WC_EMPTY and RAT_WC_NONFINITE rows are NaN.  A
+ * DomainError rollout carries no weight.
+ * Served: the LQ and power-law families (n <= 12, m <= 4) after rat_policy_evaluate with z == NULL, and source models after
+ * rat_policy_evaluate_noise with zn == zu == NULL.  RAT_ERR_UNSUPPORTED: general sizes; a source model evaluated under N(0, W) by
+ * rat_policy_evaluate (write the Gaussian as rat_user_noise); an evaluation on injected draws (the caller has x_out: combine it with
+ * weights_out on the host); rows x (N + 1) above 3640.  RAT_ERR_ARG, the handle stays usable: no evaluation on the handle yet, or costs
+ * uploaded by rat_policy_worst_case(cost != NULL) since; and a replay whose costs are not the stored ones bit for bit (NaN equals NaN):
+ * the problem, its parameters or the policy changed since the evaluation. */
+rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                        double *rows_out, double *mean_out, double *cov_out);
 /* approximate_model(problem, u_array, x_array)                 ileqg.jl:258-322
  * -> q[N+1], qv[n*(N+1)], Q[n*n*(N+1)], r[m*N], R[m*m*N], P[m*n*N], A[n*n*N], B[n*m*N], W[n*n*N] */
 rat_rc rat_approximate_model(rat_handle h, const double *u, const double *x,

@@ -412,6 +412,28 @@ function policy_worst_case(s::ILEQGSolver; kl_bounds=Float64[], thetas=Float64[]
     (bounds=rows(ob), thetas=rows(ot), weights=want_weights ? w[1:K] : nothing)
 end
 
+"""
+policy_worst_case_trajectory(s; kl_bounds, thetas): what the worst case looks like (rat_policy_worst_case_trajectory).  The mean and
+covariance of the state and the control at every step under the worst-case distribution p* ∝ exp(θ* J) q of each KL radius, and under the
+tilt of each given θ (θ = 0 is the nominal distribution q), formed on the device by replaying the last evaluate_policy on this solver's
+handle (device generator only).  Returns (bounds, thetas): each a named tuple of policy_worst_case's row vectors and, with R rows,
+mean_x (n, N+1, R), cov_x (n, n, N+1, R), mean_u (m, N, R), cov_u (m, m, N, R), cov_xu (n, m, N, R); population covariances.
+"""
+function policy_worst_case_trajectory(s::ILEQGSolver; kl_bounds=Float64[], thetas=Float64[])
+    h = s.h
+    n, m, N = dims(h.problem)
+    d = collect(Float64, kl_bounds); th = collect(Float64, thetas)
+    nb = length(d); nt = length(th); R = nb + nt; q = n + m
+    rows = zeros(8, R); mean = zeros(q, N + 1, R); cov = zeros(q, q, N + 1, R)
+    check(ccall((:rat_policy_worst_case_trajectory, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, nb > 0 ? d : C_NULL, nb, nt > 0 ? th : C_NULL, nt, rows, mean, cov))
+    part(r) = (theta=rows[1, r], kl=rows[2, r], bound=rows[3, r], bound_se=rows[4, r], tilt_mean=rows[5, r], tilt_var=rows[6, r],
+               ess=rows[7, r], flag=Int.(rows[8, r]), mean_x=mean[1:n, :, r], cov_x=cov[1:n, 1:n, :, r], mean_u=mean[n+1:q, 1:N, r],
+               cov_u=cov[n+1:q, n+1:q, 1:N, r], cov_xu=cov[1:n, n+1:q, 1:N, r])
+    (bounds=part(1:nb), thetas=part(nb+1:R))
+end
+
 "integrate_cost(problem, x_array, u_array) -- ileqg.jl:115-124"
 function integrate_cost(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_array, u_array)
     h = bind!(s.h, problem); c = Ref(0.0)
@@ -1254,7 +1276,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

@@ -92,6 +92,7 @@ EXPORTS = [
     "rat_policy_evaluate",
     "rat_policy_evaluate_noise", "rat_user_noise_check",
     "rat_policy_worst_case",
+    "rat_policy_worst_case_trajectory",
 ]
 MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 WC_SLOTS = ("theta", "kl", "bound", "bound_se", "tilt_mean", "tilt_var", "ess", "flag")      # RAT_WC_* slots of the header, in order
@@ -136,6 +137,7 @@ def lib():
                                                    C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]
         _lib.rat_user_noise_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
         _lib.rat_policy_worst_case.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp]
+        _lib.rat_policy_worst_case_trajectory.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp]
     return _lib
 
 

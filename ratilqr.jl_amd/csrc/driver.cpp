@@ -209,6 +209,22 @@ struct rat_handle_s {
     double *d_mc_zu = nullptr; size_t cap_mc_zu = 0;         // injected uniforms of one chunk (the normals use d_mc_z)
     double *d_mc_xo = nullptr; size_t cap_mc_xo = 0;         // [chunk][N+1][n] trajectory staging
     double *d_mc_uo = nullptr; size_t cap_mc_uo = 0;         // [chunk][N][m]
+    // the worst-case trajectory moments (rat_policy_worst_case_trajectory, policy_mc.hip) replay the last evaluation: the scalars of that
+    // call (its packed policy is d_mc_in, its costs d_mc_cost), and the replay's buffers, grown on demand
+    struct McReplay {
+        int kind = 0;                // 0 none; 1 a family on the tile path; 2 a source model under rat_user_noise; 3 general size; 4 a source under N(0, W)
+        bool injected = false, has_L = false;
+        uint64_t seed = 0;
+        int64_t K = 0;
+        int npn = 0, npu = 0;        // kind 2: the declared draw counts
+        size_t o_x = 0, o_l = 0, o_L = 0;   // offsets into d_mc_in
+        int n = 0, m = 0, N = 0, model = 0, W_tv = 0;   // the problem the pack was laid out for
+    } mc_rec;
+    double *d_wt_cost = nullptr; size_t cap_wt_cost = 0;     // [chunk] replayed costs
+    int *d_wt_dom = nullptr; size_t cap_wt_dom = 0;          // [chunk] replayed DomainError flags (families)
+    double *d_wt_y = nullptr; size_t cap_wt_y = 0;           // [rows][chunk] weights
+    double *d_wt_part = nullptr; size_t cap_wt_part = 0;     // [rows][N+1][WT_SLOTS][WT_PART] partials
+    double *d_wt_out = nullptr; size_t cap_wt_out = 0;       // centre [N+1][16] | mean | cov | S0, sum y^2 per row | mismatch count
 };
 
 extern "C" int32_t rat_version(void) { return RAT_VERSION; }
@@ -386,6 +402,7 @@ extern "C" void rat_destroy(rat_handle h) {
     if (h->src_noisy_mod) (void)hipModuleUnload(h->src_noisy_mod);
     for (double *q : {h->d_mc_zu, h->d_mc_xo, h->d_mc_uo}) if (q) (void)hipFree(q);
     for (double *q : {h->d_wc_red, h->d_wc_w}) if (q) (void)hipFree(q);
+    for (void *q : {(void *)h->d_wt_cost, (void *)h->d_wt_dom, (void *)h->d_wt_y, (void *)h->d_wt_part, (void *)h->d_wt_out}) if (q) (void)hipFree(q);
     if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
@@ -2034,6 +2051,7 @@ extern "C" rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const d
     // every earlier call has finished, the entry point is synchronous)
     const size_t one = 1;
     h->mc_cost_K = 0;                                             // (d_mc_cost is about to be regrown or overwritten)
+    h->mc_rec.kind = 0;
     size_t cap_red = h->d_mc_red ? MC_SCRATCH : 0;
     if ((rc = grow(&h->d_mc_in, &h->cap_mc_in, pack.size()))) return rc;
     if ((rc = grow(&h->d_mc_cost, &h->cap_mc_cost, std::max((size_t)K, one)))) return rc;
@@ -2081,6 +2099,11 @@ extern "C" rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const d
     if (cost_out) HIPCHK(hipMemcpyAsync(cost_out, h->d_mc_cost, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->mc_cost_K = K;
+    {   // what rat_policy_worst_case_trajectory needs to run these rollouts again
+        rat_handle_s::McReplay &r = h->mc_rec;
+        r.kind = h->wide ? 3 : (source ? 4 : 1); r.injected = z != nullptr; r.has_L = L != nullptr; r.seed = seed; r.K = K; r.npn = r.npu = 0;
+        r.o_x = o_x; r.o_l = o_l; r.o_L = o_L; r.n = n; r.m = m; r.N = N; r.model = h->wide ? -1 : h->pb.model; r.W_tv = h->W_tv;
+    }
     for (int i = 0; i < RAT_MC_NSTAT; ++i) stats[i] = out[i];
     for (int i = 0; i < n_theta; ++i) {
         if (risk) risk[i] = out[8 + i];
@@ -2145,6 +2168,7 @@ extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, c
     const int64_t chunk = std::min<int64_t>(K, 1 << 16);
     const size_t one = 1, nxo = (size_t)(N + 1) * n, nuo = (size_t)N * m;
     h->mc_cost_K = 0;                                             // (d_mc_cost is about to be regrown or overwritten)
+    h->mc_rec.kind = 0;
     size_t cap_red = h->d_mc_red ? MC_SCRATCH : 0;
     if ((rc = grow(&h->d_mc_in, &h->cap_mc_in, pack.size()))) return rc;
     if ((rc = grow(&h->d_mc_cost, &h->cap_mc_cost, std::max((size_t)K, one)))) return rc;
@@ -2193,6 +2217,11 @@ extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, c
         return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: a step drew more than was declared (normals_per_step = " + std::to_string(npn) +
                                  ", uniforms_per_step = " + std::to_string(npu) + "): the overdrawn values were NaN");
     h->mc_cost_K = K;
+    {
+        rat_handle_s::McReplay &r = h->mc_rec;
+        r.kind = 2; r.injected = inject; r.has_L = L != nullptr; r.seed = seed; r.K = K; r.npn = npn; r.npu = npu;
+        r.o_x = 0; r.o_l = o_l; r.o_L = o_L; r.n = n; r.m = m; r.N = N; r.model = h->pb.model; r.W_tv = h->W_tv;
+    }
     for (int i = 0; i < RAT_MC_NSTAT; ++i) stats[i] = out[i];
     for (int i = 0; i < n_theta; ++i) {
         if (risk) risk[i] = out[8 + i];
@@ -2236,6 +2265,7 @@ extern "C" rat_rc rat_policy_worst_case(rat_handle h, const double *cost, int64_
     if (weights_out && (rc = grow(&h->d_wc_w, &h->cap_wc_w, (size_t)K))) return rc;
     if (cost) {
         h->mc_cost_K = 0;                                             // (the buffer's costs are replaced; valid again after the wait)
+        h->mc_rec.kind = 0;                                           // (... and they are no evaluation's: nothing to replay)
         if ((rc = grow(&h->d_mc_cost, &h->cap_mc_cost, (size_t)K))) return rc;
         HIPCHK(hipMemcpyAsync(h->d_mc_cost, cost, (size_t)K * 8, hipMemcpyHostToDevice, h->stream));
     }
@@ -2254,6 +2284,134 @@ extern "C" rat_rc rat_policy_worst_case(rat_handle h, const double *cost, int64_
     h->mc_cost_K = K;                                                 // (uploaded costs serve a later cost == NULL call like an evaluation's)
     for (int i = 0; i < n_bound * WC_NSTAT; ++i) out_bound[i] = rows[i];
     for (int i = 0; i < n_theta * WC_NSTAT; ++i) out_theta[i] = rows[n_bound * WC_NSTAT + i];
+    return RAT_OK;
+}
+
+// The state and control mean and covariance at every step under the nominal distribution q and under the worst-case distribution
+// p* ~ exp(theta* J) q, one row per kl_bound / theta as rat_policy_worst_case's rows.  It replays the handle's last evaluation (mc_rec): the
+// same rollout kernel in the same chunks with the same seeds, the trajectories staged in buffers of the handle, and behind each chunk the
+// moment kernels of policy_mc.hip; one enqueue chain, one host wait.  The replay's costs are held against the stored ones bit for bit: a
+// difference means the problem, its parameters or the policy pack is no longer what the evaluation ran.
+extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                                   double *rows_out, double *mean_out, double *cov_out) {
+    const char *F = "rat_policy_worst_case_trajectory: ";
+    if (!h) return fail(RAT_ERR_ARG, std::string(F) + "null handle");
+    if (n_bound < 0 || n_bound > WC_MAX_BOUND) return fail(RAT_ERR_ARG, std::string(F) + "n_bound must be in 0 .. 16");
+    if (n_theta < 0 || n_theta > MC_MAX_THETA) return fail(RAT_ERR_ARG, std::string(F) + "n_theta must be in 0 .. 16");
+    if (n_bound + n_theta == 0) return fail(RAT_ERR_ARG, std::string(F) + "no kl_bound and no theta: nothing to compute");
+    if ((n_bound > 0 && !kl_bound) || (n_theta > 0 && !theta) || !rows_out || !mean_out || !cov_out)
+        return fail(RAT_ERR_ARG, std::string(F) + "null kl_bound / theta / output");
+    for (int i = 0; i < n_bound; ++i)
+        if (!(kl_bound[i] >= 0.0)) return fail(RAT_ERR_ARG, std::string(F) + "every kl_bound must be >= 0 (+Inf is allowed, NaN is not)");
+    for (int i = 0; i < n_theta; ++i)
+        if (!(theta[i] >= 0.0) || std::isinf(theta[i])) return fail(RAT_ERR_ARG, std::string(F) + "every theta must be >= 0 and finite");
+    if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
+    if (h->wide)
+        return fail(RAT_ERR_UNSUPPORTED, std::string(F) + "compiled for n <= 12, m <= 4 (general sizes: rat_rollout_noisy's x_out / u_out with "
+                                         "rat_policy_worst_case's weights_out, combined on the host)");
+    const rat_handle_s::McReplay rec = h->mc_rec;
+    if (rec.kind == 0 || h->mc_cost_K == 0 || rec.K != h->mc_cost_K)
+        return fail(RAT_ERR_ARG, std::string(F) + "no evaluation to replay: call rat_policy_evaluate / rat_policy_evaluate_noise on this handle first "
+                                 "(costs uploaded by rat_policy_worst_case are no evaluation's)");
+    if (rec.kind == 4)
+        return fail(RAT_ERR_UNSUPPORTED, std::string(F) + "a source model evaluated under N(0, W) has no trajectory output: write the Gaussian as "
+                                         "rat_user_noise and evaluate with rat_policy_evaluate_noise");
+    if (rec.injected)
+        return fail(RAT_ERR_UNSUPPORTED, std::string(F) + "the evaluation ran on injected draws, which are not kept: combine the trajectories the "
+                                         "caller has (x_out / u_out) with rat_policy_worst_case's weights_out on the host");
+    const bool source = h->pb.model == RAT_MODEL_SOURCE;
+    const char *changed = "the problem, its parameters or the policy changed since the evaluation: evaluate again";
+    if (rec.kind == 3 || rec.n != h->n || rec.m != h->m || rec.N != h->N || rec.model != h->pb.model || rec.W_tv != h->W_tv || (rec.kind == 2) != source ||
+        (source && (!h->src_un || h->src_un_npn != rec.npn || h->src_un_npu != rec.npu || !h->h_un_over)))
+        return fail(RAT_ERR_ARG, std::string(F) + changed);
+    const int n = h->n, m = h->m, N = h->N, nrows = n_bound + n_theta, d = n + m;
+    if ((long)nrows * (N + 1) > WT_MAX_ROWSTEPS)
+        return fail(RAT_ERR_UNSUPPORTED, std::string(F) + "rows x (N + 1) = " + std::to_string((long)nrows * (N + 1)) + " is above " +
+                                         std::to_string(WT_MAX_ROWSTEPS) + " (64 MiB of partial sums): ask for fewer rows per call");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t K = rec.K, chunk = std::min<int64_t>(K, 1 << 16);
+    const int ldx = source ? n : XSTR, ldu = source ? m : USTR;
+    const size_t o_mean = (size_t)(N + 1) * 16, o_cov = o_mean + (size_t)nrows * (N + 1) * d, o_ess = o_cov + (size_t)nrows * (N + 1) * d * d,
+                 o_cnt = o_ess + 2 * (size_t)nrows, n_out = o_cnt + 1, n_part = (size_t)nrows * (N + 1) * WT_SLOTS * WT_PART;
+    rat_rc rc;
+    size_t cap_red = h->d_wc_red ? WC_SCRATCH : 0;
+    if ((rc = grow(&h->d_wc_red, &cap_red, (size_t)WC_SCRATCH))) return rc;
+    if ((rc = grow(&h->d_mc_xo, &h->cap_mc_xo, (size_t)chunk * (N + 1) * ldx))) return rc;
+    if ((rc = grow(&h->d_mc_uo, &h->cap_mc_uo, std::max<size_t>((size_t)chunk * N * ldu, 1)))) return rc;
+    if ((rc = grow(&h->d_wt_cost, &h->cap_wt_cost, (size_t)chunk))) return rc;
+    if (!source && (rc = grow(&h->d_wt_dom, &h->cap_wt_dom, (size_t)chunk))) return rc;
+    if ((rc = grow(&h->d_wt_y, &h->cap_wt_y, (size_t)nrows * chunk))) return rc;
+    if ((rc = grow(&h->d_wt_part, &h->cap_wt_part, n_part))) return rc;
+    if ((rc = grow(&h->d_wt_out, &h->cap_wt_out, n_out))) return rc;
+    const double *d_x = h->d_mc_in + rec.o_x, *d_l = h->d_mc_in + rec.o_l, *d_L = rec.has_L ? h->d_mc_in + rec.o_L : nullptr;
+    // the centre: (x_nom, l) under a policy; open loop the noise-free trajectory of the handle's own rollout from the pack's (x_0, l)
+    const double *cx = d_x;
+    if (!rec.has_L) {
+        StateDev st;
+        if ((rc = op_prepare(h, 0.0, 0.0, h->opts.delta_0, &st))) return rc;
+        RolloutArgs ra; ra.st = st; ra.pb = h->pb; ra.op = h->opd; ra.dump = h->d_dump; ra.mode = 0; ra.x0 = d_x; ra.u0 = d_l; ra.notile = 0; ra.multi = 0;
+        model_rollout(h, ra, h->stream);
+        cx = h->st.xs;                                                // (slot 0: [N+1][12])
+    }
+    launch_wct_centre(cx, d_l, n, m, N, h->d_wt_out, h->stream);
+    // theta*, Jmax and the rows, on the stored costs
+    WcArgs wa;
+    memset(&wa, 0, sizeof(wa));
+    wa.cost = h->d_mc_cost; wa.K = (long)K; wa.n_bound = n_bound; wa.n_theta = n_theta; wa.scratch = h->d_wc_red; wa.weights = nullptr;
+    for (int i = 0; i < n_bound; ++i) wa.bound[i] = kl_bound[i];
+    for (int i = 0; i < n_theta; ++i) wa.theta[i] = theta[i];
+    launch_policy_wc(wa, h->stream);
+    HIPCHK(hipMemsetAsync(h->d_wt_part, 0, n_part * 8, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_wt_out + o_cnt, 0, 8, h->stream));
+    int *d_over = nullptr;
+    if (source) { HIPCHK(hipHostGetDevicePointer((void **)&d_over, h->h_un_over, 0)); *h->h_un_over = 0; }
+    WtArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    ta.xs = h->d_mc_xo; ta.us = h->d_mc_uo; ta.ldx = ldx; ta.ldu = ldu; ta.n = n; ta.m = m; ta.N = N;
+    ta.cost_re = h->d_wt_cost; ta.dom_re = source ? nullptr : h->d_wt_dom; ta.nrows = nrows; ta.wc = h->d_wc_red; ta.y = h->d_wt_y; ta.ldy = (long)chunk;
+    ta.centre = h->d_wt_out; ta.part = h->d_wt_part; ta.mismatch = reinterpret_cast<int *>(h->d_wt_out + o_cnt);
+    ta.mean = h->d_wt_out + o_mean; ta.cov = h->d_wt_out + o_cov; ta.ess = h->d_wt_out + o_ess;
+    for (int64_t k0 = 0; k0 < K; k0 += chunk) {                       // (the stream orders a chunk's rollouts behind the sums of the one before)
+        const int64_t kc = std::min(chunk, K - k0);
+        if (source) {
+            SrcUserNoisyArgs a;
+            a.xnom = d_x; a.l = d_l; a.L = d_L; a.zn = nullptr; a.zu = nullptr;
+            a.K = (long)kc; a.j0 = (long)k0; a.N = N; a.tpw = h->src_mc_tpw; a.seed = rec.seed; a.cost = h->d_wt_cost;
+            a.x_out = h->d_mc_xo; a.u_out = h->d_mc_uo; a.p = h->d_src_p; a.overdraw = d_over;
+            void *args[] = {&a};
+            HIPCHK(hipModuleLaunchKernel(h->src_un, (unsigned)((kc + a.tpw - 1) / a.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+        } else {
+            NoisyArgs a;
+            a.pb = h->pb; a.Wchol = h->d_mc_in; a.xnom = d_x; a.l = d_l; a.L = d_L; a.K = (long)kc; a.z = nullptr;
+            a.seed = rec.seed + 0x9E3779B97F4A7C15ull * (uint64_t)(k0 / chunk);
+            a.x_out = h->d_mc_xo; a.u_out = h->d_mc_uo; a.cost = h->d_wt_cost; a.dom = h->d_wt_dom;
+            launch_noisy_rollout(a, h->stream);
+        }
+        ta.kc = (long)kc; ta.cost = h->d_mc_cost + k0;
+        launch_wct_chunk(ta, h->stream);
+    }
+    launch_wct_final(ta, h->stream);
+    HIPCHK(hipGetLastError());
+    double rows[WC_MAX_ROWS * WC_NSTAT], ess[WC_MAX_ROWS * 2];
+    int bad = 0;
+    HIPCHK(hipMemcpyAsync(rows, h->d_wc_red + WC_O_ROWS, (size_t)nrows * WC_NSTAT * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(ess, h->d_wt_out + o_ess, (size_t)nrows * 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&bad, h->d_wt_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(mean_out, h->d_wt_out + o_mean, (size_t)nrows * (N + 1) * d * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(cov_out, h->d_wt_out + o_cov, (size_t)nrows * (N + 1) * d * d * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (bad != 0)
+        return fail(RAT_ERR_ARG, std::string(F) + std::to_string(bad) + " of " + std::to_string(K) + " replayed rollouts cost something else than the "
+                                 "evaluation found: " + changed);
+    // the rows' effective sample size against the moment kernel's own S0^2 / sum y^2: two routes to one number (the rows' sums are centred,
+    // these are not: 1e-6 relative is far above what either loses and far below any error of the weights)
+    for (int r = 0; r < nrows; ++r) {
+        const double e_row = rows[r * WC_NSTAT + RAT_WC_ESS], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
+        if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
+            return fail(RAT_ERR_HIP, std::string(F) + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
+                                     " is not the row's " + std::to_string(e_row));
+    }
+    for (int i = 0; i < nrows * WC_NSTAT; ++i) rows_out[i] = rows[i];
     return RAT_OK;
 }
 

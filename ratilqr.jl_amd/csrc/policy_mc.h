@@ -65,3 +65,43 @@ struct WcArgs {
 // enqueues pass 1 (mc_pass1), the variance pass, WC_PASSES search passes, the final sums, the rows and (a.weights) the weights on s;
 // the rows are a.scratch + WC_O_ROWS
 void launch_policy_wc(const WcArgs &a, hipStream_t s);
+
+// ---- rat_policy_worst_case_trajectory: the mean and covariance of (x_t, u_t) under q and under p* ~ exp(theta* J) q (policy_mc.hip) --------
+// Per step t and row r, about a centre c_t known before any rollout runs: S0 = sum y, S1 = sum y D, S2 = sum y D D' and sum y^2 over the
+// rollouts, D = (x_t, u_t) - c_t in the 12 + 4 tile, y the row's weight of the rollout.  The trajectories are replayed a chunk at a time
+// into staging buffers; behind each chunk wct_weights forms the weights (and counts replayed costs that differ from the stored ones) and
+// wct_moments adds the chunk's sums into the partial of its workgroup; wct_final sums the partials in index order.
+#define WT_SLOTS 8            /* workgroups per (step, row batch): fixed, so that the summation order depends on K alone */
+#define WT_WAVES 4            /* wavefronts per workgroup; wavefront w of slot s takes the groups of four rollouts s * 4 + w, + 32, ... */
+#define WT_ROWS 8             /* rows a workgroup accumulates (grid.z = row batches) */
+#define WT_PART 288           /* doubles per partial: S2 [16][16] | S1 [16] | S0 | sum y^2 | padding */
+#define WT_O_S1 256
+#define WT_O_S0 272
+#define WT_O_SY2 273
+#define WT_MAX_ROWSTEPS 3640  /* rows x (N + 1) at most: the partials [rows][N+1][WT_SLOTS][WT_PART] stay below 64 MiB (30 MB: 32 rows, N = 50) */
+
+struct WtArgs {
+    const double *xs, *us;    // staged trajectories of the chunk: [kc][N+1][ldx], [kc][N][ldu]
+    int ldx, ldu;
+    int n, m, N;
+    long kc;                  // rollouts of the chunk
+    const double *cost;       // [kc] the stored costs of the chunk's rollouts (NaN: DomainError, selected out)
+    const double *cost_re;    // [kc] the costs the replay formed
+    const int *dom_re;        // [kc] the replay's DomainError flags, or null (its cost is NaN already)
+    int nrows;
+    const double *wc;         // launch_policy_wc's scratch: row info at WC_O_INFO, Jmax at WC_O_AUX + 2
+    double *y;                // [nrows][ldy] weights of the chunk
+    long ldy;
+    const double *centre;     // [N+1][16]
+    double *part;             // [nrows][N+1][WT_SLOTS][WT_PART]
+    int *mismatch;            // replayed costs whose bits differ from the stored ones (NaN equals NaN)
+    // wct_final only
+    double *mean;             // [nrows][N+1][n+m]
+    double *cov;              // [nrows][N+1][(n+m)^2] column-major
+    double *ess;              // [nrows][2]: S0 and sum y^2 of step 0
+};
+// c[t] = (x[t][0..n), u[t][0..m)) in the 12 + 4 tile, zero padded, zero where the source is not finite; x [N+1][12], u [N][4]
+void launch_wct_centre(const double *x, const double *u, int n, int m, int N, double *centre, hipStream_t s);
+// one chunk: the weights and the replay check, then the chunk's sums into the partials
+void launch_wct_chunk(const WtArgs &a, hipStream_t s);
+void launch_wct_final(const WtArgs &a, hipStream_t s);

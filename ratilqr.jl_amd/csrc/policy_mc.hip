@@ -475,7 +475,153 @@ __global__ __launch_bounds__(MC_THREADS) void wc_weights(WcArgs a) {
     }
 }
 
+// ---- rat_policy_worst_case_trajectory: weighted moments of the replayed trajectories ------------------------------------------------------
+// One MFMA per group of four rollouts, step and row: lane (i = lane & 15, kk = lane >> 4) holds D_i of rollout 4 g + kk, so A = y D is
+// [16 components][4 rollouts], B = D is [4 rollouts][16 components] and C += A B is the group's sum y D D'.  S1, S0 and sum y^2 ride along
+// in the same lanes (the four rollouts of a lane column are summed at the end).  Order: wavefront w of slot s takes the groups
+// s * WT_WAVES + w, + WT_SLOTS * WT_WAVES, ... in order; the wavefronts of a workgroup (and the four rollout lanes) are summed in index
+// order through LDS into the workgroup's partial, chunk after chunk in stream order; wct_final sums the slots in index order.  No
+// floating-point atomics (the replay check counts with an integer one: a count does not depend on the order).
+typedef double wt_d4 __attribute__((ext_vector_type(4)));
+#define WT_SH (256 + 64 + 8)   /* LDS doubles per wavefront and row: tile | S1 per lane | S0 [4] | sum y^2 [4] */
+
+__global__ __launch_bounds__(MC_THREADS) void wct_centre(const double *x, const double *u, int n, int m, int N, double *c) {
+    for (int e = blockIdx.x * MC_THREADS + threadIdx.x; e < (N + 1) * 16; e += gridDim.x * MC_THREADS) {
+        const int t = e >> 4, i = e & 15;
+        double v = 0.0;
+        if (i < 12) { if (i < n) v = x[t * 12 + i]; }
+        else if (i - 12 < m && t < N) v = u[t * 4 + (i - 12)];
+        if (!(fabs(v) < __builtin_inf())) v = 0.0;                    // (a centre is only a centre: any finite value serves)
+        c[e] = v;
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void wct_weights(WtArgs a) {
+    const double Jmax = a.wc[WC_O_AUX + 2];
+    const long T = (long)gridDim.x * MC_THREADS;
+    int bad = 0;
+    for (long q = (long)blockIdx.x * MC_THREADS + threadIdx.x; q < a.kc; q += T) {
+        const double J = a.cost[q];
+        double Jr = a.cost_re[q];
+        if (a.dom_re && a.dom_re[q]) Jr = __builtin_nan("");
+        const bool same = (mc_nan(J) && mc_nan(Jr)) || __double_as_longlong(J) == __double_as_longlong(Jr);
+        bad += same ? 0 : 1;
+        for (int r = 0; r < a.nrows; ++r) {
+            const double th = a.wc[WC_O_INFO + 2 * r], st = a.wc[WC_O_INFO + 2 * r + 1];
+            double y = 0.0;                                           // (a DomainError rollout, an empty or non-finite sample: no weight)
+            if (!mc_nan(J)) {
+                if (st == WC_ST_SEARCH) y = exp(th * (J - Jmax));
+                else if (st == WC_ST_ZERO) y = 1.0;
+                else if (st == WC_ST_SAT) y = (J == Jmax) ? 1.0 : 0.0;
+            }
+            a.y[(long)r * a.ldy + q] = y;
+        }
+    }
+    if (bad) atomicAdd(a.mismatch, bad);
+}
+
+__global__ __launch_bounds__(WT_WAVES * 64) void wct_moments(WtArgs a) {
+    __shared__ double sh[WT_WAVES][WT_SH];
+    const int slot = blockIdx.x, t = blockIdx.y, r0 = blockIdx.z * WT_ROWS;
+    const int nr = (a.nrows - r0 < WT_ROWS) ? a.nrows - r0 : WT_ROWS;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
+    const int N = a.N;
+    const bool isx = i < 12;
+    const bool comp = isx ? (i < a.n) : (i - 12 < a.m && t < N);      // (padding lanes, and u at step N, stay zero)
+    const double c = a.centre[t * 16 + i];
+    wt_d4 acc[WT_ROWS];
+    double s1[WT_ROWS], s0[WT_ROWS], sy2[WT_ROWS];
+#pragma unroll
+    for (int r = 0; r < WT_ROWS; ++r) { acc[r] = (wt_d4){0.0, 0.0, 0.0, 0.0}; s1[r] = 0.0; s0[r] = 0.0; sy2[r] = 0.0; }
+    const long G = (a.kc + 3) >> 2;
+    for (long g = (long)slot * WT_WAVES + w; g < G; g += (long)WT_SLOTS * WT_WAVES) {      // (uniform over the wavefront)
+        const long q = 4 * g + kk;
+        const bool live = q < a.kc;                                   // (the K tail)
+        const double J = live ? a.cost[q] : 0.0;
+        const bool ok = live && !mc_nan(J);                           // selected, not multiplied: the trajectory may hold NaN
+        double D = 0.0;
+        if (ok && comp) D = (isx ? a.xs[(q * (N + 1) + t) * a.ldx + i] : a.us[(q * N + t) * a.ldu + (i - 12)]) - c;
+#pragma unroll
+        for (int r = 0; r < WT_ROWS; ++r) {
+            if (r < nr) {                                             // (uniform over the workgroup)
+                const double y = ok ? a.y[(long)(r0 + r) * a.ldy + q] : 0.0;
+                const double yd = y * D;
+                acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd, D, acc[r], 0, 0, 0);
+                s1[r] += yd; s0[r] += y; sy2[r] += y * y;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < WT_ROWS; ++r) {
+        if (r < nr) {
+            __syncthreads();                                          // (the previous row's sums are read)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) sh[w][(kk + 4 * reg) * 16 + i] = acc[r][reg];   // C: row (lane >> 4) + 4 reg, column lane & 15
+            sh[w][256 + lane] = s1[r];
+            if (i == 0) { sh[w][320 + kk] = s0[r]; sh[w][324 + kk] = sy2[r]; }
+            __syncthreads();
+            double *p = a.part + (((size_t)(r0 + r) * (N + 1) + t) * WT_SLOTS + slot) * WT_PART;
+            const int e = threadIdx.x;
+            double v = 0.0;
+            for (int w2 = 0; w2 < WT_WAVES; ++w2) v += sh[w2][e];
+            p[e] += v;
+            if (e < 16) {
+                v = 0.0;
+                for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][256 + k2 * 16 + e];
+                p[WT_O_S1 + e] += v;
+            } else if (e == 16 || e == 17) {
+                v = 0.0;
+                for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][(e == 16 ? 320 : 324) + k2];
+                p[(e == 16) ? WT_O_S0 : WT_O_SY2] += v;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void wct_final(WtArgs a) {
+    __shared__ double S[WT_PART];
+    const int t = blockIdx.x, r = blockIdx.y, e = threadIdx.x, N = a.N, d = a.n + a.m;
+    const double *p = a.part + ((size_t)r * (N + 1) + t) * WT_SLOTS * WT_PART;
+    for (int q = e; q < WT_PART; q += MC_THREADS) {
+        double v = 0.0;
+        for (int s = 0; s < WT_SLOTS; ++s) v += p[s * WT_PART + q];
+        S[q] = v;
+    }
+    __syncthreads();
+    const double st = a.wc[WC_O_INFO + 2 * r + 1], nan = __builtin_nan("");
+    const bool dead = (st == WC_ST_EMPTY || st == WC_ST_NONFINITE);
+    const double s0 = S[WT_O_S0];
+    const size_t o = (size_t)r * (N + 1) + t;
+    if (e < d * d) {                                                  // column-major; the upper triangle of the tile serves both halves
+        const int ii = e % d, jj = e / d;
+        const int ti = (ii < a.n) ? ii : 12 + ii - a.n, tj = (jj < a.n) ? jj : 12 + jj - a.n;
+        const int lo = ti < tj ? ti : tj, hi = ti < tj ? tj : ti;
+        const double mi = S[WT_O_S1 + ti] / s0, mj = S[WT_O_S1 + tj] / s0;
+        a.cov[o * d * d + e] = dead ? nan : S[lo * 16 + hi] / s0 - mi * mj;
+    }
+    if (e < d) {
+        const int ti = (e < a.n) ? e : 12 + e - a.n;
+        a.mean[o * d + e] = dead ? nan : a.centre[t * 16 + ti] + S[WT_O_S1 + ti] / s0;
+    }
+    if (t == 0 && e == 0) { a.ess[2 * r] = s0; a.ess[2 * r + 1] = S[WT_O_SY2]; }
+}
+
 }  // namespace
+
+void launch_wct_centre(const double *x, const double *u, int n, int m, int N, double *centre, hipStream_t s) {
+    hipLaunchKernelGGL(wct_centre, dim3((unsigned)(((N + 1) * 16 + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, s, x, u, n, m, N, centre);
+}
+
+void launch_wct_chunk(const WtArgs &a, hipStream_t s) {
+    if (a.kc <= 0 || a.nrows <= 0) return;
+    const long nb = (a.kc + MC_THREADS - 1) / MC_THREADS;
+    hipLaunchKernelGGL(wct_weights, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(MC_THREADS), 0, s, a);
+    hipLaunchKernelGGL(wct_moments, dim3(WT_SLOTS, (unsigned)(a.N + 1), (unsigned)((a.nrows + WT_ROWS - 1) / WT_ROWS)), dim3(WT_WAVES * 64), 0, s, a);
+}
+
+void launch_wct_final(const WtArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(wct_final, dim3((unsigned)(a.N + 1), (unsigned)a.nrows), dim3(MC_THREADS), 0, s, a);
+}
 
 void launch_policy_mc(const McArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(mc_pass1, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);

@@ -190,6 +190,9 @@ class GenericContext(il.Context):
     def policy_worst_case(self, *a, **k):
         self._carrier_only("policy_worst_case")
 
+    def policy_worst_case_trajectory(self, *a, **k):
+        self._carrier_only("policy_worst_case_trajectory")
+
     def solve_batch(self, *a, **k):
         self._carrier_only("solve_batch")
 

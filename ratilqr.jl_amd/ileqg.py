@@ -197,6 +197,30 @@ class Context:
             w = w[:int(self.debug_get("mc_cost_K"))]
         return dict(bounds=rows(ob), thetas=rows(ot), weights=w)
 
+    def policy_worst_case_trajectory(self, kl_bounds=(), thetas=()):
+        """What the worst case looks like (rat_policy_worst_case_trajectory): the mean and covariance of the state and the control at every
+        step under the worst-case distribution p* ~ exp(theta* J) q of each KL radius -- and under the tilt of each given theta; theta = 0 is
+        the nominal distribution q -- formed on the device by replaying the last policy_evaluate / policy_evaluate_noise of this context
+        (device generator only).  Returns {"bounds": part, "thetas": part}; a part carries policy_worst_case's row keys and, with R rows,
+        mean_x (R, N+1, n), cov_x (R, N+1, n, n), mean_u (R, N, m), cov_u (R, N, m, m), cov_xu (R, N, n, m).  Covariances are the
+        population form (weights sum to one).  A saturated row holds the moments of the rollouts attaining the maximum; an empty or
+        non-finite sample gives NaN."""
+        d = nv.f64(np.atleast_1d(np.asarray(kl_bounds, dtype=np.float64))).ravel()
+        th = nv.f64(np.atleast_1d(np.asarray(thetas, dtype=np.float64))).ravel()
+        n, m, N, R = self.n, self.m, self.N, d.size + th.size
+        rows, mean, cov = np.zeros((R, nv.WC_NSTAT)), np.zeros((R, N + 1, n + m)), np.zeros((R, N + 1, n + m, n + m))
+        nv.check(nv.lib().rat_policy_worst_case_trajectory(self.h, nv.P(d) if d.size else None, C.c_int32(d.size), nv.P(th) if th.size else None,
+                                                           C.c_int32(th.size), nv.P(rows), nv.P(mean), nv.P(cov)))
+        cov = cov.transpose(0, 1, 3, 2)                               # (column-major blocks)
+
+        def part(sl):
+            r = {k: rows[sl, i].copy() for i, k in enumerate(nv.WC_SLOTS)}
+            r["flag"] = r["flag"].astype(np.int64)
+            r.update(mean_x=mean[sl, :, :n].copy(), cov_x=cov[sl, :, :n, :n].copy(), mean_u=mean[sl, :N, n:].copy(),
+                     cov_u=cov[sl, :N, n:, n:].copy(), cov_xu=cov[sl, :N, :n, n:].copy())
+            return r
+        return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)))
+
     def integrate_cost(self, x, u):
         out = C.c_double()
         nv.check(nv.lib().rat_integrate_cost(self.h, nv.P(nv.f64(x)), nv.P(nv.f64(u)), C.byref(out)))
