@@ -315,6 +315,43 @@ rat_rc rat_policy_worst_case(rat_handle h, const double *cost, int64_t K, const 
  * the problem, its parameters or the policy changed since the evaluation. */
 rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
                                         double *rows_out, double *mean_out, double *cov_out);
+/* The tail risk of a policy, from the K Monte-Carlo costs: per level alpha the alpha-quantile of the cost (value at risk: with probability
+ * alpha the cost stays below it) and the conditional value at risk, the expected cost of the worst (1 - alpha) share of the rollouts.  With
+ * n = N_OK and s_1 <= ... <= s_n the OK costs in ascending order: a = n alpha (one rounded product), k = clamp(ceil(a), 1, n), VAR = s_k (bit
+ * for bit an element of the sample; -0.0 counts as +0.0), CVAR = VAR + sum (J - VAR)^+ / (n - a) (Rockafellar-Uryasev: ties and the
+ * fractional atom at VAR need no special case).  The tail distribution puts 1 / (n - a) on every rollout above VAR and spreads what is left,
+ * r = (n - k - c_gt) + (k - a) rollouts' worth, evenly over the c_eq rollouts at VAR.  alpha == 0 gives VAR = the minimum and CVAR = the mean.
+ * VAR is found by a radix select on the device (8 digits of 8 bits over the costs' bit patterns, every level at once, integer histograms;
+ * digits the minimum and the maximum share are not swept), the sums in one more sweep in rat_policy_evaluate's fixed order.
+ *   cost, K    as rat_policy_worst_case's: NULL for the K costs the last evaluation -- or the last call of either function with host costs --
+ *              left on the device (K 0 or that K), otherwise K host doubles (1 <= K <= 2^27), uploaded into the same buffer, NaN entries
+ *              left out; no problem needs to be set for that form, and rat_policy_worst_case_trajectory has nothing to replay after it
+ *   alpha      [n_alpha], 1 <= n_alpha <= 16, every one in [0, 1) (NaN, negative or >= 1: RAT_ERR_ARG)
+ *   rows_out   [n_alpha][RAT_TR_NSTAT]: a row of the slots below per level
+ *   weights_out[K] or NULL: the tail distribution at alpha[0] -- 1 / (n - a) where J > VAR, r / (c_eq (n - a)) where J == VAR, 0 elsewhere
+ *              and for a DomainError rollout; they sum to one
+ * Flags: RAT_TR_SATURATED when n - a < 1, the tail is thinner than one rollout: VAR = CVAR = Jmax, CVAR_SE NaN, ESS n_max, KL
+ * log(N_OK / n_max), weights uniform on the maxima.  RAT_TR_EMPTY: N_OK == 0; RAT_TR_NONFINITE: a +-Inf among the costs; every other slot
+ * but ALPHA is NaN in both.  ESS and the saturated flag say how far to trust a row: CVAR at ESS of a few rollouts is those rollouts' mean.
+ * CVAR is the worst-case expectation over every p with dp/dq <= 1 / (1 - alpha), and the tail distribution has KL(p || q) = KL, so
+ * CVAR <= rat_policy_worst_case's BOUND at kl_bound = KL on the same costs.  Integer histograms and fixed-order sums, no floating-point
+ * atomics: the same arguments return the same bits, and a row's bits depend neither on the other levels of the call nor on where the costs
+ * came from. */
+#define RAT_TR_ALPHA     0   /* the level */
+#define RAT_TR_VAR       1   /* s_k */
+#define RAT_TR_CVAR      2
+#define RAT_TR_CVAR_SE   3   /* sd of (J - VAR)^+ over (1 - alpha) sqrt(N_OK) (VAR taken as known); NaN when N_OK < 2 */
+#define RAT_TR_TAIL_N    4   /* n - a: the tail's mass in rollouts */
+#define RAT_TR_ESS       5   /* (n - a)^2 / (c_gt + r^2 / c_eq): the effective sample size of the tail distribution */
+#define RAT_TR_KL        6   /* KL(tail distribution || uniform on the N_OK rollouts) */
+#define RAT_TR_FLAG      7   /* RAT_TR_OK ... as a double */
+#define RAT_TR_NSTAT     8
+#define RAT_TR_OK        0
+#define RAT_TR_SATURATED 1
+#define RAT_TR_EMPTY     2
+#define RAT_TR_NONFINITE 3
+rat_rc rat_policy_tail_risk(rat_handle h, const double *cost, int64_t K, const double *alpha, int32_t n_alpha,
+                            double *rows_out, double *weights_out);
 /* approximate_model(problem, u_array, x_array)                 ileqg.jl:258-322
  * -> q[N+1], qv[n*(N+1)], Q[n*n*(N+1)], r[m*N], R[m*m*N], P[m*n*N], A[n*n*N], B[n*m*N], W[n*n*N] */
 rat_rc rat_approximate_model(rat_handle h, const double *u, const double *x,
@@ -679,7 +716,7 @@ int32_t rat_get_path(rat_handle h, int64_t B);
  *                            trajectories, profiles/source_model.md)                                                        (16)
  *   src_pets_tpw    16 / 32 / 64   generative source models: trajectories per wavefront of the PETS rollout kernel (64: 3.7x 16's
  *                            rollouts/s at 10^6 trajectories, equal at 10 k; profiles/source_pets.md)                     (64)
- *   mc_cost_K       read-only      costs the last rat_policy_evaluate / _noise (or rat_policy_worst_case with host costs) left on the device (0: none)
+ *   mc_cost_K       read-only      costs the last rat_policy_evaluate / _noise (or rat_policy_worst_case / rat_policy_tail_risk with host costs) left on the device (0: none)
  *   src_mc_tpw      16 / 32 / 64   source models: rollouts per wavefront of rat_policy_evaluate's rollout kernel (profiles/policy_mc.md) (64)
  *   wdiag           0 / 1    diagonal time-invariant W: inv(W) folded into M^-1's operand (takes effect at the next rat_problem_set) (1) */
 rat_rc  rat_debug_set(rat_handle h, const char *key, int64_t value);

@@ -413,6 +413,29 @@ function policy_worst_case(s::ILEQGSolver; kl_bounds=Float64[], thetas=Float64[]
 end
 
 """
+policy_tail_risk(s; alphas, costs, want_weights): the tail risk of a sample of Monte-Carlo costs (rat_policy_tail_risk).  Per level
+α ∈ [0, 1) the α-quantile of the cost (value at risk) and the conditional value at risk, the mean of the worst (1 − α) share of the
+rollouts, by a radix select on the device.  costs === nothing: the costs the last evaluate_policy on this solver's handle left on the
+device; otherwise a vector of K costs (NaN = DomainError rollout, left out).  alphas: 1 to 16 levels.  Returns a named tuple of vectors
+alpha, var, cvar, cvar_se, tail_n (= n − n α), ess, kl (of the tail distribution from the sample: cvar ≤ policy_worst_case's bound at
+kl_bounds = [kl]), flag (0 OK, 1 saturated: the tail is thinner than one rollout, 2 empty, 3 non-finite), and weights: the tail
+distribution at alphas[1], `nothing` unless want_weights.
+"""
+function policy_tail_risk(s::ILEQGSolver; alphas=Float64[], costs::Union{Nothing,Vector{Float64}}=nothing, want_weights::Bool=false)
+    h = s.h
+    al = collect(Float64, alphas); na = length(al)
+    K = costs === nothing ? Int64(debug_get(h, "mc_cost_K")) : Int64(length(costs))
+    o = zeros(8, max(na, 1))
+    w = want_weights ? zeros(max(K, 1)) : nothing
+    check(ccall((:rat_policy_tail_risk, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, costs === nothing ? C_NULL : costs, costs === nothing ? Int64(0) : K, na > 0 ? al : C_NULL, na, o,
+                want_weights ? w : C_NULL))
+    (alpha=o[1, 1:na], var=o[2, 1:na], cvar=o[3, 1:na], cvar_se=o[4, 1:na], tail_n=o[5, 1:na], ess=o[6, 1:na], kl=o[7, 1:na],
+     flag=Int.(o[8, 1:na]), weights=want_weights ? w[1:K] : nothing)
+end
+
+"""
 policy_worst_case_trajectory(s; kl_bounds, thetas): what the worst case looks like (rat_policy_worst_case_trajectory).  The mean and
 covariance of the state and the control at every step under the worst-case distribution p* ∝ exp(θ* J) q of each KL radius, and under the
 tilt of each given θ (θ = 0 is the nominal distribution q), formed on the device by replaying the last evaluate_policy on this solver's
@@ -1276,7 +1299,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_tail_risk, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

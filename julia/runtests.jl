@@ -108,6 +108,25 @@ end
     @test all([all(isapprox.(xs[ii], zeros(2), atol=1e-4)) for ii in 1:N+1])   # :172-174
 end
 
+@testset "tail risk of a policy on the device (rat_policy_tail_risk)" begin
+    N = 10
+    prob = lq_test_problem(N; cq=1.0, cr=2.0, hq=1.0, w=0.01)
+    st = ILEQGSolver(prob)
+    u_array = [0.1 * ones(2) for _ in 1:N]
+    ev = evaluate_policy(st, prob, zeros(2), u_array; K=5000, seed=7, want_costs=true)
+    tr = policy_tail_risk(st; alphas=[0.0, 0.5, 0.9, 0.99], want_weights=true)
+    J = sort(ev.costs)
+    @test all(tr.flag .== 0) && tr.var == [J[1], J[2500], J[4500], J[4950]]    # s_k, k = ceil(n α) (1 at α = 0): elements of the sample
+    @test tr.cvar[1] ≈ ev.mean rtol = 1e-12
+    @test issorted(tr.cvar) && all(tr.cvar .>= tr.var) && tr.cvar[4] <= ev.max
+    @test tr.cvar[3] ≈ sum(J[4501:end]) / 500 rtol = 1e-12
+    @test sum(tr.weights) ≈ 1.0 && sum(tr.weights .* ev.costs) ≈ tr.cvar[1]
+    wc = policy_worst_case(st; kl_bounds=tr.kl)
+    @test all(tr.cvar .<= wc.bounds.bound .* (1 + 1e-11))                      # the tail distribution lies in its own KL ball
+    up = policy_tail_risk(st; alphas=[0.9], costs=ev.costs)                    # the same costs from the host: the same bits
+    @test up.var[1] == tr.var[3] && up.cvar[1] == tr.cvar[3]
+end
+
 @testset "Cross Entropy Bilevel Optimization on the device (test/cross_entropy_bilevel_optimization_test.jl:27-41)" begin
     N = 10
     pl = PowerLawRiskSensitiveProblem(2, N, 0.01 * I2)

@@ -199,6 +199,8 @@ struct rat_handle_s {
     // the worst case over the KL ball (rat_policy_worst_case, policy_mc.hip): brackets, partials and rows; the weights
     double *d_wc_red = nullptr;                              // [WC_SCRATCH]
     double *d_wc_w = nullptr; size_t cap_wc_w = 0;           // [K]
+    // the tail risk (rat_policy_tail_risk, policy_mc.hip): the select's states and histograms, partials and rows; its weights use d_wc_w
+    double *d_tr_red = nullptr;                              // [TR_SCRATCH]
     // ... under the user's noise sampler (rat_policy_evaluate_noise): rat_src_user_noisy_rollout (source_user_noise.h), a module of its own
     // compiled for the declared draw counts by the first call that needs it
     hipModule_t src_un_mod = nullptr;
@@ -401,7 +403,7 @@ extern "C" void rat_destroy(rat_handle h) {
     for (void *q : {(void *)h->d_mc_cost, (void *)h->d_mc_dom, (void *)h->d_mc_z, (void *)h->d_mc_in, (void *)h->d_mc_red}) if (q) (void)hipFree(q);
     if (h->src_noisy_mod) (void)hipModuleUnload(h->src_noisy_mod);
     for (double *q : {h->d_mc_zu, h->d_mc_xo, h->d_mc_uo}) if (q) (void)hipFree(q);
-    for (double *q : {h->d_wc_red, h->d_wc_w}) if (q) (void)hipFree(q);
+    for (double *q : {h->d_wc_red, h->d_wc_w, h->d_tr_red}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_wt_cost, (void *)h->d_wt_dom, (void *)h->d_wt_y, (void *)h->d_wt_part, (void *)h->d_wt_out}) if (q) (void)hipFree(q);
     if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
@@ -2284,6 +2286,57 @@ extern "C" rat_rc rat_policy_worst_case(rat_handle h, const double *cost, int64_
     h->mc_cost_K = K;                                                 // (uploaded costs serve a later cost == NULL call like an evaluation's)
     for (int i = 0; i < n_bound * WC_NSTAT; ++i) out_bound[i] = rows[i];
     for (int i = 0; i < n_theta * WC_NSTAT; ++i) out_theta[i] = rows[n_bound * WC_NSTAT + i];
+    return RAT_OK;
+}
+
+// The alpha-quantile (value at risk) and the conditional value at risk of the sample of K costs, one row per level: a radix select and one
+// sweep of sums on the device (policy_mc.hip, launch_policy_tr), one enqueue chain on the handle's stream, one host wait.  cost and K mean
+// what they mean for rat_policy_worst_case, and the handle is left as that function leaves it: the chain starts with its own pass 1 over
+// d_mc_cost, uploaded costs serve a later cost == NULL call of either function and are no evaluation's to replay.
+extern "C" rat_rc rat_policy_tail_risk(rat_handle h, const double *cost, int64_t K, const double *alpha, int32_t n_alpha,
+                                       double *rows_out, double *weights_out) {
+    // (what the arguments alone decide comes first: those refusals need no handle)
+    if (n_alpha < 1 || n_alpha > TR_MAX_ALPHA) return fail(RAT_ERR_ARG, "rat_policy_tail_risk: n_alpha must be in 1 .. 16");
+    if (!alpha || !rows_out) return fail(RAT_ERR_ARG, "rat_policy_tail_risk: null alpha / rows_out");
+    for (int i = 0; i < n_alpha; ++i)
+        if (!(alpha[i] >= 0.0 && alpha[i] < 1.0)) return fail(RAT_ERR_ARG, "rat_policy_tail_risk: every alpha must be in [0, 1) (NaN is not)");
+    if (cost && K < 1) return fail(RAT_ERR_ARG, "rat_policy_tail_risk: K must be positive when costs are given");
+    if (cost && K > ((int64_t)1 << 27))
+        return fail(RAT_ERR_ARG, "rat_policy_tail_risk: K must be at most 2^27 (the costs stay on the device, 8 bytes each)");
+    if (!h) return fail(RAT_ERR_ARG, "rat_policy_tail_risk: null handle");
+    if (!cost) {
+        if (h->mc_cost_K == 0)
+            return fail(RAT_ERR_ARG, "rat_policy_tail_risk: cost is NULL and no rat_policy_evaluate / rat_policy_evaluate_noise on this handle has left "
+                                     "its costs on the device (a call with host costs leaves those instead)");
+        if (K != 0 && K != h->mc_cost_K)
+            return fail(RAT_ERR_ARG, "rat_policy_tail_risk: K = " + std::to_string(K) + ", the last evaluation left " + std::to_string(h->mc_cost_K) +
+                                     " costs on the device (pass that K, or 0)");
+        K = h->mc_cost_K;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    rat_rc rc;
+    size_t cap_red = h->d_tr_red ? TR_SCRATCH : 0;
+    if ((rc = grow(&h->d_tr_red, &cap_red, (size_t)TR_SCRATCH))) return rc;
+    if (weights_out && (rc = grow(&h->d_wc_w, &h->cap_wc_w, (size_t)K))) return rc;
+    if (cost) {
+        h->mc_cost_K = 0;                                             // (the buffer's costs are replaced; valid again after the wait)
+        h->mc_rec.kind = 0;                                           // (... and they are no evaluation's: nothing to replay)
+        if ((rc = grow(&h->d_mc_cost, &h->cap_mc_cost, (size_t)K))) return rc;
+        HIPCHK(hipMemcpyAsync(h->d_mc_cost, cost, (size_t)K * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    TrArgs a;
+    memset(&a, 0, sizeof(a));
+    a.cost = h->d_mc_cost; a.K = (long)K; a.n_alpha = n_alpha; a.scratch = h->d_tr_red;
+    a.weights = weights_out ? h->d_wc_w : nullptr;
+    for (int i = 0; i < n_alpha; ++i) a.alpha[i] = alpha[i];
+    launch_policy_tr(a, h->stream);
+    HIPCHK(hipGetLastError());
+    double rows[TR_MAX_ALPHA * TR_NSTAT];
+    HIPCHK(hipMemcpyAsync(rows, h->d_tr_red + TR_O_ROWS, (size_t)n_alpha * TR_NSTAT * 8, hipMemcpyDeviceToHost, h->stream));
+    if (weights_out) HIPCHK(hipMemcpyAsync(weights_out, h->d_wc_w, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->mc_cost_K = K;                                                 // (uploaded costs serve a later cost == NULL call like an evaluation's)
+    for (int i = 0; i < n_alpha * TR_NSTAT; ++i) rows_out[i] = rows[i];
     return RAT_OK;
 }
 

@@ -66,6 +66,40 @@ struct WcArgs {
 // the rows are a.scratch + WC_O_ROWS
 void launch_policy_wc(const WcArgs &a, hipStream_t s);
 
+// ---- rat_policy_tail_risk: the alpha-quantile (value at risk) and the conditional value at risk of the K costs (policy_mc.hip) ------------
+// A radix select for every level at once, 8 bits a pass: the key of a cost is its bit pattern made monotone (0 canonicalised; a negative
+// cost ~bits, any other bits | 1 << 63), a level's state is the digits fixed so far and the rank that is left within them.
+#define TR_MAX_ALPHA 16
+#define TR_NSTAT 8            /* RAT_TR_NSTAT of the header */
+#define TR_BITS 8             /* digit width: [16][256] u32 of LDS per workgroup, 256 bins a level for the head of the next launch to walk */
+#define TR_BINS (1 << TR_BITS)
+#define TR_PASSES (64 / TR_BITS)
+#define TR_NSUM 4             /* sums per level of tr_sums: P1, P2, c_gt, c_eq */
+#define TR_SROWS 8            /* levels tr_sums forms per sweep over the costs */
+// scratch, in doubles: part1 [5][B] | sums' partials [16][4][B] | rows [16][8] | aux [8] | state [9][16] x (prefix u64, rank u32 | rep u32) |
+// histograms [8][16][256] u32 (zeroed at the head of the chain; one set per pass, so no launch clears what another still reads)
+#define TR_O_P1 0
+#define TR_O_PS (MC_P1 * MC_BLOCKS)
+#define TR_O_ROWS (TR_O_PS + TR_MAX_ALPHA * TR_NSUM * MC_BLOCKS)
+#define TR_O_AUX (TR_O_ROWS + TR_MAX_ALPHA * TR_NSTAT)
+#define TR_O_STATE (TR_O_AUX + 8)
+#define TR_O_HIST (TR_O_STATE + (TR_PASSES + 1) * TR_MAX_ALPHA * 2)
+#define TR_HIST_DOUBLES (TR_PASSES * TR_MAX_ALPHA * TR_BINS / 2)
+#define TR_SCRATCH (TR_O_HIST + TR_HIST_DOUBLES)
+
+struct TrArgs {
+    double *cost;             // [K] costs, NaN for a DomainError rollout
+    long K;
+    int n_alpha;
+    int pass;                 // digit pass of this launch (tr_select)
+    double alpha[TR_MAX_ALPHA];
+    double *scratch;          // [TR_SCRATCH]
+    double *weights;          // [K] or null
+};
+// enqueues pass 1 (mc_pass1), the clearing of the histograms, TR_PASSES select passes, the sums, the rows and (a.weights) the weights on s;
+// the rows are a.scratch + TR_O_ROWS
+void launch_policy_tr(const TrArgs &a, hipStream_t s);
+
 // ---- rat_policy_worst_case_trajectory: the mean and covariance of (x_t, u_t) under q and under p* ~ exp(theta* J) q (policy_mc.hip) --------
 // Per step t and row r, about a centre c_t known before any rollout runs: S0 = sum y, S1 = sum y D, S2 = sum y D D' and sum y^2 over the
 // rollouts, D = (x_t, u_t) - c_t in the 12 + 4 tile, y the row's weight of the rollout.  The trajectories are replayed a chunk at a time

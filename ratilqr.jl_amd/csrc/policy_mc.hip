@@ -475,6 +475,273 @@ __global__ __launch_bounds__(MC_THREADS) void wc_weights(WcArgs a) {
     }
 }
 
+// ---- rat_policy_tail_risk: the alpha-quantile v (value at risk) and CVaR = v + sum (J - v)^+ / (n - a) of the K costs ------------------------
+// v is the k-th smallest OK cost, k = clamp(ceil(a), 1, n), a = n alpha: a radix select over the costs' keys (tr_key: the bit pattern made
+// monotone), TR_BITS bits a pass, every level of the call at once:
+//   mc_pass1    as for rat_policy_evaluate: n, min, max                                   -> part1
+//   tr_select   x TR_PASSES.  The head of pass p forms every level's state -- the p digits fixed so far and the rank left among the keys
+//               that carry them -- from the state and the histogram of pass p - 1: it walks the level's 256 bins to the one where the
+//               running count reaches the rank.  The sweep then counts, per distinct prefix, the digit p of the keys that carry it:
+//               levels that share a prefix share a histogram (`rep`, the lowest such level), distinct prefixes of one length exclude each
+//               other, so a cost makes at most one LDS add a pass.  Histograms are u32 in LDS, flushed with integer atomics into the
+//               pass's own zeroed set: integer sums are exact, the order cannot change a bit.  Digits on which the keys of min and max
+//               agree are shared by every key: those passes sweep nothing (costs of one policy share sign and exponent; all costs equal
+//               need no sweep at all).
+//   tr_sums     the head fixes the last digit: the prefix is v's key.  Per level P1 = sum (J - v)^+, P2 = sum ((J - v)^+)^2, c_gt = #{J > v},
+//               c_eq = #{J == v} in mc_pass1's order, TR_SROWS levels a sweep                                  -> partials
+//   tr_rows     second level of those sums; writes the rows
+//   tr_weights  the tail distribution of the first level, elementwise
+// A level's state, histogram walk and sums never read another level's: a row's bits do not depend on its company.
+typedef unsigned long long tr_u64;
+
+// ascending key order is ascending value order; -0.0 counts as +0.0
+__device__ __forceinline__ tr_u64 tr_key(double J) {
+    const tr_u64 b = (J == 0.0) ? 0ull : (tr_u64)__double_as_longlong(J);
+    return (b >> 63) ? ~b : (b | (1ull << 63));
+}
+__device__ __forceinline__ double tr_value(tr_u64 key) { return __longlong_as_double((long long)((key >> 63) ? (key ^ (1ull << 63)) : ~key)); }
+
+struct TrHead { double n, mx; tr_u64 kmin; int d0; bool live; double flag; };
+
+// what every launch knows about the sample; d0: the first digit on which the keys of min and max differ (TR_PASSES: all costs equal)
+__device__ __forceinline__ TrHead tr_head(const double *scr, double *sh) {
+    const McHead hd = reduce_part1(scr + TR_O_P1, sh);
+    TrHead r;
+    r.n = hd.n_ok; r.mx = hd.mx;
+    r.flag = !(hd.n_ok > 0.0) ? 2.0 : !(hd.mn > -__builtin_inf() && hd.mx < __builtin_inf()) ? 3.0 : 0.0;
+    r.live = r.flag == 0.0;
+    r.kmin = tr_key(hd.mn);
+    const tr_u64 x = r.kmin ^ tr_key(hd.mx);
+    r.d0 = (x == 0) ? TR_PASSES : (__clzll((long long)x) / TR_BITS);
+    return r;
+}
+
+// a = n alpha as one rounded product: kept out of the subtractions that follow it (n - a, k - a), which the compiler would otherwise fuse
+// with it -- __dmul_rn is a plain product to this compiler and is fused like one
+__device__ __forceinline__ double tr_prod(double n, double alpha) {
+#pragma clang fp contract(off)
+    return n * alpha;
+}
+
+// k = clamp(ceil(a), 1, n)
+__device__ __forceinline__ double tr_rank(double n, double av) {
+    double k = ceil(av);
+    k = k < 1.0 ? 1.0 : k;
+    return k > n ? n : k;
+}
+
+__device__ __forceinline__ tr_u64 *tr_gpfx(double *scr) { return (tr_u64 *)(scr + TR_O_STATE); }
+__device__ __forceinline__ tr_u64 *tr_grr(double *scr) { return tr_gpfx(scr) + (TR_PASSES + 1) * TR_MAX_ALPHA; }
+
+// the state of every level before digit pass p (p = TR_PASSES: after the last), in LDS; workgroup 0 also stores it for the next launch.
+// Lane (l, c) = (tid >> 4, tid & 15) sums bins 16 c .. 16 c + 15 of level l's histogram of pass p - 1; the lane whose chunk holds the rank
+// walks its 16 bins.  s_cs is [MC_THREADS].  Every workgroup computes the same values.
+__device__ __forceinline__ void tr_state(const TrArgs &a, const TrHead &h, int p, tr_u64 *s_pfx, unsigned *s_rank, int *s_rep, unsigned *s_cs) {
+    const int tid = threadIdx.x, l = tid >> 4, c = tid & 15;
+    tr_u64 *g_pfx = tr_gpfx(a.scratch), *g_rr = tr_grr(a.scratch);
+    __syncthreads();
+    if (p == 0) {
+        if (tid < a.n_alpha) { s_pfx[tid] = 0; s_rank[tid] = (unsigned)tr_rank(h.n, tr_prod(h.n, a.alpha[tid])); }
+    } else {
+        const bool on = l < a.n_alpha, walk = (p - 1) >= h.d0;           // (walk is uniform over the grid)
+        tr_u64 pfx = 0;
+        unsigned rank = 0, cs = 0;
+        const unsigned *hist = nullptr;
+        if (on) {
+            pfx = g_pfx[(p - 1) * TR_MAX_ALPHA + l];
+            const tr_u64 rr = g_rr[(p - 1) * TR_MAX_ALPHA + l];
+            rank = (unsigned)(rr & 0xffffffffull);
+            if (walk) {
+                hist = (const unsigned *)(a.scratch + TR_O_HIST) + ((size_t)(p - 1) * TR_MAX_ALPHA + (size_t)(rr >> 32)) * TR_BINS + 16 * c;
+                for (int j = 0; j < 16; ++j) cs += hist[j];
+            }
+        }
+        s_cs[tid] = cs;
+        if (on && c == 0) {                                           // a pass that swept nothing: the digit every key shares
+            s_pfx[l] = (pfx << TR_BITS) | (walk ? 0ull : ((h.kmin >> (64 - TR_BITS * p)) & (tr_u64)(TR_BINS - 1)));
+            s_rank[l] = rank;
+        }
+        __syncthreads();
+        if (on && walk) {
+            unsigned run = 0;
+            for (int j = 0; j < c; ++j) run += s_cs[l * 16 + j];
+            if (run < rank && rank <= run + cs) {                     // (one lane of the level: the counts below the prefix reach the rank)
+                int dg = 16 * c + 15;
+                for (int j = 0; j < 16; ++j) {
+                    const unsigned cnt = hist[j];
+                    if (run + cnt >= rank) { dg = 16 * c + j; break; }
+                    run += cnt;
+                }
+                s_pfx[l] = (pfx << TR_BITS) | (tr_u64)dg;
+                s_rank[l] = rank - run;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < a.n_alpha) {
+        int rep = tid;
+        for (int j = tid - 1; j >= 0; --j) if (s_pfx[j] == s_pfx[tid]) rep = j;
+        s_rep[tid] = rep;
+        if (blockIdx.x == 0) {
+            g_pfx[p * TR_MAX_ALPHA + tid] = s_pfx[tid];
+            g_rr[p * TR_MAX_ALPHA + tid] = (tr_u64)s_rank[tid] | ((tr_u64)rep << 32);
+        }
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(MC_THREADS) void tr_select(TrArgs a) {
+    __shared__ double sh[MC_THREADS];
+    __shared__ unsigned s_hist[TR_MAX_ALPHA * TR_BINS], s_cs[MC_THREADS], s_rank[TR_MAX_ALPHA];
+    __shared__ tr_u64 s_pfx[TR_MAX_ALPHA];
+    __shared__ int s_rep[TR_MAX_ALPHA];
+    const TrHead h = tr_head(a.scratch, sh);
+    if (!h.live) return;                                              // (uniform over the grid, like every return below)
+    tr_state(a, h, a.pass, s_pfx, s_rank, s_rep, s_cs);
+    if (a.pass < h.d0) return;                                        // every key carries the same digit here
+    const int tid = threadIdx.x;
+    for (int i = tid; i < TR_MAX_ALPHA * TR_BINS; i += MC_THREADS) s_hist[i] = 0u;
+    tr_u64 pf[TR_MAX_ALPHA];
+    bool act[TR_MAX_ALPHA];                                          // the level counts for its prefix (the same in every lane: scalar)
+#pragma unroll
+    for (int l = 0; l < TR_MAX_ALPHA; ++l) {
+        act[l] = __builtin_amdgcn_readfirstlane((int)(l < a.n_alpha && s_rep[l] == l)) != 0;
+        const tr_u64 v = act[l] ? s_pfx[l] : 0ull;
+        pf[l] = ((tr_u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32)) << 32) |
+                (tr_u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v & 0xffffffffull));
+    }
+    __syncthreads();
+    const int sd = 64 - TR_BITS * (a.pass + 1);
+    const long T = (long)MC_BLOCKS * MC_THREADS;
+    for (long k0 = (long)blockIdx.x * MC_THREADS + tid; k0 < a.K; k0 += 4 * T) {      // four loads in flight; a count has no order
+        double J[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { const long k = k0 + u * T; J[u] = (k < a.K) ? a.cost[k] : __builtin_nan(""); }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (mc_nan(J[u])) continue;
+            const tr_u64 key = tr_key(J[u]);
+            const tr_u64 hi = (a.pass == 0) ? 0ull : (key >> (sd + TR_BITS));
+            int slot = -1;
+#pragma unroll
+            for (int l = 0; l < TR_MAX_ALPHA; ++l) if (act[l] && hi == pf[l]) slot = l;
+            if (slot >= 0) atomicAdd(&s_hist[slot * TR_BINS + (int)((key >> sd) & (tr_u64)(TR_BINS - 1))], 1u);
+        }
+    }
+    __syncthreads();
+    unsigned *g_hist = (unsigned *)(a.scratch + TR_O_HIST) + (size_t)a.pass * TR_MAX_ALPHA * TR_BINS;
+    for (int i = tid; i < a.n_alpha * TR_BINS; i += MC_THREADS) {
+        const unsigned cnt = s_hist[i];
+        if (cnt) atomicAdd(&g_hist[i], cnt);
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void tr_sums(TrArgs a) {
+    __shared__ double sh[TR_NSUM * MC_THREADS];
+    __shared__ unsigned s_cs[MC_THREADS], s_rank[TR_MAX_ALPHA];
+    __shared__ tr_u64 s_pfx[TR_MAX_ALPHA];
+    __shared__ int s_rep[TR_MAX_ALPHA];
+    const TrHead h = tr_head(a.scratch, sh);
+    if (!h.live) return;
+    tr_state(a, h, TR_PASSES, s_pfx, s_rank, s_rep, s_cs);
+    const long T = (long)MC_BLOCKS * MC_THREADS;
+    for (int r0 = 0; r0 < a.n_alpha; r0 += TR_SROWS) {
+        const int ns = (a.n_alpha - r0 < TR_SROWS) ? a.n_alpha - r0 : TR_SROWS;
+        double v[TR_SROWS], acc[TR_SROWS][TR_NSUM];
+#pragma unroll
+        for (int s = 0; s < TR_SROWS; ++s) {
+            v[s] = (s < ns) ? tr_value(s_pfx[r0 + s]) : 0.0;
+            acc[s][0] = acc[s][1] = acc[s][2] = acc[s][3] = 0.0;
+        }
+        for (long k = (long)blockIdx.x * MC_THREADS + threadIdx.x; k < a.K; k += T) {
+            const double J = a.cost[k];
+            if (mc_nan(J)) continue;
+#pragma unroll
+            for (int s = 0; s < TR_SROWS; ++s) {
+                if (s < ns) {                                         // (uniform)
+                    const bool gt = J > v[s];
+                    const double d = gt ? J - v[s] : 0.0;             // about v: nothing cancels
+                    acc[s][0] += d;
+                    acc[s][1] += d * d;
+                    acc[s][2] += gt ? 1.0 : 0.0;
+                    acc[s][3] += (J == v[s]) ? 1.0 : 0.0;
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < TR_SROWS; ++s) {
+            if (s < ns) {
+                double q[TR_NSUM] = {acc[s][0], acc[s][1], acc[s][2], acc[s][3]};
+                block_tree_n<TR_NSUM>(q, sh);
+                if (threadIdx.x == 0) {
+#pragma unroll
+                    for (int i = 0; i < TR_NSUM; ++i) a.scratch[TR_O_PS + ((r0 + s) * TR_NSUM + i) * MC_BLOCKS + blockIdx.x] = q[i];
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void tr_rows(TrArgs a) {
+    __shared__ double sh[TR_NSUM * MC_THREADS];
+    const TrHead h = tr_head(a.scratch, sh);
+    const double nan = __builtin_nan(""), n = h.n;
+    for (int r = 0; r < a.n_alpha; ++r) {
+        double q[TR_NSUM] = {0.0, 0.0, 0.0, 0.0};
+        if (h.live) {
+#pragma unroll
+            for (int i = 0; i < TR_NSUM; ++i) q[i] = a.scratch[TR_O_PS + (r * TR_NSUM + i) * MC_BLOCKS + threadIdx.x];
+        }
+        block_tree_n<TR_NSUM>(q, sh);
+        if (threadIdx.x != 0) continue;
+        double o[TR_NSTAT], w_gt = nan, w_eq = nan, val = nan;
+        o[0] = a.alpha[r];
+        if (!h.live) {
+            for (int i = 1; i < 7; ++i) o[i] = nan;
+            o[7] = h.flag;
+        } else {
+            const double P1 = q[0], P2 = q[1], cgt = q[2], ceq = q[3];
+            const double av = tr_prod(n, a.alpha[r]), tail = n - av, k = tr_rank(n, av);
+            val = tr_value(tr_gpfx(a.scratch)[TR_PASSES * TR_MAX_ALPHA + r]);
+            if (tail < 1.0) {                                         // thinner than one rollout: k = n, v = Jmax, c_eq = n_max
+                o[1] = val; o[2] = val; o[3] = nan; o[4] = tail; o[5] = ceq; o[6] = log(n / ceq); o[7] = 1.0;
+                w_gt = 0.0; w_eq = 1.0 / ceq;
+            } else {
+                const double frac = k - av, ra = (n - k - cgt) + frac, wv = ra / ceq;   // ra: the mass, in rollouts, left on the atom at v
+                double s2 = P2 - P1 * P1 / n;
+                if (s2 < 0.0) s2 = 0.0;
+                o[1] = val;
+                o[2] = val + P1 / tail;                               // Rockafellar-Uryasev: ties and the fractional atom need no special case
+                o[3] = (n >= 2.0) ? sqrt(n * s2 / (n - 1.0)) / tail : nan;
+                o[4] = tail;
+                o[5] = tail * tail / (cgt + ceq * wv * wv);
+                o[6] = (cgt * log(n / tail) + (ra > 0.0 ? ra * log(n * wv / tail) : 0.0)) / tail;
+                o[7] = 0.0;
+                w_gt = 1.0 / tail; w_eq = wv / tail;
+            }
+        }
+        for (int i = 0; i < TR_NSTAT; ++i) a.scratch[TR_O_ROWS + r * TR_NSTAT + i] = o[i];
+        if (r == 0) {
+            double *x = a.scratch + TR_O_AUX;
+            x[0] = val; x[1] = w_gt; x[2] = w_eq; x[3] = h.flag; x[4] = 0.0; x[5] = 0.0; x[6] = 0.0; x[7] = 0.0;
+        }
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void tr_weights(TrArgs a) {
+    const double *x = a.scratch + TR_O_AUX;
+    const double v = x[0], w_gt = x[1], w_eq = x[2], flag = x[3];
+    const long T = (long)gridDim.x * MC_THREADS;
+    for (long k = (long)blockIdx.x * MC_THREADS + threadIdx.x; k < a.K; k += T) {
+        const double J = a.cost[k];
+        double w;
+        if (mc_nan(J)) w = 0.0;
+        else if (flag != 0.0) w = __builtin_nan("");
+        else w = (J > v) ? w_gt : (J == v) ? w_eq : 0.0;
+        a.weights[k] = w;
+    }
+}
+
 // ---- rat_policy_worst_case_trajectory: weighted moments of the replayed trajectories ------------------------------------------------------
 // One MFMA per group of four rollouts, step and row: lane (i = lane & 15, kk = lane >> 4) holds D_i of rollout 4 g + kk, so A = y D is
 // [16 components][4 rollouts], B = D is [4 rollouts][16 components] and C += A B is the group's sum y D D'.  S1, S0 and sum y^2 ride along
@@ -627,6 +894,22 @@ void launch_policy_mc(const McArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(mc_pass1, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
     hipLaunchKernelGGL(mc_pass2, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
     hipLaunchKernelGGL(mc_final, dim3(1), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_policy_tr(const TrArgs &a0, hipStream_t s) {
+    TrArgs a = a0;
+    McArgs m;
+    memset(&m, 0, sizeof(m));
+    m.cost = a.cost; m.K = a.K; m.scratch = a.scratch + TR_O_P1;
+    hipLaunchKernelGGL(mc_pass1, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, m);
+    (void)hipMemsetAsync(a.scratch + TR_O_HIST, 0, (size_t)TR_HIST_DOUBLES * sizeof(double), s);
+    for (a.pass = 0; a.pass < TR_PASSES; ++a.pass) hipLaunchKernelGGL(tr_select, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
+    hipLaunchKernelGGL(tr_sums, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
+    hipLaunchKernelGGL(tr_rows, dim3(1), dim3(MC_THREADS), 0, s, a);
+    if (a.weights) {
+        const long nb = (a.K + MC_THREADS - 1) / MC_THREADS;
+        hipLaunchKernelGGL(tr_weights, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(MC_THREADS), 0, s, a);
+    }
 }
 
 void launch_policy_wc(const WcArgs &a0, hipStream_t s) {

@@ -197,6 +197,34 @@ class Context:
             w = w[:int(self.debug_get("mc_cost_K"))]
         return dict(bounds=rows(ob), thetas=rows(ot), weights=w)
 
+    def policy_tail_risk(self, alphas, costs=None, want_weights=False):
+        """The tail risk of a sample of Monte-Carlo costs (rat_policy_tail_risk): per level alpha in [0, 1) the alpha-quantile of the cost
+        (value at risk) and the conditional value at risk, the mean of the worst (1 - alpha) share of the rollouts, by a radix select on
+        the device.  costs None: the costs the last policy_evaluate / policy_evaluate_noise on this context left on the device (or the
+        ones an earlier call of this method or of policy_worst_case uploaded); otherwise K host values (NaN = DomainError rollout, left
+        out).  alphas: 1 to 16 levels.  Returns a dict of arrays, one entry per level: alpha, var, cvar, cvar_se, tail_n (= n - n alpha),
+        ess, kl (of the tail distribution from the sample: cvar <= policy_worst_case(kl_bounds=[kl]) bound), flag (int: 0 OK, 1 saturated:
+        the tail is thinner than one rollout, 2 empty, 3 non-finite); and weights: the tail distribution at alphas[0] ((K,), summing to
+        one, 0 at a DomainError rollout; None unless want_weights)."""
+        al = nv.f64(np.atleast_1d(np.asarray(alphas, dtype=np.float64))).ravel()
+        K = 0
+        if costs is not None:
+            costs = nv.f64(costs).ravel()
+            K = costs.size
+        rows = np.zeros((al.size, nv.TR_NSTAT))
+        w = None
+        if want_weights:
+            kw = K if costs is not None else int(self.debug_get("mc_cost_K"))
+            w = np.zeros(max(kw, 1))
+        nv.check(nv.lib().rat_policy_tail_risk(self.h, nv.P(costs), C.c_int64(K), nv.P(al) if al.size else None, C.c_int32(al.size),
+                                               nv.P(rows), nv.P(w)))
+        r = {k: rows[:, i].copy() for i, k in enumerate(nv.TR_SLOTS)}
+        r["flag"] = r["flag"].astype(np.int64)
+        if w is not None:
+            w = w[:K if costs is not None else int(self.debug_get("mc_cost_K"))]
+        r["weights"] = w
+        return r
+
     def policy_worst_case_trajectory(self, kl_bounds=(), thetas=()):
         """What the worst case looks like (rat_policy_worst_case_trajectory): the mean and covariance of the state and the control at every
         step under the worst-case distribution p* ~ exp(theta* J) q of each KL radius -- and under the tilt of each given theta; theta = 0 is
