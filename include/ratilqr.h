@@ -352,6 +352,52 @@ rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *kl_bound, in
 #define RAT_TR_NONFINITE 3
 rat_rc rat_policy_tail_risk(rat_handle h, const double *cost, int64_t K, const double *alpha, int32_t n_alpha,
                             double *rows_out, double *weights_out);
+/* Safety events of a policy: how often it hits an obstacle, leaves the lane or saturates an actuator -- under the nominal distribution q (a
+ * theta = 0 row) and under the worst-case distribution p* ~ exp(theta* J) q of each kl_bound (and the tilt of each given theta), formed on
+ * the device.  An event is a quadratic function of z_t = (x_t, u_t) in R^d, d = n + m, u_N = 0, watched over a window of steps:
+ *   g_i(t, z) = z' Q_i z + a_i' z + b_i,  t_lo_i <= t <= t_hi_i;   M_ik = max over the window of g_i(t, z_t) on rollout k (the margin; a NaN g
+ *   is passed over); A_ik = [M_ik > 0] (violated: g == 0 and a NaN g are not); tau_ik = the first step of the window with g_i > 0.
+ * Half-spaces and boxes (lane edges, actuator limits) are linear events; a disc or ellipsoid is r^2 - |p - c|^2 (violated inside).  One more
+ * event, "any", is formed by the call at index n_event: the union of the given ones (its margin is the largest of theirs, its first step
+ * the earliest of theirs).  Like rat_policy_worst_case_trajectory the call takes no policy and no noise: it REPLAYS the last
+ * rat_policy_evaluate / rat_policy_evaluate_noise of the handle and checks the replayed costs against the stored ones bit for bit; the
+ * same evaluations are served and the same ones refused, with the same codes.  The quadratic part runs on the f64 matrix pipe (sixteen
+ * rollouts as the columns of Q Z, four 16 x 16 x 4 MFMAs per event and step); a call with Q == NULL does not pay for it.  Fixed summation
+ * order, no floating-point atomics: the same call returns the same bits, and an entry's bits depend neither on the other rows nor on the
+ * other events of the call ("any" depends on its events).
+ *   n_event   1 .. 16
+ *   Q         [n_event][d * d] column-major, used as given (not symmetrised), or NULL: every event is linear
+ *   a         [n_event][d];  b [n_event];  t_lo, t_hi [n_event] with 0 <= t_lo <= t_hi <= N
+ *   kl_bound, theta   as rat_policy_worst_case's (the same refusals); the rows are the bounds, then the thetas
+ *   rows_out  [(n_bound + n_theta)][RAT_WC_NSTAT]: rat_policy_worst_case's rows of the same arguments, bit for bit
+ *   event_out [(n_bound + n_theta)][n_event + 1][RAT_EV_NSTAT]: the slots below, y the row's weight of a rollout (0 for a DomainError
+ *             rollout, uniform on the maxima for a RAT_WC_SATURATED row).  RAT_WC_EMPTY and RAT_WC_NONFINITE rows are NaN except FLAG.
+ *   step_out  [(n_bound + n_theta)][n_event + 1][N+1] or NULL: sum y [g_i(t) > 0] / sum y per step, 0 outside the window: where in the
+ *             horizon the risk sits
+ *   margin_out[n_event][K] or NULL: M_ik, NaN for a DomainError rollout.  A row of it is a sample like the costs: hand it to
+ *             rat_policy_tail_risk(cost = ...) for the quantiles and CVaR of a margin, or to rat_policy_worst_case(cost = ...) for its KL
+ *             worst case (either call replaces the costs on the device: evaluate again before the next replay).
+ * RAT_ERR_ARG besides: n_event outside 1 .. 16, a NULL a / b / t_lo / t_hi, a window outside 0 <= t_lo <= t_hi <= N, a non-finite entry of
+ * Q, a or b.  RAT_ERR_UNSUPPORTED besides: partial sums above 64 MiB (the message says how many rows fit). */
+#define RAT_EV_PROB        0   /* sum y A / sum y */
+#define RAT_EV_PROB_SE     1   /* sqrt(sum y^2 (A - PROB)^2) / sum y: the self-normalised importance-sampling error; sqrt(p (1 - p) / N_OK) at theta == 0 */
+#define RAT_EV_MARGIN_MEAN 2   /* sum y M / sum y */
+#define RAT_EV_MARGIN_MAX  3   /* max of M over the OK rollouts: the same on every row */
+#define RAT_EV_FIRST_MEAN  4   /* sum y A tau / sum y A; NaN when no weighted rollout violates */
+#define RAT_EV_N_VIOL      5   /* the unweighted count of violating OK rollouts */
+#define RAT_EV_PROB_ROBUST 6   /* rat_kl_event_bound(N_VIOL / N_OK, d): d the kl_bound on a bound row, the row's own RAT_WC_KL on a theta row.  The
+                                * adversary aimed at the event itself, not at the cost: PROB <= PROB_ROBUST on every RAT_WC_OK row */
+#define RAT_EV_FLAG        7   /* the row's RAT_WC_FLAG */
+#define RAT_EV_NSTAT       8
+rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double *Q, const double *a, const double *b,
+                         const int32_t *t_lo, const int32_t *t_hi,
+                         const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                         double *rows_out, double *event_out, double *step_out, double *margin_out);
+/* The largest probability p' an event of probability p can have under any distribution within KL radius d of the sampling one:
+ * max { p' : p' log(p' / p) + (1 - p') log((1 - p') / (1 - p)) <= d }, by bisection on [p, 1] until the bracket stops shrinking: two neighbouring doubles, of which the one whose KL is nearer d is returned.  Host
+ * only: needs no handle and no GPU.  d == 0 gives p; p == 0 gives 0; p == 1 gives 1; d == +Inf with p > 0 gives 1.  NaN, p outside
+ * [0, 1] or d < 0: RAT_ERR_ARG. */
+rat_rc rat_kl_event_bound(double p, double d, double *out);
 /* approximate_model(problem, u_array, x_array)                 ileqg.jl:258-322
  * -> q[N+1], qv[n*(N+1)], Q[n*n*(N+1)], r[m*N], R[m*m*N], P[m*n*N], A[n*n*N], B[n*m*N], W[n*n*N] */
 rat_rc rat_approximate_model(rat_handle h, const double *u, const double *x,

@@ -457,6 +457,39 @@ function policy_worst_case_trajectory(s::ILEQGSolver; kl_bounds=Float64[], theta
     (bounds=part(1:nb), thetas=part(nb+1:R))
 end
 
+"""
+policy_events(s, Q, a, b, t_lo, t_hi; kl_bounds, thetas, want_steps, want_margins): how often the policy violates safety events
+(rat_policy_events).  Event i is z' Q[:, :, i] z + a[:, i]' z + b[i] > 0 at a step t_lo[i] ≤ t ≤ t_hi[i] (0-based steps, z = (x_t, u_t));
+Q === nothing: every event is linear.  Per row (the worst-case distribution of each KL radius, the tilt of each θ; θ = 0 is the nominal
+distribution) and event -- the last one is "any", their union -- the violation probability and its companions, formed on the device by
+replaying the last evaluate_policy on this solver's handle.  Returns (rows, events, steps, margins): rows (8, R) as policy_worst_case's,
+events (8, E + 1, R) by the RAT_EV_* slots, steps (N + 1, E + 1, R) and margins (K, E) or `nothing`.
+"""
+function policy_events(s::ILEQGSolver, Q::Union{Nothing,Array{Float64,3}}, a::Matrix{Float64}, b::Vector{Float64}, t_lo::Vector{Int32},
+                       t_hi::Vector{Int32}; kl_bounds=Float64[], thetas=Float64[], want_steps::Bool=false, want_margins::Bool=false)
+    h = s.h
+    n, m, N = dims(h.problem)
+    d = collect(Float64, kl_bounds); th = collect(Float64, thetas)
+    nb = length(d); nt = length(th); R = nb + nt; E = length(b)
+    K = Int64(debug_get(h, "mc_cost_K"))
+    rows = zeros(8, R); ev = zeros(8, E + 1, R)
+    steps = want_steps ? zeros(N + 1, E + 1, R) : nothing
+    margins = want_margins ? zeros(max(K, 1), max(E, 1)) : nothing
+    check(ccall((:rat_policy_events, LIB), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int32, Ptr{Float64}, Int32,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, E, Q === nothing ? C_NULL : Q, a, b, t_lo, t_hi, nb > 0 ? d : C_NULL, nb, nt > 0 ? th : C_NULL, nt, rows, ev,
+                want_steps ? steps : C_NULL, want_margins ? margins : C_NULL))
+    (rows=rows, events=ev, steps=steps, margins=margins)
+end
+
+"kl_event_bound(p, d): the largest probability an event of probability p can have within KL radius d (rat_kl_event_bound; host only)"
+function kl_event_bound(p::Real, d::Real)
+    out = Ref(0.0)
+    check(ccall((:rat_kl_event_bound, LIB), Int32, (Float64, Float64, Ref{Float64}), Float64(p), Float64(d), out))
+    out[]
+end
+
 "integrate_cost(problem, x_array, u_array) -- ileqg.jl:115-124"
 function integrate_cost(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_array, u_array)
     h = bind!(s.h, problem); c = Ref(0.0)
@@ -1299,7 +1332,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_tail_risk, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_tail_risk, policy_events, kl_event_bound, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

@@ -17,6 +17,11 @@ from . import _native as native  # noqa: F401,E402
 from .ileqg import (  # noqa: F401,E402
     Context,
     UserNoise,
+    Event,
+    halfspace,
+    ball,
+    quadratic_event,
+    kl_event_bound,
     ILEQGSolver,
     ApproximationResult,
     DynamicProgrammingResult,

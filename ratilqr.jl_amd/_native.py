@@ -94,12 +94,15 @@ EXPORTS = [
     "rat_policy_worst_case",
     "rat_policy_worst_case_trajectory",
     "rat_policy_tail_risk",
+    "rat_policy_events", "rat_kl_event_bound",
 ]
 MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 WC_SLOTS = ("theta", "kl", "bound", "bound_se", "tilt_mean", "tilt_var", "ess", "flag")      # RAT_WC_* slots of the header, in order
 WC_NSTAT, WC_OK, WC_SATURATED, WC_EMPTY, WC_NONFINITE = 8, 0, 1, 2, 3
 TR_SLOTS = ("alpha", "var", "cvar", "cvar_se", "tail_n", "ess", "kl", "flag")                # RAT_TR_* slots of the header, in order
 TR_NSTAT, TR_OK, TR_SATURATED, TR_EMPTY, TR_NONFINITE = 8, 0, 1, 2, 3
+EV_SLOTS = ("prob", "prob_se", "margin_mean", "margin_max", "first_mean", "n_viol", "prob_robust", "flag")   # RAT_EV_* slots of the header, in order
+EV_NSTAT, EV_MAX = 8, 16
 
 _lib = None
 
@@ -142,6 +145,8 @@ def lib():
         _lib.rat_policy_worst_case.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp]
         _lib.rat_policy_worst_case_trajectory.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp]
         _lib.rat_policy_tail_risk.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int32, _dp, _dp]
+        _lib.rat_policy_events.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _ip, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp]
+        _lib.rat_kl_event_bound.argtypes = [C.c_double, C.c_double, _dp]
     return _lib
 
 

@@ -227,6 +227,12 @@ struct rat_handle_s {
     double *d_wt_y = nullptr; size_t cap_wt_y = 0;           // [rows][chunk] weights
     double *d_wt_part = nullptr; size_t cap_wt_part = 0;     // [rows][N+1][WT_SLOTS][WT_PART] partials
     double *d_wt_out = nullptr; size_t cap_wt_out = 0;       // centre [N+1][16] | mean | cov | S0, sum y^2 per row | mismatch count
+    // the safety events (rat_policy_events, policy_mc.hip) ride on the same replay; grown on demand
+    double *d_ev_out = nullptr; size_t cap_ev_out = 0;       // Q [16][256] | a [16][16] | b [16] | windows | event_out | step_out | mismatch count
+    double *d_ev_part = nullptr; size_t cap_ev_part = 0;     // [row batches][steps + events][EV_SLOTS][EV_PART] partials
+    double *d_ev_margin = nullptr; size_t cap_ev_margin = 0; // [n_event + 1][chunk] margins
+    int *d_ev_tau = nullptr; size_t cap_ev_tau = 0;          // [n_event + 1][chunk] first violating steps
+    unsigned *d_ev_mask = nullptr; size_t cap_ev_mask = 0;   // [N+1][chunk] per-step indicator bits
 };
 
 extern "C" int32_t rat_version(void) { return RAT_VERSION; }
@@ -405,6 +411,7 @@ extern "C" void rat_destroy(rat_handle h) {
     for (double *q : {h->d_mc_zu, h->d_mc_xo, h->d_mc_uo}) if (q) (void)hipFree(q);
     for (double *q : {h->d_wc_red, h->d_wc_w, h->d_tr_red}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_wt_cost, (void *)h->d_wt_dom, (void *)h->d_wt_y, (void *)h->d_wt_part, (void *)h->d_wt_out}) if (q) (void)hipFree(q);
+    for (void *q : {(void *)h->d_ev_out, (void *)h->d_ev_part, (void *)h->d_ev_margin, (void *)h->d_ev_tau, (void *)h->d_ev_mask}) if (q) (void)hipFree(q);
     if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
@@ -2340,52 +2347,60 @@ extern "C" rat_rc rat_policy_tail_risk(rat_handle h, const double *cost, int64_t
     return RAT_OK;
 }
 
-// The state and control mean and covariance at every step under the nominal distribution q and under the worst-case distribution
-// p* ~ exp(theta* J) q, one row per kl_bound / theta as rat_policy_worst_case's rows.  It replays the handle's last evaluation (mc_rec): the
-// same rollout kernel in the same chunks with the same seeds, the trajectories staged in buffers of the handle, and behind each chunk the
-// moment kernels of policy_mc.hip; one enqueue chain, one host wait.  The replay's costs are held against the stored ones bit for bit: a
-// difference means the problem, its parameters or the policy pack is no longer what the evaluation ran.
-extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
-                                                   double *rows_out, double *mean_out, double *cov_out) {
-    const char *F = "rat_policy_worst_case_trajectory: ";
-    if (!h) return fail(RAT_ERR_ARG, std::string(F) + "null handle");
-    if (n_bound < 0 || n_bound > WC_MAX_BOUND) return fail(RAT_ERR_ARG, std::string(F) + "n_bound must be in 0 .. 16");
-    if (n_theta < 0 || n_theta > MC_MAX_THETA) return fail(RAT_ERR_ARG, std::string(F) + "n_theta must be in 0 .. 16");
-    if (n_bound + n_theta == 0) return fail(RAT_ERR_ARG, std::string(F) + "no kl_bound and no theta: nothing to compute");
-    if ((n_bound > 0 && !kl_bound) || (n_theta > 0 && !theta) || !rows_out || !mean_out || !cov_out)
-        return fail(RAT_ERR_ARG, std::string(F) + "null kl_bound / theta / output");
+// What rat_policy_worst_case_trajectory and rat_policy_events share: both replay the handle's last evaluation (mc_rec) -- the same rollout
+// kernel in the same chunks with the same seeds, the trajectories staged in buffers of the handle -- form each row's weights from the stored
+// costs and hold the replay's costs against those bit for bit: a difference means the problem, its parameters or the policy pack is no
+// longer what the evaluation ran.
+static const char *const REPLAY_CHANGED = "the problem, its parameters or the policy changed since the evaluation: evaluate again";
+
+// the row arguments and the state of the handle: everything either call refuses before it touches the device
+static rat_rc replay_validate(rat_handle h, const std::string &F, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                              bool outputs_ok) {
+    if (!h) return fail(RAT_ERR_ARG, F + "null handle");
+    if (n_bound < 0 || n_bound > WC_MAX_BOUND) return fail(RAT_ERR_ARG, F + "n_bound must be in 0 .. 16");
+    if (n_theta < 0 || n_theta > MC_MAX_THETA) return fail(RAT_ERR_ARG, F + "n_theta must be in 0 .. 16");
+    if (n_bound + n_theta == 0) return fail(RAT_ERR_ARG, F + "no kl_bound and no theta: nothing to compute");
+    if ((n_bound > 0 && !kl_bound) || (n_theta > 0 && !theta) || !outputs_ok) return fail(RAT_ERR_ARG, F + "null kl_bound / theta / output");
     for (int i = 0; i < n_bound; ++i)
-        if (!(kl_bound[i] >= 0.0)) return fail(RAT_ERR_ARG, std::string(F) + "every kl_bound must be >= 0 (+Inf is allowed, NaN is not)");
+        if (!(kl_bound[i] >= 0.0)) return fail(RAT_ERR_ARG, F + "every kl_bound must be >= 0 (+Inf is allowed, NaN is not)");
     for (int i = 0; i < n_theta; ++i)
-        if (!(theta[i] >= 0.0) || std::isinf(theta[i])) return fail(RAT_ERR_ARG, std::string(F) + "every theta must be >= 0 and finite");
+        if (!(theta[i] >= 0.0) || std::isinf(theta[i])) return fail(RAT_ERR_ARG, F + "every theta must be >= 0 and finite");
     if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
     if (h->wide)
-        return fail(RAT_ERR_UNSUPPORTED, std::string(F) + "compiled for n <= 12, m <= 4 (general sizes: rat_rollout_noisy's x_out / u_out with "
+        return fail(RAT_ERR_UNSUPPORTED, F + "compiled for n <= 12, m <= 4 (general sizes: rat_rollout_noisy's x_out / u_out with "
                                          "rat_policy_worst_case's weights_out, combined on the host)");
-    const rat_handle_s::McReplay rec = h->mc_rec;
+    const rat_handle_s::McReplay &rec = h->mc_rec;
     if (rec.kind == 0 || h->mc_cost_K == 0 || rec.K != h->mc_cost_K)
-        return fail(RAT_ERR_ARG, std::string(F) + "no evaluation to replay: call rat_policy_evaluate / rat_policy_evaluate_noise on this handle first "
+        return fail(RAT_ERR_ARG, F + "no evaluation to replay: call rat_policy_evaluate / rat_policy_evaluate_noise on this handle first "
                                  "(costs uploaded by rat_policy_worst_case are no evaluation's)");
     if (rec.kind == 4)
-        return fail(RAT_ERR_UNSUPPORTED, std::string(F) + "a source model evaluated under N(0, W) has no trajectory output: write the Gaussian as "
+        return fail(RAT_ERR_UNSUPPORTED, F + "a source model evaluated under N(0, W) has no trajectory output: write the Gaussian as "
                                          "rat_user_noise and evaluate with rat_policy_evaluate_noise");
     if (rec.injected)
-        return fail(RAT_ERR_UNSUPPORTED, std::string(F) + "the evaluation ran on injected draws, which are not kept: combine the trajectories the "
+        return fail(RAT_ERR_UNSUPPORTED, F + "the evaluation ran on injected draws, which are not kept: combine the trajectories the "
                                          "caller has (x_out / u_out) with rat_policy_worst_case's weights_out on the host");
     const bool source = h->pb.model == RAT_MODEL_SOURCE;
-    const char *changed = "the problem, its parameters or the policy changed since the evaluation: evaluate again";
     if (rec.kind == 3 || rec.n != h->n || rec.m != h->m || rec.N != h->N || rec.model != h->pb.model || rec.W_tv != h->W_tv || (rec.kind == 2) != source ||
         (source && (!h->src_un || h->src_un_npn != rec.npn || h->src_un_npu != rec.npu || !h->h_un_over)))
-        return fail(RAT_ERR_ARG, std::string(F) + changed);
-    const int n = h->n, m = h->m, N = h->N, nrows = n_bound + n_theta, d = n + m;
-    if ((long)nrows * (N + 1) > WT_MAX_ROWSTEPS)
-        return fail(RAT_ERR_UNSUPPORTED, std::string(F) + "rows x (N + 1) = " + std::to_string((long)nrows * (N + 1)) + " is above " +
-                                         std::to_string(WT_MAX_ROWSTEPS) + " (64 MiB of partial sums): ask for fewer rows per call");
-    HIPCHK(hipSetDevice(h->device));
+        return fail(RAT_ERR_ARG, F + REPLAY_CHANGED);
+    return RAT_OK;
+}
+
+struct ReplayChunk { int64_t k0, kc; };
+
+// The replay itself, after replay_validate: grows the staging buffers, enqueues rat_policy_worst_case's chain on the stored costs (theta*,
+// Jmax and the rows: d_wc_red), then chunk by chunk the rollouts into d_mc_xo / d_mc_uo / d_wt_cost (/ d_wt_dom) and wct_weights into
+// d_wt_y (ta's replay fields are filled here, the mismatch count is *d_mismatch), and behind(ta, chunk) enqueues the caller's own kernels
+// behind each.  The
+// stream orders a chunk's rollouts behind the sums of the one before.
+template <class Behind>
+static rat_rc replay_chunks(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta, int *d_mismatch,
+                            WtArgs &ta, Behind &&behind) {
+    const rat_handle_s::McReplay rec = h->mc_rec;
+    const bool source = h->pb.model == RAT_MODEL_SOURCE;
+    const int n = h->n, m = h->m, N = h->N, nrows = n_bound + n_theta;
     const int64_t K = rec.K, chunk = std::min<int64_t>(K, 1 << 16);
     const int ldx = source ? n : XSTR, ldu = source ? m : USTR;
-    const size_t o_mean = (size_t)(N + 1) * 16, o_cov = o_mean + (size_t)nrows * (N + 1) * d, o_ess = o_cov + (size_t)nrows * (N + 1) * d * d,
-                 o_cnt = o_ess + 2 * (size_t)nrows, n_out = o_cnt + 1, n_part = (size_t)nrows * (N + 1) * WT_SLOTS * WT_PART;
     rat_rc rc;
     size_t cap_red = h->d_wc_red ? WC_SCRATCH : 0;
     if ((rc = grow(&h->d_wc_red, &cap_red, (size_t)WC_SCRATCH))) return rc;
@@ -2394,19 +2409,7 @@ extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *k
     if ((rc = grow(&h->d_wt_cost, &h->cap_wt_cost, (size_t)chunk))) return rc;
     if (!source && (rc = grow(&h->d_wt_dom, &h->cap_wt_dom, (size_t)chunk))) return rc;
     if ((rc = grow(&h->d_wt_y, &h->cap_wt_y, (size_t)nrows * chunk))) return rc;
-    if ((rc = grow(&h->d_wt_part, &h->cap_wt_part, n_part))) return rc;
-    if ((rc = grow(&h->d_wt_out, &h->cap_wt_out, n_out))) return rc;
     const double *d_x = h->d_mc_in + rec.o_x, *d_l = h->d_mc_in + rec.o_l, *d_L = rec.has_L ? h->d_mc_in + rec.o_L : nullptr;
-    // the centre: (x_nom, l) under a policy; open loop the noise-free trajectory of the handle's own rollout from the pack's (x_0, l)
-    const double *cx = d_x;
-    if (!rec.has_L) {
-        StateDev st;
-        if ((rc = op_prepare(h, 0.0, 0.0, h->opts.delta_0, &st))) return rc;
-        RolloutArgs ra; ra.st = st; ra.pb = h->pb; ra.op = h->opd; ra.dump = h->d_dump; ra.mode = 0; ra.x0 = d_x; ra.u0 = d_l; ra.notile = 0; ra.multi = 0;
-        model_rollout(h, ra, h->stream);
-        cx = h->st.xs;                                                // (slot 0: [N+1][12])
-    }
-    launch_wct_centre(cx, d_l, n, m, N, h->d_wt_out, h->stream);
     // theta*, Jmax and the rows, on the stored costs
     WcArgs wa;
     memset(&wa, 0, sizeof(wa));
@@ -2414,17 +2417,13 @@ extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *k
     for (int i = 0; i < n_bound; ++i) wa.bound[i] = kl_bound[i];
     for (int i = 0; i < n_theta; ++i) wa.theta[i] = theta[i];
     launch_policy_wc(wa, h->stream);
-    HIPCHK(hipMemsetAsync(h->d_wt_part, 0, n_part * 8, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_wt_out + o_cnt, 0, 8, h->stream));
+    HIPCHK(hipMemsetAsync(d_mismatch, 0, sizeof(int), h->stream));
     int *d_over = nullptr;
     if (source) { HIPCHK(hipHostGetDevicePointer((void **)&d_over, h->h_un_over, 0)); *h->h_un_over = 0; }
-    WtArgs ta;
-    memset(&ta, 0, sizeof(ta));
     ta.xs = h->d_mc_xo; ta.us = h->d_mc_uo; ta.ldx = ldx; ta.ldu = ldu; ta.n = n; ta.m = m; ta.N = N;
     ta.cost_re = h->d_wt_cost; ta.dom_re = source ? nullptr : h->d_wt_dom; ta.nrows = nrows; ta.wc = h->d_wc_red; ta.y = h->d_wt_y; ta.ldy = (long)chunk;
-    ta.centre = h->d_wt_out; ta.part = h->d_wt_part; ta.mismatch = reinterpret_cast<int *>(h->d_wt_out + o_cnt);
-    ta.mean = h->d_wt_out + o_mean; ta.cov = h->d_wt_out + o_cov; ta.ess = h->d_wt_out + o_ess;
-    for (int64_t k0 = 0; k0 < K; k0 += chunk) {                       // (the stream orders a chunk's rollouts behind the sums of the one before)
+    ta.mismatch = d_mismatch;
+    for (int64_t k0 = 0; k0 < K; k0 += chunk) {
         const int64_t kc = std::min(chunk, K - k0);
         if (source) {
             SrcUserNoisyArgs a;
@@ -2441,8 +2440,56 @@ extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *k
             launch_noisy_rollout(a, h->stream);
         }
         ta.kc = (long)kc; ta.cost = h->d_mc_cost + k0;
-        launch_wct_chunk(ta, h->stream);
+        launch_wct_weights(ta, h->stream);
+        if ((rc = behind(ta, ReplayChunk{k0, kc}))) return rc;
     }
+    return RAT_OK;
+}
+
+static rat_rc replay_mismatch(const std::string &F, int bad, int64_t K) {
+    if (bad == 0) return RAT_OK;
+    return fail(RAT_ERR_ARG, F + std::to_string(bad) + " of " + std::to_string(K) + " replayed rollouts cost something else than the "
+                             "evaluation found: " + REPLAY_CHANGED);
+}
+
+// The state and control mean and covariance at every step under the nominal distribution q and under the worst-case distribution
+// p* ~ exp(theta* J) q, one row per kl_bound / theta as rat_policy_worst_case's rows: the replay above with the moment kernels of
+// policy_mc.hip behind each chunk; one enqueue chain, one host wait.
+extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                                   double *rows_out, double *mean_out, double *cov_out) {
+    const std::string F = "rat_policy_worst_case_trajectory: ";
+    rat_rc rc;
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && mean_out && cov_out))) return rc;
+    const rat_handle_s::McReplay rec = h->mc_rec;
+    const int n = h->n, m = h->m, N = h->N, nrows = n_bound + n_theta, d = n + m;
+    if ((long)nrows * (N + 1) > WT_MAX_ROWSTEPS)
+        return fail(RAT_ERR_UNSUPPORTED, F + "rows x (N + 1) = " + std::to_string((long)nrows * (N + 1)) + " is above " +
+                                         std::to_string(WT_MAX_ROWSTEPS) + " (64 MiB of partial sums): ask for fewer rows per call");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t K = rec.K;
+    const size_t o_mean = (size_t)(N + 1) * 16, o_cov = o_mean + (size_t)nrows * (N + 1) * d, o_ess = o_cov + (size_t)nrows * (N + 1) * d * d,
+                 o_cnt = o_ess + 2 * (size_t)nrows, n_out = o_cnt + 1, n_part = (size_t)nrows * (N + 1) * WT_SLOTS * WT_PART;
+    if ((rc = grow(&h->d_wt_part, &h->cap_wt_part, n_part))) return rc;
+    if ((rc = grow(&h->d_wt_out, &h->cap_wt_out, n_out))) return rc;
+    const double *d_x = h->d_mc_in + rec.o_x, *d_l = h->d_mc_in + rec.o_l;
+    // the centre: (x_nom, l) under a policy; open loop the noise-free trajectory of the handle's own rollout from the pack's (x_0, l)
+    const double *cx = d_x;
+    if (!rec.has_L) {
+        StateDev st;
+        if ((rc = op_prepare(h, 0.0, 0.0, h->opts.delta_0, &st))) return rc;
+        RolloutArgs ra; ra.st = st; ra.pb = h->pb; ra.op = h->opd; ra.dump = h->d_dump; ra.mode = 0; ra.x0 = d_x; ra.u0 = d_l; ra.notile = 0; ra.multi = 0;
+        model_rollout(h, ra, h->stream);
+        cx = h->st.xs;                                                // (slot 0: [N+1][12])
+    }
+    launch_wct_centre(cx, d_l, n, m, N, h->d_wt_out, h->stream);
+    HIPCHK(hipMemsetAsync(h->d_wt_part, 0, n_part * 8, h->stream));
+    WtArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    ta.centre = h->d_wt_out; ta.part = h->d_wt_part;
+    ta.mean = h->d_wt_out + o_mean; ta.cov = h->d_wt_out + o_cov; ta.ess = h->d_wt_out + o_ess;
+    if ((rc = replay_chunks(h, kl_bound, n_bound, theta, n_theta, reinterpret_cast<int *>(h->d_wt_out + o_cnt), ta,
+                            [&](const WtArgs &c, ReplayChunk) -> rat_rc { launch_wct_chunk(c, h->stream); return RAT_OK; })))
+        return rc;
     launch_wct_final(ta, h->stream);
     HIPCHK(hipGetLastError());
     double rows[WC_MAX_ROWS * WC_NSTAT], ess[WC_MAX_ROWS * 2];
@@ -2453,17 +2500,136 @@ extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *k
     HIPCHK(hipMemcpyAsync(mean_out, h->d_wt_out + o_mean, (size_t)nrows * (N + 1) * d * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(cov_out, h->d_wt_out + o_cov, (size_t)nrows * (N + 1) * d * d * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (bad != 0)
-        return fail(RAT_ERR_ARG, std::string(F) + std::to_string(bad) + " of " + std::to_string(K) + " replayed rollouts cost something else than the "
-                                 "evaluation found: " + changed);
+    if ((rc = replay_mismatch(F, bad, K))) return rc;
     // the rows' effective sample size against the moment kernel's own S0^2 / sum y^2: two routes to one number (the rows' sums are centred,
     // these are not: 1e-6 relative is far above what either loses and far below any error of the weights)
     for (int r = 0; r < nrows; ++r) {
         const double e_row = rows[r * WC_NSTAT + RAT_WC_ESS], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
         if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
-            return fail(RAT_ERR_HIP, std::string(F) + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
+            return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
                                      " is not the row's " + std::to_string(e_row));
     }
+    for (int i = 0; i < nrows * WC_NSTAT; ++i) rows_out[i] = rows[i];
+    return RAT_OK;
+}
+
+// p' log(p' / p) + (1 - p') log((1 - p') / (1 - p)) for p <= p' < 1, 0 < p < 1, both logarithms through log1p of the difference: near
+// p' = p the two terms are of size p' - p each and their sum of size (p' - p)^2
+static double kl_bernoulli(double q, double p) {
+    const double dl = q - p;
+    return q * std::log1p(dl / p) + (1.0 - q) * std::log1p(-dl / (1.0 - p));
+}
+
+extern "C" rat_rc rat_kl_event_bound(double p, double d, double *out) {
+    if (!out) return fail(RAT_ERR_ARG, "rat_kl_event_bound: null out");
+    if (!(p >= 0.0 && p <= 1.0)) return fail(RAT_ERR_ARG, "rat_kl_event_bound: p must be in [0, 1] (NaN is not)");
+    if (!(d >= 0.0)) return fail(RAT_ERR_ARG, "rat_kl_event_bound: d must be >= 0 (+Inf is allowed, NaN is not)");
+    if (p == 0.0 || p == 1.0 || d == 0.0) { *out = p; return RAT_OK; }   // (an event no rollout shows cannot be tilted up: its likelihood ratio is 0 / 0)
+    if (d >= -std::log(p)) { *out = 1.0; return RAT_OK; }             // KL(1 || p) = log(1 / p)
+    double lo = p, hi = 1.0;                                          // KL(lo || p) <= d < KL(hi || p), KL increasing on [p, 1]
+    for (;;) {
+        const double mid = 0.5 * (lo + hi);
+        if (!(mid > lo && mid < hi)) break;                           // the bracket is two neighbouring doubles
+        if (kl_bernoulli(mid, p) <= d) lo = mid; else hi = mid;
+    }
+    // the root lies between two neighbouring doubles: the nearer one in KL.  (Rounding down would understate an upper bound by up to a whole
+    // step of KL, 5e-12 d at p = 0.999, d = 1e-6; the nearer neighbour halves that and errs upwards as often as downwards.)
+    const double k_lo = kl_bernoulli(lo, p), k_hi = (hi < 1.0) ? kl_bernoulli(hi, p) : -std::log(p);
+    *out = (k_hi - d < d - k_lo) ? hi : lo;
+    return RAT_OK;
+}
+
+// Violation probabilities of quadratic events (include/ratilqr.h): the replay above with ev_eval and ev_sums of policy_mc.hip behind each
+// chunk in place of the moment kernels; one enqueue chain, one host wait.  PROB_ROBUST is formed here, on the host, from the counts.
+extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double *Q, const double *a, const double *b,
+                                    const int32_t *t_lo, const int32_t *t_hi,
+                                    const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                    double *rows_out, double *event_out, double *step_out, double *margin_out) {
+    const std::string F = "rat_policy_events: ";
+    rat_rc rc;
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && event_out))) return rc;
+    if (n_event < 1 || n_event > EV_MAX) return fail(RAT_ERR_ARG, F + "n_event must be in 1 .. 16");
+    if (!a || !b || !t_lo || !t_hi) return fail(RAT_ERR_ARG, F + "null a / b / t_lo / t_hi");
+    const rat_handle_s::McReplay rec = h->mc_rec;
+    const int n = h->n, m = h->m, N = h->N, nrows = n_bound + n_theta, d = n + m, ne1 = n_event + 1;
+    for (int e = 0; e < n_event; ++e) {
+        if (!(0 <= t_lo[e] && t_lo[e] <= t_hi[e] && t_hi[e] <= N))
+            return fail(RAT_ERR_ARG, F + "event " + std::to_string(e) + ": the window must satisfy 0 <= t_lo <= t_hi <= N");
+        bool fin = std::isfinite(b[e]);
+        for (int i = 0; i < d; ++i) fin = fin && std::isfinite(a[e * d + i]);
+        if (Q) for (int i = 0; i < d * d; ++i) fin = fin && std::isfinite(Q[(size_t)e * d * d + i]);
+        if (!fin) return fail(RAT_ERR_ARG, F + "event " + std::to_string(e) + ": Q, a and b must be finite");
+    }
+    const int nsteps = step_out ? N + 1 : 0, ny = nsteps + ne1, nbatch = (nrows + EV_ROWS - 1) / EV_ROWS;
+    const size_t per_batch = (size_t)ny * EV_SLOTS * EV_PART, n_part = per_batch * nbatch;
+    if (n_part * 8 > (size_t)EV_MAX_PART_BYTES)
+        return fail(RAT_ERR_UNSUPPORTED, F + std::to_string(nrows) + " rows need " + std::to_string(n_part * 8) + " bytes of partial sums, above 64 MiB: " +
+                                         std::to_string((long)((size_t)EV_MAX_PART_BYTES / (per_batch * 8)) * EV_ROWS) + " rows fit in one call at this horizon"
+                                         + (step_out ? " (more without step_out)" : ""));
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t K = rec.K, chunk = std::min<int64_t>(K, 1 << 16);
+    // the events in the 12 + 4 tile: Q as the MFMA's A operand reads it (entry (k, i) at k * 16 + i), a, b, the windows
+    const size_t o_a = (size_t)EV_MAX * 256, o_b = o_a + EV_MAX * 16, o_win = o_b + EV_MAX, o_ev = o_win + EV_MAX, o_step = o_ev + (size_t)nrows * ne1 * EV_NSTAT,
+                 o_cnt = o_step + (size_t)nrows * ne1 * nsteps, n_out = o_cnt + 1;
+    std::vector<double> in(o_ev, 0.0);
+    auto tix = [n](int i) { return i < n ? i : 12 + i - n; };
+    for (int e = 0; e < n_event; ++e) {
+        for (int i = 0; i < d; ++i) {
+            in[o_a + e * 16 + tix(i)] = a[e * d + i];
+            if (Q) for (int k = 0; k < d; ++k) in[(size_t)e * 256 + tix(k) * 16 + tix(i)] = Q[(size_t)e * d * d + i + (size_t)d * k];
+        }
+        in[o_b + e] = b[e];
+        int32_t w[2] = {t_lo[e], t_hi[e]};
+        memcpy(&in[o_win + e], w, sizeof(w));
+    }
+    if ((rc = grow(&h->d_ev_out, &h->cap_ev_out, n_out))) return rc;
+    if ((rc = grow(&h->d_ev_part, &h->cap_ev_part, n_part))) return rc;
+    if ((rc = grow(&h->d_ev_margin, &h->cap_ev_margin, (size_t)ne1 * chunk))) return rc;
+    if ((rc = grow(&h->d_ev_tau, &h->cap_ev_tau, (size_t)ne1 * chunk))) return rc;
+    if (step_out && (rc = grow(&h->d_ev_mask, &h->cap_ev_mask, (size_t)(N + 1) * chunk))) return rc;
+    HIPCHK(hipMemcpyAsync(h->d_ev_out, in.data(), o_ev * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));                          // (`in` is pageable and dies with this scope's errors: the copy is complete here)
+    EvArgs ea;
+    memset(&ea, 0, sizeof(ea));
+    ea.n_event = n_event; ea.quad = Q ? 1 : 0; ea.Qt = h->d_ev_out; ea.at = h->d_ev_out + o_a; ea.b = h->d_ev_out + o_b;
+    ea.win = reinterpret_cast<const int *>(h->d_ev_out + o_win);
+    ea.margin = h->d_ev_margin; ea.tau = h->d_ev_tau; ea.mask = step_out ? h->d_ev_mask : nullptr; ea.part = h->d_ev_part;
+    ea.event_out = h->d_ev_out + o_ev; ea.step_out = h->d_ev_out + o_step;
+    WtArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    if ((rc = replay_chunks(h, kl_bound, n_bound, theta, n_theta, reinterpret_cast<int *>(h->d_ev_out + o_cnt), ta,
+                            [&](const WtArgs &c, ReplayChunk ch) -> rat_rc {
+                                ea.xs = c.xs; ea.us = c.us; ea.ldx = c.ldx; ea.ldu = c.ldu; ea.n = c.n; ea.m = c.m; ea.N = c.N; ea.kc = c.kc; ea.cost = c.cost;
+                                ea.ldy = c.ldy; ea.nrows = c.nrows; ea.y = c.y; ea.wc = c.wc; ea.first = ch.k0 == 0;
+                                launch_ev_chunk(ea, h->stream);
+                                if (margin_out)                       // the chunk's margins, event by event, to their place among the K
+                                    HIPCHK(hipMemcpy2DAsync(margin_out + ch.k0, (size_t)K * 8, h->d_ev_margin, (size_t)c.ldy * 8, (size_t)ch.kc * 8,
+                                                            (size_t)n_event, hipMemcpyDeviceToHost, h->stream));
+                                return RAT_OK;
+                            })))
+        return rc;
+    launch_ev_final(ea, h->stream);
+    HIPCHK(hipGetLastError());
+    double rows[WC_MAX_ROWS * WC_NSTAT];
+    int bad = 0;
+    std::vector<double> ev((size_t)nrows * ne1 * EV_NSTAT);
+    HIPCHK(hipMemcpyAsync(rows, h->d_wc_red + WC_O_ROWS, (size_t)nrows * WC_NSTAT * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&bad, h->d_ev_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(ev.data(), h->d_ev_out + o_ev, ev.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    if (step_out) HIPCHK(hipMemcpyAsync(step_out, h->d_ev_out + o_step, (size_t)nrows * ne1 * nsteps * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = replay_mismatch(F, bad, K))) return rc;
+    for (int r = 0; r < nrows; ++r) {
+        double d_row = (r < n_bound) ? kl_bound[r] : rows[r * WC_NSTAT + RAT_WC_KL];
+        if (d_row < 0.0) d_row = 0.0;                                 // (a theta row's KL that rounding left below zero)
+        for (int e = 0; e < ne1; ++e) {
+            double *o = &ev[((size_t)r * ne1 + e) * EV_NSTAT];
+            const double n_ok = o[RAT_EV_PROB_ROBUST];                // (ev_final leaves N_OK in this slot)
+            if (std::isnan(n_ok) || std::isnan(d_row)) o[RAT_EV_PROB_ROBUST] = std::nan("");
+            else if ((rc = rat_kl_event_bound(o[RAT_EV_N_VIOL] / n_ok, d_row, &o[RAT_EV_PROB_ROBUST]))) return rc;
+        }
+    }
+    for (size_t i = 0; i < ev.size(); ++i) event_out[i] = ev[i];
     for (int i = 0; i < nrows * WC_NSTAT; ++i) rows_out[i] = rows[i];
     return RAT_OK;
 }

@@ -136,6 +136,54 @@ struct WtArgs {
 };
 // c[t] = (x[t][0..n), u[t][0..m)) in the 12 + 4 tile, zero padded, zero where the source is not finite; x [N+1][12], u [N][4]
 void launch_wct_centre(const double *x, const double *u, int n, int m, int N, double *centre, hipStream_t s);
-// one chunk: the weights and the replay check, then the chunk's sums into the partials
+// one chunk: the weights of its rollouts per row and the replay check (wct_weights; rat_policy_events forms its weights with it too) ...
+void launch_wct_weights(const WtArgs &a, hipStream_t s);
+// ... then, behind it, the chunk's sums into the partials
 void launch_wct_chunk(const WtArgs &a, hipStream_t s);
 void launch_wct_final(const WtArgs &a, hipStream_t s);
+
+// ---- rat_policy_events: how often a policy violates quadratic constraints, under q and under every row's tilt (policy_mc.hip) ---------------
+// An event is g(t, z) = z' Q z + a' z + b of z = (x_t, u_t) in the 12 + 4 tile, watched over the steps t_lo .. t_hi.  Behind each replayed
+// chunk (after wct_weights) ev_eval forms, per rollout and event, the margin M = max g over the window, the first step tau with g > 0 and
+// the per-step indicators -- sixteen rollouts as the columns of Q Z, four 16 x 16 x 4 MFMAs per event and step -- and ev_sums adds the
+// weighted indicator sums into the partial of its workgroup; ev_final sums the partials in index order.  Event n_event is "any": the
+// union of the given ones.
+#define EV_MAX 16             /* events a call gives; EV_MAX + 1 with "any" */
+#define EV_NSTAT 8            /* RAT_EV_NSTAT of the header */
+#define EV_SLOTS 8            /* workgroups per step / per event and row batch: fixed, so that the summation order depends on K alone */
+#define EV_ROWS 4             /* rows a workgroup accumulates (grid.z = row batches) */
+#define EV_NSUM 6             /* sums per row of an event's block: y | y A | y^2 A | y^2 (1 - A) | y M | y A tau */
+#define EV_PART 72            /* doubles per partial: a step's [EV_ROWS][EV_MAX + 1] indicator sums, or an event's [EV_ROWS][EV_NSUM] | N_VIOL | N_OK | max M */
+#define EV_O_NVIOL (EV_ROWS * EV_NSUM)
+#define EV_O_NOK (EV_O_NVIOL + 1)
+#define EV_O_MMAX (EV_O_NVIOL + 2)
+#define EV_MAX_PART_BYTES (64l << 20)   /* the partials [row batches][steps + events][EV_SLOTS][EV_PART] stay below this, as WT_MAX_ROWSTEPS keeps the moments' */
+
+struct EvArgs {
+    const double *xs, *us;    // staged trajectories of the chunk: [kc][N+1][ldx], [kc][N][ldu]
+    int ldx, ldu;
+    int n, m, N;
+    long kc;                  // rollouts of the chunk
+    const double *cost;       // [kc] the stored costs of the chunk's rollouts (NaN: DomainError, selected out)
+    int n_event;
+    int quad;                 // 0: every event is linear (Q == NULL): no matrix product
+    const double *Qt;         // [n_event][16][16] in the tile, entry (k, i) at k * 16 + i: Q_i's row i, column k (quad only)
+    const double *at;         // [n_event][16] in the tile
+    const double *b;          // [n_event]
+    const int *win;           // [n_event][2]: t_lo, t_hi
+    double *margin;           // [n_event + 1][ldy] M of the chunk's rollouts, NaN for a DomainError rollout
+    int *tau;                 // [n_event + 1][ldy] first violating step, -1: none
+    unsigned *mask;           // [N+1][ldy] bit i: event i is in its window and g_i > 0 at that step; or null (no per-step sums)
+    long ldy;
+    int nrows;
+    const double *y;          // [nrows][ldy] weights of the chunk (wct_weights)
+    int first;                // this is the call's first chunk: the partials are set, not added to
+    double *part;             // [row batches][nsteps + n_event + 1][EV_SLOTS][EV_PART], nsteps = mask ? N + 1 : 0
+    // ev_final only
+    const double *wc;         // launch_policy_wc's scratch: the rows' states at WC_O_INFO
+    double *event_out;        // [nrows][n_event + 1][EV_NSTAT]; slot 6 holds N_OK (the host forms PROB_ROBUST from it)
+    double *step_out;         // [nrows][n_event + 1][N+1] (with mask)
+};
+// one chunk, behind launch_wct_weights: the events of the staged trajectories, then the chunk's sums into the partials
+void launch_ev_chunk(const EvArgs &a, hipStream_t s);
+void launch_ev_final(const EvArgs &a, hipStream_t s);

@@ -873,21 +873,244 @@ __global__ __launch_bounds__(MC_THREADS) void wct_final(WtArgs a) {
     if (t == 0 && e == 0) { a.ess[2 * r] = s0; a.ess[2 * r + 1] = S[WT_O_SY2]; }
 }
 
+// ---- rat_policy_events: violation probabilities of quadratic events on the replayed trajectories ----------------------------------------
+// ev_eval: a wavefront takes sixteen rollouts as the columns of Z [16 components][16 rollouts] and walks the steps; lane (col = lane & 15,
+// kq = lane >> 4) holds Z[kq + 4 r][col], r = 0 .. 3 -- x components kq, kq + 4, kq + 8 and u component kq -- which is at once the B operand
+// of k-block r of Q Z (four 16 x 16 x 4 MFMAs, Q's operands from LDS) and the lane's rows of the product: z' Q z is the lane's four
+// products, summed over the four kq lanes of the column by a butterfly (every lane of a column ends with the same bits).  g of a
+// (rollout, step, event) is formed from that column alone: its bits depend on no other rollout, event or row.  The running margin, the
+// first violating step and the step's indicator bits stay in registers.
+// ev_sums: lane tid of slot s takes the rollouts s * 256 + tid, + EV_SLOTS * 256, ... in order; the lanes combine in the fixed LDS tree
+// into the slot's partial, chunk after chunk in stream order; ev_final sums the slots in index order.  A workgroup (slot, y, row batch)
+// sums either one step's indicators of every event, or one event's per-rollout terms.  No floating-point atomics, and the counts are
+// sums of ones in double: exact, so no atomics there either.
+template <bool QUAD>
+__global__ __launch_bounds__(MC_THREADS) void ev_eval(EvArgs a) {
+    __shared__ double s_q[QUAD ? EV_MAX * 256 : 1];
+    __shared__ double s_a[EV_MAX * 16], s_b[EV_MAX];
+    __shared__ int s_lo[EV_MAX], s_hi[EV_MAX];
+    const int tid = threadIdx.x, ne = a.n_event, N = a.N;
+    if (QUAD) for (int i = tid; i < ne * 256; i += MC_THREADS) s_q[i] = a.Qt[i];
+    for (int i = tid; i < ne * 16; i += MC_THREADS) s_a[i] = a.at[i];
+    if (tid < ne) { s_b[tid] = a.b[tid]; s_lo[tid] = a.win[2 * tid]; s_hi[tid] = a.win[2 * tid + 1]; }
+    __syncthreads();
+    const int w = tid >> 6, lane = tid & 63, col = lane & 15, kq = lane >> 4;
+    const double nan = __builtin_nan("");
+    const long G = (a.kc + 15) >> 4;
+    for (long g = (long)blockIdx.x * 4 + w; g < G; g += (long)gridDim.x * 4) {           // (uniform over the wavefront)
+        const long q = 16 * g + col;
+        const bool live = q < a.kc;                                   // (the K tail)
+        const bool ok = live && !mc_nan(a.cost[live ? q : 0]);        // selected, not multiplied: the trajectory may hold NaN
+        const double *xq = a.xs + q * (N + 1) * a.ldx, *uq = a.us + q * N * a.ldu;
+        double M[EV_MAX];
+        int tau[EV_MAX];
+#pragma unroll
+        for (int e = 0; e < EV_MAX; ++e) { M[e] = nan; tau[e] = -1; }
+        for (int t = 0; t <= N; ++t) {
+            double zv[4];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) zv[r] = (ok && kq + 4 * r < a.n) ? xq[t * a.ldx + kq + 4 * r] : 0.0;
+            zv[3] = (ok && kq < a.m && t < N) ? uq[t * a.ldu + kq] : 0.0;
+            unsigned bits = 0u;
+#pragma unroll
+            for (int e = 0; e < EV_MAX; ++e) {
+                if (e < ne) {                                         // (uniform over the grid)
+                    const double *ae = s_a + e * 16 + kq;
+                    double p = ae[0] * zv[0] + ae[4] * zv[1] + ae[8] * zv[2] + ae[12] * zv[3];
+                    if (QUAD) {
+                        const double *qe = s_q + e * 256 + kq * 16 + col;
+                        wt_d4 c = (wt_d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                        for (int kb = 0; kb < 4; ++kb) c = __builtin_amdgcn_mfma_f64_16x16x4f64(qe[kb * 64], zv[kb], c, 0, 0, 0);
+                        p += c[0] * zv[0] + c[1] * zv[1] + c[2] * zv[2] + c[3] * zv[3];
+                    }
+                    p += __shfl_xor(p, 16);
+                    p += __shfl_xor(p, 32);
+                    const double gv = p + s_b[e];
+                    if (t >= s_lo[e] && t <= s_hi[e]) {
+                        if (gv > M[e] || mc_nan(M[e])) M[e] = gv;     // (a NaN g never replaces a number)
+                        if (gv > 0.0) {
+                            bits |= 1u << e;
+                            if (tau[e] < 0) tau[e] = t;
+                        }
+                    }
+                }
+            }
+            if (bits) bits |= 1u << ne;
+            if (a.mask && kq == 0 && live) a.mask[(long)t * a.ldy + q] = ok ? bits : 0u;
+        }
+        if (kq == 0 && live) {
+            double Ma = nan;
+            int ta = -1;
+#pragma unroll
+            for (int e = 0; e < EV_MAX; ++e) {
+                if (e < ne) {
+                    a.margin[(long)e * a.ldy + q] = ok ? M[e] : nan;
+                    a.tau[(long)e * a.ldy + q] = ok ? tau[e] : -1;
+                    if (M[e] > Ma || mc_nan(Ma)) Ma = M[e];
+                    if (tau[e] >= 0 && (ta < 0 || tau[e] < ta)) ta = tau[e];
+                }
+            }
+            a.margin[(long)ne * a.ldy + q] = ok ? Ma : nan;
+            a.tau[(long)ne * a.ldy + q] = ok ? ta : -1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void ev_sums(EvArgs a) {
+    __shared__ double sh[(EV_MAX + 1) * MC_THREADS];
+    const int slot = blockIdx.x, by = blockIdx.y, r0 = blockIdx.z * EV_ROWS, tid = threadIdx.x;
+    const int nr = (a.nrows - r0 < EV_ROWS) ? a.nrows - r0 : EV_ROWS;
+    const int nsteps = a.mask ? a.N + 1 : 0, ny = nsteps + a.n_event + 1;
+    double *p = a.part + (((size_t)blockIdx.z * ny + by) * EV_SLOTS + slot) * EV_PART;
+    const long T = (long)EV_SLOTS * MC_THREADS;
+    if (by < nsteps) {                                                // one step: sum y [g_e(t) > 0] per row and event
+        double acc[EV_ROWS][EV_MAX + 1];
+#pragma unroll
+        for (int r = 0; r < EV_ROWS; ++r)
+#pragma unroll
+            for (int e = 0; e <= EV_MAX; ++e) acc[r][e] = 0.0;
+        for (long q = (long)slot * MC_THREADS + tid; q < a.kc; q += T) {
+            const bool ok = !mc_nan(a.cost[q]);
+            const unsigned bits = ok ? a.mask[(long)by * a.ldy + q] : 0u;
+#pragma unroll
+            for (int r = 0; r < EV_ROWS; ++r) {
+                if (r < nr) {                                         // (uniform over the workgroup)
+                    const double y = ok ? a.y[(long)(r0 + r) * a.ldy + q] : 0.0;
+#pragma unroll
+                    for (int e = 0; e <= EV_MAX; ++e) acc[r][e] += ((bits >> e) & 1u) ? y : 0.0;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < EV_ROWS; ++r) {
+            if (r < nr) {
+                block_tree_n<EV_MAX + 1>(acc[r], sh);
+                if (tid == 0) {
+#pragma unroll
+                    for (int e = 0; e <= EV_MAX; ++e) p[r * (EV_MAX + 1) + e] = a.first ? acc[r][e] : p[r * (EV_MAX + 1) + e] + acc[r][e];
+                }
+            }
+        }
+        return;
+    }
+    const int e = by - nsteps;                                        // one event: the per-rollout terms per row, the counts, the largest margin
+    double s[EV_ROWS][EV_NSUM], cnt[2] = {0.0, 0.0}, mx = -__builtin_inf();
+#pragma unroll
+    for (int r = 0; r < EV_ROWS; ++r)
+#pragma unroll
+        for (int i = 0; i < EV_NSUM; ++i) s[r][i] = 0.0;
+    for (long q = (long)slot * MC_THREADS + tid; q < a.kc; q += T) {
+        const bool ok = !mc_nan(a.cost[q]);
+        const double Mv = a.margin[(long)e * a.ldy + q];
+        const int tv = a.tau[(long)e * a.ldy + q];
+        const bool A = ok && tv >= 0;
+        cnt[0] += A ? 1.0 : 0.0;
+        cnt[1] += ok ? 1.0 : 0.0;
+        if (ok && Mv > mx) mx = Mv;
+#pragma unroll
+        for (int r = 0; r < EV_ROWS; ++r) {
+            if (r < nr) {
+                const double y = ok ? a.y[(long)(r0 + r) * a.ldy + q] : 0.0, y2 = y * y;
+                s[r][0] += y;
+                s[r][1] += A ? y : 0.0;
+                s[r][2] += A ? y2 : 0.0;
+                s[r][3] += A ? 0.0 : y2;
+                s[r][4] += ok ? y * Mv : 0.0;
+                s[r][5] += A ? y * (double)tv : 0.0;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < EV_ROWS; ++r) {
+        if (r < nr) {
+            block_tree_n<EV_NSUM>(s[r], sh);
+            if (tid == 0) {
+#pragma unroll
+                for (int i = 0; i < EV_NSUM; ++i) p[r * EV_NSUM + i] = a.first ? s[r][i] : p[r * EV_NSUM + i] + s[r][i];
+            }
+        }
+    }
+    block_tree_n<2>(cnt, sh);
+    mx = block_tree<2>(mx, sh);
+    if (tid == 0) {
+        p[EV_O_NVIOL] = a.first ? cnt[0] : p[EV_O_NVIOL] + cnt[0];
+        p[EV_O_NOK] = a.first ? cnt[1] : p[EV_O_NOK] + cnt[1];
+        p[EV_O_MMAX] = (a.first || mx > p[EV_O_MMAX]) ? mx : p[EV_O_MMAX];
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void ev_final(EvArgs a) {
+    __shared__ double S[EV_NSUM + 3];
+    const int e = blockIdx.x, r = blockIdx.y, z = r / EV_ROWS, rr = r % EV_ROWS, tid = threadIdx.x;
+    const int nsteps = a.mask ? a.N + 1 : 0, ne1 = a.n_event + 1, ny = nsteps + ne1;
+    const double *pe = a.part + ((size_t)z * ny + nsteps + e) * EV_SLOTS * EV_PART;
+    if (tid < EV_NSUM + 3) {
+        const int i = (tid < EV_NSUM) ? rr * EV_NSUM + tid : EV_O_NVIOL + (tid - EV_NSUM);
+        double v = pe[i];
+        for (int sl = 1; sl < EV_SLOTS; ++sl) {
+            const double x = pe[sl * EV_PART + i];
+            v = (i == EV_O_MMAX) ? (x > v ? x : v) : v + x;
+        }
+        S[tid] = v;
+    }
+    __syncthreads();
+    const double st = a.wc[WC_O_INFO + 2 * r + 1], nan = __builtin_nan("");
+    const bool dead = (st == WC_ST_EMPTY || st == WC_ST_NONFINITE);
+    const double sy = S[0];
+    if (tid == 0) {
+        double *o = a.event_out + ((size_t)r * ne1 + e) * EV_NSTAT;
+        const double pr = S[1] / sy, se2 = (1.0 - pr) * (1.0 - pr) * S[2] + pr * pr * S[3];
+        o[0] = dead ? nan : pr;
+        o[1] = dead ? nan : sqrt(se2) / sy;
+        o[2] = dead ? nan : S[4] / sy;
+        o[3] = dead ? nan : S[EV_NSUM + 2];
+        o[4] = dead ? nan : S[5] / S[1];                              // (NaN when no weighted rollout violates: 0 / 0)
+        o[5] = dead ? nan : S[EV_NSUM];
+        o[6] = dead ? nan : S[EV_NSUM + 1];                           // N_OK: the host forms PROB_ROBUST from it
+        o[7] = (st == WC_ST_SAT) ? 1.0 : (st == WC_ST_EMPTY) ? 2.0 : (st == WC_ST_NONFINITE) ? 3.0 : 0.0;
+    }
+    for (int t = tid; t < nsteps; t += MC_THREADS) {
+        const double *ps = a.part + ((size_t)z * ny + t) * EV_SLOTS * EV_PART + rr * (EV_MAX + 1) + e;
+        double v = 0.0;
+        for (int sl = 0; sl < EV_SLOTS; ++sl) v += ps[sl * EV_PART];
+        a.step_out[((size_t)r * ne1 + e) * nsteps + t] = dead ? nan : v / sy;
+    }
+}
+
 }  // namespace
 
 void launch_wct_centre(const double *x, const double *u, int n, int m, int N, double *centre, hipStream_t s) {
     hipLaunchKernelGGL(wct_centre, dim3((unsigned)(((N + 1) * 16 + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, s, x, u, n, m, N, centre);
 }
 
-void launch_wct_chunk(const WtArgs &a, hipStream_t s) {
+void launch_wct_weights(const WtArgs &a, hipStream_t s) {
     if (a.kc <= 0 || a.nrows <= 0) return;
     const long nb = (a.kc + MC_THREADS - 1) / MC_THREADS;
     hipLaunchKernelGGL(wct_weights, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_wct_chunk(const WtArgs &a, hipStream_t s) {
+    if (a.kc <= 0 || a.nrows <= 0) return;
     hipLaunchKernelGGL(wct_moments, dim3(WT_SLOTS, (unsigned)(a.N + 1), (unsigned)((a.nrows + WT_ROWS - 1) / WT_ROWS)), dim3(WT_WAVES * 64), 0, s, a);
 }
 
 void launch_wct_final(const WtArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(wct_final, dim3((unsigned)(a.N + 1), (unsigned)a.nrows), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_ev_chunk(const EvArgs &a, hipStream_t s) {
+    if (a.kc <= 0 || a.nrows <= 0 || a.n_event <= 0) return;
+    const long nb = (((a.kc + 15) >> 4) + 3) >> 2;                    // four groups of sixteen rollouts per workgroup
+    const dim3 ge((unsigned)(nb < 1024 ? nb : 1024));
+    if (a.quad) hipLaunchKernelGGL(ev_eval<true>, ge, dim3(MC_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(ev_eval<false>, ge, dim3(MC_THREADS), 0, s, a);
+    const int ny = (a.mask ? a.N + 1 : 0) + a.n_event + 1;
+    hipLaunchKernelGGL(ev_sums, dim3(EV_SLOTS, (unsigned)ny, (unsigned)((a.nrows + EV_ROWS - 1) / EV_ROWS)), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_ev_final(const EvArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(ev_final, dim3((unsigned)(a.n_event + 1), (unsigned)a.nrows), dim3(MC_THREADS), 0, s, a);
 }
 
 void launch_policy_mc(const McArgs &a, hipStream_t s) {

@@ -196,6 +196,9 @@ class GenericContext(il.Context):
     def policy_tail_risk(self, *a, **k):
         self._carrier_only("policy_tail_risk")
 
+    def policy_events(self, *a, **k):
+        self._carrier_only("policy_events")
+
     def solve_batch(self, *a, **k):
         self._carrier_only("solve_batch")
 

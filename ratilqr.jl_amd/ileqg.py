@@ -36,6 +36,84 @@ class UserNoise:
         self.seed = int(seed)
 
 
+class Event:
+    """A safety event of Context.policy_events: g(t, z) = z' Q z + a' z + b of z = (x_t, u_t), violated where g > 0 at a step of the window.
+    Build one with halfspace, ball or quadratic_event.  Q (or None: linear) and a are given over (x, u) -- n + m entries -- or over x
+    alone; steps is None (the whole horizon 0 .. N), one step t, or (t_lo, t_hi)."""
+
+    def __init__(self, Q, a, b, steps=None):
+        self.Q = None if Q is None else np.asarray(Q, dtype=np.float64)
+        self.a = np.atleast_1d(np.asarray(a, dtype=np.float64)).ravel()
+        self.b = float(b)
+        self.steps = steps
+
+    def dense(self, n, m, N):
+        """(Q (d, d) or None, a (d,), b, t_lo, t_hi) over d = n + m coordinates"""
+        d = n + m
+        if self.a.size not in (n, d):
+            raise ValueError(f"an event's a has {self.a.size} entries: n = {n} or n + m = {d} are served")
+        a = np.zeros(d)
+        a[:self.a.size] = self.a
+        Q = None
+        if self.Q is not None:
+            if self.Q.shape not in ((n, n), (d, d)):
+                raise ValueError(f"an event's Q is {self.Q.shape}: ({n}, {n}) or ({d}, {d}) are served")
+            Q = np.zeros((d, d))
+            Q[:self.Q.shape[0], :self.Q.shape[1]] = self.Q
+        if self.steps is None:
+            lo, hi = 0, N
+        elif np.ndim(self.steps) == 0:
+            lo = hi = int(self.steps)
+        else:
+            lo, hi = (int(v) for v in self.steps)
+        return Q, a, self.b, lo, hi
+
+
+def halfspace(a, b, steps=None):
+    """The event a' z + b > 0 (a lane edge, an actuator limit): a over (x, u) or over x alone."""
+    return Event(None, a, b, steps)
+
+
+def quadratic_event(Q, a, b, steps=None):
+    """The event z' Q z + a' z + b > 0; Q is used as given (not symmetrised), over (x, u) or over x alone."""
+    return Event(Q, a, b, steps)
+
+
+def ball(idx, centre, radius, steps=None):
+    """The event of being INSIDE the ball of that radius about `centre` in the coordinates idx of (x, u) -- a circular obstacle:
+    g = radius^2 - |z[idx] - centre|^2."""
+    idx = [int(i) for i in np.atleast_1d(idx)]
+    c = np.atleast_1d(np.asarray(centre, dtype=np.float64)).ravel()
+    if c.size != len(idx):
+        raise ValueError("ball: one centre entry per index")
+    d = max(idx) + 1
+    Q, a = np.zeros((d, d)), np.zeros(d)
+    for i, ci in zip(idx, c):
+        Q[i, i] = -1.0
+        a[i] = 2.0 * ci
+    return _BallEvent(Q, a, float(radius) ** 2 - float(c @ c), steps)
+
+
+class _BallEvent(Event):
+    """ball's event: Q and a reach as far as the largest index, and are padded to n + m whatever that is"""
+
+    def dense(self, n, m, N):
+        d, k = n + m, self.a.size
+        if k > d:
+            raise ValueError(f"ball: index {k - 1} is beyond the {d} coordinates of (x, u)")
+        Q, a = np.zeros((d, d)), np.zeros(d)
+        Q[:k, :k], a[:k] = self.Q, self.a
+        return Event(Q, a, self.b, self.steps).dense(n, m, N)
+
+
+def kl_event_bound(p, d):
+    """rat_kl_event_bound: the largest probability an event of probability p can have within KL radius d of the sampling distribution
+    (host only: no GPU needed)."""
+    out = C.c_double()
+    nv.check(nv.lib().rat_kl_event_bound(C.c_double(float(p)), C.c_double(float(d)), C.byref(out)))
+    return out.value
+
+
 class Context:
     """One rat_handle bound to one problem (device buffers sized for max_batch samples x spec_eps step sizes)."""
 
@@ -248,6 +326,43 @@ class Context:
                      cov_u=cov[sl, :N, n:, n:].copy(), cov_xu=cov[sl, :N, :n, n:].copy())
             return r
         return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)))
+
+    def policy_events(self, events, kl_bounds=(), thetas=(), want_steps=False, want_margins=False):
+        """How often the policy violates safety events (rat_policy_events): per event (halfspace, ball, quadratic_event; 1 to 16) and per
+        row -- the worst-case distribution of each KL radius, the tilt of each theta; theta = 0 is the nominal distribution -- the
+        probability that a rollout violates it, formed on the device by replaying the last policy_evaluate / policy_evaluate_noise of this
+        context like policy_worst_case_trajectory.  Returns {"bounds": part, "thetas": part, "margins": (n_event, K) or None}; a part
+        carries policy_worst_case's row keys and, with R rows, arrays (R, n_event + 1) -- the last column is "any", the union --
+        prob, prob_se, margin_mean, margin_max, first_mean, n_viol, prob_robust, event_flag, and with want_steps step (R, n_event + 1, N+1):
+        the probability of a violation at each step.  margins[i] (want_margins) is the margin of every rollout for event i, NaN for a
+        DomainError rollout: a sample to hand to policy_tail_risk(costs=) or policy_worst_case(costs=)."""
+        events = list(events)
+        d = nv.f64(np.atleast_1d(np.asarray(kl_bounds, dtype=np.float64))).ravel()
+        th = nv.f64(np.atleast_1d(np.asarray(thetas, dtype=np.float64))).ravel()
+        n, m, N, R, E = self.n, self.m, self.N, d.size + th.size, len(events)
+        dense = [e.dense(n, m, N) for e in events]
+        quad = any(q[0] is not None for q in dense)
+        Q = nv.f64(np.stack([(np.zeros((n + m, n + m)) if q[0] is None else q[0]).T for q in dense])) if quad and E else None   # column-major
+        a = nv.f64(np.stack([q[1] for q in dense])) if E else None
+        b = nv.f64(np.array([q[2] for q in dense])) if E else None
+        lo = np.ascontiguousarray([q[3] for q in dense], dtype=np.int32) if E else None
+        hi = np.ascontiguousarray([q[4] for q in dense], dtype=np.int32) if E else None
+        rows, ev = np.zeros((R, nv.WC_NSTAT)), np.zeros((R, E + 1, nv.EV_NSTAT))
+        step = np.zeros((R, E + 1, N + 1)) if want_steps else None
+        margins = np.zeros((max(E, 1), max(int(self.debug_get("mc_cost_K")), 1))) if want_margins else None
+        nv.check(nv.lib().rat_policy_events(self.h, C.c_int32(E), nv.P(Q), nv.P(a), nv.P(b), nv.PI(lo), nv.PI(hi), nv.P(d) if d.size else None,
+                                            C.c_int32(d.size), nv.P(th) if th.size else None, C.c_int32(th.size), nv.P(rows), nv.P(ev),
+                                            nv.P(step), nv.P(margins)))
+
+        def part(sl):
+            r = {k: rows[sl, i].copy() for i, k in enumerate(nv.WC_SLOTS)}
+            r["flag"] = r["flag"].astype(np.int64)
+            r.update({k: ev[sl, :, i].copy() for i, k in enumerate(nv.EV_SLOTS) if k != "flag"})
+            r["event_flag"] = ev[sl, :, nv.EV_SLOTS.index("flag")].astype(np.int64)
+            if step is not None:
+                r["step"] = step[sl].copy()
+            return r
+        return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)), margins=margins)
 
     def integrate_cost(self, x, u):
         out = C.c_double()
