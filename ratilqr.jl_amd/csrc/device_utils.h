@@ -80,6 +80,14 @@ __device__ __forceinline__ double row_sum16(double x) {
     return x;
 }
 
+// src of the lane eight columns away in the same 16-lane row, on the lanes of the banks in BM (bank q = columns 4 q .. 4 q + 3); the lane's
+// own old elsewhere: one DPP row rotation with a bank mask per 32 bits.  BM = 0x2: columns 4..7 <- 12..15.
+template <int BM>
+__device__ __forceinline__ double row_ror8_merge(double old, double src) {
+    return __hiloint2double(__builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), 0x128, 0xF, BM, false),
+                            __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), 0x128, 0xF, BM, false));
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // One 2x2-block round of the symmetric sweep (in-place inversion of M = inv(W) - theta S, ileqg.jl:365-367) with the rank-2
 // update on the matrix pipe.  m holds M (12 x 12 in the 12 x 16 accumulator layout, register r = rows 4r..4r+3).

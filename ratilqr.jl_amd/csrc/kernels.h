@@ -18,6 +18,7 @@ struct RecDev {
     int *lgen;             // [B][2] record generation the gains of each half of L / dl were solved from (0: none)
     int *count;            // [2] sweeps replayed so far in pairs (switch lq_replay_count) | evaluations that end a solve replayed (lq_replay_last_count)
     int last;              // the evaluation that ends a solve replays too (switch lq_replay_last)
+    int stack;             // the replayed pair forms row 12 of T for both recursions in one mm3 (replay_body<true, STACK>; switch lq_replay_stack)
 };
 
 struct SweepArgs {

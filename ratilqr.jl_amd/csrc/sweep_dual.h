@@ -415,6 +415,12 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
 // (no valid record, mu differs bitwise from the recorded pass's, theta == 0, or committed gains not solved from this record; the evaluation
 // alone also under rec.last = 0) -- and the caller runs the full sweep, which rewrites everything the replay wrote.  Record loads run two steps
 // ahead (three register sets).
+// STACK (GAINB only; switch lq_replay_stack): row 12 of T for BOTH recursions from one mm3.  mm3(v, Y) is v'Y: row i of the result reads
+// column i of v (registers 0..2 on the lanes j == i) and nothing else of it, and only row 12 of T is used -- so columns 0..11 of the operand
+// are free.  Column 12 of recursion B's V is rotated into column 4 of a copy of recursion A's (one DPP row rotation by eight with a bank
+// mask: columns 4..7 <- B's 12..15, the rest A's own), one mm3 runs against Y, and row 12 (register 3, g == 0) is recursion A's T row,
+// row 4 (register 1, g == 0) recursion B's: the same column of V, the same Y, the same K order and start value as the two separate
+// mm3 -- the same bits, on the lanes that read them before.  13 MFMAs per step become 10.
 // wls: WLS_DUAL doubles
 // =======================================================================================================================================
 struct RTile {
@@ -422,7 +428,7 @@ struct RTile {
     double x, xj, la;      // [qr | q] row, x_t[j], own entry of L_t (evaluation)
 };
 
-template <bool GAINB>
+template <bool GAINB, bool STACK = false>
 __device__ __forceinline__ bool replay_body(const SweepArgs &a, const int b, double *const wls) {
     int lane_ = threadIdx.x & 63;
     asm volatile("" : "+v"(lane_));      // opaque per phase (see sweep_body)
@@ -526,10 +532,21 @@ __device__ __forceinline__ bool replay_body(const SweepArgs &a, const int b, dou
         d4 mw;
         mw[0] = m0 * nwrow[0]; mw[1] = m1 * nwrow[1]; mw[2] = m2 * nwrow[2]; mw[3] = 0.0;
         const d4 y2 = mm3(mw, cz, (d4){0, 0, 0, 0});
-        const d4 tmA = mm3(vA, y2, (d4){0, 0, 0, 0});
-        d4 tmB = {0, 0, 0, 0};
-        if (GAINB) tmB = mm3(vB, y2, (d4){0, 0, 0, 0});
-        const double fvA = tmA[3] + cur.x, fvB = tmB[3] + cur.x;
+        double tA12, tB12 = 0.0;                                 // row 12 of T (lanes g == 0)
+        if (GAINB && STACK) {
+            d4 vS;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) vS[r] = row_ror8_merge<0x2>(vA[r], vB[r]);
+            vS[3] = 0.0;
+            const d4 tm = mm3(vS, y2, (d4){0, 0, 0, 0});
+            tA12 = tm[3];
+            tB12 = tm[1];
+        } else {
+            const d4 tmA = mm3(vA, y2, (d4){0, 0, 0, 0});
+            tA12 = tmA[3];
+            if (GAINB) { const d4 tmB = mm3(vB, y2, (d4){0, 0, 0, 0}); tB12 = tmB[3]; }
+        }
+        const double fvA = tA12 + cur.x, fvB = tB12 + cur.x;
         exB[g * 16 + j] = gh;
         exA[fbo] = fvA;
         lbuf[l] = cur.la;
@@ -612,5 +629,7 @@ __device__ __forceinline__ bool replay_body(const SweepArgs &a, const int b, dou
     if (l == 0) atomicAdd(rc.count + (GAINB ? 0 : 1), GAINB ? 2 : 1);     // [0] sweeps replayed in pairs, [1] last evaluations replayed
     return true;
 }
-__device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b, double *const wls) { return replay_body<true>(a, b, wls); }
+__device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b, double *const wls) {
+    return a.rec.stack ? replay_body<true, true>(a, b, wls) : replay_body<true>(a, b, wls);
+}
 __device__ __forceinline__ bool replay_eval_body(const SweepArgs &a, const int b, double *const wls) { return replay_body<false>(a, b, wls); }
