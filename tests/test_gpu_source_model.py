@@ -74,6 +74,8 @@ def check_against_oracle(r, s, x, l, L, v, hist, vt=1e-9):
 
 
 def test_operators_against_closed_forms():
+    """The pendulum (2, 1): the m x m block of R and the n x n block of Q.  The full-tile shapes, every pair-loop regime up to (12, 4), are in
+    tests/test_gpu_source_shapes.py."""
     prob = source_pendulum()
     rng = np.random.default_rng(7)
     x0, u = rng.standard_normal(2), 0.3 * rng.standard_normal((N_P, 1))
