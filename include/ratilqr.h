@@ -398,6 +398,62 @@ rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double *Q, const d
  * only: needs no handle and no GPU.  d == 0 gives p; p == 0 gives 0; p == 1 gives 1; d == +Inf with p > 0 gives 1.  NaN, p outside
  * [0, 1] or d < 0: RAT_ERR_ARG. */
 rat_rc rat_kl_event_bound(double p, double d, double *out);
+/* The probability of a RARE safety event of a policy, by adaptive importance sampling on the device: where rat_policy_events' plain Monte
+ * Carlo returns N_VIOL = 0 (a probability of 1e-8 at K <= 2^27), this call still resolves it.  The rollouts are rat_rollout_noisy's
+ * (simulate_dynamics with rng, ileqg.jl:44-55, 94-109): x_{k+1} = f(x_k, u_k) + C_k z_k with C_k = chol_lower(W(k)), under the policy
+ * (x_nom, l, L) exactly as rat_policy_evaluate takes it -- but z_k = s_k + xi_k, xi_k ~ N(0, I_n), is drawn from a proposal shifted by
+ * s in R^{N x n}, and rollout i carries the log-likelihood ratio logw_i = sum_k (-s_k' z_ik + 1/2 s_k' s_k).  One event
+ * g(t, z) = z' Q z + a' z + b of z = (x_t, u_t) over the window t_lo .. t_hi, exactly rat_policy_events' definition: M = max over the
+ * window, violated iff M > 0, a NaN g is passed over, u_N = 0.  The shift is adapted by the multilevel cross-entropy method.  Iteration
+ * j = 0 .. n_iter - 1 starts from s^(0) = shift_in (0 when NULL):
+ *   1. K rollouts under s^(j); M_i, logw_i and the DomainError flag stay on the device;
+ *   2. the level gamma_j = min(0, the ceil((1 - rho) n)-th smallest M), n the OK rollouts whose margin is a number, (1 - rho) n one rounded
+ *      product: an exact order statistic, by rat_policy_tail_risk's radix select;
+ *   3. gamma_j == 0 ends the adaptation (so does a sample with no margin to rank, or with an infinite one).  Otherwise, over the elite
+ *      E = { i : M_i >= gamma_j } with w_i = exp(logw_i - max logw), s^(j+1)_k = sum_E w_i z_ik / sum_E w_i, formed as
+ *      s^(j)_k + sum_E w_i xi_ik / sum_E w_i with xi replayed from the iteration's Philox stream (no K N n normals are stored), summed in a
+ *      fixed order without floating-point atomics.  An update that is not finite is dropped as a whole and flags RAT_RE_NONFINITE.
+ * The final pass draws K rollouts under the last shift and returns stats[RAT_RE_NSTAT], the slots below; the weights are NOT
+ * self-normalised, the proposal's density is known.  The loop stays on the device; the host reads 4 bytes per iteration (the stop rule).
+ * Keying: pass p -- the final pass is p = 0, iteration j is p = j + 1 -- draws under seed_p = seed + 0xD1B54A32D192ED03 p (mod 2^64) the
+ * way rat_policy_evaluate draws under its seed (chunks of min(K, 2^16) rollouts, chunk c keyed seed_p + 0x9E3779B97F4A7C15 c, Philox
+ * counter (index in the chunk, 0, t >> 1, component)).  So with n_iter == 0 and shift_in == NULL the call is plain Monte Carlo on
+ * rat_policy_evaluate's noise at that seed: margin_out is rat_policy_events' bit for bit and every logw is 0.  The same call returns the
+ * same bits.
+ *   K          1 .. 2^27;  n_iter 0 .. 32;  rho in (0, 0.5]: the elite share
+ *   Q          [d * d] column-major, d = n + m, used as given (not symmetrised), or NULL: a linear event (no matrix product)
+ *   a [d], b;  t_lo, t_hi with 0 <= t_lo <= t_hi <= N
+ *   shift_in   [N][n] (s_k at k n) or NULL;  shift_out [N][n] or NULL: the shift the final pass ran under -- hand it back as shift_in with
+ *              n_iter == 0 to estimate again at another K or seed
+ *   trace_out  [n_iter][RAT_RE_NTRACE] or NULL: per iteration the level gamma_j, |E|, the elite's effective sample size
+ *              (sum_E w)^2 / sum_E w^2 and |s^(j+1)|; the last three are NaN on the iteration that ended the adaptation, all four on
+ *              iterations that did not run
+ *   margin_out [K], logw_out [K] or NULL: M_i (NaN for a DomainError rollout) and logw_i of the final pass
+ * RAT_ERR_ARG: K, n_iter, rho or the window out of range, a non-finite entry of Q, a, b or shift_in, a NULL a or stats, a W(k) that is
+ * not positive definite.  RAT_ERR_UNSUPPORTED: general sizes and source models (the shift is defined on the family rollout), N > 256.
+ * The device buffers of the call (20 bytes per rollout) belong to the handle, like rat_policy_evaluate's, and are its own: the handle's
+ * recorded evaluation is not disturbed, a later rat_policy_events still replays it. */
+#define RAT_RE_PROB      0   /* (1 / N_OK) sum_i w_i [M_i > 0], w_i = exp(logw_i) */
+#define RAT_RE_PROB_SE   1   /* the sample standard error of that mean: sd(w [M > 0]) / sqrt(N_OK); NaN when N_OK < 2 */
+#define RAT_RE_ESS       2   /* (sum_A w)^2 / sum_A w^2 over the violating rollouts A; 0 when none violates */
+#define RAT_RE_N_VIOL    3
+#define RAT_RE_N_OK      4   /* rollouts without a DomainError */
+#define RAT_RE_N_DOMAIN  5
+#define RAT_RE_LOGW_MAX  6   /* the largest and ... */
+#define RAT_RE_LOGW_MIN  7   /* ... the smallest logw among the OK rollouts */
+#define RAT_RE_FLAG      8   /* RAT_RE_OK ... as a double */
+#define RAT_RE_N_ITER    9   /* adaptation iterations that ran (the one that found gamma == 0 included) */
+#define RAT_RE_LEVEL     10  /* the last gamma_j; NaN when no iteration ran */
+#define RAT_RE_NSTAT     12  /* slot 11 reserved, written as 0 */
+#define RAT_RE_NTRACE    4
+#define RAT_RE_OK          0
+#define RAT_RE_NOT_REACHED 1 /* no iteration found gamma == 0 (n_iter == 0 included): PROB is still the weighted estimate, and may be 0 */
+#define RAT_RE_EMPTY       2 /* N_OK == 0: PROB, PROB_SE and ESS are NaN */
+#define RAT_RE_NONFINITE   3 /* an infinite margin or logw, an overflowing weight or a dropped update: PROB, PROB_SE and ESS are NaN */
+rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K, uint64_t seed,
+                             const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi,
+                             const double *shift_in, int32_t n_iter, double rho,
+                             double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out);
 /* approximate_model(problem, u_array, x_array)                 ileqg.jl:258-322
  * -> q[N+1], qv[n*(N+1)], Q[n*n*(N+1)], r[m*N], R[m*m*N], P[m*n*N], A[n*n*N], B[n*m*N], W[n*n*N] */
 rat_rc rat_approximate_model(rat_handle h, const double *u, const double *x,

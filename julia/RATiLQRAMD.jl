@@ -490,6 +490,37 @@ function kl_event_bound(p::Real, d::Real)
     out[]
 end
 
+"""
+rare_event_probability(s, problem, x_nom, l_array, L_array, Q, a, b, t_lo, t_hi; K, seed, shift, n_iter, rho, want_margins, want_logw): the
+probability that the policy violates the event z' Q z + a' z + b > 0 at a step t_lo ≤ t ≤ t_hi (0-based, z = (x_t, u_t); Q === nothing: a
+linear event), however rare, by adaptive importance sampling on the device (rat_policy_rare_event): the process noise is drawn from a
+proposal shifted by s (n, N), every rollout carries its likelihood ratio, and up to n_iter multilevel cross-entropy iterations with elite
+share rho move the shift towards the event before the final pass estimates.  `shift`: where the adaptation starts (nothing: 0).  Returns a
+named tuple of the RAT_RE_* slots, shift (n, N), trace (4, n_iter): level, elite count, elite effective sample size, |shift| per
+iteration, and margins / logw (K) of the final pass or `nothing`.
+"""
+function rare_event_probability(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_nom, l_array::Vector{Vector{Float64}},
+                                L_array::Union{Nothing,Vector{Matrix{Float64}}}, Q::Union{Nothing,Matrix{Float64}}, a::Vector{Float64}, b::Real,
+                                t_lo::Integer, t_hi::Integer; K::Integer=65536, seed::Integer=0, shift::Union{Nothing,Matrix{Float64}}=nothing,
+                                n_iter::Integer=8, rho::Real=0.1, want_margins::Bool=false, want_logw::Bool=false)
+    h = bind!(s.h, problem)
+    n, m, N = dims(problem)
+    xn = x_nom isa Vector{Float64} ? x_nom : flat(x_nom)
+    l = flat(l_array)
+    L = L_array === nothing ? C_NULL : flat(L_array)
+    stats = zeros(12); shift_out = zeros(n, N); trace = zeros(4, max(n_iter, 1))
+    margins = want_margins ? Vector{Float64}(undef, K) : nothing
+    logw = want_logw ? Vector{Float64}(undef, K) : nothing
+    check(ccall((:rat_policy_rare_event, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, UInt64, Ptr{Float64}, Ptr{Float64}, Float64, Int32, Int32,
+                 Ptr{Float64}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, xn, l, L, K, UInt64(seed), Q === nothing ? C_NULL : Q, a, Float64(b), t_lo, t_hi, shift === nothing ? C_NULL : shift,
+                n_iter, Float64(rho), stats, shift_out, trace, want_margins ? margins : C_NULL, want_logw ? logw : C_NULL))
+    (prob=stats[1], prob_se=stats[2], ess=stats[3], n_viol=Int(stats[4]), n_ok=Int(stats[5]), n_domain=Int(stats[6]), logw_max=stats[7],
+     logw_min=stats[8], flag=Int(stats[9]), n_iter=Int(stats[10]), level=stats[11], shift=shift_out, trace=trace[:, 1:n_iter],
+     margins=margins, logw=logw)
+end
+
 "integrate_cost(problem, x_array, u_array) -- ileqg.jl:115-124"
 function integrate_cost(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_array, u_array)
     h = bind!(s.h, problem); c = Ref(0.0)
@@ -1332,7 +1363,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_tail_risk, policy_events, kl_event_bound, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

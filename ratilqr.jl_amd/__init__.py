@@ -22,6 +22,8 @@ from .ileqg import (  # noqa: F401,E402
     ball,
     quadratic_event,
     kl_event_bound,
+    RareEventResult,
+    rare_event_probability,
     ILEQGSolver,
     ApproximationResult,
     DynamicProgrammingResult,

@@ -95,6 +95,7 @@ EXPORTS = [
     "rat_policy_worst_case_trajectory",
     "rat_policy_tail_risk",
     "rat_policy_events", "rat_kl_event_bound",
+    "rat_policy_rare_event",
 ]
 MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 WC_SLOTS = ("theta", "kl", "bound", "bound_se", "tilt_mean", "tilt_var", "ess", "flag")      # RAT_WC_* slots of the header, in order
@@ -103,6 +104,8 @@ TR_SLOTS = ("alpha", "var", "cvar", "cvar_se", "tail_n", "ess", "kl", "flag")   
 TR_NSTAT, TR_OK, TR_SATURATED, TR_EMPTY, TR_NONFINITE = 8, 0, 1, 2, 3
 EV_SLOTS = ("prob", "prob_se", "margin_mean", "margin_max", "first_mean", "n_viol", "prob_robust", "flag")   # RAT_EV_* slots of the header, in order
 EV_NSTAT, EV_MAX = 8, 16
+RE_SLOTS = ("prob", "prob_se", "ess", "n_viol", "n_ok", "n_domain", "logw_max", "logw_min", "flag", "n_iter", "level")   # RAT_RE_* slots of the header, in order
+RE_NSTAT, RE_NTRACE, RE_OK, RE_NOT_REACHED, RE_EMPTY, RE_NONFINITE = 12, 4, 0, 1, 2, 3
 
 _lib = None
 
@@ -147,6 +150,8 @@ def lib():
         _lib.rat_policy_tail_risk.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int32, _dp, _dp]
         _lib.rat_policy_events.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _ip, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp]
         _lib.rat_kl_event_bound.argtypes = [C.c_double, C.c_double, _dp]
+        _lib.rat_policy_rare_event.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_uint64, _dp, _dp, C.c_double, C.c_int32, C.c_int32, _dp,
+                                               C.c_int32, C.c_double, _dp, _dp, _dp, _dp, _dp]
     return _lib
 
 

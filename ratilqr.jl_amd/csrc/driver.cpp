@@ -23,6 +23,7 @@
 #include "wide.h"
 #include "ce_device.h"
 #include "policy_mc.h"
+#include "rare_event.h"
 #include "source_args.h"
 #include "source_model.h"
 
@@ -234,6 +235,14 @@ struct rat_handle_s {
     double *d_ev_margin = nullptr; size_t cap_ev_margin = 0; // [n_event + 1][chunk] margins
     int *d_ev_tau = nullptr; size_t cap_ev_tau = 0;          // [n_event + 1][chunk] first violating steps
     unsigned *d_ev_mask = nullptr; size_t cap_ev_mask = 0;   // [N+1][chunk] per-step indicator bits
+    // rare events by adaptive importance sampling (rat_policy_rare_event, rare_event.hip): buffers of its own -- the call leaves the
+    // recorded evaluation (d_mc_in, d_mc_cost, mc_rec) as it found it; grown on demand
+    double *d_re_in = nullptr; size_t cap_re_in = 0;         // Wchol | x_nom | l | L | Q tile [256] | a tile [16] | shift [N][12]
+    double *d_re_margin = nullptr; size_t cap_re_margin = 0; // [K] margins of the current pass
+    double *d_re_logw = nullptr; size_t cap_re_logw = 0;     // [K] log-weights
+    int *d_re_dom = nullptr; size_t cap_re_dom = 0;          // [K] DomainError flags
+    double *d_re_part = nullptr; size_t cap_re_part = 0;     // [N * 12 + 3][RE_SLOTS] partials of the elite sums
+    double *d_re_red = nullptr;                              // [RE_SCRATCH]
 };
 
 extern "C" int32_t rat_version(void) { return RAT_VERSION; }
@@ -414,6 +423,7 @@ extern "C" void rat_destroy(rat_handle h) {
     for (double *q : {h->d_wc_red, h->d_wc_w, h->d_tr_red}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_wt_cost, (void *)h->d_wt_dom, (void *)h->d_wt_y, (void *)h->d_wt_part, (void *)h->d_wt_out}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_ev_out, (void *)h->d_ev_part, (void *)h->d_ev_margin, (void *)h->d_ev_tau, (void *)h->d_ev_mask}) if (q) (void)hipFree(q);
+    for (void *q : {(void *)h->d_re_in, (void *)h->d_re_margin, (void *)h->d_re_logw, (void *)h->d_re_dom, (void *)h->d_re_part, (void *)h->d_re_red}) if (q) (void)hipFree(q);
     if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
@@ -2634,6 +2644,102 @@ extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double 
     }
     for (size_t i = 0; i < ev.size(); ++i) event_out[i] = ev[i];
     for (int i = 0; i < nrows * WC_NSTAT; ++i) rows_out[i] = rows[i];
+    return RAT_OK;
+}
+
+// The probability of a rare safety event by adaptive importance sampling (include/ratilqr.h; rare_event.h has the chain and the keying):
+// the policy is packed as rat_policy_evaluate packs it, into buffers of this call's own, and the whole loop runs on the device.  The stop
+// rule is one 4-byte read-back per iteration: a skipped iteration then launches nothing (instead of sixteen launches that return at once;
+// either is small beside a rollout pass of milliseconds), and the host knows which trace rows exist.
+extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K, uint64_t seed,
+                                        const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi,
+                                        const double *shift_in, int32_t n_iter, double rho,
+                                        double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out) {
+    const std::string F = "rat_policy_rare_event: ";
+    if (K < 1 || K > ((int64_t)1 << 27)) return fail(RAT_ERR_ARG, F + "K must be in 1 .. 2^27");
+    if (n_iter < 0 || n_iter > RE_MAX_ITER) return fail(RAT_ERR_ARG, F + "n_iter must be in 0 .. 32");
+    if (!(rho > 0.0 && rho <= 0.5)) return fail(RAT_ERR_ARG, F + "rho must be in (0, 0.5]");
+    if (!h || !x_nom || !l || !a || !stats) return fail(RAT_ERR_ARG, F + "null handle / x_nom / l / a / stats");
+    if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
+    if (h->wide) return fail(RAT_ERR_UNSUPPORTED, F + "compiled for n <= 12, m <= 4 (the shift is defined on the family rollout)");
+    if (h->pb.model == RAT_MODEL_SOURCE) return fail(RAT_ERR_UNSUPPORTED, F + "not available for source models (the shift is defined on the family rollout)");
+    const int n = h->n, m = h->m, N = h->N, Nw = h->W_tv ? N : 1, d = n + m;
+    if (N > RE_MAX_N) return fail(RAT_ERR_UNSUPPORTED, F + "N is above " + std::to_string(RE_MAX_N) + " (the shift is staged in LDS)");
+    if (!(0 <= t_lo && t_lo <= t_hi && t_hi <= N)) return fail(RAT_ERR_ARG, F + "the window must satisfy 0 <= t_lo <= t_hi <= N");
+    bool fin = std::isfinite(b);
+    for (int i = 0; i < d; ++i) fin = fin && std::isfinite(a[i]);
+    if (Q) for (int i = 0; i < d * d; ++i) fin = fin && std::isfinite(Q[i]);
+    if (shift_in) for (int i = 0; i < N * n; ++i) fin = fin && std::isfinite(shift_in[i]);
+    if (!fin) return fail(RAT_ERR_ARG, F + "Q, a, b and shift_in must be finite");
+    HIPCHK(hipSetDevice(h->device));
+    // Wchol | x_nom | l | L as rat_policy_evaluate packs them, then the event in the 12 + 4 tile (rat_policy_events' layout) and the shift
+    std::vector<double> pack((size_t)Nw * 192, 0.0), Lc((size_t)n * n), xp, up, Lp;
+    for (int k = 0; k < Nw; ++k) {
+        if (!host_chol_lower(n, h->hW.data() + (size_t)k * n * n, Lc.data()))
+            return fail(RAT_ERR_ARG, "W(k) is not positive definite (MvNormal would throw)");
+        for (int i = 0; i < n; ++i) for (int jj = 0; jj <= i; ++jj) pack[(size_t)k * 192 + i * 16 + jj] = Lc[i + n * jj];
+    }
+    if (L) { pad_x(h, x_nom, xp); pad_L(h, L, Lp); }
+    else { xp.assign((size_t)(N + 1) * XSTR, 0.0); for (int i = 0; i < n; ++i) xp[i] = x_nom[i]; }
+    pad_u(h, l, up);
+    const size_t o_x = pack.size(); pack.insert(pack.end(), xp.begin(), xp.end());
+    const size_t o_l = pack.size(); pack.insert(pack.end(), up.begin(), up.end());
+    const size_t o_L = pack.size(); pack.insert(pack.end(), Lp.begin(), Lp.end());
+    const size_t o_q = pack.size(), o_a = o_q + 256, o_s = o_a + 16;
+    pack.resize(o_s + (size_t)N * 12, 0.0);
+    auto tix = [n](int i) { return i < n ? i : 12 + i - n; };
+    for (int i = 0; i < d; ++i) {
+        pack[o_a + tix(i)] = a[i];
+        if (Q) for (int k = 0; k < d; ++k) pack[o_q + tix(k) * 16 + tix(i)] = Q[i + (size_t)d * k];
+    }
+    if (shift_in) for (int t = 0; t < N; ++t) for (int i = 0; i < n; ++i) pack[o_s + (size_t)t * 12 + i] = shift_in[(size_t)t * n + i];
+    rat_rc rc;
+    size_t cap_red = h->d_re_red ? RE_SCRATCH : 0;
+    const size_t n_part = ((size_t)N * 12 + 3) * RE_SLOTS;
+    if ((rc = grow(&h->d_re_in, &h->cap_re_in, pack.size()))) return rc;
+    if ((rc = grow(&h->d_re_margin, &h->cap_re_margin, (size_t)K))) return rc;
+    if ((rc = grow(&h->d_re_logw, &h->cap_re_logw, (size_t)K))) return rc;
+    if ((rc = grow(&h->d_re_dom, &h->cap_re_dom, (size_t)K))) return rc;
+    if ((rc = grow(&h->d_re_part, &h->cap_re_part, n_part))) return rc;
+    if ((rc = grow(&h->d_re_red, &cap_red, (size_t)RE_SCRATCH))) return rc;
+    HIPCHK(hipMemcpy(h->d_re_in, pack.data(), pack.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(h->d_re_red + RE_O_LVL, 0, (size_t)(RE_O_TR - RE_O_LVL) * 8, h->stream));
+    ReArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.pb = h->pb; ra.Wchol = h->d_re_in; ra.xnom = h->d_re_in + o_x; ra.l = h->d_re_in + o_l; ra.L = L ? h->d_re_in + o_L : nullptr;
+    ra.K = (long)K; ra.chunk = (long)std::min<int64_t>(K, 1 << 16);
+    ra.shift = h->d_re_in + o_s; ra.Qt = h->d_re_in + o_q; ra.at = h->d_re_in + o_a; ra.b = b; ra.t_lo = t_lo; ra.t_hi = t_hi;
+    ra.margin = h->d_re_margin; ra.logw = h->d_re_logw; ra.dom = h->d_re_dom; ra.scratch = h->d_re_red; ra.part = h->d_re_part;
+    int reached = 0, n_run = 0;
+    for (int j = 0; j < n_iter; ++j) {
+        ra.seed = seed + RE_PASS_STRIDE * (uint64_t)(j + 1);
+        ra.iter = j;
+        launch_re_rollout(ra, Q != nullptr, h->stream);
+        launch_re_level(ra, rho, h->stream);
+        HIPCHK(hipGetLastError());
+        int code = 0;
+        HIPCHK(hipMemcpyAsync(&code, h->d_re_red + RE_O_CTL, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        ++n_run;
+        if (code == 1) reached = 1;
+        if (code != 0) break;                                         // gamma == 0, or nothing to rank: the shift stays
+        launch_re_adapt(ra, h->stream);
+    }
+    ra.seed = seed; ra.iter = 0; ra.reached = reached; ra.n_run = n_run;
+    launch_re_rollout(ra, Q != nullptr, h->stream);
+    launch_re_final(ra, h->stream);
+    HIPCHK(hipGetLastError());
+    double out[RE_NSTAT], tr[RE_MAX_ITER * RE_NTRACE];
+    std::vector<double> sh((size_t)N * 12);
+    HIPCHK(hipMemcpyAsync(out, h->d_re_red + RE_O_STATS, sizeof(out), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(tr, h->d_re_red + RE_O_TRACE, sizeof(tr), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(sh.data(), h->d_re_in + o_s, sh.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    if (margin_out) HIPCHK(hipMemcpyAsync(margin_out, h->d_re_margin, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
+    if (logw_out) HIPCHK(hipMemcpyAsync(logw_out, h->d_re_logw, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < RAT_RE_NSTAT; ++i) stats[i] = out[i];
+    if (shift_out) for (int t = 0; t < N; ++t) for (int i = 0; i < n; ++i) shift_out[(size_t)t * n + i] = sh[(size_t)t * 12 + i];
+    if (trace_out) for (int i = 0; i < n_iter * RAT_RE_NTRACE; ++i) trace_out[i] = (i < n_run * RAT_RE_NTRACE) ? tr[i] : std::nan("");
     return RAT_OK;
 }
 

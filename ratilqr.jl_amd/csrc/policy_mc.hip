@@ -16,27 +16,13 @@
 #include "policy_mc.h"
 #include <cstring>
 
+#include "mc_tree.h"
+
 namespace {
 
 __device__ __forceinline__ bool mc_nan(double v) { return v != v; }
 
-// the fixed tree over the MC_THREADS values of a workgroup: OP 0 sum, 1 min, 2 max.  Every lane returns the result.
-template <int OP>
-__device__ __forceinline__ double block_tree(double v, double *sh) {
-    const int tid = threadIdx.x;
-    __syncthreads();                                                  // (sh may still be read from the previous tree)
-    sh[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = MC_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            const double a = sh[tid], b = sh[tid + s];
-            sh[tid] = (OP == 0) ? a + b : (OP == 1) ? (b < a ? b : a) : (b > a ? b : a);
-        }
-        __syncthreads();
-    }
-    return sh[0];
-}
+// (block_tree and block_tree_n, the fixed trees over the MC_THREADS values of a workgroup, are mc_tree.h's)
 
 struct McHead { double n_ok, n_dom, mn, mx, sum; };
 
@@ -172,25 +158,6 @@ __global__ __launch_bounds__(MC_THREADS) void mc_final(McArgs a) {
 // Centring: c = mean and y_ref = exp(theta (mean - Jmax)) while theta (Jmax - mean) <= WC_CENTRE_MAX -- then, with y - y_ref formed as
 // y_ref expm1(theta (J - mean)), KL = theta B / sum y - log1p(A / (n y_ref)) holds its digits as theta sd(J) -> 0, where theta (m - Jmax)
 // and log Z are each far larger than their difference -- and c = Jmax, y_ref = 0 beyond (y_ref would underflow; KL is of order one there).
-
-// block_tree<0> for NQ sums at once (the same additions in the same order, NQ per barrier): sh is [NQ][MC_THREADS]
-template <int NQ>
-__device__ __forceinline__ void block_tree_n(double (&v)[NQ], double *sh) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) sh[q * MC_THREADS + tid] = v[q];
-    __syncthreads();
-    for (int s = MC_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) sh[q * MC_THREADS + tid] = sh[q * MC_THREADS + tid] + sh[q * MC_THREADS + tid + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) v[q] = sh[q * MC_THREADS];
-}
 
 struct WcHead { double n, mean, Jmax, s2, nmax, sd, klmax, kind; };
 

@@ -1,0 +1,72 @@
+// rare_event.h -- rat_policy_rare_event (include/ratilqr.h): the probability of a rare safety event by adaptive importance sampling, on the
+// device (rare_event.hip).  The process noise of rollout i is drawn from a shifted proposal, z_k = s_k + xi_k, xi_k ~ N(0, I_n), the
+// likelihood ratio rides along as logw_i = sum_k (-s_k' z_k + 1/2 s_k' s_k), and the shift s [N][n] is moved towards the event by the
+// multilevel cross-entropy method.  One adaptation iteration is
+//   re_rollout   K rollouts under s: margin M_i (rat_policy_events' M of one event), logw_i, the DomainError flag
+//   the select   launch_policy_tr (policy_mc.hip) on the margins at alpha = 1 - rho: the ceil((1 - rho) n)-th smallest M, an exact order statistic
+//   re_level     gamma = min(0, that M) and the iteration's code (0 go on, 1 gamma == 0, 2 no margin to rank, 3 not finite) -> device memory
+//   re_pass_a    n_ok, n_domain, max and min logw                                        (only when the code is 0: the host reads its 4 bytes)
+//   re_elite     replays the iteration's Philox stream: per step and component sum_E w_i xi_ik, and sum_E w_i, sum_E w_i^2, |E| over the elite
+//                E = { M_i >= gamma }, w_i = exp(logw_i - max logw); gamma and max logw are read from device memory
+//   re_update    the slots' partials in index order; s += sum_E w xi / sum_E w (= sum_E w z / sum_E w, z = s + xi); the trace row
+// and the final pass is re_rollout on a stream of its own, re_pass_a, re_pass_b (sum_A w, sum_A w^2, N_VIOL over A = { M_i > 0 }) and re_final.
+// Every sum runs in a fixed order (policy_mc.hip's: lane g of the grid takes elements g, g + T, ...; the LDS tree; the partials in the same
+// tree or in index order at the head of the next launch); no floating-point atomics: the same call returns the same bits.
+//
+// Keying.  Pass p (the final pass is p = 0, adaptation iteration j is p = j + 1) has the seed seed_p = seed + RE_PASS_STRIDE p (mod 2^64);
+// inside a pass the rollouts are keyed as rat_policy_evaluate keys them: chunks of min(K, 2^16) rollouts, chunk c under the Philox key
+// seed_p + 0x9E3779B97F4A7C15 c, counter (index within the chunk, 0, t >> 1, component), one Box-Muller transform per step pair.  With
+// n_iter == 0 and no shift the final pass therefore draws rat_policy_evaluate's noise at the same seed.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "layout.h"
+#include "policy_mc.h"
+
+#define RE_NSTAT 12           /* RAT_RE_NSTAT of the header */
+#define RE_NTRACE 4           /* RAT_RE_NTRACE */
+#define RE_MAX_ITER 32
+#define RE_MAX_N 256          /* horizon the shift's LDS copy is sized for: [N][12] doubles beside the kernel's 22 KiB of staging */
+#define RE_SLOTS 64           /* workgroups of re_elite per step pair: fixed, so that the summation order depends on K alone */
+#define RE_PASS_STRIDE 0xD1B54A32D192ED03ull
+#define RE_CHUNK_STRIDE 0x9E3779B97F4A7C15ull
+// scratch, in doubles: pass A partials [4][B] | pass B partials [3][B] | stats [12] | level: gamma, - | control: code (int), bad (int) |
+// trace [32][4] | the select's scratch [TR_SCRATCH]                  (B = MC_BLOCKS)
+#define RE_O_PA 0
+#define RE_O_PB (4 * MC_BLOCKS)
+#define RE_O_STATS (RE_O_PB + 3 * MC_BLOCKS)
+#define RE_O_LVL (RE_O_STATS + RE_NSTAT)
+#define RE_O_CTL (RE_O_LVL + 2)
+#define RE_O_TRACE (RE_O_CTL + 2)
+#define RE_O_TR (RE_O_TRACE + RE_MAX_ITER * RE_NTRACE)
+#define RE_SCRATCH (RE_O_TR + TR_SCRATCH)
+
+struct ReArgs {
+    ProblemDev pb;
+    const double *Wchol;      // [Nw][12][16] lower Cholesky factors of W(k), row-major, zero padded (rat_policy_evaluate's pack)
+    const double *xnom;       // [(N+1)][12] (open loop: only row 0 is read)
+    const double *l;          // [N][4]
+    const double *L;          // [N][4][12] or null (open loop)
+    long K, chunk;            // chunk = min(K, 2^16)
+    unsigned long long seed;  // seed_p of this pass
+    double *shift;            // [N][12] s, zero padded
+    const double *Qt;         // [16][16] in the tile as ev_eval reads it (entry (k, i) at k * 16 + i), or unused (linear event)
+    const double *at;         // [16] in the tile
+    double b;
+    int t_lo, t_hi;
+    double *margin;           // [K] M, NaN for a DomainError rollout
+    double *logw;             // [K]
+    int *dom;                 // [K]
+    double *scratch;          // [RE_SCRATCH]
+    double *part;             // [N * 12 + 3][RE_SLOTS] re_elite's partials
+    int iter;                 // adaptation iteration (re_level, re_update: the trace row)
+    int reached;              // re_final: an iteration found gamma == 0
+    int n_run;                // re_final: adaptation iterations that ran
+};
+void launch_re_rollout(const ReArgs &a, bool quad, hipStream_t s);
+// the select on the margins and re_level behind it: the code is the int at a.scratch + RE_O_CTL
+void launch_re_level(const ReArgs &a, double rho, hipStream_t s);
+// re_pass_a, re_elite, re_update
+void launch_re_adapt(const ReArgs &a, hipStream_t s);
+// re_pass_a, re_pass_b, re_final: the stats are a.scratch + RE_O_STATS
+void launch_re_final(const ReArgs &a, hipStream_t s);

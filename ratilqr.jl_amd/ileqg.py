@@ -114,6 +114,28 @@ def kl_event_bound(p, d):
     return out.value
 
 
+@dataclass
+class RareEventResult:
+    """What Context.policy_rare_event returns: the RAT_RE_* slots of the header as fields (flag: 0 OK, 1 the level never reached 0, 2 no OK
+    rollout, 3 non-finite), the shift (N, n) the final pass ran under, the trace (n_iter, 4) -- level, elite count, elite effective sample
+    size, |shift| per adaptation iteration, NaN where none ran -- and, on request, the margins and log-weights (K,) of the final pass."""
+    prob: float
+    prob_se: float
+    ess: float
+    n_viol: int
+    n_ok: int
+    n_domain: int
+    logw_max: float
+    logw_min: float
+    flag: int
+    n_iter: int
+    level: float
+    shift: np.ndarray
+    trace: np.ndarray
+    margins: np.ndarray | None = None
+    logw: np.ndarray | None = None
+
+
 class Context:
     """One rat_handle bound to one problem (device buffers sized for max_batch samples x spec_eps step sizes)."""
 
@@ -363,6 +385,35 @@ class Context:
                 r["step"] = step[sl].copy()
             return r
         return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)), margins=margins)
+
+    def policy_rare_event(self, x_nom, l, L, event, K, seed=0, shift=None, n_iter=8, rho=0.1, want_margins=False, want_logw=False):
+        """The probability of a rare safety event under the policy (x_nom, l, L) -- as policy_evaluate takes it -- by adaptive importance
+        sampling on the device (rat_policy_rare_event): the process noise is drawn from a proposal shifted by s (N, n), every rollout
+        carries its likelihood ratio, and up to n_iter multilevel cross-entropy iterations (elite share rho) move the shift towards the
+        event before the final pass estimates.  One event (halfspace, ball, quadratic_event).  shift: where the adaptation starts (None:
+        0); hand a result's shift back with n_iter=0 to estimate again at another K or seed.  LQ and power-law families, n <= 12, m <= 4.
+        Returns a RareEventResult."""
+        n, m, N = self.n, self.m, self.N
+        Q, a, b, lo, hi = event.dense(n, m, N)
+        Qc = nv.f64(Q.T) if Q is not None else None                   # column-major
+        a = nv.f64(a)
+        s_in = None
+        if shift is not None:
+            s_in = nv.f64(shift)
+            if s_in.shape != (N, n):
+                raise ValueError(f"policy_rare_event: the shift is {s_in.shape}, (N, n) = ({N}, {n}) is served")
+        K, n_iter = int(K), int(n_iter)
+        stats, s_out, trace = np.zeros(nv.RE_NSTAT), np.zeros((N, n)), np.zeros((max(n_iter, 0), nv.RE_NTRACE))
+        margins = np.zeros(max(K, 1)) if want_margins else None
+        logw = np.zeros(max(K, 1)) if want_logw else None
+        nv.check(nv.lib().rat_policy_rare_event(self.h, nv.P(nv.f64(x_nom)), nv.P(nv.f64(l)), nv.P(nv.cm3(L)) if L is not None else None,
+                                                C.c_int64(K), C.c_uint64(int(seed)), nv.P(Qc), nv.P(a), C.c_double(b), C.c_int32(lo), C.c_int32(hi),
+                                                nv.P(s_in), C.c_int32(n_iter), C.c_double(float(rho)), nv.P(stats), nv.P(s_out),
+                                                nv.P(trace) if n_iter > 0 else None, nv.P(margins), nv.P(logw)))
+        r = {k: float(stats[i]) for i, k in enumerate(nv.RE_SLOTS)}
+        for k in ("n_viol", "n_ok", "n_domain", "flag", "n_iter"):
+            r[k] = int(r[k])
+        return RareEventResult(shift=s_out, trace=trace, margins=margins, logw=logw, **r)
 
     def integrate_cost(self, x, u):
         out = C.c_double()
@@ -643,6 +694,14 @@ def evaluate_policy(problem, x, l, L=None, thetas=(), K=None, z=None, seed=0, wa
     if want_trajectories:
         raise ValueError("evaluate_policy: trajectories come with noise=UserNoise(...) only (rollout_noisy returns them for the families)")
     return _ctx(problem).policy_evaluate(x, l, L, thetas=thetas, K=K, z=z, seed=seed, want_costs=want_costs)
+
+
+def rare_event_probability(problem, x, l, L, event, K=1 << 16, seed=0, shift=None, n_iter=8, rho=0.1, want_margins=False, want_logw=False):
+    """The probability that the policy (x, l, L) violates `event`, however rare, by adaptive importance sampling on the device:
+    Context.policy_rare_event on the problem's default context.  Where policy_events counts no violation among K rollouts this still
+    returns an estimate with its standard error."""
+    return _ctx(problem).policy_rare_event(x, l, L, event, K, seed=seed, shift=shift, n_iter=n_iter, rho=rho, want_margins=want_margins,
+                                           want_logw=want_logw)
 
 
 def integrate_cost(problem, x_array, u_array):          # ileqg.jl:115-124
