@@ -2541,6 +2541,31 @@ __device__ __forceinline__ void copy_initial(const StateDev &st, const double *_
 __device__ __forceinline__ void gather_body(const StateDev &st, const int b, double *value, int *status, int *iters, int *ls_evals,
                                             double *cost, double kl_bound);
 
+// The argument block as ONE PHASE of a persistent kernel sees it.  The kernel's by-value parameter is read by scalar loads from the argument
+// segment, and the compiler issues every one of them once, at kernel entry: the bases and strides of all phases inlined into the kernel
+// are then live across the whole solve and spill (the kernel is SGPR-bound).  A phase instead takes the segment's address through an opaque
+// copy -- the scalar counterpart of the opaque lane index of sweep_body -- and builds its SweepArgs / RolloutArgs from that: what it needs
+// is loaded (from the scalar cache) at its start and dies at its end.  FusedArgs is the kernel's only parameter: offset 0 of the segment.
+// LOCAL = false: the parameter itself (the power-law family: its time loops are bound by the scalar work of pow(), and the allocator put
+// MORE spill traffic into them with phase-local arguments).
+template <bool LOCAL>
+__device__ __forceinline__ const FusedArgs &phase_args(const FusedArgs &fa) {
+    if (!LOCAL) return fa;
+    auto kp = (const __attribute__((address_space(4))) FusedArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    return *(const FusedArgs *)kp;
+}
+// The rollout's view of the batch: st / pb / op are the sweeps' (FusedArgs.sw -- one copy of the batch description on the device); only
+// the initial point, the record switches and the diagnostic buffer are the rollout's own.
+template <bool LOCAL>
+__device__ __forceinline__ RolloutArgs rollout_view(const FusedArgs &pa, const int mode) {
+    RolloutArgs ra;
+    if (!LOCAL) { ra = pa.ro; ra.mode = mode; return ra; }
+    ra.st = pa.sw.st; ra.pb = pa.sw.pb; ra.op = pa.sw.op;
+    ra.mode = mode; ra.x0 = pa.ro.x0; ra.u0 = pa.ro.u0; ra.dump = pa.ro.dump; ra.notile = pa.ro.notile; ra.multi = pa.ro.multi;
+    return ra;
+}
+
 // OCC2: the compiler is held to 256 registers so that TWO samples share a SIMD (only offered without DUALF / STG: one recursion per pass,
 // 2 KB of LDS per wave) -- the direct test of "hide a wave's dependency stalls with a second sample" for batches beyond one per SIMD.
 // MAT: the tile-free geometry with its tile records put back (rollouts write them, sweeps load them): the materialised formulation SURVEY 8d
@@ -2568,32 +2593,35 @@ __global__ __launch_bounds__(64, OCC2 ? 2 : 1) void solve_fused_kernel(FusedArgs
     //  SIMD covers the latency; 2 KB of LDS per wave)
     constexpr int FLYF = (MODEL == 1 && ((DUALF && STG && !OCC2) || (OCC2 && !DUALF && !STG)) && !MAT) ? (CTV ? 2 : 1) : 0;
     constexpr bool NT = FLYF != 0;
+    constexpr bool PL = (MODEL == 1);            // phase-local arguments (phase_args)
     // the sample's own wave initialises its state and, at the end, writes its outputs: a batch is ONE launch
     if (threadIdx.x == 0) {
-        init_state_body(st, fa.sw.op, fa.theta_in, b);
-        if (RPL) { fa.sw.rec.gen[b] = 0; fa.sw.rec.lgen[2 * b] = 0; fa.sw.rec.lgen[2 * b + 1] = 0; }     // no record yet
+        const FusedArgs &pa = phase_args<PL>(fa);
+        init_state_body(pa.sw.st, pa.sw.op, pa.theta_in, b);
+        if (RPL) { pa.sw.rec.gen[b] = 0; pa.sw.rec.lgen[2 * b] = 0; pa.sw.rec.lgen[2 * b + 1] = 0; }     // no record yet
     }
     PHASE_FENCE();
     {
-        if (NT && fa.init_x) {
-            copy_initial(st, fa.init_x, fa.init_u, fa.init_t, b);
+        const FusedArgs &pi = phase_args<PL>(fa);
+        if (NT && pi.init_x) {
+            copy_initial(pi.sw.st, pi.init_x, pi.init_u, pi.init_t, b);
         } else {
-            RolloutArgs ra = fa.ro; ra.mode = 0;
+            const RolloutArgs ra = rollout_view<PL>(pi, 0);
             rollin_body<MODEL, 0, CTV, STG, true, OCC2 ? OCC2_PREFETCH : ROLLIN_PREFETCH, NT>(ra, b, shxu, stg);
         }
         PHASE_MARK();
         PHASE_FENCE();
         PHASE_MARK();
         if (DUALF) {
-            SweepArgs sa = fa.sw; sa.mode = 6;
+            SweepArgs sa = phase_args<PL>(fa).sw; sa.mode = 6;
             sweep_dual_body<WM, false, FLYF, RPL>(sa, b, wls);
             PHASE_MARK();
             PHASE_FENCE();
-            if (threadIdx.x == 0) commit_init_body(st, b);
+            if (threadIdx.x == 0) commit_init_body(phase_args<PL>(fa).sw.st, b);
             PHASE_FENCE();
             PHASE_MARK();
         } else {
-            SweepArgs sa = fa.sw; sa.mode = 2;
+            SweepArgs sa = phase_args<PL>(fa).sw; sa.mode = 2;
             sweep_body<false, false, WM, false, OCC2 ? OCC2_SWZ : 0, FLYF>(sa, b, wls);
             PHASE_MARK();
             PHASE_FENCE();
@@ -2605,7 +2633,7 @@ __global__ __launch_bounds__(64, OCC2 ? 2 : 1) void solve_fused_kernel(FusedArgs
         const int v_stat = __atomic_load_n(&st.status[b], __ATOMIC_RELAXED), v_act = __atomic_load_n(&st.ls_active[b], __ATOMIC_RELAXED);
         if (__builtin_amdgcn_readfirstlane(v_stat) != ST_RUNNING) break;
         if (!__builtin_amdgcn_readfirstlane(v_act)) {        // step!: solve_approximate_dp!  (ileqg.jl:598-613)
-            SweepArgs sa = fa.sw; sa.mode = 0;
+            SweepArgs sa = phase_args<PL>(fa).sw; sa.mode = 0;
             sweep_body<true, false, WM, false, OCC2 ? OCC2_SWZ : 0, FLYF, false, RPL>(sa, b, wls);
             PHASE_MARK();
             PHASE_FENCE();
@@ -2613,35 +2641,39 @@ __global__ __launch_bounds__(64, OCC2 ? 2 : 1) void solve_fused_kernel(FusedArgs
             continue;
         }
         {                                                    // one candidate of line_search!  (ileqg.jl:504-581)
-            RolloutArgs ra = fa.ro; ra.mode = 1;
+            const RolloutArgs ra = rollout_view<PL>(phase_args<PL>(fa), 1);
             rollin_body<MODEL, 1, CTV, STG, true, OCC2 ? OCC2_PREFETCH : ROLLIN_PREFETCH, NT>(ra, b, shxu, stg);
             PHASE_MARK();
             PHASE_FENCE();
             PHASE_MARK();
             bool pair = DUALF;
             if (DUALF) {                                     // would accepting this candidate end solve!?  (ileqg.jl:642-653)
-                const double v_dc = *(const volatile double *)&st.d_c[b], v_mu = *(const volatile double *)&st.mu[b];
-                const int v_it = __atomic_load_n(&st.iter[b], __ATOMIC_RELAXED);            // (three loads in flight together)
+                const FusedArgs &pe = phase_args<PL>(fa);
+                const double v_dc = *(const volatile double *)&pe.sw.st.d_c[b], v_mu = *(const volatile double *)&pe.sw.st.mu[b];
+                const int v_it = __atomic_load_n(&pe.sw.st.iter[b], __ATOMIC_RELAXED);      // (three loads in flight together)
                 const double dc = readlane_f64(v_dc, 0), mu = readlane_f64(v_mu, 0);
-                const bool ends = (fa.sw.op.d > dc && mu <= fa.sw.op.mu_min) || __builtin_amdgcn_readfirstlane(v_it) == fa.sw.op.iter_max;
+                const bool ends = (pe.sw.op.d > dc && mu <= pe.sw.op.mu_min) || __builtin_amdgcn_readfirstlane(v_it) == pe.sw.op.iter_max;
                 pair = !ends;
             }
             if (pair) {
-                SweepArgs sa = fa.sw; sa.mode = 7;
+                SweepArgs sa = phase_args<PL>(fa).sw; sa.mode = 7;
                 if (!(RPL && replay_dual_body(sa, b, wls))) sweep_dual_body<WM, true, FLYF, RPL>(sa, b, wls);
             } else {
-                SweepArgs sa = fa.sw; sa.mode = 1;
+                SweepArgs sa = phase_args<PL>(fa).sw; sa.mode = 1;
                 if (!(RPL && replay_eval_body(sa, b, wls))) sweep_body<false, false, WM, true, OCC2 ? OCC2_SWZ : 0, FLYF>(sa, b, wls);
             }
             PHASE_MARK();
             PHASE_FENCE();
-            if (threadIdx.x == 0) ls_select_body(st, fa.sw.op, b, nullptr);
+            if (threadIdx.x == 0) { const FusedArgs &pa = phase_args<PL>(fa); ls_select_body(pa.sw.st, pa.sw.op, b, nullptr); }
             PHASE_FENCE();
             PHASE_MARK();
         }
     }
     PHASE_FENCE();
-    if (threadIdx.x == 0) gather_body(st, b, fa.out_value, fa.out_status, fa.out_iters, fa.out_ls, fa.out_cost, fa.kl_bound);
+    if (threadIdx.x == 0) {
+        const FusedArgs &pa = phase_args<PL>(fa);
+        gather_body(pa.sw.st, b, pa.out_value, pa.out_status, pa.out_iters, pa.out_ls, pa.out_cost, pa.kl_bound);
+    }
 }
 
 
