@@ -821,6 +821,20 @@ static rat_rc user_noise_args_ok(const char *who, int n, int m, int npn, int npu
     return RAT_OK;
 }
 
+// A compiled module on the current device and its kernel `name` (and `name2`, where a module carries two); a module that lacks one is
+// unloaded again.  What a caller does with the module it replaces comes after, at the caller.
+static rat_rc load_module_function(const std::shared_ptr<const std::vector<char>> &code, const char *name, const char *who, hipModule_t *mod_out,
+                                   hipFunction_t *fn, const char *name2 = nullptr, hipFunction_t *fn2 = nullptr) {
+    hipModule_t mod = nullptr;
+    HIPCHK(hipModuleLoadData(&mod, code->data()));
+    if (hipModuleGetFunction(fn, mod, name) != hipSuccess || (name2 && hipModuleGetFunction(fn2, mod, name2) != hipSuccess)) {
+        (void)hipModuleUnload(mod);
+        return fail(RAT_ERR_HIP, std::string(who) + ": the compiled module lacks its kernel" + (name2 ? "s" : ""));
+    }
+    *mod_out = mod;
+    return RAT_OK;
+}
+
 extern "C" rat_rc rat_user_noise_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms) {
     if (!source) return fail(RAT_ERR_ARG, "null");
     rat_rc rc = user_noise_args_ok("rat_user_noise_check", n, m, normals, uniforms);
@@ -851,11 +865,7 @@ extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32
     if ((rc = build_w_tables(h, pb, W, n, N, "rat_problem_set_source", wt))) return rc;
     hipModule_t mod = nullptr;
     hipFunction_t fr = nullptr, fl = nullptr;
-    HIPCHK(hipModuleLoadData(&mod, code->data()));
-    if (hipModuleGetFunction(&fr, mod, "rat_src_rollout") != hipSuccess || hipModuleGetFunction(&fl, mod, "rat_src_linearize") != hipSuccess) {
-        (void)hipModuleUnload(mod);
-        return fail(RAT_ERR_HIP, "rat_problem_set_source: the compiled module lacks its kernels");
-    }
+    if ((rc = load_module_function(code, "rat_src_rollout", "rat_problem_set_source", &mod, &fr, "rat_src_linearize", &fl))) return rc;
     // the new tables go to a list of their own: the previous problem's buffers are released only once every upload has succeeded
     std::vector<void *> allocs;
     auto undo = [&](rat_rc r) { free_list(allocs); (void)hipModuleUnload(mod); return r; };
@@ -1911,6 +1921,74 @@ extern "C" rat_rc rat_rollout_feedback(rat_handle h, const double *xbar, const d
 static bool host_chol_lower(int n, const double *A, double *Lo);
 template <class T> static rat_rc grow(T **p, size_t *cap, size_t need);
 
+// ---- the host path the policy analyses share: the policy pack, the chunks and their Philox keys, the rollout launches --------------------
+// Rollouts run in chunks of at most 2^16 (injected draws and trajectories are staged a chunk at a time); chunk c of a family or N(0, W)
+// source rollout draws under the Philox key seed + MC_CHUNK_STRIDE c.  Every analysis that claims another's bits takes both from here.
+static const uint64_t MC_CHUNK_STRIDE = 0x9E3779B97F4A7C15ull;
+static_assert(MC_CHUNK_STRIDE == RE_CHUNK_STRIDE, "rare_event.hip keys its chunks on the device as chunk_seed does on the host");
+static int64_t mc_chunk(int64_t K) { return std::min<int64_t>(K, 1 << 16); }
+static uint64_t chunk_seed(uint64_t seed, int64_t k0, int64_t chunk) { return seed + MC_CHUNK_STRIDE * (uint64_t)(k0 / chunk); }
+
+// The policy and the lower Cholesky factors of W(k) (MvNormal sampling unwhitens with them) as the rollout kernels read them, laid out for
+// one upload: Wchol | x_nom | l | L.  Families and source models: the padded 12 + 4 layout, a factor a 12 x 16 row-major tile; general
+// sizes: dense column-major.  L == NULL is the open loop: x_nom is x_0 alone and no L follows.  Without with_wchol (rat_user_noise draws
+// the disturbance, W is not read) the pack starts at x_nom.
+struct PolicyPack {
+    std::vector<double> data;
+    size_t o_x = 0, o_l = 0, o_L = 0;
+};
+static rat_rc pack_policy(rat_handle h, const double *x_nom, const double *l, const double *L, bool with_wchol, PolicyPack *pk) {
+    const int n = h->n, m = h->m, N = h->N, Nw = with_wchol ? (h->W_tv ? N : 1) : 0;
+    const size_t wsz = h->wide ? (size_t)n * n : 192;
+    std::vector<double> &pack = pk->data, Lc((size_t)n * n), xp, up, Lp;
+    pack.assign(Nw * wsz, 0.0);
+    for (int k = 0; k < Nw; ++k) {
+        if (!host_chol_lower(n, h->hW.data() + (size_t)k * n * n, Lc.data()))
+            return fail(RAT_ERR_ARG, "W(k) is not positive definite (MvNormal would throw)");
+        for (int i = 0; i < n; ++i) for (int jj = 0; jj <= i; ++jj) pack[k * wsz + (h->wide ? i + n * jj : i * 16 + jj)] = Lc[i + n * jj];
+    }
+    if (h->wide) {
+        xp.assign(x_nom, x_nom + (L ? (size_t)(N + 1) * n : (size_t)n)); up.assign(l, l + (size_t)N * m);
+        if (L) Lp.assign(L, L + (size_t)N * m * n);
+    } else {
+        if (L) { pad_x(h, x_nom, xp); pad_L(h, L, Lp); }
+        else { xp.assign((size_t)(N + 1) * XSTR, 0.0); for (int i = 0; i < n; ++i) xp[i] = x_nom[i]; }
+        pad_u(h, l, up);
+    }
+    pk->o_x = pack.size(); pack.insert(pack.end(), xp.begin(), xp.end());
+    pk->o_l = pack.size(); pack.insert(pack.end(), up.begin(), up.end());
+    pk->o_L = pack.size(); pack.insert(pack.end(), Lp.begin(), Lp.end());
+    return RAT_OK;
+}
+
+// where a pack's parts lie on the device: one upload at `base` (its own offsets, or the ones McReplay kept), or rat_rollout_noisy's four
+struct PolicyDev { const double *Wchol, *x, *l, *L; };
+static PolicyDev policy_dev(const double *base, size_t o_x, size_t o_l, size_t o_L, bool has_L) {
+    return PolicyDev{base, base + o_x, base + o_l, has_L ? base + o_L : nullptr};
+}
+
+// rollouts k0 .. k0 + kc of a family on the tile path (noisy_rollout_kernel), enqueued; d_z: the chunk's injected normals, NULL for the
+// generator; x_out / u_out / cost / dom: where this chunk's results go
+static void launch_noisy_chunk(rat_handle h, const PolicyDev &p, int64_t k0, int64_t kc, int64_t chunk, uint64_t seed, const double *d_z,
+                               double *x_out, double *u_out, double *cost, int *dom) {
+    NoisyArgs a;
+    a.pb = h->pb; a.Wchol = p.Wchol; a.xnom = p.x; a.l = p.l; a.L = p.L; a.K = (long)kc; a.z = d_z; a.seed = chunk_seed(seed, k0, chunk);
+    a.x_out = x_out; a.u_out = u_out; a.cost = cost; a.dom = dom;
+    launch_noisy_rollout(a, h->stream);
+}
+// the same for a source model under its rat_user_noise (the handle's src_un): the generator counts rollouts globally (j0 = k0), so every
+// chunk runs under the caller's seed; d_over: the device address of the overdraw flag
+static rat_rc launch_user_noisy_chunk(rat_handle h, const PolicyDev &p, int64_t k0, int64_t kc, uint64_t seed, const double *d_zn,
+                                      const double *d_zu, double *x_out, double *u_out, double *cost, int *d_over) {
+    SrcUserNoisyArgs a;
+    a.xnom = p.x; a.l = p.l; a.L = p.L; a.zn = d_zn; a.zu = d_zu;
+    a.K = (long)kc; a.j0 = (long)k0; a.N = h->N; a.tpw = h->src_mc_tpw; a.seed = seed; a.cost = cost;
+    a.x_out = x_out; a.u_out = u_out; a.p = h->d_src_p; a.overdraw = d_over;
+    void *args[] = {&a};
+    HIPCHK(hipModuleLaunchKernel(h->src_un, (unsigned)((kc + a.tpw - 1) / a.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+    return RAT_OK;
+}
+
 // simulate_dynamics(problem, x_0 | x_array, u_array | (l_array, L_array), rng)  -- ileqg.jl:44-55, :94-109
 extern "C" rat_rc rat_rollout_noisy(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
                                     const double *z, uint64_t seed, double *x_out, double *u_out, double *cost_out,
@@ -1920,20 +1998,21 @@ extern "C" rat_rc rat_rollout_noisy(rat_handle h, const double *x_nom, const dou
     if (K < 1) return fail(RAT_ERR_ARG, "K must be positive");
     if (h->pb.model == RAT_MODEL_SOURCE) return fail(RAT_ERR_UNSUPPORTED, "rat_rollout_noisy: not available for source models");
     HIPCHK(hipSetDevice(h->device));
-    const int n = h->n, m = h->m, N = h->N, Nw = h->W_tv ? N : 1;
+    const int n = h->n, m = h->m, N = h->N;
+    PolicyPack pk;
+    rat_rc rc;
+    if ((rc = pack_policy(h, x_nom, l, L, true, &pk))) return rc;
+    const double *pd = pk.data.data();
+    const size_t n_wc = pk.o_x, n_x = pk.o_l - pk.o_x, n_l = pk.o_L - pk.o_l, n_L = pk.data.size() - pk.o_L;   // (a temporary per part)
     if (h->wide) {                       // general size: dense column-major in and out, one workgroup per rollout
-        std::vector<double> Lw((size_t)Nw * n * n, 0.0);
-        for (int k = 0; k < Nw; ++k)
-            if (!host_chol_lower(n, h->hW.data() + (size_t)k * n * n, Lw.data() + (size_t)k * n * n))
-                return fail(RAT_ERR_ARG, "W(k) is not positive definite (MvNormal would throw)");
         const size_t sn = n, sm = m, sN = N, sK = (size_t)K;
         WideTmp t;
         WideOpArgs a = wide_op_args(h, WOP_NOISY, (long)K);
-        WIDE_NEED(a.xbar = t.in(x_nom, L ? (sN + 1) * sn : sn)); WIDE_NEED(a.l = t.in(l, sN * sm));
-        if (L) WIDE_NEED(a.L = t.in(L, sN * sm * sn));
+        WIDE_NEED(a.xbar = t.in(pd + pk.o_x, n_x)); WIDE_NEED(a.l = t.in(pd + pk.o_l, n_l));
+        if (L) WIDE_NEED(a.L = t.in(pd + pk.o_L, n_L));
         if (z) WIDE_NEED(a.z = t.in(z, sK * sN * sn));
         a.seed = seed;
-        WIDE_NEED(a.Wchol = t.in(Lw.data(), Lw.size()));
+        WIDE_NEED(a.Wchol = t.in(pd, n_wc));
         if (x_out) WIDE_NEED(a.x_out = t.out<double>(sK * (sN + 1) * sn));
         if (u_out) WIDE_NEED(a.u_out = t.out<double>(sK * sN * sm));
         if (cost_out) WIDE_NEED(a.cost_out = t.out<double>(sK));
@@ -1943,46 +2022,31 @@ extern "C" rat_rc rat_rollout_noisy(rat_handle h, const double *x_nom, const dou
         if (domain_fail) *domain_fail = 0;
         return RAT_OK;
     }
-    // lower Cholesky factors of W(k) (MvNormal sampling unwhitens with them), padded to 12 x 16 row-major
-    std::vector<double> Lc((size_t)n * n), Wc((size_t)Nw * 192, 0.0);
-    for (int k = 0; k < Nw; ++k) {
-        if (!host_chol_lower(n, h->hW.data() + (size_t)k * n * n, Lc.data()))
-            return fail(RAT_ERR_ARG, "W(k) is not positive definite (MvNormal would throw)");
-        for (int i = 0; i < n; ++i) for (int jj = 0; jj <= i; ++jj) Wc[(size_t)k * 192 + i * 16 + jj] = Lc[i + n * jj];
-    }
-    std::vector<double> xp, up, Lp;
-    if (L) { pad_x(h, x_nom, xp); pad_L(h, L, Lp); }
-    else { xp.assign((size_t)(N + 1) * XSTR, 0.0); for (int i = 0; i < n; ++i) xp[i] = x_nom[i]; }
-    pad_u(h, l, up);
-    const int64_t chunk = std::min<int64_t>(K, 1 << 16);
+    const int64_t chunk = mc_chunk(K);
     double *d_wc = nullptr, *d_x = nullptr, *d_l = nullptr, *d_L = nullptr, *d_z = nullptr, *d_xo = nullptr, *d_uo = nullptr, *d_c = nullptr;
     int *d_dom = nullptr;
     auto freeall = [&]() { for (void *q : {(void *)d_wc, (void *)d_x, (void *)d_l, (void *)d_L, (void *)d_z, (void *)d_xo, (void *)d_uo, (void *)d_c, (void *)d_dom}) if (q) (void)hipFree(q); };
 #define NALLOC(ptr, count) do { if (hipMalloc((void **)&(ptr), (size_t)(count) * sizeof(*(ptr))) != hipSuccess) { freeall(); return fail(RAT_ERR_HIP, "hipMalloc failed"); } } while (0)
-    NALLOC(d_wc, Wc.size()); NALLOC(d_x, xp.size()); NALLOC(d_l, up.size());
-    if (L) NALLOC(d_L, Lp.size());
+    NALLOC(d_wc, n_wc); NALLOC(d_x, n_x); NALLOC(d_l, n_l);
+    if (L) NALLOC(d_L, n_L);
     if (z) NALLOC(d_z, (size_t)chunk * N * n);
     if (x_out) NALLOC(d_xo, (size_t)chunk * (N + 1) * XSTR);
     if (u_out) NALLOC(d_uo, (size_t)chunk * N * USTR);
     NALLOC(d_c, chunk); NALLOC(d_dom, chunk);
 #undef NALLOC
-    rat_rc rc = RAT_OK;
     auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == RAT_OK) rc = fail(RAT_ERR_HIP, hipGetErrorString(e)); };
-    chk(hipMemcpy(d_wc, Wc.data(), Wc.size() * 8, hipMemcpyHostToDevice));
-    chk(hipMemcpy(d_x, xp.data(), xp.size() * 8, hipMemcpyHostToDevice));
-    chk(hipMemcpy(d_l, up.data(), up.size() * 8, hipMemcpyHostToDevice));
-    if (L) chk(hipMemcpy(d_L, Lp.data(), Lp.size() * 8, hipMemcpyHostToDevice));
+    chk(hipMemcpy(d_wc, pd, n_wc * 8, hipMemcpyHostToDevice));
+    chk(hipMemcpy(d_x, pd + pk.o_x, n_x * 8, hipMemcpyHostToDevice));
+    chk(hipMemcpy(d_l, pd + pk.o_l, n_l * 8, hipMemcpyHostToDevice));
+    if (L) chk(hipMemcpy(d_L, pd + pk.o_L, n_L * 8, hipMemcpyHostToDevice));
+    const PolicyDev dev{d_wc, d_x, d_l, d_L};
     std::vector<double> xo, uo, co((size_t)chunk);
     std::vector<int> dm((size_t)chunk);
     int any_dom = 0;
     for (int64_t k0 = 0; k0 < K && rc == RAT_OK; k0 += chunk) {
         const int64_t kc = std::min(chunk, K - k0);
         if (z) chk(hipMemcpy(d_z, z + (size_t)k0 * N * n, (size_t)kc * N * n * 8, hipMemcpyHostToDevice));
-        NoisyArgs a;
-        a.pb = h->pb; a.Wchol = d_wc; a.xnom = d_x; a.l = d_l; a.L = d_L; a.K = (long)kc; a.z = d_z;
-        a.seed = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(k0 / chunk);       // distinct Philox keys per chunk
-        a.x_out = d_xo; a.u_out = d_uo; a.cost = d_c; a.dom = d_dom;
-        launch_noisy_rollout(a, h->stream);
+        launch_noisy_chunk(h, dev, k0, kc, chunk, seed, d_z, d_xo, d_uo, d_c, d_dom);
         chk(hipStreamSynchronize(h->stream));
         chk(hipMemcpy(co.data(), d_c, (size_t)kc * 8, hipMemcpyDeviceToHost));
         chk(hipMemcpy(dm.data(), d_dom, (size_t)kc * 4, hipMemcpyDeviceToHost));
@@ -2008,108 +2072,35 @@ extern "C" rat_rc rat_rollout_noisy(rat_handle h, const double *x_nom, const dou
     return rc;
 }
 
-// K rollouts as rat_rollout_noisy runs them, reduced on the device (policy_mc.hip): mean, spread, extremes and the entropic risk
-// (1/theta) log E exp(theta J) that iLEQG minimises.  Every buffer is scratch of the handle; only the statistics (and, on request, the K
-// costs) come back.  The families and general sizes run noisy_rollout_kernel / WOP_NOISY unchanged -- chunks, Philox keys and all, so
-// cost_out is rat_rollout_noisy's bit for bit -- and source models run rat_src_noisy_rollout, a module of its own (source_noisy.h) that the
-// first evaluation of the problem compiles.
-extern "C" rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K, const double *z,
-                                      uint64_t seed, const double *theta, int32_t n_theta, double *stats, double *risk, double *risk_se,
-                                      double *cost_out) {
-    if (n_theta < 0 || n_theta > MC_MAX_THETA) return fail(RAT_ERR_ARG, "rat_policy_evaluate: n_theta must be in 0 .. 16");
-    if (n_theta > 0 && !theta) return fail(RAT_ERR_ARG, "rat_policy_evaluate: theta is null");
+// What rat_policy_evaluate and rat_policy_evaluate_noise share around their rollout loops: what the arguments alone decide, ...
+static rat_rc policy_eval_args_ok(const char *who, const double *theta, int32_t n_theta, int64_t K) {
+    const std::string F = std::string(who) + ": ";
+    if (n_theta < 0 || n_theta > MC_MAX_THETA) return fail(RAT_ERR_ARG, F + "n_theta must be in 0 .. 16");
+    if (n_theta > 0 && !theta) return fail(RAT_ERR_ARG, F + "theta is null");
     for (int i = 0; i < n_theta; ++i)
-        if (!(theta[i] >= 0.0)) return fail(RAT_ERR_ARG, "rat_policy_evaluate: every theta must be >= 0");
-    if (K < 1) return fail(RAT_ERR_ARG, "rat_policy_evaluate: K must be positive");
-    if (K > ((int64_t)1 << 27)) return fail(RAT_ERR_ARG, "rat_policy_evaluate: K must be at most 2^27 (the costs stay on the device, 8 bytes each)");
-    if (!h || !x_nom || !l || !stats) return fail(RAT_ERR_ARG, "null");
-    if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
-    HIPCHK(hipSetDevice(h->device));
-    const int n = h->n, m = h->m, N = h->N, Nw = h->W_tv ? N : 1;
-    const bool source = !h->wide && h->pb.model == RAT_MODEL_SOURCE;
-    // the policy and the lower Cholesky factors of W(k), packed for one upload: Wchol | x_nom | l | L (dense column-major at general
-    // size, the padded 12 + 4 layout otherwise)
-    std::vector<double> pack;
-    size_t o_x = 0, o_l = 0, o_L = 0;
-    if (h->wide) {
-        pack.assign((size_t)Nw * n * n, 0.0);
-        for (int k = 0; k < Nw; ++k)
-            if (!host_chol_lower(n, h->hW.data() + (size_t)k * n * n, pack.data() + (size_t)k * n * n))
-                return fail(RAT_ERR_ARG, "W(k) is not positive definite (MvNormal would throw)");
-        o_x = pack.size(); pack.insert(pack.end(), x_nom, x_nom + (L ? (size_t)(N + 1) * n : (size_t)n));
-        o_l = pack.size(); pack.insert(pack.end(), l, l + (size_t)N * m);
-        o_L = pack.size(); if (L) pack.insert(pack.end(), L, L + (size_t)N * m * n);
-    } else {
-        std::vector<double> Lc((size_t)n * n), xp, up, Lp;
-        pack.assign((size_t)Nw * 192, 0.0);
-        for (int k = 0; k < Nw; ++k) {
-            if (!host_chol_lower(n, h->hW.data() + (size_t)k * n * n, Lc.data()))
-                return fail(RAT_ERR_ARG, "W(k) is not positive definite (MvNormal would throw)");
-            for (int i = 0; i < n; ++i) for (int jj = 0; jj <= i; ++jj) pack[(size_t)k * 192 + i * 16 + jj] = Lc[i + n * jj];
-        }
-        if (L) { pad_x(h, x_nom, xp); pad_L(h, L, Lp); }
-        else { xp.assign((size_t)(N + 1) * XSTR, 0.0); for (int i = 0; i < n; ++i) xp[i] = x_nom[i]; }
-        pad_u(h, l, up);
-        o_x = pack.size(); pack.insert(pack.end(), xp.begin(), xp.end());
-        o_l = pack.size(); pack.insert(pack.end(), up.begin(), up.end());
-        o_L = pack.size(); pack.insert(pack.end(), Lp.begin(), Lp.end());
-    }
-    const int64_t chunk = std::min<int64_t>(K, 1 << 16);         // (rat_rollout_noisy's chunks: injected normals are staged chunk by chunk)
+        if (!(theta[i] >= 0.0)) return fail(RAT_ERR_ARG, F + "every theta must be >= 0");
+    if (K < 1) return fail(RAT_ERR_ARG, F + "K must be positive");
+    if (K > ((int64_t)1 << 27)) return fail(RAT_ERR_ARG, F + "K must be at most 2^27 (the costs stay on the device, 8 bytes each)");
+    return RAT_OK;
+}
+
+// ... the handle's scratch for the pack, the K costs and the reduction: allocated by the first call, grown on demand, kept until
+// rat_destroy (a buffer that grows is freed first: every earlier call has finished).  The caller grows the rest, then uploads the pack.
+static rat_rc policy_eval_scratch(rat_handle h, const PolicyPack &pk, int64_t K) {
     rat_rc rc;
-    if (source && !h->src_noisy) {                                // the first evaluation of this source problem compiles its rollout kernel
-        std::shared_ptr<const std::vector<char>> code;
-        std::string log;
-        if ((rc = src_compile_noisy(h->src_text.c_str(), n, m, h->src_arch_name, &code, &log))) return fail(rc, log);
-        hipModule_t mod = nullptr;
-        hipFunction_t fn = nullptr;
-        HIPCHK(hipModuleLoadData(&mod, code->data()));
-        if (hipModuleGetFunction(&fn, mod, "rat_src_noisy_rollout") != hipSuccess) {
-            (void)hipModuleUnload(mod);
-            return fail(RAT_ERR_HIP, "rat_policy_evaluate: the compiled module lacks its kernel");
-        }
-        h->src_noisy_mod = mod; h->src_noisy = fn;
-    }
-    // the handle's scratch: allocated by the first call, grown on demand, kept until rat_destroy (a buffer that grows is freed first:
-    // every earlier call has finished, the entry point is synchronous)
-    const size_t one = 1;
     h->mc_cost_K = 0;                                             // (d_mc_cost is about to be regrown or overwritten)
     h->mc_rec.kind = 0;
     size_t cap_red = h->d_mc_red ? MC_SCRATCH : 0;
-    if ((rc = grow(&h->d_mc_in, &h->cap_mc_in, pack.size()))) return rc;
-    if ((rc = grow(&h->d_mc_cost, &h->cap_mc_cost, std::max((size_t)K, one)))) return rc;
-    if ((rc = grow(&h->d_mc_red, &cap_red, (size_t)MC_SCRATCH))) return rc;
-    if (!source && !h->wide && (rc = grow(&h->d_mc_dom, &h->cap_mc_dom, (size_t)K))) return rc;
-    if (z && (rc = grow(&h->d_mc_z, &h->cap_mc_z, (size_t)chunk * N * n))) return rc;
-    HIPCHK(hipMemcpy(h->d_mc_in, pack.data(), pack.size() * 8, hipMemcpyHostToDevice));
-    const double *d_wc = h->d_mc_in, *d_x = h->d_mc_in + o_x, *d_l = h->d_mc_in + o_l, *d_L = L ? h->d_mc_in + o_L : nullptr;
-    int *d_dom = (source || h->wide) ? nullptr : h->d_mc_dom;
-    // general sizes with the generator: one launch, as rat_rollout_noisy runs it (the rollout index is the Philox counter)
-    const int64_t step = (h->wide && !z) ? K : chunk;
-    for (int64_t k0 = 0; k0 < K; k0 += step) {
-        const int64_t kc = std::min(step, K - k0);
-        if (z) {
-            HIPCHK(hipStreamSynchronize(h->stream));              // (the previous chunk's rollouts read the staging area)
-            HIPCHK(hipMemcpy(h->d_mc_z, z + (size_t)k0 * N * n, (size_t)kc * N * n * 8, hipMemcpyHostToDevice));
-        }
-        const uint64_t cseed = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(k0 / chunk);     // distinct Philox keys per chunk
-        if (h->wide) {
-            WideOpArgs a = wide_op_args(h, WOP_NOISY, (long)kc);
-            a.xbar = d_x; a.l = d_l; a.L = d_L; a.z = z ? h->d_mc_z : nullptr; a.seed = seed; a.Wchol = d_wc;
-            a.cost_out = h->d_mc_cost + k0;
-            HIPCHK(launch_wide_op(a, h->stream));
-        } else if (source) {
-            SrcNoisyArgs a;
-            a.Wchol = d_wc; a.xnom = d_x; a.l = d_l; a.L = d_L; a.z = z ? h->d_mc_z : nullptr; a.K = (long)kc; a.N = N; a.W_tv = h->W_tv;
-            a.tpw = h->src_mc_tpw; a.seed = cseed; a.cost = h->d_mc_cost + k0; a.p = h->d_src_p;
-            void *args[] = {&a};
-            HIPCHK(hipModuleLaunchKernel(h->src_noisy, (unsigned)((kc + a.tpw - 1) / a.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
-        } else {
-            NoisyArgs a;
-            a.pb = h->pb; a.Wchol = d_wc; a.xnom = d_x; a.l = d_l; a.L = d_L; a.K = (long)kc; a.z = z ? h->d_mc_z : nullptr;
-            a.seed = cseed; a.x_out = nullptr; a.u_out = nullptr; a.cost = h->d_mc_cost + k0; a.dom = d_dom + k0;
-            launch_noisy_rollout(a, h->stream);
-        }
-    }
+    if ((rc = grow(&h->d_mc_in, &h->cap_mc_in, pk.data.size()))) return rc;
+    if ((rc = grow(&h->d_mc_cost, &h->cap_mc_cost, std::max<size_t>((size_t)K, 1)))) return rc;
+    return grow(&h->d_mc_red, &cap_red, (size_t)MC_SCRATCH);
+}
+
+// ... and behind the rollouts: the K costs reduced (d_dom: the families' DomainError flags or NULL), statistics and costs copied out, one
+// host wait, the overdraw flag of a rat_user_noise evaluation (rec.kind == 2), and rec kept: what a replay needs to run these rollouts again
+static rat_rc policy_eval_finish(rat_handle h, const int *d_dom, const rat_handle_s::McReplay &rec, const double *theta,
+                                 int32_t n_theta, double *stats, double *risk, double *risk_se, double *cost_out) {
+    const int64_t K = rec.K;
     McArgs ma;
     memset(&ma, 0, sizeof(ma));
     ma.cost = h->d_mc_cost; ma.dom = d_dom; ma.K = (long)K; ma.n_theta = n_theta; ma.scratch = h->d_mc_red;
@@ -2120,18 +2111,80 @@ extern "C" rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const d
     HIPCHK(hipMemcpyAsync(out, h->d_mc_red + (MC_P1 + MC_P2) * MC_BLOCKS, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     if (cost_out) HIPCHK(hipMemcpyAsync(cost_out, h->d_mc_cost, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    if (rec.kind == 2 && *(volatile int *)h->h_un_over != 0)      // after the wait: a step that drew more than the caller declared
+        return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: a step drew more than was declared (normals_per_step = " + std::to_string(rec.npn) +
+                                 ", uniforms_per_step = " + std::to_string(rec.npu) + "): the overdrawn values were NaN");
     h->mc_cost_K = K;
-    {   // what rat_policy_worst_case_trajectory needs to run these rollouts again
-        rat_handle_s::McReplay &r = h->mc_rec;
-        r.kind = h->wide ? 3 : (source ? 4 : 1); r.injected = z != nullptr; r.has_L = L != nullptr; r.seed = seed; r.K = K; r.npn = r.npu = 0;
-        r.o_x = o_x; r.o_l = o_l; r.o_L = o_L; r.n = n; r.m = m; r.N = N; r.model = h->wide ? -1 : h->pb.model; r.W_tv = h->W_tv;
-    }
+    h->mc_rec = rec;
     for (int i = 0; i < RAT_MC_NSTAT; ++i) stats[i] = out[i];
     for (int i = 0; i < n_theta; ++i) {
         if (risk) risk[i] = out[8 + i];
         if (risk_se) risk_se[i] = out[8 + MC_MAX_THETA + i];
     }
     return RAT_OK;
+}
+
+// K rollouts as rat_rollout_noisy runs them, reduced on the device (policy_mc.hip): mean, spread, extremes and the entropic risk
+// (1/theta) log E exp(theta J) that iLEQG minimises.  Every buffer is scratch of the handle; only the statistics (and, on request, the K
+// costs) come back.  The families and general sizes run noisy_rollout_kernel / WOP_NOISY unchanged -- chunks, Philox keys and all, so
+// cost_out is rat_rollout_noisy's bit for bit -- and source models run rat_src_noisy_rollout, a module of its own (source_noisy.h) that the
+// first evaluation of the problem compiles.
+extern "C" rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K, const double *z,
+                                      uint64_t seed, const double *theta, int32_t n_theta, double *stats, double *risk, double *risk_se,
+                                      double *cost_out) {
+    rat_rc rc;
+    if ((rc = policy_eval_args_ok("rat_policy_evaluate", theta, n_theta, K))) return rc;
+    if (!h || !x_nom || !l || !stats) return fail(RAT_ERR_ARG, "null");
+    if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
+    HIPCHK(hipSetDevice(h->device));
+    const int n = h->n, m = h->m, N = h->N;
+    const bool source = !h->wide && h->pb.model == RAT_MODEL_SOURCE;
+    PolicyPack pk;
+    if ((rc = pack_policy(h, x_nom, l, L, true, &pk))) return rc;
+    const int64_t chunk = mc_chunk(K);                            // (injected normals are staged chunk by chunk)
+    if (source && !h->src_noisy) {                                // the first evaluation of this source problem compiles its rollout kernel
+        std::shared_ptr<const std::vector<char>> code;
+        std::string log;
+        if ((rc = src_compile_noisy(h->src_text.c_str(), n, m, h->src_arch_name, &code, &log))) return fail(rc, log);
+        hipModule_t mod = nullptr;
+        hipFunction_t fn = nullptr;
+        if ((rc = load_module_function(code, "rat_src_noisy_rollout", "rat_policy_evaluate", &mod, &fn))) return rc;
+        h->src_noisy_mod = mod; h->src_noisy = fn;
+    }
+    if ((rc = policy_eval_scratch(h, pk, K))) return rc;
+    if (!source && !h->wide && (rc = grow(&h->d_mc_dom, &h->cap_mc_dom, (size_t)K))) return rc;
+    if (z && (rc = grow(&h->d_mc_z, &h->cap_mc_z, (size_t)chunk * N * n))) return rc;
+    HIPCHK(hipMemcpy(h->d_mc_in, pk.data.data(), pk.data.size() * 8, hipMemcpyHostToDevice));
+    const PolicyDev dev = policy_dev(h->d_mc_in, pk.o_x, pk.o_l, pk.o_L, L != nullptr);
+    int *d_dom = (source || h->wide) ? nullptr : h->d_mc_dom;
+    // general sizes with the generator: one launch, as rat_rollout_noisy runs it (the rollout index is the Philox counter)
+    const int64_t step = (h->wide && !z) ? K : chunk;
+    for (int64_t k0 = 0; k0 < K; k0 += step) {
+        const int64_t kc = std::min(step, K - k0);
+        if (z) {
+            HIPCHK(hipStreamSynchronize(h->stream));              // (the previous chunk's rollouts read the staging area)
+            HIPCHK(hipMemcpy(h->d_mc_z, z + (size_t)k0 * N * n, (size_t)kc * N * n * 8, hipMemcpyHostToDevice));
+        }
+        const double *d_z = z ? h->d_mc_z : nullptr;
+        if (h->wide) {
+            WideOpArgs a = wide_op_args(h, WOP_NOISY, (long)kc);
+            a.xbar = dev.x; a.l = dev.l; a.L = dev.L; a.z = d_z; a.seed = seed; a.Wchol = dev.Wchol;
+            a.cost_out = h->d_mc_cost + k0;
+            HIPCHK(launch_wide_op(a, h->stream));
+        } else if (source) {
+            SrcNoisyArgs a;
+            a.Wchol = dev.Wchol; a.xnom = dev.x; a.l = dev.l; a.L = dev.L; a.z = d_z; a.K = (long)kc; a.N = N; a.W_tv = h->W_tv;
+            a.tpw = h->src_mc_tpw; a.seed = chunk_seed(seed, k0, chunk); a.cost = h->d_mc_cost + k0; a.p = h->d_src_p;
+            void *args[] = {&a};
+            HIPCHK(hipModuleLaunchKernel(h->src_noisy, (unsigned)((kc + a.tpw - 1) / a.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+        } else {
+            launch_noisy_chunk(h, dev, k0, kc, chunk, seed, d_z, nullptr, nullptr, h->d_mc_cost + k0, d_dom + k0);
+        }
+    }
+    rat_handle_s::McReplay rec;
+    rec.kind = h->wide ? 3 : (source ? 4 : 1); rec.injected = z != nullptr; rec.has_L = L != nullptr; rec.seed = seed; rec.K = K;
+    rec.o_x = pk.o_x; rec.o_l = pk.o_l; rec.o_L = pk.o_L; rec.n = n; rec.m = m; rec.N = N; rec.model = h->wide ? -1 : h->pb.model; rec.W_tv = h->W_tv;
+    return policy_eval_finish(h, d_dom, rec, theta, n_theta, stats, risk, risk_se, cost_out);
 }
 
 // rat_policy_evaluate for a source model whose disturbance is the user's rat_user_noise (source_user_noise.h) instead of N(0, W(k)): the
@@ -2141,19 +2194,14 @@ extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, c
                                             int32_t normals_per_step, int32_t uniforms_per_step, const double *zn, const double *zu,
                                             uint64_t seed, const double *theta, int32_t n_theta, double *stats, double *risk,
                                             double *risk_se, double *cost_out, double *x_out, double *u_out) {
-    if (n_theta < 0 || n_theta > MC_MAX_THETA) return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: n_theta must be in 0 .. 16");
-    if (n_theta > 0 && !theta) return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: theta is null");
-    for (int i = 0; i < n_theta; ++i)
-        if (!(theta[i] >= 0.0)) return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: every theta must be >= 0");
-    if (K < 1) return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: K must be positive");
-    if (K > ((int64_t)1 << 27)) return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: K must be at most 2^27 (the costs stay on the device, 8 bytes each)");
+    rat_rc rc;
+    if ((rc = policy_eval_args_ok("rat_policy_evaluate_noise", theta, n_theta, K))) return rc;
     if (!h || !x_nom || !l || !stats) return fail(RAT_ERR_ARG, "null");
     if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
     if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
         return fail(RAT_ERR_UNSUPPORTED, "rat_policy_evaluate_noise: the handle's problem is not a source model (only a source can define rat_user_noise)");
     const int n = h->n, m = h->m, N = h->N;
     const int npn = normals_per_step, npu = uniforms_per_step;
-    rat_rc rc;
     if ((rc = user_noise_args_ok("rat_policy_evaluate_noise", n, m, npn, npu))) return rc;
     if ((zn || zu) && ((npn > 0 && !zn) || (npu > 0 && !zu)))
         return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: injected draws need every declared stream (normals_per_step = " + std::to_string(npn) +
@@ -2165,11 +2213,7 @@ extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, c
         if ((rc = src_compile_user_noise(h->src_text.c_str(), n, m, npn, npu, h->src_arch_name, &code, &log))) return fail(rc, log);
         hipModule_t mod = nullptr;
         hipFunction_t fn = nullptr;
-        HIPCHK(hipModuleLoadData(&mod, code->data()));
-        if (hipModuleGetFunction(&fn, mod, "rat_src_user_noisy_rollout") != hipSuccess) {
-            (void)hipModuleUnload(mod);
-            return fail(RAT_ERR_HIP, "rat_policy_evaluate_noise: the compiled module lacks its kernel");
-        }
+        if ((rc = load_module_function(code, "rat_src_user_noisy_rollout", "rat_policy_evaluate_noise", &mod, &fn))) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));
         if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
         h->src_un_mod = mod; h->src_un = fn; h->src_un_npn = npn; h->src_un_npu = npu; h->src_un_loads++;
@@ -2178,28 +2222,18 @@ extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, c
         h->h_un_over = nullptr;
         return fail(RAT_ERR_HIP, "rat_policy_evaluate_noise: hipHostMalloc failed");
     }
-    // the policy in the padded 12 + 4 layout, one upload: x_nom | l | L
-    std::vector<double> pack, xp, up, Lp;
-    if (L) { pad_x(h, x_nom, xp); pad_L(h, L, Lp); }
-    else { xp.assign((size_t)(N + 1) * XSTR, 0.0); for (int i = 0; i < n; ++i) xp[i] = x_nom[i]; }
-    pad_u(h, l, up);
-    pack.insert(pack.end(), xp.begin(), xp.end());
-    const size_t o_l = pack.size(); pack.insert(pack.end(), up.begin(), up.end());
-    const size_t o_L = pack.size(); pack.insert(pack.end(), Lp.begin(), Lp.end());
+    PolicyPack pk;                                                // (W is not read: the pack starts at x_nom)
+    if ((rc = pack_policy(h, x_nom, l, L, false, &pk))) return rc;
     const bool inject = zn || zu, traj = x_out || u_out;
-    const int64_t chunk = std::min<int64_t>(K, 1 << 16);
-    const size_t one = 1, nxo = (size_t)(N + 1) * n, nuo = (size_t)N * m;
-    h->mc_cost_K = 0;                                             // (d_mc_cost is about to be regrown or overwritten)
-    h->mc_rec.kind = 0;
-    size_t cap_red = h->d_mc_red ? MC_SCRATCH : 0;
-    if ((rc = grow(&h->d_mc_in, &h->cap_mc_in, pack.size()))) return rc;
-    if ((rc = grow(&h->d_mc_cost, &h->cap_mc_cost, std::max((size_t)K, one)))) return rc;
-    if ((rc = grow(&h->d_mc_red, &cap_red, (size_t)MC_SCRATCH))) return rc;
+    const int64_t chunk = mc_chunk(K);
+    const size_t nxo = (size_t)(N + 1) * n, nuo = (size_t)N * m;
+    if ((rc = policy_eval_scratch(h, pk, K))) return rc;
     if (zn && npn > 0 && (rc = grow(&h->d_mc_z, &h->cap_mc_z, (size_t)chunk * N * npn))) return rc;
     if (zu && npu > 0 && (rc = grow(&h->d_mc_zu, &h->cap_mc_zu, (size_t)chunk * N * npu))) return rc;
     if (x_out && (rc = grow(&h->d_mc_xo, &h->cap_mc_xo, (size_t)chunk * nxo))) return rc;
     if (u_out && (rc = grow(&h->d_mc_uo, &h->cap_mc_uo, (size_t)chunk * nuo))) return rc;
-    HIPCHK(hipMemcpy(h->d_mc_in, pack.data(), pack.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_mc_in, pk.data.data(), pk.data.size() * 8, hipMemcpyHostToDevice));
+    const PolicyDev dev = policy_dev(h->d_mc_in, pk.o_x, pk.o_l, pk.o_L, L != nullptr);
     int *d_over = nullptr;
     HIPCHK(hipHostGetDevicePointer((void **)&d_over, h->h_un_over, 0));
     *h->h_un_over = 0;
@@ -2212,44 +2246,19 @@ extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, c
             if (zn && npn > 0) HIPCHK(hipMemcpy(h->d_mc_z, zn + (size_t)k0 * N * npn, (size_t)kc * N * npn * 8, hipMemcpyHostToDevice));
             if (zu && npu > 0) HIPCHK(hipMemcpy(h->d_mc_zu, zu + (size_t)k0 * N * npu, (size_t)kc * N * npu * 8, hipMemcpyHostToDevice));
         }
-        SrcUserNoisyArgs a;
-        a.xnom = h->d_mc_in; a.l = h->d_mc_in + o_l; a.L = L ? h->d_mc_in + o_L : nullptr;
-        a.zn = (zn && npn > 0) ? h->d_mc_z : nullptr; a.zu = (zu && npu > 0) ? h->d_mc_zu : nullptr;
-        a.K = (long)kc; a.j0 = (long)k0; a.N = N; a.tpw = h->src_mc_tpw; a.seed = seed; a.cost = h->d_mc_cost + k0;
-        a.x_out = x_out ? h->d_mc_xo : nullptr; a.u_out = u_out ? h->d_mc_uo : nullptr; a.p = h->d_src_p; a.overdraw = d_over;
-        void *args[] = {&a};
-        HIPCHK(hipModuleLaunchKernel(h->src_un, (unsigned)((kc + a.tpw - 1) / a.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+        if ((rc = launch_user_noisy_chunk(h, dev, k0, kc, seed, (zn && npn > 0) ? h->d_mc_z : nullptr, (zu && npu > 0) ? h->d_mc_zu : nullptr,
+                                          x_out ? h->d_mc_xo : nullptr, u_out ? h->d_mc_uo : nullptr, h->d_mc_cost + k0, d_over)))
+            return rc;
         if (traj) {                                               // (the stream orders these copies behind the chunk's rollouts; they block the host)
             if (x_out) HIPCHK(hipMemcpyAsync(x_out + (size_t)k0 * nxo, h->d_mc_xo, (size_t)kc * nxo * 8, hipMemcpyDeviceToHost, h->stream));
             if (u_out) HIPCHK(hipMemcpyAsync(u_out + (size_t)k0 * nuo, h->d_mc_uo, (size_t)kc * nuo * 8, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
         }
     }
-    McArgs ma;
-    memset(&ma, 0, sizeof(ma));
-    ma.cost = h->d_mc_cost; ma.dom = nullptr; ma.K = (long)K; ma.n_theta = n_theta; ma.scratch = h->d_mc_red;
-    for (int i = 0; i < n_theta; ++i) ma.theta[i] = theta[i];
-    launch_policy_mc(ma, h->stream);
-    HIPCHK(hipGetLastError());
-    double out[MC_OUT];
-    HIPCHK(hipMemcpyAsync(out, h->d_mc_red + (MC_P1 + MC_P2) * MC_BLOCKS, sizeof(out), hipMemcpyDeviceToHost, h->stream));
-    if (cost_out) HIPCHK(hipMemcpyAsync(cost_out, h->d_mc_cost, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (*(volatile int *)h->h_un_over != 0)                       // after the wait: a step that drew more than the caller declared
-        return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: a step drew more than was declared (normals_per_step = " + std::to_string(npn) +
-                                 ", uniforms_per_step = " + std::to_string(npu) + "): the overdrawn values were NaN");
-    h->mc_cost_K = K;
-    {
-        rat_handle_s::McReplay &r = h->mc_rec;
-        r.kind = 2; r.injected = inject; r.has_L = L != nullptr; r.seed = seed; r.K = K; r.npn = npn; r.npu = npu;
-        r.o_x = 0; r.o_l = o_l; r.o_L = o_L; r.n = n; r.m = m; r.N = N; r.model = h->pb.model; r.W_tv = h->W_tv;
-    }
-    for (int i = 0; i < RAT_MC_NSTAT; ++i) stats[i] = out[i];
-    for (int i = 0; i < n_theta; ++i) {
-        if (risk) risk[i] = out[8 + i];
-        if (risk_se) risk_se[i] = out[8 + MC_MAX_THETA + i];
-    }
-    return RAT_OK;
+    rat_handle_s::McReplay rec;
+    rec.kind = 2; rec.injected = inject; rec.has_L = L != nullptr; rec.seed = seed; rec.K = K; rec.npn = npn; rec.npu = npu;
+    rec.o_x = pk.o_x; rec.o_l = pk.o_l; rec.o_L = pk.o_L; rec.n = n; rec.m = m; rec.N = N; rec.model = h->pb.model; rec.W_tv = h->W_tv;
+    return policy_eval_finish(h, nullptr, rec, theta, n_theta, stats, risk, risk_se, cost_out);
 }
 
 // The worst-case expected cost sup { E_p[J] : KL(p || q) <= d } of the sample of K costs, by its one-dimensional dual, searched on the
@@ -2412,7 +2421,7 @@ static rat_rc replay_chunks(rat_handle h, const double *kl_bound, int32_t n_boun
     const rat_handle_s::McReplay rec = h->mc_rec;
     const bool source = h->pb.model == RAT_MODEL_SOURCE;
     const int n = h->n, m = h->m, N = h->N, nrows = n_bound + n_theta;
-    const int64_t K = rec.K, chunk = std::min<int64_t>(K, 1 << 16);
+    const int64_t K = rec.K, chunk = mc_chunk(K);
     const int ldx = source ? n : XSTR, ldu = source ? m : USTR;
     rat_rc rc;
     size_t cap_red = h->d_wc_red ? WC_SCRATCH : 0;
@@ -2422,7 +2431,7 @@ static rat_rc replay_chunks(rat_handle h, const double *kl_bound, int32_t n_boun
     if ((rc = grow(&h->d_wt_cost, &h->cap_wt_cost, (size_t)chunk))) return rc;
     if (!source && (rc = grow(&h->d_wt_dom, &h->cap_wt_dom, (size_t)chunk))) return rc;
     if ((rc = grow(&h->d_wt_y, &h->cap_wt_y, (size_t)nrows * chunk))) return rc;
-    const double *d_x = h->d_mc_in + rec.o_x, *d_l = h->d_mc_in + rec.o_l, *d_L = rec.has_L ? h->d_mc_in + rec.o_L : nullptr;
+    const PolicyDev dev = policy_dev(h->d_mc_in, rec.o_x, rec.o_l, rec.o_L, rec.has_L);
     // theta*, Jmax and the rows, on the stored costs
     WcArgs wa;
     memset(&wa, 0, sizeof(wa));
@@ -2439,18 +2448,9 @@ static rat_rc replay_chunks(rat_handle h, const double *kl_bound, int32_t n_boun
     for (int64_t k0 = 0; k0 < K; k0 += chunk) {
         const int64_t kc = std::min(chunk, K - k0);
         if (source) {
-            SrcUserNoisyArgs a;
-            a.xnom = d_x; a.l = d_l; a.L = d_L; a.zn = nullptr; a.zu = nullptr;
-            a.K = (long)kc; a.j0 = (long)k0; a.N = N; a.tpw = h->src_mc_tpw; a.seed = rec.seed; a.cost = h->d_wt_cost;
-            a.x_out = h->d_mc_xo; a.u_out = h->d_mc_uo; a.p = h->d_src_p; a.overdraw = d_over;
-            void *args[] = {&a};
-            HIPCHK(hipModuleLaunchKernel(h->src_un, (unsigned)((kc + a.tpw - 1) / a.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+            if ((rc = launch_user_noisy_chunk(h, dev, k0, kc, rec.seed, nullptr, nullptr, h->d_mc_xo, h->d_mc_uo, h->d_wt_cost, d_over))) return rc;
         } else {
-            NoisyArgs a;
-            a.pb = h->pb; a.Wchol = h->d_mc_in; a.xnom = d_x; a.l = d_l; a.L = d_L; a.K = (long)kc; a.z = nullptr;
-            a.seed = rec.seed + 0x9E3779B97F4A7C15ull * (uint64_t)(k0 / chunk);
-            a.x_out = h->d_mc_xo; a.u_out = h->d_mc_uo; a.cost = h->d_wt_cost; a.dom = h->d_wt_dom;
-            launch_noisy_rollout(a, h->stream);
+            launch_noisy_chunk(h, dev, k0, kc, chunk, rec.seed, nullptr, h->d_mc_xo, h->d_mc_uo, h->d_wt_cost, h->d_wt_dom);
         }
         ta.kc = (long)kc; ta.cost = h->d_mc_cost + k0;
         launch_wct_weights(ta, h->stream);
@@ -2580,7 +2580,7 @@ extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double 
                                          std::to_string((long)((size_t)EV_MAX_PART_BYTES / (per_batch * 8)) * EV_ROWS) + " rows fit in one call at this horizon"
                                          + (step_out ? " (more without step_out)" : ""));
     HIPCHK(hipSetDevice(h->device));
-    const int64_t K = rec.K, chunk = std::min<int64_t>(K, 1 << 16);
+    const int64_t K = rec.K, chunk = mc_chunk(K);
     // the events in the 12 + 4 tile: Q as the MFMA's A operand reads it (entry (k, i) at k * 16 + i), a, b, the windows
     const size_t o_a = (size_t)EV_MAX * 256, o_b = o_a + EV_MAX * 16, o_win = o_b + EV_MAX, o_ev = o_win + EV_MAX, o_step = o_ev + (size_t)nrows * ne1 * EV_NSTAT,
                  o_cnt = o_step + (size_t)nrows * ne1 * nsteps, n_out = o_cnt + 1;
@@ -2648,7 +2648,7 @@ extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double 
 }
 
 // The probability of a rare safety event by adaptive importance sampling (include/ratilqr.h; rare_event.h has the chain and the keying):
-// the policy is packed as rat_policy_evaluate packs it, into buffers of this call's own, and the whole loop runs on the device.  The stop
+// the policy is packed by pack_policy like every evaluation's, into buffers of this call's own, and the whole loop runs on the device.  The stop
 // rule is one 4-byte read-back per iteration: a skipped iteration then launches nothing (instead of sixteen launches that return at once;
 // either is small beside a rollout pass of milliseconds), and the host knows which trace rows exist.
 extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K, uint64_t seed,
@@ -2663,7 +2663,7 @@ extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const
     if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
     if (h->wide) return fail(RAT_ERR_UNSUPPORTED, F + "compiled for n <= 12, m <= 4 (the shift is defined on the family rollout)");
     if (h->pb.model == RAT_MODEL_SOURCE) return fail(RAT_ERR_UNSUPPORTED, F + "not available for source models (the shift is defined on the family rollout)");
-    const int n = h->n, m = h->m, N = h->N, Nw = h->W_tv ? N : 1, d = n + m;
+    const int n = h->n, m = h->m, N = h->N, d = n + m;
     if (N > RE_MAX_N) return fail(RAT_ERR_UNSUPPORTED, F + "N is above " + std::to_string(RE_MAX_N) + " (the shift is staged in LDS)");
     if (!(0 <= t_lo && t_lo <= t_hi && t_hi <= N)) return fail(RAT_ERR_ARG, F + "the window must satisfy 0 <= t_lo <= t_hi <= N");
     bool fin = std::isfinite(b);
@@ -2672,19 +2672,11 @@ extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const
     if (shift_in) for (int i = 0; i < N * n; ++i) fin = fin && std::isfinite(shift_in[i]);
     if (!fin) return fail(RAT_ERR_ARG, F + "Q, a, b and shift_in must be finite");
     HIPCHK(hipSetDevice(h->device));
-    // Wchol | x_nom | l | L as rat_policy_evaluate packs them, then the event in the 12 + 4 tile (rat_policy_events' layout) and the shift
-    std::vector<double> pack((size_t)Nw * 192, 0.0), Lc((size_t)n * n), xp, up, Lp;
-    for (int k = 0; k < Nw; ++k) {
-        if (!host_chol_lower(n, h->hW.data() + (size_t)k * n * n, Lc.data()))
-            return fail(RAT_ERR_ARG, "W(k) is not positive definite (MvNormal would throw)");
-        for (int i = 0; i < n; ++i) for (int jj = 0; jj <= i; ++jj) pack[(size_t)k * 192 + i * 16 + jj] = Lc[i + n * jj];
-    }
-    if (L) { pad_x(h, x_nom, xp); pad_L(h, L, Lp); }
-    else { xp.assign((size_t)(N + 1) * XSTR, 0.0); for (int i = 0; i < n; ++i) xp[i] = x_nom[i]; }
-    pad_u(h, l, up);
-    const size_t o_x = pack.size(); pack.insert(pack.end(), xp.begin(), xp.end());
-    const size_t o_l = pack.size(); pack.insert(pack.end(), up.begin(), up.end());
-    const size_t o_L = pack.size(); pack.insert(pack.end(), Lp.begin(), Lp.end());
+    // the policy pack (pack_policy), then the event in the 12 + 4 tile (rat_policy_events' layout) and the shift
+    rat_rc rc;
+    PolicyPack pk;
+    if ((rc = pack_policy(h, x_nom, l, L, true, &pk))) return rc;
+    std::vector<double> &pack = pk.data;
     const size_t o_q = pack.size(), o_a = o_q + 256, o_s = o_a + 16;
     pack.resize(o_s + (size_t)N * 12, 0.0);
     auto tix = [n](int i) { return i < n ? i : 12 + i - n; };
@@ -2693,7 +2685,6 @@ extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const
         if (Q) for (int k = 0; k < d; ++k) pack[o_q + tix(k) * 16 + tix(i)] = Q[i + (size_t)d * k];
     }
     if (shift_in) for (int t = 0; t < N; ++t) for (int i = 0; i < n; ++i) pack[o_s + (size_t)t * 12 + i] = shift_in[(size_t)t * n + i];
-    rat_rc rc;
     size_t cap_red = h->d_re_red ? RE_SCRATCH : 0;
     const size_t n_part = ((size_t)N * 12 + 3) * RE_SLOTS;
     if ((rc = grow(&h->d_re_in, &h->cap_re_in, pack.size()))) return rc;
@@ -2706,8 +2697,9 @@ extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const
     HIPCHK(hipMemsetAsync(h->d_re_red + RE_O_LVL, 0, (size_t)(RE_O_TR - RE_O_LVL) * 8, h->stream));
     ReArgs ra;
     memset(&ra, 0, sizeof(ra));
-    ra.pb = h->pb; ra.Wchol = h->d_re_in; ra.xnom = h->d_re_in + o_x; ra.l = h->d_re_in + o_l; ra.L = L ? h->d_re_in + o_L : nullptr;
-    ra.K = (long)K; ra.chunk = (long)std::min<int64_t>(K, 1 << 16);
+    const PolicyDev dev = policy_dev(h->d_re_in, pk.o_x, pk.o_l, pk.o_L, L != nullptr);
+    ra.pb = h->pb; ra.Wchol = dev.Wchol; ra.xnom = dev.x; ra.l = dev.l; ra.L = dev.L;
+    ra.K = (long)K; ra.chunk = (long)mc_chunk(K);
     ra.shift = h->d_re_in + o_s; ra.Qt = h->d_re_in + o_q; ra.at = h->d_re_in + o_a; ra.b = b; ra.t_lo = t_lo; ra.t_hi = t_hi;
     ra.margin = h->d_re_margin; ra.logw = h->d_re_logw; ra.dom = h->d_re_dom; ra.scratch = h->d_re_red; ra.part = h->d_re_part;
     int reached = 0, n_run = 0;
@@ -3809,11 +3801,7 @@ extern "C" rat_rc rat_pets_problem_set_source(rat_handle h, const char *source, 
     if ((rc = src_compile_gen(source, n, m, normals_per_step, uniforms_per_step, src_arch(pr.gcnArchName), &code, &log))) return fail(rc, log);
     hipModule_t mod = nullptr;
     hipFunction_t fr = nullptr;
-    HIPCHK(hipModuleLoadData(&mod, code->data()));
-    if (hipModuleGetFunction(&fr, mod, "rat_src_pets_rollout") != hipSuccess) {
-        (void)hipModuleUnload(mod);
-        return fail(RAT_ERR_HIP, "rat_pets_problem_set_source: the compiled module lacks its kernel");
-    }
+    if ((rc = load_module_function(code, "rat_src_pets_rollout", "rat_pets_problem_set_source", &mod, &fr))) return rc;
     std::vector<void *> allocs;
     auto undo = [&](rat_rc r) { free_list(allocs); (void)hipModuleUnload(mod); return r; };
     if (!h->h_gsrc_over && hipHostMalloc((void **)&h->h_gsrc_over, sizeof(int), hipHostMallocDefault) != hipSuccess) {
