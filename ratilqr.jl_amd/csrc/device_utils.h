@@ -88,6 +88,49 @@ __device__ __forceinline__ double row_ror8_merge(double old, double src) {
                             __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), 0x128, 0xF, BM, false));
 }
 
+// v_mfma_f64_4x4x4_4b_f64: four independent 4 x 4 x 4 products (blocks q = 0..3); 20 cycles of issue against the 64 of the 16 x 16 x 4 form.
+// The operand registers read like the ones of the 16 x 16 x 4 form (tools/ubench/mfma_f64_shapes.hip, one-hot inputs):
+//   A: lane (g, j) feeds A_q[row j & 3][k = g] of block q = j >> 2      B: lane (g, j) feeds B_q[k = g][column j & 3] of block q = j >> 2
+//   C / D: ONE double per lane, lane (g, j) holds D_q[row g][column j & 3] of block q = j >> 2
+// so with the A operand of a 16 x 16 x 4 product (lane (g, j) = A[row j][k = g]) block q forms rows 4 q .. 4 q + 3, and lane (g, j) ends up
+// with element (row 4 (j >> 2) + g, column j) of the 16 x 16 product -- register j >> 2 of that lane in the 16 x 16 x 4 accumulator layout, the
+// same sum in the same K order, bit for bit (same program: 1e6 random operand sets, cancellation, +-0, denormals, inf, NaN).
+#define MFMA4(a, b, c) __builtin_amdgcn_mfma_f64_4x4x4f64((a), (b), (c), 0, 0, 0)
+
+__device__ __forceinline__ double mm3_4(const double (&a)[3], const double (&b)[3], double acc) {   // K-slices 0..2, one double per lane
+    acc = MFMA4(a[0], b[0], acc);
+    acc = MFMA4(a[1], b[1], acc);
+    acc = MFMA4(a[2], b[2], acc);
+    return acc;
+}
+__device__ __forceinline__ double mm4_4(const double (&a)[4], const double (&b)[4], double acc) {   // K-slices 0..3
+    acc = MFMA4(a[0], b[0], acc);
+    acc = MFMA4(a[1], b[1], acc);
+    acc = MFMA4(a[2], b[2], acc);
+    acc = MFMA4(a[3], b[3], acc);
+    return acc;
+}
+
+// B-form of a vector that a 4 x 4 x 4 chain left one double per lane (lane (g, j): component 4 (j >> 2) + g, any column of its block):
+// r[s] on lane (g, j) = component 4 s + g for every j, i.e. bank s (columns 4 s .. 4 s + 3) of each 16-lane row copied to the other
+// three banks.  DPP row rotations with a bank mask (row_ror:n -- lane i reads lane (i - n) mod 16 of its row), VALU only.
+template <int S>
+__device__ __forceinline__ double bank_bcast(double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+#define BANK_ROR(w, n) w = __builtin_amdgcn_update_dpp(w, w, 0x120 + 4 * (n), 0xF, 1 << ((S + (n)) & 3), false)
+    // each rotation reads bank S (still the original: only the bank it lands on is written) and writes one other bank
+    BANK_ROR(lo, 1); BANK_ROR(hi, 1);
+    BANK_ROR(lo, 2); BANK_ROR(hi, 2);
+    BANK_ROR(lo, 3); BANK_ROR(hi, 3);
+#undef BANK_ROR
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ void bform3_from_blocks(double v, double (&r)[3]) {
+    r[0] = bank_bcast<0>(v);
+    r[1] = bank_bcast<1>(v);
+    r[2] = bank_bcast<2>(v);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // One 2x2-block round of the symmetric sweep (in-place inversion of M = inv(W) - theta S, ileqg.jl:365-367) with the rank-2
 // update on the matrix pipe.  m holds M (12 x 12 in the 12 x 16 accumulator layout, register r = rows 4r..4r+3).

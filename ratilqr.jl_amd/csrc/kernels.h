@@ -4,6 +4,13 @@
 
 #include "layout.h"
 
+// The closed-loop rollouts of solve_fused_kernel (LQ family, staged, not OCC2) run the seven MFMAs of the recursion's chain in the 4 x 4 x 4
+// form (kernels.hip: rollin_body<.., M4>; the same bits).  0 builds the 16 x 16 x 4 form everywhere, for an A/B measurement -- a build
+// constant, not a run-time switch: a second rollout body in the same instantiation costs the kernel SGPR spills.
+#ifndef RAT_ROLLOUT_MFMA4
+#define RAT_ROLLOUT_MFMA4 1
+#endif
+
 // Riccati-matrix record of the one-wavefront-per-sample solve (solve_fused_kernel, LQ family, kappa = 0, diagonal time-invariant W): for such a
 // problem A, B, Q, R, P, W do not depend on the trajectory, so every later paired sweep at the same mu runs the matrix half of the recursions
 // of the last full paired gain sweep again, bit for bit.  That sweep records per step what the vector half reads from it; later pairs replay

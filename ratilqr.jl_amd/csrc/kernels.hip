@@ -818,7 +818,11 @@ void launch_rollout(const RolloutArgs &a, hipStream_t s) {
 // sweeps that evaluate the candidate form f_x | f_u and the cost Hessian of step t from (x_t, u_t) and the problem tables themselves
 // (load_tile<.., FLY>); the gain sweeps that may read an accepted candidate's records are fly sweeps too, so the rest of a record is never
 // written -- the reference keeps approximate_model's result only for the trajectory it accepts (ileqg.jl:514-555), this path for none.
-template <int MODEL, int MODE, bool CTV, bool STAGE = false, bool SEP = true, int PF = ROLLIN_PREFETCH, bool NOTILE = false>
+// M4 (LQ family, closed loop; the staged rollouts of solve_fused_kernel): the seven MFMAs on the recursion's chain in the 4 x 4 x 4 form
+// (device_utils.h: MFMA4) -- each is a matrix times ONE vector, of which the 16 x 16 x 4 form computes 16 copies in 16 passes.  Same
+// operand registers, same K order, the same bits (tools/ubench/mfma_f64_shapes.hip); L's rows repeat every four, so u_t comes out in
+// B-form as before, and x_{t+1} arrives one double per lane and is spread to B-form by DPP row rotations (bform3_from_blocks).
+template <int MODEL, int MODE, bool CTV, bool STAGE = false, bool SEP = true, int PF = ROLLIN_PREFETCH, bool NOTILE = false, bool M4 = false>
 __device__ __forceinline__ void rollin_body(const RolloutArgs &a, const int c, double *const shxu, double *const stg = nullptr) {
     int lane_ = threadIdx.x & 63;        // (rollin_stage_kernel runs the E candidates of a sample as the waves of one workgroup)
     asm volatile("" : "+v"(lane_));      // opaque per phase (see sweep_body)
@@ -907,6 +911,9 @@ __device__ __forceinline__ void rollin_body(const RolloutArgs &a, const int c, d
     double xb[3];                                               // x_t in B-form
 #pragma unroll
     for (int s = 0; s < 3; ++s) xb[s] = (MODE == 0) ? a.x0[4 * s + g] : xbar[4 * s + g];
+    constexpr bool m4 = M4 && lq && MODE == 1;
+    // (M4) x_t one double per lane, as the 4 x 4 x 4 chain leaves it: lane (g, j) holds component 4 (j >> 2) + g, 0 on columns 12..15
+    [[maybe_unused]] double x1 = (j < 4) ? xb[0] : (j < 8 ? xb[1] : (j < 12 ? xb[2] : 0.0));
     double dmax = -INFINITY;
     bool dnan = false;
     int dom = 0;
@@ -1012,18 +1019,29 @@ __device__ __forceinline__ void rollin_body(const RolloutArgs &a, const int c, d
         }
         // ---- x_{t+1} = f(x_t, u_t): the x-part of [A|B][x; u] does not wait for the feedback control -----------------
         d4 xa = zero4;
-        if (lq) {
+        [[maybe_unused]] double xa1 = 0.0;                          // (M4) row 4 (j >> 2) + g of [A|B][x; u]
+        if (m4) {
+            const double za[3] = {zA[0], zA[1], zA[2]};
+            xa1 = mm3_4(za, xb, xa1);
+        } else if (lq) {
             xa = MFMA(zA[0], xb[0], xa);
             xa = MFMA(zA[1], xb[1], xa);
             xa = MFMA(zA[2], xb[2], xa);
         }
         double u = c_l;                                             // u_g on the lanes of row g (B-form slice 3)
         if (MODE == 1) {
-            d4 fb = MFMA(c_La[0], xb[0] - c_xb[0], zero4);          // L_t (x_t - xbar_t)   (:82)
-            fb = MFMA(c_La[1], xb[1] - c_xb[1], fb);
-            fb = MFMA(c_La[2], xb[2] - c_xb[2], fb);
+            double fb0;                                             // (L_t (x_t - xbar_t))_g on the lanes of row g   (:82)
+            if (m4) {
+                const double dx[3] = {xb[0] - c_xb[0], xb[1] - c_xb[1], xb[2] - c_xb[2]};
+                fb0 = mm3_4(c_La, dx, 0.0);                         // every block holds rows 0..3 of L: row g on all 16 lanes of row g
+            } else {
+                d4 fb = MFMA(c_La[0], xb[0] - c_xb[0], zero4);
+                fb = MFMA(c_La[1], xb[1] - c_xb[1], fb);
+                fb = MFMA(c_La[2], xb[2] - c_xb[2], fb);
+                fb0 = fb[0];
+            }
             const double lnew = c_l + eps * c_dl;                   // l + eps dl           (:509)
-            u = lnew + fb[0];
+            u = lnew + fb0;
             // d = maximum(norm(l_t - u_t))  (:517-519): sqrt is monotone, so the maximum is taken over the squared norms and
             // rooted once after the loop (same bits); maximum() propagates NaN
             const double du = c_l - u, dsq = du * du;
@@ -1033,7 +1051,11 @@ __device__ __forceinline__ void rollin_body(const RolloutArgs &a, const int c, d
         }
         DIAG_STAMP(0, u);
         double xn[3] = {0.0, 0.0, 0.0};
-        if (lq) {
+        if (m4) {
+            xa1 = MFMA4(zA[3], u, xa1);
+            x1 = xa1 + pb.kappa * (x1 * x1 * x1);                   // the expression below on the lane's one element
+            bform3_from_blocks(x1, xn);
+        } else if (lq) {
             xa = MFMA(zA[3], u, xa);
             // + kappa x^3, branch-free (kappa = 0 adds 0): the whole step stays ONE basic block, so the scheduler can run the
             // off-path chains (transposition, C [x;u], tile stores) of one step under the recursion of the next
@@ -2594,6 +2616,7 @@ __global__ __launch_bounds__(64, OCC2 ? 2 : 1) void solve_fused_kernel(FusedArgs
     constexpr int FLYF = (MODEL == 1 && ((DUALF && STG && !OCC2) || (OCC2 && !DUALF && !STG)) && !MAT) ? (CTV ? 2 : 1) : 0;
     constexpr bool NT = FLYF != 0;
     constexpr bool PL = (MODEL == 1);            // phase-local arguments (phase_args)
+    constexpr bool RM4 = RAT_ROLLOUT_MFMA4 && MODEL == 1 && STG && !OCC2;      // closed-loop rollout on 4 x 4 x 4 MFMAs (rollin_body: M4)
     // the sample's own wave initialises its state and, at the end, writes its outputs: a batch is ONE launch
     if (threadIdx.x == 0) {
         const FusedArgs &pa = phase_args<PL>(fa);
@@ -2642,7 +2665,7 @@ __global__ __launch_bounds__(64, OCC2 ? 2 : 1) void solve_fused_kernel(FusedArgs
         }
         {                                                    // one candidate of line_search!  (ileqg.jl:504-581)
             const RolloutArgs ra = rollout_view<PL>(phase_args<PL>(fa), 1);
-            rollin_body<MODEL, 1, CTV, STG, true, OCC2 ? OCC2_PREFETCH : ROLLIN_PREFETCH, NT>(ra, b, shxu, stg);
+            rollin_body<MODEL, 1, CTV, STG, true, OCC2 ? OCC2_PREFETCH : ROLLIN_PREFETCH, NT, RM4>(ra, b, shxu, stg);
             PHASE_MARK();
             PHASE_FENCE();
             PHASE_MARK();
