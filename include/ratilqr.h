@@ -454,6 +454,42 @@ rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const double *l,
                              const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi,
                              const double *shift_in, int32_t n_iter, double rho,
                              double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out);
+/* rat_policy_rare_event for a source model under the user's own process noise: the rollout is rat_policy_evaluate_noise's,
+ * x_{k+1} = f(x_k, u_k) + rat_user_noise(k, x_k, u_k, rng), under the policy (x_nom, l, L) exactly as that call takes it, with its
+ * DomainError rule (a NaN from the sampler included) and its overdraw rule (RAT_ERR_ARG naming the limits; the handle stays usable).  W
+ * is not read.  The proposal shifts the NORMALS THE SAMPLER DRAWS: the i-th rng.normal() of step t returns z = s[t][i] + xi, xi the
+ * generator's N(0, 1) draw, with s in R^{N x P}, P = normals_per_step, and the rollout's log-likelihood ratio logw = sum (-s z + 1/2 s^2)
+ * runs over the normals the sampler actually drew, added at the draw, in draw order: a sequential likelihood ratio, valid when the number
+ * of draws depends on earlier draws, so the estimate is unbiased for every s and the adaptation only moves its variance.
+ * rng.uniform() is NOT shifted (its likelihood ratio is 1): an event that a uniform drives -- the selector of a mixture, a jump that
+ * fires with a small probability -- cannot be made likelier by this call; write such a choice through a normal where that matters.
+ * The event g(t, z) = z' Q z + a' z + b of z = (x_t, u_t), the window, M, the level gamma_j, the elite, the update
+ * s <- s + sum_E w xi / sum_E w, the dropped non-finite update, stats[RAT_RE_NSTAT], the flags, trace_out, margin_out and logw_out are
+ * rat_policy_rare_event's, and the weights are NOT self-normalised.  The elite sum runs over all P declared normals of every step,
+ * replayed from the pass's stream whether or not that rollout drew them: a component a rollout did not draw moves its shift entry by
+ * sampling noise alone, which costs variance and introduces no bias.
+ * Keying: pass p -- the final pass is p = 0, iteration j is p = j + 1 -- draws under seed_p = seed + 0xD1B54A32D192ED03 p (mod 2^64) the
+ * way rat_policy_evaluate_noise's generator draws under its seed: the global rollout index g in the Philox counter (g lo, g hi, t,
+ * i >> 1), key seed_p, no per-chunk keys.  So with n_iter == 0 and shift_in == NULL the call is plain Monte Carlo on
+ * rat_policy_evaluate_noise's noise at that seed: margin_out is bit for bit what rat_policy_events returns behind that evaluation, and
+ * every logw is 0.  A rollout's noise does not depend on K.  The same call returns the same bits.
+ *   normals_per_step   1 .. 12 (0: RAT_ERR_ARG, there is nothing to shift; above 12: RAT_ERR_UNSUPPORTED);  uniforms_per_step >= 0.  The
+ *                      kernel is compiled for them by the first call that names them (cached per process, like rat_policy_evaluate_noise's)
+ *   shift_in, shift_out   [N][P] (row t at t P) or NULL
+ *   K, n_iter, rho, Q, a, b, t_lo, t_hi, trace_out, margin_out, logw_out   as in rat_policy_rare_event
+ * There are no injected draws: the device generator only.  RAT_ERR_ARG: what rat_policy_rare_event lists (W apart); a source without
+ * RAT_USER_NOISE, or one that does not compile, with the compiler's log in rat_last_error(); an overdraw.  RAT_ERR_UNSUPPORTED: a
+ * problem that is not a source model, normals_per_step > 12, N > 256.  The device buffers are rat_policy_rare_event's: the handle's
+ * recorded evaluation is not disturbed. */
+rat_rc rat_policy_rare_event_noise(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
+                                   int32_t normals_per_step, int32_t uniforms_per_step, uint64_t seed,
+                                   const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi,
+                                   const double *shift_in, int32_t n_iter, double rho,
+                                   double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out);
+/* Compile only, for gfx950 (no device needed), the kernel of rat_policy_rare_event_noise: RAT_OK; RAT_ERR_ARG with the log in
+ * rat_last_error() (a source without RAT_USER_NOISE among them), for negative counts and for normals == 0; RAT_ERR_UNSUPPORTED for
+ * normals > 12, n > 12 or m > 4. */
+rat_rc rat_rare_event_noise_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms);
 /* approximate_model(problem, u_array, x_array)                 ileqg.jl:258-322
  * -> q[N+1], qv[n*(N+1)], Q[n*n*(N+1)], r[m*N], R[m*m*N], P[m*n*N], A[n*n*N], B[n*m*N], W[n*n*N] */
 rat_rc rat_approximate_model(rat_handle h, const double *u, const double *x,

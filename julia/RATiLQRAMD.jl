@@ -521,6 +521,42 @@ function rare_event_probability(s::ILEQGSolver, problem::DeviceRiskSensitiveProb
      margins=margins, logw=logw)
 end
 
+"""
+rare_event_probability_noise(s, problem, x_nom, l_array, L_array, Q, a, b, t_lo, t_hi, noise; K, seed, shift, n_iter, rho, want_margins,
+want_logw): rare_event_probability for a source problem under the disturbance its own rat_user_noise draws (rat_policy_rare_event_noise).
+`noise` is a UserNoise without injected streams (the device generator only; `seed` defaults to the UserNoise's): the proposal shifts the
+normals the sampler draws -- the i-th rng.normal() of step t returns shift[i, t] + xi -- so shift is (P, N), P = noise.normals_per_step
+in 1:12; rng.uniform() is not shifted.  Returns rare_event_probability's named tuple.
+"""
+function rare_event_probability_noise(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_nom, l_array::Vector{Vector{Float64}},
+                                      L_array::Union{Nothing,Vector{Matrix{Float64}}}, Q::Union{Nothing,Matrix{Float64}}, a::Vector{Float64},
+                                      b::Real, t_lo::Integer, t_hi::Integer, noise::UserNoise; K::Integer=65536,
+                                      seed::Integer=noise.seed, shift::Union{Nothing,Matrix{Float64}}=nothing, n_iter::Integer=8,
+                                      rho::Real=0.1, want_margins::Bool=false, want_logw::Bool=false)
+    (noise.zn === nothing && noise.zu === nothing) || throw(ArgumentError("rare_event_probability_noise draws from the device generator only"))
+    h = bind!(s.h, problem)
+    n, m, N = dims(problem)
+    P = Int(noise.normals_per_step)
+    xn = x_nom isa Vector{Float64} ? x_nom : flat(x_nom)
+    l = flat(l_array)
+    L = L_array === nothing ? C_NULL : flat(L_array)
+    stats = zeros(12); shift_out = zeros(max(P, 1), N); trace = zeros(4, max(n_iter, 1))
+    margins = want_margins ? Vector{Float64}(undef, K) : nothing
+    logw = want_logw ? Vector{Float64}(undef, K) : nothing
+    check(ccall((:rat_policy_rare_event_noise, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, UInt64, Ptr{Float64}, Ptr{Float64}, Float64, Int32,
+                 Int32, Ptr{Float64}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, xn, l, L, K, noise.normals_per_step, noise.uniforms_per_step, UInt64(seed), Q === nothing ? C_NULL : Q, a, Float64(b),
+                t_lo, t_hi, shift === nothing ? C_NULL : shift, n_iter, Float64(rho), stats, shift_out, trace,
+                want_margins ? margins : C_NULL, want_logw ? logw : C_NULL))
+    (prob=stats[1], prob_se=stats[2], ess=stats[3], n_viol=Int(stats[4]), n_ok=Int(stats[5]), n_domain=Int(stats[6]), logw_max=stats[7],
+     logw_min=stats[8], flag=Int(stats[9]), n_iter=Int(stats[10]), level=stats[11], shift=shift_out, trace=trace[:, 1:n_iter],
+     margins=margins, logw=logw)
+end
+"rare_event_noise_check(source, n, m; normals_per_step, uniforms_per_step): compile the kernel of rare_event_probability_noise only (rat_rare_event_noise_check)"
+rare_event_noise_check(source::AbstractString, n::Integer, m::Integer; normals_per_step::Integer=1, uniforms_per_step::Integer=0) =
+    check(ccall((:rat_rare_event_noise_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32), source, n, m, normals_per_step, uniforms_per_step))
+
 "integrate_cost(problem, x_array, u_array) -- ileqg.jl:115-124"
 function integrate_cost(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_array, u_array)
     h = bind!(s.h, problem); c = Ref(0.0)
@@ -1363,7 +1399,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

@@ -24,6 +24,7 @@ from .ileqg import (  # noqa: F401,E402
     kl_event_bound,
     RareEventResult,
     rare_event_probability,
+    rare_event_probability_noise,
     ILEQGSolver,
     ApproximationResult,
     DynamicProgrammingResult,

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -210,6 +211,11 @@ struct rat_handle_s {
     int src_un_npn = -1, src_un_npu = -1;                    // the draw counts the loaded module was compiled for
     int64_t src_un_loads = 0;                                // switch src_un_loads (read only): modules this handle compiled or fetched from the cache
     int *h_un_over = nullptr;                                // pinned: that kernel's overdraw flag (bit 0 normals, bit 1 uniforms)
+    // ... and under a shifted proposal (rat_policy_rare_event_noise): rat_src_rare_rollout (source_rare.h), a module of its own, compiled by
+    // the first such call; it shares the overdraw flag (both calls end with a host wait)
+    hipModule_t src_re_mod = nullptr;
+    hipFunction_t src_re = nullptr;
+    int src_re_npn = -1, src_re_npu = -1;
     double *d_mc_zu = nullptr; size_t cap_mc_zu = 0;         // injected uniforms of one chunk (the normals use d_mc_z)
     double *d_mc_xo = nullptr; size_t cap_mc_xo = 0;         // [chunk][N+1][n] trajectory staging
     double *d_mc_uo = nullptr; size_t cap_mc_uo = 0;         // [chunk][N][m]
@@ -425,6 +431,7 @@ extern "C" void rat_destroy(rat_handle h) {
     for (void *q : {(void *)h->d_ev_out, (void *)h->d_ev_part, (void *)h->d_ev_margin, (void *)h->d_ev_tau, (void *)h->d_ev_mask}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_re_in, (void *)h->d_re_margin, (void *)h->d_re_logw, (void *)h->d_re_dom, (void *)h->d_re_part, (void *)h->d_re_red}) if (q) (void)hipFree(q);
     if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
+    if (h->src_re_mod) (void)hipModuleUnload(h->src_re_mod);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
     if (h->h_pcost) (void)hipHostFree(h->h_pcost);
@@ -890,6 +897,8 @@ extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32
     h->src_noisy_mod = nullptr; h->src_noisy = nullptr;
     if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
     h->src_un_mod = nullptr; h->src_un = nullptr; h->src_un_npn = h->src_un_npu = -1;
+    if (h->src_re_mod) (void)hipModuleUnload(h->src_re_mod);
+    h->src_re_mod = nullptr; h->src_re = nullptr; h->src_re_npn = h->src_re_npu = -1;
     h->src_text = source; h->src_arch_name = src_arch(pr.gcnArchName);
     h->d_src_p = const_cast<double *>(dp); h->src_np = n_params;
     h->hW.assign(W, W + (size_t)(pb.W_tv ? N : 1) * n * n);
@@ -2647,35 +2656,48 @@ extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double 
     return RAT_OK;
 }
 
-// The probability of a rare safety event by adaptive importance sampling (include/ratilqr.h; rare_event.h has the chain and the keying):
-// the policy is packed by pack_policy like every evaluation's, into buffers of this call's own, and the whole loop runs on the device.  The stop
-// rule is one 4-byte read-back per iteration: a skipped iteration then launches nothing (instead of sixteen launches that return at once;
-// either is small beside a rollout pass of milliseconds), and the host knows which trace rows exist.
-extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K, uint64_t seed,
-                                        const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi,
-                                        const double *shift_in, int32_t n_iter, double rho,
-                                        double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out) {
-    const std::string F = "rat_policy_rare_event: ";
+// ---- rare events by adaptive importance sampling: rat_policy_rare_event and rat_policy_rare_event_noise -----------------------------------
+// What the two calls share (include/ratilqr.h; rare_event.h has the chain and the keying): the argument checks, the event and the shift
+// packed behind the policy, the handle's d_re_* buffers, the adaptation loop with its one 4-byte read-back per iteration -- a skipped
+// iteration then launches nothing (instead of sixteen launches that return at once; either is small beside a rollout pass of
+// milliseconds), and the host knows which trace rows exist -- the final pass and the read-backs.  They differ in the rollout kernel, in
+// the kernel that replays its stream over the elite, and in the width of a shift row: ReKernels.
+struct ReKernels {
+    int ncol;                                                         // entries of a shift row: n (the family's z_k), or P normals per step
+    bool with_wchol;                                                  // the pack starts with chol(W(k)) (the family rollout unwhitens with it)
+    std::function<rat_rc(const ReArgs &, bool)> rollout;              // K rollouts at ra.seed under ra.shift -> margin, logw, dom (enqueued)
+    void (*adapt)(const ReArgs &, hipStream_t);                       // launch_re_adapt or launch_re_adapt_rng
+    std::function<rat_rc()> waited;                                   // after every host wait (may be empty): what the rollouts flagged
+};
+
+// what the arguments alone decide, before the problem is looked at ...
+static rat_rc re_args_head(const std::string &F, rat_handle h, const double *x_nom, const double *l, const double *a, const double *stats,
+                           int64_t K, int32_t n_iter, double rho) {
     if (K < 1 || K > ((int64_t)1 << 27)) return fail(RAT_ERR_ARG, F + "K must be in 1 .. 2^27");
     if (n_iter < 0 || n_iter > RE_MAX_ITER) return fail(RAT_ERR_ARG, F + "n_iter must be in 0 .. 32");
     if (!(rho > 0.0 && rho <= 0.5)) return fail(RAT_ERR_ARG, F + "rho must be in (0, 0.5]");
     if (!h || !x_nom || !l || !a || !stats) return fail(RAT_ERR_ARG, F + "null handle / x_nom / l / a / stats");
     if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
-    if (h->wide) return fail(RAT_ERR_UNSUPPORTED, F + "compiled for n <= 12, m <= 4 (the shift is defined on the family rollout)");
-    if (h->pb.model == RAT_MODEL_SOURCE) return fail(RAT_ERR_UNSUPPORTED, F + "not available for source models (the shift is defined on the family rollout)");
-    const int n = h->n, m = h->m, N = h->N, d = n + m;
+    return RAT_OK;
+}
+
+// ... and everything behind the refusals of the call: the horizon, the window, the finiteness checks, then the passes
+static rat_rc re_run(rat_handle h, const std::string &F, const ReKernels &kn, const double *x_nom, const double *l, const double *L, int64_t K,
+                     uint64_t seed, const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi, const double *shift_in,
+                     int32_t n_iter, double rho, double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out) {
+    const int n = h->n, m = h->m, N = h->N, d = n + m, nc = kn.ncol;
     if (N > RE_MAX_N) return fail(RAT_ERR_UNSUPPORTED, F + "N is above " + std::to_string(RE_MAX_N) + " (the shift is staged in LDS)");
     if (!(0 <= t_lo && t_lo <= t_hi && t_hi <= N)) return fail(RAT_ERR_ARG, F + "the window must satisfy 0 <= t_lo <= t_hi <= N");
     bool fin = std::isfinite(b);
     for (int i = 0; i < d; ++i) fin = fin && std::isfinite(a[i]);
     if (Q) for (int i = 0; i < d * d; ++i) fin = fin && std::isfinite(Q[i]);
-    if (shift_in) for (int i = 0; i < N * n; ++i) fin = fin && std::isfinite(shift_in[i]);
+    if (shift_in) for (int i = 0; i < N * nc; ++i) fin = fin && std::isfinite(shift_in[i]);
     if (!fin) return fail(RAT_ERR_ARG, F + "Q, a, b and shift_in must be finite");
     HIPCHK(hipSetDevice(h->device));
     // the policy pack (pack_policy), then the event in the 12 + 4 tile (rat_policy_events' layout) and the shift
     rat_rc rc;
     PolicyPack pk;
-    if ((rc = pack_policy(h, x_nom, l, L, true, &pk))) return rc;
+    if ((rc = pack_policy(h, x_nom, l, L, kn.with_wchol, &pk))) return rc;
     std::vector<double> &pack = pk.data;
     const size_t o_q = pack.size(), o_a = o_q + 256, o_s = o_a + 16;
     pack.resize(o_s + (size_t)N * 12, 0.0);
@@ -2684,7 +2706,7 @@ extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const
         pack[o_a + tix(i)] = a[i];
         if (Q) for (int k = 0; k < d; ++k) pack[o_q + tix(k) * 16 + tix(i)] = Q[i + (size_t)d * k];
     }
-    if (shift_in) for (int t = 0; t < N; ++t) for (int i = 0; i < n; ++i) pack[o_s + (size_t)t * 12 + i] = shift_in[(size_t)t * n + i];
+    if (shift_in) for (int t = 0; t < N; ++t) for (int i = 0; i < nc; ++i) pack[o_s + (size_t)t * 12 + i] = shift_in[(size_t)t * nc + i];
     size_t cap_red = h->d_re_red ? RE_SCRATCH : 0;
     const size_t n_part = ((size_t)N * 12 + 3) * RE_SLOTS;
     if ((rc = grow(&h->d_re_in, &h->cap_re_in, pack.size()))) return rc;
@@ -2699,6 +2721,7 @@ extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const
     memset(&ra, 0, sizeof(ra));
     const PolicyDev dev = policy_dev(h->d_re_in, pk.o_x, pk.o_l, pk.o_L, L != nullptr);
     ra.pb = h->pb; ra.Wchol = dev.Wchol; ra.xnom = dev.x; ra.l = dev.l; ra.L = dev.L;
+    ra.pb.n = nc;                                                     // (the family: n itself.  re_update and re_elite_rng read the row's width here)
     ra.K = (long)K; ra.chunk = (long)mc_chunk(K);
     ra.shift = h->d_re_in + o_s; ra.Qt = h->d_re_in + o_q; ra.at = h->d_re_in + o_a; ra.b = b; ra.t_lo = t_lo; ra.t_hi = t_hi;
     ra.margin = h->d_re_margin; ra.logw = h->d_re_logw; ra.dom = h->d_re_dom; ra.scratch = h->d_re_red; ra.part = h->d_re_part;
@@ -2706,19 +2729,20 @@ extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const
     for (int j = 0; j < n_iter; ++j) {
         ra.seed = seed + RE_PASS_STRIDE * (uint64_t)(j + 1);
         ra.iter = j;
-        launch_re_rollout(ra, Q != nullptr, h->stream);
+        if ((rc = kn.rollout(ra, Q != nullptr))) return rc;
         launch_re_level(ra, rho, h->stream);
         HIPCHK(hipGetLastError());
         int code = 0;
         HIPCHK(hipMemcpyAsync(&code, h->d_re_red + RE_O_CTL, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
+        if (kn.waited && (rc = kn.waited())) return rc;
         ++n_run;
         if (code == 1) reached = 1;
         if (code != 0) break;                                         // gamma == 0, or nothing to rank: the shift stays
-        launch_re_adapt(ra, h->stream);
+        kn.adapt(ra, h->stream);
     }
     ra.seed = seed; ra.iter = 0; ra.reached = reached; ra.n_run = n_run;
-    launch_re_rollout(ra, Q != nullptr, h->stream);
+    if ((rc = kn.rollout(ra, Q != nullptr))) return rc;
     launch_re_final(ra, h->stream);
     HIPCHK(hipGetLastError());
     double out[RE_NSTAT], tr[RE_MAX_ITER * RE_NTRACE];
@@ -2729,10 +2753,98 @@ extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const
     if (margin_out) HIPCHK(hipMemcpyAsync(margin_out, h->d_re_margin, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
     if (logw_out) HIPCHK(hipMemcpyAsync(logw_out, h->d_re_logw, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    if (kn.waited && (rc = kn.waited())) return rc;
     for (int i = 0; i < RAT_RE_NSTAT; ++i) stats[i] = out[i];
-    if (shift_out) for (int t = 0; t < N; ++t) for (int i = 0; i < n; ++i) shift_out[(size_t)t * n + i] = sh[(size_t)t * 12 + i];
+    if (shift_out) for (int t = 0; t < N; ++t) for (int i = 0; i < nc; ++i) shift_out[(size_t)t * nc + i] = sh[(size_t)t * 12 + i];
     if (trace_out) for (int i = 0; i < n_iter * RAT_RE_NTRACE; ++i) trace_out[i] = (i < n_run * RAT_RE_NTRACE) ? tr[i] : std::nan("");
     return RAT_OK;
+}
+
+// The family rollout (re_rollout) with its process noise z_k = s_k + xi_k: the policy is packed by pack_policy like every evaluation's, into
+// buffers of the call's own, and the whole loop runs on the device.
+extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K, uint64_t seed,
+                                        const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi,
+                                        const double *shift_in, int32_t n_iter, double rho,
+                                        double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out) {
+    const std::string F = "rat_policy_rare_event: ";
+    rat_rc rc;
+    if ((rc = re_args_head(F, h, x_nom, l, a, stats, K, n_iter, rho))) return rc;
+    if (h->wide) return fail(RAT_ERR_UNSUPPORTED, F + "compiled for n <= 12, m <= 4 (the shift is defined on the family rollout)");
+    if (h->pb.model == RAT_MODEL_SOURCE) return fail(RAT_ERR_UNSUPPORTED, F + "not available for source models (the shift is defined on the family rollout)");
+    ReKernels kn;
+    kn.ncol = h->n; kn.with_wchol = true; kn.adapt = launch_re_adapt;
+    kn.rollout = [h](const ReArgs &ra, bool quad) { launch_re_rollout(ra, quad, h->stream); return RAT_OK; };
+    return re_run(h, F, kn, x_nom, l, L, K, seed, Q, a, b, t_lo, t_hi, shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
+}
+
+static rat_rc rare_noise_args_ok(const char *who, int n, int m, int npn, int npu) {
+    rat_rc rc;
+    if ((rc = user_noise_args_ok(who, n, m, npn, npu))) return rc;
+    if (npn == 0) return fail(RAT_ERR_ARG, std::string(who) + ": normals_per_step is 0: there is no normal to shift");
+    if (npn > 12) return fail(RAT_ERR_UNSUPPORTED, std::string(who) + ": normals_per_step is above 12 (the shift is laid out [N][12])");
+    return RAT_OK;
+}
+
+extern "C" rat_rc rat_rare_event_noise_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms) {
+    if (!source) return fail(RAT_ERR_ARG, "null");
+    rat_rc rc = rare_noise_args_ok("rat_rare_event_noise_check", n, m, normals, uniforms);
+    if (rc) return rc;
+    std::string log;
+    if ((rc = src_compile_rare(source, n, m, normals, uniforms, "gfx950", nullptr, &log))) return fail(rc, log);
+    return RAT_OK;
+}
+
+// The same for a source model under its rat_user_noise: rat_src_rare_rollout (source_rare.h, a hiprtc module of its own that the first call
+// with these draw counts compiles) shifts the normals the sampler draws, re_elite_rng replays rat_rng's stream.  W is not read.  One launch
+// per pass: the generator counts rollouts globally and nothing is staged.  The overdraw flag is read after every host wait.
+extern "C" rat_rc rat_policy_rare_event_noise(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
+                                              int32_t normals_per_step, int32_t uniforms_per_step, uint64_t seed,
+                                              const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi,
+                                              const double *shift_in, int32_t n_iter, double rho,
+                                              double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out) {
+    const std::string F = "rat_policy_rare_event_noise: ";
+    rat_rc rc;
+    if ((rc = re_args_head(F, h, x_nom, l, a, stats, K, n_iter, rho))) return rc;
+    if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
+        return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_noise; the families have rat_policy_rare_event)");
+    const int n = h->n, m = h->m, npn = normals_per_step, npu = uniforms_per_step;
+    if ((rc = rare_noise_args_ok("rat_policy_rare_event_noise", n, m, npn, npu))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->src_re || h->src_re_npn != npn || h->src_re_npu != npu) {
+        std::shared_ptr<const std::vector<char>> code;
+        std::string log;
+        if ((rc = src_compile_rare(h->src_text.c_str(), n, m, npn, npu, h->src_arch_name, &code, &log))) return fail(rc, log);
+        hipModule_t mod = nullptr;
+        hipFunction_t fn = nullptr;
+        if ((rc = load_module_function(code, "rat_src_rare_rollout", "rat_policy_rare_event_noise", &mod, &fn))) return rc;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->src_re_mod) (void)hipModuleUnload(h->src_re_mod);
+        h->src_re_mod = mod; h->src_re = fn; h->src_re_npn = npn; h->src_re_npu = npu;
+    }
+    if (!h->h_un_over && hipHostMalloc((void **)&h->h_un_over, sizeof(int), hipHostMallocDefault) != hipSuccess) {
+        h->h_un_over = nullptr;
+        return fail(RAT_ERR_HIP, F + "hipHostMalloc failed");
+    }
+    int *d_over = nullptr;
+    HIPCHK(hipHostGetDevicePointer((void **)&d_over, h->h_un_over, 0));
+    *h->h_un_over = 0;
+    ReKernels kn;
+    kn.ncol = npn; kn.with_wchol = false; kn.adapt = launch_re_adapt_rng;
+    kn.rollout = [h, d_over](const ReArgs &ra, bool quad) -> rat_rc {
+        SrcRareArgs sa;
+        sa.xnom = ra.xnom; sa.l = ra.l; sa.L = ra.L; sa.shift = ra.shift; sa.Qt = ra.Qt; sa.at = ra.at; sa.b = ra.b;
+        sa.t_lo = ra.t_lo; sa.t_hi = ra.t_hi; sa.quad = quad ? 1 : 0; sa.K = ra.K; sa.N = h->N; sa.tpw = h->src_mc_tpw; sa.seed = ra.seed;
+        sa.margin = ra.margin; sa.logw = ra.logw; sa.dom = ra.dom; sa.p = h->d_src_p; sa.overdraw = d_over;
+        void *args[] = {&sa};
+        HIPCHK(hipModuleLaunchKernel(h->src_re, (unsigned)((ra.K + sa.tpw - 1) / sa.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+        return RAT_OK;
+    };
+    kn.waited = [h, npn, npu, &F]() -> rat_rc {
+        if (*(volatile int *)h->h_un_over == 0) return RAT_OK;
+        return fail(RAT_ERR_ARG, F + "a step drew more than was declared (normals_per_step = " + std::to_string(npn) +
+                                 ", uniforms_per_step = " + std::to_string(npu) + "): the overdrawn values were NaN");
+    };
+    return re_run(h, F, kn, x_nom, l, L, K, seed, Q, a, b, t_lo, t_hi, shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
 }
 
 static rat_rc linearize_slot0(rat_handle h, const double *u, const double *x, std::vector<double> *tiles, int32_t *domain_fail) {

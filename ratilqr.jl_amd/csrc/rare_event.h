@@ -17,6 +17,12 @@
 // inside a pass the rollouts are keyed as rat_policy_evaluate keys them: chunks of min(K, 2^16) rollouts, chunk c under the Philox key
 // seed_p + 0x9E3779B97F4A7C15 c, counter (index within the chunk, 0, t >> 1, component), one Box-Muller transform per step pair.  With
 // n_iter == 0 and no shift the final pass therefore draws rat_policy_evaluate's noise at the same seed.
+//
+// rat_policy_rare_event_noise (a source model under its rat_user_noise) runs the same chain with two kernels of its own: the rollout is
+// rat_src_rare_rollout (source_rare.h, a hiprtc module) and the elite sum re_elite_rng.  The shift is [N][P] in the same [N][12] layout,
+// P = normals_per_step <= 12, entry (t, i) shifting the i-th rng.normal() of step t; ReArgs.pb.n holds P for re_elite_rng and re_update.
+// Its passes have the same seeds seed_p; inside a pass the keying is rat_rng's: the global rollout index in the counter (g lo, g hi, t,
+// i >> 1), key seed_p, no chunks -- rat_policy_evaluate_noise's generator at seed_p.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -68,5 +74,8 @@ void launch_re_rollout(const ReArgs &a, bool quad, hipStream_t s);
 void launch_re_level(const ReArgs &a, double rho, hipStream_t s);
 // re_pass_a, re_elite, re_update
 void launch_re_adapt(const ReArgs &a, hipStream_t s);
+// the same for rat_policy_rare_event_noise: re_pass_a, re_elite_rng (rat_rng's stream: pb.n holds P, the normals per step; seed is seed_p,
+// Wchol / xnom / l / L / chunk are not read), re_update
+void launch_re_adapt_rng(const ReArgs &a, hipStream_t s);
 // re_pass_a, re_pass_b, re_final: the stats are a.scratch + RE_O_STATS
 void launch_re_final(const ReArgs &a, hipStream_t s);

@@ -324,6 +324,53 @@ __global__ __launch_bounds__(MC_THREADS) void re_elite(ReArgs a) {
     }
 }
 
+// re_elite for rat_rng's stream (rat_policy_rare_event_noise; a.pb.n is P, the normals a step declares): one workgroup per (slot, step),
+// the same lanes, trips, tree and slot order.  An elite rollout replays the ceil(P / 2) Philox blocks of step t -- counter (g lo, g hi,
+// t, q) with g the global rollout index, key seed_p, one Box-Muller transform each: normals 2 q and 2 q + 1 (rat_rng.h) -- whether or not
+// the rollout drew them: a component it did not draw adds sampling noise to the update and no bias to the estimate.  The workgroups of
+// step 0 also sum w, w^2 and the elite count.
+__global__ __launch_bounds__(MC_THREADS) void re_elite_rng(ReArgs a) {
+    __shared__ double sh[4 * MC_THREADS];
+    const int slot = blockIdx.x, t = blockIdx.y, tid = threadIdx.x, N = a.pb.N, P = a.pb.n;
+    const double lmax = re_head(a.scratch, sh).lmax, gamma = a.scratch[RE_O_LVL];
+    double acc[12], sw[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < 12; ++c) acc[c] = 0.0;
+    const long T = (long)RE_SLOTS * MC_THREADS;
+    for (long i = (long)slot * MC_THREADS + tid; i < a.K; i += T) {
+        if (!(a.margin[i] >= gamma)) continue;                        // (NaN margins -- DomainError rollouts among them -- are no elite)
+        const double wt = exp(a.logw[i] - lmax);
+        sw[0] += wt; sw[1] += wt * wt; sw[2] += 1.0;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            if (2 * q < P) {                                          // (uniform over the grid)
+                unsigned rr[4];
+                double z0, z1;
+                philox4x32_10((unsigned)i, (unsigned)(i >> 32), (unsigned)t, (unsigned)q, (unsigned)a.seed, (unsigned)(a.seed >> 32), rr);
+                ratn_box_muller(u01(rr[0], rr[1]), u01(rr[2], rr[3]), &z0, &z1);
+                acc[2 * q] += wt * z0;
+                acc[2 * q + 1] += wt * z1;                            // (the spare output of an odd P: never stored)
+            }
+        }
+    }
+#pragma unroll
+    for (int c0 = 0; c0 < 12; c0 += 4) {
+        if (c0 >= P) break;                                           // (uniform over the grid)
+        double v[4] = {acc[c0], acc[c0 + 1], acc[c0 + 2], acc[c0 + 3]};
+        block_tree_n<4>(v, sh);
+        if (tid == 0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (c0 + q < P) a.part[((size_t)t * 12 + c0 + q) * RE_SLOTS + slot] = v[q];
+        }
+    }
+    if (t == 0) {
+        block_tree_n<3>(sw, sh);
+        if (tid == 0)
+            for (int q = 0; q < 3; ++q) a.part[((size_t)N * 12 + q) * RE_SLOTS + slot] = sw[q];
+    }
+}
+
 __device__ __forceinline__ double re_slot_sum(const double *part, size_t e) {
     double v = 0.0;
     for (int s = 0; s < RE_SLOTS; ++s) v += part[e * RE_SLOTS + s];
@@ -386,6 +433,12 @@ void launch_re_level(const ReArgs &a, double rho, hipStream_t s) {
 void launch_re_adapt(const ReArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(re_pass_a, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
     hipLaunchKernelGGL(re_elite, dim3(RE_SLOTS, (unsigned)((a.pb.N + 1) / 2)), dim3(MC_THREADS), 0, s, a);
+    hipLaunchKernelGGL(re_update, dim3(1), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_re_adapt_rng(const ReArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(re_pass_a, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
+    hipLaunchKernelGGL(re_elite_rng, dim3(RE_SLOTS, (unsigned)a.pb.N), dim3(MC_THREADS), 0, s, a);
     hipLaunchKernelGGL(re_update, dim3(1), dim3(MC_THREADS), 0, s, a);
 }
 

@@ -75,3 +75,26 @@ struct SrcUserNoisyArgs {
     const double *p;          // the model's parameters
     int *overdraw;            // set (plain store) when a step draws more than was declared: 1 normals, 2 uniforms
 };
+
+// rat_src_rare_rollout (source_rare.h): rat_src_user_noisy_rollout under a shifted proposal on rng.normal(), with the margin of one event
+// in place of the trajectory and the cost (rat_policy_rare_event_noise); the generator only
+struct SrcRareArgs {
+    const double *xnom;       // [(N+1)][12] nominal states (open loop: only row 0 is read)
+    const double *l;          // [N][4]
+    const double *L;          // [N][4][12] or null (open loop)
+    const double *shift;      // [N][12] s, zero padded: entry i of row t shifts the i-th normal of step t
+    const double *Qt;         // [16][16] in the tile as ev_eval reads it, or unused (quad == 0)
+    const double *at;         // [16] in the tile
+    double b;
+    int t_lo, t_hi;
+    int quad;                 // the event has a matrix
+    long K;
+    int N;
+    int tpw;                  // rollouts per wavefront (lanes 0 .. tpw-1 of each 64-lane workgroup carry one)
+    unsigned long long seed;  // seed_p of this pass: the Philox key; the global rollout index is the counter
+    double *margin;           // [K] M, NaN for a DomainError rollout
+    double *logw;             // [K]
+    int *dom;                 // [K]
+    const double *p;          // the model's parameters
+    int *overdraw;            // set (plain store) when a step draws more than was declared: 1 normals, 2 uniforms
+};

@@ -32,7 +32,8 @@ struct Rtc {
 std::mutex g_mu;
 Rtc g_rtc;
 // key: (source, n, m, kind (0 risk-sensitive, 1 generative, 2 the risk-sensitive model's Monte-Carlo rollout, 3 that rollout under the
-// user's noise sampler), normals per step, uniforms per step, architecture)
+// user's noise sampler, 4 that rollout under a shifted proposal with an event's margin: source_rare.h), normals per step, uniforms per step,
+// architecture)
 std::map<std::tuple<std::string, int, int, int, int, int, std::string>, std::shared_ptr<const std::vector<char>>> g_cache;
 
 bool rtc_load(std::string *why) {           // (g_mu held)
@@ -91,17 +92,19 @@ static rat_rc compile_impl(const char *source, int n, int m, int kind, int npn, 
     // the user's source between the AD and rat_rng headers and the kernels (a source that defines all four functions compiles as either
     // kind); #line makes the compiler's messages name lines of the user's text.  A generative source does not define rat_user_f:
     // source_kernels.h is not part of its text
-    const std::string text = std::string("#include \"source_args.h\"\n#include \"rat_ad.h\"\n#include \"rat_rng.h\"\n#line 1 \"model.hip\"\n") +
+    const std::string text = std::string(kind == 4 ? "#define RAT_RNG_SHIFT 1\n" : "") + "#include \"source_args.h\"\n#include \"rat_ad.h\"\n#include \"rat_rng.h\"\n#line 1 \"model.hip\"\n" +
                              source + (kind == 0 ? "\n#line 1 \"source_kernels.h\"\n#include \"source_kernels.h\"\n"
                                       : kind == 2 ? "\n#line 1 \"source_noisy.h\"\n#include \"source_noisy.h\"\n"
                                       : kind == 3 ? "\n#line 1 \"source_user_noise.h\"\n#include \"source_user_noise.h\"\n"
+                                      : kind == 4 ? "\n#line 1 \"source_rare.h\"\n#include \"source_rare.h\"\n"
                                                   : "\n#line 1 \"source_pets.h\"\n#include \"source_pets.h\"\n");
     const char *hdr[] = {k_embed_layout_h, k_embed_source_args_h, k_embed_rat_ad_h, k_embed_source_kernels_h, k_embed_rat_normal_h,
-                         k_embed_rat_philox_h, k_embed_rat_rng_h, k_embed_source_pets_h, k_embed_source_noisy_h, k_embed_source_user_noise_h};
+                         k_embed_rat_philox_h, k_embed_rat_rng_h, k_embed_source_pets_h, k_embed_source_noisy_h, k_embed_source_user_noise_h,
+                         k_embed_source_rare_h};
     const char *hdr_names[] = {"layout.h", "source_args.h", "rat_ad.h", "source_kernels.h", "rat_normal.h", "rat_philox.h", "rat_rng.h",
-                               "source_pets.h", "source_noisy.h", "source_user_noise.h"};
+                               "source_pets.h", "source_noisy.h", "source_user_noise.h", "source_rare.h"};
     hiprtcProgram prog = nullptr;
-    if (g_rtc.create(&prog, text.c_str(), "model.hip", 10, hdr, hdr_names) != HIPRTC_SUCCESS) {
+    if (g_rtc.create(&prog, text.c_str(), "model.hip", 11, hdr, hdr_names) != HIPRTC_SUCCESS) {
         if (log) *log = "hiprtcCreateProgram failed";
         return done(RAT_ERR_ARG);
     }
@@ -155,4 +158,9 @@ rat_rc src_compile_noisy(const char *source, int n, int m, const std::string &ar
 rat_rc src_compile_user_noise(const char *source, int n, int m, int npn, int npu, const std::string &arch,
                               std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
     return compile_impl(source, n, m, 3, npn, npu, arch, code, log, ms, cached);
+}
+
+rat_rc src_compile_rare(const char *source, int n, int m, int npn, int npu, const std::string &arch,
+                        std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
+    return compile_impl(source, n, m, 4, npn, npu, arch, code, log, ms, cached);
 }

@@ -26,5 +26,9 @@ rat_rc src_compile_noisy(const char *source, int n, int m, const std::string &ar
 // RAT_USER_NOISE and rat_user_noise; -DRAT_PETS_NORMALS=npn -DRAT_PETS_UNIFORMS=npu.  A fourth kind, compiled on the first such evaluation.
 rat_rc src_compile_user_noise(const char *source, int n, int m, int npn, int npu, const std::string &arch,
                               std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
+// That rollout under a shifted proposal with the margin of one event (rat_policy_rare_event_noise): source_rare.h after the source, and
+// "#define RAT_RNG_SHIFT 1" in front of rat_rng.h -- the only kind that defines it.  A fifth kind, compiled on the first such call.
+rat_rc src_compile_rare(const char *source, int n, int m, int npn, int npu, const std::string &arch,
+                        std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
 // The offload-arch string for the device's reported gcnArchName (an xnack+ feature is never passed on).
 std::string src_arch(const char *gcn_arch_name);

@@ -1,0 +1,176 @@
+// source_rare.h -- the rollout kernel of rat_policy_rare_event_noise (include/ratilqr.h): a source model under its rat_user_noise, the
+// normals drawn from a shifted proposal, and the margin of one safety event in place of the trajectory and the cost.  Compiled by hiprtc
+// behind rat_rng.h -- with RAT_RNG_SHIFT, which this module alone defines (source_model.cpp puts it in front of rat_rng.h) -- and the
+// user's source, which defines RAT_USER_NOISE and rat_user_noise; RAT_N, RAT_M, RAT_PETS_NORMALS, RAT_PETS_UNIFORMS come from the command
+// line.  A module of its own, compiled by the first call that needs it.  The library embeds this header (Makefile: source_embed.inc).
+//
+// Rollout part: one lane per rollout, the step of rat_src_user_noisy_rollout (source_user_noise.h) operation for operation -- the
+// feedback sums in its order, c, the sampler, f, its DomainError rule (c and h are evaluated for that rule alone: no cost is formed) --
+// with the generator keyed as there: the global rollout index in the Philox counter, the pass's seed as the key.  rng.normal() returns
+// shift[t][i] + xi and adds -s z + s^2 / 2 to the lane's logw (rat_rng.h); the step's shift row is one address for the wavefront, so
+// its loads are scalar or broadcast.
+// Margin part: g(t, z) = z' Q z + a' z + b of z = (x_t, u_t) as ev_eval (policy_mc.hip) and re_g (rare_event.hip) form it, so that under
+// a zero shift the margins are rat_policy_events' bit for bit.  Every lane puts its (x_t, u_t) in the 12 + 4 tile order into row `lane`
+// of a wavefront-private LDS block (64 rows, stride 17: the sixteen columns of a group fall in different banks); the wavefront then
+// walks the four groups of sixteen rollouts: in group c lane (col = lane & 15, kq = lane >> 4) loads Z[kq + 4 r][16 c + col], r = 0 .. 3,
+// and forms g -- the a' z products, the four v_mfma_f64_16x16x4 of Q Z, the c . z products, the butterfly over the four kq lanes -- and
+// the lane with kq == c, which is lane 16 c + col, the owner of that rollout, keeps the value.  No lane leaves early: lanes without a
+// rollout (the K tail, lane >= tpw) skip the rollout part, hold zeros, take part in every group and store nothing.
+#pragma once
+#include "rat_rng.h"
+#include "source_args.h"
+
+#if !defined(RAT_N) || !defined(RAT_M)
+#error "RAT_N and RAT_M must be defined"
+#endif
+#if RAT_N > SRC_MAX_N || RAT_M > SRC_MAX_M
+#error "source models are compiled for n <= 12, m <= 4"
+#endif
+#ifndef RAT_RNG_SHIFT
+#error "source_rare.h is compiled with RAT_RNG_SHIFT in front of rat_rng.h"
+#endif
+#ifndef RAT_USER_NOISE
+#error "the source does not define RAT_USER_NOISE: rat_policy_rare_event_noise needs '#define RAT_USER_NOISE' and rat_user_noise(k, x, u, rng, w, p)"
+#endif
+#if RAT_PETS_NORMALS < 1 || RAT_PETS_NORMALS > 12
+#error "rat_policy_rare_event_noise shifts 1 .. 12 normals per step"
+#endif
+
+#define SRCRE_LD 17
+#define SRCRE_SYNC() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront")
+
+typedef double srcre_d4 __attribute__((ext_vector_type(4)));
+
+__device__ inline bool srcre_nan(double v) { return v != v; }
+
+// __shfl_xor(v, mask) over the 64 lanes (no <hip/hip_runtime.h> under hiprtc): both halves through ds_bpermute
+__device__ __forceinline__ double srcre_xor(double v, int lane, int mask) {
+    int w[2];
+    __builtin_memcpy(w, &v, 8);
+    const int src = (lane ^ mask) << 2;
+    w[0] = __builtin_amdgcn_ds_bpermute(src, w[0]);
+    w[1] = __builtin_amdgcn_ds_bpermute(src, w[1]);
+    double r;
+    __builtin_memcpy(&r, w, 8);
+    return r;
+}
+
+// g(z) of the lane's column, re_g of rare_event.hip: every lane of the column returns the same bits
+template <bool QUAD>
+__device__ __forceinline__ double srcre_g(const double (&zv)[4], const double *s_a, const double *s_q, int lane, int kq, int col, double b) {
+    const double *ae = s_a + kq;
+    double p = ae[0] * zv[0] + ae[4] * zv[1] + ae[8] * zv[2] + ae[12] * zv[3];
+    if (QUAD) {
+        const double *qe = s_q + kq * 16 + col;
+        srcre_d4 c = (srcre_d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) c = __builtin_amdgcn_mfma_f64_16x16x4f64(qe[kb * 64], zv[kb], c, 0, 0, 0);
+        p += c[0] * zv[0] + c[1] * zv[1] + c[2] * zv[2] + c[3] * zv[3];
+    }
+    p += srcre_xor(p, lane, 16);
+    p += srcre_xor(p, lane, 32);
+    return p + b;
+}
+
+extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArgs a) {
+    __shared__ double s_q[256], s_a[16], s_z[64 * SRCRE_LD];
+    const int lane = threadIdx.x, col = lane & 15, kq = lane >> 4;
+    const long j = (long)blockIdx.x * a.tpw + lane;
+    const bool live = lane < a.tpw && j < a.K;
+    const int N = a.N;
+    if (a.quad) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s_q[lane + 64 * q] = a.Qt[lane + 64 * q];
+    }
+    if (lane < 16) s_a[lane] = a.at[lane];
+    __syncthreads();
+    rat_rng rng;
+    rng.gen = true;
+    rng.zn = nullptr; rng.zu = nullptr;
+    rng.g0 = (unsigned)j; rng.g1 = (unsigned)(j >> 32); rng.t = 0;
+    rng.k0 = (unsigned)a.seed; rng.k1 = (unsigned)(a.seed >> 32);
+    rng.in = 0; rng.iu = 0; rng.over = 0; rng.spare_n = 0.0; rng.spare_u = 0.0;
+    rng.shift = a.shift; rng.logw = 0.0;
+    double x[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) x[q] = (live && q < RAT_N) ? a.xnom[q] : 0.0;
+    const double nan = __builtin_nan("");
+    double M = nan;
+    int dom = 0;
+    double *row = s_z + lane * SRCRE_LD;
+    for (int t = 0;; ++t) {
+        double u[4] = {0.0, 0.0, 0.0, 0.0};
+        if (live && t < N) {
+            if (a.L) {
+                double dx[12];
+#pragma unroll
+                for (int q = 0; q < 12; ++q) dx[q] = x[q] - a.xnom[(long)t * XSTR + q];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const double *Lr = a.L + (long)t * LSTR + i * 12;
+                    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {                     // L_t (x_t - xbar_t), rat_src_user_noisy_rollout's order
+                        a0 = __builtin_fma(Lr[q], dx[q], a0);
+                        a1 = __builtin_fma(Lr[4 + q], dx[4 + q], a1);
+                        a2 = __builtin_fma(Lr[8 + q], dx[8 + q], a2);
+                    }
+                    u[i] = a.l[(long)t * USTR + i] + ((a0 + a1) + a2);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) u[i] = a.l[(long)t * USTR + i];
+            }
+        }
+        if (t >= a.t_lo && t <= a.t_hi) {                             // (uniform over the grid)
+#pragma unroll
+            for (int q = 0; q < 12; ++q) row[q] = (q < RAT_N) ? x[q] : 0.0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) row[12 + q] = (q < RAT_M) ? u[q] : 0.0;   // (u is 0 at t == N and on a lane without a rollout)
+            SRCRE_SYNC();
+            double gv = 0.0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const double *zc = s_z + (16 * c + col) * SRCRE_LD + kq;
+                const double zv[4] = {zc[0], zc[4], zc[8], zc[12]};
+                const double gc = a.quad ? srcre_g<true>(zv, s_a, s_q, lane, kq, col, a.b) : srcre_g<false>(zv, s_a, s_q, lane, kq, col, a.b);
+                if (kq == c) gv = gc;                                 // lane 16 c + col owns rollout 16 c + col of the wavefront
+            }
+            SRCRE_SYNC();
+            if (gv > M || srcre_nan(M)) M = gv;                       // (a NaN g never replaces a number)
+        }
+        if (t == N) break;
+        if (live) {
+            bool inok = true;
+#pragma unroll
+            for (int q = 0; q < RAT_N; ++q) inok = inok && !srcre_nan(x[q]);
+#pragma unroll
+            for (int q = 0; q < RAT_M; ++q) inok = inok && !srcre_nan(u[q]);
+            const double ct = rat_user_c<double>(t, x, u, a.p);       // (for the DomainError rule alone)
+            rng.t = (unsigned)t; rng.in = 0; rng.iu = 0;
+            rng.shift = a.shift + t * 12;
+            double w[RAT_N];
+#pragma unroll
+            for (int q = 0; q < RAT_N; ++q) w[q] = 0.0;
+            rat_user_noise(t, x, u, rng, w, a.p);
+            double xn[RAT_N];
+            rat_user_f<double>(x, u, xn, a.p);
+            bool outnan = srcre_nan(ct);
+#pragma unroll
+            for (int q = 0; q < RAT_N; ++q) outnan = outnan || srcre_nan(xn[q]) || srcre_nan(w[q]);
+            if (inok && outnan) dom = 1;                              // the reference's DomainError, and a NaN disturbance
+#pragma unroll
+            for (int q = 0; q < RAT_N; ++q) x[q] = xn[q] + w[q];      // x_{t+1} = f(x_t, u_t) + w_t
+        }
+    }
+    if (!live) return;                                                // (behind the last group: nothing follows that needs the lane)
+    bool inok = true;
+#pragma unroll
+    for (int q = 0; q < RAT_N; ++q) inok = inok && !srcre_nan(x[q]);
+    const double hc = rat_user_h<double>(x, a.p);
+    if (inok && srcre_nan(hc)) dom = 1;
+    a.margin[j] = dom ? nan : M;
+    a.logw[j] = rng.logw;
+    a.dom[j] = dom;
+    if (rng.over) *a.overdraw = rng.over;
+}

@@ -199,6 +199,9 @@ class GenericContext(il.Context):
     def policy_events(self, *a, **k):
         self._carrier_only("policy_events")
 
+    def policy_rare_event_noise(self, *a, **k):
+        self._carrier_only("policy_rare_event_noise")
+
     def solve_batch(self, *a, **k):
         self._carrier_only("solve_batch")
 

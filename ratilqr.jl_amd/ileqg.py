@@ -116,8 +116,8 @@ def kl_event_bound(p, d):
 
 @dataclass
 class RareEventResult:
-    """What Context.policy_rare_event returns: the RAT_RE_* slots of the header as fields (flag: 0 OK, 1 the level never reached 0, 2 no OK
-    rollout, 3 non-finite), the shift (N, n) the final pass ran under, the trace (n_iter, 4) -- level, elite count, elite effective sample
+    """What Context.policy_rare_event / policy_rare_event_noise return: the RAT_RE_* slots of the header as fields (flag: 0 OK, 1 the level
+    never reached 0, 2 no OK rollout, 3 non-finite), the shift (N, n) -- (N, normals_per_step) under user noise -- the final pass ran under, the trace (n_iter, 4) -- level, elite count, elite effective sample
     size, |shift| per adaptation iteration, NaN where none ran -- and, on request, the margins and log-weights (K,) of the final pass."""
     prob: float
     prob_se: float
@@ -415,6 +415,42 @@ class Context:
             r[k] = int(r[k])
         return RareEventResult(shift=s_out, trace=trace, margins=margins, logw=logw, **r)
 
+    def policy_rare_event_noise(self, x_nom, l, L, event, K, noise=None, seed=None, shift=None, n_iter=8, rho=0.1, want_margins=False,
+                                want_logw=False):
+        """policy_rare_event for a source problem under the disturbance its own rat_user_noise draws (rat_policy_rare_event_noise): noise
+        is a UserNoise without injected streams (the device generator only); the proposal shifts the normals the sampler draws -- the
+        i-th rng.normal() of step t returns shift[t, i] + xi -- so the shift is (N, P), P = noise.normals_per_step in 1 .. 12.
+        rng.uniform() is not shifted: an event that a uniform drives cannot be made likelier by this call.  seed None: the UserNoise's.
+        With n_iter=0 and no shift the margins are policy_events' behind policy_evaluate_noise at the same seed, bit for bit.
+        Returns a RareEventResult."""
+        if not isinstance(noise, UserNoise):
+            raise TypeError("policy_rare_event_noise needs noise=UserNoise(...)")
+        if noise.zn is not None or noise.zu is not None:
+            raise ValueError("policy_rare_event_noise draws from the device generator only: no injected streams")
+        n, m, N, npn, npu = self.n, self.m, self.N, noise.normals_per_step, noise.uniforms_per_step
+        Q, a, b, lo, hi = event.dense(n, m, N)
+        Qc = nv.f64(Q.T) if Q is not None else None                   # column-major
+        a = nv.f64(a)
+        s_in = None
+        if shift is not None:
+            s_in = nv.f64(shift)
+            if s_in.shape != (N, npn):
+                raise ValueError(f"policy_rare_event_noise: the shift is {s_in.shape}, (N, normals_per_step) = ({N}, {npn}) is served")
+        K, n_iter = int(K), int(n_iter)
+        seed = noise.seed if seed is None else int(seed)
+        stats, s_out, trace = np.zeros(nv.RE_NSTAT), np.zeros((N, max(npn, 1))), np.zeros((max(n_iter, 0), nv.RE_NTRACE))
+        margins = np.zeros(max(K, 1)) if want_margins else None
+        logw = np.zeros(max(K, 1)) if want_logw else None
+        nv.check(nv.lib().rat_policy_rare_event_noise(self.h, nv.P(nv.f64(x_nom)), nv.P(nv.f64(l)), nv.P(nv.cm3(L)) if L is not None else None,
+                                                      C.c_int64(K), C.c_int32(npn), C.c_int32(npu), C.c_uint64(seed), nv.P(Qc), nv.P(a),
+                                                      C.c_double(b), C.c_int32(lo), C.c_int32(hi), nv.P(s_in), C.c_int32(n_iter),
+                                                      C.c_double(float(rho)), nv.P(stats), nv.P(s_out), nv.P(trace) if n_iter > 0 else None,
+                                                      nv.P(margins), nv.P(logw)))
+        r = {k: float(stats[i]) for i, k in enumerate(nv.RE_SLOTS)}
+        for k in ("n_viol", "n_ok", "n_domain", "flag", "n_iter"):
+            r[k] = int(r[k])
+        return RareEventResult(shift=s_out, trace=trace, margins=margins, logw=logw, **r)
+
     def integrate_cost(self, x, u):
         out = C.c_double()
         nv.check(nv.lib().rat_integrate_cost(self.h, nv.P(nv.f64(x)), nv.P(nv.f64(u)), C.byref(out)))
@@ -702,6 +738,14 @@ def rare_event_probability(problem, x, l, L, event, K=1 << 16, seed=0, shift=Non
     returns an estimate with its standard error."""
     return _ctx(problem).policy_rare_event(x, l, L, event, K, seed=seed, shift=shift, n_iter=n_iter, rho=rho, want_margins=want_margins,
                                            want_logw=want_logw)
+
+
+def rare_event_probability_noise(problem, x, l, L, event, noise, K=1 << 16, seed=None, shift=None, n_iter=8, rho=0.1, want_margins=False,
+                                 want_logw=False):
+    """rare_event_probability for a source problem under the disturbance its own rat_user_noise draws: Context.policy_rare_event_noise on
+    the problem's default context.  noise is a UserNoise (the device generator only); the shift is (N, noise.normals_per_step)."""
+    return _ctx(problem).policy_rare_event_noise(x, l, L, event, K, noise=noise, seed=seed, shift=shift, n_iter=n_iter, rho=rho,
+                                                 want_margins=want_margins, want_logw=want_logw)
 
 
 def integrate_cost(problem, x_array, u_array):          # ileqg.jl:115-124
