@@ -143,6 +143,19 @@ rat_rc rat_problem_set(rat_handle h, const rat_problem_desc *desc);
  * depend on them; w arrives zeroed.  rng is the rat_rng of generative source models (below): rng.normal() is N(0, 1), rng.uniform() is
  * U[0, 1), counted per step against the draw counts the caller declares, which the compile line carries as RAT_PETS_NORMALS and
  * RAT_PETS_UNIFORMS.  A source without RAT_USER_NOISE compiles and behaves exactly as before.
+ * Optionally, for safety events of the user's own (rat_policy_events_user, rat_policy_rare_event_user, below), the source defines
+ * RAT_USER_EVENT and
+ *
+ *   __device__ void rat_user_event(int k, const double *x, const double *u, double *g, const double *p);
+ *
+ * called once per step k = 0 .. N for all events: x has RAT_N entries, u has RAT_M entries and is all zeros at k = N (u_N = 0, as in
+ * rat_policy_events).  double only: no AD type is involved.  The caller declares the number of events, n_event in 1 .. 16, which the
+ * compile line carries as RAT_N_EVENT.  g[0 .. RAT_N_EVENT) ARRIVES AS NaN: an entry the function leaves alone is "not watched at this
+ * step" and is passed over exactly as a NaN g of a quadratic event is -- this is how a window is written.  g_i > 0 means violated.  In
+ * the kernel g is a local array of 16 doubles, whatever RAT_N_EVENT is.  RAT_N_EVENT is defined only while an event kernel is compiled
+ * (the whole text is compiled when the problem is set, too).  The event reads p like f, c and h: rat_problem_set_params moves an
+ * obstacle without a new evaluation, since the replay guard holds the replayed costs against the stored ones and an event parameter
+ * moves no cost.  A source without RAT_USER_EVENT compiles and behaves exactly as before.
  * Limits: n <= 12, m <= 4 (else RAT_ERR_UNSUPPORTED); batches run on the round-based path (rat_set_path FUSED / BLOCK return
  * RAT_ERR_UNSUPPORTED); rat_rollout_noisy and rat_multi are not available for source models: rat_policy_evaluate with cost_out is the way
  * to their Monte-Carlo costs, and rat_policy_evaluate_noise with x_out / u_out the way to Monte-Carlo trajectories (under the user's
@@ -162,6 +175,9 @@ rat_rc rat_source_check(const char *source, int32_t n, int32_t m);
 /* The same for the kernel of rat_policy_evaluate_noise: `source` must define RAT_USER_NOISE and rat_user_noise (else RAT_ERR_ARG, and the
  * message says so); negative draw counts are RAT_ERR_ARG. */
 rat_rc rat_user_noise_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms);
+/* The same for the kernel of rat_policy_events_user: `source` must define RAT_USER_EVENT and rat_user_event (else RAT_ERR_ARG, and the
+ * message says so); n_event outside 1 .. 16 is RAT_ERR_ARG. */
+rat_rc rat_user_event_check(const char *source, int32_t n, int32_t m, int32_t n_event);
 
 /* ---- the hot path ----------------------------------------------------------------------------- */
 
@@ -393,6 +409,19 @@ rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double *Q, const d
                          const int32_t *t_lo, const int32_t *t_hi,
                          const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
                          double *rows_out, double *event_out, double *step_out, double *margin_out);
+/* rat_policy_events for events the user writes: g_i(k, x_k, u_k), i < n_event, is what the source's rat_user_event ("source models"
+ * above) leaves in g[i] at step k -- a NaN entry is passed over, g_i > 0 is violated, u_N = 0 -- in place of Q, a, b, t_lo, t_hi.  A
+ * moving obstacle, an intersection of half-spaces (a min), any function of the state: one call per step serves all events.  M, tau, the
+ * event "any" at index n_event, the replay and its guard, kl_bound / theta, rows_out, event_out (RAT_EV_*), step_out, margin_out, the
+ * 64 MiB limit on the partial sums and PROB_ROBUST are rat_policy_events' in every respect.  Served: exactly the replays
+ * rat_policy_events serves for a source model -- an evaluation recorded by rat_policy_evaluate_noise on the device generator; the rest
+ * is refused with that call's codes.  The kernel is compiled by the first call that names this n_event (cached per process by source,
+ * n, m, n_event and architecture).  RAT_ERR_UNSUPPORTED: the problem is not a source model.  RAT_ERR_ARG: a source without
+ * RAT_USER_EVENT (the message says what to define) or one whose event does not compile, with the compiler's log (model.hip:LINE) in
+ * rat_last_error() -- the handle stays usable; n_event outside 1 .. 16. */
+rat_rc rat_policy_events_user(rat_handle h, int32_t n_event,
+                              const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                              double *rows_out, double *event_out, double *step_out, double *margin_out);
 /* The largest probability p' an event of probability p can have under any distribution within KL radius d of the sampling one:
  * max { p' : p' log(p' / p) + (1 - p') log((1 - p') / (1 - p)) <= d }, by bisection on [p, 1] until the bracket stops shrinking: two neighbouring doubles, of which the one whose KL is nearer d is returned.  Host
  * only: needs no handle and no GPU.  d == 0 gives p; p == 0 gives 0; p == 1 gives 1; d == +Inf with p > 0 gives 1.  NaN, p outside
@@ -490,6 +519,22 @@ rat_rc rat_policy_rare_event_noise(rat_handle h, const double *x_nom, const doub
  * rat_last_error() (a source without RAT_USER_NOISE among them), for negative counts and for normals == 0; RAT_ERR_UNSUPPORTED for
  * normals > 12, n > 12 or m > 4. */
 rat_rc rat_rare_event_noise_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms);
+/* rat_policy_rare_event_noise with entry `event` (0 .. n_event - 1, else RAT_ERR_ARG) of the user's rat_user_event in place of Q, a, b,
+ * t_lo, t_hi: M is the largest g[event] over the steps k = 0 .. N at which the function wrote it (NaN where it wrote none: such a
+ * rollout is no elite and does not violate), u_N = 0.  Everything else -- the keying, the shifted normals and the sequential likelihood
+ * ratio, the level, the elite, the update, stats[RAT_RE_NSTAT] and the flags, the overdraw rule, shift / trace / margin / logw -- is
+ * that call's.  With n_iter == 0 and shift_in == NULL margin_out is row `event` of rat_policy_events_user's margin_out behind
+ * rat_policy_evaluate_noise at that seed, bit for bit.  The kernel is the rollout kernel's second variant, cached per process by
+ * (source, n, m, normals, uniforms, n_event, architecture).  RAT_ERR_ARG besides: n_event outside 1 .. 16, a source without
+ * RAT_USER_EVENT.  No user events for the family call rat_policy_rare_event. */
+rat_rc rat_policy_rare_event_user(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
+                                  int32_t normals_per_step, int32_t uniforms_per_step, uint64_t seed,
+                                  int32_t n_event, int32_t event,
+                                  const double *shift_in, int32_t n_iter, double rho,
+                                  double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out);
+/* Compile only, for gfx950 (no device needed), the kernel of rat_policy_rare_event_user: rat_rare_event_noise_check's codes, and
+ * RAT_ERR_ARG for n_event outside 1 .. 16 or a source without RAT_USER_EVENT. */
+rat_rc rat_rare_event_user_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms, int32_t n_event);
 /* approximate_model(problem, u_array, x_array)                 ileqg.jl:258-322
  * -> q[N+1], qv[n*(N+1)], Q[n*n*(N+1)], r[m*N], R[m*m*N], P[m*n*N], A[n*n*N], B[n*m*N], W[n*n*N] */
 rat_rc rat_approximate_model(rat_handle h, const double *u, const double *x,

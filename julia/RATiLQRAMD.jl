@@ -483,6 +483,32 @@ function policy_events(s::ILEQGSolver, Q::Union{Nothing,Array{Float64,3}}, a::Ma
     (rows=rows, events=ev, steps=steps, margins=margins)
 end
 
+"""
+policy_events_user(s, n_event; kl_bounds, thetas, want_steps, want_margins): policy_events for the events the source problem's own
+rat_user_event writes (rat_policy_events_user): n_event in 1:16 entries of g, an entry the function leaves alone at a step is not watched
+there.  It replays the last evaluate_policy(...; noise=UserNoise(...)) on this solver's handle (the device generator only).  Returns
+policy_events' named tuple.
+"""
+function policy_events_user(s::ILEQGSolver, n_event::Integer; kl_bounds=Float64[], thetas=Float64[], want_steps::Bool=false,
+                            want_margins::Bool=false)
+    h = s.h
+    n, m, N = dims(h.problem)
+    d = collect(Float64, kl_bounds); th = collect(Float64, thetas)
+    nb = length(d); nt = length(th); R = nb + nt; E = clamp(Int(n_event), 1, 16)
+    K = Int64(debug_get(h, "mc_cost_K"))
+    rows = zeros(8, R); ev = zeros(8, E + 1, R)
+    steps = want_steps ? zeros(N + 1, E + 1, R) : nothing
+    margins = want_margins ? zeros(max(K, 1), E) : nothing
+    check(ccall((:rat_policy_events_user, LIB), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, n_event, nb > 0 ? d : C_NULL, nb, nt > 0 ? th : C_NULL, nt, rows, ev,
+                want_steps ? steps : C_NULL, want_margins ? margins : C_NULL))
+    (rows=rows, events=ev, steps=steps, margins=margins)
+end
+"user_event_check(source, n, m; n_event): compile the kernel of policy_events_user only (rat_user_event_check)"
+user_event_check(source::AbstractString, n::Integer, m::Integer; n_event::Integer=1) =
+    check(ccall((:rat_user_event_check, LIB), Int32, (Cstring, Int32, Int32, Int32), source, n, m, n_event))
+
 "kl_event_bound(p, d): the largest probability an event of probability p can have within KL radius d (rat_kl_event_bound; host only)"
 function kl_event_bound(p::Real, d::Real)
     out = Ref(0.0)
@@ -556,6 +582,39 @@ end
 "rare_event_noise_check(source, n, m; normals_per_step, uniforms_per_step): compile the kernel of rare_event_probability_noise only (rat_rare_event_noise_check)"
 rare_event_noise_check(source::AbstractString, n::Integer, m::Integer; normals_per_step::Integer=1, uniforms_per_step::Integer=0) =
     check(ccall((:rat_rare_event_noise_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32), source, n, m, normals_per_step, uniforms_per_step))
+
+"""
+rare_event_probability_user(s, problem, x_nom, l_array, L_array, n_event, event, noise; K, seed, shift, n_iter, rho, want_margins,
+want_logw): rare_event_probability_noise with entry `event` (0-based, 0:n_event-1) of the source's own rat_user_event in place of
+Q, a, b, t_lo, t_hi (rat_policy_rare_event_user).  Returns rare_event_probability's named tuple.
+"""
+function rare_event_probability_user(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_nom, l_array::Vector{Vector{Float64}},
+                                     L_array::Union{Nothing,Vector{Matrix{Float64}}}, n_event::Integer, event::Integer, noise::UserNoise;
+                                     K::Integer=65536, seed::Integer=noise.seed, shift::Union{Nothing,Matrix{Float64}}=nothing,
+                                     n_iter::Integer=8, rho::Real=0.1, want_margins::Bool=false, want_logw::Bool=false)
+    (noise.zn === nothing && noise.zu === nothing) || throw(ArgumentError("rare_event_probability_user draws from the device generator only"))
+    h = bind!(s.h, problem)
+    n, m, N = dims(problem)
+    P = Int(noise.normals_per_step)
+    xn = x_nom isa Vector{Float64} ? x_nom : flat(x_nom)
+    l = flat(l_array)
+    L = L_array === nothing ? C_NULL : flat(L_array)
+    stats = zeros(12); shift_out = zeros(max(P, 1), N); trace = zeros(4, max(n_iter, 1))
+    margins = want_margins ? Vector{Float64}(undef, K) : nothing
+    logw = want_logw ? Vector{Float64}(undef, K) : nothing
+    check(ccall((:rat_policy_rare_event_user, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, UInt64, Int32, Int32, Ptr{Float64}, Int32, Float64,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, xn, l, L, K, noise.normals_per_step, noise.uniforms_per_step, UInt64(seed), n_event, event,
+                shift === nothing ? C_NULL : shift, n_iter, Float64(rho), stats, shift_out, trace,
+                want_margins ? margins : C_NULL, want_logw ? logw : C_NULL))
+    (prob=stats[1], prob_se=stats[2], ess=stats[3], n_viol=Int(stats[4]), n_ok=Int(stats[5]), n_domain=Int(stats[6]), logw_max=stats[7],
+     logw_min=stats[8], flag=Int(stats[9]), n_iter=Int(stats[10]), level=stats[11], shift=shift_out, trace=trace[:, 1:n_iter],
+     margins=margins, logw=logw)
+end
+"rare_event_user_check(source, n, m; normals_per_step, uniforms_per_step, n_event): compile the kernel of rare_event_probability_user only (rat_rare_event_user_check)"
+rare_event_user_check(source::AbstractString, n::Integer, m::Integer; normals_per_step::Integer=1, uniforms_per_step::Integer=0, n_event::Integer=1) =
+    check(ccall((:rat_rare_event_user_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32, Int32), source, n, m, normals_per_step, uniforms_per_step, n_event))
 
 "integrate_cost(problem, x_array, u_array) -- ileqg.jl:115-124"
 function integrate_cost(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_array, u_array)
@@ -1399,7 +1458,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, rare_event_probability_user, rare_event_user_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

@@ -97,6 +97,7 @@ EXPORTS = [
     "rat_policy_events", "rat_kl_event_bound",
     "rat_policy_rare_event",
     "rat_policy_rare_event_noise", "rat_rare_event_noise_check",
+    "rat_policy_events_user", "rat_user_event_check", "rat_policy_rare_event_user", "rat_rare_event_user_check",
 ]
 MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 WC_SLOTS = ("theta", "kl", "bound", "bound_se", "tilt_mean", "tilt_var", "ess", "flag")      # RAT_WC_* slots of the header, in order
@@ -156,6 +157,11 @@ def lib():
         _lib.rat_policy_rare_event_noise.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, _dp, _dp, C.c_double,
                                                      C.c_int32, C.c_int32, _dp, C.c_int32, C.c_double, _dp, _dp, _dp, _dp, _dp]
         _lib.rat_rare_event_noise_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        _lib.rat_policy_events_user.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp]
+        _lib.rat_user_event_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32]
+        _lib.rat_policy_rare_event_user.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32,
+                                                    _dp, C.c_int32, C.c_double, _dp, _dp, _dp, _dp, _dp]
+        _lib.rat_rare_event_user_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     return _lib
 
 
@@ -213,6 +219,18 @@ def rare_event_noise_check(source, n, m, normals_per_step=1, uniforms_per_step=0
     """rat_rare_event_noise_check: compile the rollout kernel of rat_policy_rare_event_noise only (gfx950, no device needed); raises
     RatError with the compiler's log, saying that the source does not define RAT_USER_NOISE, or naming the limit on normals_per_step."""
     check(lib().rat_rare_event_noise_check(str(source).encode(), int(n), int(m), int(normals_per_step), int(uniforms_per_step)))
+
+
+def user_event_check(source, n, m, n_event=1):
+    """rat_user_event_check: compile the kernel of rat_policy_events_user only (gfx950, no device needed); raises RatError with the
+    compiler's log, or saying that the source does not define RAT_USER_EVENT."""
+    check(lib().rat_user_event_check(str(source).encode(), int(n), int(m), int(n_event)))
+
+
+def rare_event_user_check(source, n, m, normals_per_step=1, uniforms_per_step=0, n_event=1):
+    """rat_rare_event_user_check: compile the rollout kernel of rat_policy_rare_event_user only (gfx950, no device needed); raises RatError
+    with the compiler's log, saying what the source does not define, or naming the limit on normals_per_step or n_event."""
+    check(lib().rat_rare_event_user_check(str(source).encode(), int(n), int(m), int(normals_per_step), int(uniforms_per_step), int(n_event)))
 
 
 def pets_set_source(h, prob):

@@ -216,6 +216,14 @@ struct rat_handle_s {
     hipModule_t src_re_mod = nullptr;
     hipFunction_t src_re = nullptr;
     int src_re_npn = -1, src_re_npu = -1;
+    // ... the user's events on a replayed evaluation (rat_policy_events_user): rat_src_user_events (source_events.h), compiled by the first
+    // call that names this n_event; and rat_src_rare_rollout with the user's event for the margin (rat_policy_rare_event_user)
+    hipModule_t src_ev_mod = nullptr;
+    hipFunction_t src_ev = nullptr;
+    int src_ev_ne = -1;
+    hipModule_t src_reu_mod = nullptr;
+    hipFunction_t src_reu = nullptr;
+    int src_reu_npn = -1, src_reu_npu = -1, src_reu_ne = -1;
     double *d_mc_zu = nullptr; size_t cap_mc_zu = 0;         // injected uniforms of one chunk (the normals use d_mc_z)
     double *d_mc_xo = nullptr; size_t cap_mc_xo = 0;         // [chunk][N+1][n] trajectory staging
     double *d_mc_uo = nullptr; size_t cap_mc_uo = 0;         // [chunk][N][m]
@@ -432,6 +440,8 @@ extern "C" void rat_destroy(rat_handle h) {
     for (void *q : {(void *)h->d_re_in, (void *)h->d_re_margin, (void *)h->d_re_logw, (void *)h->d_re_dom, (void *)h->d_re_part, (void *)h->d_re_red}) if (q) (void)hipFree(q);
     if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
     if (h->src_re_mod) (void)hipModuleUnload(h->src_re_mod);
+    if (h->src_ev_mod) (void)hipModuleUnload(h->src_ev_mod);
+    if (h->src_reu_mod) (void)hipModuleUnload(h->src_reu_mod);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
     if (h->h_pcost) (void)hipHostFree(h->h_pcost);
@@ -899,6 +909,10 @@ extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32
     h->src_un_mod = nullptr; h->src_un = nullptr; h->src_un_npn = h->src_un_npu = -1;
     if (h->src_re_mod) (void)hipModuleUnload(h->src_re_mod);
     h->src_re_mod = nullptr; h->src_re = nullptr; h->src_re_npn = h->src_re_npu = -1;
+    if (h->src_ev_mod) (void)hipModuleUnload(h->src_ev_mod);
+    h->src_ev_mod = nullptr; h->src_ev = nullptr; h->src_ev_ne = -1;
+    if (h->src_reu_mod) (void)hipModuleUnload(h->src_reu_mod);
+    h->src_reu_mod = nullptr; h->src_reu = nullptr; h->src_reu_npn = h->src_reu_npu = h->src_reu_ne = -1;
     h->src_text = source; h->src_arch_name = src_arch(pr.gcnArchName);
     h->d_src_p = const_cast<double *>(dp); h->src_np = n_params;
     h->hW.assign(W, W + (size_t)(pb.W_tv ? N : 1) * n * n);
@@ -2561,27 +2575,20 @@ extern "C" rat_rc rat_kl_event_bound(double p, double d, double *out) {
     return RAT_OK;
 }
 
-// Violation probabilities of quadratic events (include/ratilqr.h): the replay above with ev_eval and ev_sums of policy_mc.hip behind each
-// chunk in place of the moment kernels; one enqueue chain, one host wait.  PROB_ROBUST is formed here, on the host, from the counts.
-extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double *Q, const double *a, const double *b,
-                                    const int32_t *t_lo, const int32_t *t_hi,
-                                    const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
-                                    double *rows_out, double *event_out, double *step_out, double *margin_out) {
-    const std::string F = "rat_policy_events: ";
+// ---- violation probabilities of safety events: rat_policy_events and rat_policy_events_user --------------------------------------------
+// What the two calls share (include/ratilqr.h): the replay above with an evaluation kernel and ev_sums of policy_mc.hip behind each chunk in
+// place of the moment kernels, one enqueue chain, one host wait, the 64 MiB limit on the partial sums, the output layouts, and PROB_ROBUST
+// formed here, on the host, from the counts.  They differ in the evaluation: `eval` enqueues, for the chunk that EvArgs describes, the
+// kernel that writes margin, tau and mask, and ev_sums behind it.  `in` (EV_O_EV doubles: the events in the tile, or null) goes to the
+// head of d_ev_out first.
+static const size_t EV_O_A = (size_t)EV_MAX * 256, EV_O_B = EV_O_A + EV_MAX * 16, EV_O_WIN = EV_O_B + EV_MAX, EV_O_EV = EV_O_WIN + EV_MAX;
+
+static rat_rc events_run(rat_handle h, const std::string &F, int n_event, const std::vector<double> *in, bool quad,
+                         const std::function<rat_rc(const EvArgs &)> &eval, const double *kl_bound, int32_t n_bound, const double *theta,
+                         int32_t n_theta, double *rows_out, double *event_out, double *step_out, double *margin_out) {
     rat_rc rc;
-    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && event_out))) return rc;
-    if (n_event < 1 || n_event > EV_MAX) return fail(RAT_ERR_ARG, F + "n_event must be in 1 .. 16");
-    if (!a || !b || !t_lo || !t_hi) return fail(RAT_ERR_ARG, F + "null a / b / t_lo / t_hi");
     const rat_handle_s::McReplay rec = h->mc_rec;
-    const int n = h->n, m = h->m, N = h->N, nrows = n_bound + n_theta, d = n + m, ne1 = n_event + 1;
-    for (int e = 0; e < n_event; ++e) {
-        if (!(0 <= t_lo[e] && t_lo[e] <= t_hi[e] && t_hi[e] <= N))
-            return fail(RAT_ERR_ARG, F + "event " + std::to_string(e) + ": the window must satisfy 0 <= t_lo <= t_hi <= N");
-        bool fin = std::isfinite(b[e]);
-        for (int i = 0; i < d; ++i) fin = fin && std::isfinite(a[e * d + i]);
-        if (Q) for (int i = 0; i < d * d; ++i) fin = fin && std::isfinite(Q[(size_t)e * d * d + i]);
-        if (!fin) return fail(RAT_ERR_ARG, F + "event " + std::to_string(e) + ": Q, a and b must be finite");
-    }
+    const int N = h->N, nrows = n_bound + n_theta, ne1 = n_event + 1;
     const int nsteps = step_out ? N + 1 : 0, ny = nsteps + ne1, nbatch = (nrows + EV_ROWS - 1) / EV_ROWS;
     const size_t per_batch = (size_t)ny * EV_SLOTS * EV_PART, n_part = per_batch * nbatch;
     if (n_part * 8 > (size_t)EV_MAX_PART_BYTES)
@@ -2590,30 +2597,20 @@ extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double 
                                          + (step_out ? " (more without step_out)" : ""));
     HIPCHK(hipSetDevice(h->device));
     const int64_t K = rec.K, chunk = mc_chunk(K);
-    // the events in the 12 + 4 tile: Q as the MFMA's A operand reads it (entry (k, i) at k * 16 + i), a, b, the windows
-    const size_t o_a = (size_t)EV_MAX * 256, o_b = o_a + EV_MAX * 16, o_win = o_b + EV_MAX, o_ev = o_win + EV_MAX, o_step = o_ev + (size_t)nrows * ne1 * EV_NSTAT,
+    const size_t o_a = EV_O_A, o_b = EV_O_B, o_win = EV_O_WIN, o_ev = EV_O_EV, o_step = o_ev + (size_t)nrows * ne1 * EV_NSTAT,
                  o_cnt = o_step + (size_t)nrows * ne1 * nsteps, n_out = o_cnt + 1;
-    std::vector<double> in(o_ev, 0.0);
-    auto tix = [n](int i) { return i < n ? i : 12 + i - n; };
-    for (int e = 0; e < n_event; ++e) {
-        for (int i = 0; i < d; ++i) {
-            in[o_a + e * 16 + tix(i)] = a[e * d + i];
-            if (Q) for (int k = 0; k < d; ++k) in[(size_t)e * 256 + tix(k) * 16 + tix(i)] = Q[(size_t)e * d * d + i + (size_t)d * k];
-        }
-        in[o_b + e] = b[e];
-        int32_t w[2] = {t_lo[e], t_hi[e]};
-        memcpy(&in[o_win + e], w, sizeof(w));
-    }
     if ((rc = grow(&h->d_ev_out, &h->cap_ev_out, n_out))) return rc;
     if ((rc = grow(&h->d_ev_part, &h->cap_ev_part, n_part))) return rc;
     if ((rc = grow(&h->d_ev_margin, &h->cap_ev_margin, (size_t)ne1 * chunk))) return rc;
     if ((rc = grow(&h->d_ev_tau, &h->cap_ev_tau, (size_t)ne1 * chunk))) return rc;
     if (step_out && (rc = grow(&h->d_ev_mask, &h->cap_ev_mask, (size_t)(N + 1) * chunk))) return rc;
-    HIPCHK(hipMemcpyAsync(h->d_ev_out, in.data(), o_ev * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));                          // (`in` is pageable and dies with this scope's errors: the copy is complete here)
+    if (in) {
+        HIPCHK(hipMemcpyAsync(h->d_ev_out, in->data(), o_ev * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));                      // (`in` is pageable and dies with the caller's scope: the copy is complete here)
+    }
     EvArgs ea;
     memset(&ea, 0, sizeof(ea));
-    ea.n_event = n_event; ea.quad = Q ? 1 : 0; ea.Qt = h->d_ev_out; ea.at = h->d_ev_out + o_a; ea.b = h->d_ev_out + o_b;
+    ea.n_event = n_event; ea.quad = quad ? 1 : 0; ea.Qt = h->d_ev_out; ea.at = h->d_ev_out + o_a; ea.b = h->d_ev_out + o_b;
     ea.win = reinterpret_cast<const int *>(h->d_ev_out + o_win);
     ea.margin = h->d_ev_margin; ea.tau = h->d_ev_tau; ea.mask = step_out ? h->d_ev_mask : nullptr; ea.part = h->d_ev_part;
     ea.event_out = h->d_ev_out + o_ev; ea.step_out = h->d_ev_out + o_step;
@@ -2623,7 +2620,8 @@ extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double 
                             [&](const WtArgs &c, ReplayChunk ch) -> rat_rc {
                                 ea.xs = c.xs; ea.us = c.us; ea.ldx = c.ldx; ea.ldu = c.ldu; ea.n = c.n; ea.m = c.m; ea.N = c.N; ea.kc = c.kc; ea.cost = c.cost;
                                 ea.ldy = c.ldy; ea.nrows = c.nrows; ea.y = c.y; ea.wc = c.wc; ea.first = ch.k0 == 0;
-                                launch_ev_chunk(ea, h->stream);
+                                rat_rc rce;
+                                if ((rce = eval(ea))) return rce;
                                 if (margin_out)                       // the chunk's margins, event by event, to their place among the K
                                     HIPCHK(hipMemcpy2DAsync(margin_out + ch.k0, (size_t)K * 8, h->d_ev_margin, (size_t)c.ldy * 8, (size_t)ch.kc * 8,
                                                             (size_t)n_event, hipMemcpyDeviceToHost, h->stream));
@@ -2654,6 +2652,94 @@ extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double 
     for (size_t i = 0; i < ev.size(); ++i) event_out[i] = ev[i];
     for (int i = 0; i < nrows * WC_NSTAT; ++i) rows_out[i] = rows[i];
     return RAT_OK;
+}
+
+// Quadratic events: ev_eval
+extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double *Q, const double *a, const double *b,
+                                    const int32_t *t_lo, const int32_t *t_hi,
+                                    const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                    double *rows_out, double *event_out, double *step_out, double *margin_out) {
+    const std::string F = "rat_policy_events: ";
+    rat_rc rc;
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && event_out))) return rc;
+    if (n_event < 1 || n_event > EV_MAX) return fail(RAT_ERR_ARG, F + "n_event must be in 1 .. 16");
+    if (!a || !b || !t_lo || !t_hi) return fail(RAT_ERR_ARG, F + "null a / b / t_lo / t_hi");
+    const int n = h->n, m = h->m, N = h->N, d = n + m;
+    for (int e = 0; e < n_event; ++e) {
+        if (!(0 <= t_lo[e] && t_lo[e] <= t_hi[e] && t_hi[e] <= N))
+            return fail(RAT_ERR_ARG, F + "event " + std::to_string(e) + ": the window must satisfy 0 <= t_lo <= t_hi <= N");
+        bool fin = std::isfinite(b[e]);
+        for (int i = 0; i < d; ++i) fin = fin && std::isfinite(a[e * d + i]);
+        if (Q) for (int i = 0; i < d * d; ++i) fin = fin && std::isfinite(Q[(size_t)e * d * d + i]);
+        if (!fin) return fail(RAT_ERR_ARG, F + "event " + std::to_string(e) + ": Q, a and b must be finite");
+    }
+    // the events in the 12 + 4 tile: Q as the MFMA's A operand reads it (entry (k, i) at k * 16 + i), a, b, the windows
+    std::vector<double> in(EV_O_EV, 0.0);
+    auto tix = [n](int i) { return i < n ? i : 12 + i - n; };
+    for (int e = 0; e < n_event; ++e) {
+        for (int i = 0; i < d; ++i) {
+            in[EV_O_A + e * 16 + tix(i)] = a[e * d + i];
+            if (Q) for (int k = 0; k < d; ++k) in[(size_t)e * 256 + tix(k) * 16 + tix(i)] = Q[(size_t)e * d * d + i + (size_t)d * k];
+        }
+        in[EV_O_B + e] = b[e];
+        int32_t w[2] = {t_lo[e], t_hi[e]};
+        memcpy(&in[EV_O_WIN + e], w, sizeof(w));
+    }
+    return events_run(h, F, n_event, &in, Q != nullptr, [h](const EvArgs &ea) -> rat_rc { launch_ev_chunk(ea, h->stream); return RAT_OK; },
+                      kl_bound, n_bound, theta, n_theta, rows_out, event_out, step_out, margin_out);
+}
+
+static rat_rc user_event_args_ok(const char *who, int n, int m, int n_event) {
+    if (n < 1 || m < 1) return fail(RAT_ERR_ARG, std::string(who) + ": n, m must be positive");
+    if (n_event < 1 || n_event > EV_MAX) return fail(RAT_ERR_ARG, std::string(who) + ": n_event must be in 1 .. 16");
+    if (!src_sizes_ok(n, m)) return fail(RAT_ERR_UNSUPPORTED, std::string(who) + ": source models are compiled for n <= 12, m <= 4");
+    return RAT_OK;
+}
+
+extern "C" rat_rc rat_user_event_check(const char *source, int32_t n, int32_t m, int32_t n_event) {
+    if (!source) return fail(RAT_ERR_ARG, "null");
+    rat_rc rc = user_event_args_ok("rat_user_event_check", n, m, n_event);
+    if (rc) return rc;
+    std::string log;
+    if ((rc = src_compile_events(source, n, m, n_event, "gfx950", nullptr, &log))) return fail(rc, log);
+    return RAT_OK;
+}
+
+// The user's events: rat_src_user_events (source_events.h, a hiprtc module of its own that the first call with this n_event compiles), then
+// ev_sums.  What is refused comes in rat_policy_events' order; a source that lacks RAT_USER_EVENT or does not compile leaves the handle as
+// it was.
+extern "C" rat_rc rat_policy_events_user(rat_handle h, int32_t n_event, const double *kl_bound, int32_t n_bound, const double *theta,
+                                         int32_t n_theta, double *rows_out, double *event_out, double *step_out, double *margin_out) {
+    const std::string F = "rat_policy_events_user: ";
+    rat_rc rc;
+    if (h && h->have_problem && (h->wide || h->pb.model != RAT_MODEL_SOURCE))
+        return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_event; the families have rat_policy_events)");
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && event_out))) return rc;
+    if (n_event < 1 || n_event > EV_MAX) return fail(RAT_ERR_ARG, F + "n_event must be in 1 .. 16");
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->src_ev || h->src_ev_ne != n_event) {
+        std::shared_ptr<const std::vector<char>> code;
+        std::string log;
+        if ((rc = src_compile_events(h->src_text.c_str(), h->n, h->m, n_event, h->src_arch_name, &code, &log))) return fail(rc, log);
+        hipModule_t mod = nullptr;
+        hipFunction_t fn = nullptr;
+        if ((rc = load_module_function(code, "rat_src_user_events", "rat_policy_events_user", &mod, &fn))) return rc;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->src_ev_mod) (void)hipModuleUnload(h->src_ev_mod);
+        h->src_ev_mod = mod; h->src_ev = fn; h->src_ev_ne = n_event;
+    }
+    return events_run(h, F, n_event, nullptr, false,
+                      [h](const EvArgs &ea) -> rat_rc {
+                          if (ea.kc <= 0 || ea.nrows <= 0) return RAT_OK;
+                          SrcEventArgs sa;
+                          sa.xs = ea.xs; sa.us = ea.us; sa.ldx = ea.ldx; sa.ldu = ea.ldu; sa.N = ea.N; sa.kc = ea.kc; sa.cost = ea.cost;
+                          sa.margin = ea.margin; sa.tau = ea.tau; sa.mask = ea.mask; sa.ldy = ea.ldy; sa.p = h->d_src_p;
+                          void *args[] = {&sa};
+                          HIPCHK(hipModuleLaunchKernel(h->src_ev, (unsigned)((ea.kc + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+                          launch_ev_sums(ea, h->stream);
+                          return RAT_OK;
+                      },
+                      kl_bound, n_bound, theta, n_theta, rows_out, event_out, step_out, margin_out);
 }
 
 // ---- rare events by adaptive importance sampling: rat_policy_rare_event and rat_policy_rare_event_noise -----------------------------------
@@ -2797,6 +2883,68 @@ extern "C" rat_rc rat_rare_event_noise_check(const char *source, int32_t n, int3
 // The same for a source model under its rat_user_noise: rat_src_rare_rollout (source_rare.h, a hiprtc module of its own that the first call
 // with these draw counts compiles) shifts the normals the sampler draws, re_elite_rng replays rat_rng's stream.  W is not read.  One launch
 // per pass: the generator counts rollouts globally and nothing is staged.  The overdraw flag is read after every host wait.
+// rat_policy_rare_event_noise (n_event == 0: the quadratic event) and rat_policy_rare_event_user (entry `event` of the user's
+// rat_user_event: the module's RAT_RARE_USER_EVENT variant, a module of its own beside the other; Q, a, b and the window are then the
+// caller's placeholders, which the kernel does not read) share everything else.
+static rat_rc rare_src_run(rat_handle h, const std::string &F, const char *who, const double *x_nom, const double *l, const double *L, int64_t K,
+                           int32_t normals_per_step, int32_t uniforms_per_step, uint64_t seed, int32_t n_event, int32_t event,
+                           const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi,
+                           const double *shift_in, int32_t n_iter, double rho,
+                           double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out) {
+    rat_rc rc;
+    const int n = h->n, m = h->m, npn = normals_per_step, npu = uniforms_per_step;
+    HIPCHK(hipSetDevice(h->device));
+    if (n_event > 0) {
+        if (!h->src_reu || h->src_reu_npn != npn || h->src_reu_npu != npu || h->src_reu_ne != n_event) {
+            std::shared_ptr<const std::vector<char>> code;
+            std::string log;
+            if ((rc = src_compile_rare_user(h->src_text.c_str(), n, m, npn, npu, n_event, h->src_arch_name, &code, &log))) return fail(rc, log);
+            hipModule_t mod = nullptr;
+            hipFunction_t fn = nullptr;
+            if ((rc = load_module_function(code, "rat_src_rare_rollout", who, &mod, &fn))) return rc;
+            HIPCHK(hipStreamSynchronize(h->stream));
+            if (h->src_reu_mod) (void)hipModuleUnload(h->src_reu_mod);
+            h->src_reu_mod = mod; h->src_reu = fn; h->src_reu_npn = npn; h->src_reu_npu = npu; h->src_reu_ne = n_event;
+        }
+    } else if (!h->src_re || h->src_re_npn != npn || h->src_re_npu != npu) {
+        std::shared_ptr<const std::vector<char>> code;
+        std::string log;
+        if ((rc = src_compile_rare(h->src_text.c_str(), n, m, npn, npu, h->src_arch_name, &code, &log))) return fail(rc, log);
+        hipModule_t mod = nullptr;
+        hipFunction_t fn = nullptr;
+        if ((rc = load_module_function(code, "rat_src_rare_rollout", who, &mod, &fn))) return rc;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->src_re_mod) (void)hipModuleUnload(h->src_re_mod);
+        h->src_re_mod = mod; h->src_re = fn; h->src_re_npn = npn; h->src_re_npu = npu;
+    }
+    const hipFunction_t kernel = n_event > 0 ? h->src_reu : h->src_re;
+    if (!h->h_un_over && hipHostMalloc((void **)&h->h_un_over, sizeof(int), hipHostMallocDefault) != hipSuccess) {
+        h->h_un_over = nullptr;
+        return fail(RAT_ERR_HIP, F + "hipHostMalloc failed");
+    }
+    int *d_over = nullptr;
+    HIPCHK(hipHostGetDevicePointer((void **)&d_over, h->h_un_over, 0));
+    *h->h_un_over = 0;
+    ReKernels kn;
+    kn.ncol = npn; kn.with_wchol = false; kn.adapt = launch_re_adapt_rng;
+    kn.rollout = [h, d_over, kernel, event](const ReArgs &ra, bool quad) -> rat_rc {
+        SrcRareArgs sa;
+        sa.event = event;
+        sa.xnom = ra.xnom; sa.l = ra.l; sa.L = ra.L; sa.shift = ra.shift; sa.Qt = ra.Qt; sa.at = ra.at; sa.b = ra.b;
+        sa.t_lo = ra.t_lo; sa.t_hi = ra.t_hi; sa.quad = quad ? 1 : 0; sa.K = ra.K; sa.N = h->N; sa.tpw = h->src_mc_tpw; sa.seed = ra.seed;
+        sa.margin = ra.margin; sa.logw = ra.logw; sa.dom = ra.dom; sa.p = h->d_src_p; sa.overdraw = d_over;
+        void *args[] = {&sa};
+        HIPCHK(hipModuleLaunchKernel(kernel, (unsigned)((ra.K + sa.tpw - 1) / sa.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+        return RAT_OK;
+    };
+    kn.waited = [h, npn, npu, &F]() -> rat_rc {
+        if (*(volatile int *)h->h_un_over == 0) return RAT_OK;
+        return fail(RAT_ERR_ARG, F + "a step drew more than was declared (normals_per_step = " + std::to_string(npn) +
+                                 ", uniforms_per_step = " + std::to_string(npu) + "): the overdrawn values were NaN");
+    };
+    return re_run(h, F, kn, x_nom, l, L, K, seed, Q, a, b, t_lo, t_hi, shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
+}
+
 extern "C" rat_rc rat_policy_rare_event_noise(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
                                               int32_t normals_per_step, int32_t uniforms_per_step, uint64_t seed,
                                               const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi,
@@ -2807,44 +2955,37 @@ extern "C" rat_rc rat_policy_rare_event_noise(rat_handle h, const double *x_nom,
     if ((rc = re_args_head(F, h, x_nom, l, a, stats, K, n_iter, rho))) return rc;
     if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
         return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_noise; the families have rat_policy_rare_event)");
-    const int n = h->n, m = h->m, npn = normals_per_step, npu = uniforms_per_step;
-    if ((rc = rare_noise_args_ok("rat_policy_rare_event_noise", n, m, npn, npu))) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    if (!h->src_re || h->src_re_npn != npn || h->src_re_npu != npu) {
-        std::shared_ptr<const std::vector<char>> code;
-        std::string log;
-        if ((rc = src_compile_rare(h->src_text.c_str(), n, m, npn, npu, h->src_arch_name, &code, &log))) return fail(rc, log);
-        hipModule_t mod = nullptr;
-        hipFunction_t fn = nullptr;
-        if ((rc = load_module_function(code, "rat_src_rare_rollout", "rat_policy_rare_event_noise", &mod, &fn))) return rc;
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->src_re_mod) (void)hipModuleUnload(h->src_re_mod);
-        h->src_re_mod = mod; h->src_re = fn; h->src_re_npn = npn; h->src_re_npu = npu;
-    }
-    if (!h->h_un_over && hipHostMalloc((void **)&h->h_un_over, sizeof(int), hipHostMallocDefault) != hipSuccess) {
-        h->h_un_over = nullptr;
-        return fail(RAT_ERR_HIP, F + "hipHostMalloc failed");
-    }
-    int *d_over = nullptr;
-    HIPCHK(hipHostGetDevicePointer((void **)&d_over, h->h_un_over, 0));
-    *h->h_un_over = 0;
-    ReKernels kn;
-    kn.ncol = npn; kn.with_wchol = false; kn.adapt = launch_re_adapt_rng;
-    kn.rollout = [h, d_over](const ReArgs &ra, bool quad) -> rat_rc {
-        SrcRareArgs sa;
-        sa.xnom = ra.xnom; sa.l = ra.l; sa.L = ra.L; sa.shift = ra.shift; sa.Qt = ra.Qt; sa.at = ra.at; sa.b = ra.b;
-        sa.t_lo = ra.t_lo; sa.t_hi = ra.t_hi; sa.quad = quad ? 1 : 0; sa.K = ra.K; sa.N = h->N; sa.tpw = h->src_mc_tpw; sa.seed = ra.seed;
-        sa.margin = ra.margin; sa.logw = ra.logw; sa.dom = ra.dom; sa.p = h->d_src_p; sa.overdraw = d_over;
-        void *args[] = {&sa};
-        HIPCHK(hipModuleLaunchKernel(h->src_re, (unsigned)((ra.K + sa.tpw - 1) / sa.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
-        return RAT_OK;
-    };
-    kn.waited = [h, npn, npu, &F]() -> rat_rc {
-        if (*(volatile int *)h->h_un_over == 0) return RAT_OK;
-        return fail(RAT_ERR_ARG, F + "a step drew more than was declared (normals_per_step = " + std::to_string(npn) +
-                                 ", uniforms_per_step = " + std::to_string(npu) + "): the overdrawn values were NaN");
-    };
-    return re_run(h, F, kn, x_nom, l, L, K, seed, Q, a, b, t_lo, t_hi, shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
+    if ((rc = rare_noise_args_ok("rat_policy_rare_event_noise", h->n, h->m, normals_per_step, uniforms_per_step))) return rc;
+    return rare_src_run(h, F, "rat_policy_rare_event_noise", x_nom, l, L, K, normals_per_step, uniforms_per_step, seed, 0, 0, Q, a, b, t_lo, t_hi,
+                        shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
+}
+
+extern "C" rat_rc rat_rare_event_user_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms, int32_t n_event) {
+    if (!source) return fail(RAT_ERR_ARG, "null");
+    rat_rc rc = user_event_args_ok("rat_rare_event_user_check", n, m, n_event);
+    if (rc || (rc = rare_noise_args_ok("rat_rare_event_user_check", n, m, normals, uniforms))) return rc;
+    std::string log;
+    if ((rc = src_compile_rare_user(source, n, m, normals, uniforms, n_event, "gfx950", nullptr, &log))) return fail(rc, log);
+    return RAT_OK;
+}
+
+// rat_policy_rare_event_noise with entry `event` of the user's rat_user_event for g, watched at every step the function writes it
+extern "C" rat_rc rat_policy_rare_event_user(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
+                                             int32_t normals_per_step, int32_t uniforms_per_step, uint64_t seed,
+                                             int32_t n_event, int32_t event,
+                                             const double *shift_in, int32_t n_iter, double rho,
+                                             double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out) {
+    const std::string F = "rat_policy_rare_event_user: ";
+    const double a0[SRC_MAX_N + SRC_MAX_M] = {0.0};                   // (the quadratic event's place in the pack: not read by the kernel)
+    rat_rc rc;
+    if ((rc = re_args_head(F, h, x_nom, l, a0, stats, K, n_iter, rho))) return rc;
+    if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
+        return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_event; the families have rat_policy_rare_event)");
+    if ((rc = user_event_args_ok("rat_policy_rare_event_user", h->n, h->m, n_event))) return rc;
+    if (event < 0 || event >= n_event) return fail(RAT_ERR_ARG, F + "event must be in 0 .. n_event - 1");
+    if ((rc = rare_noise_args_ok("rat_policy_rare_event_user", h->n, h->m, normals_per_step, uniforms_per_step))) return rc;
+    return rare_src_run(h, F, "rat_policy_rare_event_user", x_nom, l, L, K, normals_per_step, uniforms_per_step, seed, n_event, event, nullptr, a0,
+                        0.0, 0, h->N, shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
 }
 
 static rat_rc linearize_slot0(rat_handle h, const double *u, const double *x, std::vector<double> *tiles, int32_t *domain_fail) {

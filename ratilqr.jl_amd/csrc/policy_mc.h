@@ -186,4 +186,7 @@ struct EvArgs {
 };
 // one chunk, behind launch_wct_weights: the events of the staged trajectories, then the chunk's sums into the partials
 void launch_ev_chunk(const EvArgs &a, hipStream_t s);
+// the second half of launch_ev_chunk alone (ev_sums), behind another kernel that wrote margin, tau and mask as ev_eval writes them
+// (rat_policy_events_user: rat_src_user_events of source_events.h); xs, us, Qt, at, b, win are not read
+void launch_ev_sums(const EvArgs &a, hipStream_t s);
 void launch_ev_final(const EvArgs &a, hipStream_t s);

@@ -1072,6 +1072,11 @@ void launch_ev_chunk(const EvArgs &a, hipStream_t s) {
     const dim3 ge((unsigned)(nb < 1024 ? nb : 1024));
     if (a.quad) hipLaunchKernelGGL(ev_eval<true>, ge, dim3(MC_THREADS), 0, s, a);
     else hipLaunchKernelGGL(ev_eval<false>, ge, dim3(MC_THREADS), 0, s, a);
+    launch_ev_sums(a, s);
+}
+
+void launch_ev_sums(const EvArgs &a, hipStream_t s) {
+    if (a.kc <= 0 || a.nrows <= 0 || a.n_event <= 0) return;
     const int ny = (a.mask ? a.N + 1 : 0) + a.n_event + 1;
     hipLaunchKernelGGL(ev_sums, dim3(EV_SLOTS, (unsigned)ny, (unsigned)((a.nrows + EV_ROWS - 1) / EV_ROWS)), dim3(MC_THREADS), 0, s, a);
 }

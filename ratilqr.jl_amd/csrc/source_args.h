@@ -97,4 +97,21 @@ struct SrcRareArgs {
     int *dom;                 // [K]
     const double *p;          // the model's parameters
     int *overdraw;            // set (plain store) when a step draws more than was declared: 1 normals, 2 uniforms
+    int event;                // the RAT_RARE_USER_EVENT variant (rat_policy_rare_event_user): the entry of rat_user_event's g that is the
+                              // margin's event; Qt, at, b, quad are not read there and the window is 0 .. N.  Not read otherwise
+};
+
+// rat_src_user_events (source_events.h): ev_eval (policy_mc.hip) for the user's rat_user_event on the staged trajectories of one replayed
+// chunk, one lane per rollout (rat_policy_events_user); the outputs are ev_eval's, so that ev_sums and ev_final run behind it unchanged
+struct SrcEventArgs {
+    const double *xs, *us;    // staged trajectories of the chunk: [kc][N+1][ldx], [kc][N][ldu]
+    int ldx, ldu;
+    int N;
+    long kc;                  // rollouts of the chunk
+    const double *cost;       // [kc] the stored costs of the chunk's rollouts (NaN: DomainError, selected out)
+    double *margin;           // [RAT_N_EVENT + 1][ldy] M of the chunk's rollouts, NaN for a DomainError rollout; the last row is "any"
+    int *tau;                 // [RAT_N_EVENT + 1][ldy] first violating step, -1: none
+    unsigned *mask;           // [N+1][ldy] bit i: g_i > 0 at that step, bit RAT_N_EVENT: any of them; or null (no per-step sums)
+    long ldy;
+    const double *p;          // the model's parameters
 };

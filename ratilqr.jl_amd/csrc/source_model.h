@@ -30,5 +30,13 @@ rat_rc src_compile_user_noise(const char *source, int n, int m, int npn, int npu
 // "#define RAT_RNG_SHIFT 1" in front of rat_rng.h -- the only kind that defines it.  A fifth kind, compiled on the first such call.
 rat_rc src_compile_rare(const char *source, int n, int m, int npn, int npu, const std::string &arch,
                         std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
+// The user's events on replayed trajectories (rat_policy_events_user): source_events.h after the source, which must define RAT_USER_EVENT
+// and rat_user_event; -DRAT_N_EVENT=n_event, no draws.  A sixth kind, compiled by the first call that names this n_event.
+rat_rc src_compile_events(const char *source, int n, int m, int n_event, const std::string &arch,
+                          std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
+// src_compile_rare with the user's event for the margin (rat_policy_rare_event_user): the same text with -DRAT_RARE_USER_EVENT=1
+// -DRAT_N_EVENT=n_event.  A seventh kind.
+rat_rc src_compile_rare_user(const char *source, int n, int m, int npn, int npu, int n_event, const std::string &arch,
+                             std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
 // The offload-arch string for the device's reported gcnArchName (an xnack+ feature is never passed on).
 std::string src_arch(const char *gcn_arch_name);

@@ -16,6 +16,9 @@
 // and forms g -- the a' z products, the four v_mfma_f64_16x16x4 of Q Z, the c . z products, the butterfly over the four kq lanes -- and
 // the lane with kq == c, which is lane 16 c + col, the owner of that rollout, keeps the value.  No lane leaves early: lanes without a
 // rollout (the K tail, lane >= tpw) skip the rollout part, hold zeros, take part in every group and store nothing.
+// With RAT_RARE_USER_EVENT (rat_policy_rare_event_user; RAT_N_EVENT comes with it) the rollout part is the same text and the margin part is
+// one rat_user_event call per step on the lane's own (x_t, u_t), u_N = 0, as rat_src_user_events (source_events.h) makes it: g arrives as
+// NaN, entry a.event is the step's g, every step 0 .. N is watched.  No LDS, no MFMA, no butterfly: no lane works with another.
 #pragma once
 #include "rat_rng.h"
 #include "source_args.h"
@@ -35,7 +38,16 @@
 #if RAT_PETS_NORMALS < 1 || RAT_PETS_NORMALS > 12
 #error "rat_policy_rare_event_noise shifts 1 .. 12 normals per step"
 #endif
+#ifdef RAT_RARE_USER_EVENT
+#ifndef RAT_USER_EVENT
+#error "the source does not define RAT_USER_EVENT: rat_policy_rare_event_user needs '#define RAT_USER_EVENT' and rat_user_event(k, x, u, g, p)"
+#endif
+#if !defined(RAT_N_EVENT) || RAT_N_EVENT < 1 || RAT_N_EVENT > 16
+#error "rat_user_event is compiled for 1 .. 16 events (RAT_N_EVENT)"
+#endif
+#endif
 
+#ifndef RAT_RARE_USER_EVENT
 #define SRCRE_LD 17
 #define SRCRE_SYNC() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront")
 
@@ -71,19 +83,25 @@ __device__ __forceinline__ double srcre_g(const double (&zv)[4], const double *s
     p += srcre_xor(p, lane, 32);
     return p + b;
 }
+#else
+__device__ inline bool srcre_nan(double v) { return v != v; }
+#endif
 
 extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArgs a) {
-    __shared__ double s_q[256], s_a[16], s_z[64 * SRCRE_LD];
-    const int lane = threadIdx.x, col = lane & 15, kq = lane >> 4;
+    const int lane = threadIdx.x;
     const long j = (long)blockIdx.x * a.tpw + lane;
     const bool live = lane < a.tpw && j < a.K;
     const int N = a.N;
+#ifndef RAT_RARE_USER_EVENT
+    __shared__ double s_q[256], s_a[16], s_z[64 * SRCRE_LD];
+    const int col = lane & 15, kq = lane >> 4;
     if (a.quad) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) s_q[lane + 64 * q] = a.Qt[lane + 64 * q];
     }
     if (lane < 16) s_a[lane] = a.at[lane];
     __syncthreads();
+#endif
     rat_rng rng;
     rng.gen = true;
     rng.zn = nullptr; rng.zu = nullptr;
@@ -97,7 +115,9 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
     const double nan = __builtin_nan("");
     double M = nan;
     int dom = 0;
+#ifndef RAT_RARE_USER_EVENT
     double *row = s_z + lane * SRCRE_LD;
+#endif
     for (int t = 0;; ++t) {
         double u[4] = {0.0, 0.0, 0.0, 0.0};
         if (live && t < N) {
@@ -122,6 +142,18 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
                 for (int i = 0; i < 4; ++i) u[i] = a.l[(long)t * USTR + i];
             }
         }
+#ifdef RAT_RARE_USER_EVENT
+        if (live) {
+            double g[16];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) g[e] = nan;
+            rat_user_event(t, x, u, g, a.p);                          // (x has 12 entries, RAT_N of them live; u is 0 at t == N)
+            double gv = nan;
+#pragma unroll
+            for (int e = 0; e < RAT_N_EVENT; ++e) gv = (e == a.event) ? g[e] : gv;
+            if (gv > M || srcre_nan(M)) M = gv;                       // (a NaN g never replaces a number)
+        }
+#else
         if (t >= a.t_lo && t <= a.t_hi) {                             // (uniform over the grid)
 #pragma unroll
             for (int q = 0; q < 12; ++q) row[q] = (q < RAT_N) ? x[q] : 0.0;
@@ -139,6 +171,7 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
             SRCRE_SYNC();
             if (gv > M || srcre_nan(M)) M = gv;                       // (a NaN g never replaces a number)
         }
+#endif
         if (t == N) break;
         if (live) {
             bool inok = true;

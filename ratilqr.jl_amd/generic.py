@@ -202,6 +202,12 @@ class GenericContext(il.Context):
     def policy_rare_event_noise(self, *a, **k):
         self._carrier_only("policy_rare_event_noise")
 
+    def policy_events_user(self, *a, **k):
+        self._carrier_only("policy_events_user")
+
+    def policy_rare_event_user(self, *a, **k):
+        self._carrier_only("policy_rare_event_user")
+
     def solve_batch(self, *a, **k):
         self._carrier_only("solve_batch")
 

@@ -386,6 +386,32 @@ class Context:
             return r
         return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)), margins=margins)
 
+    def policy_events_user(self, n_event, kl_bounds=(), thetas=(), want_steps=False, want_margins=False):
+        """policy_events for the events the source problem's own rat_user_event writes (rat_policy_events_user): n_event in 1 .. 16 is the
+        number of entries of g the function may write; an entry it leaves alone at a step is not watched there.  A moving obstacle, a box
+        (a min of half-spaces), any function of (k, x, u, p).  It replays the last policy_evaluate_noise of this context (device generator
+        only) and returns policy_events' dict: the last column of every array is "any", margins is (n_event, K) or None."""
+        d = nv.f64(np.atleast_1d(np.asarray(kl_bounds, dtype=np.float64))).ravel()
+        th = nv.f64(np.atleast_1d(np.asarray(thetas, dtype=np.float64))).ravel()
+        N, R, E = self.N, d.size + th.size, int(n_event)
+        Ea = min(max(E, 1), 16)                                       # (the arrays of a call that the library refuses)
+        rows, ev = np.zeros((R, nv.WC_NSTAT)), np.zeros((R, Ea + 1, nv.EV_NSTAT))
+        step = np.zeros((R, Ea + 1, N + 1)) if want_steps else None
+        margins = np.zeros((Ea, max(int(self.debug_get("mc_cost_K")), 1))) if want_margins else None
+        nv.check(nv.lib().rat_policy_events_user(self.h, C.c_int32(E), nv.P(d) if d.size else None, C.c_int32(d.size),
+                                                 nv.P(th) if th.size else None, C.c_int32(th.size), nv.P(rows), nv.P(ev), nv.P(step),
+                                                 nv.P(margins)))
+
+        def part(sl):
+            r = {k: rows[sl, i].copy() for i, k in enumerate(nv.WC_SLOTS)}
+            r["flag"] = r["flag"].astype(np.int64)
+            r.update({k: ev[sl, :, i].copy() for i, k in enumerate(nv.EV_SLOTS) if k != "flag"})
+            r["event_flag"] = ev[sl, :, nv.EV_SLOTS.index("flag")].astype(np.int64)
+            if step is not None:
+                r["step"] = step[sl].copy()
+            return r
+        return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)), margins=margins)
+
     def policy_rare_event(self, x_nom, l, L, event, K, seed=0, shift=None, n_iter=8, rho=0.1, want_margins=False, want_logw=False):
         """The probability of a rare safety event under the policy (x_nom, l, L) -- as policy_evaluate takes it -- by adaptive importance
         sampling on the device (rat_policy_rare_event): the process noise is drawn from a proposal shifted by s (N, n), every rollout
@@ -446,6 +472,37 @@ class Context:
                                                       C.c_double(b), C.c_int32(lo), C.c_int32(hi), nv.P(s_in), C.c_int32(n_iter),
                                                       C.c_double(float(rho)), nv.P(stats), nv.P(s_out), nv.P(trace) if n_iter > 0 else None,
                                                       nv.P(margins), nv.P(logw)))
+        r = {k: float(stats[i]) for i, k in enumerate(nv.RE_SLOTS)}
+        for k in ("n_viol", "n_ok", "n_domain", "flag", "n_iter"):
+            r[k] = int(r[k])
+        return RareEventResult(shift=s_out, trace=trace, margins=margins, logw=logw, **r)
+
+    def policy_rare_event_user(self, x_nom, l, L, n_event, event, K, noise=None, seed=None, shift=None, n_iter=8, rho=0.1, want_margins=False,
+                               want_logw=False):
+        """policy_rare_event_noise with entry `event` (0 .. n_event - 1) of the source's own rat_user_event in place of the quadratic event
+        (rat_policy_rare_event_user): the margin is the largest g[event] over the steps at which the function wrote it.  With n_iter=0
+        and no shift the margins are row `event` of policy_events_user's behind policy_evaluate_noise at the same seed, bit for bit.
+        Returns a RareEventResult."""
+        if not isinstance(noise, UserNoise):
+            raise TypeError("policy_rare_event_user needs noise=UserNoise(...)")
+        if noise.zn is not None or noise.zu is not None:
+            raise ValueError("policy_rare_event_user draws from the device generator only: no injected streams")
+        N, npn, npu = self.N, noise.normals_per_step, noise.uniforms_per_step
+        s_in = None
+        if shift is not None:
+            s_in = nv.f64(shift)
+            if s_in.shape != (N, npn):
+                raise ValueError(f"policy_rare_event_user: the shift is {s_in.shape}, (N, normals_per_step) = ({N}, {npn}) is served")
+        K, n_iter = int(K), int(n_iter)
+        seed = noise.seed if seed is None else int(seed)
+        stats, s_out, trace = np.zeros(nv.RE_NSTAT), np.zeros((N, max(npn, 1))), np.zeros((max(n_iter, 0), nv.RE_NTRACE))
+        margins = np.zeros(max(K, 1)) if want_margins else None
+        logw = np.zeros(max(K, 1)) if want_logw else None
+        nv.check(nv.lib().rat_policy_rare_event_user(self.h, nv.P(nv.f64(x_nom)), nv.P(nv.f64(l)), nv.P(nv.cm3(L)) if L is not None else None,
+                                                     C.c_int64(K), C.c_int32(npn), C.c_int32(npu), C.c_uint64(seed), C.c_int32(int(n_event)),
+                                                     C.c_int32(int(event)), nv.P(s_in), C.c_int32(n_iter), C.c_double(float(rho)),
+                                                     nv.P(stats), nv.P(s_out), nv.P(trace) if n_iter > 0 else None, nv.P(margins),
+                                                     nv.P(logw)))
         r = {k: float(stats[i]) for i, k in enumerate(nv.RE_SLOTS)}
         for k in ("n_viol", "n_ok", "n_domain", "flag", "n_iter"):
             r[k] = int(r[k])
