@@ -40,6 +40,8 @@ void rat_set_error(const char *msg) { g_err = msg; }          // (multi.cpp repo
     } while (0)
 
 struct EvRec { hipEvent_t a, b; int kind; int64_t ntraj; };
+// a lazily compiled source kernel of the handle and the shape its module was compiled for (fn == NULL: empty)
+struct SrcSlot { hipModule_t mod = nullptr; hipFunction_t fn = nullptr; int npn = 0, npu = 0, nev = 0; };
 
 struct rat_handle_s {
     int device = 0;
@@ -186,13 +188,13 @@ struct rat_handle_s {
     int gsrc_npn = 0, gsrc_npu = 0;  // draws per step it declared
     int *h_gsrc_over = nullptr;      // pinned: the overdraw flag its kernel sets with a plain store (bit 0 normals, bit 1 uniforms)
     // Monte-Carlo policy evaluation (rat_policy_evaluate, policy_mc.hip): scratch of the handle, allocated by the first call, grown on demand
-    // Source models run rat_src_noisy_rollout (source_noisy.h): a module of its own, compiled by the first evaluation of the problem
-    std::string src_text;            // the source problem's text and architecture, kept for that compile (a copy per source handle, a few kB:
-                                     // the process-wide cache keys on the text and holds only code objects)
+    // Source models run the kernels of SRC_NOISY .. SRC_RARE_USER (source_model.h): a module per kind, compiled by the first call that
+    // needs it for the shape it names (src_kernel), dropped when the source problem is set again (src_drop_slots)
+    std::string src_text;            // the source problem's text and architecture, kept for those compiles (a copy per source handle, a few
+                                     // kB: the process-wide cache keys on the text and holds only code objects)
     std::string src_arch_name;
-    hipModule_t src_noisy_mod = nullptr;
-    hipFunction_t src_noisy = nullptr;
-    int src_mc_tpw = 64;             // switch src_mc_tpw: rollouts per wavefront of that kernel (16 / 32 / 64)
+    SrcSlot src_slot[SRC_NKIND];     // (the two eager kinds' entries stay empty: src_mod and gsrc_mod above)
+    int src_mc_tpw = 64;             // switch src_mc_tpw: rollouts per wavefront of those rollout kernels (16 / 32 / 64)
     double *d_mc_cost = nullptr; size_t cap_mc_cost = 0;     // [K] rollout costs
     int *d_mc_dom = nullptr; size_t cap_mc_dom = 0;          // [K] DomainError flags of the family kernel
     double *d_mc_z = nullptr; size_t cap_mc_z = 0;           // injected normals of one chunk
@@ -204,26 +206,9 @@ struct rat_handle_s {
     double *d_wc_w = nullptr; size_t cap_wc_w = 0;           // [K]
     // the tail risk (rat_policy_tail_risk, policy_mc.hip): the select's states and histograms, partials and rows; its weights use d_wc_w
     double *d_tr_red = nullptr;                              // [TR_SCRATCH]
-    // ... under the user's noise sampler (rat_policy_evaluate_noise): rat_src_user_noisy_rollout (source_user_noise.h), a module of its own
-    // compiled for the declared draw counts by the first call that needs it
-    hipModule_t src_un_mod = nullptr;
-    hipFunction_t src_un = nullptr;
-    int src_un_npn = -1, src_un_npu = -1;                    // the draw counts the loaded module was compiled for
-    int64_t src_un_loads = 0;                                // switch src_un_loads (read only): modules this handle compiled or fetched from the cache
-    int *h_un_over = nullptr;                                // pinned: that kernel's overdraw flag (bit 0 normals, bit 1 uniforms)
-    // ... and under a shifted proposal (rat_policy_rare_event_noise): rat_src_rare_rollout (source_rare.h), a module of its own, compiled by
-    // the first such call; it shares the overdraw flag (both calls end with a host wait)
-    hipModule_t src_re_mod = nullptr;
-    hipFunction_t src_re = nullptr;
-    int src_re_npn = -1, src_re_npu = -1;
-    // ... the user's events on a replayed evaluation (rat_policy_events_user): rat_src_user_events (source_events.h), compiled by the first
-    // call that names this n_event; and rat_src_rare_rollout with the user's event for the margin (rat_policy_rare_event_user)
-    hipModule_t src_ev_mod = nullptr;
-    hipFunction_t src_ev = nullptr;
-    int src_ev_ne = -1;
-    hipModule_t src_reu_mod = nullptr;
-    hipFunction_t src_reu = nullptr;
-    int src_reu_npn = -1, src_reu_npu = -1, src_reu_ne = -1;
+    // ... under the user's noise sampler (rat_policy_evaluate_noise, rat_policy_rare_event_noise / _user: the kinds that take draws)
+    int64_t src_un_loads = 0;                                // switch src_un_loads (read only): SRC_USER_NOISE modules this handle compiled or fetched from the cache
+    int *h_un_over = nullptr;                                // pinned: those kernels' overdraw flag (bit 0 normals, bit 1 uniforms; every such call ends with a host wait)
     double *d_mc_zu = nullptr; size_t cap_mc_zu = 0;         // injected uniforms of one chunk (the normals use d_mc_z)
     double *d_mc_xo = nullptr; size_t cap_mc_xo = 0;         // [chunk][N+1][n] trajectory staging
     double *d_mc_uo = nullptr; size_t cap_mc_uo = 0;         // [chunk][N][m]
@@ -419,6 +404,13 @@ static void free_list(std::vector<void *> &v) {
     for (void *p : v) (void)hipFree(p);
     v.clear();
 }
+// every lazily compiled source kernel of the handle, unloaded and forgotten (the caller has waited for the stream)
+static void src_drop_slots(rat_handle h) {
+    for (SrcSlot &s : h->src_slot) {
+        if (s.mod) (void)hipModuleUnload(s.mod);
+        s = SrcSlot();
+    }
+}
 
 extern "C" void rat_destroy(rat_handle h) {
     if (!h) return;
@@ -432,16 +424,12 @@ extern "C" void rat_destroy(rat_handle h) {
     for (double *q : {h->d_pin, h->d_pzn, h->d_pzu, h->d_ptraj, h->d_pcost, h->d_pmu, h->d_psig}) if (q) (void)hipFree(q);
     if (h->d_perr) (void)hipFree(h->d_perr);
     for (void *q : {(void *)h->d_mc_cost, (void *)h->d_mc_dom, (void *)h->d_mc_z, (void *)h->d_mc_in, (void *)h->d_mc_red}) if (q) (void)hipFree(q);
-    if (h->src_noisy_mod) (void)hipModuleUnload(h->src_noisy_mod);
+    src_drop_slots(h);
     for (double *q : {h->d_mc_zu, h->d_mc_xo, h->d_mc_uo}) if (q) (void)hipFree(q);
     for (double *q : {h->d_wc_red, h->d_wc_w, h->d_tr_red}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_wt_cost, (void *)h->d_wt_dom, (void *)h->d_wt_y, (void *)h->d_wt_part, (void *)h->d_wt_out}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_ev_out, (void *)h->d_ev_part, (void *)h->d_ev_margin, (void *)h->d_ev_tau, (void *)h->d_ev_mask}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_re_in, (void *)h->d_re_margin, (void *)h->d_re_logw, (void *)h->d_re_dom, (void *)h->d_re_part, (void *)h->d_re_red}) if (q) (void)hipFree(q);
-    if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
-    if (h->src_re_mod) (void)hipModuleUnload(h->src_re_mod);
-    if (h->src_ev_mod) (void)hipModuleUnload(h->src_ev_mod);
-    if (h->src_reu_mod) (void)hipModuleUnload(h->src_reu_mod);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
     if (h->h_pcost) (void)hipHostFree(h->h_pcost);
@@ -821,22 +809,33 @@ extern "C" rat_rc rat_problem_set(rat_handle h, const rat_problem_desc *d) {
 // ---- source models (RAT_MODEL_SOURCE): user-written f, c, h compiled at run time (source_model.cpp, source_kernels.h) -------------
 static bool src_sizes_ok(int n, int m) { return n >= 1 && m >= 1 && n <= SRC_MAX_N && m <= SRC_MAX_M; }
 
-extern "C" rat_rc rat_source_check(const char *source, int32_t n, int32_t m) {
-    if (!source) return fail(RAT_ERR_ARG, "null");
-    if (n < 1 || m < 1) return fail(RAT_ERR_ARG, "rat_source_check: n, m must be positive");
-    if (!src_sizes_ok(n, m)) return fail(RAT_ERR_UNSUPPORTED, "rat_source_check: source models are compiled for n <= 12, m <= 4");
-    std::string log;
-    const rat_rc rc = src_compile(source, n, m, "gfx950", nullptr, &log);
-    if (rc) return fail(rc, log);
+// What the numbers alone decide for a module of `kind` (source_model.h): the checks its row calls for.  A kind with events names the
+// sizes before the draw counts, the others after.
+static rat_rc src_args_ok(const char *who, SrcKind kind, int n, int m, int npn, int npu, int nev) {
+    const SrcKindRow &row = src_kind(kind);
+    const std::string F = std::string(who) + ": ";
+    const bool big = !src_sizes_ok(n, m);
+    if (n < 1 || m < 1) return fail(RAT_ERR_ARG, F + "n, m must be positive");
+    if (row.events && (nev < 1 || nev > EV_MAX)) return fail(RAT_ERR_ARG, F + "n_event must be in 1 .. 16");
+    if (row.draws && !(row.events && big) && (npn < 0 || npu < 0))
+        return fail(RAT_ERR_ARG, F + "normals_per_step, uniforms_per_step must not be negative");
+    if (big) return fail(RAT_ERR_UNSUPPORTED, F + "source models are compiled for n <= 12, m <= 4");
+    if (row.rng_shift && npn == 0) return fail(RAT_ERR_ARG, F + "normals_per_step is 0: there is no normal to shift");
+    if (row.rng_shift && npn > 12) return fail(RAT_ERR_UNSUPPORTED, F + "normals_per_step is above 12 (the shift is laid out [N][12])");
     return RAT_OK;
 }
 
-static rat_rc user_noise_args_ok(const char *who, int n, int m, int npn, int npu) {
-    if (n < 1 || m < 1) return fail(RAT_ERR_ARG, std::string(who) + ": n, m must be positive");
-    if (npn < 0 || npu < 0) return fail(RAT_ERR_ARG, std::string(who) + ": normals_per_step, uniforms_per_step must not be negative");
-    if (!src_sizes_ok(n, m)) return fail(RAT_ERR_UNSUPPORTED, std::string(who) + ": source models are compiled for n <= 12, m <= 4");
+// the rat_*_check entry points: whether `source` would be accepted as `kind`, compiled for gfx950 without a device
+static rat_rc src_check(const char *who, SrcKind kind, const char *source, int n, int m, int npn = 0, int npu = 0, int nev = 0) {
+    if (!source) return fail(RAT_ERR_ARG, "null");
+    rat_rc rc = src_args_ok(who, kind, n, m, npn, npu, nev);
+    if (rc) return rc;
+    std::string log;
+    if ((rc = src_compile(kind, source, n, m, SrcShape{npn, npu, nev}, "gfx950", nullptr, &log))) return fail(rc, log);
     return RAT_OK;
 }
+
+extern "C" rat_rc rat_source_check(const char *source, int32_t n, int32_t m) { return src_check("rat_source_check", SRC_MODEL, source, n, m); }
 
 // A compiled module on the current device and its kernel `name` (and `name2`, where a module carries two); a module that lacks one is
 // unloaded again.  What a caller does with the module it replaces comes after, at the caller.
@@ -852,13 +851,52 @@ static rat_rc load_module_function(const std::shared_ptr<const std::vector<char>
     return RAT_OK;
 }
 
-extern "C" rat_rc rat_user_noise_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms) {
-    if (!source) return fail(RAT_ERR_ARG, "null");
-    rat_rc rc = user_noise_args_ok("rat_user_noise_check", n, m, normals, uniforms);
-    if (rc) return rc;
-    std::string log;
-    if ((rc = src_compile_user_noise(source, n, m, normals, uniforms, "gfx950", nullptr, &log))) return fail(rc, log);
+// The handle's kernel of a lazily compiled kind for `shape`: compiled (or fetched from the process-wide cache) and loaded when the slot is
+// empty or holds another shape.  A compile or load that is refused leaves the slot as it was; a module that is replaced is unloaded once
+// the stream has finished with it.
+static rat_rc src_kernel(rat_handle h, SrcKind kind, const SrcShape &shape, const char *who, hipFunction_t *fn) {
+    SrcSlot &s = h->src_slot[kind];
+    if (!s.fn || s.npn != shape.npn || s.npu != shape.npu || s.nev != shape.nev) {
+        std::shared_ptr<const std::vector<char>> code;
+        std::string log;
+        rat_rc rc;
+        if ((rc = src_compile(kind, h->src_text.c_str(), h->n, h->m, shape, h->src_arch_name, &code, &log))) return fail(rc, log);
+        SrcSlot fresh{nullptr, nullptr, shape.npn, shape.npu, shape.nev};
+        if ((rc = load_module_function(code, src_kind(kind).entry, who, &fresh.mod, &fresh.fn))) return rc;
+        if (s.mod) {
+            HIPCHK(hipStreamSynchronize(h->stream));
+            (void)hipModuleUnload(s.mod);
+        }
+        s = fresh;
+        if (kind == SRC_USER_NOISE) h->src_un_loads++;
+    }
+    *fn = s.fn;
     return RAT_OK;
+}
+
+// a source kernel's launch: one wavefront per `per_block` of `count`, *args its one argument record
+static hipError_t launch_src(hipFunction_t fn, int64_t count, int per_block, hipStream_t s, void *args) {
+    void *a[] = {args};
+    return hipModuleLaunchKernel(fn, (unsigned)((count + per_block - 1) / per_block), 1, 1, 64, 1, 1, 0, s, a, nullptr);
+}
+
+// The pinned overdraw flag of a kernel that draws (bit 0 normals, bit 1 uniforms; set with a plain store, read after a host wait):
+// allocated by the first call, cleared; *d_flag (if not null): its device address
+static rat_rc overdraw_flag(int **flag, const std::string &F, int **d_flag) {
+    if (!*flag && hipHostMalloc((void **)flag, sizeof(int), hipHostMallocDefault) != hipSuccess) {
+        *flag = nullptr;
+        return fail(RAT_ERR_HIP, F + "hipHostMalloc failed");
+    }
+    if (d_flag) HIPCHK(hipHostGetDevicePointer((void **)d_flag, *flag, 0));
+    **flag = 0;
+    return RAT_OK;
+}
+static std::string overdraw_msg(const std::string &what, int npn, int npu) {
+    return what + " (normals_per_step = " + std::to_string(npn) + ", uniforms_per_step = " + std::to_string(npu) + "): the overdrawn values were NaN";
+}
+
+extern "C" rat_rc rat_user_noise_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms) {
+    return src_check("rat_user_noise_check", SRC_USER_NOISE, source, n, m, normals, uniforms);
 }
 
 extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32_t n, int32_t m, int32_t N, const double *W, int32_t W_tv,
@@ -873,7 +911,7 @@ extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32
     HIPCHK(hipGetDeviceProperties(&pr, h->device));
     std::shared_ptr<const std::vector<char>> code;
     std::string log;
-    rat_rc rc = src_compile(source, n, m, src_arch(pr.gcnArchName), &code, &log);
+    rat_rc rc = src_compile(SRC_MODEL, source, n, m, SrcShape(), src_arch(pr.gcnArchName), &code, &log);
     if (rc) return fail(rc, log);
     ProblemDev pb;
     memset(&pb, 0, sizeof(pb));
@@ -882,7 +920,8 @@ extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32
     if ((rc = build_w_tables(h, pb, W, n, N, "rat_problem_set_source", wt))) return rc;
     hipModule_t mod = nullptr;
     hipFunction_t fr = nullptr, fl = nullptr;
-    if ((rc = load_module_function(code, "rat_src_rollout", "rat_problem_set_source", &mod, &fr, "rat_src_linearize", &fl))) return rc;
+    const SrcKindRow &row = src_kind(SRC_MODEL);
+    if ((rc = load_module_function(code, row.entry, "rat_problem_set_source", &mod, &fr, row.entry2, &fl))) return rc;
     // the new tables go to a list of their own: the previous problem's buffers are released only once every upload has succeeded
     std::vector<void *> allocs;
     auto undo = [&](rat_rc r) { free_list(allocs); (void)hipModuleUnload(mod); return r; };
@@ -903,16 +942,7 @@ extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32
     h->pb_allocs.swap(allocs);
     if (h->src_mod) (void)hipModuleUnload(h->src_mod);
     h->src_mod = mod; h->src_roll = fr; h->src_lin = fl;
-    if (h->src_noisy_mod) (void)hipModuleUnload(h->src_noisy_mod);      // (the previous problem's Monte-Carlo kernel)
-    h->src_noisy_mod = nullptr; h->src_noisy = nullptr;
-    if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
-    h->src_un_mod = nullptr; h->src_un = nullptr; h->src_un_npn = h->src_un_npu = -1;
-    if (h->src_re_mod) (void)hipModuleUnload(h->src_re_mod);
-    h->src_re_mod = nullptr; h->src_re = nullptr; h->src_re_npn = h->src_re_npu = -1;
-    if (h->src_ev_mod) (void)hipModuleUnload(h->src_ev_mod);
-    h->src_ev_mod = nullptr; h->src_ev = nullptr; h->src_ev_ne = -1;
-    if (h->src_reu_mod) (void)hipModuleUnload(h->src_reu_mod);
-    h->src_reu_mod = nullptr; h->src_reu = nullptr; h->src_reu_npn = h->src_reu_npu = h->src_reu_ne = -1;
+    src_drop_slots(h);                                                   // (the previous problem's Monte-Carlo kernels)
     h->src_text = source; h->src_arch_name = src_arch(pr.gcnArchName);
     h->d_src_p = const_cast<double *>(dp); h->src_np = n_params;
     h->hW.assign(W, W + (size_t)(pb.W_tv ? N : 1) * n * n);
@@ -946,8 +976,7 @@ static void model_rollout(rat_handle h, const RolloutArgs &ra, hipStream_t s) {
     if (ncand <= 0) return;
     SrcRollArgs a;
     a.st = ra.st; a.op = ra.op; a.mode = ra.mode; a.tpw = h->src_tpw; a.x0 = ra.x0; a.u0 = ra.u0; a.p = h->d_src_p;
-    void *args[] = {&a};
-    (void)hipModuleLaunchKernel(h->src_roll, (unsigned)((ncand + a.tpw - 1) / a.tpw), 1, 1, 64, 1, 1, 0, s, args, nullptr);
+    (void)launch_src(h->src_roll, ncand, a.tpw, s, &a);
 }
 static void model_linearize(rat_handle h, const LinArgs &la, hipStream_t s) {
     if (h->pb.model != RAT_MODEL_SOURCE) { launch_linearize(la, s); return; }
@@ -1999,16 +2028,15 @@ static void launch_noisy_chunk(rat_handle h, const PolicyDev &p, int64_t k0, int
     a.x_out = x_out; a.u_out = u_out; a.cost = cost; a.dom = dom;
     launch_noisy_rollout(a, h->stream);
 }
-// the same for a source model under its rat_user_noise (the handle's src_un): the generator counts rollouts globally (j0 = k0), so every
-// chunk runs under the caller's seed; d_over: the device address of the overdraw flag
+// the same for a source model under its rat_user_noise (the handle's SRC_USER_NOISE kernel): the generator counts rollouts globally
+// (j0 = k0), so every chunk runs under the caller's seed; d_over: the device address of the overdraw flag
 static rat_rc launch_user_noisy_chunk(rat_handle h, const PolicyDev &p, int64_t k0, int64_t kc, uint64_t seed, const double *d_zn,
                                       const double *d_zu, double *x_out, double *u_out, double *cost, int *d_over) {
     SrcUserNoisyArgs a;
     a.xnom = p.x; a.l = p.l; a.L = p.L; a.zn = d_zn; a.zu = d_zu;
     a.K = (long)kc; a.j0 = (long)k0; a.N = h->N; a.tpw = h->src_mc_tpw; a.seed = seed; a.cost = cost;
     a.x_out = x_out; a.u_out = u_out; a.p = h->d_src_p; a.overdraw = d_over;
-    void *args[] = {&a};
-    HIPCHK(hipModuleLaunchKernel(h->src_un, (unsigned)((kc + a.tpw - 1) / a.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+    HIPCHK(launch_src(h->src_slot[SRC_USER_NOISE].fn, kc, a.tpw, h->stream, &a));
     return RAT_OK;
 }
 
@@ -2135,8 +2163,7 @@ static rat_rc policy_eval_finish(rat_handle h, const int *d_dom, const rat_handl
     if (cost_out) HIPCHK(hipMemcpyAsync(cost_out, h->d_mc_cost, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (rec.kind == 2 && *(volatile int *)h->h_un_over != 0)      // after the wait: a step that drew more than the caller declared
-        return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: a step drew more than was declared (normals_per_step = " + std::to_string(rec.npn) +
-                                 ", uniforms_per_step = " + std::to_string(rec.npu) + "): the overdrawn values were NaN");
+        return fail(RAT_ERR_ARG, overdraw_msg("rat_policy_evaluate_noise: a step drew more than was declared", rec.npn, rec.npu));
     h->mc_cost_K = K;
     h->mc_rec = rec;
     for (int i = 0; i < RAT_MC_NSTAT; ++i) stats[i] = out[i];
@@ -2165,15 +2192,8 @@ extern "C" rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const d
     PolicyPack pk;
     if ((rc = pack_policy(h, x_nom, l, L, true, &pk))) return rc;
     const int64_t chunk = mc_chunk(K);                            // (injected normals are staged chunk by chunk)
-    if (source && !h->src_noisy) {                                // the first evaluation of this source problem compiles its rollout kernel
-        std::shared_ptr<const std::vector<char>> code;
-        std::string log;
-        if ((rc = src_compile_noisy(h->src_text.c_str(), n, m, h->src_arch_name, &code, &log))) return fail(rc, log);
-        hipModule_t mod = nullptr;
-        hipFunction_t fn = nullptr;
-        if ((rc = load_module_function(code, "rat_src_noisy_rollout", "rat_policy_evaluate", &mod, &fn))) return rc;
-        h->src_noisy_mod = mod; h->src_noisy = fn;
-    }
+    hipFunction_t src_noisy = nullptr;                            // the first evaluation of a source problem compiles its rollout kernel
+    if (source && (rc = src_kernel(h, SRC_NOISY, SrcShape(), "rat_policy_evaluate", &src_noisy))) return rc;
     if ((rc = policy_eval_scratch(h, pk, K))) return rc;
     if (!source && !h->wide && (rc = grow(&h->d_mc_dom, &h->cap_mc_dom, (size_t)K))) return rc;
     if (z && (rc = grow(&h->d_mc_z, &h->cap_mc_z, (size_t)chunk * N * n))) return rc;
@@ -2198,8 +2218,7 @@ extern "C" rat_rc rat_policy_evaluate(rat_handle h, const double *x_nom, const d
             SrcNoisyArgs a;
             a.Wchol = dev.Wchol; a.xnom = dev.x; a.l = dev.l; a.L = dev.L; a.z = d_z; a.K = (long)kc; a.N = N; a.W_tv = h->W_tv;
             a.tpw = h->src_mc_tpw; a.seed = chunk_seed(seed, k0, chunk); a.cost = h->d_mc_cost + k0; a.p = h->d_src_p;
-            void *args[] = {&a};
-            HIPCHK(hipModuleLaunchKernel(h->src_noisy, (unsigned)((kc + a.tpw - 1) / a.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+            HIPCHK(launch_src(src_noisy, kc, a.tpw, h->stream, &a));
         } else {
             launch_noisy_chunk(h, dev, k0, kc, chunk, seed, d_z, nullptr, nullptr, h->d_mc_cost + k0, d_dom + k0);
         }
@@ -2225,26 +2244,16 @@ extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, c
         return fail(RAT_ERR_UNSUPPORTED, "rat_policy_evaluate_noise: the handle's problem is not a source model (only a source can define rat_user_noise)");
     const int n = h->n, m = h->m, N = h->N;
     const int npn = normals_per_step, npu = uniforms_per_step;
-    if ((rc = user_noise_args_ok("rat_policy_evaluate_noise", n, m, npn, npu))) return rc;
+    if ((rc = src_args_ok("rat_policy_evaluate_noise", SRC_USER_NOISE, n, m, npn, npu, 0))) return rc;
     if ((zn || zu) && ((npn > 0 && !zn) || (npu > 0 && !zu)))
         return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: injected draws need every declared stream (normals_per_step = " + std::to_string(npn) +
                                  ", uniforms_per_step = " + std::to_string(npu) + ")");
     HIPCHK(hipSetDevice(h->device));
-    if (!h->src_un || h->src_un_npn != npn || h->src_un_npu != npu) {       // the first evaluation with these draw counts compiles the kernel
-        std::shared_ptr<const std::vector<char>> code;
-        std::string log;
-        if ((rc = src_compile_user_noise(h->src_text.c_str(), n, m, npn, npu, h->src_arch_name, &code, &log))) return fail(rc, log);
-        hipModule_t mod = nullptr;
-        hipFunction_t fn = nullptr;
-        if ((rc = load_module_function(code, "rat_src_user_noisy_rollout", "rat_policy_evaluate_noise", &mod, &fn))) return rc;
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->src_un_mod) (void)hipModuleUnload(h->src_un_mod);
-        h->src_un_mod = mod; h->src_un = fn; h->src_un_npn = npn; h->src_un_npu = npu; h->src_un_loads++;
-    }
-    if (!h->h_un_over && hipHostMalloc((void **)&h->h_un_over, sizeof(int), hipHostMallocDefault) != hipSuccess) {
-        h->h_un_over = nullptr;
-        return fail(RAT_ERR_HIP, "rat_policy_evaluate_noise: hipHostMalloc failed");
-    }
+    // the first evaluation with these draw counts compiles the kernel (launch_user_noisy_chunk, which a replay calls too, takes it from the slot)
+    hipFunction_t fn = nullptr;
+    int *d_over = nullptr;
+    if ((rc = src_kernel(h, SRC_USER_NOISE, SrcShape{npn, npu, 0}, "rat_policy_evaluate_noise", &fn))) return rc;
+    if ((rc = overdraw_flag(&h->h_un_over, "rat_policy_evaluate_noise: ", &d_over))) return rc;
     PolicyPack pk;                                                // (W is not read: the pack starts at x_nom)
     if ((rc = pack_policy(h, x_nom, l, L, false, &pk))) return rc;
     const bool inject = zn || zu, traj = x_out || u_out;
@@ -2257,9 +2266,6 @@ extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, c
     if (u_out && (rc = grow(&h->d_mc_uo, &h->cap_mc_uo, (size_t)chunk * nuo))) return rc;
     HIPCHK(hipMemcpy(h->d_mc_in, pk.data.data(), pk.data.size() * 8, hipMemcpyHostToDevice));
     const PolicyDev dev = policy_dev(h->d_mc_in, pk.o_x, pk.o_l, pk.o_L, L != nullptr);
-    int *d_over = nullptr;
-    HIPCHK(hipHostGetDevicePointer((void **)&d_over, h->h_un_over, 0));
-    *h->h_un_over = 0;
     // the generator without trajectories needs no staging: one launch (the rollout index is the Philox counter either way)
     const int64_t step = (inject || traj) ? chunk : K;
     for (int64_t k0 = 0; k0 < K; k0 += step) {
@@ -2425,8 +2431,9 @@ static rat_rc replay_validate(rat_handle h, const std::string &F, const double *
         return fail(RAT_ERR_UNSUPPORTED, F + "the evaluation ran on injected draws, which are not kept: combine the trajectories the "
                                          "caller has (x_out / u_out) with rat_policy_worst_case's weights_out on the host");
     const bool source = h->pb.model == RAT_MODEL_SOURCE;
+    const SrcSlot &un = h->src_slot[SRC_USER_NOISE];
     if (rec.kind == 3 || rec.n != h->n || rec.m != h->m || rec.N != h->N || rec.model != h->pb.model || rec.W_tv != h->W_tv || (rec.kind == 2) != source ||
-        (source && (!h->src_un || h->src_un_npn != rec.npn || h->src_un_npu != rec.npu || !h->h_un_over)))
+        (source && (!un.fn || un.npn != rec.npn || un.npu != rec.npu || !h->h_un_over)))
         return fail(RAT_ERR_ARG, F + REPLAY_CHANGED);
     return RAT_OK;
 }
@@ -2689,20 +2696,8 @@ extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double 
                       kl_bound, n_bound, theta, n_theta, rows_out, event_out, step_out, margin_out);
 }
 
-static rat_rc user_event_args_ok(const char *who, int n, int m, int n_event) {
-    if (n < 1 || m < 1) return fail(RAT_ERR_ARG, std::string(who) + ": n, m must be positive");
-    if (n_event < 1 || n_event > EV_MAX) return fail(RAT_ERR_ARG, std::string(who) + ": n_event must be in 1 .. 16");
-    if (!src_sizes_ok(n, m)) return fail(RAT_ERR_UNSUPPORTED, std::string(who) + ": source models are compiled for n <= 12, m <= 4");
-    return RAT_OK;
-}
-
 extern "C" rat_rc rat_user_event_check(const char *source, int32_t n, int32_t m, int32_t n_event) {
-    if (!source) return fail(RAT_ERR_ARG, "null");
-    rat_rc rc = user_event_args_ok("rat_user_event_check", n, m, n_event);
-    if (rc) return rc;
-    std::string log;
-    if ((rc = src_compile_events(source, n, m, n_event, "gfx950", nullptr, &log))) return fail(rc, log);
-    return RAT_OK;
+    return src_check("rat_user_event_check", SRC_EVENTS, source, n, m, 0, 0, n_event);
 }
 
 // The user's events: rat_src_user_events (source_events.h, a hiprtc module of its own that the first call with this n_event compiles), then
@@ -2717,25 +2712,15 @@ extern "C" rat_rc rat_policy_events_user(rat_handle h, int32_t n_event, const do
     if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && event_out))) return rc;
     if (n_event < 1 || n_event > EV_MAX) return fail(RAT_ERR_ARG, F + "n_event must be in 1 .. 16");
     HIPCHK(hipSetDevice(h->device));
-    if (!h->src_ev || h->src_ev_ne != n_event) {
-        std::shared_ptr<const std::vector<char>> code;
-        std::string log;
-        if ((rc = src_compile_events(h->src_text.c_str(), h->n, h->m, n_event, h->src_arch_name, &code, &log))) return fail(rc, log);
-        hipModule_t mod = nullptr;
-        hipFunction_t fn = nullptr;
-        if ((rc = load_module_function(code, "rat_src_user_events", "rat_policy_events_user", &mod, &fn))) return rc;
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->src_ev_mod) (void)hipModuleUnload(h->src_ev_mod);
-        h->src_ev_mod = mod; h->src_ev = fn; h->src_ev_ne = n_event;
-    }
+    hipFunction_t kernel = nullptr;
+    if ((rc = src_kernel(h, SRC_EVENTS, SrcShape{0, 0, n_event}, "rat_policy_events_user", &kernel))) return rc;
     return events_run(h, F, n_event, nullptr, false,
-                      [h](const EvArgs &ea) -> rat_rc {
+                      [h, kernel](const EvArgs &ea) -> rat_rc {
                           if (ea.kc <= 0 || ea.nrows <= 0) return RAT_OK;
                           SrcEventArgs sa;
                           sa.xs = ea.xs; sa.us = ea.us; sa.ldx = ea.ldx; sa.ldu = ea.ldu; sa.N = ea.N; sa.kc = ea.kc; sa.cost = ea.cost;
                           sa.margin = ea.margin; sa.tau = ea.tau; sa.mask = ea.mask; sa.ldy = ea.ldy; sa.p = h->d_src_p;
-                          void *args[] = {&sa};
-                          HIPCHK(hipModuleLaunchKernel(h->src_ev, (unsigned)((ea.kc + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+                          HIPCHK(launch_src(kernel, ea.kc, 64, h->stream, &sa));
                           launch_ev_sums(ea, h->stream);
                           return RAT_OK;
                       },
@@ -2863,21 +2848,8 @@ extern "C" rat_rc rat_policy_rare_event(rat_handle h, const double *x_nom, const
     return re_run(h, F, kn, x_nom, l, L, K, seed, Q, a, b, t_lo, t_hi, shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
 }
 
-static rat_rc rare_noise_args_ok(const char *who, int n, int m, int npn, int npu) {
-    rat_rc rc;
-    if ((rc = user_noise_args_ok(who, n, m, npn, npu))) return rc;
-    if (npn == 0) return fail(RAT_ERR_ARG, std::string(who) + ": normals_per_step is 0: there is no normal to shift");
-    if (npn > 12) return fail(RAT_ERR_UNSUPPORTED, std::string(who) + ": normals_per_step is above 12 (the shift is laid out [N][12])");
-    return RAT_OK;
-}
-
 extern "C" rat_rc rat_rare_event_noise_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms) {
-    if (!source) return fail(RAT_ERR_ARG, "null");
-    rat_rc rc = rare_noise_args_ok("rat_rare_event_noise_check", n, m, normals, uniforms);
-    if (rc) return rc;
-    std::string log;
-    if ((rc = src_compile_rare(source, n, m, normals, uniforms, "gfx950", nullptr, &log))) return fail(rc, log);
-    return RAT_OK;
+    return src_check("rat_rare_event_noise_check", SRC_RARE, source, n, m, normals, uniforms);
 }
 
 // The same for a source model under its rat_user_noise: rat_src_rare_rollout (source_rare.h, a hiprtc module of its own that the first call
@@ -2892,39 +2864,12 @@ static rat_rc rare_src_run(rat_handle h, const std::string &F, const char *who, 
                            const double *shift_in, int32_t n_iter, double rho,
                            double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out) {
     rat_rc rc;
-    const int n = h->n, m = h->m, npn = normals_per_step, npu = uniforms_per_step;
+    const int npn = normals_per_step, npu = uniforms_per_step;
     HIPCHK(hipSetDevice(h->device));
-    if (n_event > 0) {
-        if (!h->src_reu || h->src_reu_npn != npn || h->src_reu_npu != npu || h->src_reu_ne != n_event) {
-            std::shared_ptr<const std::vector<char>> code;
-            std::string log;
-            if ((rc = src_compile_rare_user(h->src_text.c_str(), n, m, npn, npu, n_event, h->src_arch_name, &code, &log))) return fail(rc, log);
-            hipModule_t mod = nullptr;
-            hipFunction_t fn = nullptr;
-            if ((rc = load_module_function(code, "rat_src_rare_rollout", who, &mod, &fn))) return rc;
-            HIPCHK(hipStreamSynchronize(h->stream));
-            if (h->src_reu_mod) (void)hipModuleUnload(h->src_reu_mod);
-            h->src_reu_mod = mod; h->src_reu = fn; h->src_reu_npn = npn; h->src_reu_npu = npu; h->src_reu_ne = n_event;
-        }
-    } else if (!h->src_re || h->src_re_npn != npn || h->src_re_npu != npu) {
-        std::shared_ptr<const std::vector<char>> code;
-        std::string log;
-        if ((rc = src_compile_rare(h->src_text.c_str(), n, m, npn, npu, h->src_arch_name, &code, &log))) return fail(rc, log);
-        hipModule_t mod = nullptr;
-        hipFunction_t fn = nullptr;
-        if ((rc = load_module_function(code, "rat_src_rare_rollout", who, &mod, &fn))) return rc;
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->src_re_mod) (void)hipModuleUnload(h->src_re_mod);
-        h->src_re_mod = mod; h->src_re = fn; h->src_re_npn = npn; h->src_re_npu = npu;
-    }
-    const hipFunction_t kernel = n_event > 0 ? h->src_reu : h->src_re;
-    if (!h->h_un_over && hipHostMalloc((void **)&h->h_un_over, sizeof(int), hipHostMallocDefault) != hipSuccess) {
-        h->h_un_over = nullptr;
-        return fail(RAT_ERR_HIP, F + "hipHostMalloc failed");
-    }
+    hipFunction_t kernel = nullptr;
     int *d_over = nullptr;
-    HIPCHK(hipHostGetDevicePointer((void **)&d_over, h->h_un_over, 0));
-    *h->h_un_over = 0;
+    if ((rc = src_kernel(h, n_event > 0 ? SRC_RARE_USER : SRC_RARE, SrcShape{npn, npu, n_event}, who, &kernel))) return rc;
+    if ((rc = overdraw_flag(&h->h_un_over, F, &d_over))) return rc;
     ReKernels kn;
     kn.ncol = npn; kn.with_wchol = false; kn.adapt = launch_re_adapt_rng;
     kn.rollout = [h, d_over, kernel, event](const ReArgs &ra, bool quad) -> rat_rc {
@@ -2933,14 +2878,12 @@ static rat_rc rare_src_run(rat_handle h, const std::string &F, const char *who, 
         sa.xnom = ra.xnom; sa.l = ra.l; sa.L = ra.L; sa.shift = ra.shift; sa.Qt = ra.Qt; sa.at = ra.at; sa.b = ra.b;
         sa.t_lo = ra.t_lo; sa.t_hi = ra.t_hi; sa.quad = quad ? 1 : 0; sa.K = ra.K; sa.N = h->N; sa.tpw = h->src_mc_tpw; sa.seed = ra.seed;
         sa.margin = ra.margin; sa.logw = ra.logw; sa.dom = ra.dom; sa.p = h->d_src_p; sa.overdraw = d_over;
-        void *args[] = {&sa};
-        HIPCHK(hipModuleLaunchKernel(kernel, (unsigned)((ra.K + sa.tpw - 1) / sa.tpw), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+        HIPCHK(launch_src(kernel, ra.K, sa.tpw, h->stream, &sa));
         return RAT_OK;
     };
     kn.waited = [h, npn, npu, &F]() -> rat_rc {
         if (*(volatile int *)h->h_un_over == 0) return RAT_OK;
-        return fail(RAT_ERR_ARG, F + "a step drew more than was declared (normals_per_step = " + std::to_string(npn) +
-                                 ", uniforms_per_step = " + std::to_string(npu) + "): the overdrawn values were NaN");
+        return fail(RAT_ERR_ARG, overdraw_msg(F + "a step drew more than was declared", npn, npu));
     };
     return re_run(h, F, kn, x_nom, l, L, K, seed, Q, a, b, t_lo, t_hi, shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
 }
@@ -2955,18 +2898,13 @@ extern "C" rat_rc rat_policy_rare_event_noise(rat_handle h, const double *x_nom,
     if ((rc = re_args_head(F, h, x_nom, l, a, stats, K, n_iter, rho))) return rc;
     if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
         return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_noise; the families have rat_policy_rare_event)");
-    if ((rc = rare_noise_args_ok("rat_policy_rare_event_noise", h->n, h->m, normals_per_step, uniforms_per_step))) return rc;
+    if ((rc = src_args_ok("rat_policy_rare_event_noise", SRC_RARE, h->n, h->m, normals_per_step, uniforms_per_step, 0))) return rc;
     return rare_src_run(h, F, "rat_policy_rare_event_noise", x_nom, l, L, K, normals_per_step, uniforms_per_step, seed, 0, 0, Q, a, b, t_lo, t_hi,
                         shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
 }
 
 extern "C" rat_rc rat_rare_event_user_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms, int32_t n_event) {
-    if (!source) return fail(RAT_ERR_ARG, "null");
-    rat_rc rc = user_event_args_ok("rat_rare_event_user_check", n, m, n_event);
-    if (rc || (rc = rare_noise_args_ok("rat_rare_event_user_check", n, m, normals, uniforms))) return rc;
-    std::string log;
-    if ((rc = src_compile_rare_user(source, n, m, normals, uniforms, n_event, "gfx950", nullptr, &log))) return fail(rc, log);
-    return RAT_OK;
+    return src_check("rat_rare_event_user_check", SRC_RARE_USER, source, n, m, normals, uniforms, n_event);
 }
 
 // rat_policy_rare_event_noise with entry `event` of the user's rat_user_event for g, watched at every step the function writes it
@@ -2981,9 +2919,9 @@ extern "C" rat_rc rat_policy_rare_event_user(rat_handle h, const double *x_nom, 
     if ((rc = re_args_head(F, h, x_nom, l, a0, stats, K, n_iter, rho))) return rc;
     if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
         return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_event; the families have rat_policy_rare_event)");
-    if ((rc = user_event_args_ok("rat_policy_rare_event_user", h->n, h->m, n_event))) return rc;
+    if ((rc = src_args_ok("rat_policy_rare_event_user", SRC_EVENTS, h->n, h->m, 0, 0, n_event))) return rc;      // n_event, then event, then the draws
     if (event < 0 || event >= n_event) return fail(RAT_ERR_ARG, F + "event must be in 0 .. n_event - 1");
-    if ((rc = rare_noise_args_ok("rat_policy_rare_event_user", h->n, h->m, normals_per_step, uniforms_per_step))) return rc;
+    if ((rc = src_args_ok("rat_policy_rare_event_user", SRC_RARE, h->n, h->m, normals_per_step, uniforms_per_step, 0))) return rc;
     return rare_src_run(h, F, "rat_policy_rare_event_user", x_nom, l, L, K, normals_per_step, uniforms_per_step, seed, n_event, event, nullptr, a0,
                         0.0, 0, h->N, shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
 }
@@ -4022,26 +3960,14 @@ extern "C" rat_rc rat_pets_problem_set(rat_handle h, const rat_gen_problem_desc 
 }
 
 // ---- generative source models: f_stochastic, c, h written by the user (source_model.cpp, rat_rng.h, source_pets.h) ----------------
-static rat_rc gsrc_args_ok(const char *who, int n, int m, int npn, int npu) {
-    if (n < 1 || m < 1) return fail(RAT_ERR_ARG, std::string(who) + ": n, m must be positive");
-    if (npn < 0 || npu < 0) return fail(RAT_ERR_ARG, std::string(who) + ": normals_per_step, uniforms_per_step must not be negative");
-    if (!src_sizes_ok(n, m)) return fail(RAT_ERR_UNSUPPORTED, std::string(who) + ": source models are compiled for n <= 12, m <= 4");
-    return RAT_OK;
-}
-
 extern "C" rat_rc rat_pets_source_check(const char *source, int32_t n, int32_t m, int32_t normals_per_step, int32_t uniforms_per_step) {
-    if (!source) return fail(RAT_ERR_ARG, "null");
-    rat_rc rc = gsrc_args_ok("rat_pets_source_check", n, m, normals_per_step, uniforms_per_step);
-    if (rc) return rc;
-    std::string log;
-    if ((rc = src_compile_gen(source, n, m, normals_per_step, uniforms_per_step, "gfx950", nullptr, &log))) return fail(rc, log);
-    return RAT_OK;
+    return src_check("rat_pets_source_check", SRC_PETS, source, n, m, normals_per_step, uniforms_per_step);
 }
 
 extern "C" rat_rc rat_pets_problem_set_source(rat_handle h, const char *source, int32_t n, int32_t m, int32_t N, int32_t normals_per_step,
                                               int32_t uniforms_per_step, const double *params, int64_t n_params) {
     if (!h || !source) return fail(RAT_ERR_ARG, "null");
-    rat_rc rc = gsrc_args_ok("rat_pets_problem_set_source", n, m, normals_per_step, uniforms_per_step);
+    rat_rc rc = src_args_ok("rat_pets_problem_set_source", SRC_PETS, n, m, normals_per_step, uniforms_per_step, 0);
     if (rc) return rc;
     if (N < 1) return fail(RAT_ERR_ARG, "rat_pets_problem_set_source: N must be positive");
     if (n_params < 0 || (n_params > 0 && !params)) return fail(RAT_ERR_ARG, "rat_pets_problem_set_source: bad parameter array");
@@ -4051,16 +3977,14 @@ extern "C" rat_rc rat_pets_problem_set_source(rat_handle h, const char *source, 
     HIPCHK(hipGetDeviceProperties(&pr, h->device));
     std::shared_ptr<const std::vector<char>> code;
     std::string log;
-    if ((rc = src_compile_gen(source, n, m, normals_per_step, uniforms_per_step, src_arch(pr.gcnArchName), &code, &log))) return fail(rc, log);
+    if ((rc = src_compile(SRC_PETS, source, n, m, SrcShape{normals_per_step, uniforms_per_step, 0}, src_arch(pr.gcnArchName), &code, &log)))
+        return fail(rc, log);
     hipModule_t mod = nullptr;
     hipFunction_t fr = nullptr;
-    if ((rc = load_module_function(code, "rat_src_pets_rollout", "rat_pets_problem_set_source", &mod, &fr))) return rc;
+    if ((rc = load_module_function(code, src_kind(SRC_PETS).entry, "rat_pets_problem_set_source", &mod, &fr))) return rc;
     std::vector<void *> allocs;
     auto undo = [&](rat_rc r) { free_list(allocs); (void)hipModuleUnload(mod); return r; };
-    if (!h->h_gsrc_over && hipHostMalloc((void **)&h->h_gsrc_over, sizeof(int), hipHostMallocDefault) != hipSuccess) {
-        h->h_gsrc_over = nullptr;
-        return undo(fail(RAT_ERR_HIP, "rat_pets_problem_set_source: hipHostMalloc failed"));
-    }
+    if ((rc = overdraw_flag(&h->h_gsrc_over, "rat_pets_problem_set_source: ", nullptr))) return undo(rc);     // (pets_rollouts asks for its device address)
     std::vector<double> pv(params, params + n_params);
     if (pv.empty()) pv.push_back(0.0);
     const double *dp = nullptr;
@@ -4098,15 +4022,13 @@ static void pets_rollouts(rat_handle h, const PetsArgs &a, hipStream_t s) {
     sa.zn = a.zn; sa.zu = a.zu; sa.seed = a.seed; sa.traj0 = a.traj0; sa.traj_cost = a.traj_cost; sa.p = h->d_gsrc_p;
     sa.overdraw = nullptr;
     (void)hipHostGetDevicePointer((void **)&sa.overdraw, h->h_gsrc_over, 0);
-    void *args[] = {&sa};
-    (void)hipModuleLaunchKernel(h->gsrc_roll, (unsigned)((ntraj + sa.tpw - 1) / sa.tpw), 1, 1, 64, 1, 1, 0, s, args, nullptr);
+    (void)launch_src(h->gsrc_roll, ntraj, sa.tpw, s, &sa);
     launch_pets_mean(a, s);
 }
 // after the wait: a step that drew more than the source declared (the flag is cleared before every launch chain)
 static rat_rc gsrc_overdraw(rat_handle h) {
     if (!h->gsrc || *(volatile int *)h->h_gsrc_over == 0) return RAT_OK;
-    return fail(RAT_ERR_ARG, "generative source model: a step drew more than it declared (normals_per_step = " + std::to_string(h->gsrc_npn) +
-                             ", uniforms_per_step = " + std::to_string(h->gsrc_npu) + "): the overdrawn values were NaN");
+    return fail(RAT_ERR_ARG, overdraw_msg("generative source model: a step drew more than it declared", h->gsrc_npn, h->gsrc_npu));
 }
 
 extern "C" void rat_pets_initialize(rat_pets_solver *s) {                     // pets.jl:70-74

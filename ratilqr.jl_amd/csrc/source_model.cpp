@@ -31,10 +31,7 @@ struct Rtc {
 
 std::mutex g_mu;
 Rtc g_rtc;
-// key: (source, n, m, kind (0 risk-sensitive, 1 generative, 2 the risk-sensitive model's Monte-Carlo rollout, 3 that rollout under the
-// user's noise sampler, 4 that rollout under a shifted proposal with an event's margin: source_rare.h, 5 the user's events on replayed
-// trajectories: source_events.h, 6 kind 4 with the user's event for the margin: source_rare.h under RAT_RARE_USER_EVENT), normals per step,
-// uniforms per step, events of rat_user_event (0 where the kind has none), architecture)
+// key: (source, n, m, SrcKind, normals per step, uniforms per step, events of rat_user_event (0 where the kind takes none), architecture)
 std::map<std::tuple<std::string, int, int, int, int, int, int, std::string>, std::shared_ptr<const std::vector<char>>> g_cache;
 
 bool rtc_load(std::string *why) {           // (g_mu held)
@@ -72,8 +69,23 @@ std::string src_arch(const char *gcn_arch_name) {
     return out.empty() ? std::string("gfx950") : out;
 }
 
-static rat_rc compile_impl(const char *source, int n, int m, int kind, int npn, int npu, int nev, const std::string &arch,
-                          std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
+// indexed by SrcKind:  header                 entry                         entry2               rng_shift draws events rare_user_event
+static const SrcKindRow k_kinds[SRC_NKIND] = {
+    /* SRC_MODEL      */ {"source_kernels.h",    "rat_src_rollout",            "rat_src_linearize", false,    false, false, false},
+    /* SRC_PETS       */ {"source_pets.h",       "rat_src_pets_rollout",       nullptr,             false,    true,  false, false},
+    /* SRC_NOISY      */ {"source_noisy.h",      "rat_src_noisy_rollout",      nullptr,             false,    false, false, false},
+    /* SRC_USER_NOISE */ {"source_user_noise.h", "rat_src_user_noisy_rollout", nullptr,             false,    true,  false, false},
+    /* SRC_RARE       */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  false, false},
+    /* SRC_EVENTS     */ {"source_events.h",     "rat_src_user_events",        nullptr,             false,    false, true,  false},
+    /* SRC_RARE_USER  */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  true,  true},
+};
+
+const SrcKindRow &src_kind(SrcKind kind) { return k_kinds[kind]; }
+
+rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShape &shape, const std::string &arch,
+                   std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
+    const SrcKindRow &row = k_kinds[kind];
+    const int npn = row.draws ? shape.npn : 0, npu = row.draws ? shape.npu : 0, nev = row.events ? shape.nev : 0;
     const auto t0 = std::chrono::steady_clock::now();
     auto done = [&](rat_rc rc) {
         if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -81,7 +93,7 @@ static rat_rc compile_impl(const char *source, int n, int m, int kind, int npn, 
     };
     std::lock_guard<std::mutex> lk(g_mu);
     if (cached) *cached = false;
-    const auto key = std::make_tuple(std::string(source), n, m, kind, npn, npu, nev, arch);
+    const auto key = std::make_tuple(std::string(source), n, m, (int)kind, npn, npu, nev, arch);
     auto it = g_cache.find(key);
     if (it != g_cache.end()) {
         if (code) *code = it->second;
@@ -90,16 +102,11 @@ static rat_rc compile_impl(const char *source, int n, int m, int kind, int npn, 
     }
     std::string why;
     if (!rtc_load(&why)) { if (log) *log = why; return done(RAT_ERR_UNSUPPORTED); }
-    // the user's source between the AD and rat_rng headers and the kernels (a source that defines all four functions compiles as either
-    // kind); #line makes the compiler's messages name lines of the user's text.  A generative source does not define rat_user_f:
-    // source_kernels.h is not part of its text
-    const std::string text = std::string(kind == 4 || kind == 6 ? "#define RAT_RNG_SHIFT 1\n" : "") + "#include \"source_args.h\"\n#include \"rat_ad.h\"\n#include \"rat_rng.h\"\n#line 1 \"model.hip\"\n" +
-                             source + (kind == 0 ? "\n#line 1 \"source_kernels.h\"\n#include \"source_kernels.h\"\n"
-                                      : kind == 2 ? "\n#line 1 \"source_noisy.h\"\n#include \"source_noisy.h\"\n"
-                                      : kind == 3 ? "\n#line 1 \"source_user_noise.h\"\n#include \"source_user_noise.h\"\n"
-                                      : kind == 4 || kind == 6 ? "\n#line 1 \"source_rare.h\"\n#include \"source_rare.h\"\n"
-                                      : kind == 5 ? "\n#line 1 \"source_events.h\"\n#include \"source_events.h\"\n"
-                                                  : "\n#line 1 \"source_pets.h\"\n#include \"source_pets.h\"\n");
+    // the user's source between the AD and rat_rng headers and the kind's kernels (a source that defines all four functions compiles as
+    // either of the first two kinds); #line makes the compiler's messages name lines of the user's text
+    const std::string text = std::string(row.rng_shift ? "#define RAT_RNG_SHIFT 1\n" : "") +
+                             "#include \"source_args.h\"\n#include \"rat_ad.h\"\n#include \"rat_rng.h\"\n#line 1 \"model.hip\"\n" + source +
+                             "\n#line 1 \"" + row.header + "\"\n#include \"" + row.header + "\"\n";
     const char *hdr[] = {k_embed_layout_h, k_embed_source_args_h, k_embed_rat_ad_h, k_embed_source_kernels_h, k_embed_rat_normal_h,
                          k_embed_rat_philox_h, k_embed_rat_rng_h, k_embed_source_pets_h, k_embed_source_noisy_h, k_embed_source_user_noise_h,
                          k_embed_source_rare_h, k_embed_source_events_h};
@@ -113,8 +120,10 @@ static rat_rc compile_impl(const char *source, int n, int m, int kind, int npn, 
     const std::string dn = "-DRAT_N=" + std::to_string(n), dm = "-DRAT_M=" + std::to_string(m), oa = "--offload-arch=" + arch;
     const std::string dpn = "-DRAT_PETS_NORMALS=" + std::to_string(npn), dpu = "-DRAT_PETS_UNIFORMS=" + std::to_string(npu);
     const std::string dne = "-DRAT_N_EVENT=" + std::to_string(nev);
-    const char *opts[] = {"-O3", "-std=c++17", dn.c_str(), dm.c_str(), oa.c_str(), dpn.c_str(), dpu.c_str(), dne.c_str(), "-DRAT_RARE_USER_EVENT=1"};
-    const hiprtcResult rc = g_rtc.compile(prog, kind == 6 ? 9 : kind == 5 ? 8 : 7, opts);   // (the kinds from before see the options from before)
+    std::vector<const char *> opts = {"-O3", "-std=c++17", dn.c_str(), dm.c_str(), oa.c_str(), dpn.c_str(), dpu.c_str()};
+    if (row.events) opts.push_back(dne.c_str());
+    if (row.rare_user_event) opts.push_back("-DRAT_RARE_USER_EVENT=1");
+    const hiprtcResult rc = g_rtc.compile(prog, (int)opts.size(), opts.data());
     size_t ls = 0;
     std::string lg;
     if (g_rtc.log_size(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
@@ -141,39 +150,4 @@ static rat_rc compile_impl(const char *source, int n, int m, int kind, int npn, 
     if (code) *code = obj;
     if (log) *log = lg;
     return done(RAT_OK);
-}
-
-rat_rc src_compile(const char *source, int n, int m, const std::string &arch, std::shared_ptr<const std::vector<char>> *code,
-                   std::string *log, double *ms, bool *cached) {
-    return compile_impl(source, n, m, 0, 0, 0, 0, arch, code, log, ms, cached);
-}
-
-rat_rc src_compile_gen(const char *source, int n, int m, int npn, int npu, const std::string &arch,
-                       std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
-    return compile_impl(source, n, m, 1, npn, npu, 0, arch, code, log, ms, cached);
-}
-
-rat_rc src_compile_noisy(const char *source, int n, int m, const std::string &arch, std::shared_ptr<const std::vector<char>> *code,
-                         std::string *log, double *ms, bool *cached) {
-    return compile_impl(source, n, m, 2, 0, 0, 0, arch, code, log, ms, cached);
-}
-
-rat_rc src_compile_user_noise(const char *source, int n, int m, int npn, int npu, const std::string &arch,
-                              std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
-    return compile_impl(source, n, m, 3, npn, npu, 0, arch, code, log, ms, cached);
-}
-
-rat_rc src_compile_rare(const char *source, int n, int m, int npn, int npu, const std::string &arch,
-                        std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
-    return compile_impl(source, n, m, 4, npn, npu, 0, arch, code, log, ms, cached);
-}
-
-rat_rc src_compile_events(const char *source, int n, int m, int n_event, const std::string &arch,
-                          std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
-    return compile_impl(source, n, m, 5, 0, 0, n_event, arch, code, log, ms, cached);
-}
-
-rat_rc src_compile_rare_user(const char *source, int n, int m, int npn, int npu, int n_event, const std::string &arch,
-                             std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
-    return compile_impl(source, n, m, 6, npn, npu, n_event, arch, code, log, ms, cached);
 }

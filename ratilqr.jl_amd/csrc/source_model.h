@@ -8,35 +8,35 @@
 
 #include "../../include/ratilqr.h"
 
-// Compiles the user's source behind the embedded headers (rat_ad.h, rat_rng.h, source_args.h, layout.h; source_kernels.h after it) for
-// `arch` with -O3 -std=c++17 -DRAT_N=n -DRAT_M=m -DRAT_PETS_NORMALS=0 -DRAT_PETS_UNIFORMS=0.  RAT_OK: *code holds the code object (shared with the cache).  RAT_ERR_ARG: *log holds the
-// compiler's log.  RAT_ERR_UNSUPPORTED: hiprtc is not available in this process.  *ms (if not null): wall time of the call; *cached:
-// whether the code object came from the cache.
-rat_rc src_compile(const char *source, int n, int m, const std::string &arch, std::shared_ptr<const std::vector<char>> *code,
-                   std::string *log, double *ms = nullptr, bool *cached = nullptr);
-// The same for a generative source (PETS): source_pets.h after it, -DRAT_PETS_NORMALS=npn -DRAT_PETS_UNIFORMS=npu.  Cached apart from
-// risk-sensitive compiles of the same text.
-rat_rc src_compile_gen(const char *source, int n, int m, int npn, int npu, const std::string &arch,
-                       std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
-// The Monte-Carlo rollout kernel of a risk-sensitive source (rat_policy_evaluate): source_noisy.h after it.  A third kind with a cache key
-// of its own, compiled on the first evaluation of a source problem, not when the problem is set.
-rat_rc src_compile_noisy(const char *source, int n, int m, const std::string &arch, std::shared_ptr<const std::vector<char>> *code,
-                         std::string *log, double *ms = nullptr, bool *cached = nullptr);
-// That rollout under the user's noise sampler (rat_policy_evaluate_noise): source_user_noise.h after the source, which must define
-// RAT_USER_NOISE and rat_user_noise; -DRAT_PETS_NORMALS=npn -DRAT_PETS_UNIFORMS=npu.  A fourth kind, compiled on the first such evaluation.
-rat_rc src_compile_user_noise(const char *source, int n, int m, int npn, int npu, const std::string &arch,
-                              std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
-// That rollout under a shifted proposal with the margin of one event (rat_policy_rare_event_noise): source_rare.h after the source, and
-// "#define RAT_RNG_SHIFT 1" in front of rat_rng.h -- the only kind that defines it.  A fifth kind, compiled on the first such call.
-rat_rc src_compile_rare(const char *source, int n, int m, int npn, int npu, const std::string &arch,
-                        std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
-// The user's events on replayed trajectories (rat_policy_events_user): source_events.h after the source, which must define RAT_USER_EVENT
-// and rat_user_event; -DRAT_N_EVENT=n_event, no draws.  A sixth kind, compiled by the first call that names this n_event.
-rat_rc src_compile_events(const char *source, int n, int m, int n_event, const std::string &arch,
-                          std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
-// src_compile_rare with the user's event for the margin (rat_policy_rare_event_user): the same text with -DRAT_RARE_USER_EVENT=1
-// -DRAT_N_EVENT=n_event.  A seventh kind.
-rat_rc src_compile_rare_user(const char *source, int n, int m, int npn, int npu, int n_event, const std::string &arch,
-                             std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
+// The modules a source can be compiled into.  (The numbers are part of the cache key.)
+enum SrcKind {
+    SRC_MODEL = 0,       // the risk-sensitive model's rollout and linearisation (rat_problem_set_source)
+    SRC_PETS,            // a generative source's PETS rollout (rat_pets_problem_set_source)
+    SRC_NOISY,           // the Monte-Carlo rollout under N(0, W) (rat_policy_evaluate)
+    SRC_USER_NOISE,      // that rollout under the user's rat_user_noise (rat_policy_evaluate_noise)
+    SRC_RARE,            // that under a shifted proposal, with a quadratic event's margin (rat_policy_rare_event_noise)
+    SRC_EVENTS,          // the user's rat_user_event on replayed trajectories (rat_policy_events_user)
+    SRC_RARE_USER,       // SRC_RARE with entry `event` of rat_user_event for the margin (rat_policy_rare_event_user)
+    SRC_NKIND
+};
+// One row per kind: what its translation unit is made of and what the module exports.  Every kind is the user's text behind
+// source_args.h, rat_ad.h and rat_rng.h, then `header` (under a #line of its own), compiled for `arch` with -O3 -std=c++17 -DRAT_N=n
+// -DRAT_M=m -DRAT_PETS_NORMALS=npn -DRAT_PETS_UNIFORMS=npu (0 where the kind takes no draws).
+struct SrcKindRow {
+    const char *header;          // embedded header with the kind's kernels
+    const char *entry, *entry2;  // kernels the module exports (entry2: NULL but for SRC_MODEL's linearisation)
+    bool rng_shift;              // "#define RAT_RNG_SHIFT 1" in front of everything
+    bool draws;                  // takes npn, npu (a sampler's source must define RAT_USER_NOISE: the header refuses it otherwise)
+    bool events;                 // takes nev: -DRAT_N_EVENT=nev (the source must define RAT_USER_EVENT)
+    bool rare_user_event;        // -DRAT_RARE_USER_EVENT=1
+};
+const SrcKindRow &src_kind(SrcKind kind);
+struct SrcShape { int npn = 0, npu = 0, nev = 0; };      // (fields a kind does not take are read as 0)
+
+// Compiles `source` as `kind`.  RAT_OK: *code holds the code object (shared with the cache, which keys on source, n, m, kind, shape and
+// arch).  RAT_ERR_ARG: *log holds the compiler's log.  RAT_ERR_UNSUPPORTED: hiprtc is not available in this process.  *ms (if not null):
+// wall time of the call; *cached: whether the code object came from the cache.
+rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShape &shape, const std::string &arch,
+                   std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms = nullptr, bool *cached = nullptr);
 // The offload-arch string for the device's reported gcnArchName (an xnack+ feature is never passed on).
 std::string src_arch(const char *gcn_arch_name);
