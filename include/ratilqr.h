@@ -331,6 +331,27 @@ rat_rc rat_policy_worst_case(rat_handle h, const double *cost, int64_t K, const 
  * the problem, its parameters or the policy changed since the evaluation. */
 rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
                                         double *rows_out, double *mean_out, double *cov_out);
+/* What the adversary does to the noise: the mean and covariance of the disturbance w_t at every step t = 0 .. N-1, and its covariance with
+ * the (x_t, u_t) it acts on, under the nominal distribution q (a theta = 0 row) and under p* ~ exp(theta* J) q of each kl_bound (and the
+ * tilt of each given theta).  w_t is what the rollout added: chol_lower(W(t)) z_t for the families, what rat_user_noise wrote for a source
+ * model.  The call takes no policy and no noise: it REPLAYS the last evaluation exactly as rat_policy_worst_case_trajectory does -- the
+ * same chunks and seeds, the same bit-for-bit check against the stored costs -- with the rollouts keeping w_t in a staging buffer of the
+ * handle, and sums per step and row S0, S1 and S2 = sum y Dw Dw' (one f64 MFMA per four rollouts, step and row) and, when cov_wz_out is
+ * given, sum y Dw Dz' (a second one) of Dw = w_t - c_w[t], Dz = (x_t, u_t) - c_t.  c_t is the trajectory call's centre; c_w[t] is the w_t
+ * of the first rollout whose cost is not NaN among the first min(K, 65536) (0 where that is not finite, or where there is none).  Fixed
+ * summation order, no floating-point atomics: the same call returns the same bits, and a row's bits do not depend on the other rows.
+ *   kl_bound, theta   as rat_policy_worst_case's (the same refusals)
+ *   rows_out   [(n_bound + n_theta)][RAT_WC_NSTAT]: rat_policy_worst_case's rows of the same arguments, bit for bit (bounds, then thetas)
+ *   mean_w_out [(n_bound + n_theta)][N][n]: E w_t
+ *   cov_w_out  [(n_bound + n_theta)][N][n^2] column-major, the population form sum y (w - mean)(w - mean)' / sum y; exactly symmetric
+ *   cov_wz_out [(n_bound + n_theta)][N][n (n+m)] column-major (w's component the row, z = (x_t, u_t) the column), or NULL: the second
+ *              product is then not formed.  cov_wz pinv(cov_z) on the x block is the adversary's feedback gain.
+ * A RAT_WC_SATURATED row holds the moments of the rollouts that attain Jmax; RAT_WC_EMPTY and RAT_WC_NONFINITE rows are NaN.  A
+ * DomainError rollout carries no weight (it is selected out: its w may hold NaN).
+ * Served and refused as rat_policy_worst_case_trajectory, with the same codes; the cap of its own is rows x N above 1899 (partial sums of
+ * 552 doubles in 8 slots per row and step against 64 MiB): RAT_ERR_UNSUPPORTED. */
+rat_rc rat_policy_worst_case_disturbance(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                         double *rows_out, double *mean_w_out, double *cov_w_out, double *cov_wz_out);
 /* The tail risk of a policy, from the K Monte-Carlo costs: per level alpha the alpha-quantile of the cost (value at risk: with probability
  * alpha the cost stays below it) and the conditional value at risk, the expected cost of the worst (1 - alpha) share of the rollouts.  With
  * n = N_OK and s_1 <= ... <= s_n the OK costs in ascending order: a = n alpha (one rounded product), k = clamp(ceil(a), 1, n), VAR = s_k (bit

@@ -458,6 +458,31 @@ function policy_worst_case_trajectory(s::ILEQGSolver; kl_bounds=Float64[], theta
 end
 
 """
+policy_worst_case_disturbance(s; kl_bounds, thetas, cross): what the adversary does to the noise (rat_policy_worst_case_disturbance).  The
+mean and covariance of the disturbance w_t at every step and its covariance with the state and control it acts on, under the worst-case
+distribution p* ∝ exp(θ* J) q of each KL radius and under the tilt of each given θ (θ = 0 is the nominal distribution q), formed on the
+device by replaying the last evaluate_policy on this solver's handle like policy_worst_case_trajectory.  Returns (bounds, thetas): each a
+named tuple of policy_worst_case's row vectors and, with R rows, mean_w (n, N, R), cov_w (n, n, N, R) and, with cross, cov_wx (n, n, N, R)
+and cov_wu (n, m, N, R) (`nothing` otherwise); population covariances.  cov_wx[:, :, t, r] * pinv(cov_x[:, :, t, r]) of
+policy_worst_case_trajectory is the adversary's feedback gain.
+"""
+function policy_worst_case_disturbance(s::ILEQGSolver; kl_bounds=Float64[], thetas=Float64[], cross::Bool=true)
+    h = s.h
+    n, m, N = dims(h.problem)
+    d = collect(Float64, kl_bounds); th = collect(Float64, thetas)
+    nb = length(d); nt = length(th); R = nb + nt; q = n + m
+    rows = zeros(8, R); mean = zeros(n, N, R); cov = zeros(n, n, N, R)
+    wz = cross ? zeros(n, q, N, R) : nothing
+    check(ccall((:rat_policy_worst_case_disturbance, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, nb > 0 ? d : C_NULL, nb, nt > 0 ? th : C_NULL, nt, rows, mean, cov, cross ? wz : C_NULL))
+    part(r) = (theta=rows[1, r], kl=rows[2, r], bound=rows[3, r], bound_se=rows[4, r], tilt_mean=rows[5, r], tilt_var=rows[6, r],
+               ess=rows[7, r], flag=Int.(rows[8, r]), mean_w=mean[:, :, r], cov_w=cov[:, :, :, r],
+               cov_wx=cross ? wz[:, 1:n, :, r] : nothing, cov_wu=cross ? wz[:, n+1:q, :, r] : nothing)
+    (bounds=part(1:nb), thetas=part(nb+1:R))
+end
+
+"""
 policy_events(s, Q, a, b, t_lo, t_hi; kl_bounds, thetas, want_steps, want_margins): how often the policy violates safety events
 (rat_policy_events).  Event i is z' Q[:, :, i] z + a[:, i]' z + b[i] > 0 at a step t_lo[i] ≤ t ≤ t_hi[i] (0-based steps, z = (x_t, u_t));
 Q === nothing: every event is linear.  Per row (the worst-case distribution of each KL radius, the tilt of each θ; θ = 0 is the nominal
@@ -1458,7 +1483,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, rare_event_probability_user, rare_event_user_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, rare_event_probability_user, rare_event_user_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

@@ -93,6 +93,7 @@ EXPORTS = [
     "rat_policy_evaluate_noise", "rat_user_noise_check",
     "rat_policy_worst_case",
     "rat_policy_worst_case_trajectory",
+    "rat_policy_worst_case_disturbance",
     "rat_policy_tail_risk",
     "rat_policy_events", "rat_kl_event_bound",
     "rat_policy_rare_event",
@@ -149,6 +150,7 @@ def lib():
         _lib.rat_user_noise_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
         _lib.rat_policy_worst_case.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp]
         _lib.rat_policy_worst_case_trajectory.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp]
+        _lib.rat_policy_worst_case_disturbance.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp]
         _lib.rat_policy_tail_risk.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int32, _dp, _dp]
         _lib.rat_policy_events.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _ip, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp]
         _lib.rat_kl_event_bound.argtypes = [C.c_double, C.c_double, _dp]

@@ -228,6 +228,11 @@ struct rat_handle_s {
     double *d_wt_y = nullptr; size_t cap_wt_y = 0;           // [rows][chunk] weights
     double *d_wt_part = nullptr; size_t cap_wt_part = 0;     // [rows][N+1][WT_SLOTS][WT_PART] partials
     double *d_wt_out = nullptr; size_t cap_wt_out = 0;       // centre [N+1][16] | mean | cov | S0, sum y^2 per row | mismatch count
+    // the worst-case disturbance moments (rat_policy_worst_case_disturbance, policy_mc.hip) ride on the same replay, with the rollouts
+    // keeping w; only that call allocates these
+    double *d_mc_wo = nullptr; size_t cap_mc_wo = 0;         // [chunk][N][n] disturbance staging (the leading dimension of d_mc_xo)
+    double *d_wd_part = nullptr; size_t cap_wd_part = 0;     // [rows][N][WT_SLOTS][WD_PART] partials
+    double *d_wd_out = nullptr; size_t cap_wd_out = 0;       // c [N+1][16] | c_w [N][16] | mean_w | cov_w | cov_wz | S0, sum y^2 per row | mismatch count
     // the safety events (rat_policy_events, policy_mc.hip) ride on the same replay; grown on demand
     double *d_ev_out = nullptr; size_t cap_ev_out = 0;       // Q [16][256] | a [16][16] | b [16] | windows | event_out | step_out | mismatch count
     double *d_ev_part = nullptr; size_t cap_ev_part = 0;     // [row batches][steps + events][EV_SLOTS][EV_PART] partials
@@ -428,6 +433,7 @@ extern "C" void rat_destroy(rat_handle h) {
     for (double *q : {h->d_mc_zu, h->d_mc_xo, h->d_mc_uo}) if (q) (void)hipFree(q);
     for (double *q : {h->d_wc_red, h->d_wc_w, h->d_tr_red}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_wt_cost, (void *)h->d_wt_dom, (void *)h->d_wt_y, (void *)h->d_wt_part, (void *)h->d_wt_out}) if (q) (void)hipFree(q);
+    for (double *q : {h->d_mc_wo, h->d_wd_part, h->d_wd_out}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_ev_out, (void *)h->d_ev_part, (void *)h->d_ev_margin, (void *)h->d_ev_tau, (void *)h->d_ev_mask}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_re_in, (void *)h->d_re_margin, (void *)h->d_re_logw, (void *)h->d_re_dom, (void *)h->d_re_part, (void *)h->d_re_red}) if (q) (void)hipFree(q);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
@@ -2020,22 +2026,22 @@ static PolicyDev policy_dev(const double *base, size_t o_x, size_t o_l, size_t o
 }
 
 // rollouts k0 .. k0 + kc of a family on the tile path (noisy_rollout_kernel), enqueued; d_z: the chunk's injected normals, NULL for the
-// generator; x_out / u_out / cost / dom: where this chunk's results go
+// generator; x_out / u_out / cost / dom: where this chunk's results go; w_out: where its disturbances go (the disturbance replay alone)
 static void launch_noisy_chunk(rat_handle h, const PolicyDev &p, int64_t k0, int64_t kc, int64_t chunk, uint64_t seed, const double *d_z,
-                               double *x_out, double *u_out, double *cost, int *dom) {
+                               double *x_out, double *u_out, double *cost, int *dom, double *w_out = nullptr) {
     NoisyArgs a;
     a.pb = h->pb; a.Wchol = p.Wchol; a.xnom = p.x; a.l = p.l; a.L = p.L; a.K = (long)kc; a.z = d_z; a.seed = chunk_seed(seed, k0, chunk);
-    a.x_out = x_out; a.u_out = u_out; a.cost = cost; a.dom = dom;
+    a.x_out = x_out; a.u_out = u_out; a.cost = cost; a.dom = dom; a.w_out = w_out;
     launch_noisy_rollout(a, h->stream);
 }
 // the same for a source model under its rat_user_noise (the handle's SRC_USER_NOISE kernel): the generator counts rollouts globally
 // (j0 = k0), so every chunk runs under the caller's seed; d_over: the device address of the overdraw flag
 static rat_rc launch_user_noisy_chunk(rat_handle h, const PolicyDev &p, int64_t k0, int64_t kc, uint64_t seed, const double *d_zn,
-                                      const double *d_zu, double *x_out, double *u_out, double *cost, int *d_over) {
+                                      const double *d_zu, double *x_out, double *u_out, double *cost, int *d_over, double *w_out = nullptr) {
     SrcUserNoisyArgs a;
     a.xnom = p.x; a.l = p.l; a.L = p.L; a.zn = d_zn; a.zu = d_zu;
     a.K = (long)kc; a.j0 = (long)k0; a.N = h->N; a.tpw = h->src_mc_tpw; a.seed = seed; a.cost = cost;
-    a.x_out = x_out; a.u_out = u_out; a.p = h->d_src_p; a.overdraw = d_over;
+    a.x_out = x_out; a.u_out = u_out; a.p = h->d_src_p; a.overdraw = d_over; a.w_out = w_out;
     HIPCHK(launch_src(h->src_slot[SRC_USER_NOISE].fn, kc, a.tpw, h->stream, &a));
     return RAT_OK;
 }
@@ -2444,10 +2450,11 @@ struct ReplayChunk { int64_t k0, kc; };
 // Jmax and the rows: d_wc_red), then chunk by chunk the rollouts into d_mc_xo / d_mc_uo / d_wt_cost (/ d_wt_dom) and wct_weights into
 // d_wt_y (ta's replay fields are filled here, the mismatch count is *d_mismatch), and behind(ta, chunk) enqueues the caller's own kernels
 // behind each.  The
-// stream orders a chunk's rollouts behind the sums of the one before.
+// stream orders a chunk's rollouts behind the sums of the one before.  d_wo (rat_policy_worst_case_disturbance alone; the caller grew it):
+// the rollouts keep the chunk's disturbances there, [kc][N][ldx].
 template <class Behind>
 static rat_rc replay_chunks(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta, int *d_mismatch,
-                            WtArgs &ta, Behind &&behind) {
+                            WtArgs &ta, Behind &&behind, double *d_wo = nullptr) {
     const rat_handle_s::McReplay rec = h->mc_rec;
     const bool source = h->pb.model == RAT_MODEL_SOURCE;
     const int n = h->n, m = h->m, N = h->N, nrows = n_bound + n_theta;
@@ -2478,9 +2485,9 @@ static rat_rc replay_chunks(rat_handle h, const double *kl_bound, int32_t n_boun
     for (int64_t k0 = 0; k0 < K; k0 += chunk) {
         const int64_t kc = std::min(chunk, K - k0);
         if (source) {
-            if ((rc = launch_user_noisy_chunk(h, dev, k0, kc, rec.seed, nullptr, nullptr, h->d_mc_xo, h->d_mc_uo, h->d_wt_cost, d_over))) return rc;
+            if ((rc = launch_user_noisy_chunk(h, dev, k0, kc, rec.seed, nullptr, nullptr, h->d_mc_xo, h->d_mc_uo, h->d_wt_cost, d_over, d_wo))) return rc;
         } else {
-            launch_noisy_chunk(h, dev, k0, kc, chunk, rec.seed, nullptr, h->d_mc_xo, h->d_mc_uo, h->d_wt_cost, h->d_wt_dom);
+            launch_noisy_chunk(h, dev, k0, kc, chunk, rec.seed, nullptr, h->d_mc_xo, h->d_mc_uo, h->d_wt_cost, h->d_wt_dom, d_wo);
         }
         ta.kc = (long)kc; ta.cost = h->d_mc_cost + k0;
         launch_wct_weights(ta, h->stream);
@@ -2493,6 +2500,24 @@ static rat_rc replay_mismatch(const std::string &F, int bad, int64_t K) {
     if (bad == 0) return RAT_OK;
     return fail(RAT_ERR_ARG, F + std::to_string(bad) + " of " + std::to_string(K) + " replayed rollouts cost something else than the "
                              "evaluation found: " + REPLAY_CHANGED);
+}
+
+// The centre c_t of the (x_t, u_t) tile, enqueued into centre [N+1][16]: (x_nom, l) under a policy; open loop the noise-free trajectory of
+// the handle's own rollout from the pack's (x_0, l)
+static rat_rc replay_centre(rat_handle h, double *centre) {
+    const rat_handle_s::McReplay &rec = h->mc_rec;
+    const double *d_x = h->d_mc_in + rec.o_x, *d_l = h->d_mc_in + rec.o_l;
+    const double *cx = d_x;
+    if (!rec.has_L) {
+        StateDev st;
+        rat_rc rc;
+        if ((rc = op_prepare(h, 0.0, 0.0, h->opts.delta_0, &st))) return rc;
+        RolloutArgs ra; ra.st = st; ra.pb = h->pb; ra.op = h->opd; ra.dump = h->d_dump; ra.mode = 0; ra.x0 = d_x; ra.u0 = d_l; ra.notile = 0; ra.multi = 0;
+        model_rollout(h, ra, h->stream);
+        cx = h->st.xs;                                                // (slot 0: [N+1][12])
+    }
+    launch_wct_centre(cx, d_l, h->n, h->m, h->N, centre, h->stream);
+    return RAT_OK;
 }
 
 // The state and control mean and covariance at every step under the nominal distribution q and under the worst-case distribution
@@ -2514,17 +2539,7 @@ extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *k
                  o_cnt = o_ess + 2 * (size_t)nrows, n_out = o_cnt + 1, n_part = (size_t)nrows * (N + 1) * WT_SLOTS * WT_PART;
     if ((rc = grow(&h->d_wt_part, &h->cap_wt_part, n_part))) return rc;
     if ((rc = grow(&h->d_wt_out, &h->cap_wt_out, n_out))) return rc;
-    const double *d_x = h->d_mc_in + rec.o_x, *d_l = h->d_mc_in + rec.o_l;
-    // the centre: (x_nom, l) under a policy; open loop the noise-free trajectory of the handle's own rollout from the pack's (x_0, l)
-    const double *cx = d_x;
-    if (!rec.has_L) {
-        StateDev st;
-        if ((rc = op_prepare(h, 0.0, 0.0, h->opts.delta_0, &st))) return rc;
-        RolloutArgs ra; ra.st = st; ra.pb = h->pb; ra.op = h->opd; ra.dump = h->d_dump; ra.mode = 0; ra.x0 = d_x; ra.u0 = d_l; ra.notile = 0; ra.multi = 0;
-        model_rollout(h, ra, h->stream);
-        cx = h->st.xs;                                                // (slot 0: [N+1][12])
-    }
-    launch_wct_centre(cx, d_l, n, m, N, h->d_wt_out, h->stream);
+    if ((rc = replay_centre(h, h->d_wt_out))) return rc;
     HIPCHK(hipMemsetAsync(h->d_wt_part, 0, n_part * 8, h->stream));
     WtArgs ta;
     memset(&ta, 0, sizeof(ta));
@@ -2546,6 +2561,68 @@ extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *k
     if ((rc = replay_mismatch(F, bad, K))) return rc;
     // the rows' effective sample size against the moment kernel's own S0^2 / sum y^2: two routes to one number (the rows' sums are centred,
     // these are not: 1e-6 relative is far above what either loses and far below any error of the weights)
+    for (int r = 0; r < nrows; ++r) {
+        const double e_row = rows[r * WC_NSTAT + RAT_WC_ESS], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
+        if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
+            return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
+                                     " is not the row's " + std::to_string(e_row));
+    }
+    for (int i = 0; i < nrows * WC_NSTAT; ++i) rows_out[i] = rows[i];
+    return RAT_OK;
+}
+
+// What the adversary does to the noise: the mean and covariance of the disturbance w_t at every step, and its covariance with the
+// (x_t, u_t) it acts on, under q and under p* ~ exp(theta* J) q, one row per kl_bound / theta.  The trajectory call's replay with the
+// rollouts keeping w_t (d_mc_wo) and wcd_moments behind each chunk; one enqueue chain, one host wait.
+extern "C" rat_rc rat_policy_worst_case_disturbance(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                                    double *rows_out, double *mean_w_out, double *cov_w_out, double *cov_wz_out) {
+    const std::string F = "rat_policy_worst_case_disturbance: ";
+    rat_rc rc;
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && mean_w_out && cov_w_out))) return rc;
+    const rat_handle_s::McReplay rec = h->mc_rec;
+    const int n = h->n, m = h->m, N = h->N, nrows = n_bound + n_theta, d = n + m;
+    if ((long)nrows * N > WD_MAX_ROWSTEPS)
+        return fail(RAT_ERR_UNSUPPORTED, F + "rows x N = " + std::to_string((long)nrows * N) + " is above " +
+                                         std::to_string(WD_MAX_ROWSTEPS) + " (64 MiB of partial sums): ask for fewer rows per call");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t K = rec.K, chunk = mc_chunk(K);
+    const bool cross = cov_wz_out != nullptr;
+    const int ldw = (h->pb.model == RAT_MODEL_SOURCE) ? n : XSTR;     // (the leading dimension of the staged x)
+    const size_t rs = (size_t)nrows * N;
+    const size_t o_cw = (size_t)(N + 1) * 16, o_mean = o_cw + (size_t)N * 16, o_cov = o_mean + rs * n, o_wz = o_cov + rs * n * n,
+                 o_ess = o_wz + (cross ? rs * n * d : 0), o_cnt = o_ess + 2 * (size_t)nrows, n_out = o_cnt + 1,
+                 n_part = rs * WT_SLOTS * WD_PART;
+    if ((rc = grow(&h->d_wd_part, &h->cap_wd_part, n_part))) return rc;
+    if ((rc = grow(&h->d_wd_out, &h->cap_wd_out, n_out))) return rc;
+    if ((rc = grow(&h->d_mc_wo, &h->cap_mc_wo, (size_t)chunk * N * ldw))) return rc;
+    if ((rc = replay_centre(h, h->d_wd_out))) return rc;
+    HIPCHK(hipMemsetAsync(h->d_wd_part, 0, n_part * 8, h->stream));
+    WdArgs da;
+    memset(&da, 0, sizeof(da));
+    da.t.centre = h->d_wd_out;
+    da.ws = h->d_mc_wo; da.ldw = ldw; da.cross = cross ? 1 : 0; da.cw = h->d_wd_out + o_cw; da.part = h->d_wd_part;
+    da.mean_w = h->d_wd_out + o_mean; da.cov_w = h->d_wd_out + o_cov; da.cov_wz = cross ? h->d_wd_out + o_wz : nullptr;
+    da.ess = h->d_wd_out + o_ess;
+    if ((rc = replay_chunks(h, kl_bound, n_bound, theta, n_theta, reinterpret_cast<int *>(h->d_wd_out + o_cnt), da.t,
+                            [&](const WtArgs &, ReplayChunk c) -> rat_rc {
+                                if (c.k0 == 0) launch_wcd_centre(da, h->stream);   // c_w: fixed before the first chunk's sums
+                                launch_wcd_chunk(da, h->stream);
+                                return RAT_OK;
+                            }, h->d_mc_wo)))
+        return rc;
+    launch_wcd_final(da, h->stream);
+    HIPCHK(hipGetLastError());
+    double rows[WC_MAX_ROWS * WC_NSTAT], ess[WC_MAX_ROWS * 2];
+    int bad = 0;
+    HIPCHK(hipMemcpyAsync(rows, h->d_wc_red + WC_O_ROWS, (size_t)nrows * WC_NSTAT * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(ess, h->d_wd_out + o_ess, (size_t)nrows * 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&bad, h->d_wd_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(mean_w_out, h->d_wd_out + o_mean, rs * n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(cov_w_out, h->d_wd_out + o_cov, rs * n * n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (cross) HIPCHK(hipMemcpyAsync(cov_wz_out, h->d_wd_out + o_wz, rs * n * d * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = replay_mismatch(F, bad, K))) return rc;
+    // the rows' effective sample size against the moment kernel's own, as rat_policy_worst_case_trajectory holds it
     for (int r = 0; r < nrows; ++r) {
         const double e_row = rows[r * WC_NSTAT + RAT_WC_ESS], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
         if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))

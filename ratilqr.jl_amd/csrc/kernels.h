@@ -151,6 +151,7 @@ struct NoisyArgs {              // Monte-Carlo rollouts under process noise (sim
     unsigned long long seed;
     double *x_out, *u_out, *cost;   // [K][(N+1)][12], [K][N][4], [K]; any may be null
     int *dom;                       // [K] DomainError flags or null
+    double *w_out;                  // [K][N][12] the disturbance w_k each step added, or null (rat_policy_worst_case_disturbance's replay)
 };
 void launch_noisy_rollout(const NoisyArgs &a, hipStream_t s);
 

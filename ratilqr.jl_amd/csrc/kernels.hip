@@ -3664,6 +3664,7 @@ __global__ __launch_bounds__(64) void noisy_rollout_kernel(NoisyArgs a) {
         double w = 0.0;                                               // w_k = chol_lower(W(k)) z_k
 #pragma unroll
         for (int q = 0; q < 12; ++q) w = fma(a.Wchol[(long)kw * 192 + jx * 16 + q], shz[row][q], w);
+        if (live && j < 12 && a.w_out) a.w_out[(k * N + t) * XSTR + j] = (j < n) ? w : 0.0;
         x = (j < n) ? xn + w : 0.0;
         WAVE_SYNC();
     }

@@ -142,6 +142,39 @@ void launch_wct_weights(const WtArgs &a, hipStream_t s);
 void launch_wct_chunk(const WtArgs &a, hipStream_t s);
 void launch_wct_final(const WtArgs &a, hipStream_t s);
 
+// ---- rat_policy_worst_case_disturbance: the mean and covariance of the disturbance w_t, and its covariance with (x_t, u_t) (policy_mc.hip) ----
+// The trajectory call's replay with the rollouts keeping w_t as well (staged [kc][N][ldw]).  Per step t < N and row, about the centres
+// c_w[t] and c_t: S0, S1w = sum y Dw, S1z = sum y Dz, S2ww = sum y Dw Dw', S2wz = sum y Dw Dz' and sum y^2, Dw = w_t - c_w[t] in lanes
+// 0 .. 11 of the tile, Dz = (x_t, u_t) - c_t as wct_moments has it.  wcd_moments keeps wct_moments' schedule (WT_SLOTS, WT_WAVES, WT_ROWS)
+// and issues one MFMA per product; wcd_final sums the slots in index order.  c_w[t] is the w_t of the first rollout of the first chunk
+// whose stored cost is not NaN (0 where that is not finite, or where the chunk has none): wcd_centre, behind the first chunk's rollouts.
+#define WD_PART 552           /* doubles per partial: S2ww [16][16] | S2wz [16][16] | S1w [16] | S1z [16] | S0 | sum y^2 | padding */
+#define WD_O_WZ 256
+#define WD_O_S1W 512
+#define WD_O_S1Z 528
+#define WD_O_S0 544
+#define WD_O_SY2 545
+#define WD_MAX_ROWSTEPS 1899  /* rows x N at most: the partials [rows][N][WT_SLOTS][WD_PART] stay below 64 MiB (56.5 MB: 32 rows, N = 50) */
+
+struct WdArgs {
+    WtArgs t;                 // the replay's fields as wct_weights fills them, and centre = c_t [N+1][16]; part, mean, cov, ess are not read
+    const double *ws;         // [kc][N][ldw] the staged disturbances of the chunk
+    int ldw;
+    int cross;                // S2wz and S1z are wanted
+    double *cw;               // [N][16] c_w, zero padded
+    double *part;             // [nrows][N][WT_SLOTS][WD_PART]
+    // wcd_final only
+    double *mean_w;           // [nrows][N][n]
+    double *cov_w;            // [nrows][N][n^2] column-major
+    double *cov_wz;           // [nrows][N][n (n+m)] column-major, or null
+    double *ess;              // [nrows][2]: S0 and sum y^2 of step 0
+};
+// c_w from the first chunk (a.t.kc, a.t.cost, a.ws): behind that chunk's rollouts, before its sums
+void launch_wcd_centre(const WdArgs &a, hipStream_t s);
+// one chunk, behind launch_wct_weights: the chunk's sums into the partials
+void launch_wcd_chunk(const WdArgs &a, hipStream_t s);
+void launch_wcd_final(const WdArgs &a, hipStream_t s);
+
 // ---- rat_policy_events: how often a policy violates quadratic constraints, under q and under every row's tilt (policy_mc.hip) ---------------
 // An event is g(t, z) = z' Q z + a' z + b of z = (x_t, u_t) in the 12 + 4 tile, watched over the steps t_lo .. t_hi.  Behind each replayed
 // chunk (after wct_weights) ev_eval forms, per rollout and event, the margin M = max g over the window, the first step tau with g > 0 and

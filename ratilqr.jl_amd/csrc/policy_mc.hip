@@ -840,6 +840,146 @@ __global__ __launch_bounds__(MC_THREADS) void wct_final(WtArgs a) {
     if (t == 0 && e == 0) { a.ess[2 * r] = s0; a.ess[2 * r + 1] = S[WT_O_SY2]; }
 }
 
+// ---- rat_policy_worst_case_disturbance: weighted moments of the replayed disturbances -----------------------------------------------------
+// wct_moments' schedule and lane layout with two tiles per lane: Dw = w_t - c_w[t] (lanes i < n; lanes 12 .. 15 stay zero) and
+// Dz = (x_t, u_t) - c_t.  Per group, step and row one MFMA A = y Dw, B = Dw for sum y Dw Dw', and with CROSS a second one with the same A
+// and B = Dz: C[i][j] = sum y Dw_i Dz_j, w's component the row.  S1w, S1z, S0 and sum y^2 ride along.  The same order: a wavefront's
+// groups in order, wavefronts and rollout lanes in index order through LDS, chunk after chunk in stream order, the slots in wcd_final.
+// c_w: the first rollout of the first chunk that has a cost is as good a guess of where w_t lies as any one draw -- within a few
+// standard deviations of the mean wherever the sampler puts that -- and it is known before the first sums, the same for every row.
+#define WD_SH (256 + 256 + 64 + 64 + 8)   /* LDS doubles per wavefront and row: ww | wz | S1w per lane | S1z per lane | S0 [4] | sum y^2 [4] */
+#define WD_NONE 0x7fffffff
+
+__global__ __launch_bounds__(MC_THREADS) void wcd_centre(WdArgs a) {
+    __shared__ int first;
+    if (threadIdx.x == 0) first = WD_NONE;
+    __syncthreads();
+    for (long q = threadIdx.x; q < a.t.kc; q += MC_THREADS)
+        if (!mc_nan(a.t.cost[q])) { atomicMin(&first, (int)q); break; }                  // (an integer minimum: no order in it)
+    __syncthreads();
+    const int q = first, N = a.t.N;
+    for (int e = threadIdx.x; e < N * 16; e += MC_THREADS) {
+        const int t = e >> 4, i = e & 15;
+        double v = 0.0;
+        if (q != WD_NONE && i < a.t.n) v = a.ws[((long)q * N + t) * a.ldw + i];
+        if (!(fabs(v) < __builtin_inf())) v = 0.0;                    // (a centre is only a centre: any finite value serves)
+        a.cw[e] = v;
+    }
+}
+
+template <bool CROSS>
+__global__ __launch_bounds__(WT_WAVES * 64) void wcd_moments(WdArgs a) {
+    __shared__ double sh[WT_WAVES][WD_SH];
+    const int slot = blockIdx.x, t = blockIdx.y, r0 = blockIdx.z * WT_ROWS;
+    const int nrows = a.t.nrows, N = a.t.N;
+    const int nr = (nrows - r0 < WT_ROWS) ? nrows - r0 : WT_ROWS;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
+    const bool isx = i < 12;
+    const bool compw = i < a.t.n;                                     // (padding lanes stay zero)
+    const bool compz = isx ? (i < a.t.n) : (i - 12 < a.t.m);          // (t < N throughout)
+    const double cw = a.cw[t * 16 + i], cz = a.t.centre[t * 16 + i];
+    wt_d4 aww[WT_ROWS], awz[WT_ROWS];
+    double s1w[WT_ROWS], s1z[WT_ROWS], s0[WT_ROWS], sy2[WT_ROWS];
+#pragma unroll
+    for (int r = 0; r < WT_ROWS; ++r) {
+        aww[r] = (wt_d4){0.0, 0.0, 0.0, 0.0}; awz[r] = (wt_d4){0.0, 0.0, 0.0, 0.0};
+        s1w[r] = 0.0; s1z[r] = 0.0; s0[r] = 0.0; sy2[r] = 0.0;
+    }
+    const long kc = a.t.kc, G = (kc + 3) >> 2;
+    for (long g = (long)slot * WT_WAVES + w; g < G; g += (long)WT_SLOTS * WT_WAVES) {      // (uniform over the wavefront)
+        const long q = 4 * g + kk;
+        const bool live = q < kc;                                     // (the K tail)
+        const double J = live ? a.t.cost[q] : 0.0;
+        const bool ok = live && !mc_nan(J);                           // selected, not multiplied: w and the trajectory may hold NaN
+        double Dw = 0.0, Dz = 0.0;
+        if (ok && compw) Dw = a.ws[(q * N + t) * a.ldw + i] - cw;
+        if (CROSS && ok && compz) Dz = (isx ? a.t.xs[(q * (N + 1) + t) * a.t.ldx + i] : a.t.us[(q * N + t) * a.t.ldu + (i - 12)]) - cz;
+#pragma unroll
+        for (int r = 0; r < WT_ROWS; ++r) {
+            if (r < nr) {                                             // (uniform over the workgroup)
+                const double y = ok ? a.t.y[(long)(r0 + r) * a.t.ldy + q] : 0.0;
+                const double yd = y * Dw;
+                aww[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd, Dw, aww[r], 0, 0, 0);
+                if (CROSS) {
+                    awz[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd, Dz, awz[r], 0, 0, 0);
+                    s1z[r] += y * Dz;
+                }
+                s1w[r] += yd; s0[r] += y; sy2[r] += y * y;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < WT_ROWS; ++r) {
+        if (r < nr) {
+            __syncthreads();                                          // (the previous row's sums are read)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {                       // C: row (lane >> 4) + 4 reg, column lane & 15
+                sh[w][(kk + 4 * reg) * 16 + i] = aww[r][reg];
+                if (CROSS) sh[w][256 + (kk + 4 * reg) * 16 + i] = awz[r][reg];
+            }
+            sh[w][512 + lane] = s1w[r];
+            if (CROSS) sh[w][576 + lane] = s1z[r];
+            if (i == 0) { sh[w][640 + kk] = s0[r]; sh[w][644 + kk] = sy2[r]; }
+            __syncthreads();
+            double *p = a.part + (((size_t)(r0 + r) * N + t) * WT_SLOTS + slot) * WD_PART;
+            const int e = threadIdx.x;
+            double v = 0.0;
+            for (int w2 = 0; w2 < WT_WAVES; ++w2) v += sh[w2][e];
+            p[e] += v;
+            if (CROSS) {
+                v = 0.0;
+                for (int w2 = 0; w2 < WT_WAVES; ++w2) v += sh[w2][256 + e];
+                p[WD_O_WZ + e] += v;
+            }
+            if (e < 16) {
+                v = 0.0;
+                for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][512 + k2 * 16 + e];
+                p[WD_O_S1W + e] += v;
+            } else if (e < 32) {
+                if (CROSS) {
+                    v = 0.0;
+                    for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][576 + k2 * 16 + (e - 16)];
+                    p[WD_O_S1Z + (e - 16)] += v;
+                }
+            } else if (e == 32 || e == 33) {
+                v = 0.0;
+                for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][(e == 32 ? 640 : 644) + k2];
+                p[(e == 32) ? WD_O_S0 : WD_O_SY2] += v;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void wcd_final(WdArgs a) {
+    __shared__ double S[WD_PART];
+    const int t = blockIdx.x, r = blockIdx.y, e = threadIdx.x, N = a.t.N, n = a.t.n, d = a.t.n + a.t.m;
+    const double *p = a.part + ((size_t)r * N + t) * WT_SLOTS * WD_PART;
+    for (int q = e; q < WD_PART; q += MC_THREADS) {
+        double v = 0.0;
+        for (int s = 0; s < WT_SLOTS; ++s) v += p[s * WD_PART + q];
+        S[q] = v;
+    }
+    __syncthreads();
+    const double st = a.t.wc[WC_O_INFO + 2 * r + 1], nan = __builtin_nan("");
+    const bool dead = (st == WC_ST_EMPTY || st == WC_ST_NONFINITE);
+    const double s0 = S[WD_O_S0];
+    const size_t o = (size_t)r * N + t;
+    if (e < n * n) {                                                  // column-major; the upper triangle of the tile serves both halves
+        const int ii = e % n, jj = e / n;
+        const int lo = ii < jj ? ii : jj, hi = ii < jj ? jj : ii;
+        const double mi = S[WD_O_S1W + ii] / s0, mj = S[WD_O_S1W + jj] / s0;
+        a.cov_w[o * n * n + e] = dead ? nan : S[lo * 16 + hi] / s0 - mi * mj;
+    }
+    if (a.cov_wz && e < n * d) {                                      // column-major [n][n+m]: w's component the row
+        const int ii = e % n, jj = e / n;
+        const int tj = (jj < n) ? jj : 12 + jj - n;
+        const double mi = S[WD_O_S1W + ii] / s0, mj = S[WD_O_S1Z + tj] / s0;
+        a.cov_wz[o * n * d + e] = dead ? nan : S[WD_O_WZ + ii * 16 + tj] / s0 - mi * mj;
+    }
+    if (e < n) a.mean_w[o * n + e] = dead ? nan : a.cw[t * 16 + e] + S[WD_O_S1W + e] / s0;
+    if (t == 0 && e == 0) { a.ess[2 * r] = s0; a.ess[2 * r + 1] = S[WD_O_SY2]; }
+}
+
 // ---- rat_policy_events: violation probabilities of quadratic events on the replayed trajectories ----------------------------------------
 // ev_eval: a wavefront takes sixteen rollouts as the columns of Z [16 components][16 rollouts] and walks the steps; lane (col = lane & 15,
 // kq = lane >> 4) holds Z[kq + 4 r][col], r = 0 .. 3 -- x components kq, kq + 4, kq + 8 and u component kq -- which is at once the B operand
@@ -1064,6 +1204,21 @@ void launch_wct_chunk(const WtArgs &a, hipStream_t s) {
 
 void launch_wct_final(const WtArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(wct_final, dim3((unsigned)(a.N + 1), (unsigned)a.nrows), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_wcd_centre(const WdArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(wcd_centre, dim3(1), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_wcd_chunk(const WdArgs &a, hipStream_t s) {
+    if (a.t.kc <= 0) return;
+    const dim3 grid(WT_SLOTS, (unsigned)a.t.N, (unsigned)((a.t.nrows + WT_ROWS - 1) / WT_ROWS));
+    if (a.cross) hipLaunchKernelGGL(wcd_moments<true>, grid, dim3(WT_WAVES * 64), 0, s, a);
+    else hipLaunchKernelGGL(wcd_moments<false>, grid, dim3(WT_WAVES * 64), 0, s, a);
+}
+
+void launch_wcd_final(const WdArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(wcd_final, dim3((unsigned)a.t.N, (unsigned)a.t.nrows), dim3(MC_THREADS), 0, s, a);
 }
 
 void launch_ev_chunk(const EvArgs &a, hipStream_t s) {

@@ -74,6 +74,7 @@ struct SrcUserNoisyArgs {
     double *u_out;            // [K][N][m] dense, or null
     const double *p;          // the model's parameters
     int *overdraw;            // set (plain store) when a step draws more than was declared: 1 normals, 2 uniforms
+    double *w_out;            // [K][N][n] dense: what rat_user_noise wrote at every step, or null (rat_policy_worst_case_disturbance's replay)
 };
 
 // rat_src_rare_rollout (source_rare.h): rat_src_user_noisy_rollout under a shifted proposal on rng.normal(), with the margin of one event

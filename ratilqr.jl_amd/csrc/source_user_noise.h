@@ -30,6 +30,7 @@ __device__ inline bool srcun_nan(double v) { return v != v; }
 // 512 registers and 396 B per lane -- every rng draw is a Philox block inlined at its call site).  The sampler runs
 // before f: with f first the 12 x 4 source spilled 1940 B per lane.  x_out / u_out (either may be null): dense [n x (N+1)] / [m x N] per rollout, rollout
 // slowest -- rat_rollout_noisy's layout -- written straight from the lane; a DomainError rollout writes what it computed and a NaN cost.
+// w_out (null but for rat_policy_worst_case_disturbance's replay): dense [n x N] per rollout, the w the sampler wrote, before it is added.
 extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcUserNoisyArgs a) {
     const int lane = threadIdx.x;
     const long j = (long)blockIdx.x * a.tpw + lane;
@@ -95,6 +96,10 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
 #pragma unroll
         for (int q = 0; q < RAT_N; ++q) w[q] = 0.0;
         rat_user_noise(t, x, u, rng, w, a.p);
+        if (a.w_out) {
+#pragma unroll
+            for (int q = 0; q < RAT_N; ++q) a.w_out[(j * N + t) * (long)RAT_N + q] = w[q];
+        }
         double xn[RAT_N];
         rat_user_f<double>(x, u, xn, a.p);
         bool outnan = srcun_nan(ct);

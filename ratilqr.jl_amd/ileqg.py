@@ -349,6 +349,34 @@ class Context:
             return r
         return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)))
 
+    def policy_worst_case_disturbance(self, kl_bounds=(), thetas=(), cross=True):
+        """What the adversary does to the noise (rat_policy_worst_case_disturbance): the mean and covariance of the disturbance w_t at every
+        step, and its covariance with the state and the control it acts on, under the worst-case distribution p* ~ exp(theta* J) q of each
+        KL radius -- and under the tilt of each given theta; theta = 0 is the nominal distribution q -- formed on the device by replaying
+        the last policy_evaluate / policy_evaluate_noise of this context like policy_worst_case_trajectory.  Returns {"bounds": part,
+        "thetas": part}; a part carries policy_worst_case's row keys and, with R rows, mean_w (R, N, n), cov_w (R, N, n, n) and, with
+        cross, cov_wx (R, N, n, n) and cov_wu (R, N, n, m): entry [i, j] is Cov(w_t[i], x_t[j]).  Population covariances.
+        cov_wx[r, t] @ pinv(policy_worst_case_trajectory's cov_x[r, t]) is the adversary's feedback gain at step t."""
+        d = nv.f64(np.atleast_1d(np.asarray(kl_bounds, dtype=np.float64))).ravel()
+        th = nv.f64(np.atleast_1d(np.asarray(thetas, dtype=np.float64))).ravel()
+        n, m, N, R = self.n, self.m, self.N, d.size + th.size
+        rows, mean, cov = np.zeros((R, nv.WC_NSTAT)), np.zeros((R, N, n)), np.zeros((R, N, n, n))
+        wz = np.zeros((R, N, n + m, n)) if cross else None
+        nv.check(nv.lib().rat_policy_worst_case_disturbance(self.h, nv.P(d) if d.size else None, C.c_int32(d.size), nv.P(th) if th.size else None,
+                                                            C.c_int32(th.size), nv.P(rows), nv.P(mean), nv.P(cov), nv.P(wz)))
+        cov = cov.transpose(0, 1, 3, 2)                               # (column-major blocks)
+        if cross:
+            wz = wz.transpose(0, 1, 3, 2)                             # [R, N, n, n+m]
+
+        def part(sl):
+            r = {k: rows[sl, i].copy() for i, k in enumerate(nv.WC_SLOTS)}
+            r["flag"] = r["flag"].astype(np.int64)
+            r.update(mean_w=mean[sl].copy(), cov_w=cov[sl].copy())
+            if cross:
+                r.update(cov_wx=wz[sl, :, :, :n].copy(), cov_wu=wz[sl, :, :, n:].copy())
+            return r
+        return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)))
+
     def policy_events(self, events, kl_bounds=(), thetas=(), want_steps=False, want_margins=False):
         """How often the policy violates safety events (rat_policy_events): per event (halfspace, ball, quadratic_event; 1 to 16) and per
         row -- the worst-case distribution of each KL radius, the tilt of each theta; theta = 0 is the nominal distribution -- the
