@@ -156,6 +156,28 @@ rat_rc rat_problem_set(rat_handle h, const rat_problem_desc *desc);
  * (the whole text is compiled when the problem is set, too).  The event reads p like f, c and h: rat_problem_set_params moves an
  * obstacle without a new evaluation, since the replay guard holds the replayed costs against the stored ones and an event parameter
  * moves no cost.  A source without RAT_USER_EVENT compiles and behaves exactly as before.
+ * Optionally, for a controller of the user's own in the Monte-Carlo analyses (a saturating or rate-limited actuator behind the affine
+ * law, or a baseline controller under the same noise and seeds), the source defines RAT_USER_POLICY and
+ *
+ *   __device__ void rat_user_policy(int k, const double *x, const double *u_prev, double *u, const double *p);
+ *
+ * called once per step k = 0 .. N-1 of every MONTE-CARLO ROLLOUT of the source: rat_policy_evaluate, rat_policy_evaluate_noise,
+ * rat_policy_rare_event_noise, rat_policy_rare_event_user, and through the replay of rat_policy_evaluate_noise's rollouts
+ * rat_policy_worst_case_trajectory, rat_policy_worst_case_disturbance, rat_policy_events and rat_policy_events_user.  The call comes
+ * after the library has formed u_k = l_k + L_k (x_k - xbar_k) (l_k open loop, L == NULL) and before anything reads u: the cost, the
+ * sampler, f, x_out / u_out / the replayed disturbances, the events.  x: 12 doubles, RAT_N of them live, the rest 0.  u: 4 doubles, RAT_M
+ * live, the rest 0; it ARRIVES HOLDING THE AFFINE LAW'S CONTROL and leaves holding the control that is applied -- an entry the function
+ * leaves alone stays affine.  u_prev: 4 doubles, the control applied at step k - 1, all zeros at k = 0 (rate limits, actuator lag).  p:
+ * the problem's parameters, so rat_problem_set_params moves a limit without recompiling (a replay of an evaluation made under other
+ * parameters is refused as ever: the replayed costs differ).  double only: no AD type reaches the hook.  A NaN in u[0 .. RAT_M) after the
+ * hook where x and the affine u had none is a DomainError of that rollout, as a NaN from f is: its cost is NaN, it is counted in
+ * N_DOMAIN, and dom is set by the rare-event calls.  u_out holds applied controls; rat_user_noise and rat_user_event receive the applied
+ * u; the centre (xbar_t, l_t) of the worst-case moment sums stays as it is (it is only a centring).
+ * The hook does NOT run in the solver: rat_ileqg_solve / rat_ileqg_solve_batch, their rollouts and linearisation, rat_rollout_open,
+ * rat_rollout_feedback and rat_integrate_cost see the affine law alone -- iLEQG remains the reference's algorithm, and the policy it
+ * returns is optimal for the unconstrained problem -- nor in PETS, nor for the LQ / power-law families.  A source without RAT_USER_POLICY
+ * compiles to what it compiled to before and behaves exactly as before; a source that defines the hook and leaves u alone returns the
+ * bits the same source without the hook returns.
  * Limits: n <= 12, m <= 4 (else RAT_ERR_UNSUPPORTED); batches run on the round-based path (rat_set_path FUSED / BLOCK return
  * RAT_ERR_UNSUPPORTED); rat_rollout_noisy and rat_multi are not available for source models: rat_policy_evaluate with cost_out is the way
  * to their Monte-Carlo costs, and rat_policy_evaluate_noise with x_out / u_out the way to Monte-Carlo trajectories (under the user's
@@ -178,6 +200,9 @@ rat_rc rat_user_noise_check(const char *source, int32_t n, int32_t m, int32_t no
 /* The same for the kernel of rat_policy_events_user: `source` must define RAT_USER_EVENT and rat_user_event (else RAT_ERR_ARG, and the
  * message says so); n_event outside 1 .. 16 is RAT_ERR_ARG. */
 rat_rc rat_user_event_check(const char *source, int32_t n, int32_t m, int32_t n_event);
+/* The same for rat_user_policy, in the rollout kernel of rat_policy_evaluate: `source` must define RAT_USER_POLICY and rat_user_policy
+ * (else RAT_ERR_ARG, and the message says so; a wrong signature is a compile error). */
+rat_rc rat_user_policy_check(const char *source, int32_t n, int32_t m);
 
 /* ---- the hot path ----------------------------------------------------------------------------- */
 

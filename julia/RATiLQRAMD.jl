@@ -533,6 +533,9 @@ end
 "user_event_check(source, n, m; n_event): compile the kernel of policy_events_user only (rat_user_event_check)"
 user_event_check(source::AbstractString, n::Integer, m::Integer; n_event::Integer=1) =
     check(ccall((:rat_user_event_check, LIB), Int32, (Cstring, Int32, Int32, Int32), source, n, m, n_event))
+"user_policy_check(source, n, m): compile the Monte-Carlo rollout kernel with the source's rat_user_policy only (rat_user_policy_check)"
+user_policy_check(source::AbstractString, n::Integer, m::Integer) =
+    check(ccall((:rat_user_policy_check, LIB), Int32, (Cstring, Int32, Int32), source, n, m))
 
 "kl_event_bound(p, d): the largest probability an event of probability p can have within KL radius d (rat_kl_event_bound; host only)"
 function kl_event_bound(p::Real, d::Real)
@@ -1483,7 +1486,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, rare_event_probability_user, rare_event_user_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, user_policy_check, rare_event_probability_user, rare_event_user_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

@@ -905,6 +905,17 @@ extern "C" rat_rc rat_user_noise_check(const char *source, int32_t n, int32_t m,
     return src_check("rat_user_noise_check", SRC_USER_NOISE, source, n, m, normals, uniforms);
 }
 
+// The rollout kernel of rat_policy_evaluate (the one Monte-Carlo kernel every source compiles as) behind a guard that refuses a text
+// without the hook.  The guard follows the user's text, so the compiler's line numbers stay the user's; the guarded text is a cache key of
+// its own, so a hookless source that rat_policy_evaluate has compiled already is not taken for one with the hook.
+extern "C" rat_rc rat_user_policy_check(const char *source, int32_t n, int32_t m) {
+    if (!source) return fail(RAT_ERR_ARG, "null");
+    const std::string text = std::string(source) +
+        "\n#ifndef RAT_USER_POLICY\n#error \"the source does not define RAT_USER_POLICY: the Monte-Carlo rollouts apply "
+        "'#define RAT_USER_POLICY' and rat_user_policy(k, x, u_prev, u, p)\"\n#endif\n";
+    return src_check("rat_user_policy_check", SRC_NOISY, text.c_str(), n, m);
+}
+
 extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32_t n, int32_t m, int32_t N, const double *W, int32_t W_tv,
                                          const double *params, int64_t n_params) {
     if (!h || !source || !W) return fail(RAT_ERR_ARG, "null");

@@ -109,11 +109,11 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
                              "\n#line 1 \"" + row.header + "\"\n#include \"" + row.header + "\"\n";
     const char *hdr[] = {k_embed_layout_h, k_embed_source_args_h, k_embed_rat_ad_h, k_embed_source_kernels_h, k_embed_rat_normal_h,
                          k_embed_rat_philox_h, k_embed_rat_rng_h, k_embed_source_pets_h, k_embed_source_noisy_h, k_embed_source_user_noise_h,
-                         k_embed_source_rare_h, k_embed_source_events_h};
+                         k_embed_source_rare_h, k_embed_source_events_h, k_embed_source_policy_h};
     const char *hdr_names[] = {"layout.h", "source_args.h", "rat_ad.h", "source_kernels.h", "rat_normal.h", "rat_philox.h", "rat_rng.h",
-                               "source_pets.h", "source_noisy.h", "source_user_noise.h", "source_rare.h", "source_events.h"};
+                               "source_pets.h", "source_noisy.h", "source_user_noise.h", "source_rare.h", "source_events.h", "source_policy.h"};
     hiprtcProgram prog = nullptr;
-    if (g_rtc.create(&prog, text.c_str(), "model.hip", 12, hdr, hdr_names) != HIPRTC_SUCCESS) {
+    if (g_rtc.create(&prog, text.c_str(), "model.hip", (int)(sizeof(hdr) / sizeof(hdr[0])), hdr, hdr_names) != HIPRTC_SUCCESS) {
         if (log) *log = "hiprtcCreateProgram failed";
         return done(RAT_ERR_ARG);
     }

@@ -6,6 +6,7 @@
 #include "rat_normal.h"
 #include "rat_philox.h"
 #include "source_args.h"
+#include "source_policy.h"
 
 #if !defined(RAT_N) || !defined(RAT_M)
 #error "RAT_N and RAT_M must be defined"
@@ -36,6 +37,9 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_noisy_rollout(SrcNoisyA
     for (int q = 0; q < RAT_N; ++q) znext[q] = 0.0;
     double cost = 0.0;
     int dom = 0;
+#ifdef RAT_USER_POLICY
+    double up[4] = {0.0, 0.0, 0.0, 0.0};                              // the control applied at step t - 1
+#endif
     for (int t = 0; t < N; ++t) {
         double u[4];
         if (a.L) {
@@ -58,6 +62,9 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_noisy_rollout(SrcNoisyA
 #pragma unroll
             for (int j = 0; j < 4; ++j) u[j] = a.l[(long)t * USTR + j];
         }
+#ifdef RAT_USER_POLICY
+        if (rat_src_policy(t, x, u, up, a.p)) dom = 1;                // the user's controller: u is the applied control from here on
+#endif
         bool inok = true;
 #pragma unroll
         for (int q = 0; q < RAT_N; ++q) inok = inok && !srcn_nan(x[q]);

@@ -22,6 +22,7 @@
 #pragma once
 #include "rat_rng.h"
 #include "source_args.h"
+#include "source_policy.h"
 
 #if !defined(RAT_N) || !defined(RAT_M)
 #error "RAT_N and RAT_M must be defined"
@@ -115,6 +116,9 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
     const double nan = __builtin_nan("");
     double M = nan;
     int dom = 0;
+#ifdef RAT_USER_POLICY
+    double up[4] = {0.0, 0.0, 0.0, 0.0};                              // the control applied at step t - 1
+#endif
 #ifndef RAT_RARE_USER_EVENT
     double *row = s_z + lane * SRCRE_LD;
 #endif
@@ -141,6 +145,9 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
 #pragma unroll
                 for (int i = 0; i < 4; ++i) u[i] = a.l[(long)t * USTR + i];
             }
+#ifdef RAT_USER_POLICY
+            if (rat_src_policy(t, x, u, up, a.p)) dom = 1;            // the user's controller: the margin, c, the sampler and f see the applied control
+#endif
         }
 #ifdef RAT_RARE_USER_EVENT
         if (live) {

@@ -6,6 +6,7 @@
 #pragma once
 #include "rat_rng.h"
 #include "source_args.h"
+#include "source_policy.h"
 
 #if !defined(RAT_N) || !defined(RAT_M)
 #error "RAT_N and RAT_M must be defined"
@@ -50,6 +51,9 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
     double *__restrict__ uo = a.u_out ? a.u_out + j * (long)N * RAT_M : nullptr;
     double cost = 0.0;
     int dom = 0;
+#ifdef RAT_USER_POLICY
+    double up[4] = {0.0, 0.0, 0.0, 0.0};                              // the control applied at step t - 1
+#endif
     for (int t = 0; t < N; ++t) {
         double u[4];
         if (a.L) {
@@ -72,6 +76,9 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
 #pragma unroll
             for (int i = 0; i < 4; ++i) u[i] = a.l[(long)t * USTR + i];
         }
+#ifdef RAT_USER_POLICY
+        if (rat_src_policy(t, x, u, up, a.p)) dom = 1;                // the user's controller: u_out, c, the sampler and f see the applied control
+#endif
         if (xo) {
 #pragma unroll
             for (int q = 0; q < RAT_N; ++q) xo[(long)t * RAT_N + q] = x[q];
