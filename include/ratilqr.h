@@ -178,6 +178,39 @@ rat_rc rat_problem_set(rat_handle h, const rat_problem_desc *desc);
  * returns is optimal for the unconstrained problem -- nor in PETS, nor for the LQ / power-law families.  A source without RAT_USER_POLICY
  * compiles to what it compiled to before and behaves exactly as before; a source that defines the hook and leaves u alone returns the
  * bits the same source without the hook returns.
+ * Optionally, for model parameters that are not known exactly (a mass, a friction coefficient, an obstacle's position to +-20 %), the source
+ * defines RAT_USER_PARAMS and
+ *
+ *   template <class R> __device__ void rat_user_params(R &rng, const double *p, double *q);
+ *
+ * which draws the parameters of ONE Monte-Carlo rollout.  p: the problem's n_params parameters, the nominal ones, as
+ * rat_problem_set_params left them.  q: RAT_N_PARAMS = n_params doubles; it ARRIVES HOLDING A COPY OF p and leaves holding this rollout's
+ * parameters -- an entry the function leaves alone stays nominal.  The hook is called once per rollout, in front of step 0; from then on q
+ * is what that rollout passes as p to rat_user_c, rat_user_f, rat_user_h, rat_user_noise, rat_user_policy and rat_user_event.  rng is a
+ * counted generator with rng.normal() / rng.uniform(), rat_rng's interface with bounds of its own, RAT_PARAM_NORMALS and
+ * RAT_PARAM_UNIFORMS: a draw beyond them returns NaN and is an overdraw (RAT_ERR_ARG naming the limits, checked once after the wait; the
+ * handle stays usable).  double only: no AD type reaches the hook.  A NaN in q[0 .. n_params) where p had none is a DomainError of that
+ * rollout: NaN cost, counted in RAT_MC_N_DOMAIN, dom set by the rare-event calls.
+ * The hook runs only where rat_policy_params_sampling has switched parameter sampling on for the handle (below; off is the default, and
+ * rat_problem_set_source switches it off again), and then in the kernels that carry a counted rng: rat_policy_evaluate_noise,
+ * rat_policy_rare_event_noise, rat_policy_rare_event_user, and through the replay of rat_policy_evaluate_noise's rollouts
+ * rat_policy_worst_case_trajectory, rat_policy_worst_case_disturbance, rat_policy_events and rat_policy_events_user -- the replays run
+ * the rollouts again under the same seed, so they form the same q; the kernel of rat_policy_events_user forms q once more from the
+ * rollout's index and the seed.  Changing the sampling state between an evaluation and its replay is caught by the replay guard like any
+ * other change: the replayed costs differ from the stored ones.  With sampling on, a source without the hook is RAT_ERR_ARG, and the
+ * message says so.  With sampling off every kernel is compiled without the hook, whether or not the source defines it: a source that
+ * defines RAT_USER_PARAMS returns the bits the same source without it returns, and a source without it compiles to what it compiled to
+ * before.  With sampling on, a hook that leaves q alone returns the sampling-off bits provided the user's expressions define their bits:
+ * a sum of two products may be fused around either product, and the compiler's choice can differ between p in scalar and q in vector
+ * registers (a few ulp; '#pragma clang fp contract(off)' in the functions that read p settles it).  NOT covered, all of them on the nominal p always: rat_policy_evaluate under N(0, W) (no counted rng), the solver, its rollouts
+ * and its linearisation, PETS, the LQ / power-law families, general sizes.  One GPU.
+ * Draw keying: a rollout's parameters depend neither on K nor on how a call is cut into launches.  Injected: the i-th parameter normal /
+ * uniform of rollout j is zpn[j * param_normals + i] / zpu[j * param_uniforms + i].  Generator: Philox4x32-10 with the call's seed as key and
+ * counter (g lo, g hi, 0xFFFFFFFF, i / 2) for normals, (g lo, g hi, 0xFFFFFFFF, 0x80000000 | i / 2) for uniforms, g the global rollout
+ * index; Box-Muller pairing and the 53-bit uniform as for the per-step draws, whose counters (step word t < N) stay bit for bit what they
+ * were.  The rare-event calls run every pass under the pass's seed, the final pass under the call's.  Their proposal shifts the per-step
+ * normals alone: parameter normals are NOT shifted and add nothing to logw, so an event that a parameter drives cannot be made likelier
+ * by these calls (as one driven by a uniform cannot).
  * Limits: n <= 12, m <= 4 (else RAT_ERR_UNSUPPORTED); batches run on the round-based path (rat_set_path FUSED / BLOCK return
  * RAT_ERR_UNSUPPORTED); rat_rollout_noisy and rat_multi are not available for source models: rat_policy_evaluate with cost_out is the way
  * to their Monte-Carlo costs, and rat_policy_evaluate_noise with x_out / u_out the way to Monte-Carlo trajectories (under the user's
@@ -203,6 +236,24 @@ rat_rc rat_user_event_check(const char *source, int32_t n, int32_t m, int32_t n_
 /* The same for rat_user_policy, in the rollout kernel of rat_policy_evaluate: `source` must define RAT_USER_POLICY and rat_user_policy
  * (else RAT_ERR_ARG, and the message says so; a wrong signature is a compile error). */
 rat_rc rat_user_policy_check(const char *source, int32_t n, int32_t m);
+/* Parameter sampling of the handle (rat_user_params above): param_normals / param_uniforms are the most rng.normal() / rng.uniform() calls
+ * of the hook.  zpn [param_normals x K_injected], zpu [param_uniforms x K_injected] (column-major: rollout slowest): injected draws, every
+ * declared stream (else RAT_ERR_ARG), copied by the call -- the library keeps no pointer into the caller's arrays -- and a later call with
+ * K > K_injected is RAT_ERR_ARG; both NULL: the device generator, keyed by each call's seed (K_injected is not read).  Counts (0, 0) with
+ * both streams NULL switch sampling OFF, the default.  Negative counts: RAT_ERR_ARG.  A problem that is not a source model:
+ * RAT_ERR_UNSUPPORTED.  n_params == 0: RAT_ERR_ARG; n_params > 32: RAT_ERR_UNSUPPORTED.  The kernels are compiled for the new state by the
+ * next call that needs them (another module per kind, cached like every other). */
+rat_rc rat_policy_params_sampling(rat_handle h, int32_t param_normals, int32_t param_uniforms, const double *zpn, const double *zpu,
+                                  int64_t K_injected);
+/* Compiles the rollout kernel of rat_policy_evaluate_noise with sampling on for gfx950, without a device: `source` must define
+ * RAT_USER_PARAMS and rat_user_params (else RAT_ERR_ARG, and the message says so); n_params outside 1 .. 32 and negative counts are refused
+ * as rat_policy_params_sampling refuses them. */
+rat_rc rat_user_params_check(const char *source, int32_t n, int32_t m, int32_t n_params, int32_t normals, int32_t uniforms,
+                             int32_t param_normals, int32_t param_uniforms);
+/* The hook alone: q of rollouts 0 .. K - 1 under `seed` (or under the handle's injected draws), q_out [n_params x K] column-major -- the
+ * parameters behind the cost_out of rat_policy_evaluate_noise with that seed, and behind the final pass of a rare-event call with it.
+ * Sampling must be on (else RAT_ERR_ARG). */
+rat_rc rat_policy_params_sample(rat_handle h, int64_t K, uint64_t seed, double *q_out);
 
 /* ---- the hot path ----------------------------------------------------------------------------- */
 

@@ -294,6 +294,44 @@ function set_params!(s::ILEQGSolver, problem::DeviceSourceProblem, params::Vecto
     check(ccall((:rat_problem_set_params, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64), h.ptr, params, length(params)))
     s
 end
+"""
+ParamSampling(param_normals, param_uniforms=0; zpn=nothing, zpu=nothing): model parameters drawn per rollout by the source's rat_user_params
+(include/ratilqr.h): the most rng.normal() / rng.uniform() calls of the hook, and injected streams zpn (param_normals, K), zpu
+(param_uniforms, K) -- every declared one -- or the device generator keyed by each call's seed.
+"""
+struct ParamSampling
+    param_normals::Int32
+    param_uniforms::Int32
+    zpn::Union{Nothing,Array{Float64}}
+    zpu::Union{Nothing,Array{Float64}}
+end
+ParamSampling(param_normals::Integer, param_uniforms::Integer=0; zpn=nothing, zpu=nothing) =
+    ParamSampling(Int32(param_normals), Int32(param_uniforms), zpn, zpu)
+"set_param_sampling!(s, problem, ps): switch per-rollout parameters on (a ParamSampling) or off (nothing) for the solver's handle (rat_policy_params_sampling)"
+function set_param_sampling!(s::ILEQGSolver, problem::DeviceSourceProblem, ps::Union{Nothing,ParamSampling})
+    h = bind!(s.h, problem)
+    if ps === nothing
+        check(ccall((:rat_policy_params_sampling, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int64), h.ptr, 0, 0, C_NULL, C_NULL, 0))
+        return s
+    end
+    K = ps.zpn !== nothing && ps.param_normals > 0 ? length(ps.zpn) ÷ ps.param_normals :
+        (ps.zpu !== nothing && ps.param_uniforms > 0 ? length(ps.zpu) ÷ ps.param_uniforms : 0)
+    check(ccall((:rat_policy_params_sampling, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int64), h.ptr, ps.param_normals,
+                ps.param_uniforms, ps.zpn === nothing ? C_NULL : ps.zpn, ps.zpu === nothing ? C_NULL : ps.zpu, K))
+    s
+end
+"sample_params(s, problem, K; seed): the parameters rat_user_params draws for rollouts 0 .. K-1, (n_params, K) (rat_policy_params_sample)"
+function sample_params(s::ILEQGSolver, problem::DeviceSourceProblem, K::Integer; seed::Integer=0)
+    h = bind!(s.h, problem)
+    q = Matrix{Float64}(undef, length(problem.params), K)
+    check(ccall((:rat_policy_params_sample, LIB), Int32, (Ptr{Cvoid}, Int64, UInt64, Ptr{Float64}), h.ptr, K, UInt64(seed), q))
+    q
+end
+"user_params_check(source, n, m, n_params; normals_per_step, uniforms_per_step, param_normals, param_uniforms): compile the rollout kernel with parameter sampling on only (rat_user_params_check)"
+user_params_check(source::AbstractString, n::Integer, m::Integer, n_params::Integer; normals_per_step::Integer=0, uniforms_per_step::Integer=0,
+                  param_normals::Integer=0, param_uniforms::Integer=0) =
+    check(ccall((:rat_user_params_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32, Int32, Int32, Int32), source, n, m, n_params,
+                normals_per_step, uniforms_per_step, param_normals, param_uniforms))
 "simulate_dynamics(problem, x_0, u_array) -- ileqg.jl:18-38"
 function simulate_dynamics(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_0::Vector{Float64}, u_array::Vector{Vector{Float64}})
     h = bind!(s.h, problem); n, m, N = dims(problem)
@@ -1486,7 +1524,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, user_policy_check, rare_event_probability_user, rare_event_user_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

@@ -100,6 +100,7 @@ EXPORTS = [
     "rat_policy_rare_event_noise", "rat_rare_event_noise_check",
     "rat_policy_events_user", "rat_user_event_check", "rat_policy_rare_event_user", "rat_rare_event_user_check",
     "rat_user_policy_check",
+    "rat_policy_params_sampling", "rat_user_params_check", "rat_policy_params_sample",
 ]
 MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 WC_SLOTS = ("theta", "kl", "bound", "bound_se", "tilt_mean", "tilt_var", "ess", "flag")      # RAT_WC_* slots of the header, in order
@@ -166,6 +167,9 @@ def lib():
                                                     _dp, C.c_int32, C.c_double, _dp, _dp, _dp, _dp, _dp]
         _lib.rat_rare_event_user_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
         _lib.rat_user_policy_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32]
+        _lib.rat_policy_params_sampling.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, C.c_int64]
+        _lib.rat_user_params_check.argtypes = [C.c_char_p] + [C.c_int32] * 7
+        _lib.rat_policy_params_sample.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, _dp]
     return _lib
 
 
@@ -235,6 +239,14 @@ def user_policy_check(source, n, m):
     """rat_user_policy_check: compile the Monte-Carlo rollout kernel with the source's rat_user_policy only (gfx950, no device needed);
     raises RatError with the compiler's log, or saying that the source does not define RAT_USER_POLICY."""
     check(lib().rat_user_policy_check(str(source).encode(), int(n), int(m)))
+
+
+def user_params_check(source, n, m, n_params, normals_per_step=0, uniforms_per_step=0, param_normals=0, param_uniforms=0):
+    """rat_user_params_check: compile the rollout kernel of rat_policy_evaluate_noise with parameter sampling on (gfx950, no device
+    needed); raises RatError with the compiler's log, saying that the source does not define RAT_USER_PARAMS, or naming the limit on
+    n_params (1 .. 32) or the counts."""
+    check(lib().rat_user_params_check(str(source).encode(), int(n), int(m), int(n_params), int(normals_per_step), int(uniforms_per_step),
+                                      int(param_normals), int(param_uniforms)))
 
 
 def rare_event_user_check(source, n, m, normals_per_step=1, uniforms_per_step=0, n_event=1):

@@ -41,7 +41,7 @@ void rat_set_error(const char *msg) { g_err = msg; }          // (multi.cpp repo
 
 struct EvRec { hipEvent_t a, b; int kind; int64_t ntraj; };
 // a lazily compiled source kernel of the handle and the shape its module was compiled for (fn == NULL: empty)
-struct SrcSlot { hipModule_t mod = nullptr; hipFunction_t fn = nullptr; int npn = 0, npu = 0, nev = 0; };
+struct SrcSlot { hipModule_t mod = nullptr; hipFunction_t fn = nullptr; int npn = 0, npu = 0, nev = 0, npar = 0, ppn = 0, ppu = 0; };
 
 struct rat_handle_s {
     int device = 0;
@@ -210,6 +210,12 @@ struct rat_handle_s {
     int64_t src_un_loads = 0;                                // switch src_un_loads (read only): SRC_USER_NOISE modules this handle compiled or fetched from the cache
     int *h_un_over = nullptr;                                // pinned: those kernels' overdraw flag (bit 0 normals, bit 1 uniforms; every such call ends with a host wait)
     double *d_mc_zu = nullptr; size_t cap_mc_zu = 0;         // injected uniforms of one chunk (the normals use d_mc_z)
+    // model parameters drawn per rollout (rat_policy_params_sampling; source_params.h): off for every handle until that call, and again
+    // when the source problem is set anew.  The kinds with param_draws are compiled for this state (src_kernel)
+    bool ps_on = false;
+    int ps_pn = 0, ps_pu = 0;                                // parameter normals / uniforms per rollout
+    int64_t ps_K = 0;                                        // rollouts the injected streams hold (0: the device generator)
+    double *d_ps_zn = nullptr, *d_ps_zu = nullptr;           // the library's copy of the injected streams, whole: [ps_K][ps_pn], [ps_K][ps_pu]
     double *d_mc_xo = nullptr; size_t cap_mc_xo = 0;         // [chunk][N+1][n] trajectory staging
     double *d_mc_uo = nullptr; size_t cap_mc_uo = 0;         // [chunk][N][m]
     // the worst-case trajectory moments (rat_policy_worst_case_trajectory, policy_mc.hip) replay the last evaluation: the scalars of that
@@ -430,7 +436,7 @@ extern "C" void rat_destroy(rat_handle h) {
     if (h->d_perr) (void)hipFree(h->d_perr);
     for (void *q : {(void *)h->d_mc_cost, (void *)h->d_mc_dom, (void *)h->d_mc_z, (void *)h->d_mc_in, (void *)h->d_mc_red}) if (q) (void)hipFree(q);
     src_drop_slots(h);
-    for (double *q : {h->d_mc_zu, h->d_mc_xo, h->d_mc_uo}) if (q) (void)hipFree(q);
+    for (double *q : {h->d_mc_zu, h->d_mc_xo, h->d_mc_uo, h->d_ps_zn, h->d_ps_zu}) if (q) (void)hipFree(q);
     for (double *q : {h->d_wc_red, h->d_wc_w, h->d_tr_red}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_wt_cost, (void *)h->d_wt_dom, (void *)h->d_wt_y, (void *)h->d_wt_part, (void *)h->d_wt_out}) if (q) (void)hipFree(q);
     for (double *q : {h->d_mc_wo, h->d_wd_part, h->d_wd_out}) if (q) (void)hipFree(q);
@@ -832,16 +838,31 @@ static rat_rc src_args_ok(const char *who, SrcKind kind, int n, int m, int npn, 
 }
 
 // the rat_*_check entry points: whether `source` would be accepted as `kind`, compiled for gfx950 without a device
-static rat_rc src_check(const char *who, SrcKind kind, const char *source, int n, int m, int npn = 0, int npu = 0, int nev = 0) {
+// (npar > 0: with parameter sampling on for npar parameters, ppn normals and ppu uniforms per rollout -- what params_args_ok accepted)
+static rat_rc src_check(const char *who, SrcKind kind, const char *source, int n, int m, int npn = 0, int npu = 0, int nev = 0, int npar = 0,
+                        int ppn = 0, int ppu = 0) {
     if (!source) return fail(RAT_ERR_ARG, "null");
     rat_rc rc = src_args_ok(who, kind, n, m, npn, npu, nev);
     if (rc) return rc;
     std::string log;
-    if ((rc = src_compile(kind, source, n, m, SrcShape{npn, npu, nev}, "gfx950", nullptr, &log))) return fail(rc, log);
+    if ((rc = src_compile(kind, source, n, m, SrcShape{npn, npu, nev, npar, ppn, ppu}, "gfx950", nullptr, &log))) return fail(rc, log);
     return RAT_OK;
 }
 
 extern "C" rat_rc rat_source_check(const char *source, int32_t n, int32_t m) { return src_check("rat_source_check", SRC_MODEL, source, n, m); }
+
+// Parameter sampling back to the default of every handle: off, the injected streams released (the caller has waited for the stream)
+static void params_sampling_off(rat_handle h) {
+    for (double **q : {&h->d_ps_zn, &h->d_ps_zu}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    h->ps_on = false; h->ps_pn = 0; h->ps_pu = 0; h->ps_K = 0;
+}
+// What the handle's sampling state asks of a call with K rollouts, and the streams its kernels read
+static rat_rc params_ready(rat_handle h, const std::string &F, int64_t K) {
+    if (h->ps_on && h->ps_K > 0 && K > h->ps_K)
+        return fail(RAT_ERR_ARG, F + "K = " + std::to_string(K) + " is above the " + std::to_string(h->ps_K) +
+                                 " rollouts the injected parameter draws hold (rat_policy_params_sampling, K_injected)");
+    return RAT_OK;
+}
 
 // A compiled module on the current device and its kernel `name` (and `name2`, where a module carries two); a module that lacks one is
 // unloaded again.  What a caller does with the module it replaces comes after, at the caller.
@@ -860,14 +881,19 @@ static rat_rc load_module_function(const std::shared_ptr<const std::vector<char>
 // The handle's kernel of a lazily compiled kind for `shape`: compiled (or fetched from the process-wide cache) and loaded when the slot is
 // empty or holds another shape.  A compile or load that is refused leaves the slot as it was; a module that is replaced is unloaded once
 // the stream has finished with it.
-static rat_rc src_kernel(rat_handle h, SrcKind kind, const SrcShape &shape, const char *who, hipFunction_t *fn) {
+// A kind that takes parameter draws is compiled for the handle's sampling state (rat_policy_params_sampling), which the caller's shape
+// need not name: switching sampling on, off or to other counts is another module, as other draw counts are.
+static rat_rc src_kernel(rat_handle h, SrcKind kind, SrcShape shape, const char *who, hipFunction_t *fn) {
     SrcSlot &s = h->src_slot[kind];
-    if (!s.fn || s.npn != shape.npn || s.npu != shape.npu || s.nev != shape.nev) {
+    const bool ps = src_kind(kind).param_draws && h->ps_on;
+    shape.npar = ps ? (int)h->src_np : 0; shape.ppn = ps ? h->ps_pn : 0; shape.ppu = ps ? h->ps_pu : 0;
+    if (!s.fn || s.npn != shape.npn || s.npu != shape.npu || s.nev != shape.nev || s.npar != shape.npar || s.ppn != shape.ppn ||
+        s.ppu != shape.ppu) {
         std::shared_ptr<const std::vector<char>> code;
         std::string log;
         rat_rc rc;
         if ((rc = src_compile(kind, h->src_text.c_str(), h->n, h->m, shape, h->src_arch_name, &code, &log))) return fail(rc, log);
-        SrcSlot fresh{nullptr, nullptr, shape.npn, shape.npu, shape.nev};
+        SrcSlot fresh{nullptr, nullptr, shape.npn, shape.npu, shape.nev, shape.npar, shape.ppn, shape.ppu};
         if ((rc = load_module_function(code, src_kind(kind).entry, who, &fresh.mod, &fresh.fn))) return rc;
         if (s.mod) {
             HIPCHK(hipStreamSynchronize(h->stream));
@@ -899,6 +925,13 @@ static rat_rc overdraw_flag(int **flag, const std::string &F, int **d_flag) {
 }
 static std::string overdraw_msg(const std::string &what, int npn, int npu) {
     return what + " (normals_per_step = " + std::to_string(npn) + ", uniforms_per_step = " + std::to_string(npu) + "): the overdrawn values were NaN";
+}
+// what a nonzero flag of a kernel with parameter draws says: bits 2 and 3 are rat_user_params' (source_params.h), bits 0 and 1 a step's
+static rat_rc overdraw_fail(rat_handle h, const std::string &F, int flag, int npn, int npu) {
+    if (flag & 12)
+        return fail(RAT_ERR_ARG, F + "rat_user_params drew more than was declared (param_normals = " + std::to_string(h->ps_pn) +
+                                 ", param_uniforms = " + std::to_string(h->ps_pu) + "): the overdrawn values were NaN");
+    return fail(RAT_ERR_ARG, overdraw_msg(F + "a step drew more than was declared", npn, npu));
 }
 
 extern "C" rat_rc rat_user_noise_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms) {
@@ -960,6 +993,7 @@ extern "C" rat_rc rat_problem_set_source(rat_handle h, const char *source, int32
     if (h->src_mod) (void)hipModuleUnload(h->src_mod);
     h->src_mod = mod; h->src_roll = fr; h->src_lin = fl;
     src_drop_slots(h);                                                   // (the previous problem's Monte-Carlo kernels)
+    params_sampling_off(h);                                              // (the hook and the parameter count belong to the problem)
     h->src_text = source; h->src_arch_name = src_arch(pr.gcnArchName);
     h->d_src_p = const_cast<double *>(dp); h->src_np = n_params;
     h->hW.assign(W, W + (size_t)(pb.W_tv ? N : 1) * n * n);
@@ -2053,6 +2087,7 @@ static rat_rc launch_user_noisy_chunk(rat_handle h, const PolicyDev &p, int64_t 
     a.xnom = p.x; a.l = p.l; a.L = p.L; a.zn = d_zn; a.zu = d_zu;
     a.K = (long)kc; a.j0 = (long)k0; a.N = h->N; a.tpw = h->src_mc_tpw; a.seed = seed; a.cost = cost;
     a.x_out = x_out; a.u_out = u_out; a.p = h->d_src_p; a.overdraw = d_over; a.w_out = w_out;
+    a.zpn = h->d_ps_zn; a.zpu = h->d_ps_zu;                           // (null unless sampling is on with injected draws)
     HIPCHK(launch_src(h->src_slot[SRC_USER_NOISE].fn, kc, a.tpw, h->stream, &a));
     return RAT_OK;
 }
@@ -2179,8 +2214,8 @@ static rat_rc policy_eval_finish(rat_handle h, const int *d_dom, const rat_handl
     HIPCHK(hipMemcpyAsync(out, h->d_mc_red + (MC_P1 + MC_P2) * MC_BLOCKS, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     if (cost_out) HIPCHK(hipMemcpyAsync(cost_out, h->d_mc_cost, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (rec.kind == 2 && *(volatile int *)h->h_un_over != 0)      // after the wait: a step that drew more than the caller declared
-        return fail(RAT_ERR_ARG, overdraw_msg("rat_policy_evaluate_noise: a step drew more than was declared", rec.npn, rec.npu));
+    if (rec.kind == 2 && *(volatile int *)h->h_un_over != 0)      // after the wait: a step, or rat_user_params, that drew more than was declared
+        return overdraw_fail(h, "rat_policy_evaluate_noise: ", *(volatile int *)h->h_un_over, rec.npn, rec.npu);
     h->mc_cost_K = K;
     h->mc_rec = rec;
     for (int i = 0; i < RAT_MC_NSTAT; ++i) stats[i] = out[i];
@@ -2265,6 +2300,7 @@ extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, c
     if ((zn || zu) && ((npn > 0 && !zn) || (npu > 0 && !zu)))
         return fail(RAT_ERR_ARG, "rat_policy_evaluate_noise: injected draws need every declared stream (normals_per_step = " + std::to_string(npn) +
                                  ", uniforms_per_step = " + std::to_string(npu) + ")");
+    if ((rc = params_ready(h, "rat_policy_evaluate_noise: ", K))) return rc;
     HIPCHK(hipSetDevice(h->device));
     // the first evaluation with these draw counts compiles the kernel (launch_user_noisy_chunk, which a replay calls too, takes it from the slot)
     hipFunction_t fn = nullptr;
@@ -2305,6 +2341,97 @@ extern "C" rat_rc rat_policy_evaluate_noise(rat_handle h, const double *x_nom, c
     rec.kind = 2; rec.injected = inject; rec.has_L = L != nullptr; rec.seed = seed; rec.K = K; rec.npn = npn; rec.npu = npu;
     rec.o_x = pk.o_x; rec.o_l = pk.o_l; rec.o_L = pk.o_L; rec.n = n; rec.m = m; rec.N = N; rec.model = h->pb.model; rec.W_tv = h->W_tv;
     return policy_eval_finish(h, nullptr, rec, theta, n_theta, stats, risk, risk_se, cost_out);
+}
+
+// ---- model parameters drawn per rollout (rat_user_params; include/ratilqr.h "Source models", csrc/source_params.h) ------------------------
+// what the numbers alone decide about sampling n_params parameters with ppn normals and ppu uniforms per rollout
+static rat_rc params_args_ok(const std::string &F, int64_t n_params, int ppn, int ppu) {
+    if (ppn < 0 || ppu < 0) return fail(RAT_ERR_ARG, F + "param_normals, param_uniforms must not be negative");
+    if (n_params < 1) return fail(RAT_ERR_ARG, F + "the problem has no parameters (n_params = 0): there is nothing to draw");
+    if (n_params > 32) return fail(RAT_ERR_UNSUPPORTED, F + "n_params = " + std::to_string(n_params) + " is above 32 (every rollout keeps its parameters in registers)");
+    return RAT_OK;
+}
+
+// The rollout kernel of rat_policy_evaluate_noise with sampling on, compiled for gfx950 without a device
+extern "C" rat_rc rat_user_params_check(const char *source, int32_t n, int32_t m, int32_t n_params, int32_t normals, int32_t uniforms,
+                                        int32_t param_normals, int32_t param_uniforms) {
+    if (!source) return fail(RAT_ERR_ARG, "null");
+    rat_rc rc;
+    if ((rc = params_args_ok("rat_user_params_check: ", n_params, param_normals, param_uniforms))) return rc;
+    return src_check("rat_user_params_check", SRC_USER_NOISE, source, n, m, normals, uniforms, 0, n_params, param_normals, param_uniforms);
+}
+
+// Handle state, not arguments: the entry points that roll out keep their signatures.  Counts (0, 0) with no stream switch sampling off.
+// Injected streams are copied to the device whole; the handle keeps no pointer into the caller's arrays.
+extern "C" rat_rc rat_policy_params_sampling(rat_handle h, int32_t param_normals, int32_t param_uniforms, const double *zpn, const double *zpu,
+                                             int64_t K_injected) {
+    const std::string F = "rat_policy_params_sampling: ";
+    if (!h) return fail(RAT_ERR_ARG, F + "null handle");
+    const int ppn = param_normals, ppu = param_uniforms;
+    HIPCHK(hipSetDevice(h->device));
+    if (ppn == 0 && ppu == 0 && !zpn && !zpu) {                       // off: the default of every handle
+        HIPCHK(hipStreamSynchronize(h->stream));
+        params_sampling_off(h);
+        return RAT_OK;
+    }
+    if (ppn < 0 || ppu < 0) return fail(RAT_ERR_ARG, F + "param_normals, param_uniforms must not be negative");
+    if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
+    if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
+        return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_params)");
+    rat_rc rc;
+    if ((rc = params_args_ok(F, h->src_np, ppn, ppu))) return rc;
+    const bool inject = zpn || zpu;
+    if (inject && ((ppn > 0 && !zpn) || (ppu > 0 && !zpu)))
+        return fail(RAT_ERR_ARG, F + "injected draws need every declared stream (param_normals = " + std::to_string(ppn) + ", param_uniforms = " +
+                                 std::to_string(ppu) + ")");
+    if (inject && (K_injected < 1 || K_injected > ((int64_t)1 << 27))) return fail(RAT_ERR_ARG, F + "K_injected must be in 1 .. 2^27");
+    // the new streams first: a refused allocation leaves the state as it was
+    double *d_zn = nullptr, *d_zu = nullptr;
+    auto undo = [&](rat_rc r) { if (d_zn) (void)hipFree(d_zn); if (d_zu) (void)hipFree(d_zu); return r; };
+    if (inject && ppn > 0) {
+        if (hipMalloc((void **)&d_zn, (size_t)K_injected * ppn * 8) != hipSuccess) return undo(fail(RAT_ERR_HIP, F + "hipMalloc failed"));
+        if (hipMemcpy(d_zn, zpn, (size_t)K_injected * ppn * 8, hipMemcpyHostToDevice) != hipSuccess) return undo(fail(RAT_ERR_HIP, F + "hipMemcpy failed"));
+    }
+    if (inject && ppu > 0) {
+        if (hipMalloc((void **)&d_zu, (size_t)K_injected * ppu * 8) != hipSuccess) return undo(fail(RAT_ERR_HIP, F + "hipMalloc failed"));
+        if (hipMemcpy(d_zu, zpu, (size_t)K_injected * ppu * 8, hipMemcpyHostToDevice) != hipSuccess) return undo(fail(RAT_ERR_HIP, F + "hipMemcpy failed"));
+    }
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return undo(fail(RAT_ERR_HIP, F + "hipStreamSynchronize failed"));
+    params_sampling_off(h);
+    h->ps_on = true; h->ps_pn = ppn; h->ps_pu = ppu; h->ps_K = inject ? K_injected : 0; h->d_ps_zn = d_zn; h->d_ps_zu = d_zu;
+    return RAT_OK;
+}
+
+// The hook alone: q of rollouts 0 .. K - 1 under `seed` (or the handle's injected draws), [n_params x K] column-major -- the parameters
+// behind the cost_out of an evaluation with that seed.  Chunks of 2^16 rollouts through the trajectory staging area.
+extern "C" rat_rc rat_policy_params_sample(rat_handle h, int64_t K, uint64_t seed, double *q_out) {
+    const std::string F = "rat_policy_params_sample: ";
+    if (!h || !q_out) return fail(RAT_ERR_ARG, F + "null handle / q_out");
+    if (K < 1 || K > ((int64_t)1 << 27)) return fail(RAT_ERR_ARG, F + "K must be in 1 .. 2^27");
+    if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
+    if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
+        return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_params)");
+    if (!h->ps_on) return fail(RAT_ERR_ARG, F + "parameter sampling is off: call rat_policy_params_sampling first");
+    rat_rc rc;
+    if ((rc = params_ready(h, F, K))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    hipFunction_t kernel = nullptr;
+    int *d_over = nullptr;
+    if ((rc = src_kernel(h, SRC_PARAMS, SrcShape(), "rat_policy_params_sample", &kernel))) return rc;
+    if ((rc = overdraw_flag(&h->h_un_over, F, &d_over))) return rc;
+    const int64_t chunk = mc_chunk(K), np = h->src_np;
+    if ((rc = grow(&h->d_mc_xo, &h->cap_mc_xo, (size_t)chunk * np))) return rc;
+    for (int64_t k0 = 0; k0 < K; k0 += chunk) {
+        const int64_t kc = std::min(chunk, K - k0);
+        SrcParamsArgs a;
+        a.p = h->d_src_p; a.zpn = h->d_ps_zn; a.zpu = h->d_ps_zu; a.seed = seed; a.K = (long)kc; a.j0 = (long)k0; a.q_out = h->d_mc_xo;
+        a.overdraw = d_over;
+        HIPCHK(launch_src(kernel, kc, 64, h->stream, &a));
+        HIPCHK(hipMemcpyAsync(q_out + (size_t)k0 * np, h->d_mc_xo, (size_t)kc * np * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));                      // (the next chunk writes the staging area; q_out is pageable)
+    }
+    const int flag = *(volatile int *)h->h_un_over;
+    return flag == 0 ? RAT_OK : overdraw_fail(h, F, flag, 0, 0);
 }
 
 // The worst-case expected cost sup { E_p[J] : KL(p || q) <= d } of the sample of K costs, by its one-dimensional dual, searched on the
@@ -2472,6 +2599,14 @@ static rat_rc replay_chunks(rat_handle h, const double *kl_bound, int32_t n_boun
     const int64_t K = rec.K, chunk = mc_chunk(K);
     const int ldx = source ? n : XSTR, ldu = source ? m : USTR;
     rat_rc rc;
+    if (source) {
+        // the rollout kernel for the handle's parameter-sampling state as it is NOW (the slot's, unless rat_policy_params_sampling was
+        // called behind the evaluation): where that state changed, the replayed costs differ from the stored ones and the guard
+        // (replay_mismatch) refuses the replay
+        hipFunction_t fn = nullptr;
+        if ((rc = params_ready(h, "the replay: ", K))) return rc;
+        if ((rc = src_kernel(h, SRC_USER_NOISE, SrcShape{rec.npn, rec.npu, 0}, "the replay", &fn))) return rc;
+    }
     size_t cap_red = h->d_wc_red ? WC_SCRATCH : 0;
     if ((rc = grow(&h->d_wc_red, &cap_red, (size_t)WC_SCRATCH))) return rc;
     if ((rc = grow(&h->d_mc_xo, &h->cap_mc_xo, (size_t)chunk * (N + 1) * ldx))) return rc;
@@ -2679,7 +2814,7 @@ extern "C" rat_rc rat_kl_event_bound(double p, double d, double *out) {
 static const size_t EV_O_A = (size_t)EV_MAX * 256, EV_O_B = EV_O_A + EV_MAX * 16, EV_O_WIN = EV_O_B + EV_MAX, EV_O_EV = EV_O_WIN + EV_MAX;
 
 static rat_rc events_run(rat_handle h, const std::string &F, int n_event, const std::vector<double> *in, bool quad,
-                         const std::function<rat_rc(const EvArgs &)> &eval, const double *kl_bound, int32_t n_bound, const double *theta,
+                         const std::function<rat_rc(const EvArgs &, int64_t)> &eval, const double *kl_bound, int32_t n_bound, const double *theta,
                          int32_t n_theta, double *rows_out, double *event_out, double *step_out, double *margin_out) {
     rat_rc rc;
     const rat_handle_s::McReplay rec = h->mc_rec;
@@ -2716,7 +2851,7 @@ static rat_rc events_run(rat_handle h, const std::string &F, int n_event, const 
                                 ea.xs = c.xs; ea.us = c.us; ea.ldx = c.ldx; ea.ldu = c.ldu; ea.n = c.n; ea.m = c.m; ea.N = c.N; ea.kc = c.kc; ea.cost = c.cost;
                                 ea.ldy = c.ldy; ea.nrows = c.nrows; ea.y = c.y; ea.wc = c.wc; ea.first = ch.k0 == 0;
                                 rat_rc rce;
-                                if ((rce = eval(ea))) return rce;
+                                if ((rce = eval(ea, ch.k0))) return rce;
                                 if (margin_out)                       // the chunk's margins, event by event, to their place among the K
                                     HIPCHK(hipMemcpy2DAsync(margin_out + ch.k0, (size_t)K * 8, h->d_ev_margin, (size_t)c.ldy * 8, (size_t)ch.kc * 8,
                                                             (size_t)n_event, hipMemcpyDeviceToHost, h->stream));
@@ -2780,7 +2915,7 @@ extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double 
         int32_t w[2] = {t_lo[e], t_hi[e]};
         memcpy(&in[EV_O_WIN + e], w, sizeof(w));
     }
-    return events_run(h, F, n_event, &in, Q != nullptr, [h](const EvArgs &ea) -> rat_rc { launch_ev_chunk(ea, h->stream); return RAT_OK; },
+    return events_run(h, F, n_event, &in, Q != nullptr, [h](const EvArgs &ea, int64_t) -> rat_rc { launch_ev_chunk(ea, h->stream); return RAT_OK; },
                       kl_bound, n_bound, theta, n_theta, rows_out, event_out, step_out, margin_out);
 }
 
@@ -2802,12 +2937,14 @@ extern "C" rat_rc rat_policy_events_user(rat_handle h, int32_t n_event, const do
     HIPCHK(hipSetDevice(h->device));
     hipFunction_t kernel = nullptr;
     if ((rc = src_kernel(h, SRC_EVENTS, SrcShape{0, 0, n_event}, "rat_policy_events_user", &kernel))) return rc;
+    const uint64_t seed = h->mc_rec.seed;                             // the replayed evaluation's: rat_src_user_events forms q from it again
     return events_run(h, F, n_event, nullptr, false,
-                      [h, kernel](const EvArgs &ea) -> rat_rc {
+                      [h, kernel, seed](const EvArgs &ea, int64_t k0) -> rat_rc {
                           if (ea.kc <= 0 || ea.nrows <= 0) return RAT_OK;
                           SrcEventArgs sa;
                           sa.xs = ea.xs; sa.us = ea.us; sa.ldx = ea.ldx; sa.ldu = ea.ldu; sa.N = ea.N; sa.kc = ea.kc; sa.cost = ea.cost;
                           sa.margin = ea.margin; sa.tau = ea.tau; sa.mask = ea.mask; sa.ldy = ea.ldy; sa.p = h->d_src_p;
+                          sa.zpn = h->d_ps_zn; sa.zpu = h->d_ps_zu; sa.seed = seed; sa.j0 = (long)k0;     // (read with sampling on alone)
                           HIPCHK(launch_src(kernel, ea.kc, 64, h->stream, &sa));
                           launch_ev_sums(ea, h->stream);
                           return RAT_OK;
@@ -2956,6 +3093,7 @@ static rat_rc rare_src_run(rat_handle h, const std::string &F, const char *who, 
     HIPCHK(hipSetDevice(h->device));
     hipFunction_t kernel = nullptr;
     int *d_over = nullptr;
+    if ((rc = params_ready(h, F, K))) return rc;
     if ((rc = src_kernel(h, n_event > 0 ? SRC_RARE_USER : SRC_RARE, SrcShape{npn, npu, n_event}, who, &kernel))) return rc;
     if ((rc = overdraw_flag(&h->h_un_over, F, &d_over))) return rc;
     ReKernels kn;
@@ -2966,12 +3104,13 @@ static rat_rc rare_src_run(rat_handle h, const std::string &F, const char *who, 
         sa.xnom = ra.xnom; sa.l = ra.l; sa.L = ra.L; sa.shift = ra.shift; sa.Qt = ra.Qt; sa.at = ra.at; sa.b = ra.b;
         sa.t_lo = ra.t_lo; sa.t_hi = ra.t_hi; sa.quad = quad ? 1 : 0; sa.K = ra.K; sa.N = h->N; sa.tpw = h->src_mc_tpw; sa.seed = ra.seed;
         sa.margin = ra.margin; sa.logw = ra.logw; sa.dom = ra.dom; sa.p = h->d_src_p; sa.overdraw = d_over;
+        sa.zpn = h->d_ps_zn; sa.zpu = h->d_ps_zu;
         HIPCHK(launch_src(kernel, ra.K, sa.tpw, h->stream, &sa));
         return RAT_OK;
     };
     kn.waited = [h, npn, npu, &F]() -> rat_rc {
-        if (*(volatile int *)h->h_un_over == 0) return RAT_OK;
-        return fail(RAT_ERR_ARG, overdraw_msg(F + "a step drew more than was declared", npn, npu));
+        const int flag = *(volatile int *)h->h_un_over;
+        return flag == 0 ? RAT_OK : overdraw_fail(h, F, flag, npn, npu);
     };
     return re_run(h, F, kn, x_nom, l, L, K, seed, Q, a, b, t_lo, t_hi, shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
 }

@@ -75,6 +75,8 @@ struct SrcUserNoisyArgs {
     const double *p;          // the model's parameters
     int *overdraw;            // set (plain store) when a step draws more than was declared: 1 normals, 2 uniforms
     double *w_out;            // [K][N][n] dense: what rat_user_noise wrote at every step, or null (rat_policy_worst_case_disturbance's replay)
+    const double *zpn, *zpu;  // RAT_USER_PARAMS_ON alone (source_params.h): the handle's injected parameter draws, whole ([K_injected][param
+                              // normals], [K_injected][param uniforms], indexed by j + j0), or both null (Philox keyed by seed).  Not read otherwise
 };
 
 // rat_src_rare_rollout (source_rare.h): rat_src_user_noisy_rollout under a shifted proposal on rng.normal(), with the margin of one event
@@ -100,6 +102,7 @@ struct SrcRareArgs {
     int *overdraw;            // set (plain store) when a step draws more than was declared: 1 normals, 2 uniforms
     int event;                // the RAT_RARE_USER_EVENT variant (rat_policy_rare_event_user): the entry of rat_user_event's g that is the
                               // margin's event; Qt, at, b, quad are not read there and the window is 0 .. N.  Not read otherwise
+    const double *zpn, *zpu;  // RAT_USER_PARAMS_ON alone: as SrcUserNoisyArgs' (the rollout index is global here: one launch per pass)
 };
 
 // rat_src_user_events (source_events.h): ev_eval (policy_mc.hip) for the user's rat_user_event on the staged trajectories of one replayed
@@ -115,4 +118,18 @@ struct SrcEventArgs {
     unsigned *mask;           // [N+1][ldy] bit i: g_i > 0 at that step, bit RAT_N_EVENT: any of them; or null (no per-step sums)
     long ldy;
     const double *p;          // the model's parameters
+    const double *zpn, *zpu;  // RAT_USER_PARAMS_ON alone: as SrcUserNoisyArgs', with the seed and the global index of the chunk's first rollout
+    unsigned long long seed;  // of the replayed evaluation, from which the kernel forms every rollout's parameters again
+    long j0;
+};
+
+// rat_src_params_sample (source_params.h): rat_user_params alone for rollouts 0 .. K - 1 (rat_policy_params_sample)
+struct SrcParamsArgs {
+    const double *p;          // the model's nominal parameters
+    const double *zpn, *zpu;  // the handle's injected parameter draws, or both null (Philox keyed by seed)
+    unsigned long long seed;
+    long K;                   // rollouts of this launch
+    long j0;                  // global index of this launch's first rollout
+    double *q_out;            // [K][RAT_N_PARAMS]
+    int *overdraw;            // set (plain store) when the hook draws more than was declared: 4 normals, 8 uniforms
 };

@@ -14,6 +14,7 @@
 // byte that comes from memory is used once, by the lane that fetched it.  The stores (margin, tau, mask) are coalesced over the lanes.
 #pragma once
 #include "source_args.h"
+#include "source_params.h"
 
 #if !defined(RAT_N) || !defined(RAT_M)
 #error "RAT_N and RAT_M must be defined"
@@ -39,6 +40,16 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_events(SrcEventArg
     const double *xq = a.xs + q * (N + 1) * a.ldx, *uq = a.us + q * N * a.ldu;
     double M[RAT_N_EVENT];
     int tau[RAT_N_EVENT];
+#ifdef RAT_USER_PARAMS_ON
+    // the rollout's parameters, formed again from its global index and the replayed evaluation's seed (or the stored injected draws): a
+    // handful of Philox blocks, no stored copy.  An overdraw or a NaN here was the rollout kernel's to report (the stored cost is NaN)
+    double qp[RAT_N_PARAMS];
+    int pover = 0;
+    if (ok) (void)rat_src_params(q + a.j0, a.seed, a.zpn, a.zpu, a.p, qp, pover);
+#define SRCEV_P qp
+#else
+#define SRCEV_P a.p
+#endif
 #pragma unroll
     for (int e = 0; e < RAT_N_EVENT; ++e) { M[e] = nan; tau[e] = -1; }
     for (int t = 0; t <= N; ++t) {
@@ -51,7 +62,7 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_events(SrcEventArg
             for (int i = 0; i < RAT_M; ++i) u[i] = (t < N) ? uq[(long)t * a.ldu + i] : 0.0;
 #pragma unroll
             for (int e = 0; e < 16; ++e) g[e] = nan;
-            rat_user_event(t, x, u, g, a.p);
+            rat_user_event(t, x, u, g, SRCEV_P);
 #pragma unroll
             for (int e = 0; e < RAT_N_EVENT; ++e) {
                 const double gv = g[e];

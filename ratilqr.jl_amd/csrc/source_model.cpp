@@ -31,8 +31,9 @@ struct Rtc {
 
 std::mutex g_mu;
 Rtc g_rtc;
-// key: (source, n, m, SrcKind, normals per step, uniforms per step, events of rat_user_event (0 where the kind takes none), architecture)
-std::map<std::tuple<std::string, int, int, int, int, int, int, std::string>, std::shared_ptr<const std::vector<char>>> g_cache;
+// key: (source, n, m, SrcKind, normals per step, uniforms per step, events of rat_user_event (0 where the kind takes none), parameters
+// drawn per rollout (0: sampling off) with their normals and uniforms, architecture)
+std::map<std::tuple<std::string, int, int, int, int, int, int, int, int, int, std::string>, std::shared_ptr<const std::vector<char>>> g_cache;
 
 bool rtc_load(std::string *why) {           // (g_mu held)
     if (!g_rtc.tried) {
@@ -69,15 +70,16 @@ std::string src_arch(const char *gcn_arch_name) {
     return out.empty() ? std::string("gfx950") : out;
 }
 
-// indexed by SrcKind:  header                 entry                         entry2               rng_shift draws events rare_user_event
+// indexed by SrcKind:  header                 entry                         entry2               rng_shift draws events rare_user_event param_draws
 static const SrcKindRow k_kinds[SRC_NKIND] = {
-    /* SRC_MODEL      */ {"source_kernels.h",    "rat_src_rollout",            "rat_src_linearize", false,    false, false, false},
-    /* SRC_PETS       */ {"source_pets.h",       "rat_src_pets_rollout",       nullptr,             false,    true,  false, false},
-    /* SRC_NOISY      */ {"source_noisy.h",      "rat_src_noisy_rollout",      nullptr,             false,    false, false, false},
-    /* SRC_USER_NOISE */ {"source_user_noise.h", "rat_src_user_noisy_rollout", nullptr,             false,    true,  false, false},
-    /* SRC_RARE       */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  false, false},
-    /* SRC_EVENTS     */ {"source_events.h",     "rat_src_user_events",        nullptr,             false,    false, true,  false},
-    /* SRC_RARE_USER  */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  true,  true},
+    /* SRC_MODEL      */ {"source_kernels.h",    "rat_src_rollout",            "rat_src_linearize", false,    false, false, false, false},
+    /* SRC_PETS       */ {"source_pets.h",       "rat_src_pets_rollout",       nullptr,             false,    true,  false, false, false},
+    /* SRC_NOISY      */ {"source_noisy.h",      "rat_src_noisy_rollout",      nullptr,             false,    false, false, false, false},
+    /* SRC_USER_NOISE */ {"source_user_noise.h", "rat_src_user_noisy_rollout", nullptr,             false,    true,  false, false, true},
+    /* SRC_RARE       */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  false, false, true},
+    /* SRC_EVENTS     */ {"source_events.h",     "rat_src_user_events",        nullptr,             false,    false, true,  false, true},
+    /* SRC_RARE_USER  */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  true,  true,  true},
+    /* SRC_PARAMS     */ {"source_params.h",     "rat_src_params_sample",      nullptr,             false,    false, false, false, true},
 };
 
 const SrcKindRow &src_kind(SrcKind kind) { return k_kinds[kind]; }
@@ -86,6 +88,7 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
                    std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
     const SrcKindRow &row = k_kinds[kind];
     const int npn = row.draws ? shape.npn : 0, npu = row.draws ? shape.npu : 0, nev = row.events ? shape.nev : 0;
+    const int npar = row.param_draws ? shape.npar : 0, ppn = npar > 0 ? shape.ppn : 0, ppu = npar > 0 ? shape.ppu : 0;
     const auto t0 = std::chrono::steady_clock::now();
     auto done = [&](rat_rc rc) {
         if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -93,7 +96,7 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
     };
     std::lock_guard<std::mutex> lk(g_mu);
     if (cached) *cached = false;
-    const auto key = std::make_tuple(std::string(source), n, m, (int)kind, npn, npu, nev, arch);
+    const auto key = std::make_tuple(std::string(source), n, m, (int)kind, npn, npu, nev, npar, ppn, ppu, arch);
     auto it = g_cache.find(key);
     if (it != g_cache.end()) {
         if (code) *code = it->second;
@@ -109,9 +112,10 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
                              "\n#line 1 \"" + row.header + "\"\n#include \"" + row.header + "\"\n";
     const char *hdr[] = {k_embed_layout_h, k_embed_source_args_h, k_embed_rat_ad_h, k_embed_source_kernels_h, k_embed_rat_normal_h,
                          k_embed_rat_philox_h, k_embed_rat_rng_h, k_embed_source_pets_h, k_embed_source_noisy_h, k_embed_source_user_noise_h,
-                         k_embed_source_rare_h, k_embed_source_events_h, k_embed_source_policy_h};
+                         k_embed_source_rare_h, k_embed_source_events_h, k_embed_source_policy_h, k_embed_source_params_h};
     const char *hdr_names[] = {"layout.h", "source_args.h", "rat_ad.h", "source_kernels.h", "rat_normal.h", "rat_philox.h", "rat_rng.h",
-                               "source_pets.h", "source_noisy.h", "source_user_noise.h", "source_rare.h", "source_events.h", "source_policy.h"};
+                               "source_pets.h", "source_noisy.h", "source_user_noise.h", "source_rare.h", "source_events.h", "source_policy.h",
+                               "source_params.h"};
     hiprtcProgram prog = nullptr;
     if (g_rtc.create(&prog, text.c_str(), "model.hip", (int)(sizeof(hdr) / sizeof(hdr[0])), hdr, hdr_names) != HIPRTC_SUCCESS) {
         if (log) *log = "hiprtcCreateProgram failed";
@@ -123,6 +127,13 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
     std::vector<const char *> opts = {"-O3", "-std=c++17", dn.c_str(), dm.c_str(), oa.c_str(), dpn.c_str(), dpu.c_str()};
     if (row.events) opts.push_back(dne.c_str());
     if (row.rare_user_event) opts.push_back("-DRAT_RARE_USER_EVENT=1");
+    const std::string dnp = "-DRAT_N_PARAMS=" + std::to_string(npar), dppn = "-DRAT_PARAM_NORMALS=" + std::to_string(ppn),
+                      dppu = "-DRAT_PARAM_UNIFORMS=" + std::to_string(ppu);
+    if (npar > 0) {                                                   // parameter sampling is on
+        opts.push_back("-DRAT_USER_PARAMS_ON=1");
+        opts.push_back(dnp.c_str()); opts.push_back(dppn.c_str()); opts.push_back(dppu.c_str());
+    }
+    if (kind == SRC_PARAMS) opts.push_back("-DRAT_PARAMS_SAMPLE_KERNEL=1");
     const hiprtcResult rc = g_rtc.compile(prog, (int)opts.size(), opts.data());
     size_t ls = 0;
     std::string lg;

@@ -17,11 +17,14 @@ enum SrcKind {
     SRC_RARE,            // that under a shifted proposal, with a quadratic event's margin (rat_policy_rare_event_noise)
     SRC_EVENTS,          // the user's rat_user_event on replayed trajectories (rat_policy_events_user)
     SRC_RARE_USER,       // SRC_RARE with entry `event` of rat_user_event for the margin (rat_policy_rare_event_user)
+    SRC_PARAMS,          // the user's rat_user_params alone (rat_policy_params_sample)
     SRC_NKIND
 };
 // One row per kind: what its translation unit is made of and what the module exports.  Every kind is the user's text behind
 // source_args.h, rat_ad.h and rat_rng.h, then `header` (under a #line of its own), compiled for `arch` with -O3 -std=c++17 -DRAT_N=n
-// -DRAT_M=m -DRAT_PETS_NORMALS=npn -DRAT_PETS_UNIFORMS=npu (0 where the kind takes no draws).
+// -DRAT_M=m -DRAT_PETS_NORMALS=npn -DRAT_PETS_UNIFORMS=npu (0 where the kind takes no draws).  A kind that takes parameter draws gets
+// -DRAT_USER_PARAMS_ON=1 -DRAT_N_PARAMS=npar -DRAT_PARAM_NORMALS=ppn -DRAT_PARAM_UNIFORMS=ppu as well when the shape has npar > 0
+// (parameter sampling is on, rat_policy_params_sampling); with npar == 0 its command line is what it was without the feature.
 struct SrcKindRow {
     const char *header;          // embedded header with the kind's kernels
     const char *entry, *entry2;  // kernels the module exports (entry2: NULL but for SRC_MODEL's linearisation)
@@ -29,9 +32,13 @@ struct SrcKindRow {
     bool draws;                  // takes npn, npu (a sampler's source must define RAT_USER_NOISE: the header refuses it otherwise)
     bool events;                 // takes nev: -DRAT_N_EVENT=nev (the source must define RAT_USER_EVENT)
     bool rare_user_event;        // -DRAT_RARE_USER_EVENT=1
+    bool param_draws;            // takes npar, ppn, ppu: the kernels that call rat_user_params once per rollout (source_params.h)
 };
 const SrcKindRow &src_kind(SrcKind kind);
-struct SrcShape { int npn = 0, npu = 0, nev = 0; };      // (fields a kind does not take are read as 0)
+struct SrcShape {                                        // (fields a kind does not take are read as 0)
+    int npn = 0, npu = 0, nev = 0;
+    int npar = 0, ppn = 0, ppu = 0;                      // parameter sampling: RAT_N_PARAMS (0: off), parameter normals / uniforms per rollout
+};
 
 // Compiles `source` as `kind`.  RAT_OK: *code holds the code object (shared with the cache, which keys on source, n, m, kind, shape and
 // arch).  RAT_ERR_ARG: *log holds the compiler's log.  RAT_ERR_UNSUPPORTED: hiprtc is not available in this process.  *ms (if not null):

@@ -1,0 +1,106 @@
+// source_params.h -- model parameters drawn per rollout (rat_user_params, include/ratilqr.h "Source models"), as the Monte-Carlo kernels of
+// source models apply them: rat_src_user_noisy_rollout (source_user_noise.h), both variants of rat_src_rare_rollout (source_rare.h) and
+// rat_src_user_events (source_events.h) include this header and call rat_src_params once per rollout, in front of step 0, then hand q to
+// the user's functions wherever they handed a.p.  rat_src_params_sample at the end is the kernel of rat_policy_params_sample (SRC_PARAMS):
+// the hook alone.  The solver's kernels (source_kernels.h), rat_src_noisy_rollout (source_noisy.h: no counted rng) and PETS (source_pets.h)
+// do not include it: they run on the nominal p.  Without RAT_USER_PARAMS_ON -- the state of every handle until
+// rat_policy_params_sampling switches sampling on -- the header is empty, whether or not the source defines the hook: the kernels
+// compile to what they compiled to before.  RAT_N_PARAMS, RAT_PARAM_NORMALS, RAT_PARAM_UNIFORMS come from the command line with
+// RAT_USER_PARAMS_ON.  The library embeds this header (Makefile: source_embed.inc).
+//
+// The i-th parameter normal / uniform of the rollout with GLOBAL index g (independent of K and of how a call is cut into launches):
+//   injected   zpn[g RAT_PARAM_NORMALS + i],  zpu[g RAT_PARAM_UNIFORMS + i]   (the handle's copy of the caller's streams, whole)
+//   generator  Philox4x32-10 (rat_philox.h), key (seed lo, seed hi):
+//                normals   counter (g lo, g hi, 0xFFFFFFFF, i / 2): u01(r0, r1), u01(r2, r3), Box-Muller -> normal 2q, normal 2q + 1
+//                uniforms  counter (g lo, g hi, 0xFFFFFFFF, 0x80000000 | i / 2): uniform 2q is u01(r0, r1), uniform 2q + 1 is u01(r2, r3)
+// rat_rng's pairing (rat_rng.h) under a step word no step uses, so the per-step draws keep their counters.  Never shifted: under
+// RAT_RNG_SHIFT the parameter normals come from N(0, 1) and add nothing to logw.
+#pragma once
+
+#ifdef RAT_USER_PARAMS_ON
+#include "rat_normal.h"
+#include "rat_philox.h"
+#include "source_args.h"
+
+#ifndef RAT_USER_PARAMS
+#error "the source does not define RAT_USER_PARAMS: parameter sampling is on (rat_policy_params_sampling) and needs '#define RAT_USER_PARAMS' and rat_user_params(rng, p, q)"
+#endif
+#if !defined(RAT_N_PARAMS) || RAT_N_PARAMS < 1 || RAT_N_PARAMS > 32
+#error "rat_user_params is compiled for 1 .. 32 parameters (RAT_N_PARAMS)"
+#endif
+#if !defined(RAT_PARAM_NORMALS) || !defined(RAT_PARAM_UNIFORMS)
+#error "RAT_PARAM_NORMALS and RAT_PARAM_UNIFORMS must be defined"
+#endif
+
+// rat_rng's interface (normal(), uniform()) with bounds of its own; a draw beyond them returns NaN and records the overdraw (bit 0
+// normals, bit 1 uniforms: the caller moves them to bits 2 and 3 of the kernel's flag)
+struct rat_param_rng {
+    const double *zn, *zu;        // injected: this rollout's slots; generator: null
+    bool gen;
+    unsigned g0, g1, k0, k1;      // generator: the rollout's counter words, key
+    int in, iu, over;
+    double spare_n, spare_u;      // the second output of the last generator block
+
+    __device__ __forceinline__ double normal() {
+        const int i = in++;
+        if (i >= RAT_PARAM_NORMALS) { over |= 1; return __builtin_nan(""); }
+        if (!gen) return zn[i];
+        if (i & 1) return spare_n;
+        unsigned r[4];
+        philox4x32_10(g0, g1, 0xFFFFFFFFu, (unsigned)(i >> 1), k0, k1, r);
+        double z0;
+        ratn_box_muller(u01(r[0], r[1]), u01(r[2], r[3]), &z0, &spare_n);
+        return z0;
+    }
+    __device__ __forceinline__ double uniform() {
+        const int i = iu++;
+        if (i >= RAT_PARAM_UNIFORMS) { over |= 2; return __builtin_nan(""); }
+        if (!gen) return zu[i];
+        if (i & 1) return spare_u;
+        unsigned r[4];
+        philox4x32_10(g0, g1, 0xFFFFFFFFu, 0x80000000u | (unsigned)(i >> 1), k0, k1, r);
+        spare_u = u01(r[2], r[3]);
+        return u01(r[0], r[1]);
+    }
+};
+
+// The rollout's parameters.  q arrives as anything and leaves holding what rat_user_params made of a copy of p[0 .. RAT_N_PARAMS) for the
+// rollout with global index g; zpn, zpu: the handle's injected streams (whole, indexed by g) or both null: the generator under `seed`.
+// over: the hook's overdraw bits are OR-ed in at bits 2 (normals) and 3 (uniforms).  Returns true where q holds a NaN although p had
+// none: the rollout's DomainError (the caller sets dom).  A hook that leaves q alone changes no bit.
+__device__ __forceinline__ bool rat_src_params(long g, unsigned long long seed, const double *zpn, const double *zpu, const double *p,
+                                               double (&q)[RAT_N_PARAMS], int &over) {
+    rat_param_rng rng;
+    rng.gen = (zpn == nullptr && zpu == nullptr);
+    rng.zn = (rng.gen || RAT_PARAM_NORMALS == 0) ? nullptr : zpn + g * (long)RAT_PARAM_NORMALS;
+    rng.zu = (rng.gen || RAT_PARAM_UNIFORMS == 0) ? nullptr : zpu + g * (long)RAT_PARAM_UNIFORMS;
+    rng.g0 = (unsigned)g; rng.g1 = (unsigned)(g >> 32);
+    rng.k0 = (unsigned)seed; rng.k1 = (unsigned)(seed >> 32);
+    rng.in = 0; rng.iu = 0; rng.over = 0; rng.spare_n = 0.0; rng.spare_u = 0.0;
+    bool inok = true;
+#pragma unroll
+    for (int i = 0; i < RAT_N_PARAMS; ++i) { q[i] = p[i]; inok = inok && !(q[i] != q[i]); }
+    rat_user_params(rng, p, q);
+    bool outnan = false;
+#pragma unroll
+    for (int i = 0; i < RAT_N_PARAMS; ++i) outnan = outnan || (q[i] != q[i]);
+    over |= rng.over << 2;
+    return inok && outnan;
+}
+
+#ifdef RAT_PARAMS_SAMPLE_KERNEL
+// rat_policy_params_sample: the hook alone for rollouts j0 .. j0 + K - 1, one lane each; q_out [K][RAT_N_PARAMS], rollout slowest
+extern "C" __global__ __launch_bounds__(64) void rat_src_params_sample(SrcParamsArgs a) {
+    const long j = (long)blockIdx.x * 64 + threadIdx.x;
+    if (j >= a.K) return;
+    double q[RAT_N_PARAMS];
+    int over = 0;
+    (void)rat_src_params(j + a.j0, a.seed, a.zpn, a.zpu, a.p, q, over);
+#pragma unroll
+    for (int i = 0; i < RAT_N_PARAMS; ++i) a.q_out[j * (long)RAT_N_PARAMS + i] = q[i];
+    if (over) *a.overdraw = over;
+}
+#endif
+#elif defined(RAT_PARAMS_SAMPLE_KERNEL)
+#error "rat_policy_params_sample is compiled with parameter sampling on"
+#endif

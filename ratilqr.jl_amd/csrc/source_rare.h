@@ -23,6 +23,7 @@
 #include "rat_rng.h"
 #include "source_args.h"
 #include "source_policy.h"
+#include "source_params.h"
 
 #if !defined(RAT_N) || !defined(RAT_M)
 #error "RAT_N and RAT_M must be defined"
@@ -88,6 +89,13 @@ __device__ __forceinline__ double srcre_g(const double (&zv)[4], const double *s
 __device__ inline bool srcre_nan(double v) { return v != v; }
 #endif
 
+// what the rollout hands the user's functions as p: the rollout's own parameters (source_params.h) or the problem's
+#ifdef RAT_USER_PARAMS_ON
+#define SRCRE_P q
+#else
+#define SRCRE_P a.p
+#endif
+
 extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArgs a) {
     const int lane = threadIdx.x;
     const long j = (long)blockIdx.x * a.tpw + lane;
@@ -116,6 +124,12 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
     const double nan = __builtin_nan("");
     double M = nan;
     int dom = 0;
+#ifdef RAT_USER_PARAMS_ON
+    // this rollout's parameters, drawn once in front of step 0 from N(0, 1) / U[0, 1): never shifted, nothing added to logw (a lane without
+    // a rollout calls none of the user's functions and holds nothing here)
+    double q[RAT_N_PARAMS];
+    if (live && rat_src_params(j, a.seed, a.zpn, a.zpu, a.p, q, rng.over)) dom = 1;
+#endif
 #ifdef RAT_USER_POLICY
     double up[4] = {0.0, 0.0, 0.0, 0.0};                              // the control applied at step t - 1
 #endif
@@ -146,7 +160,7 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
                 for (int i = 0; i < 4; ++i) u[i] = a.l[(long)t * USTR + i];
             }
 #ifdef RAT_USER_POLICY
-            if (rat_src_policy(t, x, u, up, a.p)) dom = 1;            // the user's controller: the margin, c, the sampler and f see the applied control
+            if (rat_src_policy(t, x, u, up, SRCRE_P)) dom = 1;            // the user's controller: the margin, c, the sampler and f see the applied control
 #endif
         }
 #ifdef RAT_RARE_USER_EVENT
@@ -154,7 +168,7 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
             double g[16];
 #pragma unroll
             for (int e = 0; e < 16; ++e) g[e] = nan;
-            rat_user_event(t, x, u, g, a.p);                          // (x has 12 entries, RAT_N of them live; u is 0 at t == N)
+            rat_user_event(t, x, u, g, SRCRE_P);                          // (x has 12 entries, RAT_N of them live; u is 0 at t == N)
             double gv = nan;
 #pragma unroll
             for (int e = 0; e < RAT_N_EVENT; ++e) gv = (e == a.event) ? g[e] : gv;
@@ -186,15 +200,15 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
             for (int q = 0; q < RAT_N; ++q) inok = inok && !srcre_nan(x[q]);
 #pragma unroll
             for (int q = 0; q < RAT_M; ++q) inok = inok && !srcre_nan(u[q]);
-            const double ct = rat_user_c<double>(t, x, u, a.p);       // (for the DomainError rule alone)
+            const double ct = rat_user_c<double>(t, x, u, SRCRE_P);       // (for the DomainError rule alone)
             rng.t = (unsigned)t; rng.in = 0; rng.iu = 0;
             rng.shift = a.shift + t * 12;
             double w[RAT_N];
 #pragma unroll
             for (int q = 0; q < RAT_N; ++q) w[q] = 0.0;
-            rat_user_noise(t, x, u, rng, w, a.p);
+            rat_user_noise(t, x, u, rng, w, SRCRE_P);
             double xn[RAT_N];
-            rat_user_f<double>(x, u, xn, a.p);
+            rat_user_f<double>(x, u, xn, SRCRE_P);
             bool outnan = srcre_nan(ct);
 #pragma unroll
             for (int q = 0; q < RAT_N; ++q) outnan = outnan || srcre_nan(xn[q]) || srcre_nan(w[q]);
@@ -207,7 +221,7 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
     bool inok = true;
 #pragma unroll
     for (int q = 0; q < RAT_N; ++q) inok = inok && !srcre_nan(x[q]);
-    const double hc = rat_user_h<double>(x, a.p);
+    const double hc = rat_user_h<double>(x, SRCRE_P);
     if (inok && srcre_nan(hc)) dom = 1;
     a.margin[j] = dom ? nan : M;
     a.logw[j] = rng.logw;

@@ -7,6 +7,7 @@
 #include "rat_rng.h"
 #include "source_args.h"
 #include "source_policy.h"
+#include "source_params.h"
 
 #if !defined(RAT_N) || !defined(RAT_M)
 #error "RAT_N and RAT_M must be defined"
@@ -19,6 +20,13 @@
 #endif
 
 __device__ inline bool srcun_nan(double v) { return v != v; }
+
+// what the rollout hands the user's functions as p: the rollout's own parameters (source_params.h) or the problem's
+#ifdef RAT_USER_PARAMS_ON
+#define SRCUN_P q
+#else
+#define SRCUN_P a.p
+#endif
 
 // ---- noisy rollout under the user's sampler: one lane per Monte-Carlo rollout, the state in registers ----------------------------------
 // rat_src_noisy_rollout (source_noisy.h) with w_t = rat_user_noise(t, x_t, u_t, rng) in place of chol_lower(W(t)) z_t: the same feedback
@@ -51,6 +59,10 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
     double *__restrict__ uo = a.u_out ? a.u_out + j * (long)N * RAT_M : nullptr;
     double cost = 0.0;
     int dom = 0;
+#ifdef RAT_USER_PARAMS_ON
+    double q[RAT_N_PARAMS];                                           // this rollout's parameters, drawn once in front of step 0
+    if (rat_src_params(g, a.seed, a.zpn, a.zpu, a.p, q, rng.over)) dom = 1;
+#endif
 #ifdef RAT_USER_POLICY
     double up[4] = {0.0, 0.0, 0.0, 0.0};                              // the control applied at step t - 1
 #endif
@@ -77,7 +89,7 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
             for (int i = 0; i < 4; ++i) u[i] = a.l[(long)t * USTR + i];
         }
 #ifdef RAT_USER_POLICY
-        if (rat_src_policy(t, x, u, up, a.p)) dom = 1;                // the user's controller: u_out, c, the sampler and f see the applied control
+        if (rat_src_policy(t, x, u, up, SRCUN_P)) dom = 1;                // the user's controller: u_out, c, the sampler and f see the applied control
 #endif
         if (xo) {
 #pragma unroll
@@ -92,7 +104,7 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
         for (int q = 0; q < RAT_N; ++q) inok = inok && !srcun_nan(x[q]);
 #pragma unroll
         for (int q = 0; q < RAT_M; ++q) inok = inok && !srcun_nan(u[q]);
-        const double ct = rat_user_c<double>(t, x, u, a.p);           // integrate_cost: c(t, x_t, u_t) in order   (ileqg.jl:118-121)
+        const double ct = rat_user_c<double>(t, x, u, SRCUN_P);           // integrate_cost: c(t, x_t, u_t) in order   (ileqg.jl:118-121)
         cost += ct;
         rng.t = (unsigned)t; rng.in = 0; rng.iu = 0;
         if (!rng.gen) {
@@ -102,13 +114,13 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
         double w[RAT_N];
 #pragma unroll
         for (int q = 0; q < RAT_N; ++q) w[q] = 0.0;
-        rat_user_noise(t, x, u, rng, w, a.p);
+        rat_user_noise(t, x, u, rng, w, SRCUN_P);
         if (a.w_out) {
 #pragma unroll
             for (int q = 0; q < RAT_N; ++q) a.w_out[(j * N + t) * (long)RAT_N + q] = w[q];
         }
         double xn[RAT_N];
-        rat_user_f<double>(x, u, xn, a.p);
+        rat_user_f<double>(x, u, xn, SRCUN_P);
         bool outnan = srcun_nan(ct);
 #pragma unroll
         for (int q = 0; q < RAT_N; ++q) outnan = outnan || srcun_nan(xn[q]) || srcun_nan(w[q]);
@@ -123,7 +135,7 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
     bool inok = true;
 #pragma unroll
     for (int q = 0; q < RAT_N; ++q) inok = inok && !srcun_nan(x[q]);
-    const double hc = rat_user_h<double>(x, a.p);                     // ... then h(x_N)   (ileqg.jl:122)
+    const double hc = rat_user_h<double>(x, SRCUN_P);                     // ... then h(x_N)   (ileqg.jl:122)
     if (inok && srcun_nan(hc)) dom = 1;
     cost += hc;
     a.cost[j] = dom ? __builtin_nan("") : cost;

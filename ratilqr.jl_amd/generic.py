@@ -211,6 +211,12 @@ class GenericContext(il.Context):
     def policy_rare_event_user(self, *a, **k):
         self._carrier_only("policy_rare_event_user")
 
+    def set_param_sampling(self, *a, **k):
+        self._carrier_only("set_param_sampling")
+
+    def sample_params(self, *a, **k):
+        self._carrier_only("sample_params")
+
     def solve_batch(self, *a, **k):
         self._carrier_only("solve_batch")
 

@@ -36,6 +36,18 @@ class UserNoise:
         self.seed = int(seed)
 
 
+class ParamSampling:
+    """Model parameters drawn per rollout (Context.set_param_sampling, rat_policy_params_sampling): what the source's rat_user_params
+    draws for one rollout (param_normals, param_uniforms: the most rng.normal() / rng.uniform() calls of the hook) and where the draws
+    come from -- injected streams zpn (K, param_normals) and zpu (K, param_uniforms), every declared one, rollout j reading row j
+    whatever K a later call has (no more than the streams hold), or the device generator keyed by each call's seed."""
+
+    def __init__(self, param_normals, param_uniforms=0, zpn=None, zpu=None):
+        self.param_normals, self.param_uniforms = int(param_normals), int(param_uniforms)
+        self.zpn = None if zpn is None else nv.f64(zpn)
+        self.zpu = None if zpu is None else nv.f64(zpu)
+
+
 class Event:
     """A safety event of Context.policy_events: g(t, z) = z' Q z + a' z + b of z = (x_t, u_t), violated where g > 0 at a step of the window.
     Build one with halfspace, ball or quadratic_event.  Q (or None: linear) and a are given over (x, u) -- n + m entries -- or over x
@@ -177,6 +189,34 @@ class Context:
         p = nv.f64(np.atleast_1d(params))
         nv.check(nv.lib().rat_problem_set_params(self.h, nv.P(p) if p.size else None, C.c_int64(p.size)))
         self.params = p.copy()
+
+    def set_param_sampling(self, ps):
+        """Switch per-rollout model parameters on (a ParamSampling) or off (None, the default) for this handle
+        (rat_policy_params_sampling): with sampling on, policy_evaluate_noise, the rare-event calls under user noise and the replays
+        behind policy_evaluate_noise call the source's rat_user_params once per rollout.  Injected streams are copied by the call."""
+        if ps is None:
+            nv.check(nv.lib().rat_policy_params_sampling(self.h, C.c_int32(0), C.c_int32(0), None, None, C.c_int64(0)))
+            return
+        if not isinstance(ps, ParamSampling):
+            raise TypeError("set_param_sampling needs a ParamSampling or None")
+        pn, pu, K = ps.param_normals, ps.param_uniforms, 0
+        for z, per, name in ((ps.zpn, pn, "zpn"), (ps.zpu, pu, "zpu")):
+            if z is not None and per > 0:
+                if z.size % per:
+                    raise ValueError(f"{name} holds {z.size} draws: no multiple of {per}")
+                if K and z.size // per != K:
+                    raise ValueError("zpn and zpu hold different numbers of rollouts")
+                K = z.size // per
+        nv.check(nv.lib().rat_policy_params_sampling(self.h, C.c_int32(pn), C.c_int32(pu), nv.P(ps.zpn), nv.P(ps.zpu), C.c_int64(K)))
+
+    def sample_params(self, K, seed=0):
+        """The parameters rat_user_params draws for rollouts 0 .. K - 1 under `seed` (or the injected draws): (K, n_params), row j behind
+        costs[j] of policy_evaluate_noise with that seed (rat_policy_params_sample)."""
+        K = int(K)
+        np_ = getattr(self, "params", np.zeros(0)).size
+        q = np.zeros((max(K, 0), np_))
+        nv.check(nv.lib().rat_policy_params_sample(self.h, C.c_int64(K), C.c_uint64(int(seed)), nv.P(q)))
+        return q
 
     # ---- operator forms --------------------------------------------------------------------------
     def rollout_open(self, x0, u):
