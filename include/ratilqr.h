@@ -428,6 +428,32 @@ rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *kl_bound, in
  * 552 doubles in 8 slots per row and step against 64 MiB): RAT_ERR_UNSUPPORTED. */
 rat_rc rat_policy_worst_case_disturbance(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
                                          double *rows_out, double *mean_w_out, double *cov_w_out, double *cov_wz_out);
+/* What the adversary picks among the uncertain parameters: the mean and covariance of the parameters q that rat_user_params drew for the
+ * rollouts (P = n_params, 1 .. 32), and their covariance with the rollout's cost J, under the nominal distribution (a theta = 0 row) and
+ * under p* ~ exp(theta* J) q of each kl_bound (and the tilt of each given theta).  The call takes no policy and no noise: it REPLAYS the
+ * last rat_policy_evaluate_noise exactly as rat_policy_worst_case_trajectory does -- the same chunks and seeds, the same bit-for-bit check
+ * against the stored costs -- and behind each chunk forms the chunk's q again from the rollout index and the evaluation's seed (the kernel
+ * of rat_policy_params_sample; the handle's injected parameter streams are served too) into a staging buffer of the handle.  Per row it
+ * sums S0, sum y^2, S1 = sum y Dq, S2 = sum y Dq Dq' (f64 MFMAs: one 16 x 16 block for P <= 16, the blocks (0,0), (0,1), (1,1) above) and,
+ * when cov_qJ_out is given, sum y DJ, sum y DJ^2 and sum y DJ Dq, of Dq = q - c_q, DJ = J - c_J.  c_q and c_J are the q and the cost of
+ * the first rollout whose stored cost is not NaN among the first min(K, 65536) (0 where that is not finite, or where there is none).
+ * Fixed summation order, no floating-point atomics: the same call returns the same bits, and a row's bits do not depend on the other rows.
+ *   kl_bound, theta   as rat_policy_worst_case's (the same refusals)
+ *   rows_out   [(n_bound + n_theta)][RAT_WC_NSTAT]: rat_policy_worst_case's rows of the same arguments, bit for bit (bounds, then thetas)
+ *   mean_q_out [(n_bound + n_theta)][P]: E q
+ *   cov_q_out  [(n_bound + n_theta)][P^2] column-major, the population form sum y (q - mean)(q - mean)' / sum y; exactly symmetric
+ *   cov_qJ_out [(n_bound + n_theta)][P], or NULL (the cost sums are then not formed): Cov(q_i, J) under the row's distribution, which is
+ *              dE_theta[q_i] / dtheta at the row's tilt.  cov_qJ[i]^2 / (cov_q[i,i] RAT_WC_TILT_VAR) is the linear share of Var J that
+ *              parameter i explains.
+ * A RAT_WC_SATURATED row holds the moments of the rollouts that attain Jmax; RAT_WC_EMPTY and RAT_WC_NONFINITE rows are NaN.  A
+ * DomainError rollout carries no weight (it is selected out: its q may hold NaN).
+ * Refused, the handle staying usable: parameter sampling off on the handle: RAT_ERR_ARG (call rat_policy_params_sampling, then evaluate);
+ * a problem that is not a source model, general sizes: RAT_ERR_UNSUPPORTED; no evaluation, or costs uploaded since: RAT_ERR_ARG; an
+ * evaluation under N(0, W) or on injected noise draws: RAT_ERR_UNSUPPORTED; parameters, policy or sampling state changed since the
+ * evaluation: RAT_ERR_ARG (the replay guard).  No cap on the rows of its own: the partial sums are 840 doubles in 8 slots per row, 1.7 MB
+ * at the 32 rows the arguments allow, against the siblings' 64 MiB. */
+rat_rc rat_policy_worst_case_params(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                    double *rows_out, double *mean_q_out, double *cov_q_out, double *cov_qJ_out);
 /* The tail risk of a policy, from the K Monte-Carlo costs: per level alpha the alpha-quantile of the cost (value at risk: with probability
  * alpha the cost stays below it) and the conditional value at risk, the expected cost of the worst (1 - alpha) share of the rollouts.  With
  * n = N_OK and s_1 <= ... <= s_n the OK costs in ascending order: a = n alpha (one rounded product), k = clamp(ceil(a), 1, n), VAR = s_k (bit

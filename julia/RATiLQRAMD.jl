@@ -521,6 +521,37 @@ function policy_worst_case_disturbance(s::ILEQGSolver; kl_bounds=Float64[], thet
 end
 
 """
+policy_worst_case_params(s, problem; kl_bounds, thetas, cost): what the adversary picks among the uncertain parameters
+(rat_policy_worst_case_params).  The mean and covariance of the parameters q that the source's rat_user_params drew for the rollouts, and
+their covariance with the rollout's cost, under the worst-case distribution p* ∝ exp(θ* J) q of each KL radius and under the tilt of each
+given θ (θ = 0 is the nominal distribution), formed on the device by replaying the last evaluate_policy under user noise on this solver's
+handle (parameter sampling on: set_param_sampling!) like policy_worst_case_trajectory.  Returns (bounds, thetas): each a named tuple of
+policy_worst_case's row vectors and, with R rows and P = length(problem.params), mean_q (P, R), cov_q (P, P, R) (population form, exactly
+symmetric) and, with cost, cov_qJ (P, R) -- dE[q]/dθ at the row's tilt -- and the derived explained_share (P, R):
+cov_qJ[i]^2 / (cov_q[i, i] tilt_var), the linear share of Var J that parameter i explains (`nothing` without cost).
+"""
+function policy_worst_case_params(s::ILEQGSolver, problem::DeviceSourceProblem; kl_bounds=Float64[], thetas=Float64[], cost::Bool=true)
+    h = bind!(s.h, problem)
+    P = length(problem.params)
+    d = collect(Float64, kl_bounds); th = collect(Float64, thetas)
+    nb = length(d); nt = length(th); R = nb + nt
+    rows = zeros(8, R); mean = zeros(P, R); cov = zeros(P, P, R)
+    qJ = cost ? zeros(P, R) : nothing
+    check(ccall((:rat_policy_worst_case_params, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, nb > 0 ? d : C_NULL, nb, nt > 0 ? th : C_NULL, nt, rows, mean, cov, cost ? qJ : C_NULL))
+    function share(r)
+        cost || return nothing
+        v = [qJ[i, k]^2 / (cov[i, i, k] * rows[6, k]) for i in 1:P, k in r]
+        map(x -> isfinite(x) ? x : NaN, v)
+    end
+    part(r) = (theta=rows[1, r], kl=rows[2, r], bound=rows[3, r], bound_se=rows[4, r], tilt_mean=rows[5, r], tilt_var=rows[6, r],
+               ess=rows[7, r], flag=Int.(rows[8, r]), mean_q=mean[:, r], cov_q=cov[:, :, r], cov_qJ=cost ? qJ[:, r] : nothing,
+               explained_share=share(r))
+    (bounds=part(1:nb), thetas=part(nb+1:R))
+end
+
+"""
 policy_events(s, Q, a, b, t_lo, t_hi; kl_bounds, thetas, want_steps, want_margins): how often the policy violates safety events
 (rat_policy_events).  Event i is z' Q[:, :, i] z + a[:, i]' z + b[i] > 0 at a step t_lo[i] ≤ t ≤ t_hi[i] (0-based steps, z = (x_t, u_t));
 Q === nothing: every event is linear.  Per row (the worst-case distribution of each KL radius, the tilt of each θ; θ = 0 is the nominal
@@ -1524,7 +1555,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

@@ -18,6 +18,7 @@ from .ileqg import (  # noqa: F401,E402
     Context,
     UserNoise,
     ParamSampling,
+    explained_share,
     Event,
     halfspace,
     ball,

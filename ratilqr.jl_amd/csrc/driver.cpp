@@ -239,6 +239,11 @@ struct rat_handle_s {
     double *d_mc_wo = nullptr; size_t cap_mc_wo = 0;         // [chunk][N][n] disturbance staging (the leading dimension of d_mc_xo)
     double *d_wd_part = nullptr; size_t cap_wd_part = 0;     // [rows][N][WT_SLOTS][WD_PART] partials
     double *d_wd_out = nullptr; size_t cap_wd_out = 0;       // c [N+1][16] | c_w [N][16] | mean_w | cov_w | cov_wz | S0, sum y^2 per row | mismatch count
+    // the worst-case parameter moments (rat_policy_worst_case_params, policy_mc.hip) ride on the same replay, with the SRC_PARAMS kernel
+    // forming each chunk's q again; only that call allocates these
+    double *d_wp_q = nullptr; size_t cap_wp_q = 0;           // [chunk][n_params] parameter staging
+    double *d_wp_part = nullptr; size_t cap_wp_part = 0;     // [rows][WT_SLOTS][WP_PART] partials
+    double *d_wp_out = nullptr; size_t cap_wp_out = 0;       // c_q [32], c_J | mean_q | cov_q | cov_qJ | S0, sum y^2, mean J, var J per row | mismatch count
     // the safety events (rat_policy_events, policy_mc.hip) ride on the same replay; grown on demand
     double *d_ev_out = nullptr; size_t cap_ev_out = 0;       // Q [16][256] | a [16][16] | b [16] | windows | event_out | step_out | mismatch count
     double *d_ev_part = nullptr; size_t cap_ev_part = 0;     // [row batches][steps + events][EV_SLOTS][EV_PART] partials
@@ -440,6 +445,7 @@ extern "C" void rat_destroy(rat_handle h) {
     for (double *q : {h->d_wc_red, h->d_wc_w, h->d_tr_red}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_wt_cost, (void *)h->d_wt_dom, (void *)h->d_wt_y, (void *)h->d_wt_part, (void *)h->d_wt_out}) if (q) (void)hipFree(q);
     for (double *q : {h->d_mc_wo, h->d_wd_part, h->d_wd_out}) if (q) (void)hipFree(q);
+    for (double *q : {h->d_wp_q, h->d_wp_part, h->d_wp_out}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_ev_out, (void *)h->d_ev_part, (void *)h->d_ev_margin, (void *)h->d_ev_tau, (void *)h->d_ev_mask}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_re_in, (void *)h->d_re_margin, (void *)h->d_re_logw, (void *)h->d_re_dom, (void *)h->d_re_part, (void *)h->d_re_red}) if (q) (void)hipFree(q);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
@@ -2771,6 +2777,76 @@ extern "C" rat_rc rat_policy_worst_case_disturbance(rat_handle h, const double *
     // the rows' effective sample size against the moment kernel's own, as rat_policy_worst_case_trajectory holds it
     for (int r = 0; r < nrows; ++r) {
         const double e_row = rows[r * WC_NSTAT + RAT_WC_ESS], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
+        if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
+            return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
+                                     " is not the row's " + std::to_string(e_row));
+    }
+    for (int i = 0; i < nrows * WC_NSTAT; ++i) rows_out[i] = rows[i];
+    return RAT_OK;
+}
+
+// What the adversary picks among the model's uncertain parameters: the mean and covariance of the rollouts' drawn parameters q
+// (rat_user_params) and their covariance with the cost, under q's own distribution and under p* ~ exp(theta* J) q, one row per kl_bound /
+// theta.  The trajectory call's replay; behind each chunk the SRC_PARAMS kernel forms the chunk's q again from the rollout index and the
+// evaluation's seed (or the handle's injected streams) into d_wp_q, then wcp_moments; one enqueue chain, one host wait.
+extern "C" rat_rc rat_policy_worst_case_params(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                               double *rows_out, double *mean_q_out, double *cov_q_out, double *cov_qJ_out) {
+    const std::string F = "rat_policy_worst_case_params: ";
+    rat_rc rc;
+    if (!h) return fail(RAT_ERR_ARG, F + "null handle");
+    if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
+    if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
+        return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_params)");
+    if (!h->ps_on)
+        return fail(RAT_ERR_ARG, F + "parameter sampling is off: call rat_policy_params_sampling, then rat_policy_evaluate_noise, first");
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && mean_q_out && cov_q_out))) return rc;
+    const rat_handle_s::McReplay rec = h->mc_rec;
+    const int nrows = n_bound + n_theta, P = (int)h->src_np;          // (1 .. 32: rat_policy_params_sampling accepted it)
+    HIPCHK(hipSetDevice(h->device));
+    hipFunction_t kq = nullptr;
+    int *d_over = nullptr;
+    if ((rc = src_kernel(h, SRC_PARAMS, SrcShape(), "rat_policy_worst_case_params", &kq))) return rc;
+    if ((rc = overdraw_flag(&h->h_un_over, F, &d_over))) return rc;
+    const int64_t K = rec.K, chunk = mc_chunk(K);
+    const bool cross = cov_qJ_out != nullptr;
+    const size_t o_mean = WP_NCENTRE, o_cov = o_mean + (size_t)nrows * P, o_qJ = o_cov + (size_t)nrows * P * P,
+                 o_ess = o_qJ + (cross ? (size_t)nrows * P : 0), o_cnt = o_ess + 4 * (size_t)nrows, n_out = o_cnt + 1,
+                 n_part = (size_t)nrows * WT_SLOTS * WP_PART;
+    if ((rc = grow(&h->d_wp_part, &h->cap_wp_part, n_part))) return rc;
+    if ((rc = grow(&h->d_wp_out, &h->cap_wp_out, n_out))) return rc;
+    if ((rc = grow(&h->d_wp_q, &h->cap_wp_q, (size_t)chunk * P))) return rc;
+    HIPCHK(hipMemsetAsync(h->d_wp_part, 0, n_part * 8, h->stream));
+    WpArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.qs = h->d_wp_q; pa.P = P; pa.cross = cross ? 1 : 0; pa.centre = h->d_wp_out; pa.part = h->d_wp_part;
+    pa.mean_q = h->d_wp_out + o_mean; pa.cov_q = h->d_wp_out + o_cov; pa.cov_qJ = cross ? h->d_wp_out + o_qJ : nullptr;
+    pa.ess = h->d_wp_out + o_ess;
+    if ((rc = replay_chunks(h, kl_bound, n_bound, theta, n_theta, reinterpret_cast<int *>(h->d_wp_out + o_cnt), pa.t,
+                            [&](const WtArgs &, ReplayChunk c) -> rat_rc {
+                                SrcParamsArgs sa;                     // the q the chunk's rollouts used: the same index, seed and streams
+                                sa.p = h->d_src_p; sa.zpn = h->d_ps_zn; sa.zpu = h->d_ps_zu; sa.seed = rec.seed; sa.K = (long)c.kc;
+                                sa.j0 = (long)c.k0; sa.q_out = h->d_wp_q; sa.overdraw = d_over;
+                                HIPCHK(launch_src(kq, c.kc, 64, h->stream, &sa));
+                                if (c.k0 == 0) launch_wcp_centre(pa, h->stream);   // c_q, c_J: fixed before the first chunk's sums
+                                launch_wcp_chunk(pa, h->stream);
+                                return RAT_OK;
+                            })))
+        return rc;
+    launch_wcp_final(pa, h->stream);
+    HIPCHK(hipGetLastError());
+    double rows[WC_MAX_ROWS * WC_NSTAT], ess[WC_MAX_ROWS * 4];
+    int bad = 0;
+    HIPCHK(hipMemcpyAsync(rows, h->d_wc_red + WC_O_ROWS, (size_t)nrows * WC_NSTAT * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(ess, h->d_wp_out + o_ess, (size_t)nrows * 32, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&bad, h->d_wp_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(mean_q_out, h->d_wp_out + o_mean, (size_t)nrows * P * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(cov_q_out, h->d_wp_out + o_cov, (size_t)nrows * P * P * 8, hipMemcpyDeviceToHost, h->stream));
+    if (cross) HIPCHK(hipMemcpyAsync(cov_qJ_out, h->d_wp_out + o_qJ, (size_t)nrows * P * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = replay_mismatch(F, bad, K))) return rc;
+    // the rows' effective sample size against the moment kernel's own, as rat_policy_worst_case_trajectory holds it
+    for (int r = 0; r < nrows; ++r) {
+        const double e_row = rows[r * WC_NSTAT + RAT_WC_ESS], e_mom = ess[4 * r] * ess[4 * r] / ess[4 * r + 1];
         if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
             return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
                                      " is not the row's " + std::to_string(e_row));

@@ -175,6 +175,43 @@ void launch_wcd_centre(const WdArgs &a, hipStream_t s);
 void launch_wcd_chunk(const WdArgs &a, hipStream_t s);
 void launch_wcd_final(const WdArgs &a, hipStream_t s);
 
+// ---- rat_policy_worst_case_params: the mean and covariance of the rollouts' drawn parameters q, and their covariance with the cost ---------
+// The trajectory call's replay; behind each chunk the SRC_PARAMS kernel forms the chunk's q again (staged [kc][P], P = n_params <= 32) and
+// wcp_moments adds, per row and about the centres c_q and c_J: S0, sum y^2, S1 = sum y Dq, S2 = sum y Dq Dq' and, with the cost sums,
+// sum y DJ, sum y DJ^2 and sum y DJ Dq; Dq = q - c_q in two tiles of sixteen lanes, DJ = J - c_J.  wcp_moments keeps wct_moments' schedule
+// (WT_SLOTS, WT_WAVES, WT_ROWS) with one step: one MFMA per group and row for P <= 16, three -- the blocks (0,0), (0,1), (1,1) of S2 --
+// above; wcp_final sums the slots in index order and mirrors block (1,0).  c_q and c_J are the q and the cost of the first rollout of the
+// first chunk whose stored cost is not NaN (0 where that is not finite, or where the chunk has none): wcp_centre, behind the first
+// chunk's q, as wcd_centre.  The partials [rows <= 32][WT_SLOTS][WP_PART] are 1.7 MB at most: no cap on the rows beyond WC_MAX_ROWS.
+#define WP_MAXP 32            /* parameters at most (source_params.h) */
+#define WP_PART 840           /* doubles per partial: S2 blocks (0,0) | (0,1) | (1,1), [16][16] each | S1 [32] | SJq [32] | S0 | sum y^2 | SJ | SJ2 | padding */
+#define WP_O_S1 768
+#define WP_O_SJQ 800
+#define WP_O_S0 832
+#define WP_O_SY2 833
+#define WP_O_SJ 834
+#define WP_O_SJ2 835
+#define WP_NCENTRE 40         /* doubles of the centre: c_q [32] | c_J | padding */
+
+struct WpArgs {
+    WtArgs t;                 // the replay's fields as wct_weights fills them (kc, cost, y, ldy, nrows, wc); the trajectory fields are not read
+    const double *qs;         // [kc][P] the staged parameters of the chunk
+    int P;
+    int cross;                // the cost sums are wanted
+    double *centre;           // [WP_NCENTRE]
+    double *part;             // [nrows][WT_SLOTS][WP_PART]
+    // wcp_final only
+    double *mean_q;           // [nrows][P]
+    double *cov_q;            // [nrows][P^2] column-major
+    double *cov_qJ;           // [nrows][P], or null
+    double *ess;              // [nrows][4]: S0, sum y^2, and with the cost sums the mean and variance of J the moment kernel finds
+};
+// the centres from the first chunk (a.t.kc, a.t.cost, a.qs): behind that chunk's q, before its sums
+void launch_wcp_centre(const WpArgs &a, hipStream_t s);
+// one chunk, behind launch_wct_weights and the chunk's q: the chunk's sums into the partials
+void launch_wcp_chunk(const WpArgs &a, hipStream_t s);
+void launch_wcp_final(const WpArgs &a, hipStream_t s);
+
 // ---- rat_policy_events: how often a policy violates quadratic constraints, under q and under every row's tilt (policy_mc.hip) ---------------
 // An event is g(t, z) = z' Q z + a' z + b of z = (x_t, u_t) in the 12 + 4 tile, watched over the steps t_lo .. t_hi.  Behind each replayed
 // chunk (after wct_weights) ev_eval forms, per rollout and event, the margin M = max g over the window, the first step tau with g > 0 and

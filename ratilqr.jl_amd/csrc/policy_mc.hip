@@ -980,6 +980,157 @@ __global__ __launch_bounds__(MC_THREADS) void wcd_final(WdArgs a) {
     if (t == 0 && e == 0) { a.ess[2 * r] = s0; a.ess[2 * r + 1] = S[WD_O_SY2]; }
 }
 
+// ---- rat_policy_worst_case_params: weighted moments of the rollouts' drawn parameters ----------------------------------------------------
+// wct_moments' schedule and lane layout with one step and up to two tiles of sixteen parameters per lane: lane (i, kk) holds Dq_i (tile 0)
+// and Dq_{16 + i} (tile 1, TWO) of rollout 4 g + kk.  Per group and row A0 = y Dq(tile 0), B0 = Dq(tile 0) give block (0,0) of
+// sum y Dq Dq'; with TWO, A0 and B1 give block (0,1) and A1, B1 block (1,1); block (1,0) is (0,1)' and is never formed.  S1, S0, sum y^2
+// and, with CROSS, sum y DJ, sum y DJ^2, sum y DJ Dq ride along in the same lanes.  Padding lanes (parameter index >= P) and padding
+// rollouts enter as exact zeros; a rollout without a cost is selected out (its q may hold NaN).  The same order as wct_moments: a
+// wavefront's groups in order, wavefronts and rollout lanes in index order through LDS, chunk after chunk in stream order, the slots in
+// wcp_final.  The centres: wcd_centre's rule, for q and for J.
+#define WP_SH (768 + 4 * 64 + 16)   /* LDS doubles per wavefront and row: three blocks | S1 and SJq per lane and tile | S0, sum y^2, SJ, SJ2 [4] each */
+
+__global__ __launch_bounds__(MC_THREADS) void wcp_centre(WpArgs a) {
+    __shared__ int first;
+    if (threadIdx.x == 0) first = WD_NONE;
+    __syncthreads();
+    for (long q = threadIdx.x; q < a.t.kc; q += MC_THREADS)
+        if (!mc_nan(a.t.cost[q])) { atomicMin(&first, (int)q); break; }                  // (an integer minimum: no order in it)
+    __syncthreads();
+    const int q = first;
+    for (int e = threadIdx.x; e < WP_NCENTRE; e += MC_THREADS) {
+        double v = 0.0;
+        if (q != WD_NONE && e < a.P) v = a.qs[(long)q * a.P + e];
+        if (q != WD_NONE && e == WP_MAXP) v = a.t.cost[q];
+        if (!(fabs(v) < __builtin_inf())) v = 0.0;                    // (a centre is only a centre: any finite value serves)
+        a.centre[e] = v;
+    }
+}
+
+template <bool TWO, bool CROSS>
+__global__ __launch_bounds__(WT_WAVES * 64) void wcp_moments(WpArgs a) {
+    __shared__ double sh[WT_WAVES][WP_SH];
+    const int slot = blockIdx.x, r0 = blockIdx.y * WT_ROWS;
+    const int nrows = a.t.nrows, P = a.P;
+    const int nr = (nrows - r0 < WT_ROWS) ? nrows - r0 : WT_ROWS;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
+    const bool comp0 = i < P, comp1 = TWO && 16 + i < P;             // (padding lanes stay zero)
+    const double c0 = a.centre[i], c1 = a.centre[16 + i], cJ = a.centre[WP_MAXP];
+    wt_d4 a00[WT_ROWS], a01[WT_ROWS], a11[WT_ROWS];
+    double s1a[WT_ROWS], s1b[WT_ROWS], sqa[WT_ROWS], sqb[WT_ROWS], s0[WT_ROWS], sy2[WT_ROWS], sj[WT_ROWS], sj2[WT_ROWS];
+#pragma unroll
+    for (int r = 0; r < WT_ROWS; ++r) {
+        a00[r] = (wt_d4){0.0, 0.0, 0.0, 0.0}; a01[r] = (wt_d4){0.0, 0.0, 0.0, 0.0}; a11[r] = (wt_d4){0.0, 0.0, 0.0, 0.0};
+        s1a[r] = 0.0; s1b[r] = 0.0; sqa[r] = 0.0; sqb[r] = 0.0; s0[r] = 0.0; sy2[r] = 0.0; sj[r] = 0.0; sj2[r] = 0.0;
+    }
+    const long kc = a.t.kc, G = (kc + 3) >> 2;
+    for (long g = (long)slot * WT_WAVES + w; g < G; g += (long)WT_SLOTS * WT_WAVES) {      // (uniform over the wavefront)
+        const long q = 4 * g + kk;
+        const bool live = q < kc;                                     // (the K tail)
+        const double J = live ? a.t.cost[q] : 0.0;
+        const bool ok = live && !mc_nan(J);                           // selected, not multiplied: q may hold NaN
+        double D0 = 0.0, D1 = 0.0;
+        if (ok && comp0) D0 = a.qs[q * P + i] - c0;
+        if (TWO && ok && comp1) D1 = a.qs[q * P + 16 + i] - c1;
+        const double DJ = (CROSS && ok) ? J - cJ : 0.0;
+#pragma unroll
+        for (int r = 0; r < WT_ROWS; ++r) {
+            if (r < nr) {                                             // (uniform over the workgroup)
+                const double y = ok ? a.t.y[(long)(r0 + r) * a.t.ldy + q] : 0.0;
+                const double yd0 = y * D0;
+                a00[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd0, D0, a00[r], 0, 0, 0);
+                s1a[r] += yd0;
+                if (TWO) {
+                    const double yd1 = y * D1;
+                    a01[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd0, D1, a01[r], 0, 0, 0);
+                    a11[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd1, D1, a11[r], 0, 0, 0);
+                    s1b[r] += yd1;
+                }
+                s0[r] += y; sy2[r] += y * y;
+                if (CROSS) {
+                    const double yj = y * DJ;
+                    sj[r] += yj; sj2[r] += yj * DJ; sqa[r] += yj * D0;
+                    if (TWO) sqb[r] += yj * D1;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < WT_ROWS; ++r) {
+        if (r < nr) {
+            __syncthreads();                                          // (the previous row's sums are read)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {                       // C: row (lane >> 4) + 4 reg, column lane & 15
+                sh[w][(kk + 4 * reg) * 16 + i] = a00[r][reg];
+                if (TWO) { sh[w][256 + (kk + 4 * reg) * 16 + i] = a01[r][reg]; sh[w][512 + (kk + 4 * reg) * 16 + i] = a11[r][reg]; }
+            }
+            sh[w][768 + lane] = s1a[r];
+            if (TWO) sh[w][832 + lane] = s1b[r];
+            if (CROSS) { sh[w][896 + lane] = sqa[r]; if (TWO) sh[w][960 + lane] = sqb[r]; }
+            if (i == 0) {
+                sh[w][1024 + kk] = s0[r]; sh[w][1028 + kk] = sy2[r];
+                if (CROSS) { sh[w][1032 + kk] = sj[r]; sh[w][1036 + kk] = sj2[r]; }
+            }
+            __syncthreads();
+            double *p = a.part + ((size_t)(r0 + r) * WT_SLOTS + slot) * WP_PART;
+            const int e = threadIdx.x;
+            for (int b = 0; b < (TWO ? 3 : 1); ++b) {
+                double v = 0.0;
+                for (int w2 = 0; w2 < WT_WAVES; ++w2) v += sh[w2][b * 256 + e];
+                p[b * 256 + e] += v;
+            }
+            if (e < 64) {                                             // S1 [32], then SJq [32]: tile e2 >> 4, component e2 & 15
+                const int e2 = e & 31, o = (e < 32 ? 768 : 896) + (e2 >> 4) * 64 + (e2 & 15);
+                if ((TWO || e2 < 16) && (CROSS || e < 32)) {
+                    double v = 0.0;
+                    for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][o + k2 * 16];
+                    p[(e < 32 ? WP_O_S1 : WP_O_SJQ) + e2] += v;
+                }
+            } else if (e < 68) {                                      // S0, sum y^2, SJ, SJ2
+                const int s = e - 64;
+                if (CROSS || s < 2) {
+                    double v = 0.0;
+                    for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][1024 + 4 * s + k2];
+                    p[WP_O_S0 + s] += v;
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void wcp_final(WpArgs a) {
+#pragma clang fp contract(off)                                        // S2 / S0 - m m' with m m' rounded: where one rollout carries all the weight the two are the same product, and the covariance is exactly 0
+    __shared__ double S[WP_PART];
+    const int r = blockIdx.x, e0 = threadIdx.x, P = a.P;
+    const double *p = a.part + (size_t)r * WT_SLOTS * WP_PART;
+    for (int q = e0; q < WP_PART; q += MC_THREADS) {
+        double v = 0.0;
+        for (int s = 0; s < WT_SLOTS; ++s) v += p[s * WP_PART + q];
+        S[q] = v;
+    }
+    __syncthreads();
+    const double st = a.t.wc[WC_O_INFO + 2 * r + 1], nan = __builtin_nan("");
+    const bool dead = (st == WC_ST_EMPTY || st == WC_ST_NONFINITE);
+    const double s0 = S[WP_O_S0];
+    for (int e = e0; e < P * P; e += MC_THREADS) {                    // column-major; the upper triangle serves both halves, block (0,1) block (1,0)
+        const int ii = e % P, jj = e / P;
+        const int lo = ii < jj ? ii : jj, hi = ii < jj ? jj : ii;
+        const int blk = (lo >> 4) + (hi >> 4);                        // (0,0) -> 0, (0,1) -> 1, (1,1) -> 2
+        const double mi = S[WP_O_S1 + ii] / s0, mj = S[WP_O_S1 + jj] / s0;
+        a.cov_q[(size_t)r * P * P + e] = dead ? nan : S[blk * 256 + (lo & 15) * 16 + (hi & 15)] / s0 - mi * mj;
+    }
+    if (e0 < P) {
+        const double mi = S[WP_O_S1 + e0] / s0;
+        a.mean_q[(size_t)r * P + e0] = dead ? nan : a.centre[e0] + mi;
+        if (a.cov_qJ) a.cov_qJ[(size_t)r * P + e0] = dead ? nan : S[WP_O_SJQ + e0] / s0 - mi * (S[WP_O_SJ] / s0);
+    }
+    if (e0 == 0) {
+        const double mj = S[WP_O_SJ] / s0;
+        a.ess[4 * r] = s0; a.ess[4 * r + 1] = S[WP_O_SY2];
+        a.ess[4 * r + 2] = a.centre[WP_MAXP] + mj; a.ess[4 * r + 3] = S[WP_O_SJ2] / s0 - mj * mj;
+    }
+}
+
 // ---- rat_policy_events: violation probabilities of quadratic events on the replayed trajectories ----------------------------------------
 // ev_eval: a wavefront takes sixteen rollouts as the columns of Z [16 components][16 rollouts] and walks the steps; lane (col = lane & 15,
 // kq = lane >> 4) holds Z[kq + 4 r][col], r = 0 .. 3 -- x components kq, kq + 4, kq + 8 and u component kq -- which is at once the B operand
@@ -1219,6 +1370,26 @@ void launch_wcd_chunk(const WdArgs &a, hipStream_t s) {
 
 void launch_wcd_final(const WdArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(wcd_final, dim3((unsigned)a.t.N, (unsigned)a.t.nrows), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_wcp_centre(const WpArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(wcp_centre, dim3(1), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_wcp_chunk(const WpArgs &a, hipStream_t s) {
+    if (a.t.kc <= 0) return;
+    const dim3 grid(WT_SLOTS, (unsigned)((a.t.nrows + WT_ROWS - 1) / WT_ROWS)), block(WT_WAVES * 64);
+    if (a.P > 16) {
+        if (a.cross) hipLaunchKernelGGL((wcp_moments<true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((wcp_moments<true, false>), grid, block, 0, s, a);
+    } else {
+        if (a.cross) hipLaunchKernelGGL((wcp_moments<false, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((wcp_moments<false, false>), grid, block, 0, s, a);
+    }
+}
+
+void launch_wcp_final(const WpArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(wcp_final, dim3((unsigned)a.t.nrows), dim3(MC_THREADS), 0, s, a);
 }
 
 void launch_ev_chunk(const EvArgs &a, hipStream_t s) {

@@ -196,6 +196,9 @@ class GenericContext(il.Context):
     def policy_worst_case_disturbance(self, *a, **k):
         self._carrier_only("policy_worst_case_disturbance")
 
+    def policy_worst_case_params(self, *a, **k):
+        self._carrier_only("policy_worst_case_params")
+
     def policy_tail_risk(self, *a, **k):
         self._carrier_only("policy_tail_risk")
 

@@ -48,6 +48,16 @@ class ParamSampling:
         self.zpu = None if zpu is None else nv.f64(zpu)
 
 
+def explained_share(cov_q, cov_qJ, tilt_var):
+    """The linear share of the cost's variance that each parameter explains under a row's distribution, from the outputs of
+    Context.policy_worst_case_params: cov_qJ[i]^2 / (cov_q[i, i] tilt_var) -- the squared correlation of q_i with J.  cov_q (R, P, P),
+    cov_qJ (R, P), tilt_var (R,); (R, P), NaN where a parameter or the cost does not vary."""
+    cov_q, cov_qJ, tilt_var = np.asarray(cov_q, float), np.asarray(cov_qJ, float), np.asarray(tilt_var, float)
+    with np.errstate(all="ignore"):
+        share = cov_qJ ** 2 / (np.diagonal(cov_q, axis1=-2, axis2=-1) * tilt_var[..., None])
+    return np.where(np.isfinite(share), share, np.nan)
+
+
 class Event:
     """A safety event of Context.policy_events: g(t, z) = z' Q z + a' z + b of z = (x_t, u_t), violated where g > 0 at a step of the window.
     Build one with halfspace, ball or quadratic_event.  Q (or None: linear) and a are given over (x, u) -- n + m entries -- or over x
@@ -414,6 +424,34 @@ class Context:
             r.update(mean_w=mean[sl].copy(), cov_w=cov[sl].copy())
             if cross:
                 r.update(cov_wx=wz[sl, :, :, :n].copy(), cov_wu=wz[sl, :, :, n:].copy())
+            return r
+        return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)))
+
+    def policy_worst_case_params(self, kl_bounds=(), thetas=(), cost=True):
+        """What the adversary picks among the uncertain parameters (rat_policy_worst_case_params): the mean and covariance of the
+        parameters q that the source's rat_user_params drew for the rollouts, and their covariance with the rollout's cost, under the
+        worst-case distribution p* ~ exp(theta* J) q of each KL radius -- and under the tilt of each given theta; theta = 0 is the nominal
+        distribution -- formed on the device by replaying the last policy_evaluate_noise of this context (parameter sampling on, device
+        generator for the noise) like policy_worst_case_trajectory.  Returns {"bounds": part, "thetas": part}; a part carries
+        policy_worst_case's row keys and, with R rows and P = n_params, mean_q (R, P), cov_q (R, P, P) (population form, exactly
+        symmetric) and, with cost, cov_qJ (R, P) -- dE[q] / dtheta at the row's tilt -- and the derived explained_share (R, P):
+        cov_qJ[i]^2 / (cov_q[i, i] tilt_var), the linear share of the cost's variance that parameter i explains (NaN where a parameter or
+        the cost does not vary)."""
+        d = nv.f64(np.atleast_1d(np.asarray(kl_bounds, dtype=np.float64))).ravel()
+        th = nv.f64(np.atleast_1d(np.asarray(thetas, dtype=np.float64))).ravel()
+        P, R = getattr(self, "params", np.zeros(0)).size, d.size + th.size
+        rows, mean, cov = np.zeros((R, nv.WC_NSTAT)), np.zeros((R, P)), np.zeros((R, P, P))
+        qJ = np.zeros((R, P)) if cost else None
+        nv.check(nv.lib().rat_policy_worst_case_params(self.h, nv.P(d) if d.size else None, C.c_int32(d.size), nv.P(th) if th.size else None,
+                                                       C.c_int32(th.size), nv.P(rows), nv.P(mean), nv.P(cov), nv.P(qJ)))
+        cov = cov.transpose(0, 2, 1)                                  # (column-major blocks)
+
+        def part(sl):
+            r = {k: rows[sl, i].copy() for i, k in enumerate(nv.WC_SLOTS)}
+            r["flag"] = r["flag"].astype(np.int64)
+            r.update(mean_q=mean[sl].copy(), cov_q=cov[sl].copy())
+            if cost:
+                r.update(cov_qJ=qJ[sl].copy(), explained_share=explained_share(cov[sl], qJ[sl], r["tilt_var"]))
             return r
         return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)))
 
