@@ -491,6 +491,36 @@ rat_rc rat_policy_worst_case_params(rat_handle h, const double *kl_bound, int32_
 #define RAT_TR_NONFINITE 3
 rat_rc rat_policy_tail_risk(rat_handle h, const double *cost, int64_t K, const double *alpha, int32_t n_alpha,
                             double *rows_out, double *weights_out);
+/* What the tail looks like: the moments of rat_policy_worst_case_trajectory / _disturbance / _params under the CVaR adversary's
+ * distribution instead of the KL adversary's -- per level alpha the tail distribution of rat_policy_tail_risk, which puts equal weight on
+ * every rollout above VAR, r / c_eq of it on each rollout at VAR and none below: "what do the worst (1 - alpha) of the rollouts look like".
+ * Each call REPLAYS the last evaluation exactly as its worst-case sibling does -- the same chunks and seeds, the same bit-for-bit check
+ * against the stored costs, the same centres, partial sums and fixed summation order -- with rat_policy_tail_risk's chain on the stored
+ * costs as the source of the rows and of the weights.
+ *   alpha      [n_alpha], 1 <= n_alpha <= 16, every one in [0, 1): rat_policy_tail_risk's rules (RAT_ERR_ARG)
+ *   rows_out   [n_alpha][RAT_TR_NSTAT]: what rat_policy_tail_risk(h, NULL, 0, alpha, n_alpha, ...) returns on the stored costs, bit for bit
+ *   the moment outputs: the sibling's layouts with n_alpha rows -- mean_out [n_alpha][N+1][n+m], cov_out [n_alpha][N+1][(n+m)^2]
+ *              column-major; mean_w_out [n_alpha][N][n], cov_w_out [n_alpha][N][n^2], cov_wz_out [n_alpha][N][n (n+m)] or NULL;
+ *              mean_q_out [n_alpha][P], cov_q_out [n_alpha][P^2], cov_qJ_out [n_alpha][P] or NULL -- in the population form
+ *              sum y (. - mean)(. - mean)' / sum y
+ * alpha == 0 is the whole sample: the nominal row, bit for bit the theta = 0 row of the sibling.  A RAT_TR_SATURATED level (a tail
+ * thinner than one rollout) holds the moments of the rollouts that attain Jmax; RAT_TR_EMPTY and RAT_TR_NONFINITE levels are NaN in every
+ * output (the call still returns RAT_OK).  A DomainError rollout carries no weight.  A row's bits do not depend on the other levels of
+ * the call.
+ * The schedule: at alpha = 0.99 one rollout in a hundred carries weight, so the moment kernels read, per group of four rollouts, one word
+ * of "level r has weight here" bits first; a group without weight in a row issues no MFMA for it, a group without weight in any row is
+ * not loaded, and a rollout without weight in a row is selected out of that row's operands.  Adding 0 D changes no bit of a sum where D
+ * is finite, so on finite data the results are those of the sibling's dense kernels on the same weights, bit for bit.  The one
+ * difference: a rollout WITHOUT weight in a row whose trajectory, disturbance or parameters hold Inf or NaN is left out of that row,
+ * where the dense kernels form 0 Inf = NaN (the worst-case calls give every rollout with a cost a positive weight, so it cannot arise
+ * there).
+ * Served and refused as the siblings, with the same codes and caps (rows x (N + 1) above 3640, rows x N above 1899 with n_alpha rows);
+ * costs uploaded by rat_policy_tail_risk(cost != NULL) are no evaluation's.  rat_policy_events has no CVaR rows. */
+rat_rc rat_policy_tail_trajectory(rat_handle h, const double *alpha, int32_t n_alpha, double *rows_out, double *mean_out, double *cov_out);
+rat_rc rat_policy_tail_disturbance(rat_handle h, const double *alpha, int32_t n_alpha, double *rows_out, double *mean_w_out,
+                                   double *cov_w_out, double *cov_wz_out);
+rat_rc rat_policy_tail_params(rat_handle h, const double *alpha, int32_t n_alpha, double *rows_out, double *mean_q_out,
+                              double *cov_q_out, double *cov_qJ_out);
 /* Safety events of a policy: how often it hits an obstacle, leaves the lane or saturates an actuator -- under the nominal distribution q (a
  * theta = 0 row) and under the worst-case distribution p* ~ exp(theta* J) q of each kl_bound (and the tilt of each given theta), formed on
  * the device.  An event is a quadratic function of z_t = (x_t, u_t) in R^d, d = n + m, u_N = 0, watched over a window of steps:
@@ -1026,6 +1056,8 @@ int32_t rat_get_path(rat_handle h, int64_t B);
  *                            rollouts/s at 10^6 trajectories, equal at 10 k; profiles/source_pets.md)                     (64)
  *   mc_cost_K       read-only      costs the last rat_policy_evaluate / _noise (or rat_policy_worst_case / rat_policy_tail_risk with host costs) left on the device (0: none)
  *   src_mc_tpw      16 / 32 / 64   source models: rollouts per wavefront of rat_policy_evaluate's rollout kernel (profiles/policy_mc.md) (64)
+ *   tail_dense      0 / 1    rat_policy_tail_trajectory / _disturbance / _params run the worst-case calls' dense moment kernels on the tail
+ *                            weights instead of the liveness schedule: what that schedule is measured against (profiles/policy_tail_scenarios.md) (0)
  *   wdiag           0 / 1    diagonal time-invariant W: inv(W) folded into M^-1's operand (takes effect at the next rat_problem_set) (1) */
 rat_rc  rat_debug_set(rat_handle h, const char *key, int64_t value);
 rat_rc  rat_debug_get(rat_handle h, const char *key, int64_t *value);      /* the EFFECTIVE value on this handle */

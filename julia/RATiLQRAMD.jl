@@ -551,6 +551,62 @@ function policy_worst_case_params(s::ILEQGSolver, problem::DeviceSourceProblem; 
     (bounds=part(1:nb), thetas=part(nb+1:R))
 end
 
+tail_rows(o, r) = (alpha=o[1, r], var=o[2, r], cvar=o[3, r], cvar_se=o[4, r], tail_n=o[5, r], ess=o[6, r], kl=o[7, r], flag=Int.(o[8, r]))
+
+"""
+policy_tail_trajectory(s; alphas): what the tail looks like (rat_policy_tail_trajectory).  The mean and covariance of the state and the
+control at every step over the worst (1 − α) share of the rollouts -- the tail distribution of policy_tail_risk, the CVaR adversary's --
+per level α ∈ [0, 1) (1 to 16 levels; α = 0 is the nominal distribution), formed on the device by replaying the last evaluate_policy on
+this solver's handle like policy_worst_case_trajectory.  Returns a named tuple of policy_tail_risk's row vectors and, with R levels,
+mean_x (n, N+1, R), cov_x (n, n, N+1, R), mean_u (m, N, R), cov_u (m, m, N, R), cov_xu (n, m, N, R); population covariances.
+"""
+function policy_tail_trajectory(s::ILEQGSolver; alphas=Float64[])
+    h = s.h
+    n, m, N = dims(h.problem)
+    al = collect(Float64, alphas); R = length(al); q = n + m
+    rows = zeros(8, R); mean = zeros(q, N + 1, R); cov = zeros(q, q, N + 1, R)
+    check(ccall((:rat_policy_tail_trajectory, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, R > 0 ? al : C_NULL, R, rows, mean, cov))
+    merge(tail_rows(rows, 1:R), (mean_x=mean[1:n, :, :], cov_x=cov[1:n, 1:n, :, :], mean_u=mean[n+1:q, 1:N, :],
+                                 cov_u=cov[n+1:q, n+1:q, 1:N, :], cov_xu=cov[1:n, n+1:q, 1:N, :]))
+end
+
+"""
+policy_tail_disturbance(s; alphas, cross): what the noise of the tail looks like (rat_policy_tail_disturbance):
+policy_worst_case_disturbance's moments over the worst (1 − α) share of the rollouts per level.  Returns a named tuple of
+policy_tail_risk's row vectors and, with R levels, mean_w (n, N, R), cov_w (n, n, N, R) and, with cross, cov_wx (n, n, N, R) and cov_wu
+(n, m, N, R) (`nothing` otherwise).
+"""
+function policy_tail_disturbance(s::ILEQGSolver; alphas=Float64[], cross::Bool=true)
+    h = s.h
+    n, m, N = dims(h.problem)
+    al = collect(Float64, alphas); R = length(al); q = n + m
+    rows = zeros(8, R); mean = zeros(n, N, R); cov = zeros(n, n, N, R)
+    wz = cross ? zeros(n, q, N, R) : nothing
+    check(ccall((:rat_policy_tail_disturbance, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, R > 0 ? al : C_NULL, R, rows, mean, cov, cross ? wz : C_NULL))
+    merge(tail_rows(rows, 1:R), (mean_w=mean, cov_w=cov, cov_wx=cross ? wz[:, 1:n, :, :] : nothing, cov_wu=cross ? wz[:, n+1:q, :, :] : nothing))
+end
+
+"""
+policy_tail_params(s, problem; alphas, cost): which parameters the tail drew (rat_policy_tail_params): policy_worst_case_params' moments
+over the worst (1 − α) share of the rollouts per level.  Returns a named tuple of policy_tail_risk's row vectors and, with R levels and
+P = length(problem.params), mean_q (P, R), cov_q (P, P, R) and, with cost, cov_qJ (P, R) (`nothing` otherwise).
+"""
+function policy_tail_params(s::ILEQGSolver, problem::DeviceSourceProblem; alphas=Float64[], cost::Bool=true)
+    h = bind!(s.h, problem)
+    P = length(problem.params)
+    al = collect(Float64, alphas); R = length(al)
+    rows = zeros(8, R); mean = zeros(P, R); cov = zeros(P, P, R)
+    qJ = cost ? zeros(P, R) : nothing
+    check(ccall((:rat_policy_tail_params, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, R > 0 ? al : C_NULL, R, rows, mean, cov, cost ? qJ : C_NULL))
+    merge(tail_rows(rows, 1:R), (mean_q=mean, cov_q=cov, cov_qJ=qJ))
+end
+
 """
 policy_events(s, Q, a, b, t_lo, t_hi; kl_bounds, thetas, want_steps, want_margins): how often the policy violates safety events
 (rat_policy_events).  Event i is z' Q[:, :, i] z + a[:, i]' z + b[i] > 0 at a step t_lo[i] ≤ t ≤ t_hi[i] (0-based steps, z = (x_t, u_t));
@@ -1555,7 +1611,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

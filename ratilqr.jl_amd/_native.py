@@ -96,6 +96,7 @@ EXPORTS = [
     "rat_policy_worst_case_disturbance",
     "rat_policy_worst_case_params",
     "rat_policy_tail_risk",
+    "rat_policy_tail_trajectory", "rat_policy_tail_disturbance", "rat_policy_tail_params",
     "rat_policy_events", "rat_kl_event_bound",
     "rat_policy_rare_event",
     "rat_policy_rare_event_noise", "rat_rare_event_noise_check",
@@ -156,6 +157,9 @@ def lib():
         _lib.rat_policy_worst_case_disturbance.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp]
         _lib.rat_policy_worst_case_params.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp]
         _lib.rat_policy_tail_risk.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int32, _dp, _dp]
+        _lib.rat_policy_tail_trajectory.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp]
+        _lib.rat_policy_tail_disturbance.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, _dp]
+        _lib.rat_policy_tail_params.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, _dp]
         _lib.rat_policy_events.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _ip, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp]
         _lib.rat_kl_event_bound.argtypes = [C.c_double, C.c_double, _dp]
         _lib.rat_policy_rare_event.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_uint64, _dp, _dp, C.c_double, C.c_int32, C.c_int32, _dp,

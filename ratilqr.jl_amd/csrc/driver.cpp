@@ -244,6 +244,10 @@ struct rat_handle_s {
     double *d_wp_q = nullptr; size_t cap_wp_q = 0;           // [chunk][n_params] parameter staging
     double *d_wp_part = nullptr; size_t cap_wp_part = 0;     // [rows][WT_SLOTS][WP_PART] partials
     double *d_wp_out = nullptr; size_t cap_wp_out = 0;       // c_q [32], c_J | mean_q | cov_q | cov_qJ | S0, sum y^2, mean J, var J per row | mismatch count
+    // the tail calls (rat_policy_tail_trajectory / _disturbance / _params, policy_mc.hip) ride on the same replay with the tail-risk chain
+    // as the row source; their moment kernels skip what the liveness words call dead
+    unsigned *d_tl_live = nullptr; size_t cap_tl_live = 0;   // [chunk / 4] one word per group of four rollouts: bit r, level r has weight there
+    bool tail_dense = false;                                 // switch tail_dense: those calls run the worst-case calls' dense moment kernels (measurement)
     // the safety events (rat_policy_events, policy_mc.hip) ride on the same replay; grown on demand
     double *d_ev_out = nullptr; size_t cap_ev_out = 0;       // Q [16][256] | a [16][16] | b [16] | windows | event_out | step_out | mismatch count
     double *d_ev_part = nullptr; size_t cap_ev_part = 0;     // [row batches][steps + events][EV_SLOTS][EV_PART] partials
@@ -341,6 +345,7 @@ static const DebugSwitch debug_switches[] = {
     {"src_pets_tpw", [](rat_handle h, int64_t v) { h->src_pets_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_pets_tpw; }},
     {"mc_cost_K", [](rat_handle, int64_t) {}, [](rat_handle h) -> int64_t { return h->mc_cost_K; }},   // read-only
     {"src_mc_tpw", [](rat_handle h, int64_t v) { h->src_mc_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_mc_tpw; }},
+    {"tail_dense", [](rat_handle h, int64_t v) { h->tail_dense = (v != 0); }, [](rat_handle h) -> int64_t { return h->tail_dense; }},
     {"src_un_loads", [](rat_handle, int64_t) {}, [](rat_handle h) -> int64_t { return h->src_un_loads; }},
 };
 // what the requests amount to on this handle (speculation width, forced pairings)
@@ -443,7 +448,7 @@ extern "C" void rat_destroy(rat_handle h) {
     src_drop_slots(h);
     for (double *q : {h->d_mc_zu, h->d_mc_xo, h->d_mc_uo, h->d_ps_zn, h->d_ps_zu}) if (q) (void)hipFree(q);
     for (double *q : {h->d_wc_red, h->d_wc_w, h->d_tr_red}) if (q) (void)hipFree(q);
-    for (void *q : {(void *)h->d_wt_cost, (void *)h->d_wt_dom, (void *)h->d_wt_y, (void *)h->d_wt_part, (void *)h->d_wt_out}) if (q) (void)hipFree(q);
+    for (void *q : {(void *)h->d_wt_cost, (void *)h->d_wt_dom, (void *)h->d_wt_y, (void *)h->d_wt_part, (void *)h->d_wt_out, (void *)h->d_tl_live}) if (q) (void)hipFree(q);
     for (double *q : {h->d_mc_wo, h->d_wd_part, h->d_wd_out}) if (q) (void)hipFree(q);
     for (double *q : {h->d_wp_q, h->d_wp_part, h->d_wp_out}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_ev_out, (void *)h->d_ev_part, (void *)h->d_ev_margin, (void *)h->d_ev_tau, (void *)h->d_ev_mask}) if (q) (void)hipFree(q);
@@ -2554,6 +2559,20 @@ extern "C" rat_rc rat_policy_tail_risk(rat_handle h, const double *cost, int64_t
 // longer what the evaluation ran.
 static const char *const REPLAY_CHANGED = "the problem, its parameters or the policy changed since the evaluation: evaluate again";
 
+static rat_rc replay_validate_handle(rat_handle h, const std::string &F, const char *rows_fn);
+
+// The rows of a replay, by their source: KL radii and thetas (rat_policy_worst_case's chain: the worst-case calls and the events) or CVaR
+// levels (rat_policy_tail_risk's chain: the tail calls, n_alpha > 0 and no kl_bound or theta then)
+struct ReplaySpec {
+    const double *kl_bound; int32_t n_bound; const double *theta; int32_t n_theta; const double *alpha; int32_t n_alpha;
+    bool tail() const { return n_alpha > 0; }
+    int nrows() const { return tail() ? n_alpha : n_bound + n_theta; }
+};
+static ReplaySpec replay_kl(const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta) {
+    return ReplaySpec{kl_bound, n_bound, theta, n_theta, nullptr, 0};
+}
+static ReplaySpec replay_tail(const double *alpha, int32_t n_alpha) { return ReplaySpec{nullptr, 0, nullptr, 0, alpha, n_alpha}; }
+
 // the row arguments and the state of the handle: everything either call refuses before it touches the device
 static rat_rc replay_validate(rat_handle h, const std::string &F, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
                               bool outputs_ok) {
@@ -2566,20 +2585,35 @@ static rat_rc replay_validate(rat_handle h, const std::string &F, const double *
         if (!(kl_bound[i] >= 0.0)) return fail(RAT_ERR_ARG, F + "every kl_bound must be >= 0 (+Inf is allowed, NaN is not)");
     for (int i = 0; i < n_theta; ++i)
         if (!(theta[i] >= 0.0) || std::isinf(theta[i])) return fail(RAT_ERR_ARG, F + "every theta must be >= 0 and finite");
+    return replay_validate_handle(h, F, "rat_policy_worst_case");
+}
+
+// the row arguments of the tail calls: rat_policy_tail_risk's rules and messages for the levels
+static rat_rc replay_validate_alpha(const std::string &F, const double *alpha, int32_t n_alpha, bool outputs_ok) {
+    if (n_alpha < 1 || n_alpha > TR_MAX_ALPHA) return fail(RAT_ERR_ARG, F + "n_alpha must be in 1 .. 16");
+    if (!alpha || !outputs_ok) return fail(RAT_ERR_ARG, F + "null alpha / output");
+    for (int i = 0; i < n_alpha; ++i)
+        if (!(alpha[i] >= 0.0 && alpha[i] < 1.0)) return fail(RAT_ERR_ARG, F + "every alpha must be in [0, 1) (NaN is not)");
+    return RAT_OK;
+}
+
+// the state of the handle; rows_fn: the function whose weights_out serves the host route (the one that forms this call's rows)
+static rat_rc replay_validate_handle(rat_handle h, const std::string &F, const char *rows_fn) {
+    if (!h) return fail(RAT_ERR_ARG, F + "null handle");
     if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
     if (h->wide)
-        return fail(RAT_ERR_UNSUPPORTED, F + "compiled for n <= 12, m <= 4 (general sizes: rat_rollout_noisy's x_out / u_out with "
-                                         "rat_policy_worst_case's weights_out, combined on the host)");
+        return fail(RAT_ERR_UNSUPPORTED, F + "compiled for n <= 12, m <= 4 (general sizes: rat_rollout_noisy's x_out / u_out with " +
+                                         rows_fn + "'s weights_out, combined on the host)");
     const rat_handle_s::McReplay &rec = h->mc_rec;
     if (rec.kind == 0 || h->mc_cost_K == 0 || rec.K != h->mc_cost_K)
         return fail(RAT_ERR_ARG, F + "no evaluation to replay: call rat_policy_evaluate / rat_policy_evaluate_noise on this handle first "
-                                 "(costs uploaded by rat_policy_worst_case are no evaluation's)");
+                                 "(costs uploaded by " + rows_fn + " are no evaluation's)");
     if (rec.kind == 4)
         return fail(RAT_ERR_UNSUPPORTED, F + "a source model evaluated under N(0, W) has no trajectory output: write the Gaussian as "
                                          "rat_user_noise and evaluate with rat_policy_evaluate_noise");
     if (rec.injected)
         return fail(RAT_ERR_UNSUPPORTED, F + "the evaluation ran on injected draws, which are not kept: combine the trajectories the "
-                                         "caller has (x_out / u_out) with rat_policy_worst_case's weights_out on the host");
+                                         "caller has (x_out / u_out) with " + rows_fn + "'s weights_out on the host");
     const bool source = h->pb.model == RAT_MODEL_SOURCE;
     const SrcSlot &un = h->src_slot[SRC_USER_NOISE];
     if (rec.kind == 3 || rec.n != h->n || rec.m != h->m || rec.N != h->N || rec.model != h->pb.model || rec.W_tv != h->W_tv || (rec.kind == 2) != source ||
@@ -2596,12 +2630,14 @@ struct ReplayChunk { int64_t k0, kc; };
 // behind each.  The
 // stream orders a chunk's rollouts behind the sums of the one before.  d_wo (rat_policy_worst_case_disturbance alone; the caller grew it):
 // the rollouts keep the chunk's disturbances there, [kc][N][ldx].
+// The second row source (rs.tail(): the tail calls): rat_policy_tail_risk's chain on the stored costs (the
+// rows: d_tr_red) with tlt_levels behind it, which leaves every level's quantile, atom weight and state in d_wc_red where the worst-case
+// chain leaves a row's theta and state, and per chunk tlt_weights, which also writes the chunk's liveness words into d_tl_live.
 template <class Behind>
-static rat_rc replay_chunks(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta, int *d_mismatch,
-                            WtArgs &ta, Behind &&behind, double *d_wo = nullptr) {
+static rat_rc replay_chunks(rat_handle h, const ReplaySpec &rs, int *d_mismatch, WtArgs &ta, Behind &&behind, double *d_wo = nullptr) {
     const rat_handle_s::McReplay rec = h->mc_rec;
-    const bool source = h->pb.model == RAT_MODEL_SOURCE;
-    const int n = h->n, m = h->m, N = h->N, nrows = n_bound + n_theta;
+    const bool source = h->pb.model == RAT_MODEL_SOURCE, tail = rs.tail();
+    const int n = h->n, m = h->m, N = h->N, nrows = rs.nrows();
     const int64_t K = rec.K, chunk = mc_chunk(K);
     const int ldx = source ? n : XSTR, ldu = source ? m : USTR;
     rat_rc rc;
@@ -2621,13 +2657,26 @@ static rat_rc replay_chunks(rat_handle h, const double *kl_bound, int32_t n_boun
     if (!source && (rc = grow(&h->d_wt_dom, &h->cap_wt_dom, (size_t)chunk))) return rc;
     if ((rc = grow(&h->d_wt_y, &h->cap_wt_y, (size_t)nrows * chunk))) return rc;
     const PolicyDev dev = policy_dev(h->d_mc_in, rec.o_x, rec.o_l, rec.o_L, rec.has_L);
-    // theta*, Jmax and the rows, on the stored costs
-    WcArgs wa;
-    memset(&wa, 0, sizeof(wa));
-    wa.cost = h->d_mc_cost; wa.K = (long)K; wa.n_bound = n_bound; wa.n_theta = n_theta; wa.scratch = h->d_wc_red; wa.weights = nullptr;
-    for (int i = 0; i < n_bound; ++i) wa.bound[i] = kl_bound[i];
-    for (int i = 0; i < n_theta; ++i) wa.theta[i] = theta[i];
-    launch_policy_wc(wa, h->stream);
+    if (tail) {
+        // the levels' quantiles, atoms and rows, on the stored costs
+        size_t cap_tr = h->d_tr_red ? TR_SCRATCH : 0;
+        if ((rc = grow(&h->d_tr_red, &cap_tr, (size_t)TR_SCRATCH))) return rc;
+        if ((rc = grow(&h->d_tl_live, &h->cap_tl_live, (size_t)((chunk + 3) / 4)))) return rc;
+        TrArgs tr;
+        memset(&tr, 0, sizeof(tr));
+        tr.cost = h->d_mc_cost; tr.K = (long)K; tr.n_alpha = rs.n_alpha; tr.scratch = h->d_tr_red; tr.weights = nullptr;
+        for (int i = 0; i < rs.n_alpha; ++i) tr.alpha[i] = rs.alpha[i];
+        launch_policy_tr(tr, h->stream);
+        launch_tlt_levels(tr, h->d_wc_red, h->stream);
+    } else {
+        // theta*, Jmax and the rows, on the stored costs
+        WcArgs wa;
+        memset(&wa, 0, sizeof(wa));
+        wa.cost = h->d_mc_cost; wa.K = (long)K; wa.n_bound = rs.n_bound; wa.n_theta = rs.n_theta; wa.scratch = h->d_wc_red; wa.weights = nullptr;
+        for (int i = 0; i < rs.n_bound; ++i) wa.bound[i] = rs.kl_bound[i];
+        for (int i = 0; i < rs.n_theta; ++i) wa.theta[i] = rs.theta[i];
+        launch_policy_wc(wa, h->stream);
+    }
     HIPCHK(hipMemsetAsync(d_mismatch, 0, sizeof(int), h->stream));
     int *d_over = nullptr;
     if (source) { HIPCHK(hipHostGetDevicePointer((void **)&d_over, h->h_un_over, 0)); *h->h_un_over = 0; }
@@ -2642,7 +2691,8 @@ static rat_rc replay_chunks(rat_handle h, const double *kl_bound, int32_t n_boun
             launch_noisy_chunk(h, dev, k0, kc, chunk, rec.seed, nullptr, h->d_mc_xo, h->d_mc_uo, h->d_wt_cost, h->d_wt_dom, d_wo);
         }
         ta.kc = (long)kc; ta.cost = h->d_mc_cost + k0;
-        launch_wct_weights(ta, h->stream);
+        if (tail) launch_tlt_weights(ta, h->d_tl_live, h->stream);
+        else launch_wct_weights(ta, h->stream);
         if ((rc = behind(ta, ReplayChunk{k0, kc}))) return rc;
     }
     return RAT_OK;
@@ -2652,6 +2702,15 @@ static rat_rc replay_mismatch(const std::string &F, int bad, int64_t K) {
     if (bad == 0) return RAT_OK;
     return fail(RAT_ERR_ARG, F + std::to_string(bad) + " of " + std::to_string(K) + " replayed rollouts cost something else than the "
                              "evaluation found: " + REPLAY_CHANGED);
+}
+
+// Where a replay's rows lie on the device and which slot holds their effective sample size: rat_policy_worst_case's, or (the tail
+// calls) rat_policy_tail_risk's
+struct ReplayRows { const double *d_rows; int nstat, ess; };
+static ReplayRows replay_rows(rat_handle h, bool tail) {
+    static_assert(TR_MAX_ALPHA * TR_NSTAT <= WC_MAX_ROWS * WC_NSTAT, "the callers' row buffers hold either kind");
+    if (tail) return ReplayRows{h->d_tr_red + TR_O_ROWS, TR_NSTAT, RAT_TR_ESS};
+    return ReplayRows{h->d_wc_red + WC_O_ROWS, WC_NSTAT, RAT_WC_ESS};
 }
 
 // The centre c_t of the (x_t, u_t) tile, enqueued into centre [N+1][16]: (x_nom, l) under a policy; open loop the noise-free trajectory of
@@ -2675,13 +2734,13 @@ static rat_rc replay_centre(rat_handle h, double *centre) {
 // The state and control mean and covariance at every step under the nominal distribution q and under the worst-case distribution
 // p* ~ exp(theta* J) q, one row per kl_bound / theta as rat_policy_worst_case's rows: the replay above with the moment kernels of
 // policy_mc.hip behind each chunk; one enqueue chain, one host wait.
-extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
-                                                   double *rows_out, double *mean_out, double *cov_out) {
-    const std::string F = "rat_policy_worst_case_trajectory: ";
+// (rs.tail(): rat_policy_tail_trajectory -- the rows are CVaR levels, the weights the tail distribution's, the moment kernel the liveness
+// schedule's)
+static rat_rc replay_trajectory(rat_handle h, const std::string &F, const ReplaySpec &rs, double *rows_out, double *mean_out, double *cov_out) {
     rat_rc rc;
-    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && mean_out && cov_out))) return rc;
+    const bool tail = rs.tail();
     const rat_handle_s::McReplay rec = h->mc_rec;
-    const int n = h->n, m = h->m, N = h->N, nrows = n_bound + n_theta, d = n + m;
+    const int n = h->n, m = h->m, N = h->N, nrows = rs.nrows(), d = n + m;
     if ((long)nrows * (N + 1) > WT_MAX_ROWSTEPS)
         return fail(RAT_ERR_UNSUPPORTED, F + "rows x (N + 1) = " + std::to_string((long)nrows * (N + 1)) + " is above " +
                                          std::to_string(WT_MAX_ROWSTEPS) + " (64 MiB of partial sums): ask for fewer rows per call");
@@ -2697,14 +2756,19 @@ extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *k
     memset(&ta, 0, sizeof(ta));
     ta.centre = h->d_wt_out; ta.part = h->d_wt_part;
     ta.mean = h->d_wt_out + o_mean; ta.cov = h->d_wt_out + o_cov; ta.ess = h->d_wt_out + o_ess;
-    if ((rc = replay_chunks(h, kl_bound, n_bound, theta, n_theta, reinterpret_cast<int *>(h->d_wt_out + o_cnt), ta,
-                            [&](const WtArgs &c, ReplayChunk) -> rat_rc { launch_wct_chunk(c, h->stream); return RAT_OK; })))
+    if ((rc = replay_chunks(h, rs, reinterpret_cast<int *>(h->d_wt_out + o_cnt), ta,
+                            [&](const WtArgs &c, ReplayChunk) -> rat_rc {
+                                if (tail && !h->tail_dense) launch_tlt_chunk(c, h->d_tl_live, h->stream);
+                                else launch_wct_chunk(c, h->stream);
+                                return RAT_OK;
+                            })))
         return rc;
     launch_wct_final(ta, h->stream);
     HIPCHK(hipGetLastError());
+    const ReplayRows rr = replay_rows(h, tail);
     double rows[WC_MAX_ROWS * WC_NSTAT], ess[WC_MAX_ROWS * 2];
     int bad = 0;
-    HIPCHK(hipMemcpyAsync(rows, h->d_wc_red + WC_O_ROWS, (size_t)nrows * WC_NSTAT * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(rows, rr.d_rows, (size_t)nrows * rr.nstat * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(ess, h->d_wt_out + o_ess, (size_t)nrows * 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(&bad, h->d_wt_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(mean_out, h->d_wt_out + o_mean, (size_t)nrows * (N + 1) * d * 8, hipMemcpyDeviceToHost, h->stream));
@@ -2714,25 +2778,43 @@ extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *k
     // the rows' effective sample size against the moment kernel's own S0^2 / sum y^2: two routes to one number (the rows' sums are centred,
     // these are not: 1e-6 relative is far above what either loses and far below any error of the weights)
     for (int r = 0; r < nrows; ++r) {
-        const double e_row = rows[r * WC_NSTAT + RAT_WC_ESS], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
+        const double e_row = rows[r * rr.nstat + rr.ess], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
         if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
             return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
                                      " is not the row's " + std::to_string(e_row));
     }
-    for (int i = 0; i < nrows * WC_NSTAT; ++i) rows_out[i] = rows[i];
+    for (int i = 0; i < nrows * rr.nstat; ++i) rows_out[i] = rows[i];
     return RAT_OK;
+}
+
+extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                                   double *rows_out, double *mean_out, double *cov_out) {
+    const std::string F = "rat_policy_worst_case_trajectory: ";
+    rat_rc rc;
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && mean_out && cov_out))) return rc;
+    return replay_trajectory(h, F, replay_kl(kl_bound, n_bound, theta, n_theta), rows_out, mean_out, cov_out);
+}
+
+// What the worst 1 - alpha of the rollouts look like: the same moments under the CVaR adversary's distribution -- the tail distribution of
+// rat_policy_tail_risk -- one row per level.  The same replay with that function's chain as the row source.
+extern "C" rat_rc rat_policy_tail_trajectory(rat_handle h, const double *alpha, int32_t n_alpha, double *rows_out, double *mean_out, double *cov_out) {
+    const std::string F = "rat_policy_tail_trajectory: ";
+    rat_rc rc;
+    if ((rc = replay_validate_alpha(F, alpha, n_alpha, rows_out && mean_out && cov_out))) return rc;
+    if ((rc = replay_validate_handle(h, F, "rat_policy_tail_risk"))) return rc;
+    return replay_trajectory(h, F, replay_tail(alpha, n_alpha), rows_out, mean_out, cov_out);
 }
 
 // What the adversary does to the noise: the mean and covariance of the disturbance w_t at every step, and its covariance with the
 // (x_t, u_t) it acts on, under q and under p* ~ exp(theta* J) q, one row per kl_bound / theta.  The trajectory call's replay with the
 // rollouts keeping w_t (d_mc_wo) and wcd_moments behind each chunk; one enqueue chain, one host wait.
-extern "C" rat_rc rat_policy_worst_case_disturbance(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
-                                                    double *rows_out, double *mean_w_out, double *cov_w_out, double *cov_wz_out) {
-    const std::string F = "rat_policy_worst_case_disturbance: ";
+// (rs.tail(): rat_policy_tail_disturbance, as replay_trajectory serves rat_policy_tail_trajectory)
+static rat_rc replay_disturbance(rat_handle h, const std::string &F, const ReplaySpec &rs, double *rows_out, double *mean_w_out, double *cov_w_out,
+                                 double *cov_wz_out) {
     rat_rc rc;
-    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && mean_w_out && cov_w_out))) return rc;
+    const bool tail = rs.tail();
     const rat_handle_s::McReplay rec = h->mc_rec;
-    const int n = h->n, m = h->m, N = h->N, nrows = n_bound + n_theta, d = n + m;
+    const int n = h->n, m = h->m, N = h->N, nrows = rs.nrows(), d = n + m;
     if ((long)nrows * N > WD_MAX_ROWSTEPS)
         return fail(RAT_ERR_UNSUPPORTED, F + "rows x N = " + std::to_string((long)nrows * N) + " is above " +
                                          std::to_string(WD_MAX_ROWSTEPS) + " (64 MiB of partial sums): ask for fewer rows per call");
@@ -2740,10 +2822,10 @@ extern "C" rat_rc rat_policy_worst_case_disturbance(rat_handle h, const double *
     const int64_t K = rec.K, chunk = mc_chunk(K);
     const bool cross = cov_wz_out != nullptr;
     const int ldw = (h->pb.model == RAT_MODEL_SOURCE) ? n : XSTR;     // (the leading dimension of the staged x)
-    const size_t rs = (size_t)nrows * N;
-    const size_t o_cw = (size_t)(N + 1) * 16, o_mean = o_cw + (size_t)N * 16, o_cov = o_mean + rs * n, o_wz = o_cov + rs * n * n,
-                 o_ess = o_wz + (cross ? rs * n * d : 0), o_cnt = o_ess + 2 * (size_t)nrows, n_out = o_cnt + 1,
-                 n_part = rs * WT_SLOTS * WD_PART;
+    const size_t nrs = (size_t)nrows * N;                             // (rows x steps)
+    const size_t o_cw = (size_t)(N + 1) * 16, o_mean = o_cw + (size_t)N * 16, o_cov = o_mean + nrs * n, o_wz = o_cov + nrs * n * n,
+                 o_ess = o_wz + (cross ? nrs * n * d : 0), o_cnt = o_ess + 2 * (size_t)nrows, n_out = o_cnt + 1,
+                 n_part = nrs * WT_SLOTS * WD_PART;
     if ((rc = grow(&h->d_wd_part, &h->cap_wd_part, n_part))) return rc;
     if ((rc = grow(&h->d_wd_out, &h->cap_wd_out, n_out))) return rc;
     if ((rc = grow(&h->d_mc_wo, &h->cap_mc_wo, (size_t)chunk * N * ldw))) return rc;
@@ -2755,57 +2837,82 @@ extern "C" rat_rc rat_policy_worst_case_disturbance(rat_handle h, const double *
     da.ws = h->d_mc_wo; da.ldw = ldw; da.cross = cross ? 1 : 0; da.cw = h->d_wd_out + o_cw; da.part = h->d_wd_part;
     da.mean_w = h->d_wd_out + o_mean; da.cov_w = h->d_wd_out + o_cov; da.cov_wz = cross ? h->d_wd_out + o_wz : nullptr;
     da.ess = h->d_wd_out + o_ess;
-    if ((rc = replay_chunks(h, kl_bound, n_bound, theta, n_theta, reinterpret_cast<int *>(h->d_wd_out + o_cnt), da.t,
+    if ((rc = replay_chunks(h, rs, reinterpret_cast<int *>(h->d_wd_out + o_cnt), da.t,
                             [&](const WtArgs &, ReplayChunk c) -> rat_rc {
                                 if (c.k0 == 0) launch_wcd_centre(da, h->stream);   // c_w: fixed before the first chunk's sums
-                                launch_wcd_chunk(da, h->stream);
+                                if (tail && !h->tail_dense) launch_tld_chunk(da, h->d_tl_live, h->stream);
+                                else launch_wcd_chunk(da, h->stream);
                                 return RAT_OK;
                             }, h->d_mc_wo)))
         return rc;
     launch_wcd_final(da, h->stream);
     HIPCHK(hipGetLastError());
+    const ReplayRows rr = replay_rows(h, tail);
     double rows[WC_MAX_ROWS * WC_NSTAT], ess[WC_MAX_ROWS * 2];
     int bad = 0;
-    HIPCHK(hipMemcpyAsync(rows, h->d_wc_red + WC_O_ROWS, (size_t)nrows * WC_NSTAT * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(rows, rr.d_rows, (size_t)nrows * rr.nstat * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(ess, h->d_wd_out + o_ess, (size_t)nrows * 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(&bad, h->d_wd_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(mean_w_out, h->d_wd_out + o_mean, rs * n * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(cov_w_out, h->d_wd_out + o_cov, rs * n * n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (cross) HIPCHK(hipMemcpyAsync(cov_wz_out, h->d_wd_out + o_wz, rs * n * d * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(mean_w_out, h->d_wd_out + o_mean, nrs * n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(cov_w_out, h->d_wd_out + o_cov, nrs * n * n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (cross) HIPCHK(hipMemcpyAsync(cov_wz_out, h->d_wd_out + o_wz, nrs * n * d * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if ((rc = replay_mismatch(F, bad, K))) return rc;
     // the rows' effective sample size against the moment kernel's own, as rat_policy_worst_case_trajectory holds it
     for (int r = 0; r < nrows; ++r) {
-        const double e_row = rows[r * WC_NSTAT + RAT_WC_ESS], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
+        const double e_row = rows[r * rr.nstat + rr.ess], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
         if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
             return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
                                      " is not the row's " + std::to_string(e_row));
     }
-    for (int i = 0; i < nrows * WC_NSTAT; ++i) rows_out[i] = rows[i];
+    for (int i = 0; i < nrows * rr.nstat; ++i) rows_out[i] = rows[i];
     return RAT_OK;
+}
+
+extern "C" rat_rc rat_policy_worst_case_disturbance(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                                    double *rows_out, double *mean_w_out, double *cov_w_out, double *cov_wz_out) {
+    const std::string F = "rat_policy_worst_case_disturbance: ";
+    rat_rc rc;
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && mean_w_out && cov_w_out))) return rc;
+    return replay_disturbance(h, F, replay_kl(kl_bound, n_bound, theta, n_theta), rows_out, mean_w_out, cov_w_out, cov_wz_out);
+}
+
+// What the noise of the worst 1 - alpha of the rollouts looks like: the same moments under the tail distribution of each level
+extern "C" rat_rc rat_policy_tail_disturbance(rat_handle h, const double *alpha, int32_t n_alpha, double *rows_out, double *mean_w_out,
+                                              double *cov_w_out, double *cov_wz_out) {
+    const std::string F = "rat_policy_tail_disturbance: ";
+    rat_rc rc;
+    if ((rc = replay_validate_alpha(F, alpha, n_alpha, rows_out && mean_w_out && cov_w_out))) return rc;
+    if ((rc = replay_validate_handle(h, F, "rat_policy_tail_risk"))) return rc;
+    return replay_disturbance(h, F, replay_tail(alpha, n_alpha), rows_out, mean_w_out, cov_w_out, cov_wz_out);
 }
 
 // What the adversary picks among the model's uncertain parameters: the mean and covariance of the rollouts' drawn parameters q
 // (rat_user_params) and their covariance with the cost, under q's own distribution and under p* ~ exp(theta* J) q, one row per kl_bound /
 // theta.  The trajectory call's replay; behind each chunk the SRC_PARAMS kernel forms the chunk's q again from the rollout index and the
 // evaluation's seed (or the handle's injected streams) into d_wp_q, then wcp_moments; one enqueue chain, one host wait.
-extern "C" rat_rc rat_policy_worst_case_params(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
-                                               double *rows_out, double *mean_q_out, double *cov_q_out, double *cov_qJ_out) {
-    const std::string F = "rat_policy_worst_case_params: ";
-    rat_rc rc;
+// what either parameter call refuses before the row arguments are looked at
+static rat_rc replay_params_ready(rat_handle h, const std::string &F) {
     if (!h) return fail(RAT_ERR_ARG, F + "null handle");
     if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
     if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
         return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_params)");
     if (!h->ps_on)
         return fail(RAT_ERR_ARG, F + "parameter sampling is off: call rat_policy_params_sampling, then rat_policy_evaluate_noise, first");
-    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && mean_q_out && cov_q_out))) return rc;
+    return RAT_OK;
+}
+
+// (rs.tail(): rat_policy_tail_params, as replay_trajectory serves rat_policy_tail_trajectory; fn: the call's name)
+static rat_rc replay_params(rat_handle h, const std::string &F, const char *fn, const ReplaySpec &rs, double *rows_out, double *mean_q_out,
+                            double *cov_q_out, double *cov_qJ_out) {
+    rat_rc rc;
+    const bool tail = rs.tail();
     const rat_handle_s::McReplay rec = h->mc_rec;
-    const int nrows = n_bound + n_theta, P = (int)h->src_np;          // (1 .. 32: rat_policy_params_sampling accepted it)
+    const int nrows = rs.nrows(), P = (int)h->src_np;   // (1 .. 32: rat_policy_params_sampling accepted it)
     HIPCHK(hipSetDevice(h->device));
     hipFunction_t kq = nullptr;
     int *d_over = nullptr;
-    if ((rc = src_kernel(h, SRC_PARAMS, SrcShape(), "rat_policy_worst_case_params", &kq))) return rc;
+    if ((rc = src_kernel(h, SRC_PARAMS, SrcShape(), fn, &kq))) return rc;
     if ((rc = overdraw_flag(&h->h_un_over, F, &d_over))) return rc;
     const int64_t K = rec.K, chunk = mc_chunk(K);
     const bool cross = cov_qJ_out != nullptr;
@@ -2821,22 +2928,24 @@ extern "C" rat_rc rat_policy_worst_case_params(rat_handle h, const double *kl_bo
     pa.qs = h->d_wp_q; pa.P = P; pa.cross = cross ? 1 : 0; pa.centre = h->d_wp_out; pa.part = h->d_wp_part;
     pa.mean_q = h->d_wp_out + o_mean; pa.cov_q = h->d_wp_out + o_cov; pa.cov_qJ = cross ? h->d_wp_out + o_qJ : nullptr;
     pa.ess = h->d_wp_out + o_ess;
-    if ((rc = replay_chunks(h, kl_bound, n_bound, theta, n_theta, reinterpret_cast<int *>(h->d_wp_out + o_cnt), pa.t,
+    if ((rc = replay_chunks(h, rs, reinterpret_cast<int *>(h->d_wp_out + o_cnt), pa.t,
                             [&](const WtArgs &, ReplayChunk c) -> rat_rc {
                                 SrcParamsArgs sa;                     // the q the chunk's rollouts used: the same index, seed and streams
                                 sa.p = h->d_src_p; sa.zpn = h->d_ps_zn; sa.zpu = h->d_ps_zu; sa.seed = rec.seed; sa.K = (long)c.kc;
                                 sa.j0 = (long)c.k0; sa.q_out = h->d_wp_q; sa.overdraw = d_over;
                                 HIPCHK(launch_src(kq, c.kc, 64, h->stream, &sa));
                                 if (c.k0 == 0) launch_wcp_centre(pa, h->stream);   // c_q, c_J: fixed before the first chunk's sums
-                                launch_wcp_chunk(pa, h->stream);
+                                if (tail && !h->tail_dense) launch_tlp_chunk(pa, h->d_tl_live, h->stream);
+                                else launch_wcp_chunk(pa, h->stream);
                                 return RAT_OK;
                             })))
         return rc;
     launch_wcp_final(pa, h->stream);
     HIPCHK(hipGetLastError());
+    const ReplayRows rr = replay_rows(h, tail);
     double rows[WC_MAX_ROWS * WC_NSTAT], ess[WC_MAX_ROWS * 4];
     int bad = 0;
-    HIPCHK(hipMemcpyAsync(rows, h->d_wc_red + WC_O_ROWS, (size_t)nrows * WC_NSTAT * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(rows, rr.d_rows, (size_t)nrows * rr.nstat * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(ess, h->d_wp_out + o_ess, (size_t)nrows * 32, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(&bad, h->d_wp_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(mean_q_out, h->d_wp_out + o_mean, (size_t)nrows * P * 8, hipMemcpyDeviceToHost, h->stream));
@@ -2846,13 +2955,34 @@ extern "C" rat_rc rat_policy_worst_case_params(rat_handle h, const double *kl_bo
     if ((rc = replay_mismatch(F, bad, K))) return rc;
     // the rows' effective sample size against the moment kernel's own, as rat_policy_worst_case_trajectory holds it
     for (int r = 0; r < nrows; ++r) {
-        const double e_row = rows[r * WC_NSTAT + RAT_WC_ESS], e_mom = ess[4 * r] * ess[4 * r] / ess[4 * r + 1];
+        const double e_row = rows[r * rr.nstat + rr.ess], e_mom = ess[4 * r] * ess[4 * r] / ess[4 * r + 1];
         if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
             return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
                                      " is not the row's " + std::to_string(e_row));
     }
-    for (int i = 0; i < nrows * WC_NSTAT; ++i) rows_out[i] = rows[i];
+    for (int i = 0; i < nrows * rr.nstat; ++i) rows_out[i] = rows[i];
     return RAT_OK;
+}
+
+extern "C" rat_rc rat_policy_worst_case_params(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                               double *rows_out, double *mean_q_out, double *cov_q_out, double *cov_qJ_out) {
+    const std::string F = "rat_policy_worst_case_params: ";
+    rat_rc rc;
+    if ((rc = replay_params_ready(h, F))) return rc;
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && mean_q_out && cov_q_out))) return rc;
+    return replay_params(h, F, "rat_policy_worst_case_params", replay_kl(kl_bound, n_bound, theta, n_theta), rows_out, mean_q_out, cov_q_out,
+                         cov_qJ_out);
+}
+
+// Which parameters the worst 1 - alpha of the rollouts drew: the same moments under the tail distribution of each level
+extern "C" rat_rc rat_policy_tail_params(rat_handle h, const double *alpha, int32_t n_alpha, double *rows_out, double *mean_q_out,
+                                         double *cov_q_out, double *cov_qJ_out) {
+    const std::string F = "rat_policy_tail_params: ";
+    rat_rc rc;
+    if ((rc = replay_validate_alpha(F, alpha, n_alpha, rows_out && mean_q_out && cov_q_out))) return rc;
+    if ((rc = replay_params_ready(h, F))) return rc;
+    if ((rc = replay_validate_handle(h, F, "rat_policy_tail_risk"))) return rc;
+    return replay_params(h, F, "rat_policy_tail_params", replay_tail(alpha, n_alpha), rows_out, mean_q_out, cov_q_out, cov_qJ_out);
 }
 
 // p' log(p' / p) + (1 - p') log((1 - p') / (1 - p)) for p <= p' < 1, 0 < p < 1, both logarithms through log1p of the difference: near
@@ -2922,7 +3052,7 @@ static rat_rc events_run(rat_handle h, const std::string &F, int n_event, const 
     ea.event_out = h->d_ev_out + o_ev; ea.step_out = h->d_ev_out + o_step;
     WtArgs ta;
     memset(&ta, 0, sizeof(ta));
-    if ((rc = replay_chunks(h, kl_bound, n_bound, theta, n_theta, reinterpret_cast<int *>(h->d_ev_out + o_cnt), ta,
+    if ((rc = replay_chunks(h, replay_kl(kl_bound, n_bound, theta, n_theta), reinterpret_cast<int *>(h->d_ev_out + o_cnt), ta,
                             [&](const WtArgs &c, ReplayChunk ch) -> rat_rc {
                                 ea.xs = c.xs; ea.us = c.us; ea.ldx = c.ldx; ea.ldu = c.ldu; ea.n = c.n; ea.m = c.m; ea.N = c.N; ea.kc = c.kc; ea.cost = c.cost;
                                 ea.ldy = c.ldy; ea.nrows = c.nrows; ea.y = c.y; ea.wc = c.wc; ea.first = ch.k0 == 0;

@@ -212,6 +212,27 @@ void launch_wcp_centre(const WpArgs &a, hipStream_t s);
 void launch_wcp_chunk(const WpArgs &a, hipStream_t s);
 void launch_wcp_final(const WpArgs &a, hipStream_t s);
 
+// ---- rat_policy_tail_trajectory / _disturbance / _params: the same moments under the CVaR adversary, one row per level (policy_mc.hip) ------
+// The rows are rat_policy_tail_risk's (launch_policy_tr on the stored costs); the weights are tr_weights' rule up to the common factor
+// 1 / tail, which the moment kernels divide out through S0: y = 1 above the level's quantile v, y_eq on it, 0 below and for a DomainError
+// rollout.  tlt_levels, behind the tail-risk chain, writes every level's (v, y_eq, state) where the worst-case kernels keep a row's
+// (theta, state) -- a scratch of launch_policy_wc's size, WtArgs::wc -- so that wct_final / wcd_final / wcp_final serve unchanged; a level
+// thinner than one rollout is v = Jmax, y_eq = 1.  tlt_weights is wct_weights' counterpart and also writes, per group of four rollouts,
+// one word whose bit r says "some y of level r in this group is not zero".  tlt_moments / tld_moments / tlp_moments are wct_moments /
+// wcd_moments / wcp_moments with that word read first (the bodies are shared; the worst-case instantiations are compiled as before): a
+// wavefront issues nothing for a row its group is dead in, loads nothing for a group dead in every row of the workgroup, and selects a
+// rollout without weight in a row out of that row's operands.  Adding 0 D to a sum changes no bit where D is finite, so on finite data
+// the two schedules agree bit for bit; a rollout without weight that holds Inf or NaN is left out, where the dense schedule forms 0 Inf.
+#define TL_O_YEQ WC_O_ROWS    /* y_eq of level r at wc[TL_O_YEQ + r]; v and the state at wc[WC_O_INFO + 2 r], + 1 (WC_ST_SEARCH: live) */
+// behind launch_policy_tr(a, s): the levels of a (its scratch) into wc [WC_SCRATCH]
+void launch_tlt_levels(const TrArgs &a, double *wc, hipStream_t s);
+// one chunk: the weights of its rollouts per level, the replay check and the liveness words live [(kc + 3) / 4] (a.wc: tlt_levels' output)
+void launch_tlt_weights(const WtArgs &a, unsigned *live, hipStream_t s);
+// ... then, behind it, the chunk's sums into the partials: launch_wct_chunk / launch_wcd_chunk / launch_wcp_chunk with the liveness schedule
+void launch_tlt_chunk(const WtArgs &a, const unsigned *live, hipStream_t s);
+void launch_tld_chunk(const WdArgs &a, const unsigned *live, hipStream_t s);
+void launch_tlp_chunk(const WpArgs &a, const unsigned *live, hipStream_t s);
+
 // ---- rat_policy_events: how often a policy violates quadratic constraints, under q and under every row's tilt (policy_mc.hip) ---------------
 // An event is g(t, z) = z' Q z + a' z + b of z = (x_t, u_t) in the 12 + 4 tile, watched over the steps t_lo .. t_hi.  Behind each replayed
 // chunk (after wct_weights) ev_eval forms, per rollout and event, the margin M = max g over the window, the first step tau with g > 0 and

@@ -754,7 +754,69 @@ __global__ __launch_bounds__(MC_THREADS) void wct_weights(WtArgs a) {
     if (bad) atomicAdd(a.mismatch, bad);
 }
 
-__global__ __launch_bounds__(WT_WAVES * 64) void wct_moments(WtArgs a) {
+// ---- the tail calls' rows: every level's (v, y_eq, state) behind the tail-risk chain, then the weights and the liveness words per chunk ----
+// tlt_levels repeats tr_rows' second level of the sums and its arithmetic for the atom -- the same partials in the same tree, so y_eq is
+// the w_eq tail of TR_O_AUX bit for bit at level 0 -- for every level, and writes them where the worst-case kernels keep (theta, state).
+__global__ __launch_bounds__(MC_THREADS) void tlt_levels(TrArgs a, double *wc) {
+    __shared__ double sh[TR_NSUM * MC_THREADS];
+    const TrHead h = tr_head(a.scratch, sh);
+    const double n = h.n;
+    for (int r = 0; r < a.n_alpha; ++r) {
+        double q[TR_NSUM] = {0.0, 0.0, 0.0, 0.0};
+        if (h.live) {
+#pragma unroll
+            for (int i = 0; i < TR_NSUM; ++i) q[i] = a.scratch[TR_O_PS + (r * TR_NSUM + i) * MC_BLOCKS + threadIdx.x];
+        }
+        block_tree_n<TR_NSUM>(q, sh);
+        if (threadIdx.x != 0) continue;
+        double v = 0.0, ye = 0.0, st = (h.flag == 2.0) ? WC_ST_EMPTY : WC_ST_NONFINITE;
+        if (h.live) {
+            const double cgt = q[2], ceq = q[3];
+            const double av = tr_prod(n, a.alpha[r]), tail = n - av, k = tr_rank(n, av);
+            v = tr_value(tr_gpfx(a.scratch)[TR_PASSES * TR_MAX_ALPHA + r]);
+            if (tail < 1.0) ye = 1.0;                                 // thinner than one rollout: v = Jmax, the weight on the rollouts that reach it
+            else { const double frac = k - av, ra = (n - k - cgt) + frac; ye = ra / ceq; }
+            st = WC_ST_SEARCH;
+        }
+        wc[WC_O_INFO + 2 * r] = v; wc[WC_O_INFO + 2 * r + 1] = st; wc[TL_O_YEQ + r] = ye;
+    }
+}
+
+// Lane q of a wavefront takes rollout q; the four lanes of a group combine their rows' "y != 0" bits by two exchanges within the group
+// (the loop runs over whole groups, so the four are in it together) and the first writes the word.
+__global__ __launch_bounds__(MC_THREADS) void tlt_weights(WtArgs a, unsigned *lv) {
+    const long T = (long)gridDim.x * MC_THREADS, kc4 = (a.kc + 3) & ~3l;
+    int bad = 0;
+    for (long q = (long)blockIdx.x * MC_THREADS + threadIdx.x; q < kc4; q += T) {
+        const bool in = q < a.kc;                                     // (the K tail: no cost, no weight, no bit)
+        const double J = in ? a.cost[q] : __builtin_nan("");
+        if (in) {
+            double Jr = a.cost_re[q];
+            if (a.dom_re && a.dom_re[q]) Jr = __builtin_nan("");
+            const bool same = (mc_nan(J) && mc_nan(Jr)) || __double_as_longlong(J) == __double_as_longlong(Jr);
+            bad += same ? 0 : 1;
+        }
+        unsigned bits = 0u;
+        for (int r = 0; r < a.nrows; ++r) {
+            const double v = a.wc[WC_O_INFO + 2 * r], st = a.wc[WC_O_INFO + 2 * r + 1], ye = a.wc[TL_O_YEQ + r];
+            double y = 0.0;                                           // (a DomainError rollout, an empty or non-finite sample: no weight)
+            if (!mc_nan(J) && st == WC_ST_SEARCH) y = (J > v) ? 1.0 : (J == v) ? ye : 0.0;
+            if (in) a.y[(long)r * a.ldy + q] = y;
+            bits |= (y != 0.0) ? (1u << r) : 0u;
+        }
+        bits |= (unsigned)__shfl_xor((int)bits, 1);
+        bits |= (unsigned)__shfl_xor((int)bits, 2);
+        if ((q & 3) == 0) lv[q >> 2] = bits;
+    }
+    if (bad) atomicAdd(a.mismatch, bad);
+}
+
+// The body of wct_moments (TAIL = false) and of tlt_moments (TAIL = true: the liveness schedule of the tail calls, policy_mc.h).  With
+// TAIL the wavefront reads its group's liveness word first -- wave-uniform, a group is one wavefront's work, so the tests are scalar
+// branches -- skips a group dead in every row of the workgroup before any load, issues nothing for a row the group is dead in, and
+// selects a rollout without weight in a row out of both operands of that row's product.
+template <bool TAIL>
+__device__ __forceinline__ void wct_moments_body(const WtArgs &a, const unsigned *lv) {
     __shared__ double sh[WT_WAVES][WT_SH];
     const int slot = blockIdx.x, t = blockIdx.y, r0 = blockIdx.z * WT_ROWS;
     const int nr = (a.nrows - r0 < WT_ROWS) ? a.nrows - r0 : WT_ROWS;
@@ -769,6 +831,11 @@ __global__ __launch_bounds__(WT_WAVES * 64) void wct_moments(WtArgs a) {
     for (int r = 0; r < WT_ROWS; ++r) { acc[r] = (wt_d4){0.0, 0.0, 0.0, 0.0}; s1[r] = 0.0; s0[r] = 0.0; sy2[r] = 0.0; }
     const long G = (a.kc + 3) >> 2;
     for (long g = (long)slot * WT_WAVES + w; g < G; g += (long)WT_SLOTS * WT_WAVES) {      // (uniform over the wavefront)
+        unsigned on = 0xffu;
+        if (TAIL) {
+            on = (unsigned)__builtin_amdgcn_readfirstlane((int)((lv[g] >> r0) & 0xffu));
+            if (on == 0u) continue;                                   // dead in every row of the workgroup: nothing is loaded
+        }
         const long q = 4 * g + kk;
         const bool live = q < a.kc;                                   // (the K tail)
         const double J = live ? a.cost[q] : 0.0;
@@ -777,10 +844,11 @@ __global__ __launch_bounds__(WT_WAVES * 64) void wct_moments(WtArgs a) {
         if (ok && comp) D = (isx ? a.xs[(q * (N + 1) + t) * a.ldx + i] : a.us[(q * N + t) * a.ldu + (i - 12)]) - c;
 #pragma unroll
         for (int r = 0; r < WT_ROWS; ++r) {
-            if (r < nr) {                                             // (uniform over the workgroup)
+            if (r < nr && (!TAIL || ((on >> r) & 1u))) {              // (uniform over the workgroup; with TAIL over the wavefront)
                 const double y = ok ? a.y[(long)(r0 + r) * a.ldy + q] : 0.0;
-                const double yd = y * D;
-                acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd, D, acc[r], 0, 0, 0);
+                const bool has = !TAIL || y != 0.0;
+                const double Dr = has ? D : 0.0, yd = has ? y * D : 0.0;
+                acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd, Dr, acc[r], 0, 0, 0);
                 s1[r] += yd; s0[r] += y; sy2[r] += y * y;
             }
         }
@@ -811,6 +879,9 @@ __global__ __launch_bounds__(WT_WAVES * 64) void wct_moments(WtArgs a) {
         }
     }
 }
+
+__global__ __launch_bounds__(WT_WAVES * 64) void wct_moments(WtArgs a) { wct_moments_body<false>(a, nullptr); }
+__global__ __launch_bounds__(WT_WAVES * 64) void tlt_moments(WtArgs a, const unsigned *live) { wct_moments_body<true>(a, live); }
 
 __global__ __launch_bounds__(MC_THREADS) void wct_final(WtArgs a) {
     __shared__ double S[WT_PART];
@@ -867,8 +938,8 @@ __global__ __launch_bounds__(MC_THREADS) void wcd_centre(WdArgs a) {
     }
 }
 
-template <bool CROSS>
-__global__ __launch_bounds__(WT_WAVES * 64) void wcd_moments(WdArgs a) {
+template <bool CROSS, bool TAIL>                                     // (TAIL: the liveness schedule, as wct_moments_body has it)
+__device__ __forceinline__ void wcd_moments_body(const WdArgs &a, const unsigned *lv) {
     __shared__ double sh[WT_WAVES][WD_SH];
     const int slot = blockIdx.x, t = blockIdx.y, r0 = blockIdx.z * WT_ROWS;
     const int nrows = a.t.nrows, N = a.t.N;
@@ -887,6 +958,11 @@ __global__ __launch_bounds__(WT_WAVES * 64) void wcd_moments(WdArgs a) {
     }
     const long kc = a.t.kc, G = (kc + 3) >> 2;
     for (long g = (long)slot * WT_WAVES + w; g < G; g += (long)WT_SLOTS * WT_WAVES) {      // (uniform over the wavefront)
+        unsigned on = 0xffu;
+        if (TAIL) {
+            on = (unsigned)__builtin_amdgcn_readfirstlane((int)((lv[g] >> r0) & 0xffu));
+            if (on == 0u) continue;                                   // dead in every row of the workgroup: nothing is loaded
+        }
         const long q = 4 * g + kk;
         const bool live = q < kc;                                     // (the K tail)
         const double J = live ? a.t.cost[q] : 0.0;
@@ -896,13 +972,15 @@ __global__ __launch_bounds__(WT_WAVES * 64) void wcd_moments(WdArgs a) {
         if (CROSS && ok && compz) Dz = (isx ? a.t.xs[(q * (N + 1) + t) * a.t.ldx + i] : a.t.us[(q * N + t) * a.t.ldu + (i - 12)]) - cz;
 #pragma unroll
         for (int r = 0; r < WT_ROWS; ++r) {
-            if (r < nr) {                                             // (uniform over the workgroup)
+            if (r < nr && (!TAIL || ((on >> r) & 1u))) {              // (uniform over the workgroup; with TAIL over the wavefront)
                 const double y = ok ? a.t.y[(long)(r0 + r) * a.t.ldy + q] : 0.0;
-                const double yd = y * Dw;
-                aww[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd, Dw, aww[r], 0, 0, 0);
+                const bool has = !TAIL || y != 0.0;
+                const double Dwr = has ? Dw : 0.0, yd = has ? y * Dw : 0.0;
+                aww[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd, Dwr, aww[r], 0, 0, 0);
                 if (CROSS) {
-                    awz[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd, Dz, awz[r], 0, 0, 0);
-                    s1z[r] += y * Dz;
+                    const double Dzr = has ? Dz : 0.0;
+                    awz[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd, Dzr, awz[r], 0, 0, 0);
+                    s1z[r] += has ? y * Dz : 0.0;
                 }
                 s1w[r] += yd; s0[r] += y; sy2[r] += y * y;
             }
@@ -949,6 +1027,11 @@ __global__ __launch_bounds__(WT_WAVES * 64) void wcd_moments(WdArgs a) {
         }
     }
 }
+
+template <bool CROSS>
+__global__ __launch_bounds__(WT_WAVES * 64) void wcd_moments(WdArgs a) { wcd_moments_body<CROSS, false>(a, nullptr); }
+template <bool CROSS>
+__global__ __launch_bounds__(WT_WAVES * 64) void tld_moments(WdArgs a, const unsigned *live) { wcd_moments_body<CROSS, true>(a, live); }
 
 __global__ __launch_bounds__(MC_THREADS) void wcd_final(WdArgs a) {
     __shared__ double S[WD_PART];
@@ -1007,8 +1090,8 @@ __global__ __launch_bounds__(MC_THREADS) void wcp_centre(WpArgs a) {
     }
 }
 
-template <bool TWO, bool CROSS>
-__global__ __launch_bounds__(WT_WAVES * 64) void wcp_moments(WpArgs a) {
+template <bool TWO, bool CROSS, bool TAIL>                           // (TAIL: the liveness schedule, as wct_moments_body has it)
+__device__ __forceinline__ void wcp_moments_body(const WpArgs &a, const unsigned *lv) {
     __shared__ double sh[WT_WAVES][WP_SH];
     const int slot = blockIdx.x, r0 = blockIdx.y * WT_ROWS;
     const int nrows = a.t.nrows, P = a.P;
@@ -1025,6 +1108,11 @@ __global__ __launch_bounds__(WT_WAVES * 64) void wcp_moments(WpArgs a) {
     }
     const long kc = a.t.kc, G = (kc + 3) >> 2;
     for (long g = (long)slot * WT_WAVES + w; g < G; g += (long)WT_SLOTS * WT_WAVES) {      // (uniform over the wavefront)
+        unsigned on = 0xffu;
+        if (TAIL) {
+            on = (unsigned)__builtin_amdgcn_readfirstlane((int)((lv[g] >> r0) & 0xffu));
+            if (on == 0u) continue;                                   // dead in every row of the workgroup: nothing is loaded
+        }
         const long q = 4 * g + kk;
         const bool live = q < kc;                                     // (the K tail)
         const double J = live ? a.t.cost[q] : 0.0;
@@ -1035,22 +1123,24 @@ __global__ __launch_bounds__(WT_WAVES * 64) void wcp_moments(WpArgs a) {
         const double DJ = (CROSS && ok) ? J - cJ : 0.0;
 #pragma unroll
         for (int r = 0; r < WT_ROWS; ++r) {
-            if (r < nr) {                                             // (uniform over the workgroup)
+            if (r < nr && (!TAIL || ((on >> r) & 1u))) {              // (uniform over the workgroup; with TAIL over the wavefront)
                 const double y = ok ? a.t.y[(long)(r0 + r) * a.t.ldy + q] : 0.0;
-                const double yd0 = y * D0;
-                a00[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd0, D0, a00[r], 0, 0, 0);
+                const bool has = !TAIL || y != 0.0;
+                const double D0r = has ? D0 : 0.0, yd0 = has ? y * D0 : 0.0;
+                a00[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd0, D0r, a00[r], 0, 0, 0);
                 s1a[r] += yd0;
+                const double D1r = (TWO && has) ? D1 : 0.0;
                 if (TWO) {
-                    const double yd1 = y * D1;
-                    a01[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd0, D1, a01[r], 0, 0, 0);
-                    a11[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd1, D1, a11[r], 0, 0, 0);
+                    const double yd1 = has ? y * D1 : 0.0;
+                    a01[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd0, D1r, a01[r], 0, 0, 0);
+                    a11[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd1, D1r, a11[r], 0, 0, 0);
                     s1b[r] += yd1;
                 }
                 s0[r] += y; sy2[r] += y * y;
                 if (CROSS) {
                     const double yj = y * DJ;
-                    sj[r] += yj; sj2[r] += yj * DJ; sqa[r] += yj * D0;
-                    if (TWO) sqb[r] += yj * D1;
+                    sj[r] += yj; sj2[r] += yj * DJ; sqa[r] += yj * D0r;
+                    if (TWO) sqb[r] += yj * D1r;
                 }
             }
         }
@@ -1097,6 +1187,11 @@ __global__ __launch_bounds__(WT_WAVES * 64) void wcp_moments(WpArgs a) {
         }
     }
 }
+
+template <bool TWO, bool CROSS>
+__global__ __launch_bounds__(WT_WAVES * 64) void wcp_moments(WpArgs a) { wcp_moments_body<TWO, CROSS, false>(a, nullptr); }
+template <bool TWO, bool CROSS>
+__global__ __launch_bounds__(WT_WAVES * 64) void tlp_moments(WpArgs a, const unsigned *live) { wcp_moments_body<TWO, CROSS, true>(a, live); }
 
 __global__ __launch_bounds__(MC_THREADS) void wcp_final(WpArgs a) {
 #pragma clang fp contract(off)                                        // S2 / S0 - m m' with m m' rounded: where one rollout carries all the weight the two are the same product, and the covariance is exactly 0
@@ -1390,6 +1485,40 @@ void launch_wcp_chunk(const WpArgs &a, hipStream_t s) {
 
 void launch_wcp_final(const WpArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(wcp_final, dim3((unsigned)a.t.nrows), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_tlt_levels(const TrArgs &a, double *wc, hipStream_t s) {
+    hipLaunchKernelGGL(tlt_levels, dim3(1), dim3(MC_THREADS), 0, s, a, wc);
+}
+
+void launch_tlt_weights(const WtArgs &a, unsigned *live, hipStream_t s) {
+    if (a.kc <= 0 || a.nrows <= 0) return;
+    const long nb = (a.kc + MC_THREADS - 1) / MC_THREADS;
+    hipLaunchKernelGGL(tlt_weights, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(MC_THREADS), 0, s, a, live);
+}
+
+void launch_tlt_chunk(const WtArgs &a, const unsigned *live, hipStream_t s) {
+    if (a.kc <= 0 || a.nrows <= 0) return;
+    hipLaunchKernelGGL(tlt_moments, dim3(WT_SLOTS, (unsigned)(a.N + 1), (unsigned)((a.nrows + WT_ROWS - 1) / WT_ROWS)), dim3(WT_WAVES * 64), 0, s, a, live);
+}
+
+void launch_tld_chunk(const WdArgs &a, const unsigned *live, hipStream_t s) {
+    if (a.t.kc <= 0) return;
+    const dim3 grid(WT_SLOTS, (unsigned)a.t.N, (unsigned)((a.t.nrows + WT_ROWS - 1) / WT_ROWS));
+    if (a.cross) hipLaunchKernelGGL(tld_moments<true>, grid, dim3(WT_WAVES * 64), 0, s, a, live);
+    else hipLaunchKernelGGL(tld_moments<false>, grid, dim3(WT_WAVES * 64), 0, s, a, live);
+}
+
+void launch_tlp_chunk(const WpArgs &a, const unsigned *live, hipStream_t s) {
+    if (a.t.kc <= 0) return;
+    const dim3 grid(WT_SLOTS, (unsigned)((a.t.nrows + WT_ROWS - 1) / WT_ROWS)), block(WT_WAVES * 64);
+    if (a.P > 16) {
+        if (a.cross) hipLaunchKernelGGL((tlp_moments<true, true>), grid, block, 0, s, a, live);
+        else hipLaunchKernelGGL((tlp_moments<true, false>), grid, block, 0, s, a, live);
+    } else {
+        if (a.cross) hipLaunchKernelGGL((tlp_moments<false, true>), grid, block, 0, s, a, live);
+        else hipLaunchKernelGGL((tlp_moments<false, false>), grid, block, 0, s, a, live);
+    }
 }
 
 void launch_ev_chunk(const EvArgs &a, hipStream_t s) {

@@ -202,6 +202,15 @@ class GenericContext(il.Context):
     def policy_tail_risk(self, *a, **k):
         self._carrier_only("policy_tail_risk")
 
+    def policy_tail_trajectory(self, *a, **k):
+        self._carrier_only("policy_tail_trajectory")
+
+    def policy_tail_disturbance(self, *a, **k):
+        self._carrier_only("policy_tail_disturbance")
+
+    def policy_tail_params(self, *a, **k):
+        self._carrier_only("policy_tail_params")
+
     def policy_events(self, *a, **k):
         self._carrier_only("policy_events")
 

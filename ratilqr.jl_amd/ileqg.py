@@ -455,6 +455,67 @@ class Context:
             return r
         return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)))
 
+    def _tail_rows(self, alphas):
+        al = nv.f64(np.atleast_1d(np.asarray(alphas, dtype=np.float64))).ravel()
+        return al, np.zeros((al.size, nv.TR_NSTAT))
+
+    @staticmethod
+    def _tail_part(rows):
+        r = {k: rows[:, i].copy() for i, k in enumerate(nv.TR_SLOTS)}
+        r["flag"] = r["flag"].astype(np.int64)
+        return r
+
+    def policy_tail_trajectory(self, alphas):
+        """What the tail looks like (rat_policy_tail_trajectory): the mean and covariance of the state and the control at every step over
+        the worst (1 - alpha) share of the rollouts -- the tail distribution of policy_tail_risk, the CVaR adversary's -- per level alpha in
+        [0, 1) (1 to 16 levels; alpha = 0 is the nominal distribution), formed on the device by replaying the last policy_evaluate /
+        policy_evaluate_noise of this context like policy_worst_case_trajectory.  Returns one dict: policy_tail_risk's row keys (alpha, var,
+        cvar, ..., flag) and, with R levels, mean_x (R, N+1, n), cov_x (R, N+1, n, n), mean_u (R, N, m), cov_u (R, N, m, m), cov_xu
+        (R, N, n, m), population form.  A saturated level holds the moments of the rollouts attaining the maximum; an empty or non-finite
+        sample gives NaN."""
+        al, rows = self._tail_rows(alphas)
+        n, m, N, R = self.n, self.m, self.N, al.size
+        mean, cov = np.zeros((R, N + 1, n + m)), np.zeros((R, N + 1, n + m, n + m))
+        nv.check(nv.lib().rat_policy_tail_trajectory(self.h, nv.P(al) if al.size else None, C.c_int32(al.size), nv.P(rows), nv.P(mean), nv.P(cov)))
+        cov = cov.transpose(0, 1, 3, 2)                               # (column-major blocks)
+        r = self._tail_part(rows)
+        r.update(mean_x=mean[:, :, :n].copy(), cov_x=cov[:, :, :n, :n].copy(), mean_u=mean[:, :N, n:].copy(),
+                 cov_u=cov[:, :N, n:, n:].copy(), cov_xu=cov[:, :N, :n, n:].copy())
+        return r
+
+    def policy_tail_disturbance(self, alphas, cross=True):
+        """What the noise of the tail looks like (rat_policy_tail_disturbance): policy_worst_case_disturbance's moments over the worst
+        (1 - alpha) share of the rollouts per level.  Returns one dict: policy_tail_risk's row keys and, with R levels, mean_w (R, N, n),
+        cov_w (R, N, n, n) and, with cross, cov_wx (R, N, n, n) and cov_wu (R, N, n, m)."""
+        al, rows = self._tail_rows(alphas)
+        n, m, N, R = self.n, self.m, self.N, al.size
+        mean, cov = np.zeros((R, N, n)), np.zeros((R, N, n, n))
+        wz = np.zeros((R, N, n + m, n)) if cross else None
+        nv.check(nv.lib().rat_policy_tail_disturbance(self.h, nv.P(al) if al.size else None, C.c_int32(al.size), nv.P(rows), nv.P(mean), nv.P(cov),
+                                                      nv.P(wz)))
+        r = self._tail_part(rows)
+        r.update(mean_w=mean, cov_w=cov.transpose(0, 1, 3, 2).copy())  # (column-major blocks)
+        if cross:
+            wz = wz.transpose(0, 1, 3, 2)                             # [R, N, n, n+m]
+            r.update(cov_wx=wz[:, :, :, :n].copy(), cov_wu=wz[:, :, :, n:].copy())
+        return r
+
+    def policy_tail_params(self, alphas, cost=True):
+        """Which parameters the tail drew (rat_policy_tail_params): policy_worst_case_params' moments over the worst (1 - alpha) share of
+        the rollouts per level.  Returns one dict: policy_tail_risk's row keys and, with R levels and P = n_params, mean_q (R, P), cov_q
+        (R, P, P) and, with cost, cov_qJ (R, P)."""
+        al, rows = self._tail_rows(alphas)
+        P, R = getattr(self, "params", np.zeros(0)).size, al.size
+        mean, cov = np.zeros((R, P)), np.zeros((R, P, P))
+        qJ = np.zeros((R, P)) if cost else None
+        nv.check(nv.lib().rat_policy_tail_params(self.h, nv.P(al) if al.size else None, C.c_int32(al.size), nv.P(rows), nv.P(mean), nv.P(cov),
+                                                 nv.P(qJ)))
+        r = self._tail_part(rows)
+        r.update(mean_q=mean, cov_q=cov.transpose(0, 2, 1).copy())    # (column-major blocks)
+        if cost:
+            r.update(cov_qJ=qJ)
+        return r
+
     def policy_events(self, events, kl_bounds=(), thetas=(), want_steps=False, want_margins=False):
         """How often the policy violates safety events (rat_policy_events): per event (halfspace, ball, quadratic_event; 1 to 16) and per
         row -- the worst-case distribution of each KL radius, the tilt of each theta; theta = 0 is the nominal distribution -- the
