@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -2622,7 +2623,7 @@ static rat_rc replay_validate_handle(rat_handle h, const std::string &F, const c
     return RAT_OK;
 }
 
-struct ReplayChunk { int64_t k0, kc; };
+struct ReplayChunk { int64_t k0, kc; const unsigned *live; };       // live: the chunk's liveness words, or null for the dense moment kernels
 
 // The replay itself, after replay_validate: grows the staging buffers, enqueues rat_policy_worst_case's chain on the stored costs (theta*,
 // Jmax and the rows: d_wc_red), then chunk by chunk the rollouts into d_mc_xo / d_mc_uo / d_wt_cost (/ d_wt_dom) and wct_weights into
@@ -2632,7 +2633,8 @@ struct ReplayChunk { int64_t k0, kc; };
 // the rollouts keep the chunk's disturbances there, [kc][N][ldx].
 // The second row source (rs.tail(): the tail calls): rat_policy_tail_risk's chain on the stored costs (the
 // rows: d_tr_red) with tlt_levels behind it, which leaves every level's quantile, atom weight and state in d_wc_red where the worst-case
-// chain leaves a row's theta and state, and per chunk tlt_weights, which also writes the chunk's liveness words into d_tl_live.
+// chain leaves a row's theta and state, and per chunk tlt_weights, which also writes the chunk's liveness words into d_tl_live; the
+// chunk handed to behind carries them, unless the switch tail_dense asks for the dense moment kernels on the same weights.
 template <class Behind>
 static rat_rc replay_chunks(rat_handle h, const ReplaySpec &rs, int *d_mismatch, WtArgs &ta, Behind &&behind, double *d_wo = nullptr) {
     const rat_handle_s::McReplay rec = h->mc_rec;
@@ -2683,6 +2685,7 @@ static rat_rc replay_chunks(rat_handle h, const ReplaySpec &rs, int *d_mismatch,
     ta.xs = h->d_mc_xo; ta.us = h->d_mc_uo; ta.ldx = ldx; ta.ldu = ldu; ta.n = n; ta.m = m; ta.N = N;
     ta.cost_re = h->d_wt_cost; ta.dom_re = source ? nullptr : h->d_wt_dom; ta.nrows = nrows; ta.wc = h->d_wc_red; ta.y = h->d_wt_y; ta.ldy = (long)chunk;
     ta.mismatch = d_mismatch;
+    const unsigned *live = (tail && !h->tail_dense) ? h->d_tl_live : nullptr;
     for (int64_t k0 = 0; k0 < K; k0 += chunk) {
         const int64_t kc = std::min(chunk, K - k0);
         if (source) {
@@ -2693,7 +2696,7 @@ static rat_rc replay_chunks(rat_handle h, const ReplaySpec &rs, int *d_mismatch,
         ta.kc = (long)kc; ta.cost = h->d_mc_cost + k0;
         if (tail) launch_tlt_weights(ta, h->d_tl_live, h->stream);
         else launch_wct_weights(ta, h->stream);
-        if ((rc = behind(ta, ReplayChunk{k0, kc}))) return rc;
+        if ((rc = behind(ta, ReplayChunk{k0, kc, live}))) return rc;
     }
     return RAT_OK;
 }
@@ -2711,6 +2714,37 @@ static ReplayRows replay_rows(rat_handle h, bool tail) {
     static_assert(TR_MAX_ALPHA * TR_NSTAT <= WC_MAX_ROWS * WC_NSTAT, "the callers' row buffers hold either kind");
     if (tail) return ReplayRows{h->d_tr_red + TR_O_ROWS, TR_NSTAT, RAT_TR_ESS};
     return ReplayRows{h->d_wc_red + WC_O_ROWS, WC_NSTAT, RAT_WC_ESS};
+}
+
+// The end of a moment replay, behind its *_final kernel: the rows, the moment kernel's (S0, sum y^2) per row (d_out + o_ess, ess_stride
+// doubles a row), the mismatch count (d_out + o_cnt) and the call's outputs (copies; a null destination is skipped) to the host, the
+// call's one host wait, the replay guard, and the rows' effective sample size against the moment kernel's own S0^2 / sum y^2: two routes
+// to one number (the rows' sums are centred, these are not: 1e-6 relative is far above what either loses and far below any error of the
+// weights).  rows_out is written last: a refused call leaves it alone.
+struct ReplayCopy { double *dst; size_t off, count; };
+static rat_rc replay_finish(rat_handle h, const std::string &F, bool tail, int nrows, const double *d_out, size_t o_ess, int ess_stride, size_t o_cnt,
+                            std::initializer_list<ReplayCopy> copies, double *rows_out) {
+    rat_rc rc;
+    HIPCHK(hipGetLastError());
+    const ReplayRows rr = replay_rows(h, tail);
+    double rows[WC_MAX_ROWS * WC_NSTAT], ess[WC_MAX_ROWS * 4];
+    int bad = 0;
+    HIPCHK(hipMemcpyAsync(rows, rr.d_rows, (size_t)nrows * rr.nstat * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(ess, d_out + o_ess, (size_t)nrows * ess_stride * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&bad, d_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    for (const ReplayCopy &c : copies)
+        if (c.dst) HIPCHK(hipMemcpyAsync(c.dst, d_out + c.off, c.count * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = replay_mismatch(F, bad, h->mc_rec.K))) return rc;
+    for (int r = 0; r < nrows; ++r) {
+        const double *e = ess + ess_stride * r;
+        const double e_row = rows[r * rr.nstat + rr.ess], e_mom = e[0] * e[0] / e[1];
+        if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
+            return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
+                                     " is not the row's " + std::to_string(e_row));
+    }
+    for (int i = 0; i < nrows * rr.nstat; ++i) rows_out[i] = rows[i];
+    return RAT_OK;
 }
 
 // The centre c_t of the (x_t, u_t) tile, enqueued into centre [N+1][16]: (x_nom, l) under a policy; open loop the noise-free trajectory of
@@ -2738,14 +2772,11 @@ static rat_rc replay_centre(rat_handle h, double *centre) {
 // schedule's)
 static rat_rc replay_trajectory(rat_handle h, const std::string &F, const ReplaySpec &rs, double *rows_out, double *mean_out, double *cov_out) {
     rat_rc rc;
-    const bool tail = rs.tail();
-    const rat_handle_s::McReplay rec = h->mc_rec;
     const int n = h->n, m = h->m, N = h->N, nrows = rs.nrows(), d = n + m;
     if ((long)nrows * (N + 1) > WT_MAX_ROWSTEPS)
         return fail(RAT_ERR_UNSUPPORTED, F + "rows x (N + 1) = " + std::to_string((long)nrows * (N + 1)) + " is above " +
                                          std::to_string(WT_MAX_ROWSTEPS) + " (64 MiB of partial sums): ask for fewer rows per call");
     HIPCHK(hipSetDevice(h->device));
-    const int64_t K = rec.K;
     const size_t o_mean = (size_t)(N + 1) * 16, o_cov = o_mean + (size_t)nrows * (N + 1) * d, o_ess = o_cov + (size_t)nrows * (N + 1) * d * d,
                  o_cnt = o_ess + 2 * (size_t)nrows, n_out = o_cnt + 1, n_part = (size_t)nrows * (N + 1) * WT_SLOTS * WT_PART;
     if ((rc = grow(&h->d_wt_part, &h->cap_wt_part, n_part))) return rc;
@@ -2757,34 +2788,11 @@ static rat_rc replay_trajectory(rat_handle h, const std::string &F, const Replay
     ta.centre = h->d_wt_out; ta.part = h->d_wt_part;
     ta.mean = h->d_wt_out + o_mean; ta.cov = h->d_wt_out + o_cov; ta.ess = h->d_wt_out + o_ess;
     if ((rc = replay_chunks(h, rs, reinterpret_cast<int *>(h->d_wt_out + o_cnt), ta,
-                            [&](const WtArgs &c, ReplayChunk) -> rat_rc {
-                                if (tail && !h->tail_dense) launch_tlt_chunk(c, h->d_tl_live, h->stream);
-                                else launch_wct_chunk(c, h->stream);
-                                return RAT_OK;
-                            })))
+                            [&](const WtArgs &c, ReplayChunk ch) -> rat_rc { launch_wct_chunk(c, ch.live, h->stream); return RAT_OK; })))
         return rc;
     launch_wct_final(ta, h->stream);
-    HIPCHK(hipGetLastError());
-    const ReplayRows rr = replay_rows(h, tail);
-    double rows[WC_MAX_ROWS * WC_NSTAT], ess[WC_MAX_ROWS * 2];
-    int bad = 0;
-    HIPCHK(hipMemcpyAsync(rows, rr.d_rows, (size_t)nrows * rr.nstat * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(ess, h->d_wt_out + o_ess, (size_t)nrows * 16, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(&bad, h->d_wt_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(mean_out, h->d_wt_out + o_mean, (size_t)nrows * (N + 1) * d * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(cov_out, h->d_wt_out + o_cov, (size_t)nrows * (N + 1) * d * d * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if ((rc = replay_mismatch(F, bad, K))) return rc;
-    // the rows' effective sample size against the moment kernel's own S0^2 / sum y^2: two routes to one number (the rows' sums are centred,
-    // these are not: 1e-6 relative is far above what either loses and far below any error of the weights)
-    for (int r = 0; r < nrows; ++r) {
-        const double e_row = rows[r * rr.nstat + rr.ess], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
-        if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
-            return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
-                                     " is not the row's " + std::to_string(e_row));
-    }
-    for (int i = 0; i < nrows * rr.nstat; ++i) rows_out[i] = rows[i];
-    return RAT_OK;
+    return replay_finish(h, F, rs.tail(), nrows, h->d_wt_out, o_ess, 2, o_cnt,
+                         {{mean_out, o_mean, (size_t)nrows * (N + 1) * d}, {cov_out, o_cov, (size_t)nrows * (N + 1) * d * d}}, rows_out);
 }
 
 extern "C" rat_rc rat_policy_worst_case_trajectory(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
@@ -2812,14 +2820,12 @@ extern "C" rat_rc rat_policy_tail_trajectory(rat_handle h, const double *alpha, 
 static rat_rc replay_disturbance(rat_handle h, const std::string &F, const ReplaySpec &rs, double *rows_out, double *mean_w_out, double *cov_w_out,
                                  double *cov_wz_out) {
     rat_rc rc;
-    const bool tail = rs.tail();
-    const rat_handle_s::McReplay rec = h->mc_rec;
     const int n = h->n, m = h->m, N = h->N, nrows = rs.nrows(), d = n + m;
     if ((long)nrows * N > WD_MAX_ROWSTEPS)
         return fail(RAT_ERR_UNSUPPORTED, F + "rows x N = " + std::to_string((long)nrows * N) + " is above " +
                                          std::to_string(WD_MAX_ROWSTEPS) + " (64 MiB of partial sums): ask for fewer rows per call");
     HIPCHK(hipSetDevice(h->device));
-    const int64_t K = rec.K, chunk = mc_chunk(K);
+    const int64_t chunk = mc_chunk(h->mc_rec.K);
     const bool cross = cov_wz_out != nullptr;
     const int ldw = (h->pb.model == RAT_MODEL_SOURCE) ? n : XSTR;     // (the leading dimension of the staged x)
     const size_t nrs = (size_t)nrows * N;                             // (rows x steps)
@@ -2840,33 +2846,13 @@ static rat_rc replay_disturbance(rat_handle h, const std::string &F, const Repla
     if ((rc = replay_chunks(h, rs, reinterpret_cast<int *>(h->d_wd_out + o_cnt), da.t,
                             [&](const WtArgs &, ReplayChunk c) -> rat_rc {
                                 if (c.k0 == 0) launch_wcd_centre(da, h->stream);   // c_w: fixed before the first chunk's sums
-                                if (tail && !h->tail_dense) launch_tld_chunk(da, h->d_tl_live, h->stream);
-                                else launch_wcd_chunk(da, h->stream);
+                                launch_wcd_chunk(da, c.live, h->stream);
                                 return RAT_OK;
                             }, h->d_mc_wo)))
         return rc;
     launch_wcd_final(da, h->stream);
-    HIPCHK(hipGetLastError());
-    const ReplayRows rr = replay_rows(h, tail);
-    double rows[WC_MAX_ROWS * WC_NSTAT], ess[WC_MAX_ROWS * 2];
-    int bad = 0;
-    HIPCHK(hipMemcpyAsync(rows, rr.d_rows, (size_t)nrows * rr.nstat * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(ess, h->d_wd_out + o_ess, (size_t)nrows * 16, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(&bad, h->d_wd_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(mean_w_out, h->d_wd_out + o_mean, nrs * n * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(cov_w_out, h->d_wd_out + o_cov, nrs * n * n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (cross) HIPCHK(hipMemcpyAsync(cov_wz_out, h->d_wd_out + o_wz, nrs * n * d * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if ((rc = replay_mismatch(F, bad, K))) return rc;
-    // the rows' effective sample size against the moment kernel's own, as rat_policy_worst_case_trajectory holds it
-    for (int r = 0; r < nrows; ++r) {
-        const double e_row = rows[r * rr.nstat + rr.ess], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
-        if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
-            return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
-                                     " is not the row's " + std::to_string(e_row));
-    }
-    for (int i = 0; i < nrows * rr.nstat; ++i) rows_out[i] = rows[i];
-    return RAT_OK;
+    return replay_finish(h, F, rs.tail(), nrows, h->d_wd_out, o_ess, 2, o_cnt,
+                         {{mean_w_out, o_mean, nrs * n}, {cov_w_out, o_cov, nrs * n * n}, {cov_wz_out, o_wz, nrs * n * d}}, rows_out);
 }
 
 extern "C" rat_rc rat_policy_worst_case_disturbance(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
@@ -2906,7 +2892,6 @@ static rat_rc replay_params_ready(rat_handle h, const std::string &F) {
 static rat_rc replay_params(rat_handle h, const std::string &F, const char *fn, const ReplaySpec &rs, double *rows_out, double *mean_q_out,
                             double *cov_q_out, double *cov_qJ_out) {
     rat_rc rc;
-    const bool tail = rs.tail();
     const rat_handle_s::McReplay rec = h->mc_rec;
     const int nrows = rs.nrows(), P = (int)h->src_np;   // (1 .. 32: rat_policy_params_sampling accepted it)
     HIPCHK(hipSetDevice(h->device));
@@ -2914,7 +2899,7 @@ static rat_rc replay_params(rat_handle h, const std::string &F, const char *fn, 
     int *d_over = nullptr;
     if ((rc = src_kernel(h, SRC_PARAMS, SrcShape(), fn, &kq))) return rc;
     if ((rc = overdraw_flag(&h->h_un_over, F, &d_over))) return rc;
-    const int64_t K = rec.K, chunk = mc_chunk(K);
+    const int64_t chunk = mc_chunk(rec.K);
     const bool cross = cov_qJ_out != nullptr;
     const size_t o_mean = WP_NCENTRE, o_cov = o_mean + (size_t)nrows * P, o_qJ = o_cov + (size_t)nrows * P * P,
                  o_ess = o_qJ + (cross ? (size_t)nrows * P : 0), o_cnt = o_ess + 4 * (size_t)nrows, n_out = o_cnt + 1,
@@ -2935,33 +2920,14 @@ static rat_rc replay_params(rat_handle h, const std::string &F, const char *fn, 
                                 sa.j0 = (long)c.k0; sa.q_out = h->d_wp_q; sa.overdraw = d_over;
                                 HIPCHK(launch_src(kq, c.kc, 64, h->stream, &sa));
                                 if (c.k0 == 0) launch_wcp_centre(pa, h->stream);   // c_q, c_J: fixed before the first chunk's sums
-                                if (tail && !h->tail_dense) launch_tlp_chunk(pa, h->d_tl_live, h->stream);
-                                else launch_wcp_chunk(pa, h->stream);
+                                launch_wcp_chunk(pa, c.live, h->stream);
                                 return RAT_OK;
                             })))
         return rc;
     launch_wcp_final(pa, h->stream);
-    HIPCHK(hipGetLastError());
-    const ReplayRows rr = replay_rows(h, tail);
-    double rows[WC_MAX_ROWS * WC_NSTAT], ess[WC_MAX_ROWS * 4];
-    int bad = 0;
-    HIPCHK(hipMemcpyAsync(rows, rr.d_rows, (size_t)nrows * rr.nstat * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(ess, h->d_wp_out + o_ess, (size_t)nrows * 32, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(&bad, h->d_wp_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(mean_q_out, h->d_wp_out + o_mean, (size_t)nrows * P * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(cov_q_out, h->d_wp_out + o_cov, (size_t)nrows * P * P * 8, hipMemcpyDeviceToHost, h->stream));
-    if (cross) HIPCHK(hipMemcpyAsync(cov_qJ_out, h->d_wp_out + o_qJ, (size_t)nrows * P * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if ((rc = replay_mismatch(F, bad, K))) return rc;
-    // the rows' effective sample size against the moment kernel's own, as rat_policy_worst_case_trajectory holds it
-    for (int r = 0; r < nrows; ++r) {
-        const double e_row = rows[r * rr.nstat + rr.ess], e_mom = ess[4 * r] * ess[4 * r] / ess[4 * r + 1];
-        if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
-            return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
-                                     " is not the row's " + std::to_string(e_row));
-    }
-    for (int i = 0; i < nrows * rr.nstat; ++i) rows_out[i] = rows[i];
-    return RAT_OK;
+    return replay_finish(h, F, rs.tail(), nrows, h->d_wp_out, o_ess, 4, o_cnt,
+                         {{mean_q_out, o_mean, (size_t)nrows * P}, {cov_q_out, o_cov, (size_t)nrows * P * P}, {cov_qJ_out, o_qJ, (size_t)nrows * P}},
+                         rows_out);
 }
 
 extern "C" rat_rc rat_policy_worst_case_params(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,

@@ -138,8 +138,9 @@ struct WtArgs {
 void launch_wct_centre(const double *x, const double *u, int n, int m, int N, double *centre, hipStream_t s);
 // one chunk: the weights of its rollouts per row and the replay check (wct_weights; rat_policy_events forms its weights with it too) ...
 void launch_wct_weights(const WtArgs &a, hipStream_t s);
-// ... then, behind it, the chunk's sums into the partials
-void launch_wct_chunk(const WtArgs &a, hipStream_t s);
+// ... then, behind it, the chunk's sums into the partials.  live: the chunk's liveness words (launch_tlt_weights wrote them: the tail
+// calls' schedule, below), or null for the dense schedule; launch_wcd_chunk and launch_wcp_chunk take it likewise
+void launch_wct_chunk(const WtArgs &a, const unsigned *live, hipStream_t s);
 void launch_wct_final(const WtArgs &a, hipStream_t s);
 
 // ---- rat_policy_worst_case_disturbance: the mean and covariance of the disturbance w_t, and its covariance with (x_t, u_t) (policy_mc.hip) ----
@@ -172,7 +173,7 @@ struct WdArgs {
 // c_w from the first chunk (a.t.kc, a.t.cost, a.ws): behind that chunk's rollouts, before its sums
 void launch_wcd_centre(const WdArgs &a, hipStream_t s);
 // one chunk, behind launch_wct_weights: the chunk's sums into the partials
-void launch_wcd_chunk(const WdArgs &a, hipStream_t s);
+void launch_wcd_chunk(const WdArgs &a, const unsigned *live, hipStream_t s);
 void launch_wcd_final(const WdArgs &a, hipStream_t s);
 
 // ---- rat_policy_worst_case_params: the mean and covariance of the rollouts' drawn parameters q, and their covariance with the cost ---------
@@ -209,7 +210,7 @@ struct WpArgs {
 // the centres from the first chunk (a.t.kc, a.t.cost, a.qs): behind that chunk's q, before its sums
 void launch_wcp_centre(const WpArgs &a, hipStream_t s);
 // one chunk, behind launch_wct_weights and the chunk's q: the chunk's sums into the partials
-void launch_wcp_chunk(const WpArgs &a, hipStream_t s);
+void launch_wcp_chunk(const WpArgs &a, const unsigned *live, hipStream_t s);
 void launch_wcp_final(const WpArgs &a, hipStream_t s);
 
 // ---- rat_policy_tail_trajectory / _disturbance / _params: the same moments under the CVaR adversary, one row per level (policy_mc.hip) ------
@@ -219,7 +220,7 @@ void launch_wcp_final(const WpArgs &a, hipStream_t s);
 // (theta, state) -- a scratch of launch_policy_wc's size, WtArgs::wc -- so that wct_final / wcd_final / wcp_final serve unchanged; a level
 // thinner than one rollout is v = Jmax, y_eq = 1.  tlt_weights is wct_weights' counterpart and also writes, per group of four rollouts,
 // one word whose bit r says "some y of level r in this group is not zero".  tlt_moments / tld_moments / tlp_moments are wct_moments /
-// wcd_moments / wcp_moments with that word read first (the bodies are shared; the worst-case instantiations are compiled as before): a
+// wcd_moments / wcp_moments with that word read first (one body, moments_body, serves all six; TAIL is a template argument): a
 // wavefront issues nothing for a row its group is dead in, loads nothing for a group dead in every row of the workgroup, and selects a
 // rollout without weight in a row out of that row's operands.  Adding 0 D to a sum changes no bit where D is finite, so on finite data
 // the two schedules agree bit for bit; a rollout without weight that holds Inf or NaN is left out, where the dense schedule forms 0 Inf.
@@ -228,10 +229,7 @@ void launch_wcp_final(const WpArgs &a, hipStream_t s);
 void launch_tlt_levels(const TrArgs &a, double *wc, hipStream_t s);
 // one chunk: the weights of its rollouts per level, the replay check and the liveness words live [(kc + 3) / 4] (a.wc: tlt_levels' output)
 void launch_tlt_weights(const WtArgs &a, unsigned *live, hipStream_t s);
-// ... then, behind it, the chunk's sums into the partials: launch_wct_chunk / launch_wcd_chunk / launch_wcp_chunk with the liveness schedule
-void launch_tlt_chunk(const WtArgs &a, const unsigned *live, hipStream_t s);
-void launch_tld_chunk(const WdArgs &a, const unsigned *live, hipStream_t s);
-void launch_tlp_chunk(const WpArgs &a, const unsigned *live, hipStream_t s);
+// ... then, behind it, the chunk's sums into the partials: launch_wct_chunk / launch_wcd_chunk / launch_wcp_chunk with live
 
 // ---- rat_policy_events: how often a policy violates quadratic constraints, under q and under every row's tilt (policy_mc.hip) ---------------
 // An event is g(t, z) = z' Q z + a' z + b of z = (x_t, u_t) in the 12 + 4 tile, watched over the steps t_lo .. t_hi.  Behind each replayed

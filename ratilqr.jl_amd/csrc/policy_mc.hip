@@ -709,16 +709,147 @@ __global__ __launch_bounds__(MC_THREADS) void tr_weights(TrArgs a) {
     }
 }
 
-// ---- rat_policy_worst_case_trajectory: weighted moments of the replayed trajectories ------------------------------------------------------
-// One MFMA per group of four rollouts, step and row: lane (i = lane & 15, kk = lane >> 4) holds D_i of rollout 4 g + kk, so A = y D is
-// [16 components][4 rollouts], B = D is [4 rollouts][16 components] and C += A B is the group's sum y D D'.  S1, S0 and sum y^2 ride along
-// in the same lanes (the four rollouts of a lane column are summed at the end).  Order: wavefront w of slot s takes the groups
-// s * WT_WAVES + w, + WT_SLOTS * WT_WAVES, ... in order; the wavefronts of a workgroup (and the four rollout lanes) are summed in index
-// order through LDS into the workgroup's partial, chunk after chunk in stream order; wct_final sums the slots in index order.  No
-// floating-point atomics (the replay check counts with an integer one: a count does not depend on the order).
+// ---- the moment replays: weighted moments of what the replayed rollouts held, one schedule for three payloads ------------------------------
+// rat_policy_worst_case_trajectory / _disturbance / _params and their rat_policy_tail_* siblings.  One MFMA per group of four rollouts,
+// row and product: lane (i = lane & 15, kk = lane >> 4) holds component i of a deviation D of rollout 4 g + kk, so A = y D is
+// [16 components][4 rollouts], B = D' is [4 rollouts][16 components] and C += A B is the group's sum y D D'.  Sums per lane (S1 = sum y D)
+// and per rollout lane kk (S0 = sum y, sum y^2) ride along; the four rollouts of a lane column are summed at the end.  Order: wavefront w of
+// slot s takes the groups s * WT_WAVES + w, + WT_SLOTS * WT_WAVES, ... in order; the wavefronts of a workgroup (and the four rollout
+// lanes) are summed in index order through LDS into the workgroup's partial, chunk after chunk in stream order; *_final sums the slots in
+// index order.  No floating-point atomics (the replay check counts with an integer one: a count does not depend on the order).
+//
+// moments_body is that schedule, once.  A payload F says what a lane holds and which products a row forms:
+//   TILES, VECS, SCALARS   C tiles per row, sums per lane, sums per rollout lane (scalars 0 and 1 are S0 and sum y^2, which moments_body
+//                          adds itself); the LDS per wavefront and row is their tiles | vectors | scalars
+//   o_tile, o_vec, o_scalar   where each lands in the partial (the WT_O_* / WD_O_* / WP_O_* of policy_mc.h)
+//   batch()                the row batch of the workgroup: the grid axis behind the step, or, for the one-step parameters, the step's own
+//   part(row, slot)        the partial of (row, the workgroup's step, slot)
+//   load(q, ok, J)         the lane's deviations of rollout q (ok: it has a cost, J; otherwise exact zeros: selected, not multiplied --
+//                          the data may hold NaN)
+//   row(c, v, s, y, has, d)   one row's MFMAs and sums: has false selects the rollout out of both operands
+// Everything is resolved at compile time and inlined: the kernels below are the instantiations.
 typedef double wt_d4 __attribute__((ext_vector_type(4)));
-#define WT_SH (256 + 64 + 8)   /* LDS doubles per wavefront and row: tile | S1 per lane | S0 [4] | sum y^2 [4] */
+#define WD_NONE 0x7fffffff
 
+__device__ __forceinline__ wt_d4 wt_mfma(double a, double b, wt_d4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+
+// With TAIL (the liveness schedule of the tail calls, policy_mc.h) the wavefront reads its group's liveness word first -- wave-uniform, a
+// group is one wavefront's work, so the tests are scalar branches -- skips a group dead in every row of the workgroup before any load,
+// issues nothing for a row the group is dead in, and selects a rollout without weight in a row out of both operands of that row's
+// products.
+template <class F, bool TAIL>
+__device__ __forceinline__ void moments_body(const F &f, const WtArgs &t, const unsigned *lv) {
+    constexpr int NT = F::TILES, NV = F::VECS, NS = F::SCALARS, O_V = NT * 256, O_S = O_V + NV * 64;
+    __shared__ double sh[WT_WAVES][O_S + NS * 4];
+    const int slot = blockIdx.x, r0 = F::batch() * WT_ROWS;
+    const int nr = (t.nrows - r0 < WT_ROWS) ? t.nrows - r0 : WT_ROWS;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
+    wt_d4 c[WT_ROWS][NT];
+    double v[WT_ROWS][NV], s[WT_ROWS][NS];
+#pragma unroll
+    for (int r = 0; r < WT_ROWS; ++r) {
+#pragma unroll
+        for (int b = 0; b < NT; ++b) c[r][b] = (wt_d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int b = 0; b < NV; ++b) v[r][b] = 0.0;
+#pragma unroll
+        for (int b = 0; b < NS; ++b) s[r][b] = 0.0;
+    }
+    const long kc = t.kc, G = (kc + 3) >> 2;
+    for (long g = (long)slot * WT_WAVES + w; g < G; g += (long)WT_SLOTS * WT_WAVES) {      // (uniform over the wavefront)
+        unsigned on = 0xffu;
+        if (TAIL) {
+            on = (unsigned)__builtin_amdgcn_readfirstlane((int)((lv[g] >> r0) & 0xffu));
+            if (on == 0u) continue;                                   // dead in every row of the workgroup: nothing is loaded
+        }
+        const long q = 4 * g + kk;
+        const bool live = q < kc;                                     // (the K tail)
+        const double J = live ? t.cost[q] : 0.0;
+        const bool ok = live && !mc_nan(J);
+        const typename F::Dev d = f.load(q, ok, J);
+#pragma unroll
+        for (int r = 0; r < WT_ROWS; ++r) {
+            if (r < nr && (!TAIL || ((on >> r) & 1u))) {              // (uniform over the workgroup; with TAIL over the wavefront)
+                const double y = ok ? t.y[(long)(r0 + r) * t.ldy + q] : 0.0;
+                f.row(c[r], v[r], s[r], y, !TAIL || y != 0.0, d);
+                s[r][0] += y; s[r][1] += y * y;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < WT_ROWS; ++r) {
+        if (r < nr) {
+            __syncthreads();                                          // (the previous row's sums are read)
+#pragma unroll
+            for (int b = 0; b < NT; ++b)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) sh[w][b * 256 + (kk + 4 * reg) * 16 + i] = c[r][b][reg];   // C: row (lane >> 4) + 4 reg, column lane & 15
+#pragma unroll
+            for (int b = 0; b < NV; ++b) sh[w][O_V + b * 64 + lane] = v[r][b];
+            if (i == 0) {
+#pragma unroll
+                for (int b = 0; b < NS; ++b) sh[w][O_S + b * 4 + kk] = s[r][b];
+            }
+            __syncthreads();
+            double *p = f.part(r0 + r, slot);
+            const int e = threadIdx.x;
+#pragma unroll
+            for (int b = 0; b < NT; ++b) {
+                double a = 0.0;
+                for (int w2 = 0; w2 < WT_WAVES; ++w2) a += sh[w2][b * 256 + e];
+                p[F::o_tile(b) + e] += a;
+            }
+            if (e < NV * 16) {                                        // vector e >> 4, component e & 15
+                double a = 0.0;
+                for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) a += sh[w2][O_V + (e >> 4) * 64 + k2 * 16 + (e & 15)];
+                p[F::o_vec(e >> 4) + (e & 15)] += a;
+            } else if (e < NV * 16 + NS) {
+                double a = 0.0;
+                for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) a += sh[w2][O_S + (e - NV * 16) * 4 + k2];
+                p[F::o_scalar(e - NV * 16)] += a;
+            }
+        }
+    }
+}
+
+// The replay check of rollout q, whose stored cost is J: the replay found the same bits (NaN equals NaN; dom_re: its DomainError flag)
+__device__ __forceinline__ bool replay_same(const WtArgs &a, long q, double J) {
+    double Jr = a.cost_re[q];
+    if (a.dom_re && a.dom_re[q]) Jr = __builtin_nan("");
+    return (mc_nan(J) && mc_nan(Jr)) || __double_as_longlong(J) == __double_as_longlong(Jr);
+}
+
+// The first rollout of the chunk that has a cost, WD_NONE where none has (the whole workgroup calls it).  c_w, c_q and c_J are that
+// rollout's: as good a guess of where a draw lies as any one draw -- within a few standard deviations of the mean wherever the sampler
+// puts that -- and known before the first sums, the same for every row.
+__device__ __forceinline__ int first_with_cost(const double *cost, long kc) {
+    __shared__ int first;
+    if (threadIdx.x == 0) first = WD_NONE;
+    __syncthreads();
+    for (long q = threadIdx.x; q < kc; q += MC_THREADS)
+        if (!mc_nan(cost[q])) { atomicMin(&first, (int)q); break; }                      // (an integer minimum: no order in it)
+    __syncthreads();
+    return first;
+}
+
+// S[q] = sum over the slots, in index order, of the partials p [WT_SLOTS][PART] (the whole workgroup calls it; S is ready on return)
+template <int PART>
+__device__ __forceinline__ void slot_sum(const double *p, double *S) {
+    for (int q = threadIdx.x; q < PART; q += MC_THREADS) {
+        double v = 0.0;
+        for (int s = 0; s < WT_SLOTS; ++s) v += p[s * PART + q];
+        S[q] = v;
+    }
+    __syncthreads();
+}
+
+// a row of an empty or non-finite sample: its moments are NaN
+__device__ __forceinline__ bool row_dead(const double *wc, int r) {
+    const double st = wc[WC_O_INFO + 2 * r + 1];
+    return st == WC_ST_EMPTY || st == WC_ST_NONFINITE;
+}
+
+// ---- rat_policy_worst_case_trajectory: D = (x_t, u_t) - c_t in the 12 + 4 tile, one product -------------------------------------------------
 __global__ __launch_bounds__(MC_THREADS) void wct_centre(const double *x, const double *u, int n, int m, int N, double *c) {
     for (int e = blockIdx.x * MC_THREADS + threadIdx.x; e < (N + 1) * 16; e += gridDim.x * MC_THREADS) {
         const int t = e >> 4, i = e & 15;
@@ -736,10 +867,7 @@ __global__ __launch_bounds__(MC_THREADS) void wct_weights(WtArgs a) {
     int bad = 0;
     for (long q = (long)blockIdx.x * MC_THREADS + threadIdx.x; q < a.kc; q += T) {
         const double J = a.cost[q];
-        double Jr = a.cost_re[q];
-        if (a.dom_re && a.dom_re[q]) Jr = __builtin_nan("");
-        const bool same = (mc_nan(J) && mc_nan(Jr)) || __double_as_longlong(J) == __double_as_longlong(Jr);
-        bad += same ? 0 : 1;
+        bad += replay_same(a, q, J) ? 0 : 1;
         for (int r = 0; r < a.nrows; ++r) {
             const double th = a.wc[WC_O_INFO + 2 * r], st = a.wc[WC_O_INFO + 2 * r + 1];
             double y = 0.0;                                           // (a DomainError rollout, an empty or non-finite sample: no weight)
@@ -790,12 +918,7 @@ __global__ __launch_bounds__(MC_THREADS) void tlt_weights(WtArgs a, unsigned *lv
     for (long q = (long)blockIdx.x * MC_THREADS + threadIdx.x; q < kc4; q += T) {
         const bool in = q < a.kc;                                     // (the K tail: no cost, no weight, no bit)
         const double J = in ? a.cost[q] : __builtin_nan("");
-        if (in) {
-            double Jr = a.cost_re[q];
-            if (a.dom_re && a.dom_re[q]) Jr = __builtin_nan("");
-            const bool same = (mc_nan(J) && mc_nan(Jr)) || __double_as_longlong(J) == __double_as_longlong(Jr);
-            bad += same ? 0 : 1;
-        }
+        if (in) bad += replay_same(a, q, J) ? 0 : 1;
         unsigned bits = 0u;
         for (int r = 0; r < a.nrows; ++r) {
             const double v = a.wc[WC_O_INFO + 2 * r], st = a.wc[WC_O_INFO + 2 * r + 1], ye = a.wc[TL_O_YEQ + r];
@@ -811,90 +934,43 @@ __global__ __launch_bounds__(MC_THREADS) void tlt_weights(WtArgs a, unsigned *lv
     if (bad) atomicAdd(a.mismatch, bad);
 }
 
-// The body of wct_moments (TAIL = false) and of tlt_moments (TAIL = true: the liveness schedule of the tail calls, policy_mc.h).  With
-// TAIL the wavefront reads its group's liveness word first -- wave-uniform, a group is one wavefront's work, so the tests are scalar
-// branches -- skips a group dead in every row of the workgroup before any load, issues nothing for a row the group is dead in, and
-// selects a rollout without weight in a row out of both operands of that row's product.
-template <bool TAIL>
-__device__ __forceinline__ void wct_moments_body(const WtArgs &a, const unsigned *lv) {
-    __shared__ double sh[WT_WAVES][WT_SH];
-    const int slot = blockIdx.x, t = blockIdx.y, r0 = blockIdx.z * WT_ROWS;
-    const int nr = (a.nrows - r0 < WT_ROWS) ? a.nrows - r0 : WT_ROWS;
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
-    const int N = a.N;
-    const bool isx = i < 12;
-    const bool comp = isx ? (i < a.n) : (i - 12 < a.m && t < N);      // (padding lanes, and u at step N, stay zero)
-    const double c = a.centre[t * 16 + i];
-    wt_d4 acc[WT_ROWS];
-    double s1[WT_ROWS], s0[WT_ROWS], sy2[WT_ROWS];
-#pragma unroll
-    for (int r = 0; r < WT_ROWS; ++r) { acc[r] = (wt_d4){0.0, 0.0, 0.0, 0.0}; s1[r] = 0.0; s0[r] = 0.0; sy2[r] = 0.0; }
-    const long G = (a.kc + 3) >> 2;
-    for (long g = (long)slot * WT_WAVES + w; g < G; g += (long)WT_SLOTS * WT_WAVES) {      // (uniform over the wavefront)
-        unsigned on = 0xffu;
-        if (TAIL) {
-            on = (unsigned)__builtin_amdgcn_readfirstlane((int)((lv[g] >> r0) & 0xffu));
-            if (on == 0u) continue;                                   // dead in every row of the workgroup: nothing is loaded
-        }
-        const long q = 4 * g + kk;
-        const bool live = q < a.kc;                                   // (the K tail)
-        const double J = live ? a.cost[q] : 0.0;
-        const bool ok = live && !mc_nan(J);                           // selected, not multiplied: the trajectory may hold NaN
+struct TrajectoryMoments {
+    static constexpr int TILES = 1, VECS = 1, SCALARS = 2;
+    static __device__ __forceinline__ constexpr int o_tile(int) { return 0; }
+    static __device__ __forceinline__ constexpr int o_vec(int) { return WT_O_S1; }
+    static __device__ __forceinline__ constexpr int o_scalar(int s) { return s == 0 ? WT_O_S0 : WT_O_SY2; }
+    static __device__ __forceinline__ int batch() { return blockIdx.z; }
+    struct Dev { double D; };
+    const WtArgs &a;
+    const int t, i;
+    const bool isx, comp;
+    const double c;
+    __device__ __forceinline__ TrajectoryMoments(const WtArgs &a_)
+        : a(a_), t(blockIdx.y), i(threadIdx.x & 15), isx(i < 12),
+          comp(isx ? (i < a_.n) : (i - 12 < a_.m && t < a_.N)),       // (padding lanes, and u at step N, stay zero)
+          c(a_.centre[t * 16 + i]) {}
+    __device__ __forceinline__ double *part(int row, int slot) const { return a.part + (((size_t)row * (a.N + 1) + t) * WT_SLOTS + slot) * WT_PART; }
+    __device__ __forceinline__ Dev load(long q, bool ok, double) const {
         double D = 0.0;
-        if (ok && comp) D = (isx ? a.xs[(q * (N + 1) + t) * a.ldx + i] : a.us[(q * N + t) * a.ldu + (i - 12)]) - c;
-#pragma unroll
-        for (int r = 0; r < WT_ROWS; ++r) {
-            if (r < nr && (!TAIL || ((on >> r) & 1u))) {              // (uniform over the workgroup; with TAIL over the wavefront)
-                const double y = ok ? a.y[(long)(r0 + r) * a.ldy + q] : 0.0;
-                const bool has = !TAIL || y != 0.0;
-                const double Dr = has ? D : 0.0, yd = has ? y * D : 0.0;
-                acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd, Dr, acc[r], 0, 0, 0);
-                s1[r] += yd; s0[r] += y; sy2[r] += y * y;
-            }
-        }
+        if (ok && comp) D = (isx ? a.xs[(q * (a.N + 1) + t) * a.ldx + i] : a.us[(q * a.N + t) * a.ldu + (i - 12)]) - c;
+        return Dev{D};
     }
-#pragma unroll
-    for (int r = 0; r < WT_ROWS; ++r) {
-        if (r < nr) {
-            __syncthreads();                                          // (the previous row's sums are read)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) sh[w][(kk + 4 * reg) * 16 + i] = acc[r][reg];   // C: row (lane >> 4) + 4 reg, column lane & 15
-            sh[w][256 + lane] = s1[r];
-            if (i == 0) { sh[w][320 + kk] = s0[r]; sh[w][324 + kk] = sy2[r]; }
-            __syncthreads();
-            double *p = a.part + (((size_t)(r0 + r) * (N + 1) + t) * WT_SLOTS + slot) * WT_PART;
-            const int e = threadIdx.x;
-            double v = 0.0;
-            for (int w2 = 0; w2 < WT_WAVES; ++w2) v += sh[w2][e];
-            p[e] += v;
-            if (e < 16) {
-                v = 0.0;
-                for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][256 + k2 * 16 + e];
-                p[WT_O_S1 + e] += v;
-            } else if (e == 16 || e == 17) {
-                v = 0.0;
-                for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][(e == 16 ? 320 : 324) + k2];
-                p[(e == 16) ? WT_O_S0 : WT_O_SY2] += v;
-            }
-        }
+    __device__ __forceinline__ void row(wt_d4 (&C)[TILES], double (&v)[VECS], double (&)[SCALARS], double y, bool has, const Dev &d) const {
+        const double Dr = has ? d.D : 0.0, yd = has ? y * d.D : 0.0;
+        C[0] = wt_mfma(yd, Dr, C[0]);
+        v[0] += yd;
     }
-}
+};
 
-__global__ __launch_bounds__(WT_WAVES * 64) void wct_moments(WtArgs a) { wct_moments_body<false>(a, nullptr); }
-__global__ __launch_bounds__(WT_WAVES * 64) void tlt_moments(WtArgs a, const unsigned *live) { wct_moments_body<true>(a, live); }
+__global__ __launch_bounds__(WT_WAVES * 64) void wct_moments(WtArgs a) { moments_body<TrajectoryMoments, false>(TrajectoryMoments(a), a, nullptr); }
+__global__ __launch_bounds__(WT_WAVES * 64) void tlt_moments(WtArgs a, const unsigned *live) { moments_body<TrajectoryMoments, true>(TrajectoryMoments(a), a, live); }
 
 __global__ __launch_bounds__(MC_THREADS) void wct_final(WtArgs a) {
     __shared__ double S[WT_PART];
     const int t = blockIdx.x, r = blockIdx.y, e = threadIdx.x, N = a.N, d = a.n + a.m;
-    const double *p = a.part + ((size_t)r * (N + 1) + t) * WT_SLOTS * WT_PART;
-    for (int q = e; q < WT_PART; q += MC_THREADS) {
-        double v = 0.0;
-        for (int s = 0; s < WT_SLOTS; ++s) v += p[s * WT_PART + q];
-        S[q] = v;
-    }
-    __syncthreads();
-    const double st = a.wc[WC_O_INFO + 2 * r + 1], nan = __builtin_nan("");
-    const bool dead = (st == WC_ST_EMPTY || st == WC_ST_NONFINITE);
+    slot_sum<WT_PART>(a.part + ((size_t)r * (N + 1) + t) * WT_SLOTS * WT_PART, S);
+    const double nan = __builtin_nan("");
+    const bool dead = row_dead(a.wc, r);
     const double s0 = S[WT_O_S0];
     const size_t o = (size_t)r * (N + 1) + t;
     if (e < d * d) {                                                  // column-major; the upper triangle of the tile serves both halves
@@ -911,24 +987,11 @@ __global__ __launch_bounds__(MC_THREADS) void wct_final(WtArgs a) {
     if (t == 0 && e == 0) { a.ess[2 * r] = s0; a.ess[2 * r + 1] = S[WT_O_SY2]; }
 }
 
-// ---- rat_policy_worst_case_disturbance: weighted moments of the replayed disturbances -----------------------------------------------------
-// wct_moments' schedule and lane layout with two tiles per lane: Dw = w_t - c_w[t] (lanes i < n; lanes 12 .. 15 stay zero) and
-// Dz = (x_t, u_t) - c_t.  Per group, step and row one MFMA A = y Dw, B = Dw for sum y Dw Dw', and with CROSS a second one with the same A
-// and B = Dz: C[i][j] = sum y Dw_i Dz_j, w's component the row.  S1w, S1z, S0 and sum y^2 ride along.  The same order: a wavefront's
-// groups in order, wavefronts and rollout lanes in index order through LDS, chunk after chunk in stream order, the slots in wcd_final.
-// c_w: the first rollout of the first chunk that has a cost is as good a guess of where w_t lies as any one draw -- within a few
-// standard deviations of the mean wherever the sampler puts that -- and it is known before the first sums, the same for every row.
-#define WD_SH (256 + 256 + 64 + 64 + 8)   /* LDS doubles per wavefront and row: ww | wz | S1w per lane | S1z per lane | S0 [4] | sum y^2 [4] */
-#define WD_NONE 0x7fffffff
-
+// ---- rat_policy_worst_case_disturbance: Dw = w_t - c_w[t] (lanes i < n; lanes 12 .. 15 stay zero) and Dz = (x_t, u_t) - c_t ------------------
+// Per group, step and row one MFMA A = y Dw, B = Dw for sum y Dw Dw', and with CROSS a second one with the same A and B = Dz:
+// C[i][j] = sum y Dw_i Dz_j, w's component the row.  S1w and, with CROSS, S1z ride along.  c_w: first_with_cost's rollout.
 __global__ __launch_bounds__(MC_THREADS) void wcd_centre(WdArgs a) {
-    __shared__ int first;
-    if (threadIdx.x == 0) first = WD_NONE;
-    __syncthreads();
-    for (long q = threadIdx.x; q < a.t.kc; q += MC_THREADS)
-        if (!mc_nan(a.t.cost[q])) { atomicMin(&first, (int)q); break; }                  // (an integer minimum: no order in it)
-    __syncthreads();
-    const int q = first, N = a.t.N;
+    const int q = first_with_cost(a.t.cost, a.t.kc), N = a.t.N;
     for (int e = threadIdx.x; e < N * 16; e += MC_THREADS) {
         const int t = e >> 4, i = e & 15;
         double v = 0.0;
@@ -938,113 +1001,54 @@ __global__ __launch_bounds__(MC_THREADS) void wcd_centre(WdArgs a) {
     }
 }
 
-template <bool CROSS, bool TAIL>                                     // (TAIL: the liveness schedule, as wct_moments_body has it)
-__device__ __forceinline__ void wcd_moments_body(const WdArgs &a, const unsigned *lv) {
-    __shared__ double sh[WT_WAVES][WD_SH];
-    const int slot = blockIdx.x, t = blockIdx.y, r0 = blockIdx.z * WT_ROWS;
-    const int nrows = a.t.nrows, N = a.t.N;
-    const int nr = (nrows - r0 < WT_ROWS) ? nrows - r0 : WT_ROWS;
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
-    const bool isx = i < 12;
-    const bool compw = i < a.t.n;                                     // (padding lanes stay zero)
-    const bool compz = isx ? (i < a.t.n) : (i - 12 < a.t.m);          // (t < N throughout)
-    const double cw = a.cw[t * 16 + i], cz = a.t.centre[t * 16 + i];
-    wt_d4 aww[WT_ROWS], awz[WT_ROWS];
-    double s1w[WT_ROWS], s1z[WT_ROWS], s0[WT_ROWS], sy2[WT_ROWS];
-#pragma unroll
-    for (int r = 0; r < WT_ROWS; ++r) {
-        aww[r] = (wt_d4){0.0, 0.0, 0.0, 0.0}; awz[r] = (wt_d4){0.0, 0.0, 0.0, 0.0};
-        s1w[r] = 0.0; s1z[r] = 0.0; s0[r] = 0.0; sy2[r] = 0.0;
-    }
-    const long kc = a.t.kc, G = (kc + 3) >> 2;
-    for (long g = (long)slot * WT_WAVES + w; g < G; g += (long)WT_SLOTS * WT_WAVES) {      // (uniform over the wavefront)
-        unsigned on = 0xffu;
-        if (TAIL) {
-            on = (unsigned)__builtin_amdgcn_readfirstlane((int)((lv[g] >> r0) & 0xffu));
-            if (on == 0u) continue;                                   // dead in every row of the workgroup: nothing is loaded
-        }
-        const long q = 4 * g + kk;
-        const bool live = q < kc;                                     // (the K tail)
-        const double J = live ? a.t.cost[q] : 0.0;
-        const bool ok = live && !mc_nan(J);                           // selected, not multiplied: w and the trajectory may hold NaN
+template <bool CROSS>
+struct DisturbanceMoments {
+    static constexpr int TILES = CROSS ? 2 : 1, VECS = CROSS ? 2 : 1, SCALARS = 2;
+    static __device__ __forceinline__ constexpr int o_tile(int b) { return b == 0 ? 0 : WD_O_WZ; }
+    static __device__ __forceinline__ constexpr int o_vec(int b) { return b == 0 ? WD_O_S1W : WD_O_S1Z; }
+    static __device__ __forceinline__ constexpr int o_scalar(int s) { return s == 0 ? WD_O_S0 : WD_O_SY2; }
+    static __device__ __forceinline__ int batch() { return blockIdx.z; }
+    struct Dev { double Dw, Dz; };
+    const WdArgs &a;
+    const int t, i;
+    const bool isx, compw, compz;
+    const double cw, cz;
+    __device__ __forceinline__ DisturbanceMoments(const WdArgs &a_)
+        : a(a_), t(blockIdx.y), i(threadIdx.x & 15), isx(i < 12),
+          compw(i < a_.t.n),                                          // (padding lanes stay zero)
+          compz(isx ? (i < a_.t.n) : (i - 12 < a_.t.m)),              // (t < N throughout)
+          cw(a_.cw[t * 16 + i]), cz(a_.t.centre[t * 16 + i]) {}
+    __device__ __forceinline__ double *part(int row, int slot) const { return a.part + (((size_t)row * a.t.N + t) * WT_SLOTS + slot) * WD_PART; }
+    __device__ __forceinline__ Dev load(long q, bool ok, double) const {
+        const int N = a.t.N;
         double Dw = 0.0, Dz = 0.0;
         if (ok && compw) Dw = a.ws[(q * N + t) * a.ldw + i] - cw;
         if (CROSS && ok && compz) Dz = (isx ? a.t.xs[(q * (N + 1) + t) * a.t.ldx + i] : a.t.us[(q * N + t) * a.t.ldu + (i - 12)]) - cz;
-#pragma unroll
-        for (int r = 0; r < WT_ROWS; ++r) {
-            if (r < nr && (!TAIL || ((on >> r) & 1u))) {              // (uniform over the workgroup; with TAIL over the wavefront)
-                const double y = ok ? a.t.y[(long)(r0 + r) * a.t.ldy + q] : 0.0;
-                const bool has = !TAIL || y != 0.0;
-                const double Dwr = has ? Dw : 0.0, yd = has ? y * Dw : 0.0;
-                aww[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd, Dwr, aww[r], 0, 0, 0);
-                if (CROSS) {
-                    const double Dzr = has ? Dz : 0.0;
-                    awz[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd, Dzr, awz[r], 0, 0, 0);
-                    s1z[r] += has ? y * Dz : 0.0;
-                }
-                s1w[r] += yd; s0[r] += y; sy2[r] += y * y;
-            }
-        }
+        return Dev{Dw, Dz};
     }
-#pragma unroll
-    for (int r = 0; r < WT_ROWS; ++r) {
-        if (r < nr) {
-            __syncthreads();                                          // (the previous row's sums are read)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {                       // C: row (lane >> 4) + 4 reg, column lane & 15
-                sh[w][(kk + 4 * reg) * 16 + i] = aww[r][reg];
-                if (CROSS) sh[w][256 + (kk + 4 * reg) * 16 + i] = awz[r][reg];
-            }
-            sh[w][512 + lane] = s1w[r];
-            if (CROSS) sh[w][576 + lane] = s1z[r];
-            if (i == 0) { sh[w][640 + kk] = s0[r]; sh[w][644 + kk] = sy2[r]; }
-            __syncthreads();
-            double *p = a.part + (((size_t)(r0 + r) * N + t) * WT_SLOTS + slot) * WD_PART;
-            const int e = threadIdx.x;
-            double v = 0.0;
-            for (int w2 = 0; w2 < WT_WAVES; ++w2) v += sh[w2][e];
-            p[e] += v;
-            if (CROSS) {
-                v = 0.0;
-                for (int w2 = 0; w2 < WT_WAVES; ++w2) v += sh[w2][256 + e];
-                p[WD_O_WZ + e] += v;
-            }
-            if (e < 16) {
-                v = 0.0;
-                for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][512 + k2 * 16 + e];
-                p[WD_O_S1W + e] += v;
-            } else if (e < 32) {
-                if (CROSS) {
-                    v = 0.0;
-                    for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][576 + k2 * 16 + (e - 16)];
-                    p[WD_O_S1Z + (e - 16)] += v;
-                }
-            } else if (e == 32 || e == 33) {
-                v = 0.0;
-                for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][(e == 32 ? 640 : 644) + k2];
-                p[(e == 32) ? WD_O_S0 : WD_O_SY2] += v;
-            }
+    __device__ __forceinline__ void row(wt_d4 (&C)[TILES], double (&v)[VECS], double (&)[SCALARS], double y, bool has, const Dev &d) const {
+        const double Dwr = has ? d.Dw : 0.0, yd = has ? y * d.Dw : 0.0;
+        C[0] = wt_mfma(yd, Dwr, C[0]);
+        if constexpr (CROSS) {
+            const double Dzr = has ? d.Dz : 0.0;
+            C[1] = wt_mfma(yd, Dzr, C[1]);
+            v[1] += has ? y * d.Dz : 0.0;
         }
+        v[0] += yd;
     }
-}
+};
 
 template <bool CROSS>
-__global__ __launch_bounds__(WT_WAVES * 64) void wcd_moments(WdArgs a) { wcd_moments_body<CROSS, false>(a, nullptr); }
+__global__ __launch_bounds__(WT_WAVES * 64) void wcd_moments(WdArgs a) { moments_body<DisturbanceMoments<CROSS>, false>(DisturbanceMoments<CROSS>(a), a.t, nullptr); }
 template <bool CROSS>
-__global__ __launch_bounds__(WT_WAVES * 64) void tld_moments(WdArgs a, const unsigned *live) { wcd_moments_body<CROSS, true>(a, live); }
+__global__ __launch_bounds__(WT_WAVES * 64) void tld_moments(WdArgs a, const unsigned *live) { moments_body<DisturbanceMoments<CROSS>, true>(DisturbanceMoments<CROSS>(a), a.t, live); }
 
 __global__ __launch_bounds__(MC_THREADS) void wcd_final(WdArgs a) {
     __shared__ double S[WD_PART];
     const int t = blockIdx.x, r = blockIdx.y, e = threadIdx.x, N = a.t.N, n = a.t.n, d = a.t.n + a.t.m;
-    const double *p = a.part + ((size_t)r * N + t) * WT_SLOTS * WD_PART;
-    for (int q = e; q < WD_PART; q += MC_THREADS) {
-        double v = 0.0;
-        for (int s = 0; s < WT_SLOTS; ++s) v += p[s * WD_PART + q];
-        S[q] = v;
-    }
-    __syncthreads();
-    const double st = a.t.wc[WC_O_INFO + 2 * r + 1], nan = __builtin_nan("");
-    const bool dead = (st == WC_ST_EMPTY || st == WC_ST_NONFINITE);
+    slot_sum<WD_PART>(a.part + ((size_t)r * N + t) * WT_SLOTS * WD_PART, S);
+    const double nan = __builtin_nan("");
+    const bool dead = row_dead(a.t.wc, r);
     const double s0 = S[WD_O_S0];
     const size_t o = (size_t)r * N + t;
     if (e < n * n) {                                                  // column-major; the upper triangle of the tile serves both halves
@@ -1063,24 +1067,13 @@ __global__ __launch_bounds__(MC_THREADS) void wcd_final(WdArgs a) {
     if (t == 0 && e == 0) { a.ess[2 * r] = s0; a.ess[2 * r + 1] = S[WD_O_SY2]; }
 }
 
-// ---- rat_policy_worst_case_params: weighted moments of the rollouts' drawn parameters ----------------------------------------------------
-// wct_moments' schedule and lane layout with one step and up to two tiles of sixteen parameters per lane: lane (i, kk) holds Dq_i (tile 0)
-// and Dq_{16 + i} (tile 1, TWO) of rollout 4 g + kk.  Per group and row A0 = y Dq(tile 0), B0 = Dq(tile 0) give block (0,0) of
-// sum y Dq Dq'; with TWO, A0 and B1 give block (0,1) and A1, B1 block (1,1); block (1,0) is (0,1)' and is never formed.  S1, S0, sum y^2
-// and, with CROSS, sum y DJ, sum y DJ^2, sum y DJ Dq ride along in the same lanes.  Padding lanes (parameter index >= P) and padding
-// rollouts enter as exact zeros; a rollout without a cost is selected out (its q may hold NaN).  The same order as wct_moments: a
-// wavefront's groups in order, wavefronts and rollout lanes in index order through LDS, chunk after chunk in stream order, the slots in
-// wcp_final.  The centres: wcd_centre's rule, for q and for J.
-#define WP_SH (768 + 4 * 64 + 16)   /* LDS doubles per wavefront and row: three blocks | S1 and SJq per lane and tile | S0, sum y^2, SJ, SJ2 [4] each */
-
+// ---- rat_policy_worst_case_params: one step, Dq = q - c_q in up to two tiles of sixteen parameters per lane ----------------------------------
+// Lane (i, kk) holds Dq_i (tile 0) and Dq_{16 + i} (tile 1, TWO) of rollout 4 g + kk.  Per group and row A0 = y Dq(tile 0), B0 = Dq(tile 0)
+// give block (0,0) of sum y Dq Dq'; with TWO, A0 and B1 give block (0,1) and A1, B1 block (1,1); block (1,0) is (0,1)' and is never
+// formed.  S1 per tile and, with CROSS, sum y DJ Dq per tile ride along in the lanes, sum y DJ and sum y DJ^2 in the rollout lanes.
+// Padding lanes (parameter index >= P) and padding rollouts enter as exact zeros.  The centres: first_with_cost's rollout, for q and for J.
 __global__ __launch_bounds__(MC_THREADS) void wcp_centre(WpArgs a) {
-    __shared__ int first;
-    if (threadIdx.x == 0) first = WD_NONE;
-    __syncthreads();
-    for (long q = threadIdx.x; q < a.t.kc; q += MC_THREADS)
-        if (!mc_nan(a.t.cost[q])) { atomicMin(&first, (int)q); break; }                  // (an integer minimum: no order in it)
-    __syncthreads();
-    const int q = first;
+    const int q = first_with_cost(a.t.cost, a.t.kc);
     for (int e = threadIdx.x; e < WP_NCENTRE; e += MC_THREADS) {
         double v = 0.0;
         if (q != WD_NONE && e < a.P) v = a.qs[(long)q * a.P + e];
@@ -1090,122 +1083,60 @@ __global__ __launch_bounds__(MC_THREADS) void wcp_centre(WpArgs a) {
     }
 }
 
-template <bool TWO, bool CROSS, bool TAIL>                           // (TAIL: the liveness schedule, as wct_moments_body has it)
-__device__ __forceinline__ void wcp_moments_body(const WpArgs &a, const unsigned *lv) {
-    __shared__ double sh[WT_WAVES][WP_SH];
-    const int slot = blockIdx.x, r0 = blockIdx.y * WT_ROWS;
-    const int nrows = a.t.nrows, P = a.P;
-    const int nr = (nrows - r0 < WT_ROWS) ? nrows - r0 : WT_ROWS;
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
-    const bool comp0 = i < P, comp1 = TWO && 16 + i < P;             // (padding lanes stay zero)
-    const double c0 = a.centre[i], c1 = a.centre[16 + i], cJ = a.centre[WP_MAXP];
-    wt_d4 a00[WT_ROWS], a01[WT_ROWS], a11[WT_ROWS];
-    double s1a[WT_ROWS], s1b[WT_ROWS], sqa[WT_ROWS], sqb[WT_ROWS], s0[WT_ROWS], sy2[WT_ROWS], sj[WT_ROWS], sj2[WT_ROWS];
-#pragma unroll
-    for (int r = 0; r < WT_ROWS; ++r) {
-        a00[r] = (wt_d4){0.0, 0.0, 0.0, 0.0}; a01[r] = (wt_d4){0.0, 0.0, 0.0, 0.0}; a11[r] = (wt_d4){0.0, 0.0, 0.0, 0.0};
-        s1a[r] = 0.0; s1b[r] = 0.0; sqa[r] = 0.0; sqb[r] = 0.0; s0[r] = 0.0; sy2[r] = 0.0; sj[r] = 0.0; sj2[r] = 0.0;
-    }
-    const long kc = a.t.kc, G = (kc + 3) >> 2;
-    for (long g = (long)slot * WT_WAVES + w; g < G; g += (long)WT_SLOTS * WT_WAVES) {      // (uniform over the wavefront)
-        unsigned on = 0xffu;
-        if (TAIL) {
-            on = (unsigned)__builtin_amdgcn_readfirstlane((int)((lv[g] >> r0) & 0xffu));
-            if (on == 0u) continue;                                   // dead in every row of the workgroup: nothing is loaded
-        }
-        const long q = 4 * g + kk;
-        const bool live = q < kc;                                     // (the K tail)
-        const double J = live ? a.t.cost[q] : 0.0;
-        const bool ok = live && !mc_nan(J);                           // selected, not multiplied: q may hold NaN
+template <bool TWO, bool CROSS>
+struct ParamMoments {
+    static constexpr int NQ = TWO ? 2 : 1;                            // parameter tiles: vectors 0 .. NQ - 1 are S1, NQ .. 2 NQ - 1 (CROSS) are SJq
+    static constexpr int TILES = TWO ? 3 : 1, VECS = CROSS ? 2 * NQ : NQ, SCALARS = CROSS ? 4 : 2;
+    static __device__ __forceinline__ constexpr int o_tile(int b) { return b * 256; }
+    static __device__ __forceinline__ constexpr int o_vec(int b) { return b < NQ ? WP_O_S1 + b * 16 : WP_O_SJQ + (b - NQ) * 16; }
+    static __device__ __forceinline__ constexpr int o_scalar(int s) { return WP_O_S0 + s; }   // S0, sum y^2, SJ, SJ2
+    static __device__ __forceinline__ int batch() { return blockIdx.y; }
+    struct Dev { double D0, D1, DJ; };
+    const WpArgs &a;
+    const int i;
+    const bool comp0, comp1;
+    const double c0, c1, cJ;
+    __device__ __forceinline__ ParamMoments(const WpArgs &a_)
+        : a(a_), i(threadIdx.x & 15), comp0(i < a_.P), comp1(TWO && 16 + i < a_.P),          // (padding lanes stay zero)
+          c0(a_.centre[i]), c1(a_.centre[16 + i]), cJ(a_.centre[WP_MAXP]) {}
+    __device__ __forceinline__ double *part(int row, int slot) const { return a.part + ((size_t)row * WT_SLOTS + slot) * WP_PART; }
+    __device__ __forceinline__ Dev load(long q, bool ok, double J) const {
         double D0 = 0.0, D1 = 0.0;
-        if (ok && comp0) D0 = a.qs[q * P + i] - c0;
-        if (TWO && ok && comp1) D1 = a.qs[q * P + 16 + i] - c1;
-        const double DJ = (CROSS && ok) ? J - cJ : 0.0;
-#pragma unroll
-        for (int r = 0; r < WT_ROWS; ++r) {
-            if (r < nr && (!TAIL || ((on >> r) & 1u))) {              // (uniform over the workgroup; with TAIL over the wavefront)
-                const double y = ok ? a.t.y[(long)(r0 + r) * a.t.ldy + q] : 0.0;
-                const bool has = !TAIL || y != 0.0;
-                const double D0r = has ? D0 : 0.0, yd0 = has ? y * D0 : 0.0;
-                a00[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd0, D0r, a00[r], 0, 0, 0);
-                s1a[r] += yd0;
-                const double D1r = (TWO && has) ? D1 : 0.0;
-                if (TWO) {
-                    const double yd1 = has ? y * D1 : 0.0;
-                    a01[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd0, D1r, a01[r], 0, 0, 0);
-                    a11[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(yd1, D1r, a11[r], 0, 0, 0);
-                    s1b[r] += yd1;
-                }
-                s0[r] += y; sy2[r] += y * y;
-                if (CROSS) {
-                    const double yj = y * DJ;
-                    sj[r] += yj; sj2[r] += yj * DJ; sqa[r] += yj * D0r;
-                    if (TWO) sqb[r] += yj * D1r;
-                }
-            }
+        if (ok && comp0) D0 = a.qs[q * a.P + i] - c0;
+        if (TWO && ok && comp1) D1 = a.qs[q * a.P + 16 + i] - c1;
+        return Dev{D0, D1, (CROSS && ok) ? J - cJ : 0.0};
+    }
+    __device__ __forceinline__ void row(wt_d4 (&C)[TILES], double (&v)[VECS], double (&s)[SCALARS], double y, bool has, const Dev &d) const {
+        const double D0r = has ? d.D0 : 0.0, yd0 = has ? y * d.D0 : 0.0;
+        C[0] = wt_mfma(yd0, D0r, C[0]);
+        v[0] += yd0;
+        const double D1r = (TWO && has) ? d.D1 : 0.0;
+        if constexpr (TWO) {
+            const double yd1 = has ? y * d.D1 : 0.0;
+            C[1] = wt_mfma(yd0, D1r, C[1]);
+            C[2] = wt_mfma(yd1, D1r, C[2]);
+            v[1] += yd1;
+        }
+        if constexpr (CROSS) {
+            const double yj = y * d.DJ;
+            s[2] += yj; s[3] += yj * d.DJ; v[NQ] += yj * D0r;
+            if constexpr (TWO) v[NQ + 1] += yj * D1r;
         }
     }
-#pragma unroll
-    for (int r = 0; r < WT_ROWS; ++r) {
-        if (r < nr) {
-            __syncthreads();                                          // (the previous row's sums are read)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {                       // C: row (lane >> 4) + 4 reg, column lane & 15
-                sh[w][(kk + 4 * reg) * 16 + i] = a00[r][reg];
-                if (TWO) { sh[w][256 + (kk + 4 * reg) * 16 + i] = a01[r][reg]; sh[w][512 + (kk + 4 * reg) * 16 + i] = a11[r][reg]; }
-            }
-            sh[w][768 + lane] = s1a[r];
-            if (TWO) sh[w][832 + lane] = s1b[r];
-            if (CROSS) { sh[w][896 + lane] = sqa[r]; if (TWO) sh[w][960 + lane] = sqb[r]; }
-            if (i == 0) {
-                sh[w][1024 + kk] = s0[r]; sh[w][1028 + kk] = sy2[r];
-                if (CROSS) { sh[w][1032 + kk] = sj[r]; sh[w][1036 + kk] = sj2[r]; }
-            }
-            __syncthreads();
-            double *p = a.part + ((size_t)(r0 + r) * WT_SLOTS + slot) * WP_PART;
-            const int e = threadIdx.x;
-            for (int b = 0; b < (TWO ? 3 : 1); ++b) {
-                double v = 0.0;
-                for (int w2 = 0; w2 < WT_WAVES; ++w2) v += sh[w2][b * 256 + e];
-                p[b * 256 + e] += v;
-            }
-            if (e < 64) {                                             // S1 [32], then SJq [32]: tile e2 >> 4, component e2 & 15
-                const int e2 = e & 31, o = (e < 32 ? 768 : 896) + (e2 >> 4) * 64 + (e2 & 15);
-                if ((TWO || e2 < 16) && (CROSS || e < 32)) {
-                    double v = 0.0;
-                    for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][o + k2 * 16];
-                    p[(e < 32 ? WP_O_S1 : WP_O_SJQ) + e2] += v;
-                }
-            } else if (e < 68) {                                      // S0, sum y^2, SJ, SJ2
-                const int s = e - 64;
-                if (CROSS || s < 2) {
-                    double v = 0.0;
-                    for (int w2 = 0; w2 < WT_WAVES; ++w2) for (int k2 = 0; k2 < 4; ++k2) v += sh[w2][1024 + 4 * s + k2];
-                    p[WP_O_S0 + s] += v;
-                }
-            }
-        }
-    }
-}
+};
 
 template <bool TWO, bool CROSS>
-__global__ __launch_bounds__(WT_WAVES * 64) void wcp_moments(WpArgs a) { wcp_moments_body<TWO, CROSS, false>(a, nullptr); }
+__global__ __launch_bounds__(WT_WAVES * 64) void wcp_moments(WpArgs a) { moments_body<ParamMoments<TWO, CROSS>, false>(ParamMoments<TWO, CROSS>(a), a.t, nullptr); }
 template <bool TWO, bool CROSS>
-__global__ __launch_bounds__(WT_WAVES * 64) void tlp_moments(WpArgs a, const unsigned *live) { wcp_moments_body<TWO, CROSS, true>(a, live); }
+__global__ __launch_bounds__(WT_WAVES * 64) void tlp_moments(WpArgs a, const unsigned *live) { moments_body<ParamMoments<TWO, CROSS>, true>(ParamMoments<TWO, CROSS>(a), a.t, live); }
 
 __global__ __launch_bounds__(MC_THREADS) void wcp_final(WpArgs a) {
 #pragma clang fp contract(off)                                        // S2 / S0 - m m' with m m' rounded: where one rollout carries all the weight the two are the same product, and the covariance is exactly 0
     __shared__ double S[WP_PART];
     const int r = blockIdx.x, e0 = threadIdx.x, P = a.P;
-    const double *p = a.part + (size_t)r * WT_SLOTS * WP_PART;
-    for (int q = e0; q < WP_PART; q += MC_THREADS) {
-        double v = 0.0;
-        for (int s = 0; s < WT_SLOTS; ++s) v += p[s * WP_PART + q];
-        S[q] = v;
-    }
-    __syncthreads();
-    const double st = a.t.wc[WC_O_INFO + 2 * r + 1], nan = __builtin_nan("");
-    const bool dead = (st == WC_ST_EMPTY || st == WC_ST_NONFINITE);
+    slot_sum<WP_PART>(a.part + (size_t)r * WT_SLOTS * WP_PART, S);
+    const double nan = __builtin_nan("");
+    const bool dead = row_dead(a.t.wc, r);
     const double s0 = S[WP_O_S0];
     for (int e = e0; e < P * P; e += MC_THREADS) {                    // column-major; the upper triangle serves both halves, block (0,1) block (1,0)
         const int ii = e % P, jj = e / P;
@@ -1443,9 +1374,16 @@ void launch_wct_weights(const WtArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(wct_weights, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(MC_THREADS), 0, s, a);
 }
 
-void launch_wct_chunk(const WtArgs &a, hipStream_t s) {
+// a chunk's sums behind its weights: the dense kernel, or (live: the chunk's liveness words) its tail sibling
+template <class A>
+static void launch_moments(void (*dense)(A), void (*tail)(A, const unsigned *), dim3 grid, const A &a, const unsigned *live, hipStream_t s) {
+    if (live) hipLaunchKernelGGL(tail, grid, dim3(WT_WAVES * 64), 0, s, a, live);
+    else hipLaunchKernelGGL(dense, grid, dim3(WT_WAVES * 64), 0, s, a);
+}
+
+void launch_wct_chunk(const WtArgs &a, const unsigned *live, hipStream_t s) {
     if (a.kc <= 0 || a.nrows <= 0) return;
-    hipLaunchKernelGGL(wct_moments, dim3(WT_SLOTS, (unsigned)(a.N + 1), (unsigned)((a.nrows + WT_ROWS - 1) / WT_ROWS)), dim3(WT_WAVES * 64), 0, s, a);
+    launch_moments(wct_moments, tlt_moments, dim3(WT_SLOTS, (unsigned)(a.N + 1), (unsigned)((a.nrows + WT_ROWS - 1) / WT_ROWS)), a, live, s);
 }
 
 void launch_wct_final(const WtArgs &a, hipStream_t s) {
@@ -1456,11 +1394,11 @@ void launch_wcd_centre(const WdArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(wcd_centre, dim3(1), dim3(MC_THREADS), 0, s, a);
 }
 
-void launch_wcd_chunk(const WdArgs &a, hipStream_t s) {
+void launch_wcd_chunk(const WdArgs &a, const unsigned *live, hipStream_t s) {
     if (a.t.kc <= 0) return;
     const dim3 grid(WT_SLOTS, (unsigned)a.t.N, (unsigned)((a.t.nrows + WT_ROWS - 1) / WT_ROWS));
-    if (a.cross) hipLaunchKernelGGL(wcd_moments<true>, grid, dim3(WT_WAVES * 64), 0, s, a);
-    else hipLaunchKernelGGL(wcd_moments<false>, grid, dim3(WT_WAVES * 64), 0, s, a);
+    if (a.cross) launch_moments(wcd_moments<true>, tld_moments<true>, grid, a, live, s);
+    else launch_moments(wcd_moments<false>, tld_moments<false>, grid, a, live, s);
 }
 
 void launch_wcd_final(const WdArgs &a, hipStream_t s) {
@@ -1471,15 +1409,15 @@ void launch_wcp_centre(const WpArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(wcp_centre, dim3(1), dim3(MC_THREADS), 0, s, a);
 }
 
-void launch_wcp_chunk(const WpArgs &a, hipStream_t s) {
+void launch_wcp_chunk(const WpArgs &a, const unsigned *live, hipStream_t s) {
     if (a.t.kc <= 0) return;
-    const dim3 grid(WT_SLOTS, (unsigned)((a.t.nrows + WT_ROWS - 1) / WT_ROWS)), block(WT_WAVES * 64);
+    const dim3 grid(WT_SLOTS, (unsigned)((a.t.nrows + WT_ROWS - 1) / WT_ROWS));
     if (a.P > 16) {
-        if (a.cross) hipLaunchKernelGGL((wcp_moments<true, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((wcp_moments<true, false>), grid, block, 0, s, a);
+        if (a.cross) launch_moments(wcp_moments<true, true>, tlp_moments<true, true>, grid, a, live, s);
+        else launch_moments(wcp_moments<true, false>, tlp_moments<true, false>, grid, a, live, s);
     } else {
-        if (a.cross) hipLaunchKernelGGL((wcp_moments<false, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((wcp_moments<false, false>), grid, block, 0, s, a);
+        if (a.cross) launch_moments(wcp_moments<false, true>, tlp_moments<false, true>, grid, a, live, s);
+        else launch_moments(wcp_moments<false, false>, tlp_moments<false, false>, grid, a, live, s);
     }
 }
 
@@ -1495,30 +1433,6 @@ void launch_tlt_weights(const WtArgs &a, unsigned *live, hipStream_t s) {
     if (a.kc <= 0 || a.nrows <= 0) return;
     const long nb = (a.kc + MC_THREADS - 1) / MC_THREADS;
     hipLaunchKernelGGL(tlt_weights, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(MC_THREADS), 0, s, a, live);
-}
-
-void launch_tlt_chunk(const WtArgs &a, const unsigned *live, hipStream_t s) {
-    if (a.kc <= 0 || a.nrows <= 0) return;
-    hipLaunchKernelGGL(tlt_moments, dim3(WT_SLOTS, (unsigned)(a.N + 1), (unsigned)((a.nrows + WT_ROWS - 1) / WT_ROWS)), dim3(WT_WAVES * 64), 0, s, a, live);
-}
-
-void launch_tld_chunk(const WdArgs &a, const unsigned *live, hipStream_t s) {
-    if (a.t.kc <= 0) return;
-    const dim3 grid(WT_SLOTS, (unsigned)a.t.N, (unsigned)((a.t.nrows + WT_ROWS - 1) / WT_ROWS));
-    if (a.cross) hipLaunchKernelGGL(tld_moments<true>, grid, dim3(WT_WAVES * 64), 0, s, a, live);
-    else hipLaunchKernelGGL(tld_moments<false>, grid, dim3(WT_WAVES * 64), 0, s, a, live);
-}
-
-void launch_tlp_chunk(const WpArgs &a, const unsigned *live, hipStream_t s) {
-    if (a.t.kc <= 0) return;
-    const dim3 grid(WT_SLOTS, (unsigned)((a.t.nrows + WT_ROWS - 1) / WT_ROWS)), block(WT_WAVES * 64);
-    if (a.P > 16) {
-        if (a.cross) hipLaunchKernelGGL((tlp_moments<true, true>), grid, block, 0, s, a, live);
-        else hipLaunchKernelGGL((tlp_moments<true, false>), grid, block, 0, s, a, live);
-    } else {
-        if (a.cross) hipLaunchKernelGGL((tlp_moments<false, true>), grid, block, 0, s, a, live);
-        else hipLaunchKernelGGL((tlp_moments<false, false>), grid, block, 0, s, a, live);
-    }
 }
 
 void launch_ev_chunk(const EvArgs &a, hipStream_t s) {

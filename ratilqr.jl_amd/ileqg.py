@@ -389,15 +389,7 @@ class Context:
         rows, mean, cov = np.zeros((R, nv.WC_NSTAT)), np.zeros((R, N + 1, n + m)), np.zeros((R, N + 1, n + m, n + m))
         nv.check(nv.lib().rat_policy_worst_case_trajectory(self.h, nv.P(d) if d.size else None, C.c_int32(d.size), nv.P(th) if th.size else None,
                                                            C.c_int32(th.size), nv.P(rows), nv.P(mean), nv.P(cov)))
-        cov = cov.transpose(0, 1, 3, 2)                               # (column-major blocks)
-
-        def part(sl):
-            r = {k: rows[sl, i].copy() for i, k in enumerate(nv.WC_SLOTS)}
-            r["flag"] = r["flag"].astype(np.int64)
-            r.update(mean_x=mean[sl, :, :n].copy(), cov_x=cov[sl, :, :n, :n].copy(), mean_u=mean[sl, :N, n:].copy(),
-                     cov_u=cov[sl, :N, n:, n:].copy(), cov_xu=cov[sl, :N, :n, n:].copy())
-            return r
-        return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)))
+        return self._wc_parts(rows, d.size, lambda sl, r: self._unpack_trajectory(mean[sl], cov[sl]))
 
     def policy_worst_case_disturbance(self, kl_bounds=(), thetas=(), cross=True):
         """What the adversary does to the noise (rat_policy_worst_case_disturbance): the mean and covariance of the disturbance w_t at every
@@ -414,18 +406,7 @@ class Context:
         wz = np.zeros((R, N, n + m, n)) if cross else None
         nv.check(nv.lib().rat_policy_worst_case_disturbance(self.h, nv.P(d) if d.size else None, C.c_int32(d.size), nv.P(th) if th.size else None,
                                                             C.c_int32(th.size), nv.P(rows), nv.P(mean), nv.P(cov), nv.P(wz)))
-        cov = cov.transpose(0, 1, 3, 2)                               # (column-major blocks)
-        if cross:
-            wz = wz.transpose(0, 1, 3, 2)                             # [R, N, n, n+m]
-
-        def part(sl):
-            r = {k: rows[sl, i].copy() for i, k in enumerate(nv.WC_SLOTS)}
-            r["flag"] = r["flag"].astype(np.int64)
-            r.update(mean_w=mean[sl].copy(), cov_w=cov[sl].copy())
-            if cross:
-                r.update(cov_wx=wz[sl, :, :, :n].copy(), cov_wu=wz[sl, :, :, n:].copy())
-            return r
-        return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)))
+        return self._wc_parts(rows, d.size, lambda sl, r: self._unpack_disturbance(mean[sl], cov[sl], wz[sl] if cross else None))
 
     def policy_worst_case_params(self, kl_bounds=(), thetas=(), cost=True):
         """What the adversary picks among the uncertain parameters (rat_policy_worst_case_params): the mean and covariance of the
@@ -444,16 +425,46 @@ class Context:
         qJ = np.zeros((R, P)) if cost else None
         nv.check(nv.lib().rat_policy_worst_case_params(self.h, nv.P(d) if d.size else None, C.c_int32(d.size), nv.P(th) if th.size else None,
                                                        C.c_int32(th.size), nv.P(rows), nv.P(mean), nv.P(cov), nv.P(qJ)))
-        cov = cov.transpose(0, 2, 1)                                  # (column-major blocks)
 
+        def moments(sl, r):
+            out = self._unpack_params(mean[sl], cov[sl], qJ[sl] if cost else None)
+            if cost:
+                out.update(explained_share=explained_share(out["cov_q"], out["cov_qJ"], r["tilt_var"]))
+            return out
+        return self._wc_parts(rows, d.size, moments)
+
+    # What a moment replay's worst-case call and its tail sibling share: the family's moments out of the C ABI's buffers (column-major
+    # blocks, the 12 + 4 layout's (x, u) split), as fresh arrays
+    @staticmethod
+    def _wc_parts(rows, n_bound, moments):
+        """{"bounds": part, "thetas": part} of a worst-case replay: policy_worst_case's row keys and moments(slice, rows so far)"""
         def part(sl):
             r = {k: rows[sl, i].copy() for i, k in enumerate(nv.WC_SLOTS)}
             r["flag"] = r["flag"].astype(np.int64)
-            r.update(mean_q=mean[sl].copy(), cov_q=cov[sl].copy())
-            if cost:
-                r.update(cov_qJ=qJ[sl].copy(), explained_share=explained_share(cov[sl], qJ[sl], r["tilt_var"]))
+            r.update(moments(sl, r))
             return r
-        return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)))
+        return dict(bounds=part(slice(0, n_bound)), thetas=part(slice(n_bound, rows.shape[0])))
+
+    def _unpack_trajectory(self, mean, cov):
+        n, N = self.n, self.N
+        cov = cov.transpose(0, 1, 3, 2)
+        return dict(mean_x=mean[:, :, :n].copy(), cov_x=cov[:, :, :n, :n].copy(), mean_u=mean[:, :N, n:].copy(),
+                    cov_u=cov[:, :N, n:, n:].copy(), cov_xu=cov[:, :N, :n, n:].copy())
+
+    def _unpack_disturbance(self, mean, cov, wz):
+        n = self.n
+        out = dict(mean_w=mean.copy(), cov_w=cov.transpose(0, 1, 3, 2).copy())
+        if wz is not None:
+            wz = wz.transpose(0, 1, 3, 2)                             # [R, N, n, n+m]
+            out.update(cov_wx=wz[:, :, :, :n].copy(), cov_wu=wz[:, :, :, n:].copy())
+        return out
+
+    @staticmethod
+    def _unpack_params(mean, cov, qJ):
+        out = dict(mean_q=mean.copy(), cov_q=cov.transpose(0, 2, 1).copy())
+        if qJ is not None:
+            out.update(cov_qJ=qJ.copy())
+        return out
 
     def _tail_rows(self, alphas):
         al = nv.f64(np.atleast_1d(np.asarray(alphas, dtype=np.float64))).ravel()
@@ -477,10 +488,8 @@ class Context:
         n, m, N, R = self.n, self.m, self.N, al.size
         mean, cov = np.zeros((R, N + 1, n + m)), np.zeros((R, N + 1, n + m, n + m))
         nv.check(nv.lib().rat_policy_tail_trajectory(self.h, nv.P(al) if al.size else None, C.c_int32(al.size), nv.P(rows), nv.P(mean), nv.P(cov)))
-        cov = cov.transpose(0, 1, 3, 2)                               # (column-major blocks)
         r = self._tail_part(rows)
-        r.update(mean_x=mean[:, :, :n].copy(), cov_x=cov[:, :, :n, :n].copy(), mean_u=mean[:, :N, n:].copy(),
-                 cov_u=cov[:, :N, n:, n:].copy(), cov_xu=cov[:, :N, :n, n:].copy())
+        r.update(self._unpack_trajectory(mean, cov))
         return r
 
     def policy_tail_disturbance(self, alphas, cross=True):
@@ -494,10 +503,7 @@ class Context:
         nv.check(nv.lib().rat_policy_tail_disturbance(self.h, nv.P(al) if al.size else None, C.c_int32(al.size), nv.P(rows), nv.P(mean), nv.P(cov),
                                                       nv.P(wz)))
         r = self._tail_part(rows)
-        r.update(mean_w=mean, cov_w=cov.transpose(0, 1, 3, 2).copy())  # (column-major blocks)
-        if cross:
-            wz = wz.transpose(0, 1, 3, 2)                             # [R, N, n, n+m]
-            r.update(cov_wx=wz[:, :, :, :n].copy(), cov_wu=wz[:, :, :, n:].copy())
+        r.update(self._unpack_disturbance(mean, cov, wz))
         return r
 
     def policy_tail_params(self, alphas, cost=True):
@@ -511,9 +517,7 @@ class Context:
         nv.check(nv.lib().rat_policy_tail_params(self.h, nv.P(al) if al.size else None, C.c_int32(al.size), nv.P(rows), nv.P(mean), nv.P(cov),
                                                  nv.P(qJ)))
         r = self._tail_part(rows)
-        r.update(mean_q=mean, cov_q=cov.transpose(0, 2, 1).copy())    # (column-major blocks)
-        if cost:
-            r.update(cov_qJ=qJ)
+        r.update(self._unpack_params(mean, cov, qJ))
         return r
 
     def policy_events(self, events, kl_bounds=(), thetas=(), want_steps=False, want_margins=False):
