@@ -1,7 +1,7 @@
 // source_events.h -- the evaluation kernel of rat_policy_events_user (include/ratilqr.h): the user's rat_user_event on the replayed
 // trajectories of a source model, in place of ev_eval's quadratic g (policy_mc.hip).  Compiled by hiprtc behind the user's source, which
 // defines RAT_USER_EVENT and rat_user_event; RAT_N, RAT_M and RAT_N_EVENT come from the command line.  A module of its own, compiled by the
-// first call that names an n_event.  The library embeds this header (Makefile: source_embed.inc).
+// first call that names an n_event.
 //
 // One lane per rollout of the chunk, walking t = 0 .. N: the lane loads its own row x_t (RAT_N doubles of xs [kc][N+1][ldx]) and u_t (RAT_M
 // doubles of us [kc][N][ldu]; zeros at t == N), sets g[0 .. 16) to NaN and calls rat_user_event once for all events.  An entry the function
@@ -13,15 +13,9 @@
 // load touches one or two 128-byte lines per lane and none is shared between lanes; the next step reads on in the same lines, so every
 // byte that comes from memory is used once, by the lane that fetched it.  The stores (margin, tau, mask) are coalesced over the lanes.
 #pragma once
-#include "source_args.h"
+#include "source_step.h"
 #include "source_params.h"
 
-#if !defined(RAT_N) || !defined(RAT_M)
-#error "RAT_N and RAT_M must be defined"
-#endif
-#if RAT_N > SRC_MAX_N || RAT_M > SRC_MAX_M
-#error "source models are compiled for n <= 12, m <= 4"
-#endif
 #ifndef RAT_USER_EVENT
 #error "the source does not define RAT_USER_EVENT: rat_policy_events_user needs '#define RAT_USER_EVENT' and rat_user_event(k, x, u, g, p)"
 #endif
@@ -29,27 +23,22 @@
 #error "rat_user_event is compiled for 1 .. 16 events (RAT_N_EVENT)"
 #endif
 
-__device__ inline bool srcev_nan(double v) { return v != v; }
-
 extern "C" __global__ __launch_bounds__(64) void rat_src_user_events(SrcEventArgs a) {
     const long q = (long)blockIdx.x * 64 + threadIdx.x;
     if (q >= a.kc) return;                                            // (the K tail: no lane works with another)
     const int N = a.N;
     const double nan = __builtin_nan("");
-    const bool ok = !srcev_nan(a.cost[q]);                            // selected, not multiplied: the trajectory may hold NaN
+    const bool ok = !src_nan(a.cost[q]);                              // selected, not multiplied: the trajectory may hold NaN
     const double *xq = a.xs + q * (N + 1) * a.ldx, *uq = a.us + q * N * a.ldu;
     double M[RAT_N_EVENT];
     int tau[RAT_N_EVENT];
-#ifdef RAT_USER_PARAMS_ON
-    // the rollout's parameters, formed again from its global index and the replayed evaluation's seed (or the stored injected draws): a
-    // handful of Philox blocks, no stored copy.  An overdraw or a NaN here was the rollout kernel's to report (the stored cost is NaN)
-    double qp[RAT_N_PARAMS];
+    // the rollout's parameters, where sampling is on, formed again from its global index and the replayed evaluation's seed (or the stored
+    // injected draws): a handful of Philox blocks, no stored copy.  An overdraw or a NaN here was the rollout kernel's to report (the stored
+    // cost is NaN)
+    src_rollout_params own;
     int pover = 0;
-    if (ok) (void)rat_src_params(q + a.j0, a.seed, a.zpn, a.zpu, a.p, qp, pover);
-#define SRCEV_P qp
-#else
-#define SRCEV_P a.p
-#endif
+    if (ok) (void)own.draw(q + a.j0, a.seed, a.zpn, a.zpu, a.p, pover);
+    const double *p = own.of(a.p);
 #pragma unroll
     for (int e = 0; e < RAT_N_EVENT; ++e) { M[e] = nan; tau[e] = -1; }
     for (int t = 0; t <= N; ++t) {
@@ -62,11 +51,11 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_events(SrcEventArg
             for (int i = 0; i < RAT_M; ++i) u[i] = (t < N) ? uq[(long)t * a.ldu + i] : 0.0;
 #pragma unroll
             for (int e = 0; e < 16; ++e) g[e] = nan;
-            rat_user_event(t, x, u, g, SRCEV_P);
+            rat_user_event(t, x, u, g, p);
 #pragma unroll
             for (int e = 0; e < RAT_N_EVENT; ++e) {
                 const double gv = g[e];
-                if (gv > M[e] || srcev_nan(M[e])) M[e] = gv;          // (a NaN g never replaces a number)
+                if (gv > M[e] || src_nan(M[e])) M[e] = gv;            // (a NaN g never replaces a number)
                 if (gv > 0.0) {
                     bits |= 1u << e;
                     if (tau[e] < 0) tau[e] = t;
@@ -82,7 +71,7 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_events(SrcEventArg
     for (int e = 0; e < RAT_N_EVENT; ++e) {
         a.margin[(long)e * a.ldy + q] = ok ? M[e] : nan;
         a.tau[(long)e * a.ldy + q] = ok ? tau[e] : -1;
-        if (M[e] > Ma || srcev_nan(Ma)) Ma = M[e];
+        if (M[e] > Ma || src_nan(Ma)) Ma = M[e];
         if (tau[e] >= 0 && (ta < 0 || tau[e] < ta)) ta = tau[e];
     }
     a.margin[(long)RAT_N_EVENT * a.ldy + q] = ok ? Ma : nan;

@@ -1,6 +1,6 @@
 // source_kernels.h -- the two model kernels of the runtime-compiled family (RAT_MODEL_SOURCE).  Compiled by hiprtc behind the user's
 // source, which defines rat_user_f / rat_user_c / rat_user_h (include/ratilqr.h, "Source models"); RAT_N, RAT_M come from the command
-// line.  The library embeds this header at build time (Makefile: source_embed.inc) -- nothing is read from disk at run time.
+// line.
 //
 // The kernels restate rollout_kernel and linearize_kernel (kernels.hip) for a model the library does not know at build time: same slots,
 // same candidate step sizes eps lambda^k (repeated multiplication), same d = maximum(norm(l_t - u_t)) with NaN propagation, same domain
@@ -8,18 +8,10 @@
 // Everything downstream -- sweeps, line-search selection, gather -- reads only those records, so it runs unchanged.
 #pragma once
 #include "rat_ad.h"
-#include "source_args.h"
-
-#if !defined(RAT_N) || !defined(RAT_M)
-#error "RAT_N and RAT_M must be defined"
-#endif
-#if RAT_N > SRC_MAX_N || RAT_M > SRC_MAX_M
-#error "source models are compiled for n <= 12, m <= 4"
-#endif
+#include "source_step.h"
 
 #define SRC_NZ (RAT_N + RAT_M)
 __device__ inline int src_pad(int i) { return i < RAT_N ? i : 12 + (i - RAT_N); }   // z index -> row / column of the padded 16-wide tile
-__device__ inline bool src_nan(double v) { return v != v; }
 
 // ---- rollout: one lane per trajectory, the state in registers ----------------------------------------------------------------------
 // (a one-step software prefetch of l, dl, xbar and L was measured: no change in solves/s at 2.5x the VGPRs; profiles/source_model.md)
@@ -65,17 +57,10 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rollout(SrcRollArgs a) 
             double dq[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const double *Lr = Lb + (long)t * LSTR + j * 12;
-                double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {                         // L_t (x_t - xbar_t)   (ileqg.jl:82), rollout_kernel's order
-                    a0 = __builtin_fma(Lr[q], dx[q], a0);
-                    a1 = __builtin_fma(Lr[4 + q], dx[4 + q], a1);
-                    a2 = __builtin_fma(Lr[8 + q], dx[8 + q], a2);
-                }
+                const double Ldx = src_gain_row(Lb + (long)t * LSTR + j * 12, dx);
                 const double c_l = lnom[(long)t * USTR + j];
                 const double lnew = c_l + eps * dlb[(long)t * USTR + j];   // l + eps dl   (:509)
-                u[j] = lnew + ((a0 + a1) + a2);
+                u[j] = lnew + Ldx;
                 const double du = c_l - u[j];
                 dq[j] = du * du;
             }

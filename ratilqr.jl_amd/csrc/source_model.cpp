@@ -14,7 +14,7 @@
 
 namespace {
 
-// the embedded headers (Makefile: source_embed.inc, raw string literals of the files)
+// the embedded headers (Makefile: source_embed.inc, raw string literals of the files of EMBED_H, then k_embed_texts and k_embed_names)
 #include "source_embed.inc"
 
 struct Rtc {
@@ -110,14 +110,9 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
     const std::string text = std::string(row.rng_shift ? "#define RAT_RNG_SHIFT 1\n" : "") +
                              "#include \"source_args.h\"\n#include \"rat_ad.h\"\n#include \"rat_rng.h\"\n#line 1 \"model.hip\"\n" + source +
                              "\n#line 1 \"" + row.header + "\"\n#include \"" + row.header + "\"\n";
-    const char *hdr[] = {k_embed_layout_h, k_embed_source_args_h, k_embed_rat_ad_h, k_embed_source_kernels_h, k_embed_rat_normal_h,
-                         k_embed_rat_philox_h, k_embed_rat_rng_h, k_embed_source_pets_h, k_embed_source_noisy_h, k_embed_source_user_noise_h,
-                         k_embed_source_rare_h, k_embed_source_events_h, k_embed_source_policy_h, k_embed_source_params_h};
-    const char *hdr_names[] = {"layout.h", "source_args.h", "rat_ad.h", "source_kernels.h", "rat_normal.h", "rat_philox.h", "rat_rng.h",
-                               "source_pets.h", "source_noisy.h", "source_user_noise.h", "source_rare.h", "source_events.h", "source_policy.h",
-                               "source_params.h"};
     hiprtcProgram prog = nullptr;
-    if (g_rtc.create(&prog, text.c_str(), "model.hip", (int)(sizeof(hdr) / sizeof(hdr[0])), hdr, hdr_names) != HIPRTC_SUCCESS) {
+    if (g_rtc.create(&prog, text.c_str(), "model.hip", (int)(sizeof(k_embed_texts) / sizeof(k_embed_texts[0])), k_embed_texts,
+                     k_embed_names) != HIPRTC_SUCCESS) {
         if (log) *log = "hiprtcCreateProgram failed";
         return done(RAT_ERR_ARG);
     }

@@ -1,21 +1,12 @@
 // source_noisy.h -- the Monte-Carlo rollout kernel of source models (rat_policy_evaluate, include/ratilqr.h).  Compiled by hiprtc behind the
 // user's source (rat_user_f / rat_user_c / rat_user_h; RAT_N, RAT_M from the command line) as a module of its own, on the first
 // rat_policy_evaluate of a source problem: a handle that never evaluates a policy never pays for it (as a third kernel of the model
-// module it lengthened that module's compile by 7-16 %, around and over the tenth allowed: DESIGN.md section 7, profiles/policy_mc.md).  The library embeds this header at build time (Makefile: source_embed.inc).
+// module it lengthened that module's compile by 7-16 %, around and over the tenth allowed: DESIGN.md section 7, profiles/policy_mc.md).
 #pragma once
 #include "rat_normal.h"
 #include "rat_philox.h"
-#include "source_args.h"
+#include "source_step.h"
 #include "source_policy.h"
-
-#if !defined(RAT_N) || !defined(RAT_M)
-#error "RAT_N and RAT_M must be defined"
-#endif
-#if RAT_N > SRC_MAX_N || RAT_M > SRC_MAX_M
-#error "source models are compiled for n <= 12, m <= 4"
-#endif
-
-__device__ inline bool srcn_nan(double v) { return v != v; }
 
 // ---- noisy rollout: one lane per Monte-Carlo rollout, the state in registers ------------------------------------------------------------
 // noisy_rollout_kernel (kernels.hip) restated for a model the library does not know at build time: x_{t+1} = f(x_t, u_t) + chol_lower(W(t)) z_t
@@ -48,15 +39,8 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_noisy_rollout(SrcNoisyA
             for (int q = 0; q < 12; ++q) dx[q] = x[q] - a.xnom[(long)t * XSTR + q];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const double *Lr = a.L + (long)t * LSTR + j * 12;
-                double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {                         // L_t (x_t - xbar_t)   (ileqg.jl:104), rat_src_rollout's order (source_kernels.h)
-                    a0 = __builtin_fma(Lr[q], dx[q], a0);
-                    a1 = __builtin_fma(Lr[4 + q], dx[4 + q], a1);
-                    a2 = __builtin_fma(Lr[8 + q], dx[8 + q], a2);
-                }
-                u[j] = a.l[(long)t * USTR + j] + ((a0 + a1) + a2);
+                const double Ldx = src_gain_row(a.L + (long)t * LSTR + j * 12, dx);
+                u[j] = a.l[(long)t * USTR + j] + Ldx;
             }
         } else {
 #pragma unroll
@@ -67,16 +51,16 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_noisy_rollout(SrcNoisyA
 #endif
         bool inok = true;
 #pragma unroll
-        for (int q = 0; q < RAT_N; ++q) inok = inok && !srcn_nan(x[q]);
+        for (int q = 0; q < RAT_N; ++q) inok = inok && !src_nan(x[q]);
 #pragma unroll
-        for (int q = 0; q < RAT_M; ++q) inok = inok && !srcn_nan(u[q]);
+        for (int q = 0; q < RAT_M; ++q) inok = inok && !src_nan(u[q]);
         const double ct = rat_user_c<double>(t, x, u, a.p);           // integrate_cost: c(t, x_t, u_t) in order   (ileqg.jl:118-121)
         cost += ct;
         double xn[RAT_N];
         rat_user_f<double>(x, u, xn, a.p);
-        bool outnan = srcn_nan(ct);
+        bool outnan = src_nan(ct);
 #pragma unroll
-        for (int q = 0; q < RAT_N; ++q) outnan = outnan || srcn_nan(xn[q]);
+        for (int q = 0; q < RAT_N; ++q) outnan = outnan || src_nan(xn[q]);
         if (inok && outnan) dom = 1;                                  // the reference's DomainError
         double z[RAT_N];
         if (a.z) {
@@ -104,9 +88,9 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_noisy_rollout(SrcNoisyA
     }
     bool inok = true;
 #pragma unroll
-    for (int q = 0; q < RAT_N; ++q) inok = inok && !srcn_nan(x[q]);
+    for (int q = 0; q < RAT_N; ++q) inok = inok && !src_nan(x[q]);
     const double hc = rat_user_h<double>(x, a.p);                     // ... then h(x_N)   (ileqg.jl:122)
-    if (inok && srcn_nan(hc)) dom = 1;
+    if (inok && src_nan(hc)) dom = 1;
     cost += hc;
     a.cost[k] = dom ? __builtin_nan("") : cost;
 }

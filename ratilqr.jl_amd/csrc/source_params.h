@@ -6,7 +6,7 @@
 // do not include it: they run on the nominal p.  Without RAT_USER_PARAMS_ON -- the state of every handle until
 // rat_policy_params_sampling switches sampling on -- the header is empty, whether or not the source defines the hook: the kernels
 // compile to what they compiled to before.  RAT_N_PARAMS, RAT_PARAM_NORMALS, RAT_PARAM_UNIFORMS come from the command line with
-// RAT_USER_PARAMS_ON.  The library embeds this header (Makefile: source_embed.inc).
+// RAT_USER_PARAMS_ON.  src_rollout_params at the end is what those kernels hold: the rollout's own q, or nothing with sampling off.
 //
 // The i-th parameter normal / uniform of the rollout with GLOBAL index g (independent of K and of how a call is cut into launches):
 //   injected   zpn[g RAT_PARAM_NORMALS + i],  zpu[g RAT_PARAM_UNIFORMS + i]   (the handle's copy of the caller's streams, whole)
@@ -16,6 +16,7 @@
 // rat_rng's pairing (rat_rng.h) under a step word no step uses, so the per-step draws keep their counters.  Never shifted: under
 // RAT_RNG_SHIFT the parameter normals come from N(0, 1) and add nothing to logw.
 #pragma once
+#include "source_step.h"
 
 #ifdef RAT_USER_PARAMS_ON
 #include "rat_normal.h"
@@ -79,11 +80,11 @@ __device__ __forceinline__ bool rat_src_params(long g, unsigned long long seed, 
     rng.in = 0; rng.iu = 0; rng.over = 0; rng.spare_n = 0.0; rng.spare_u = 0.0;
     bool inok = true;
 #pragma unroll
-    for (int i = 0; i < RAT_N_PARAMS; ++i) { q[i] = p[i]; inok = inok && !(q[i] != q[i]); }
+    for (int i = 0; i < RAT_N_PARAMS; ++i) { q[i] = p[i]; inok = inok && !src_nan(q[i]); }
     rat_user_params(rng, p, q);
     bool outnan = false;
 #pragma unroll
-    for (int i = 0; i < RAT_N_PARAMS; ++i) outnan = outnan || (q[i] != q[i]);
+    for (int i = 0; i < RAT_N_PARAMS; ++i) outnan = outnan || src_nan(q[i]);
     over |= rng.over << 2;
     return inok && outnan;
 }
@@ -104,3 +105,19 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_params_sample(SrcParams
 #elif defined(RAT_PARAMS_SAMPLE_KERNEL)
 #error "rat_policy_params_sample is compiled with parameter sampling on"
 #endif
+
+// What a rollout hands the user's functions as p: the problem's, or with parameter sampling on its own, drawn once in front of step 0.
+// Without RAT_USER_PARAMS_ON the type is empty, draw() does nothing and of() is its argument: no q[] exists.
+struct src_rollout_params {
+#ifdef RAT_USER_PARAMS_ON
+    double q[RAT_N_PARAMS];
+    // rat_src_params: true for the DomainError of a NaN parameter; the hook's overdraw bits go to `over`
+    __device__ __forceinline__ bool draw(long g, unsigned long long seed, const double *zpn, const double *zpu, const double *p, int &over) {
+        return rat_src_params(g, seed, zpn, zpu, p, q, over);
+    }
+    __device__ __forceinline__ const double *of(const double *) const { return q; }
+#else
+    __device__ __forceinline__ bool draw(long, unsigned long long, const double *, const double *, const double *, int &) { return false; }
+    __device__ __forceinline__ const double *of(const double *p) const { return p; }
+#endif
+};

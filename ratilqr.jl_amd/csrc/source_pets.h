@@ -1,6 +1,6 @@
 // source_pets.h -- the rollout kernel of generative source models (PETS, include/ratilqr.h "Generative source models").  Compiled by hiprtc
 // behind rat_rng.h and the user's source, which defines rat_user_f_stochastic / rat_user_c / rat_user_h; RAT_N, RAT_M, RAT_PETS_NORMALS,
-// RAT_PETS_UNIFORMS come from the command line.  The library embeds this header at build time (Makefile: source_embed.inc).
+// RAT_PETS_UNIFORMS come from the command line.
 //
 // rat_src_pets_rollout restates compute_cost_worker (pets.jl:76-98) for a model the library does not know at build time: one lane per
 // trajectory, the state in registers, the K trajectories of a control sample on consecutive lanes (they share its control loads); each
@@ -8,14 +8,7 @@
 // family's pets_mean_kernel (kernels.hip), launched after this kernel.
 #pragma once
 #include "rat_rng.h"
-#include "source_args.h"
-
-#if !defined(RAT_N) || !defined(RAT_M)
-#error "RAT_N and RAT_M must be defined"
-#endif
-#if RAT_N > SRC_MAX_N || RAT_M > SRC_MAX_M
-#error "source models are compiled for n <= 12, m <= 4"
-#endif
+#include "source_step.h"
 
 extern "C" __global__ __launch_bounds__(64) void rat_src_pets_rollout(SrcPetsArgs a) {
     const int lane = threadIdx.x;

@@ -4,7 +4,8 @@
 // law and in front of everything that reads u -- the trajectory outputs, the cost, the sampler, f, the events.  The solver's own kernels
 // (source_kernels.h), PETS (source_pets.h) and rat_src_user_events (source_events.h, which reads the u a rollout kernel wrote) do not
 // include it: iLEQG stays the reference's algorithm.  Without RAT_USER_POLICY the header is empty and the kernels hold no u_prev: a
-// source without the hook compiles to what it compiled to before.  The library embeds this header (Makefile: source_embed.inc).
+// source without the hook compiles to what it compiled to before.  The NaN tests below stay spelt out, not src_nan (source_step.h): with
+// the predicate one row of the kernels' resource table moves (profiles/source_step.md).
 #pragma once
 
 #ifdef RAT_USER_POLICY

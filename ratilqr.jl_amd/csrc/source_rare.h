@@ -2,13 +2,15 @@
 // normals drawn from a shifted proposal, and the margin of one safety event in place of the trajectory and the cost.  Compiled by hiprtc
 // behind rat_rng.h -- with RAT_RNG_SHIFT, which this module alone defines (source_model.cpp puts it in front of rat_rng.h) -- and the
 // user's source, which defines RAT_USER_NOISE and rat_user_noise; RAT_N, RAT_M, RAT_PETS_NORMALS, RAT_PETS_UNIFORMS come from the command
-// line.  A module of its own, compiled by the first call that needs it.  The library embeds this header (Makefile: source_embed.inc).
+// line.  A module of its own, compiled by the first call that needs it.
 //
 // Rollout part: one lane per rollout, the step of rat_src_user_noisy_rollout (source_user_noise.h) operation for operation -- the
-// feedback sums in its order, c, the sampler, f, its DomainError rule (c and h are evaluated for that rule alone: no cost is formed) --
-// with the generator keyed as there: the global rollout index in the Philox counter, the pass's seed as the key.  rng.normal() returns
-// shift[t][i] + xi and adds -s z + s^2 / 2 to the lane's logw (rat_rng.h); the step's shift row is one address for the wavefront, so
-// its loads are scalar or broadcast.
+// feedback sums in its order (src_affine of source_step.h here, the same sums written out there), c, the sampler, f, its DomainError
+// rule (c and h are evaluated for that rule alone: no cost is formed).  The step is a second text, not a shared function (a shared one
+// moves the registers of both kernels: profiles/source_step.md), so "operation for operation" is kept by hand and watched by
+// tests/test_gpu_rare_event_noise.py.  The generator is keyed as there: the global rollout index in the Philox counter, the pass's seed
+// as the key.  rng.normal() returns shift[t][i] + xi and adds -s z + s^2 / 2 to the lane's logw (rat_rng.h); the step's shift row is one
+// address for the wavefront, so its loads are scalar or broadcast.
 // Margin part: g(t, z) = z' Q z + a' z + b of z = (x_t, u_t) as ev_eval (policy_mc.hip) and re_g (rare_event.hip) form it, so that under
 // a zero shift the margins are rat_policy_events' bit for bit.  Every lane puts its (x_t, u_t) in the 12 + 4 tile order into row `lane`
 // of a wavefront-private LDS block (64 rows, stride 17: the sixteen columns of a group fall in different banks); the wavefront then
@@ -21,16 +23,10 @@
 // NaN, entry a.event is the step's g, every step 0 .. N is watched.  No LDS, no MFMA, no butterfly: no lane works with another.
 #pragma once
 #include "rat_rng.h"
-#include "source_args.h"
+#include "source_step.h"
 #include "source_policy.h"
 #include "source_params.h"
 
-#if !defined(RAT_N) || !defined(RAT_M)
-#error "RAT_N and RAT_M must be defined"
-#endif
-#if RAT_N > SRC_MAX_N || RAT_M > SRC_MAX_M
-#error "source models are compiled for n <= 12, m <= 4"
-#endif
 #ifndef RAT_RNG_SHIFT
 #error "source_rare.h is compiled with RAT_RNG_SHIFT in front of rat_rng.h"
 #endif
@@ -54,8 +50,6 @@
 #define SRCRE_SYNC() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront")
 
 typedef double srcre_d4 __attribute__((ext_vector_type(4)));
-
-__device__ inline bool srcre_nan(double v) { return v != v; }
 
 // __shfl_xor(v, mask) over the 64 lanes (no <hip/hip_runtime.h> under hiprtc): both halves through ds_bpermute
 __device__ __forceinline__ double srcre_xor(double v, int lane, int mask) {
@@ -85,15 +79,6 @@ __device__ __forceinline__ double srcre_g(const double (&zv)[4], const double *s
     p += srcre_xor(p, lane, 32);
     return p + b;
 }
-#else
-__device__ inline bool srcre_nan(double v) { return v != v; }
-#endif
-
-// what the rollout hands the user's functions as p: the rollout's own parameters (source_params.h) or the problem's
-#ifdef RAT_USER_PARAMS_ON
-#define SRCRE_P q
-#else
-#define SRCRE_P a.p
 #endif
 
 extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArgs a) {
@@ -124,12 +109,11 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
     const double nan = __builtin_nan("");
     double M = nan;
     int dom = 0;
-#ifdef RAT_USER_PARAMS_ON
-    // this rollout's parameters, drawn once in front of step 0 from N(0, 1) / U[0, 1): never shifted, nothing added to logw (a lane without
-    // a rollout calls none of the user's functions and holds nothing here)
-    double q[RAT_N_PARAMS];
-    if (live && rat_src_params(j, a.seed, a.zpn, a.zpu, a.p, q, rng.over)) dom = 1;
-#endif
+    // this rollout's parameters, where sampling is on, from N(0, 1) / U[0, 1): never shifted, nothing added to logw (a lane without a
+    // rollout calls none of the user's functions and holds nothing here)
+    src_rollout_params own;
+    if (live && own.draw(j, a.seed, a.zpn, a.zpu, a.p, rng.over)) dom = 1;
+    const double *p = own.of(a.p);
 #ifdef RAT_USER_POLICY
     double up[4] = {0.0, 0.0, 0.0, 0.0};                              // the control applied at step t - 1
 #endif
@@ -139,28 +123,9 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
     for (int t = 0;; ++t) {
         double u[4] = {0.0, 0.0, 0.0, 0.0};
         if (live && t < N) {
-            if (a.L) {
-                double dx[12];
-#pragma unroll
-                for (int q = 0; q < 12; ++q) dx[q] = x[q] - a.xnom[(long)t * XSTR + q];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const double *Lr = a.L + (long)t * LSTR + i * 12;
-                    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {                     // L_t (x_t - xbar_t), rat_src_user_noisy_rollout's order
-                        a0 = __builtin_fma(Lr[q], dx[q], a0);
-                        a1 = __builtin_fma(Lr[4 + q], dx[4 + q], a1);
-                        a2 = __builtin_fma(Lr[8 + q], dx[8 + q], a2);
-                    }
-                    u[i] = a.l[(long)t * USTR + i] + ((a0 + a1) + a2);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) u[i] = a.l[(long)t * USTR + i];
-            }
+            src_affine(t, x, a.xnom, a.l, a.L, u);                    // (rat_src_user_noisy_rollout's sums, in its order)
 #ifdef RAT_USER_POLICY
-            if (rat_src_policy(t, x, u, up, SRCRE_P)) dom = 1;            // the user's controller: the margin, c, the sampler and f see the applied control
+            if (rat_src_policy(t, x, u, up, p)) dom = 1;              // the user's controller: the margin, c, the sampler and f see the applied control
 #endif
         }
 #ifdef RAT_RARE_USER_EVENT
@@ -168,11 +133,11 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
             double g[16];
 #pragma unroll
             for (int e = 0; e < 16; ++e) g[e] = nan;
-            rat_user_event(t, x, u, g, SRCRE_P);                          // (x has 12 entries, RAT_N of them live; u is 0 at t == N)
+            rat_user_event(t, x, u, g, p);                            // (x has 12 entries, RAT_N of them live; u is 0 at t == N)
             double gv = nan;
 #pragma unroll
             for (int e = 0; e < RAT_N_EVENT; ++e) gv = (e == a.event) ? g[e] : gv;
-            if (gv > M || srcre_nan(M)) M = gv;                       // (a NaN g never replaces a number)
+            if (gv > M || src_nan(M)) M = gv;                         // (a NaN g never replaces a number)
         }
 #else
         if (t >= a.t_lo && t <= a.t_hi) {                             // (uniform over the grid)
@@ -190,28 +155,28 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
                 if (kq == c) gv = gc;                                 // lane 16 c + col owns rollout 16 c + col of the wavefront
             }
             SRCRE_SYNC();
-            if (gv > M || srcre_nan(M)) M = gv;                       // (a NaN g never replaces a number)
+            if (gv > M || src_nan(M)) M = gv;                         // (a NaN g never replaces a number)
         }
 #endif
         if (t == N) break;
         if (live) {
             bool inok = true;
 #pragma unroll
-            for (int q = 0; q < RAT_N; ++q) inok = inok && !srcre_nan(x[q]);
+            for (int q = 0; q < RAT_N; ++q) inok = inok && !src_nan(x[q]);
 #pragma unroll
-            for (int q = 0; q < RAT_M; ++q) inok = inok && !srcre_nan(u[q]);
-            const double ct = rat_user_c<double>(t, x, u, SRCRE_P);       // (for the DomainError rule alone)
+            for (int q = 0; q < RAT_M; ++q) inok = inok && !src_nan(u[q]);
+            const double ct = rat_user_c<double>(t, x, u, p);         // (for the DomainError rule alone)
             rng.t = (unsigned)t; rng.in = 0; rng.iu = 0;
             rng.shift = a.shift + t * 12;
             double w[RAT_N];
 #pragma unroll
             for (int q = 0; q < RAT_N; ++q) w[q] = 0.0;
-            rat_user_noise(t, x, u, rng, w, SRCRE_P);
+            rat_user_noise(t, x, u, rng, w, p);
             double xn[RAT_N];
-            rat_user_f<double>(x, u, xn, SRCRE_P);
-            bool outnan = srcre_nan(ct);
+            rat_user_f<double>(x, u, xn, p);
+            bool outnan = src_nan(ct);
 #pragma unroll
-            for (int q = 0; q < RAT_N; ++q) outnan = outnan || srcre_nan(xn[q]) || srcre_nan(w[q]);
+            for (int q = 0; q < RAT_N; ++q) outnan = outnan || src_nan(xn[q]) || src_nan(w[q]);
             if (inok && outnan) dom = 1;                              // the reference's DomainError, and a NaN disturbance
 #pragma unroll
             for (int q = 0; q < RAT_N; ++q) x[q] = xn[q] + w[q];      // x_{t+1} = f(x_t, u_t) + w_t
@@ -220,9 +185,9 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
     if (!live) return;                                                // (behind the last group: nothing follows that needs the lane)
     bool inok = true;
 #pragma unroll
-    for (int q = 0; q < RAT_N; ++q) inok = inok && !srcre_nan(x[q]);
-    const double hc = rat_user_h<double>(x, SRCRE_P);
-    if (inok && srcre_nan(hc)) dom = 1;
+    for (int q = 0; q < RAT_N; ++q) inok = inok && !src_nan(x[q]);
+    const double hc = rat_user_h<double>(x, p);
+    if (inok && src_nan(hc)) dom = 1;
     a.margin[j] = dom ? nan : M;
     a.logw[j] = rng.logw;
     a.dom[j] = dom;

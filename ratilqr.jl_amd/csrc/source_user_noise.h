@@ -2,30 +2,15 @@
 // include/ratilqr.h "Source models").  Compiled by hiprtc behind rat_rng.h and the user's source, which defines RAT_USER_NOISE and
 // rat_user_noise next to rat_user_f / rat_user_c / rat_user_h; RAT_N, RAT_M, RAT_PETS_NORMALS, RAT_PETS_UNIFORMS come from the command
 // line.  A module of its own, compiled by the first call that needs it, as source_noisy.h is: a handle that never evaluates under user
-// noise never pays for it.  The library embeds this header at build time (Makefile: source_embed.inc).
+// noise never pays for it.
 #pragma once
 #include "rat_rng.h"
-#include "source_args.h"
+#include "source_step.h"
 #include "source_policy.h"
 #include "source_params.h"
 
-#if !defined(RAT_N) || !defined(RAT_M)
-#error "RAT_N and RAT_M must be defined"
-#endif
-#if RAT_N > SRC_MAX_N || RAT_M > SRC_MAX_M
-#error "source models are compiled for n <= 12, m <= 4"
-#endif
 #ifndef RAT_USER_NOISE
 #error "the source does not define RAT_USER_NOISE: rat_policy_evaluate_noise needs '#define RAT_USER_NOISE' and rat_user_noise(k, x, u, rng, w, p)"
-#endif
-
-__device__ inline bool srcun_nan(double v) { return v != v; }
-
-// what the rollout hands the user's functions as p: the rollout's own parameters (source_params.h) or the problem's
-#ifdef RAT_USER_PARAMS_ON
-#define SRCUN_P q
-#else
-#define SRCUN_P a.p
 #endif
 
 // ---- noisy rollout under the user's sampler: one lane per Monte-Carlo rollout, the state in registers ----------------------------------
@@ -35,10 +20,12 @@ __device__ inline bool srcun_nan(double v) { return v != v; }
 // (j N + t) normals + i / (j N + t) uniforms + i with j counted from the launch's first rollout (the host stages a chunk at a time), or
 // Philox4x32-10 with the GLOBAL rollout index j + j0 in the counter and the caller's seed as the key -- no per-chunk seeds, so the result
 // does not depend on how K is cut into launches.  Every per-lane array is indexed by unrolled loop counters only, so nothing is forced into scratch;
-// what spills is a matter of size (the pendulum of the tests: 148 VGPRs, none; the 12 x 4 LQ source with 12 normals and a uniform: all
-// 512 registers and 396 B per lane -- every rng draw is a Philox block inlined at its call site).  The sampler runs
-// before f: with f first the 12 x 4 source spilled 1940 B per lane.  x_out / u_out (either may be null): dense [n x (N+1)] / [m x N] per rollout, rollout
-// slowest -- rat_rollout_noisy's layout -- written straight from the lane; a DomainError rollout writes what it computed and a NaN cost.
+// what spills is a matter of size (the pendulum of the tests: none; the 12 x 4 LQ source with 12 normals and a uniform: all 512 registers
+// and 636 B per lane, 628 B under the clamp + rate hook, profiles/policy_user_policy.md -- every rng draw is a Philox block inlined at its
+// call site).  The sampler runs before f: with f first the 12 x 4 source spilled 1940 B per lane.  The affine law is
+// written out here, not src_affine (source_step.h): with the helper one row of the resource table moves (profiles/source_step.md).
+// x_out / u_out (either may be null): dense [n x (N+1)] / [m x N] per rollout, rollout slowest -- rat_rollout_noisy's layout -- written
+// straight from the lane; a DomainError rollout writes what it computed and a NaN cost.
 // w_out (null but for rat_policy_worst_case_disturbance's replay): dense [n x N] per rollout, the w the sampler wrote, before it is added.
 extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcUserNoisyArgs a) {
     const int lane = threadIdx.x;
@@ -59,10 +46,9 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
     double *__restrict__ uo = a.u_out ? a.u_out + j * (long)N * RAT_M : nullptr;
     double cost = 0.0;
     int dom = 0;
-#ifdef RAT_USER_PARAMS_ON
-    double q[RAT_N_PARAMS];                                           // this rollout's parameters, drawn once in front of step 0
-    if (rat_src_params(g, a.seed, a.zpn, a.zpu, a.p, q, rng.over)) dom = 1;
-#endif
+    src_rollout_params own;
+    if (own.draw(g, a.seed, a.zpn, a.zpu, a.p, rng.over)) dom = 1;
+    const double *p = own.of(a.p);
 #ifdef RAT_USER_POLICY
     double up[4] = {0.0, 0.0, 0.0, 0.0};                              // the control applied at step t - 1
 #endif
@@ -89,7 +75,7 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
             for (int i = 0; i < 4; ++i) u[i] = a.l[(long)t * USTR + i];
         }
 #ifdef RAT_USER_POLICY
-        if (rat_src_policy(t, x, u, up, SRCUN_P)) dom = 1;                // the user's controller: u_out, c, the sampler and f see the applied control
+        if (rat_src_policy(t, x, u, up, p)) dom = 1;                  // the user's controller: u_out, c, the sampler and f see the applied control
 #endif
         if (xo) {
 #pragma unroll
@@ -101,10 +87,10 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
         }
         bool inok = true;
 #pragma unroll
-        for (int q = 0; q < RAT_N; ++q) inok = inok && !srcun_nan(x[q]);
+        for (int q = 0; q < RAT_N; ++q) inok = inok && !src_nan(x[q]);
 #pragma unroll
-        for (int q = 0; q < RAT_M; ++q) inok = inok && !srcun_nan(u[q]);
-        const double ct = rat_user_c<double>(t, x, u, SRCUN_P);           // integrate_cost: c(t, x_t, u_t) in order   (ileqg.jl:118-121)
+        for (int q = 0; q < RAT_M; ++q) inok = inok && !src_nan(u[q]);
+        const double ct = rat_user_c<double>(t, x, u, p);             // integrate_cost: c(t, x_t, u_t) in order   (ileqg.jl:118-121)
         cost += ct;
         rng.t = (unsigned)t; rng.in = 0; rng.iu = 0;
         if (!rng.gen) {
@@ -114,16 +100,16 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
         double w[RAT_N];
 #pragma unroll
         for (int q = 0; q < RAT_N; ++q) w[q] = 0.0;
-        rat_user_noise(t, x, u, rng, w, SRCUN_P);
+        rat_user_noise(t, x, u, rng, w, p);
         if (a.w_out) {
 #pragma unroll
             for (int q = 0; q < RAT_N; ++q) a.w_out[(j * N + t) * (long)RAT_N + q] = w[q];
         }
         double xn[RAT_N];
-        rat_user_f<double>(x, u, xn, SRCUN_P);
-        bool outnan = srcun_nan(ct);
+        rat_user_f<double>(x, u, xn, p);
+        bool outnan = src_nan(ct);
 #pragma unroll
-        for (int q = 0; q < RAT_N; ++q) outnan = outnan || srcun_nan(xn[q]) || srcun_nan(w[q]);
+        for (int q = 0; q < RAT_N; ++q) outnan = outnan || src_nan(xn[q]) || src_nan(w[q]);
         if (inok && outnan) dom = 1;                                  // the reference's DomainError, and a NaN disturbance
 #pragma unroll
         for (int q = 0; q < RAT_N; ++q) x[q] = xn[q] + w[q];          // x_{t+1} = f(x_t, u_t) + w_t
@@ -134,9 +120,9 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_user_noisy_rollout(SrcU
     }
     bool inok = true;
 #pragma unroll
-    for (int q = 0; q < RAT_N; ++q) inok = inok && !srcun_nan(x[q]);
-    const double hc = rat_user_h<double>(x, SRCUN_P);                     // ... then h(x_N)   (ileqg.jl:122)
-    if (inok && srcun_nan(hc)) dom = 1;
+    for (int q = 0; q < RAT_N; ++q) inok = inok && !src_nan(x[q]);
+    const double hc = rat_user_h<double>(x, p);                       // ... then h(x_N)   (ileqg.jl:122)
+    if (inok && src_nan(hc)) dom = 1;
     cost += hc;
     a.cost[j] = dom ? __builtin_nan("") : cost;
     if (rng.over) *a.overdraw = rng.over;

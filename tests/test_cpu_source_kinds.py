@@ -77,13 +77,15 @@ REQUESTS = FIRST + FIRST + CHANGED + IGNORED + REFUSED
 
 
 def embed_inc(path):
-    """csrc/Makefile's rule for source_embed.inc: the headers of EMBED_H as raw string literals"""
+    """csrc/Makefile's rule for source_embed.inc: the headers of EMBED_H as raw string literals, then the arrays of their texts and names"""
     names = re.search(r"^EMBED_H = (.*)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).split()
     with open(path, "w") as out:
         for name in names:
             out.write('static const char k_embed_%s[] = R"RATEMBED(' % name.replace(".", "_"))
             out.write(open(os.path.join(CSRC, name)).read())
             out.write(')RATEMBED";\n')
+        out.write("static const char *const k_embed_texts[] = {%s};\n" % "".join("k_embed_%s, " % name.replace(".", "_") for name in names))
+        out.write("static const char *const k_embed_names[] = {%s};\n" % "".join('"%s", ' % name for name in names))
 
 
 def build_probe(tmp, flags=()):
