@@ -9,6 +9,14 @@
 // Comparisons, fmin / fmax and fabs's branch look at the value only.  No fast-math: NaN in a value is how a model signals a domain
 // error, and it has to survive.
 //
+// At singular points (tests/ad_edge_cases.py, profiles/ad_edges.md) the derivatives are what plain IEEE evaluation of the chain rule gives:
+// sqrt at 0 has slope Inf and curvature NaN, log and 1 / x at 0 have infinite partials, and a non-finite slope times the zero seed of
+// another variable is NaN in that variable's partial.  One exception: pow(T, double) returns exactly 0 for a partial whose coefficient
+// (p, or p (p - 1)) is 0.  pow with a dual exponent differentiates through exp(b log a), so its partials are NaN for a base <= 0 even
+// where the value is fine.  fabs has slope +1 at +-0; fmin and fmax return the first argument at a tie and the other one beside a NaN.
+// Division differs between the types: rat_dual uses (a' - q b') / b, rat_hdual multiplies by 1 / b, whose curvature 2 / b^3 leaves the
+// double range for |b| outside about [1e-102, 1e102]; the two agree for denominators in [1e-100, 1e100] and need not beyond.
+//
 // The header compiles as device code under hiprtc (the JIT of the source-model family) and as plain host C++ (its unit test).
 #pragma once
 
@@ -115,8 +123,9 @@ RAT_AD_FN rat_hdual operator/(double a, const rat_hdual &b) { return rat_hdual(a
     RAT_AD_FN T sqrt(const T &a) { const double s = sqrt(a.v), d1 = 0.5 / s; return rat_chain(a, s, d1, -0.5 * d1 / a.v); } \
     RAT_AD_FN T tanh(const T &a) { const double t = tanh(a.v), s = 1.0 - t * t; return rat_chain(a, t, s, -2.0 * t * s); } \
     RAT_AD_FN T atan(const T &a) { const double r = 1.0 / (1.0 + a.v * a.v); return rat_chain(a, atan(a.v), r, -2.0 * a.v * r * r); } \
-    RAT_AD_FN T pow(const T &a, double p) {                                                       \
-        return rat_chain(a, pow(a.v, p), p * pow(a.v, p - 1.0), p * (p - 1.0) * pow(a.v, p - 2.0)); }              \
+    RAT_AD_FN T pow(const T &a, double p) {      /* a zero coefficient is a zero partial: pow(x, 1.0) and pow(x, 0.0) at x = 0 */ \
+        const double c1 = p, c2 = p * (p - 1.0);                                                  \
+        return rat_chain(a, pow(a.v, p), c1 == 0.0 ? 0.0 : c1 * pow(a.v, p - 1.0), c2 == 0.0 ? 0.0 : c2 * pow(a.v, p - 2.0)); } \
     RAT_AD_FN T pow(const T &a, const T &b) {                                                     \
         T r = exp(b * log(a)); r.v = pow(a.v, b.v); return r; }                                   \
     RAT_AD_FN T pow(double a, const T &b) { T r = exp(b * log(a)); r.v = pow(a, b.v); return r; } \
