@@ -210,7 +210,8 @@ rat_rc rat_problem_set(rat_handle h, const rat_problem_desc *desc);
  * index; Box-Muller pairing and the 53-bit uniform as for the per-step draws, whose counters (step word t < N) stay bit for bit what they
  * were.  The rare-event calls run every pass under the pass's seed, the final pass under the call's.  Their proposal shifts the per-step
  * normals alone: parameter normals are NOT shifted and add nothing to logw, so an event that a parameter drives cannot be made likelier
- * by these calls (as one driven by a uniform cannot).
+ * by these calls (as one driven by a uniform cannot).  rat_policy_rare_event_params (below) shifts the parameter normals as well and is
+ * the call for such an event.
  * Limits: n <= 12, m <= 4 (else RAT_ERR_UNSUPPORTED); batches run on the round-based path (rat_set_path FUSED / BLOCK return
  * RAT_ERR_UNSUPPORTED); rat_rollout_noisy and rat_multi are not available for source models: rat_policy_evaluate with cost_out is the way
  * to their Monte-Carlo costs, and rat_policy_evaluate_noise with x_out / u_out the way to Monte-Carlo trajectories (under the user's
@@ -688,6 +689,44 @@ rat_rc rat_policy_rare_event_user(rat_handle h, const double *x_nom, const doubl
 /* Compile only, for gfx950 (no device needed), the kernel of rat_policy_rare_event_user: rat_rare_event_noise_check's codes, and
  * RAT_ERR_ARG for n_event outside 1 .. 16 or a source without RAT_USER_EVENT. */
 rat_rc rat_rare_event_user_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms, int32_t n_event);
+/* Rare events that an uncertain parameter drives: rat_policy_rare_event_noise (n_event == 0: the quadratic event Q, a, b, t_lo, t_hi) or
+ * rat_policy_rare_event_user (n_event in 1 .. 16: entry `event` of rat_user_event; Q, a, b, t_lo, t_hi are not read) with the normals of
+ * rat_user_params drawn from a shifted proposal too.  The handle's parameter sampling must be on (rat_policy_params_sampling) with the
+ * device generator, PN = its param_normals in 1 .. 12.  The i-th rng.normal() of the hook returns z = ps[i] + xi, xi the N(0, 1) draw of
+ * the generator (counter (g lo, g hi, 0xFFFFFFFF, i / 2), key the pass's seed), and adds fma(-ps[i], z, ps[i]^2 / 2) to the rollout's logw
+ * at the draw, before step 0; a hook that draws fewer normals than it declared adds fewer terms, so the likelihood ratio stays sequential
+ * and the estimate unbiased for every ps.  rng.uniform() of the hook is not shifted.  logw is the whole ratio, parameter part included:
+ * the level, the elite E and the weights w_i = exp(logw_i - max logw) are those calls', and with bit 1 of `adapt` the parameter shift
+ * moves by ps <- ps + sum_E w_i xi^p_i / sum_E w_i, xi^p replayed from the pass's parameter stream, all PN components whether or not the
+ * hook drew them, in the fixed order of the step shift's sums.
+ *   adapt        bit 0: adapt the step shift; bit 1: adapt the parameter shift; 1, 2 or 3.  A part whose bit is clear stays at its *_in
+ *                (0 when NULL) through every iteration, is still applied and still counted in logw: an event that the parameters alone
+ *                drive is estimated with adapt == 2, and pays no variance for step shifts that would move by sampling noise alone.
+ *   shift_in, shift_out    [N][P] or NULL, as in rat_policy_rare_event_noise;  pshift_in, pshift_out   [PN] or NULL
+ *   trace_out    [n_iter][RAT_RE_NTRACE] as there, |s| over the step shift only;  ptrace_out [n_iter]: |ps^(j+1)|, NaN wherever column 3 of
+ *                trace_out is NaN
+ *   normals_per_step   1 .. 12 as there: a model without process noise declares one normal and multiplies it by 0
+ * A non-finite entry in either adapted part drops the whole update of that iteration, both parts together (RAT_RE_NONFINITE).  Each
+ * iteration's rollouts, parameters included, run under that pass's seed, the final pass under the call's.  With pshift_in == NULL (or
+ * zeros) and adapt == 1 every output is bit for bit rat_policy_rare_event_noise's / _user's on the same handle at the same seed.
+ * RAT_ERR_ARG: what those calls list; parameter sampling off on the handle (the message says to call rat_policy_params_sampling);
+ * param_normals == 0 (nothing to shift); adapt outside 1 .. 3; a non-finite pshift_in; n_event outside 0 .. 16; event outside
+ * 0 .. n_event - 1.  RAT_ERR_UNSUPPORTED: what those calls list; param_normals > 12 (the width of a shift row); injected parameter
+ * streams on the handle (the proposal is defined on the generator, like the step draws); a problem that is not a source model.  The
+ * handle stays usable after every refusal and the recorded evaluation is not disturbed. */
+rat_rc rat_policy_rare_event_params(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
+                                    int32_t normals_per_step, int32_t uniforms_per_step, uint64_t seed,
+                                    int32_t n_event, int32_t event,
+                                    const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi,
+                                    const double *shift_in, const double *pshift_in, int32_t adapt, int32_t n_iter, double rho,
+                                    double *stats, double *shift_out, double *pshift_out, double *trace_out, double *ptrace_out,
+                                    double *margin_out, double *logw_out);
+/* Compile only, for gfx950 (no device needed), the kernel of rat_policy_rare_event_params with sampling on for n_params parameters:
+ * rat_rare_event_noise_check's codes (n_event == 0) or rat_rare_event_user_check's (n_event in 1 .. 16), rat_user_params_check's for the
+ * parameter counts (a source without RAT_USER_PARAMS: RAT_ERR_ARG), RAT_ERR_ARG for param_normals == 0 and for n_event outside 0 .. 16,
+ * RAT_ERR_UNSUPPORTED for param_normals > 12. */
+rat_rc rat_rare_event_params_check(const char *source, int32_t n, int32_t m, int32_t n_params, int32_t normals, int32_t uniforms,
+                                   int32_t param_normals, int32_t param_uniforms, int32_t n_event);
 /* approximate_model(problem, u_array, x_array)                 ileqg.jl:258-322
  * -> q[N+1], qv[n*(N+1)], Q[n*n*(N+1)], r[m*N], R[m*m*N], P[m*n*N], A[n*n*N], B[n*m*N], W[n*n*N] */
 rat_rc rat_approximate_model(rat_handle h, const double *u, const double *x,

@@ -769,6 +769,53 @@ end
 rare_event_user_check(source::AbstractString, n::Integer, m::Integer; normals_per_step::Integer=1, uniforms_per_step::Integer=0, n_event::Integer=1) =
     check(ccall((:rat_rare_event_user_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32, Int32), source, n, m, normals_per_step, uniforms_per_step, n_event))
 
+"""
+rare_event_probability_params(s, problem, x_nom, l_array, L_array, noise, ps; n_event, event, Q, a, b, t_lo, t_hi, K, seed, shift, param_shift,
+adapt, n_iter, rho, want_margins, want_logw): rare_event_probability_noise (n_event = 0: the event Q, a, b, t_lo, t_hi) or
+rare_event_probability_user (n_event in 1:16: entry `event`, 0-based, of rat_user_event) for an event that an uncertain parameter drives
+(rat_policy_rare_event_params).  Parameter sampling must be on for the solver's handle with the device generator (set_param_sampling! with
+`ps`, whose param_normals in 1:12 is the width of the parameter shift): the i-th rng.normal() of rat_user_params returns param_shift[i] + xi
+and its likelihood ratio is part of every rollout's logw.  adapt: :both, :step or :params -- the part that is not adapted stays at the shift
+handed in (nothing: 0), is still applied and still counted.  Returns rare_event_probability's named tuple with param_shift (param_normals)
+and param_trace (n_iter).
+"""
+function rare_event_probability_params(s::ILEQGSolver, problem::DeviceSourceProblem, x_nom, l_array::Vector{Vector{Float64}},
+                                       L_array::Union{Nothing,Vector{Matrix{Float64}}}, noise::UserNoise, ps::ParamSampling;
+                                       n_event::Integer=0, event::Integer=0, Q::Union{Nothing,Matrix{Float64}}=nothing,
+                                       a::Union{Nothing,Vector{Float64}}=nothing, b::Real=0.0, t_lo::Integer=0, t_hi::Integer=0,
+                                       K::Integer=65536, seed::Integer=noise.seed, shift::Union{Nothing,Matrix{Float64}}=nothing,
+                                       param_shift::Union{Nothing,Vector{Float64}}=nothing, adapt::Symbol=:both, n_iter::Integer=8,
+                                       rho::Real=0.1, want_margins::Bool=false, want_logw::Bool=false)
+    (noise.zn === nothing && noise.zu === nothing) || throw(ArgumentError("rare_event_probability_params draws from the device generator only"))
+    adapt in (:both, :step, :params) || throw(ArgumentError("adapt is :both, :step or :params"))
+    (n_event > 0 || a !== nothing) || throw(ArgumentError("the quadratic event (n_event = 0) needs a"))
+    h = bind!(s.h, problem)
+    n, m, N = dims(problem)
+    P = Int(noise.normals_per_step); PN = Int(ps.param_normals)
+    xn = x_nom isa Vector{Float64} ? x_nom : flat(x_nom)
+    l = flat(l_array)
+    L = L_array === nothing ? C_NULL : flat(L_array)
+    stats = zeros(12); shift_out = zeros(max(P, 1), N); pshift_out = zeros(max(PN, 1)); trace = zeros(4, max(n_iter, 1)); ptrace = zeros(max(n_iter, 1))
+    margins = want_margins ? Vector{Float64}(undef, K) : nothing
+    logw = want_logw ? Vector{Float64}(undef, K) : nothing
+    check(ccall((:rat_policy_rare_event_params, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, UInt64, Int32, Int32, Ptr{Float64}, Ptr{Float64},
+                 Float64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, xn, l, L, K, noise.normals_per_step, noise.uniforms_per_step, UInt64(seed), n_event, event, Q === nothing ? C_NULL : Q,
+                a === nothing ? C_NULL : a, Float64(b), t_lo, t_hi, shift === nothing ? C_NULL : shift,
+                param_shift === nothing ? C_NULL : param_shift, adapt === :step ? 1 : (adapt === :params ? 2 : 3), n_iter, Float64(rho), stats,
+                shift_out, pshift_out, trace, ptrace, want_margins ? margins : C_NULL, want_logw ? logw : C_NULL))
+    (prob=stats[1], prob_se=stats[2], ess=stats[3], n_viol=Int(stats[4]), n_ok=Int(stats[5]), n_domain=Int(stats[6]), logw_max=stats[7],
+     logw_min=stats[8], flag=Int(stats[9]), n_iter=Int(stats[10]), level=stats[11], shift=shift_out, trace=trace[:, 1:n_iter],
+     margins=margins, logw=logw, param_shift=pshift_out[1:PN], param_trace=ptrace[1:n_iter])
+end
+"rare_event_params_check(source, n, m, n_params; normals_per_step, uniforms_per_step, param_normals, param_uniforms, n_event): compile the kernel of rare_event_probability_params only (rat_rare_event_params_check)"
+rare_event_params_check(source::AbstractString, n::Integer, m::Integer, n_params::Integer; normals_per_step::Integer=1, uniforms_per_step::Integer=0,
+                        param_normals::Integer=1, param_uniforms::Integer=0, n_event::Integer=0) =
+    check(ccall((:rat_rare_event_params_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32), source, n, m, n_params,
+                normals_per_step, uniforms_per_step, param_normals, param_uniforms, n_event))
+
 "integrate_cost(problem, x_array, u_array) -- ileqg.jl:115-124"
 function integrate_cost(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_array, u_array)
     h = bind!(s.h, problem); c = Ref(0.0)
@@ -1611,7 +1658,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, rare_event_probability_params, rare_event_params_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

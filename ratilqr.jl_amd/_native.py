@@ -103,6 +103,7 @@ EXPORTS = [
     "rat_policy_events_user", "rat_user_event_check", "rat_policy_rare_event_user", "rat_rare_event_user_check",
     "rat_user_policy_check",
     "rat_policy_params_sampling", "rat_user_params_check", "rat_policy_params_sample",
+    "rat_policy_rare_event_params", "rat_rare_event_params_check",
 ]
 MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 WC_SLOTS = ("theta", "kl", "bound", "bound_se", "tilt_mean", "tilt_var", "ess", "flag")      # RAT_WC_* slots of the header, in order
@@ -176,6 +177,10 @@ def lib():
         _lib.rat_policy_params_sampling.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, C.c_int64]
         _lib.rat_user_params_check.argtypes = [C.c_char_p] + [C.c_int32] * 7
         _lib.rat_policy_params_sample.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, _dp]
+        _lib.rat_policy_rare_event_params.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32,
+                                                      _dp, _dp, C.c_double, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.c_int32, C.c_double,
+                                                      _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+        _lib.rat_rare_event_params_check.argtypes = [C.c_char_p] + [C.c_int32] * 8
     return _lib
 
 
@@ -259,6 +264,14 @@ def rare_event_user_check(source, n, m, normals_per_step=1, uniforms_per_step=0,
     """rat_rare_event_user_check: compile the rollout kernel of rat_policy_rare_event_user only (gfx950, no device needed); raises RatError
     with the compiler's log, saying what the source does not define, or naming the limit on normals_per_step or n_event."""
     check(lib().rat_rare_event_user_check(str(source).encode(), int(n), int(m), int(normals_per_step), int(uniforms_per_step), int(n_event)))
+
+
+def rare_event_params_check(source, n, m, n_params, normals_per_step=1, uniforms_per_step=0, param_normals=1, param_uniforms=0, n_event=0):
+    """rat_rare_event_params_check: compile the rollout kernel of rat_policy_rare_event_params only (gfx950, no device needed) -- the
+    quadratic event's variant with n_event=0, rat_user_event's with n_event in 1 .. 16; raises RatError with the compiler's log, saying
+    what the source does not define, or naming the limit on the counts (param_normals in 1 .. 12)."""
+    check(lib().rat_rare_event_params_check(str(source).encode(), int(n), int(m), int(n_params), int(normals_per_step), int(uniforms_per_step),
+                                            int(param_normals), int(param_uniforms), int(n_event)))
 
 
 def pets_set_source(h, prob):

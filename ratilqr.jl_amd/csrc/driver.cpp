@@ -42,7 +42,7 @@ void rat_set_error(const char *msg) { g_err = msg; }          // (multi.cpp repo
 
 struct EvRec { hipEvent_t a, b; int kind; int64_t ntraj; };
 // a lazily compiled source kernel of the handle and the shape its module was compiled for (fn == NULL: empty)
-struct SrcSlot { hipModule_t mod = nullptr; hipFunction_t fn = nullptr; int npn = 0, npu = 0, nev = 0, npar = 0, ppn = 0, ppu = 0; };
+struct SrcSlot { hipModule_t mod = nullptr; hipFunction_t fn = nullptr; int npn = 0, npu = 0, nev = 0, npar = 0, ppn = 0, ppu = 0, pshift = 0; };
 
 struct rat_handle_s {
     int device = 0;
@@ -852,12 +852,12 @@ static rat_rc src_args_ok(const char *who, SrcKind kind, int n, int m, int npn, 
 // the rat_*_check entry points: whether `source` would be accepted as `kind`, compiled for gfx950 without a device
 // (npar > 0: with parameter sampling on for npar parameters, ppn normals and ppu uniforms per rollout -- what params_args_ok accepted)
 static rat_rc src_check(const char *who, SrcKind kind, const char *source, int n, int m, int npn = 0, int npu = 0, int nev = 0, int npar = 0,
-                        int ppn = 0, int ppu = 0) {
+                        int ppn = 0, int ppu = 0, int pshift = 0) {
     if (!source) return fail(RAT_ERR_ARG, "null");
     rat_rc rc = src_args_ok(who, kind, n, m, npn, npu, nev);
     if (rc) return rc;
     std::string log;
-    if ((rc = src_compile(kind, source, n, m, SrcShape{npn, npu, nev, npar, ppn, ppu}, "gfx950", nullptr, &log))) return fail(rc, log);
+    if ((rc = src_compile(kind, source, n, m, SrcShape{npn, npu, nev, npar, ppn, ppu, pshift}, "gfx950", nullptr, &log))) return fail(rc, log);
     return RAT_OK;
 }
 
@@ -900,12 +900,12 @@ static rat_rc src_kernel(rat_handle h, SrcKind kind, SrcShape shape, const char 
     const bool ps = src_kind(kind).param_draws && h->ps_on;
     shape.npar = ps ? (int)h->src_np : 0; shape.ppn = ps ? h->ps_pn : 0; shape.ppu = ps ? h->ps_pu : 0;
     if (!s.fn || s.npn != shape.npn || s.npu != shape.npu || s.nev != shape.nev || s.npar != shape.npar || s.ppn != shape.ppn ||
-        s.ppu != shape.ppu) {
+        s.ppu != shape.ppu || s.pshift != shape.pshift) {
         std::shared_ptr<const std::vector<char>> code;
         std::string log;
         rat_rc rc;
         if ((rc = src_compile(kind, h->src_text.c_str(), h->n, h->m, shape, h->src_arch_name, &code, &log))) return fail(rc, log);
-        SrcSlot fresh{nullptr, nullptr, shape.npn, shape.npu, shape.nev, shape.npar, shape.ppn, shape.ppu};
+        SrcSlot fresh{nullptr, nullptr, shape.npn, shape.npu, shape.nev, shape.npar, shape.ppn, shape.ppu, shape.pshift};
         if ((rc = load_module_function(code, src_kind(kind).entry, who, &fresh.mod, &fresh.fn))) return rc;
         if (s.mod) {
             HIPCHK(hipStreamSynchronize(h->stream));
@@ -3130,6 +3130,12 @@ extern "C" rat_rc rat_policy_events_user(rat_handle h, int32_t n_event, const do
 // iteration then launches nothing (instead of sixteen launches that return at once; either is small beside a rollout pass of
 // milliseconds), and the host knows which trace rows exist -- the final pass and the read-backs.  They differ in the rollout kernel, in
 // the kernel that replays its stream over the elite, and in the width of a shift row: ReKernels.
+struct ReParamShift {                                                 // rat_policy_rare_event_params: the parameter row of the shift table
+    int pn;                                                           // its width: the handle's param_normals, 1 .. 12
+    int fix;                                                          // bit 0: the step rows stay at shift_in; bit 1: the parameter row at pshift_in
+    const double *pshift_in;                                          // [pn] or null
+    double *pshift_out, *ptrace_out;                                  // [pn], [n_iter], or null
+};
 struct ReKernels {
     int ncol;                                                         // entries of a shift row: n (the family's z_k), or P normals per step
     bool with_wchol;                                                  // the pack starts with chol(W(k)) (the family rollout unwhitens with it)
@@ -3152,8 +3158,9 @@ static rat_rc re_args_head(const std::string &F, rat_handle h, const double *x_n
 // ... and everything behind the refusals of the call: the horizon, the window, the finiteness checks, then the passes
 static rat_rc re_run(rat_handle h, const std::string &F, const ReKernels &kn, const double *x_nom, const double *l, const double *L, int64_t K,
                      uint64_t seed, const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi, const double *shift_in,
-                     int32_t n_iter, double rho, double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out) {
-    const int n = h->n, m = h->m, N = h->N, d = n + m, nc = kn.ncol;
+                     int32_t n_iter, double rho, double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out,
+                     const ReParamShift *par = nullptr) {
+    const int n = h->n, m = h->m, N = h->N, d = n + m, nc = kn.ncol, pn = par ? par->pn : 0;
     if (N > RE_MAX_N) return fail(RAT_ERR_UNSUPPORTED, F + "N is above " + std::to_string(RE_MAX_N) + " (the shift is staged in LDS)");
     if (!(0 <= t_lo && t_lo <= t_hi && t_hi <= N)) return fail(RAT_ERR_ARG, F + "the window must satisfy 0 <= t_lo <= t_hi <= N");
     bool fin = std::isfinite(b);
@@ -3161,6 +3168,8 @@ static rat_rc re_run(rat_handle h, const std::string &F, const ReKernels &kn, co
     if (Q) for (int i = 0; i < d * d; ++i) fin = fin && std::isfinite(Q[i]);
     if (shift_in) for (int i = 0; i < N * nc; ++i) fin = fin && std::isfinite(shift_in[i]);
     if (!fin) return fail(RAT_ERR_ARG, F + "Q, a, b and shift_in must be finite");
+    if (par && par->pshift_in) for (int i = 0; i < pn; ++i) fin = fin && std::isfinite(par->pshift_in[i]);
+    if (!fin) return fail(RAT_ERR_ARG, F + "pshift_in must be finite");
     HIPCHK(hipSetDevice(h->device));
     // the policy pack (pack_policy), then the event in the 12 + 4 tile (rat_policy_events' layout) and the shift
     rat_rc rc;
@@ -3168,15 +3177,16 @@ static rat_rc re_run(rat_handle h, const std::string &F, const ReKernels &kn, co
     if ((rc = pack_policy(h, x_nom, l, L, kn.with_wchol, &pk))) return rc;
     std::vector<double> &pack = pk.data;
     const size_t o_q = pack.size(), o_a = o_q + 256, o_s = o_a + 16;
-    pack.resize(o_s + (size_t)N * 12, 0.0);
+    pack.resize(o_s + (size_t)(N + 1) * 12, 0.0);                     // (row N: the parameter shift, read with pn > 0 alone)
     auto tix = [n](int i) { return i < n ? i : 12 + i - n; };
     for (int i = 0; i < d; ++i) {
         pack[o_a + tix(i)] = a[i];
         if (Q) for (int k = 0; k < d; ++k) pack[o_q + tix(k) * 16 + tix(i)] = Q[i + (size_t)d * k];
     }
     if (shift_in) for (int t = 0; t < N; ++t) for (int i = 0; i < nc; ++i) pack[o_s + (size_t)t * 12 + i] = shift_in[(size_t)t * nc + i];
+    if (par && par->pshift_in) for (int i = 0; i < pn; ++i) pack[o_s + (size_t)N * 12 + i] = par->pshift_in[i];
     size_t cap_red = h->d_re_red ? RE_SCRATCH : 0;
-    const size_t n_part = ((size_t)N * 12 + 3) * RE_SLOTS;
+    const size_t n_part = ((size_t)N * 12 + 3 + 12) * RE_SLOTS;
     if ((rc = grow(&h->d_re_in, &h->cap_re_in, pack.size()))) return rc;
     if ((rc = grow(&h->d_re_margin, &h->cap_re_margin, (size_t)K))) return rc;
     if ((rc = grow(&h->d_re_logw, &h->cap_re_logw, (size_t)K))) return rc;
@@ -3191,6 +3201,7 @@ static rat_rc re_run(rat_handle h, const std::string &F, const ReKernels &kn, co
     ra.pb = h->pb; ra.Wchol = dev.Wchol; ra.xnom = dev.x; ra.l = dev.l; ra.L = dev.L;
     ra.pb.n = nc;                                                     // (the family: n itself.  re_update and re_elite_rng read the row's width here)
     ra.K = (long)K; ra.chunk = (long)mc_chunk(K);
+    ra.pn = pn; ra.fix = par ? par->fix : 0;
     ra.shift = h->d_re_in + o_s; ra.Qt = h->d_re_in + o_q; ra.at = h->d_re_in + o_a; ra.b = b; ra.t_lo = t_lo; ra.t_hi = t_hi;
     ra.margin = h->d_re_margin; ra.logw = h->d_re_logw; ra.dom = h->d_re_dom; ra.scratch = h->d_re_red; ra.part = h->d_re_part;
     int reached = 0, n_run = 0;
@@ -3213,10 +3224,11 @@ static rat_rc re_run(rat_handle h, const std::string &F, const ReKernels &kn, co
     if ((rc = kn.rollout(ra, Q != nullptr))) return rc;
     launch_re_final(ra, h->stream);
     HIPCHK(hipGetLastError());
-    double out[RE_NSTAT], tr[RE_MAX_ITER * RE_NTRACE];
-    std::vector<double> sh((size_t)N * 12);
+    double out[RE_NSTAT], tr[RE_MAX_ITER * RE_NTRACE], ptr[RE_MAX_ITER];
+    std::vector<double> sh((size_t)(N + 1) * 12);
     HIPCHK(hipMemcpyAsync(out, h->d_re_red + RE_O_STATS, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(tr, h->d_re_red + RE_O_TRACE, sizeof(tr), hipMemcpyDeviceToHost, h->stream));
+    if (par) HIPCHK(hipMemcpyAsync(ptr, h->d_re_red + RE_O_PTRACE, sizeof(ptr), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(sh.data(), h->d_re_in + o_s, sh.size() * 8, hipMemcpyDeviceToHost, h->stream));
     if (margin_out) HIPCHK(hipMemcpyAsync(margin_out, h->d_re_margin, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
     if (logw_out) HIPCHK(hipMemcpyAsync(logw_out, h->d_re_logw, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
@@ -3225,6 +3237,9 @@ static rat_rc re_run(rat_handle h, const std::string &F, const ReKernels &kn, co
     for (int i = 0; i < RAT_RE_NSTAT; ++i) stats[i] = out[i];
     if (shift_out) for (int t = 0; t < N; ++t) for (int i = 0; i < nc; ++i) shift_out[(size_t)t * nc + i] = sh[(size_t)t * 12 + i];
     if (trace_out) for (int i = 0; i < n_iter * RAT_RE_NTRACE; ++i) trace_out[i] = (i < n_run * RAT_RE_NTRACE) ? tr[i] : std::nan("");
+    if (par && par->pshift_out) for (int i = 0; i < pn; ++i) par->pshift_out[i] = sh[(size_t)N * 12 + i];
+    if (par && par->ptrace_out)                                       // |ps| of the iterations that updated: NaN wherever the trace's |s| is
+        for (int j = 0; j < n_iter; ++j) par->ptrace_out[j] = (j < n_run && !std::isnan(tr[j * RAT_RE_NTRACE + 3])) ? ptr[j] : std::nan("");
     return RAT_OK;
 }
 
@@ -3259,14 +3274,15 @@ static rat_rc rare_src_run(rat_handle h, const std::string &F, const char *who, 
                            int32_t normals_per_step, int32_t uniforms_per_step, uint64_t seed, int32_t n_event, int32_t event,
                            const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi,
                            const double *shift_in, int32_t n_iter, double rho,
-                           double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out) {
+                           double *stats, double *shift_out, double *trace_out, double *margin_out, double *logw_out,
+                           const ReParamShift *par = nullptr) {
     rat_rc rc;
     const int npn = normals_per_step, npu = uniforms_per_step;
     HIPCHK(hipSetDevice(h->device));
     hipFunction_t kernel = nullptr;
     int *d_over = nullptr;
     if ((rc = params_ready(h, F, K))) return rc;
-    if ((rc = src_kernel(h, n_event > 0 ? SRC_RARE_USER : SRC_RARE, SrcShape{npn, npu, n_event}, who, &kernel))) return rc;
+    if ((rc = src_kernel(h, n_event > 0 ? SRC_RARE_USER : SRC_RARE, SrcShape{npn, npu, n_event, 0, 0, 0, par ? 1 : 0}, who, &kernel))) return rc;
     if ((rc = overdraw_flag(&h->h_un_over, F, &d_over))) return rc;
     ReKernels kn;
     kn.ncol = npn; kn.with_wchol = false; kn.adapt = launch_re_adapt_rng;
@@ -3284,7 +3300,8 @@ static rat_rc rare_src_run(rat_handle h, const std::string &F, const char *who, 
         const int flag = *(volatile int *)h->h_un_over;
         return flag == 0 ? RAT_OK : overdraw_fail(h, F, flag, npn, npu);
     };
-    return re_run(h, F, kn, x_nom, l, L, K, seed, Q, a, b, t_lo, t_hi, shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
+    return re_run(h, F, kn, x_nom, l, L, K, seed, Q, a, b, t_lo, t_hi, shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out,
+                  par);
 }
 
 extern "C" rat_rc rat_policy_rare_event_noise(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
@@ -3323,6 +3340,58 @@ extern "C" rat_rc rat_policy_rare_event_user(rat_handle h, const double *x_nom, 
     if ((rc = src_args_ok("rat_policy_rare_event_user", SRC_RARE, h->n, h->m, normals_per_step, uniforms_per_step, 0))) return rc;
     return rare_src_run(h, F, "rat_policy_rare_event_user", x_nom, l, L, K, normals_per_step, uniforms_per_step, seed, n_event, event, nullptr, a0,
                         0.0, 0, h->N, shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out);
+}
+
+// What the parameter row asks of the counts alone: rat_policy_rare_event_params and its compile-only check
+static rat_rc re_params_counts_ok(const std::string &F, int n_event, int ppn) {
+    if (n_event < 0 || n_event > EV_MAX) return fail(RAT_ERR_ARG, F + "n_event must be in 0 .. 16 (0: the quadratic event)");
+    if (ppn == 0) return fail(RAT_ERR_ARG, F + "param_normals is 0: there is no parameter normal to shift");
+    if (ppn > 12) return fail(RAT_ERR_UNSUPPORTED, F + "param_normals is above 12 (the parameter shift is one row of the [N + 1][12] table)");
+    return RAT_OK;
+}
+
+extern "C" rat_rc rat_rare_event_params_check(const char *source, int32_t n, int32_t m, int32_t n_params, int32_t normals, int32_t uniforms,
+                                              int32_t param_normals, int32_t param_uniforms, int32_t n_event) {
+    const std::string F = "rat_rare_event_params_check: ";
+    if (!source) return fail(RAT_ERR_ARG, "null");
+    rat_rc rc;
+    if ((rc = params_args_ok(F, n_params, param_normals, param_uniforms))) return rc;
+    if ((rc = re_params_counts_ok(F, n_event, param_normals))) return rc;
+    return src_check("rat_rare_event_params_check", n_event > 0 ? SRC_RARE_USER : SRC_RARE, source, n, m, normals, uniforms, n_event, n_params,
+                     param_normals, param_uniforms, 1);
+}
+
+// rat_policy_rare_event_noise (n_event == 0) or rat_policy_rare_event_user (n_event > 0) with the normals of rat_user_params shifted too:
+// the modules' RAT_PARAM_SHIFT variants (source_params.h), row N of the shift table, one more row of re_elite_rng (rare_event.h)
+extern "C" rat_rc rat_policy_rare_event_params(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
+                                               int32_t normals_per_step, int32_t uniforms_per_step, uint64_t seed,
+                                               int32_t n_event, int32_t event,
+                                               const double *Q, const double *a, double b, int32_t t_lo, int32_t t_hi,
+                                               const double *shift_in, const double *pshift_in, int32_t adapt, int32_t n_iter, double rho,
+                                               double *stats, double *shift_out, double *pshift_out, double *trace_out, double *ptrace_out,
+                                               double *margin_out, double *logw_out) {
+    const std::string F = "rat_policy_rare_event_params: ";
+    const char *who = "rat_policy_rare_event_params";
+    const double a0[SRC_MAX_N + SRC_MAX_M] = {0.0};                   // (the quadratic event's place in the pack under a user event)
+    rat_rc rc;
+    if (n_event < 0 || n_event > EV_MAX) return fail(RAT_ERR_ARG, F + "n_event must be in 0 .. 16 (0: the quadratic event)");
+    const bool user = n_event > 0;
+    if ((rc = re_args_head(F, h, x_nom, l, user ? a0 : a, stats, K, n_iter, rho))) return rc;
+    if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
+        return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_params)");
+    if (user && (event < 0 || event >= n_event)) return fail(RAT_ERR_ARG, F + "event must be in 0 .. n_event - 1");
+    if ((rc = src_args_ok(who, SRC_RARE, h->n, h->m, normals_per_step, uniforms_per_step, 0))) return rc;
+    if (adapt < 1 || adapt > 3) return fail(RAT_ERR_ARG, F + "adapt must be 1 (the step shift), 2 (the parameter shift) or 3 (both)");
+    if (!h->ps_on) return fail(RAT_ERR_ARG, F + "parameter sampling is off: call rat_policy_params_sampling first");
+    if ((rc = re_params_counts_ok(F, n_event, h->ps_pn))) return rc;
+    if (h->ps_K > 0 || h->d_ps_zn || h->d_ps_zu)
+        return fail(RAT_ERR_UNSUPPORTED, F + "the handle holds injected parameter draws: the proposal is defined on the generator");
+    const ReParamShift par{h->ps_pn, ((adapt & 1) ? 0 : 1) | ((adapt & 2) ? 0 : 2), pshift_in, pshift_out, ptrace_out};
+    if (user)
+        return rare_src_run(h, F, who, x_nom, l, L, K, normals_per_step, uniforms_per_step, seed, n_event, event, nullptr, a0, 0.0, 0, h->N,
+                            shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out, &par);
+    return rare_src_run(h, F, who, x_nom, l, L, K, normals_per_step, uniforms_per_step, seed, 0, 0, Q, a, b, t_lo, t_hi, shift_in, n_iter, rho,
+                        stats, shift_out, trace_out, margin_out, logw_out, &par);
 }
 
 static rat_rc linearize_slot0(rat_handle h, const double *u, const double *x, std::vector<double> *tiles, int32_t *domain_fail) {

@@ -23,6 +23,13 @@
 // P = normals_per_step <= 12, entry (t, i) shifting the i-th rng.normal() of step t; ReArgs.pb.n holds P for re_elite_rng and re_update.
 // Its passes have the same seeds seed_p; inside a pass the keying is rat_rng's: the global rollout index in the counter (g lo, g hi, t,
 // i >> 1), key seed_p, no chunks -- rat_policy_evaluate_noise's generator at seed_p.
+//
+// rat_policy_rare_event_params is that call with the normals of rat_user_params shifted as well (source_params.h, RAT_PARAM_SHIFT): the shift
+// table has a row N, entry i shifting the i-th parameter normal (ReArgs.pn of them, <= 12), and re_elite_rng has a row N that replays the
+// parameter stream -- counter (g lo, g hi, 0xFFFFFFFF, i >> 1), key seed_p -- over the same elite with the same weights, into partials
+// behind the three sums.  ReArgs.fix names the part the caller holds still (bit 0 the step rows, bit 1 the parameter row): re_elite_rng
+// is launched for the rows that move, re_update checks and moves those alone -- one non-finite entry in either drops the whole update --
+// and writes |ps| of the parameter row beside the trace.  With pn == 0 (every other call) no kernel reads row N or the new partials.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,7 +44,7 @@
 #define RE_PASS_STRIDE 0xD1B54A32D192ED03ull
 #define RE_CHUNK_STRIDE 0x9E3779B97F4A7C15ull
 // scratch, in doubles: pass A partials [4][B] | pass B partials [3][B] | stats [12] | level: gamma, - | control: code (int), bad (int) |
-// trace [32][4] | the select's scratch [TR_SCRATCH]                  (B = MC_BLOCKS)
+// trace [32][4] | the select's scratch [TR_SCRATCH] | |ps| per iteration [32]      (B = MC_BLOCKS)
 #define RE_O_PA 0
 #define RE_O_PB (4 * MC_BLOCKS)
 #define RE_O_STATS (RE_O_PB + 3 * MC_BLOCKS)
@@ -45,7 +52,8 @@
 #define RE_O_CTL (RE_O_LVL + 2)
 #define RE_O_TRACE (RE_O_CTL + 2)
 #define RE_O_TR (RE_O_TRACE + RE_MAX_ITER * RE_NTRACE)
-#define RE_SCRATCH (RE_O_TR + TR_SCRATCH)
+#define RE_O_PTRACE (RE_O_TR + TR_SCRATCH)
+#define RE_SCRATCH (RE_O_PTRACE + RE_MAX_ITER)
 
 struct ReArgs {
     ProblemDev pb;
@@ -55,7 +63,7 @@ struct ReArgs {
     const double *L;          // [N][4][12] or null (open loop)
     long K, chunk;            // chunk = min(K, 2^16)
     unsigned long long seed;  // seed_p of this pass
-    double *shift;            // [N][12] s, zero padded
+    double *shift;            // [N][12] s, zero padded; [N + 1][12] with pn > 0: row N is the parameter shift
     const double *Qt;         // [16][16] in the tile as ev_eval reads it (entry (k, i) at k * 16 + i), or unused (linear event)
     const double *at;         // [16] in the tile
     double b;
@@ -64,10 +72,12 @@ struct ReArgs {
     double *logw;             // [K]
     int *dom;                 // [K]
     double *scratch;          // [RE_SCRATCH]
-    double *part;             // [N * 12 + 3][RE_SLOTS] re_elite's partials
+    double *part;             // [N * 12 + 3 + 12][RE_SLOTS] re_elite's partials: the step rows, sum w, sum w^2, |E|, the parameter row
     int iter;                 // adaptation iteration (re_level, re_update: the trace row)
     int reached;              // re_final: an iteration found gamma == 0
     int n_run;                // re_final: adaptation iterations that ran
+    int pn;                   // rat_policy_rare_event_params: the parameter normals a rollout declares (the width of row N), else 0
+    int fix;                  // with pn > 0: bit 0 the step rows, bit 1 the parameter row stay at their shift_in (0: everything is adapted)
 };
 void launch_re_rollout(const ReArgs &a, bool quad, hipStream_t s);
 // the select on the margins and re_level behind it: the code is the int at a.scratch + RE_O_CTL
@@ -75,7 +85,7 @@ void launch_re_level(const ReArgs &a, double rho, hipStream_t s);
 // re_pass_a, re_elite, re_update
 void launch_re_adapt(const ReArgs &a, hipStream_t s);
 // the same for rat_policy_rare_event_noise: re_pass_a, re_elite_rng (rat_rng's stream: pb.n holds P, the normals per step; seed is seed_p,
-// Wchol / xnom / l / L / chunk are not read), re_update
+// Wchol / xnom / l / L / chunk are not read), re_update; with pn > 0 the rows of re_elite_rng that a.fix leaves to move
 void launch_re_adapt_rng(const ReArgs &a, hipStream_t s);
 // re_pass_a, re_pass_b, re_final: the stats are a.scratch + RE_O_STATS
 void launch_re_final(const ReArgs &a, hipStream_t s);

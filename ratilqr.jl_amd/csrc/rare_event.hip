@@ -329,9 +329,17 @@ __global__ __launch_bounds__(MC_THREADS) void re_elite(ReArgs a) {
 // t, q) with g the global rollout index, key seed_p, one Box-Muller transform each: normals 2 q and 2 q + 1 (rat_rng.h) -- whether or not
 // the rollout drew them: a component it did not draw adds sampling noise to the update and no bias to the estimate.  The workgroups of
 // step 0 also sum w, w^2 and the elite count.
+// rat_policy_rare_event_params (a.pn > 0): row N of the grid replays the a.pn parameter normals -- the blocks with the step word
+// 0xFFFFFFFF of source_params.h -- into the partials behind the three sums, and a.fix takes the rows that stay still out of the grid: with
+// bit 0 the grid is row N alone, with bit 1 it ends at row N - 1.  The first row of the grid, whichever it is, sums w, w^2 and the count.
 __global__ __launch_bounds__(MC_THREADS) void re_elite_rng(ReArgs a) {
     __shared__ double sh[4 * MC_THREADS];
-    const int slot = blockIdx.x, t = blockIdx.y, tid = threadIdx.x, N = a.pb.N, P = a.pb.n;
+    const int slot = blockIdx.x, tid = threadIdx.x, N = a.pb.N;
+    const int t = (int)blockIdx.y + ((a.pn > 0 && (a.fix & 1)) ? N : 0);
+    const bool prow = t == N;                                         // (uniform over the workgroup)
+    const int P = prow ? a.pn : a.pb.n;
+    const unsigned tw = prow ? 0xFFFFFFFFu : (unsigned)t;
+    const size_t e0 = prow ? (size_t)N * 12 + 3 : (size_t)t * 12;
     const double lmax = re_head(a.scratch, sh).lmax, gamma = a.scratch[RE_O_LVL];
     double acc[12], sw[3] = {0.0, 0.0, 0.0};
 #pragma unroll
@@ -346,7 +354,7 @@ __global__ __launch_bounds__(MC_THREADS) void re_elite_rng(ReArgs a) {
             if (2 * q < P) {                                          // (uniform over the grid)
                 unsigned rr[4];
                 double z0, z1;
-                philox4x32_10((unsigned)i, (unsigned)(i >> 32), (unsigned)t, (unsigned)q, (unsigned)a.seed, (unsigned)(a.seed >> 32), rr);
+                philox4x32_10((unsigned)i, (unsigned)(i >> 32), tw, (unsigned)q, (unsigned)a.seed, (unsigned)(a.seed >> 32), rr);
                 ratn_box_muller(u01(rr[0], rr[1]), u01(rr[2], rr[3]), &z0, &z1);
                 acc[2 * q] += wt * z0;
                 acc[2 * q + 1] += wt * z1;                            // (the spare output of an odd P: never stored)
@@ -361,10 +369,10 @@ __global__ __launch_bounds__(MC_THREADS) void re_elite_rng(ReArgs a) {
         if (tid == 0) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                if (c0 + q < P) a.part[((size_t)t * 12 + c0 + q) * RE_SLOTS + slot] = v[q];
+                if (c0 + q < P) a.part[(e0 + c0 + q) * RE_SLOTS + slot] = v[q];
         }
     }
-    if (t == 0) {
+    if (blockIdx.y == 0) {
         block_tree_n<3>(sw, sh);
         if (tid == 0)
             for (int q = 0; q < 3; ++q) a.part[((size_t)N * 12 + q) * RE_SLOTS + slot] = sw[q];
@@ -377,19 +385,30 @@ __device__ __forceinline__ double re_slot_sum(const double *part, size_t e) {
     return v;
 }
 
-// the slots in index order; s += sum_E w xi / sum_E w, all of it or (a sum that is not finite, no weight) none of it; the trace row
+// the slots in index order; s += sum_E w xi / sum_E w, all of it or (a sum that is not finite, no weight) none of it; the trace row.
+// With a.pn > 0 (rat_policy_rare_event_params) the parameter row, ps += sum_E w xi^p / sum_E w, is the second part of the same update: a
+// part that a.fix holds still is neither checked nor moved, an entry that is not finite in either moving part drops both, and |ps| goes
+// beside the trace.  The step part's sums keep their lanes and their tree, so a call without a parameter row returns the bits it returned.
 __global__ __launch_bounds__(MC_THREADS) void re_update(ReArgs a) {
     __shared__ double sh[MC_THREADS];
+    __shared__ double s_ps[12];
     __shared__ int s_bad;
-    const int tid = threadIdx.x, N = a.pb.N, n = a.pb.n, ne = N * 12;
+    const int tid = threadIdx.x, N = a.pb.N, n = a.pb.n, ne = N * 12, pn = a.pn;
+    const bool mv_s = !(pn > 0 && (a.fix & 1)), mv_p = pn > 0 && !(a.fix & 2);
     if (tid == 0) s_bad = 0;
     __syncthreads();
     const double W = re_slot_sum(a.part, (size_t)ne), W2 = re_slot_sum(a.part, (size_t)ne + 1), cnt = re_slot_sum(a.part, (size_t)ne + 2);
     int bad = !(W > 0.0 && W < __builtin_inf());
-    for (int e = tid; e < ne; e += MC_THREADS) {
-        if (e % 12 >= n) continue;
-        const double d = re_slot_sum(a.part, (size_t)e) / W;
-        if (!(fabs(a.shift[e] + d) < __builtin_inf())) bad = 1;
+    if (mv_s) {
+        for (int e = tid; e < ne; e += MC_THREADS) {
+            if (e % 12 >= n) continue;
+            const double d = re_slot_sum(a.part, (size_t)e) / W;
+            if (!(fabs(a.shift[e] + d) < __builtin_inf())) bad = 1;
+        }
+    }
+    if (mv_p && tid < pn) {
+        const double d = re_slot_sum(a.part, (size_t)ne + 3 + tid) / W;
+        if (!(fabs(a.shift[ne + tid] + d) < __builtin_inf())) bad = 1;
     }
     if (bad) atomicOr(&s_bad, 1);
     __syncthreads();
@@ -398,13 +417,24 @@ __global__ __launch_bounds__(MC_THREADS) void re_update(ReArgs a) {
     for (int e = tid; e < ne; e += MC_THREADS) {
         if (e % 12 >= n) continue;
         double sv = a.shift[e];
-        if (!bad) { sv += re_slot_sum(a.part, (size_t)e) / W; a.shift[e] = sv; }
+        if (!bad && mv_s) { sv += re_slot_sum(a.part, (size_t)e) / W; a.shift[e] = sv; }
         ss += sv * sv;
     }
     ss = block_tree<0>(ss, sh);
+    if (tid < pn) {                                                   // (pn <= 12: the row is summed by one lane, in index order)
+        double pv = a.shift[ne + tid];
+        if (!bad && mv_p) { pv += re_slot_sum(a.part, (size_t)ne + 3 + tid) / W; a.shift[ne + tid] = pv; }
+        s_ps[tid] = pv;
+    }
+    __syncthreads();
     if (tid == 0) {
         double *tr = a.scratch + RE_O_TRACE + a.iter * RE_NTRACE;
         tr[1] = cnt; tr[2] = W * W / W2; tr[3] = sqrt(ss);
+        if (pn > 0) {
+            double pss = 0.0;
+            for (int e = 0; e < pn; ++e) pss += s_ps[e] * s_ps[e];
+            a.scratch[RE_O_PTRACE + a.iter] = sqrt(pss);
+        }
         if (bad) reinterpret_cast<int *>(a.scratch + RE_O_CTL)[1] = 1;
     }
 }
@@ -438,7 +468,8 @@ void launch_re_adapt(const ReArgs &a, hipStream_t s) {
 
 void launch_re_adapt_rng(const ReArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(re_pass_a, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
-    hipLaunchKernelGGL(re_elite_rng, dim3(RE_SLOTS, (unsigned)a.pb.N), dim3(MC_THREADS), 0, s, a);
+    const int rows = ((a.pn > 0 && (a.fix & 1)) ? 0 : a.pb.N) + ((a.pn > 0 && !(a.fix & 2)) ? 1 : 0);   // (the caller moves at least one part)
+    hipLaunchKernelGGL(re_elite_rng, dim3(RE_SLOTS, (unsigned)rows), dim3(MC_THREADS), 0, s, a);
     hipLaunchKernelGGL(re_update, dim3(1), dim3(MC_THREADS), 0, s, a);
 }
 

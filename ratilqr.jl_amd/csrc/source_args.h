@@ -85,7 +85,8 @@ struct SrcRareArgs {
     const double *xnom;       // [(N+1)][12] nominal states (open loop: only row 0 is read)
     const double *l;          // [N][4]
     const double *L;          // [N][4][12] or null (open loop)
-    const double *shift;      // [N][12] s, zero padded: entry i of row t shifts the i-th normal of step t
+    const double *shift;      // [N][12] s, zero padded: entry i of row t shifts the i-th normal of step t; a module compiled with
+                              // RAT_PARAM_SHIFT reads a row N as well: entry i shifts the i-th parameter normal
     const double *Qt;         // [16][16] in the tile as ev_eval reads it, or unused (quad == 0)
     const double *at;         // [16] in the tile
     double b;

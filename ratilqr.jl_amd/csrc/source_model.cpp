@@ -32,8 +32,9 @@ struct Rtc {
 std::mutex g_mu;
 Rtc g_rtc;
 // key: (source, n, m, SrcKind, normals per step, uniforms per step, events of rat_user_event (0 where the kind takes none), parameters
-// drawn per rollout (0: sampling off) with their normals and uniforms, architecture)
-std::map<std::tuple<std::string, int, int, int, int, int, int, int, int, int, std::string>, std::shared_ptr<const std::vector<char>>> g_cache;
+// drawn per rollout (0: sampling off) with their normals and uniforms, whether the parameter normals are shifted (0 where the kind has
+// no shifted proposal), architecture)
+std::map<std::tuple<std::string, int, int, int, int, int, int, int, int, int, int, std::string>, std::shared_ptr<const std::vector<char>>> g_cache;
 
 bool rtc_load(std::string *why) {           // (g_mu held)
     if (!g_rtc.tried) {
@@ -89,6 +90,7 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
     const SrcKindRow &row = k_kinds[kind];
     const int npn = row.draws ? shape.npn : 0, npu = row.draws ? shape.npu : 0, nev = row.events ? shape.nev : 0;
     const int npar = row.param_draws ? shape.npar : 0, ppn = npar > 0 ? shape.ppn : 0, ppu = npar > 0 ? shape.ppu : 0;
+    const int pshift = row.rng_shift ? shape.pshift : 0;
     const auto t0 = std::chrono::steady_clock::now();
     auto done = [&](rat_rc rc) {
         if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -96,7 +98,7 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
     };
     std::lock_guard<std::mutex> lk(g_mu);
     if (cached) *cached = false;
-    const auto key = std::make_tuple(std::string(source), n, m, (int)kind, npn, npu, nev, npar, ppn, ppu, arch);
+    const auto key = std::make_tuple(std::string(source), n, m, (int)kind, npn, npu, nev, npar, ppn, ppu, pshift, arch);
     auto it = g_cache.find(key);
     if (it != g_cache.end()) {
         if (code) *code = it->second;
@@ -128,6 +130,7 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
         opts.push_back("-DRAT_USER_PARAMS_ON=1");
         opts.push_back(dnp.c_str()); opts.push_back(dppn.c_str()); opts.push_back(dppu.c_str());
     }
+    if (pshift) opts.push_back("-DRAT_PARAM_SHIFT=1");
     if (kind == SRC_PARAMS) opts.push_back("-DRAT_PARAMS_SAMPLE_KERNEL=1");
     const hiprtcResult rc = g_rtc.compile(prog, (int)opts.size(), opts.data());
     size_t ls = 0;

@@ -24,7 +24,8 @@ enum SrcKind {
 // source_args.h, rat_ad.h and rat_rng.h, then `header` (under a #line of its own), compiled for `arch` with -O3 -std=c++17 -DRAT_N=n
 // -DRAT_M=m -DRAT_PETS_NORMALS=npn -DRAT_PETS_UNIFORMS=npu (0 where the kind takes no draws).  A kind that takes parameter draws gets
 // -DRAT_USER_PARAMS_ON=1 -DRAT_N_PARAMS=npar -DRAT_PARAM_NORMALS=ppn -DRAT_PARAM_UNIFORMS=ppu as well when the shape has npar > 0
-// (parameter sampling is on, rat_policy_params_sampling); with npar == 0 its command line is what it was without the feature.
+// (parameter sampling is on, rat_policy_params_sampling); with npar == 0 its command line is what it was without the feature.  The two
+// rng_shift kinds get -DRAT_PARAM_SHIFT=1 besides when the shape has pshift (rat_policy_rare_event_params: source_params.h).
 struct SrcKindRow {
     const char *header;          // embedded header with the kind's kernels
     const char *entry, *entry2;  // kernels the module exports (entry2: NULL but for SRC_MODEL's linearisation)
@@ -38,6 +39,8 @@ const SrcKindRow &src_kind(SrcKind kind);
 struct SrcShape {                                        // (fields a kind does not take are read as 0)
     int npn = 0, npu = 0, nev = 0;
     int npar = 0, ppn = 0, ppu = 0;                      // parameter sampling: RAT_N_PARAMS (0: off), parameter normals / uniforms per rollout
+    int pshift = 0;                                      // 1: -DRAT_PARAM_SHIFT=1, the parameter normals are shifted too (rat_policy_rare_event_params);
+                                                         // read by the rng_shift kinds alone (SRC_RARE, SRC_RARE_USER), which need npar > 0 with it
 };
 
 // Compiles `source` as `kind`.  RAT_OK: *code holds the code object (shared with the cache, which keys on source, n, m, kind, shape and

@@ -13,8 +13,14 @@
 //   generator  Philox4x32-10 (rat_philox.h), key (seed lo, seed hi):
 //                normals   counter (g lo, g hi, 0xFFFFFFFF, i / 2): u01(r0, r1), u01(r2, r3), Box-Muller -> normal 2q, normal 2q + 1
 //                uniforms  counter (g lo, g hi, 0xFFFFFFFF, 0x80000000 | i / 2): uniform 2q is u01(r0, r1), uniform 2q + 1 is u01(r2, r3)
-// rat_rng's pairing (rat_rng.h) under a step word no step uses, so the per-step draws keep their counters.  Never shifted: under
-// RAT_RNG_SHIFT the parameter normals come from N(0, 1) and add nothing to logw.
+// rat_rng's pairing (rat_rng.h) under a step word no step uses, so the per-step draws keep their counters.  Under RAT_RNG_SHIFT alone the
+// parameter normals come from N(0, 1) and add nothing to logw (rat_policy_rare_event_noise / _user).
+//
+// RAT_PARAM_SHIFT (the rat_policy_rare_event_params variant of source_rare.h's modules alone; it comes from the command line with
+// RAT_USER_PARAMS_ON): the i-th parameter normal is drawn from the shifted proposal, z = pshift[i] + xi with xi the draw above, and
+// -s z + s^2 / 2 is added to the rollout's logw at the draw, in draw order, in rat_rng.h's form; a hook that draws fewer normals than it
+// declared adds fewer terms.  The shift row [RAT_PARAM_NORMALS] is one address for the whole wavefront.  Uniforms are not shifted.
+// Without the macro RAT_PARAM_NORMAL is the identity, the struct has no further member and the functions no further argument.
 #pragma once
 #include "source_step.h"
 
@@ -32,6 +38,22 @@
 #if !defined(RAT_PARAM_NORMALS) || !defined(RAT_PARAM_UNIFORMS)
 #error "RAT_PARAM_NORMALS and RAT_PARAM_UNIFORMS must be defined"
 #endif
+#if defined(RAT_PARAM_SHIFT) && (RAT_PARAM_NORMALS < 1 || RAT_PARAM_NORMALS > 12)
+#error "rat_policy_rare_event_params shifts 1 .. 12 parameter normals"
+#endif
+#if defined(RAT_PARAM_SHIFT) && defined(RAT_PARAMS_SAMPLE_KERNEL)
+#error "rat_policy_params_sample draws from N(0, 1): it is not compiled with RAT_PARAM_SHIFT"
+#endif
+
+#ifdef RAT_PARAM_SHIFT
+#define RAT_PARAM_NORMAL(i, xi) proposal(i, xi)
+#define RAT_PARAM_SHIFT_ARGS , const double *pshift, double &logw
+#define RAT_PARAM_SHIFT_PASS , pshift, logw
+#else
+#define RAT_PARAM_NORMAL(i, xi) xi
+#define RAT_PARAM_SHIFT_ARGS
+#define RAT_PARAM_SHIFT_PASS
+#endif
 
 // rat_rng's interface (normal(), uniform()) with bounds of its own; a draw beyond them returns NaN and records the overdraw (bit 0
 // normals, bit 1 uniforms: the caller moves them to bits 2 and 3 of the kernel's flag)
@@ -41,17 +63,27 @@ struct rat_param_rng {
     unsigned g0, g1, k0, k1;      // generator: the rollout's counter words, key
     int in, iu, over;
     double spare_n, spare_u;      // the second output of the last generator block
+#ifdef RAT_PARAM_SHIFT
+    const double *shift;          // the parameter shift row [RAT_PARAM_NORMALS]: one address for the whole wavefront
+    double logw;
+    __device__ __forceinline__ double proposal(int i, double xi) {
+        const double sv = shift[i];
+        const double z = sv + xi;
+        logw += __builtin_fma(-sv, z, 0.5 * sv * sv);
+        return z;
+    }
+#endif
 
     __device__ __forceinline__ double normal() {
         const int i = in++;
         if (i >= RAT_PARAM_NORMALS) { over |= 1; return __builtin_nan(""); }
-        if (!gen) return zn[i];
-        if (i & 1) return spare_n;
+        if (!gen) return RAT_PARAM_NORMAL(i, zn[i]);
+        if (i & 1) return RAT_PARAM_NORMAL(i, spare_n);
         unsigned r[4];
         philox4x32_10(g0, g1, 0xFFFFFFFFu, (unsigned)(i >> 1), k0, k1, r);
         double z0;
         ratn_box_muller(u01(r[0], r[1]), u01(r[2], r[3]), &z0, &spare_n);
-        return z0;
+        return RAT_PARAM_NORMAL(i, z0);
     }
     __device__ __forceinline__ double uniform() {
         const int i = iu++;
@@ -69,8 +101,9 @@ struct rat_param_rng {
 // rollout with global index g; zpn, zpu: the handle's injected streams (whole, indexed by g) or both null: the generator under `seed`.
 // over: the hook's overdraw bits are OR-ed in at bits 2 (normals) and 3 (uniforms).  Returns true where q holds a NaN although p had
 // none: the rollout's DomainError (the caller sets dom).  A hook that leaves q alone changes no bit.
+// Under RAT_PARAM_SHIFT: pshift is the shift row of the parameter normals, logw leaves holding the parameter part of the likelihood ratio.
 __device__ __forceinline__ bool rat_src_params(long g, unsigned long long seed, const double *zpn, const double *zpu, const double *p,
-                                               double (&q)[RAT_N_PARAMS], int &over) {
+                                               double (&q)[RAT_N_PARAMS], int &over RAT_PARAM_SHIFT_ARGS) {
     rat_param_rng rng;
     rng.gen = (zpn == nullptr && zpu == nullptr);
     rng.zn = (rng.gen || RAT_PARAM_NORMALS == 0) ? nullptr : zpn + g * (long)RAT_PARAM_NORMALS;
@@ -78,6 +111,9 @@ __device__ __forceinline__ bool rat_src_params(long g, unsigned long long seed, 
     rng.g0 = (unsigned)g; rng.g1 = (unsigned)(g >> 32);
     rng.k0 = (unsigned)seed; rng.k1 = (unsigned)(seed >> 32);
     rng.in = 0; rng.iu = 0; rng.over = 0; rng.spare_n = 0.0; rng.spare_u = 0.0;
+#ifdef RAT_PARAM_SHIFT
+    rng.shift = pshift; rng.logw = 0.0;
+#endif
     bool inok = true;
 #pragma unroll
     for (int i = 0; i < RAT_N_PARAMS; ++i) { q[i] = p[i]; inok = inok && !src_nan(q[i]); }
@@ -86,6 +122,9 @@ __device__ __forceinline__ bool rat_src_params(long g, unsigned long long seed, 
 #pragma unroll
     for (int i = 0; i < RAT_N_PARAMS; ++i) outnan = outnan || src_nan(q[i]);
     over |= rng.over << 2;
+#ifdef RAT_PARAM_SHIFT
+    logw = rng.logw;
+#endif
     return inok && outnan;
 }
 
@@ -104,6 +143,8 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_params_sample(SrcParams
 #endif
 #elif defined(RAT_PARAMS_SAMPLE_KERNEL)
 #error "rat_policy_params_sample is compiled with parameter sampling on"
+#elif defined(RAT_PARAM_SHIFT)
+#error "RAT_PARAM_SHIFT needs parameter sampling on (rat_policy_params_sampling)"
 #endif
 
 // What a rollout hands the user's functions as p: the problem's, or with parameter sampling on its own, drawn once in front of step 0.
@@ -111,9 +152,11 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_params_sample(SrcParams
 struct src_rollout_params {
 #ifdef RAT_USER_PARAMS_ON
     double q[RAT_N_PARAMS];
-    // rat_src_params: true for the DomainError of a NaN parameter; the hook's overdraw bits go to `over`
-    __device__ __forceinline__ bool draw(long g, unsigned long long seed, const double *zpn, const double *zpu, const double *p, int &over) {
-        return rat_src_params(g, seed, zpn, zpu, p, q, over);
+    // rat_src_params: true for the DomainError of a NaN parameter; the hook's overdraw bits go to `over` (and under RAT_PARAM_SHIFT the
+    // parameter part of the rollout's likelihood ratio to `logw`)
+    __device__ __forceinline__ bool draw(long g, unsigned long long seed, const double *zpn, const double *zpu, const double *p,
+                                         int &over RAT_PARAM_SHIFT_ARGS) {
+        return rat_src_params(g, seed, zpn, zpu, p, q, over RAT_PARAM_SHIFT_PASS);
     }
     __device__ __forceinline__ const double *of(const double *) const { return q; }
 #else

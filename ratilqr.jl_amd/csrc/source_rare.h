@@ -21,6 +21,8 @@
 // With RAT_RARE_USER_EVENT (rat_policy_rare_event_user; RAT_N_EVENT comes with it) the rollout part is the same text and the margin part is
 // one rat_user_event call per step on the lane's own (x_t, u_t), u_N = 0, as rat_src_user_events (source_events.h) makes it: g arrives as
 // NaN, entry a.event is the step's g, every step 0 .. N is watched.  No LDS, no MFMA, no butterfly: no lane works with another.
+// With RAT_PARAM_SHIFT (rat_policy_rare_event_params; either variant, parameter sampling on) the shift table has a row N: entry i shifts
+// the i-th rng.normal() of rat_user_params (source_params.h), whose likelihood ratio is where the lane's logw starts.
 #pragma once
 #include "rat_rng.h"
 #include "source_step.h"
@@ -109,10 +111,15 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_rare_rollout(SrcRareArg
     const double nan = __builtin_nan("");
     double M = nan;
     int dom = 0;
-    // this rollout's parameters, where sampling is on, from N(0, 1) / U[0, 1): never shifted, nothing added to logw (a lane without a
-    // rollout calls none of the user's functions and holds nothing here)
+    // this rollout's parameters, where sampling is on, from N(0, 1) / U[0, 1): not shifted, nothing added to logw -- or under
+    // RAT_PARAM_SHIFT (rat_policy_rare_event_params) the normals from the proposal shifted by row N of the shift table, and the lane's
+    // logw starts from the parameter part (a lane without a rollout calls none of the user's functions and holds nothing here)
     src_rollout_params own;
+#ifdef RAT_PARAM_SHIFT
+    if (live && own.draw(j, a.seed, a.zpn, a.zpu, a.p, rng.over, a.shift + N * 12, rng.logw)) dom = 1;
+#else
     if (live && own.draw(j, a.seed, a.zpn, a.zpu, a.p, rng.over)) dom = 1;
+#endif
     const double *p = own.of(a.p);
 #ifdef RAT_USER_POLICY
     double up[4] = {0.0, 0.0, 0.0, 0.0};                              // the control applied at step t - 1

@@ -223,6 +223,9 @@ class GenericContext(il.Context):
     def policy_rare_event_user(self, *a, **k):
         self._carrier_only("policy_rare_event_user")
 
+    def policy_rare_event_params(self, *a, **k):
+        self._carrier_only("policy_rare_event_params")
+
     def set_param_sampling(self, *a, **k):
         self._carrier_only("set_param_sampling")
 

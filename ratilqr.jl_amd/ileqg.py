@@ -156,6 +156,8 @@ class RareEventResult:
     trace: np.ndarray
     margins: np.ndarray | None = None
     logw: np.ndarray | None = None
+    param_shift: np.ndarray | None = None                             # policy_rare_event_params alone: (param_normals,)
+    param_trace: np.ndarray | None = None                             # ... and (n_iter,): |param_shift| after every iteration that updated
 
 
 class Context:
@@ -171,9 +173,11 @@ class Context:
         nv.check(L.rat_create(C.byref(opts) if opts is not None else None, self.max_batch, self.spec_eps,
                               self.device, C.byref(self.h)))
         self._fin = weakref.finalize(self, L.rat_destroy, self.h)
+        self._param_normals = 0                                       # param_normals of the handle's parameter sampling (0: off)
         self._keep = self._upload(problem) if problem is not None else None
 
     def _upload(self, problem):
+        self._param_normals = 0                                       # (rat_problem_set_source switches parameter sampling off)
         if getattr(problem, "model", 0) == MODEL_SOURCE:            # user-written f, c, h: compiled at run time (rat_problem_set_source)
             keep = nv.set_source(self.h, problem)
             self.params = keep["params"].copy()                       # what this handle's kernels read (set_params changes it)
@@ -206,6 +210,7 @@ class Context:
         behind policy_evaluate_noise call the source's rat_user_params once per rollout.  Injected streams are copied by the call."""
         if ps is None:
             nv.check(nv.lib().rat_policy_params_sampling(self.h, C.c_int32(0), C.c_int32(0), None, None, C.c_int64(0)))
+            self._param_normals = 0
             return
         if not isinstance(ps, ParamSampling):
             raise TypeError("set_param_sampling needs a ParamSampling or None")
@@ -218,6 +223,7 @@ class Context:
                     raise ValueError("zpn and zpu hold different numbers of rollouts")
                 K = z.size // per
         nv.check(nv.lib().rat_policy_params_sampling(self.h, C.c_int32(pn), C.c_int32(pu), nv.P(ps.zpn), nv.P(ps.zpu), C.c_int64(K)))
+        self._param_normals = pn
 
     def sample_params(self, K, seed=0):
         """The parameters rat_user_params draws for rollouts 0 .. K - 1 under `seed` (or the injected draws): (K, n_params), row j behind
@@ -679,6 +685,57 @@ class Context:
             r[k] = int(r[k])
         return RareEventResult(shift=s_out, trace=trace, margins=margins, logw=logw, **r)
 
+    def policy_rare_event_params(self, x_nom, l, L, event, K, noise=None, seed=None, shift=None, param_shift=None, adapt="both", n_iter=8,
+                                 rho=0.1, n_event=0, want_margins=False, want_logw=False):
+        """policy_rare_event_noise (n_event=0: event is an Event) or policy_rare_event_user (n_event in 1 .. 16: event is the entry of
+        rat_user_event) for an event that an uncertain parameter drives (rat_policy_rare_event_params): with parameter sampling on
+        (set_param_sampling, the device generator) the i-th rng.normal() of the source's rat_user_params returns param_shift[i] + xi and
+        its likelihood ratio is part of every rollout's logw.  adapt: "both", "step" or "params" -- the part that is not adapted stays
+        at the shift handed in (0 for None), is still applied and still counted; "params" is the choice for an event that the
+        parameters alone drive.  A model without process noise declares one normal per step and multiplies it by 0.
+        Returns a RareEventResult with param_shift (param_normals,) and param_trace (n_iter,)."""
+        if not isinstance(noise, UserNoise):
+            raise TypeError("policy_rare_event_params needs noise=UserNoise(...)")
+        if noise.zn is not None or noise.zu is not None:
+            raise ValueError("policy_rare_event_params draws from the device generator only: no injected streams")
+        if adapt not in ("both", "step", "params"):
+            raise ValueError('policy_rare_event_params: adapt is "both", "step" or "params"')
+        n, m, N, npn, npu, pn = self.n, self.m, self.N, noise.normals_per_step, noise.uniforms_per_step, self._param_normals
+        n_event = int(n_event)
+        Qc, a, b, lo, hi, ev = None, None, 0.0, 0, 0, 0
+        if n_event == 0:
+            Q, a, b, lo, hi = event.dense(n, m, N)
+            Qc = nv.f64(Q.T) if Q is not None else None               # column-major
+            a = nv.f64(a)
+        else:
+            ev = int(event)
+        s_in = ps_in = None
+        if shift is not None:
+            s_in = nv.f64(shift)
+            if s_in.shape != (N, npn):
+                raise ValueError(f"policy_rare_event_params: the shift is {s_in.shape}, (N, normals_per_step) = ({N}, {npn}) is served")
+        if param_shift is not None:
+            ps_in = nv.f64(param_shift)
+            if ps_in.shape != (pn,):
+                raise ValueError(f"policy_rare_event_params: the parameter shift is {ps_in.shape}, (param_normals,) = ({pn},) is served")
+        K, n_iter = int(K), int(n_iter)
+        seed = noise.seed if seed is None else int(seed)
+        stats, s_out, trace = np.zeros(nv.RE_NSTAT), np.zeros((N, max(npn, 1))), np.zeros((max(n_iter, 0), nv.RE_NTRACE))
+        ps_out, ptrace = np.zeros(max(pn, 1)), np.zeros(max(n_iter, 0))
+        margins = np.zeros(max(K, 1)) if want_margins else None
+        logw = np.zeros(max(K, 1)) if want_logw else None
+        nv.check(nv.lib().rat_policy_rare_event_params(self.h, nv.P(nv.f64(x_nom)), nv.P(nv.f64(l)), nv.P(nv.cm3(L)) if L is not None else None,
+                                                       C.c_int64(K), C.c_int32(npn), C.c_int32(npu), C.c_uint64(seed), C.c_int32(n_event),
+                                                       C.c_int32(ev), nv.P(Qc), nv.P(a), C.c_double(b), C.c_int32(lo), C.c_int32(hi),
+                                                       nv.P(s_in), nv.P(ps_in), C.c_int32({"step": 1, "params": 2, "both": 3}[adapt]),
+                                                       C.c_int32(n_iter), C.c_double(float(rho)), nv.P(stats), nv.P(s_out), nv.P(ps_out),
+                                                       nv.P(trace) if n_iter > 0 else None, nv.P(ptrace) if n_iter > 0 else None,
+                                                       nv.P(margins), nv.P(logw)))
+        r = {k: float(stats[i]) for i, k in enumerate(nv.RE_SLOTS)}
+        for k in ("n_viol", "n_ok", "n_domain", "flag", "n_iter"):
+            r[k] = int(r[k])
+        return RareEventResult(shift=s_out, trace=trace, margins=margins, logw=logw, param_shift=ps_out[:pn], param_trace=ptrace, **r)
+
     def integrate_cost(self, x, u):
         out = C.c_double()
         nv.check(nv.lib().rat_integrate_cost(self.h, nv.P(nv.f64(x)), nv.P(nv.f64(u)), C.byref(out)))
@@ -974,6 +1031,16 @@ def rare_event_probability_noise(problem, x, l, L, event, noise, K=1 << 16, seed
     the problem's default context.  noise is a UserNoise (the device generator only); the shift is (N, noise.normals_per_step)."""
     return _ctx(problem).policy_rare_event_noise(x, l, L, event, K, noise=noise, seed=seed, shift=shift, n_iter=n_iter, rho=rho,
                                                  want_margins=want_margins, want_logw=want_logw)
+
+
+def rare_event_probability_params(problem, x, l, L, event, noise, sampling, K=1 << 16, seed=None, shift=None, param_shift=None, adapt="both",
+                                  n_iter=8, rho=0.1, n_event=0, want_margins=False, want_logw=False):
+    """rare_event_probability_noise for an event that an uncertain parameter drives: Context.policy_rare_event_params on the problem's
+    default context, with parameter sampling switched on as `sampling` (a ParamSampling on the device generator) says."""
+    ctx = _ctx(problem)
+    ctx.set_param_sampling(sampling)
+    return ctx.policy_rare_event_params(x, l, L, event, K, noise=noise, seed=seed, shift=shift, param_shift=param_shift, adapt=adapt,
+                                        n_iter=n_iter, rho=rho, n_event=n_event, want_margins=want_margins, want_logw=want_logw)
 
 
 def integrate_cost(problem, x_array, u_array):          # ileqg.jl:115-124
