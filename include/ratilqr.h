@@ -1056,6 +1056,8 @@ int32_t rat_get_path(rat_handle h, int64_t B);
  *                            (rat_debug_set clears it)
  *   lq_replay_stack 0 / 1    the replayed pair forms row 12 of T for both recursions in one stacked chain of three MFMAs (column 12 of the gain
  *                            recursion's V in column 4 of the evaluation's operand); 0 = one chain each; identical outputs   (1)
+ *   lq_replay_factor 0 / 1   the replayed pair takes the LDL' factor of H from the record (the recording pass stores it in lanes of the
+ *                            -M^-1 words that hold no matrix data); 0 = every step factors the recorded H again; identical outputs  (1)
  *   fly             0 / 1    round-based path, E > 1: line-search candidates without tile records                         (1)
  *   fly_multi       0 / 1    ... and all candidates of a sample rolled out by one wavefront                               (1)
  *   dual            0 / 1    round-based path: candidate 0 paired with the next gain sweep in one wavefront              (E > 1)

@@ -251,6 +251,32 @@ __device__ __forceinline__ double racc_diag(double racc, double nth12, double sj
     return __builtin_fma(nsj, q, racc);
 }
 
+// H = L D L' of the 4 x 4 control Hessian (ileqg.jl:372-382), every lane the whole factor.  The gain recursion of a full pair records it
+// and a replayed pair loads it instead of factoring again (sweep_dual.h; layout.h: REC_FACT_*), so both must round alike: ONE order in
+// source -- the one the compiler's contraction gave every place before (profiles/lq_replay_factor.md).
+struct Ldl4 {
+    double l10, l20, l30, l21, l31, l32, d1, d2, d3, i0, i1, i2, i3;       // d0 = h00; i_k = 1 / d_k
+};
+__device__ __forceinline__ Ldl4 ldl4_factor(double h00, double h01, double h02, double h03, double h11, double h12, double h13,
+                                            double h22, double h23, double h33) {
+#pragma clang fp contract(off)
+    Ldl4 f;
+    f.i0 = fast_rcp(h00);
+    f.l10 = h01 * f.i0; f.l20 = h02 * f.i0; f.l30 = h03 * f.i0;
+    f.d1 = __builtin_fma(-h01, f.l10, h11);
+    f.i1 = fast_rcp(f.d1);
+    f.l21 = __builtin_fma(-h01, f.l20, h12) * f.i1;
+    f.l31 = __builtin_fma(-h01, f.l30, h13) * f.i1;
+    const double p21 = f.d1 * f.l21, p31 = f.d1 * f.l31;
+    f.d2 = __builtin_fma(-f.l21, p21, __builtin_fma(-h02, f.l20, h22));
+    f.i2 = fast_rcp(f.d2);
+    f.l32 = __builtin_fma(-f.l31, p21, __builtin_fma(-h02, f.l30, h23)) * f.i2;
+    const double p32 = f.d2 * f.l32;
+    f.d3 = __builtin_fma(-f.l32, p32, __builtin_fma(-f.l31, p31, __builtin_fma(-h03, f.l30, h33)));
+    f.i3 = fast_rcp(f.d3);
+    return f;
+}
+
 // The four 16-lane rows of x, each broadcast to every row (v_permlane32_swap + v_permlane16_swap, gfx950; tools/ubench/xlane.hip checks
 // the pattern lane by lane): r[g] on lane (., j) = x of lane (g, j).
 __device__ __forceinline__ void rows_bcast(double x, double (&r)[4]) {

@@ -70,6 +70,7 @@ struct rat_handle_s {
                                      // sweep (RecDev, kernels.h; switch lq_replay)
     bool lq_replay_last = true;      // ... and so does the evaluation that ends the solve (replay_eval_body; switch lq_replay_last)
     bool lq_replay_stack = true;     // ... the replayed pair's two T rows from one stacked mm3 (replay_body<true, STACK>; switch lq_replay_stack)
+    bool lq_replay_factor = true;    // ... the replayed pair's LDL' of H from the record (replay_body<true, .., FACT>; switch lq_replay_factor)
     RecDev rec = {};                 // ... its per-sample words (st_allocs) and the record (rec.m: rec_cap doubles, allocated by the first batch that uses it)
     size_t rec_cap = 0;
     unsigned xepoch = 0;             // ... launches so far (the hand-over words carry it: nothing to clear between launches)
@@ -340,6 +341,7 @@ static const DebugSwitch debug_switches[] = {
     {"lq_replay_last_count", [](rat_handle h, int64_t) { if (h->rec.count) { (void)hipStreamSynchronize(h->stream); (void)hipMemset(h->rec.count + 1, 0, sizeof(int)); } },
      [](rat_handle h) -> int64_t { int c = 0; if (h->rec.count) { (void)hipStreamSynchronize(h->stream); (void)hipMemcpy(&c, h->rec.count + 1, sizeof(int), hipMemcpyDeviceToHost); } return c; }},
     {"lq_replay_stack", [](rat_handle h, int64_t v) { h->lq_replay_stack = (v != 0); }, [](rat_handle h) -> int64_t { return h->lq_replay_stack; }},
+    {"lq_replay_factor", [](rat_handle h, int64_t v) { h->lq_replay_factor = (v != 0); }, [](rat_handle h) -> int64_t { return h->lq_replay_factor; }},
     {"psw_acl", [](rat_handle h, int64_t v) { h->psw_acl = (v != 0); }, [](rat_handle h) -> int64_t { return h->psw_acl; }},
     {"psw_comp", [](rat_handle h, int64_t v) { h->psw_comp = (int)std::max<int64_t>(100, v); }, [](rat_handle h) -> int64_t { return h->psw_comp; }},
     {"src_tpw", [](rat_handle h, int64_t v) { h->src_tpw = (v >= 64) ? 64 : (v >= 32 ? 32 : 16); }, [](rat_handle h) -> int64_t { return h->src_tpw; }},
@@ -1464,6 +1466,7 @@ static rat_rc run_batch(rat_handle h, const double *theta_dev, int B, const Batc
             fa.sw.rec = h->rec;
             fa.sw.rec.last = h->lq_replay_last ? 1 : 0;
             fa.sw.rec.stack = h->lq_replay_stack ? 1 : 0;
+            fa.sw.rec.factor = h->lq_replay_factor ? 1 : 0;
         }
         fa.theta_in = theta_dev;
         fa.out_value = out.value; fa.out_status = out.status; fa.out_iters = out.iters; fa.out_ls = out.ls;

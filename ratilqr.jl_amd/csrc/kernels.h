@@ -15,7 +15,8 @@
 // problem A, B, Q, R, P, W do not depend on the trajectory, so every later paired sweep at the same mu runs the matrix half of the recursions
 // of the last full paired gain sweep again, bit for bit.  That sweep records per step what the vector half reads from it; later pairs replay
 // only the vector half (sweep_dual.h: replay_body), and so does the evaluation that ends the solve.  Null m: no record (every sweep runs in full).
-#define REC_STEP 256       /* doubles per step: lane-major, 4 per lane = -M^-1 (3 accumulator registers) and [G | H + mu I] (register 3 of F) */
+#define REC_STEP 256       /* doubles per step: lane-major, 4 per lane = -M^-1 (3 accumulator registers) and [G | H + mu I] (register 3 of F); */
+                           /* on the lanes of column 12 the three -M^-1 words hold the LDL' factor of H (layout.h: REC_FACT_*) */
 struct RecDev {
     double *m;             // [B][N][REC_STEP]
     double *mu;            // [B] mu of the recorded pass (bitwise: the replay gate)
@@ -25,7 +26,8 @@ struct RecDev {
     int *lgen;             // [B][2] record generation the gains of each half of L / dl were solved from (0: none)
     int *count;            // [2] sweeps replayed so far in pairs (switch lq_replay_count) | evaluations that end a solve replayed (lq_replay_last_count)
     int last;              // the evaluation that ends a solve replays too (switch lq_replay_last)
-    int stack;             // the replayed pair forms row 12 of T for both recursions in one mm3 (replay_body<true, STACK>; switch lq_replay_stack)
+    short stack;           // the replayed pair forms row 12 of T for both recursions in one mm3 (replay_body<true, STACK>; switch lq_replay_stack)
+    short factor;          // (two shorts: FusedArgs stays a whole number of 64-B lines) the replayed pair takes the LDL' of H from the record (layout.h: REC_FACT_*; replay_body<true, .., FACT>; switch lq_replay_factor)
 };
 
 struct SweepArgs {

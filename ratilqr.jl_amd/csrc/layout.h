@@ -70,7 +70,16 @@
  * several of them -- or runs them on several wavefronts of one workgroup -- declares ONE area per wave instead of one per instantiation. */
 #define WLS_SWEEP 232       /* sweep_body: gain rows [L|dl] 64 + exchange area 168 */
 #define WLS_DUAL  400       /* sweep_dual_body: 64 + 2 x 168 */
-#define ROLLIN_NST 52       /* longest horizon whose closed-loop operands are staged in LDS by the fused solves */
+/* The LDL' factor of H inside the Riccati-matrix record (kernels.h: RecDev; writer sweep_dual_body<.., REC>, reader replay_body<true, ..>).
+ * The three -M^-1 words of a lane hold columns 0..11 of the matrix; on the lanes of column 12 they carry the factor instead: word r of lane
+ * (g, 12) is value 3 g + r of  l10 l20 l30 | l21 l31 l32 | d1 d2 i0 | i1 i2 i3  (i_k = 1 / d_k).  The reader spreads them over the wave
+ * through twelve doubles of the gain recursion's exchange area that no lane writes otherwise: the idle slots of the lanes g == 0. */
+#define REC_FACT_J 12
+#define REC_FACT_VAL(g, r) (3 * (g) + (r))
+#define EX_FACT 104         /* exB[EX_FACT + value]; the other lanes' copies of their three words land on EX_FACT_SINK .. + 2 */
+#define EX_FACT_SINK 116
+#define EX_ZERO3 100        /* exA[EX_ZERO3 + 0, 4, 8] = 0: what the factor's lanes multiply their three words with in theta s' M^-1 s */
+#define ROLLIN_NST 52      /* longest horizon whose closed-loop operands are staged in LDS by the fused solves */
 #define STG_CL ((ROLLIN_NST * LSTR + 63) / 64)
 #define STG_CX (((ROLLIN_NST + 1) * XSTR + 63) / 64)
 #define STG_CU ((ROLLIN_NST * USTR + 63) / 64)

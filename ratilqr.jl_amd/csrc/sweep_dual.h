@@ -219,6 +219,7 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
             xzB = mm3(vB, cz, (d4){0, 0, 0, 0});
         }
         d4 tmA, tmB;
+        [[maybe_unused]] double mrec[3] = {0.0, 0.0, 0.0};          // REC: -M^-1 of recursion B as recorded (theta == 0: no valid record)
         if (theta != 0.0) {
             exA[svo] = vA[3]; exB[svo] = vB[3];
             d4 mA, mB;
@@ -239,10 +240,8 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
             if (!deadB && (!(pdB > 0) || !(rprodB * 0.0 == 0.0))) deadB = 2;      // @assert isposdef(M) (:366)
             rexpA += __builtin_amdgcn_frexp_exp(rprodA); rprodA = __builtin_amdgcn_frexp_mant(rprodA);
             rexpB += __builtin_amdgcn_frexp_exp(rprodB); rprodB = __builtin_amdgcn_frexp_mant(rprodB);
-            if (REC) {
-                *reinterpret_cast<double2 *>(recp + (long)t * REC_STEP) = make_double2(mB[0], mB[1]);
-                recp[(long)t * REC_STEP + 2] = mB[2];
-                rchk = fma((mB[0] + mB[1]) + mB[2], 0.0, rchk);
+            if (REC) {                                               // (stored below, once the step's factor of H can ride along)
+                mrec[0] = mB[0]; mrec[1] = mB[1]; mrec[2] = mB[2];
             }
             if (WM == 2) {
                 raccA = racc_diag(raccA, nth12, exA[84 + j], mA[0], mA[1], mA[2], exA[84 + g], exA[84 + 4 + g], exA[84 + 8 + g]);
@@ -302,14 +301,24 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
         const double h11 = exB[16 + 13], h12 = exB[16 + 14], h13 = exB[16 + 15];
         const double h22 = exB[32 + 14], h23 = exB[32 + 15], h33 = exB[48 + 15];
         const double g0 = exB[goff[0]], g1 = exB[goff[1]], g2 = exB[goff[2]], g3 = exB[goff[3]];
-        const double d0 = h00, i0 = fast_rcp(d0);
-        const double l10 = h01 * i0, l20 = h02 * i0, l30 = h03 * i0;
-        const double d1 = h11 - l10 * h01, i1 = fast_rcp(d1);
-        const double l21 = (h12 - l20 * h01) * i1, l31 = (h13 - l30 * h01) * i1;
-        const double d2 = h22 - l20 * h02 - l21 * (l21 * d1), i2 = fast_rcp(d2);
-        const double l32 = (h23 - l30 * h02 - l31 * (l21 * d1)) * i2;
-        const double d3 = h33 - l30 * h03 - l31 * (l31 * d1) - l32 * (l32 * d2), i3 = fast_rcp(d3);
-        if (!deadB && !(d0 > 0.0 && d1 > 0.0 && d2 > 0.0 && d3 > 0.0)) deadB = 1;    // !isposdef(H) (:372): left to the plain kernel
+        const Ldl4 f = ldl4_factor(h00, h01, h02, h03, h11, h12, h13, h22, h23, h33);
+        const double l10 = f.l10, l20 = f.l20, l30 = f.l30, l21 = f.l21, l31 = f.l31, l32 = f.l32, i0 = f.i0, i1 = f.i1, i2 = f.i2, i3 = f.i3;
+        if (!deadB && !(h00 > 0.0 && f.d1 > 0.0 && f.d2 > 0.0 && f.d3 > 0.0)) deadB = 1;    // !isposdef(H) (:372): left to the plain kernel
+        if (REC) {
+            // the record's -M^-1 words, the factor on the lanes of column 12 (layout.h: REC_FACT_*; nothing in this pass reads mrec again).
+            // Every value is on every lane: a per-lane select, exact for any bits; a non-finite one invalidates the record through rchk
+            const double fv[12] = {f.l10, f.l20, f.l30, f.l21, f.l31, f.l32, f.d1, f.d2, f.i0, f.i1, f.i2, f.i3};
+            const bool g1 = g & 1, g2 = g & 2, fl = (j == REC_FACT_J);
+            double w[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const double lo = g1 ? fv[REC_FACT_VAL(1, r)] : fv[REC_FACT_VAL(0, r)], hi = g1 ? fv[REC_FACT_VAL(3, r)] : fv[REC_FACT_VAL(2, r)];
+                w[r] = fl ? (g2 ? hi : lo) : mrec[r];
+            }
+            *reinterpret_cast<double2 *>(recp + (long)t * REC_STEP) = make_double2(w[0], w[1]);
+            recp[(long)t * REC_STEP + 2] = w[2];
+            rchk = fma((w[0] + w[1]) + w[2], 0.0, rchk);
+        }
         const double y0 = -g0;
         const double y1 = -g1 - l10 * y0;
         const double y2 = -g2 - l20 * y0 - l21 * y1;
@@ -421,6 +430,11 @@ __device__ __forceinline__ void sweep_dual_body(const SweepArgs &a, const int b,
 // mask: columns 4..7 <- B's 12..15, the rest A's own), one mm3 runs against Y, and row 12 (register 3, g == 0) is recursion A's T row,
 // row 4 (register 1, g == 0) recursion B's: the same column of V, the same Y, the same K order and start value as the two separate
 // mm3 -- the same bits, on the lanes that read them before.  13 MFMAs per step become 10.
+// FACT (GAINB only; switch lq_replay_factor): the LDL' of H is not formed again.  H + mu I is matrix data: the factor every lane would compute
+// from the recorded H is the one recursion B of the recording pass computed at that step (one helper, one rounding order: ldl4_factor), and
+// that pass stored it on the column-12 lanes of the three -M^-1 words (layout.h: REC_FACT_*).  Those lanes copy their words to twelve idle
+// doubles of exB before the step's fence, every lane reads the ten values the substitutions need; the substitutions, laB, Ua and the
+// V update are the same source either way.
 // wls: WLS_DUAL doubles
 // =======================================================================================================================================
 struct RTile {
@@ -428,7 +442,7 @@ struct RTile {
     double x, xj, la;      // [qr | q] row, x_t[j], own entry of L_t (evaluation)
 };
 
-template <bool GAINB, bool STACK = false>
+template <bool GAINB, bool STACK = false, bool FACT = false>
 __device__ __forceinline__ bool replay_body(const SweepArgs &a, const int b, double *const wls) {
     int lane_ = threadIdx.x & 63;
     asm volatile("" : "+v"(lane_));      // opaque per phase (see sweep_body)
@@ -481,6 +495,9 @@ __device__ __forceinline__ bool replay_body(const SweepArgs &a, const int b, dou
     const int lx = (l < 17) ? l : TS_PAD - TS_QR;
     const int jc = (j < 12) ? j : 11;
     const int svo = (g == 0) ? 84 + j : 104 + l, fbo = (g == 0) ? 64 + j : 104 + l;
+    [[maybe_unused]] const int fwo = (j == REC_FACT_J) ? EX_FACT + REC_FACT_VAL(g, 0) : EX_FACT_SINK;     // FACT: where this lane's three words go
+    const int sro = (j == REC_FACT_J) ? EX_ZERO3 : 84 + g;       // s_vec rows g, 4 + g, 8 + g of racc_diag; the factor's lanes: three zeros
+    if (l < 3) exA[EX_ZERO3 + 4 * l] = 0.0;
     [[maybe_unused]] double *const pgl = (j < 12) ? Lout + g * 12 + j : (j == 12 ? dlout + g : sample_sink(st, b) + l);
     [[maybe_unused]] const long sgl = (j < 12) ? LSTR : (j == 12 ? USTR : 0);
     double zt[3], dg[3], nwrow[3];                               // [A | B] image and diagonal selectors (FlyCtx), -inv(W)_ii of this lane's rows
@@ -525,10 +542,14 @@ __device__ __forceinline__ bool replay_body(const SweepArgs &a, const int b, dou
         if (GAINB) probe += (vB[0] + vB[1]) + (vB[2] + vB[3]);
         if (__ballot(!(probe - probe == 0.0))) return false;
         const double m0 = cur.m01.x, m1 = cur.m01.y, m2 = cur.m2h.x, gh = cur.m2h.y;
+        // column 12 of the three -M^-1 words is the recorded factor of H (layout.h: REC_FACT_*), not matrix data: handed to every lane
+        // through the exchange area.  What those lanes feed takes no bit from a finite value there: rows 12..15 of Y, which nothing reads,
+        // and racc through nth12 = 0 -- against zeros (sro), so that the sum stays finite whatever s_vec is
+        if (GAINB && FACT) { exB[fwo] = m0; exB[fwo + 1] = m1; exB[fwo + 2] = m2; }
         exA[svo] = vA[3];
         if (GAINB) exB[svo] = vB[3];
         // theta s_vec' M^-1 s_vec (:387) of the evaluation (a gain sweep's own value is not used by step!)
-        raccA = racc_diag(raccA, nth12, exA[84 + j], m0, m1, m2, exA[84 + g], exA[84 + 4 + g], exA[84 + 8 + g]);
+        raccA = racc_diag(raccA, nth12, exA[84 + j], m0, m1, m2, exA[sro], exA[sro + 4], exA[sro + 8]);
         d4 mw;
         mw[0] = m0 * nwrow[0]; mw[1] = m1 * nwrow[1]; mw[2] = m2 * nwrow[2]; mw[3] = 0.0;
         const d4 y2 = mm3(mw, cz, (d4){0, 0, 0, 0});
@@ -556,17 +577,20 @@ __device__ __forceinline__ bool replay_body(const SweepArgs &a, const int b, dou
         const double qc = readlane_f64(cur.x, 16);
         if (GAINB) {                                             // optimal gains (:372-382)
             const double gaB = fma(gh, m12, exB[gaoff]);
-            const double h00 = exB[12], h01 = exB[13], h02 = exB[14], h03 = exB[15];
-            const double h11 = exB[16 + 13], h12 = exB[16 + 14], h13 = exB[16 + 15];
-            const double h22 = exB[32 + 14], h23 = exB[32 + 15], h33 = exB[48 + 15];
             const double g0 = exB[goff[0]], g1 = exB[goff[1]], g2 = exB[goff[2]], g3 = exB[goff[3]];
-            const double d0 = h00, i0 = fast_rcp(d0);
-            const double l10 = h01 * i0, l20 = h02 * i0, l30 = h03 * i0;
-            const double d1 = h11 - l10 * h01, i1 = fast_rcp(d1);
-            const double l21 = (h12 - l20 * h01) * i1, l31 = (h13 - l30 * h01) * i1;
-            const double d2 = h22 - l20 * h02 - l21 * (l21 * d1), i2 = fast_rcp(d2);
-            const double l32 = (h23 - l30 * h02 - l31 * (l21 * d1)) * i2;
-            const double d3 = h33 - l30 * h03 - l31 * (l31 * d1) - l32 * (l32 * d2), i3 = fast_rcp(d3);
+            double l10, l20, l30, l21, l31, l32, i0, i1, i2, i3;
+            if (FACT) {                                          // the factor the recorded pass formed from these very H (d1, d2: not needed)
+                const double *const fx = exB + EX_FACT;
+                l10 = fx[REC_FACT_VAL(0, 0)]; l20 = fx[REC_FACT_VAL(0, 1)]; l30 = fx[REC_FACT_VAL(0, 2)];
+                l21 = fx[REC_FACT_VAL(1, 0)]; l31 = fx[REC_FACT_VAL(1, 1)]; l32 = fx[REC_FACT_VAL(1, 2)];
+                i0 = fx[REC_FACT_VAL(2, 2)]; i1 = fx[REC_FACT_VAL(3, 0)]; i2 = fx[REC_FACT_VAL(3, 1)]; i3 = fx[REC_FACT_VAL(3, 2)];
+            } else {
+                const double h00 = exB[12], h01 = exB[13], h02 = exB[14], h03 = exB[15];
+                const double h11 = exB[16 + 13], h12 = exB[16 + 14], h13 = exB[16 + 15];
+                const double h22 = exB[32 + 14], h23 = exB[32 + 15], h33 = exB[48 + 15];
+                const Ldl4 f = ldl4_factor(h00, h01, h02, h03, h11, h12, h13, h22, h23, h33);
+                l10 = f.l10; l20 = f.l20; l30 = f.l30; l21 = f.l21; l31 = f.l31; l32 = f.l32; i0 = f.i0; i1 = f.i1; i2 = f.i2; i3 = f.i3;
+            }
             const double y0 = -g0;
             const double y1 = -g1 - l10 * y0;
             const double yy2 = -g2 - l20 * y0 - l21 * y1;
@@ -630,6 +654,7 @@ __device__ __forceinline__ bool replay_body(const SweepArgs &a, const int b, dou
     return true;
 }
 __device__ __forceinline__ bool replay_dual_body(const SweepArgs &a, const int b, double *const wls) {
+    if (a.rec.factor) return a.rec.stack ? replay_body<true, true, true>(a, b, wls) : replay_body<true, false, true>(a, b, wls);
     return a.rec.stack ? replay_body<true, true>(a, b, wls) : replay_body<true>(a, b, wls);
 }
 __device__ __forceinline__ bool replay_eval_body(const SweepArgs &a, const int b, double *const wls) { return replay_body<false>(a, b, wls); }
