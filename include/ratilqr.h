@@ -516,7 +516,7 @@ rat_rc rat_policy_tail_risk(rat_handle h, const double *cost, int64_t K, const d
  * where the dense kernels form 0 Inf = NaN (the worst-case calls give every rollout with a cost a positive weight, so it cannot arise
  * there).
  * Served and refused as the siblings, with the same codes and caps (rows x (N + 1) above 3640, rows x N above 1899 with n_alpha rows);
- * costs uploaded by rat_policy_tail_risk(cost != NULL) are no evaluation's.  rat_policy_events has no CVaR rows. */
+ * costs uploaded by rat_policy_tail_risk(cost != NULL) are no evaluation's.  The safety events of the tail: rat_policy_tail_events, below. */
 rat_rc rat_policy_tail_trajectory(rat_handle h, const double *alpha, int32_t n_alpha, double *rows_out, double *mean_out, double *cov_out);
 rat_rc rat_policy_tail_disturbance(rat_handle h, const double *alpha, int32_t n_alpha, double *rows_out, double *mean_w_out,
                                    double *cov_w_out, double *cov_wz_out);
@@ -576,6 +576,38 @@ rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double *Q, const d
 rat_rc rat_policy_events_user(rat_handle h, int32_t n_event,
                               const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
                               double *rows_out, double *event_out, double *step_out, double *margin_out);
+/* Safety events under the CVaR adversary: among the worst (1 - alpha) share of the rollouts, how often is an event violated, where in the
+ * horizon and by how much.  rat_policy_events / rat_policy_events_user with one row per level of rat_policy_tail_risk in place of the
+ * kl_bound / theta rows.  The events, their windows, the extra event "any" at index n_event, M, A, tau and margin_out are the siblings'
+ * in every respect; so is the replay: the same guard against the stored costs, the same evaluations served and refused with the same
+ * codes, the same 64 MiB limit on the partial sums, with n_alpha rows.
+ *   alpha      [n_alpha], 1 <= n_alpha <= 16, every one in [0, 1): rat_policy_tail_risk's rules (RAT_ERR_ARG)
+ *   rows_out   [n_alpha][RAT_TR_NSTAT]: what rat_policy_tail_risk(h, NULL, 0, alpha, n_alpha, ...) returns on the stored costs, bit for bit
+ *   event_out  [n_alpha][n_event + 1][RAT_EV_NSTAT] and step_out [n_alpha][n_event + 1][N+1] (or NULL): the RAT_EV_* slots with y the
+ *              level's tail weight of a rollout -- 1 / (n - a) above VAR, r / (c_eq (n - a)) at VAR, 0 below and for a DomainError rollout,
+ *              uniform on the maxima for a RAT_TR_SATURATED level.  Two slots mean something of their own on a tail row:
+ *              RAT_EV_FLAG is the row's RAT_TR_FLAG (RAT_TR_EMPTY and RAT_TR_NONFINITE rows are NaN except FLAG; the call still returns
+ *              RAT_OK), and RAT_EV_PROB_ROBUST is the CVaR adversary aimed at the event itself, min(1, (N_VIOL / N_OK) / (TAIL_N / N_OK))
+ *              in plain double arithmetic on the device: the largest probability of the event under any p with dp/dq <= N_OK / TAIL_N,
+ *              hence PROB <= PROB_ROBUST on every RAT_TR_OK row -- where every violator lies in the tail the two are one number whose
+ *              two roundings may differ in the last bit: PROB is returned then, so the inequality holds in the bits as well.  N_VIOL
+ *              and MARGIN_MAX are unweighted, the same on every row.
+ *   margin_out [n_event][K] or NULL: rat_policy_events' bit for bit
+ * alpha == 0 is the whole sample: its event_out and step_out rows are the theta = 0 row of rat_policy_events on the same evaluation bit
+ * for bit, and PROB_ROBUST equals PROB there.  A row's bits depend neither on the other levels nor on the other events of the call ("any"
+ * depends on its events).  No floating-point atomics, a fixed summation order.
+ * The schedule is the tail scenarios': at alpha = 0.99 one rollout in a hundred carries weight, so the sums read, per group of four
+ * rollouts, the word of "level r has weight here" bits first.  A group without weight in any row of a workgroup is not loaded (the
+ * unweighted counts and the largest margin still see every rollout) and a rollout without weight in a row adds nothing to it.  Adding 0
+ * changes no bit of a sum, so the results are those of rat_policy_events' own sums on the same weights bit for bit; the one difference: a
+ * rollout WITHOUT weight in a row whose margin is NaN (every g of its window NaN) is left out of that row's MARGIN_MEAN, where the dense
+ * sums form 0 NaN.  The switch tail_dense runs the dense sums on the tail weights. */
+rat_rc rat_policy_tail_events(rat_handle h, int32_t n_event, const double *Q, const double *a, const double *b,
+                              const int32_t *t_lo, const int32_t *t_hi,
+                              const double *alpha, int32_t n_alpha,
+                              double *rows_out, double *event_out, double *step_out, double *margin_out);
+rat_rc rat_policy_tail_events_user(rat_handle h, int32_t n_event, const double *alpha, int32_t n_alpha,
+                                   double *rows_out, double *event_out, double *step_out, double *margin_out);
 /* The largest probability p' an event of probability p can have under any distribution within KL radius d of the sampling one:
  * max { p' : p' log(p' / p) + (1 - p') log((1 - p') / (1 - p)) <= d }, by bisection on [p, 1] until the bracket stops shrinking: two neighbouring doubles, of which the one whose KL is nearer d is returned.  Host
  * only: needs no handle and no GPU.  d == 0 gives p; p == 0 gives 0; p == 1 gives 1; d == +Inf with p > 0 gives 1.  NaN, p outside
@@ -1098,7 +1130,8 @@ int32_t rat_get_path(rat_handle h, int64_t B);
  *   mc_cost_K       read-only      costs the last rat_policy_evaluate / _noise (or rat_policy_worst_case / rat_policy_tail_risk with host costs) left on the device (0: none)
  *   src_mc_tpw      16 / 32 / 64   source models: rollouts per wavefront of rat_policy_evaluate's rollout kernel (profiles/policy_mc.md) (64)
  *   tail_dense      0 / 1    rat_policy_tail_trajectory / _disturbance / _params run the worst-case calls' dense moment kernels on the tail
- *                            weights instead of the liveness schedule: what that schedule is measured against (profiles/policy_tail_scenarios.md) (0)
+ *                            weights instead of the liveness schedule: what that schedule is measured against (profiles/policy_tail_scenarios.md) (0);
+ *                            rat_policy_tail_events / _user likewise run rat_policy_events' dense sums (profiles/policy_tail_events.md)
  *   wdiag           0 / 1    diagonal time-invariant W: inv(W) folded into M^-1's operand (takes effect at the next rat_problem_set) (1) */
 rat_rc  rat_debug_set(rat_handle h, const char *key, int64_t value);
 rat_rc  rat_debug_get(rat_handle h, const char *key, int64_t *value);      /* the EFFECTIVE value on this handle */

@@ -655,6 +655,48 @@ function policy_events_user(s::ILEQGSolver, n_event::Integer; kl_bounds=Float64[
                 want_steps ? steps : C_NULL, want_margins ? margins : C_NULL))
     (rows=rows, events=ev, steps=steps, margins=margins)
 end
+
+"""
+policy_tail_events(s, Q, a, b, t_lo, t_hi; alphas, want_steps, want_margins): safety events under the CVaR adversary
+(rat_policy_tail_events).  policy_events' events with one row per level α ∈ [0, 1) (1 to 16 levels; α = 0 is the nominal distribution):
+among the worst (1 − α) share of the rollouts -- the tail distribution of policy_tail_risk -- how often each event is violated, where in
+the horizon and by how much.  Returns (rows, events, steps, margins): rows (8, R) as policy_tail_risk's, the rest as policy_events';
+slot RAT_EV_PROB_ROBUST is min(1, (N_VIOL / N_OK) / (TAIL_N / N_OK)) and slot RAT_EV_FLAG the level's flag.
+"""
+function policy_tail_events(s::ILEQGSolver, Q::Union{Nothing,Array{Float64,3}}, a::Matrix{Float64}, b::Vector{Float64}, t_lo::Vector{Int32},
+                            t_hi::Vector{Int32}; alphas=Float64[], want_steps::Bool=false, want_margins::Bool=false)
+    h = s.h
+    n, m, N = dims(h.problem)
+    al = collect(Float64, alphas); R = length(al); E = length(b)
+    K = Int64(debug_get(h, "mc_cost_K"))
+    rows = zeros(8, R); ev = zeros(8, E + 1, R)
+    steps = want_steps ? zeros(N + 1, E + 1, R) : nothing
+    margins = want_margins ? zeros(max(K, 1), max(E, 1)) : nothing
+    check(ccall((:rat_policy_tail_events, LIB), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int32,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, E, Q === nothing ? C_NULL : Q, a, b, t_lo, t_hi, R > 0 ? al : C_NULL, R, rows, ev,
+                want_steps ? steps : C_NULL, want_margins ? margins : C_NULL))
+    (rows=rows, events=ev, steps=steps, margins=margins)
+end
+
+"""
+policy_tail_events_user(s, n_event; alphas, want_steps, want_margins): policy_tail_events for the events the source problem's own
+rat_user_event writes (rat_policy_tail_events_user); n_event as policy_events_user takes it.  Returns policy_tail_events' named tuple.
+"""
+function policy_tail_events_user(s::ILEQGSolver, n_event::Integer; alphas=Float64[], want_steps::Bool=false, want_margins::Bool=false)
+    h = s.h
+    n, m, N = dims(h.problem)
+    al = collect(Float64, alphas); R = length(al); E = clamp(Int(n_event), 1, 16)
+    K = Int64(debug_get(h, "mc_cost_K"))
+    rows = zeros(8, R); ev = zeros(8, E + 1, R)
+    steps = want_steps ? zeros(N + 1, E + 1, R) : nothing
+    margins = want_margins ? zeros(max(K, 1), E) : nothing
+    check(ccall((:rat_policy_tail_events_user, LIB), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, n_event, R > 0 ? al : C_NULL, R, rows, ev, want_steps ? steps : C_NULL, want_margins ? margins : C_NULL))
+    (rows=rows, events=ev, steps=steps, margins=margins)
+end
 "user_event_check(source, n, m; n_event): compile the kernel of policy_events_user only (rat_user_event_check)"
 user_event_check(source::AbstractString, n::Integer, m::Integer; n_event::Integer=1) =
     check(ccall((:rat_user_event_check, LIB), Int32, (Cstring, Int32, Int32, Int32), source, n, m, n_event))
@@ -1658,7 +1700,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, rare_event_probability_params, rare_event_params_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, policy_tail_events, policy_tail_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, rare_event_probability_params, rare_event_params_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

@@ -104,6 +104,7 @@ EXPORTS = [
     "rat_user_policy_check",
     "rat_policy_params_sampling", "rat_user_params_check", "rat_policy_params_sample",
     "rat_policy_rare_event_params", "rat_rare_event_params_check",
+    "rat_policy_tail_events", "rat_policy_tail_events_user",
 ]
 MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 WC_SLOTS = ("theta", "kl", "bound", "bound_se", "tilt_mean", "tilt_var", "ess", "flag")      # RAT_WC_* slots of the header, in order
@@ -170,6 +171,8 @@ def lib():
         _lib.rat_rare_event_noise_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
         _lib.rat_policy_events_user.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp]
         _lib.rat_user_event_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32]
+        _lib.rat_policy_tail_events.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _ip, _dp, C.c_int32, _dp, _dp, _dp, _dp]
+        _lib.rat_policy_tail_events_user.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp]
         _lib.rat_policy_rare_event_user.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32,
                                                     _dp, C.c_int32, C.c_double, _dp, _dp, _dp, _dp, _dp]
         _lib.rat_rare_event_user_check.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]

@@ -2985,15 +2985,17 @@ extern "C" rat_rc rat_kl_event_bound(double p, double d, double *out) {
 // place of the moment kernels, one enqueue chain, one host wait, the 64 MiB limit on the partial sums, the output layouts, and PROB_ROBUST
 // formed here, on the host, from the counts.  They differ in the evaluation: `eval` enqueues, for the chunk that EvArgs describes, the
 // kernel that writes margin, tau and mask, and ev_sums behind it.  `in` (EV_O_EV doubles: the events in the tile, or null) goes to the
-// head of d_ev_out first.
+// head of d_ev_out first.  `rs` is the replay's row source: KL radii and thetas, or (rat_policy_tail_events / _user) CVaR levels -- then the
+// chunk carries its liveness words to ev_sums' tail sibling and PROB_ROBUST comes from tle_final, not from here.
 static const size_t EV_O_A = (size_t)EV_MAX * 256, EV_O_B = EV_O_A + EV_MAX * 16, EV_O_WIN = EV_O_B + EV_MAX, EV_O_EV = EV_O_WIN + EV_MAX;
 
 static rat_rc events_run(rat_handle h, const std::string &F, int n_event, const std::vector<double> *in, bool quad,
-                         const std::function<rat_rc(const EvArgs &, int64_t)> &eval, const double *kl_bound, int32_t n_bound, const double *theta,
-                         int32_t n_theta, double *rows_out, double *event_out, double *step_out, double *margin_out) {
+                         const std::function<rat_rc(const EvArgs &, int64_t)> &eval, const ReplaySpec &rs, double *rows_out, double *event_out,
+                         double *step_out, double *margin_out) {
     rat_rc rc;
     const rat_handle_s::McReplay rec = h->mc_rec;
-    const int N = h->N, nrows = n_bound + n_theta, ne1 = n_event + 1;
+    const bool tail = rs.tail();
+    const int N = h->N, nrows = rs.nrows(), ne1 = n_event + 1;
     const int nsteps = step_out ? N + 1 : 0, ny = nsteps + ne1, nbatch = (nrows + EV_ROWS - 1) / EV_ROWS;
     const size_t per_batch = (size_t)ny * EV_SLOTS * EV_PART, n_part = per_batch * nbatch;
     if (n_part * 8 > (size_t)EV_MAX_PART_BYTES)
@@ -3021,10 +3023,11 @@ static rat_rc events_run(rat_handle h, const std::string &F, int n_event, const 
     ea.event_out = h->d_ev_out + o_ev; ea.step_out = h->d_ev_out + o_step;
     WtArgs ta;
     memset(&ta, 0, sizeof(ta));
-    if ((rc = replay_chunks(h, replay_kl(kl_bound, n_bound, theta, n_theta), reinterpret_cast<int *>(h->d_ev_out + o_cnt), ta,
+    if ((rc = replay_chunks(h, rs, reinterpret_cast<int *>(h->d_ev_out + o_cnt), ta,
                             [&](const WtArgs &c, ReplayChunk ch) -> rat_rc {
                                 ea.xs = c.xs; ea.us = c.us; ea.ldx = c.ldx; ea.ldu = c.ldu; ea.n = c.n; ea.m = c.m; ea.N = c.N; ea.kc = c.kc; ea.cost = c.cost;
                                 ea.ldy = c.ldy; ea.nrows = c.nrows; ea.y = c.y; ea.wc = c.wc; ea.first = ch.k0 == 0;
+                                ea.live = ch.live; ea.tr = tail ? replay_rows(h, true).d_rows : nullptr;
                                 rat_rc rce;
                                 if ((rce = eval(ea, ch.k0))) return rce;
                                 if (margin_out)                       // the chunk's margins, event by event, to their place among the K
@@ -3038,14 +3041,15 @@ static rat_rc events_run(rat_handle h, const std::string &F, int n_event, const 
     double rows[WC_MAX_ROWS * WC_NSTAT];
     int bad = 0;
     std::vector<double> ev((size_t)nrows * ne1 * EV_NSTAT);
-    HIPCHK(hipMemcpyAsync(rows, h->d_wc_red + WC_O_ROWS, (size_t)nrows * WC_NSTAT * 8, hipMemcpyDeviceToHost, h->stream));
+    const ReplayRows rr = replay_rows(h, tail);
+    HIPCHK(hipMemcpyAsync(rows, rr.d_rows, (size_t)nrows * rr.nstat * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(&bad, h->d_ev_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(ev.data(), h->d_ev_out + o_ev, ev.size() * 8, hipMemcpyDeviceToHost, h->stream));
     if (step_out) HIPCHK(hipMemcpyAsync(step_out, h->d_ev_out + o_step, (size_t)nrows * ne1 * nsteps * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if ((rc = replay_mismatch(F, bad, K))) return rc;
-    for (int r = 0; r < nrows; ++r) {
-        double d_row = (r < n_bound) ? kl_bound[r] : rows[r * WC_NSTAT + RAT_WC_KL];
+    for (int r = 0; r < nrows && !tail; ++r) {                        // (a tail row's PROB_ROBUST is tle_final's)
+        double d_row = (r < rs.n_bound) ? rs.kl_bound[r] : rows[r * WC_NSTAT + RAT_WC_KL];
         if (d_row < 0.0) d_row = 0.0;                                 // (a theta row's KL that rounding left below zero)
         for (int e = 0; e < ne1; ++e) {
             double *o = &ev[((size_t)r * ne1 + e) * EV_NSTAT];
@@ -3055,18 +3059,14 @@ static rat_rc events_run(rat_handle h, const std::string &F, int n_event, const 
         }
     }
     for (size_t i = 0; i < ev.size(); ++i) event_out[i] = ev[i];
-    for (int i = 0; i < nrows * WC_NSTAT; ++i) rows_out[i] = rows[i];
+    for (int i = 0; i < nrows * rr.nstat; ++i) rows_out[i] = rows[i];
     return RAT_OK;
 }
 
-// Quadratic events: ev_eval
-extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double *Q, const double *a, const double *b,
-                                    const int32_t *t_lo, const int32_t *t_hi,
-                                    const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
-                                    double *rows_out, double *event_out, double *step_out, double *margin_out) {
-    const std::string F = "rat_policy_events: ";
-    rat_rc rc;
-    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && event_out))) return rc;
+// Quadratic events: ev_eval.  Behind the call's own validation of its rows and of the handle (rs: the rows, KL or tail)
+static rat_rc events_quad(rat_handle h, const std::string &F, int32_t n_event, const double *Q, const double *a, const double *b,
+                          const int32_t *t_lo, const int32_t *t_hi, const ReplaySpec &rs,
+                          double *rows_out, double *event_out, double *step_out, double *margin_out) {
     if (n_event < 1 || n_event > EV_MAX) return fail(RAT_ERR_ARG, F + "n_event must be in 1 .. 16");
     if (!a || !b || !t_lo || !t_hi) return fail(RAT_ERR_ARG, F + "null a / b / t_lo / t_hi");
     const int n = h->n, m = h->m, N = h->N, d = n + m;
@@ -3091,7 +3091,29 @@ extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double 
         memcpy(&in[EV_O_WIN + e], w, sizeof(w));
     }
     return events_run(h, F, n_event, &in, Q != nullptr, [h](const EvArgs &ea, int64_t) -> rat_rc { launch_ev_chunk(ea, h->stream); return RAT_OK; },
-                      kl_bound, n_bound, theta, n_theta, rows_out, event_out, step_out, margin_out);
+                      rs, rows_out, event_out, step_out, margin_out);
+}
+
+extern "C" rat_rc rat_policy_events(rat_handle h, int32_t n_event, const double *Q, const double *a, const double *b,
+                                    const int32_t *t_lo, const int32_t *t_hi,
+                                    const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                    double *rows_out, double *event_out, double *step_out, double *margin_out) {
+    const std::string F = "rat_policy_events: ";
+    rat_rc rc;
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && event_out))) return rc;
+    return events_quad(h, F, n_event, Q, a, b, t_lo, t_hi, replay_kl(kl_bound, n_bound, theta, n_theta), rows_out, event_out, step_out, margin_out);
+}
+
+// The same events under the CVaR adversary: one row per level of rat_policy_tail_risk, the replay's second row source (replay_tail), the
+// sums by tle_sums on the liveness words and PROB_ROBUST by tle_final (policy_mc.h)
+extern "C" rat_rc rat_policy_tail_events(rat_handle h, int32_t n_event, const double *Q, const double *a, const double *b,
+                                         const int32_t *t_lo, const int32_t *t_hi, const double *alpha, int32_t n_alpha,
+                                         double *rows_out, double *event_out, double *step_out, double *margin_out) {
+    const std::string F = "rat_policy_tail_events: ";
+    rat_rc rc;
+    if ((rc = replay_validate_alpha(F, alpha, n_alpha, rows_out && event_out))) return rc;
+    if ((rc = replay_validate_handle(h, F, "rat_policy_tail_risk"))) return rc;
+    return events_quad(h, F, n_event, Q, a, b, t_lo, t_hi, replay_tail(alpha, n_alpha), rows_out, event_out, step_out, margin_out);
 }
 
 extern "C" rat_rc rat_user_event_check(const char *source, int32_t n, int32_t m, int32_t n_event) {
@@ -3101,17 +3123,20 @@ extern "C" rat_rc rat_user_event_check(const char *source, int32_t n, int32_t m,
 // The user's events: rat_src_user_events (source_events.h, a hiprtc module of its own that the first call with this n_event compiles), then
 // ev_sums.  What is refused comes in rat_policy_events' order; a source that lacks RAT_USER_EVENT or does not compile leaves the handle as
 // it was.
-extern "C" rat_rc rat_policy_events_user(rat_handle h, int32_t n_event, const double *kl_bound, int32_t n_bound, const double *theta,
-                                         int32_t n_theta, double *rows_out, double *event_out, double *step_out, double *margin_out) {
-    const std::string F = "rat_policy_events_user: ";
-    rat_rc rc;
+static rat_rc events_user_not_source(rat_handle h, const std::string &F) {
     if (h && h->have_problem && (h->wide || h->pb.model != RAT_MODEL_SOURCE))
         return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_event; the families have rat_policy_events)");
-    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && event_out))) return rc;
+    return RAT_OK;
+}
+
+// fn: the call's name.  Behind the call's own validation, as events_quad
+static rat_rc events_user(rat_handle h, const std::string &F, const char *fn, int32_t n_event, const ReplaySpec &rs,
+                          double *rows_out, double *event_out, double *step_out, double *margin_out) {
+    rat_rc rc;
     if (n_event < 1 || n_event > EV_MAX) return fail(RAT_ERR_ARG, F + "n_event must be in 1 .. 16");
     HIPCHK(hipSetDevice(h->device));
     hipFunction_t kernel = nullptr;
-    if ((rc = src_kernel(h, SRC_EVENTS, SrcShape{0, 0, n_event}, "rat_policy_events_user", &kernel))) return rc;
+    if ((rc = src_kernel(h, SRC_EVENTS, SrcShape{0, 0, n_event}, fn, &kernel))) return rc;
     const uint64_t seed = h->mc_rec.seed;                             // the replayed evaluation's: rat_src_user_events forms q from it again
     return events_run(h, F, n_event, nullptr, false,
                       [h, kernel, seed](const EvArgs &ea, int64_t k0) -> rat_rc {
@@ -3124,7 +3149,26 @@ extern "C" rat_rc rat_policy_events_user(rat_handle h, int32_t n_event, const do
                           launch_ev_sums(ea, h->stream);
                           return RAT_OK;
                       },
-                      kl_bound, n_bound, theta, n_theta, rows_out, event_out, step_out, margin_out);
+                      rs, rows_out, event_out, step_out, margin_out);
+}
+
+extern "C" rat_rc rat_policy_events_user(rat_handle h, int32_t n_event, const double *kl_bound, int32_t n_bound, const double *theta,
+                                         int32_t n_theta, double *rows_out, double *event_out, double *step_out, double *margin_out) {
+    const std::string F = "rat_policy_events_user: ";
+    rat_rc rc;
+    if ((rc = events_user_not_source(h, F))) return rc;
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && event_out))) return rc;
+    return events_user(h, F, "rat_policy_events_user", n_event, replay_kl(kl_bound, n_bound, theta, n_theta), rows_out, event_out, step_out, margin_out);
+}
+
+extern "C" rat_rc rat_policy_tail_events_user(rat_handle h, int32_t n_event, const double *alpha, int32_t n_alpha,
+                                              double *rows_out, double *event_out, double *step_out, double *margin_out) {
+    const std::string F = "rat_policy_tail_events_user: ";
+    rat_rc rc;
+    if ((rc = events_user_not_source(h, F))) return rc;
+    if ((rc = replay_validate_alpha(F, alpha, n_alpha, rows_out && event_out))) return rc;
+    if ((rc = replay_validate_handle(h, F, "rat_policy_tail_risk"))) return rc;
+    return events_user(h, F, "rat_policy_tail_events_user", n_event, replay_tail(alpha, n_alpha), rows_out, event_out, step_out, margin_out);
 }
 
 // ---- rare events by adaptive importance sampling: rat_policy_rare_event and rat_policy_rare_event_noise -----------------------------------

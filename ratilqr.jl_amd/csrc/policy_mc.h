@@ -272,6 +272,9 @@ struct EvArgs {
     const double *wc;         // launch_policy_wc's scratch: the rows' states at WC_O_INFO
     double *event_out;        // [nrows][n_event + 1][EV_NSTAT]; slot 6 holds N_OK (the host forms PROB_ROBUST from it)
     double *step_out;         // [nrows][n_event + 1][N+1] (with mask)
+    // rat_policy_tail_events only (null otherwise)
+    const unsigned *live;     // the chunk's liveness words (launch_tlt_weights): launch_ev_sums enqueues tle_sums in place of ev_sums
+    const double *tr;         // launch_policy_tr's rows [nrows][TR_NSTAT]: launch_ev_final enqueues tle_final in place of ev_final
 };
 // one chunk, behind launch_wct_weights: the events of the staged trajectories, then the chunk's sums into the partials
 void launch_ev_chunk(const EvArgs &a, hipStream_t s);
@@ -279,3 +282,17 @@ void launch_ev_chunk(const EvArgs &a, hipStream_t s);
 // (rat_policy_events_user: rat_src_user_events of source_events.h); xs, us, Qt, at, b, win are not read
 void launch_ev_sums(const EvArgs &a, hipStream_t s);
 void launch_ev_final(const EvArgs &a, hipStream_t s);
+
+// ---- rat_policy_tail_events / _user: the same event sums under the CVaR adversary, one row per level (policy_mc.hip) ----------------------------
+// The rows, the weights y (1 above the level's quantile, y_eq on it, 0 below and for a DomainError rollout; ev_final's ratios divide the
+// common factor 1 / tail out) and the liveness words are the tail calls' above: launch_policy_tr, launch_tlt_levels, launch_tlt_weights.
+// With EvArgs::live set launch_ev_sums enqueues tle_sums: ev_sums' lanes, rollouts, trees and partials (EV_PART, EV_SLOTS) with the
+// group's word read first.  A step's workgroup loads nothing for a group without weight in any of its rows, or for a rollout whose
+// indicator bits are all clear at that step; an event's workgroup reads cost, margin and tau of every rollout (N_VIOL, N_OK and the
+// largest margin are unweighted) and the weights of the rows the group is live in; a rollout without weight in a row is selected out of
+// that row's y M.  Adding 0 to a sum changes no bit, so the partials are ev_sums' on the same weights bit for bit, but for a rollout
+// without weight whose margin is NaN (every g of its window NaN), which ev_sums carries into MARGIN_MEAN as 0 NaN.  With live null (the
+// switch tail_dense) ev_sums itself runs on the tail weights.  With EvArgs::tr set launch_ev_final enqueues tle_final: ev_final with
+// FLAG the level's RAT_TR_FLAG and PROB_ROBUST = min(1, (N_VIOL / N_OK) / (TAIL_N / N_OK)) formed in place (never below PROB: where every
+// violator lies in the tail the two are the same number, sum y A / sum y and the quotient of the counts, and their roundings may differ
+// in the last bit; PROB is returned then).

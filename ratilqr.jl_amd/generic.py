@@ -226,6 +226,12 @@ class GenericContext(il.Context):
     def policy_rare_event_params(self, *a, **k):
         self._carrier_only("policy_rare_event_params")
 
+    def policy_tail_events(self, *a, **k):
+        self._carrier_only("policy_tail_events")
+
+    def policy_tail_events_user(self, *a, **k):
+        self._carrier_only("policy_tail_events_user")
+
     def set_param_sampling(self, *a, **k):
         self._carrier_only("set_param_sampling")
 

@@ -526,6 +526,31 @@ class Context:
         r.update(self._unpack_params(mean, cov, qJ))
         return r
 
+    def _events_dense(self, events):
+        """The events of policy_events / policy_tail_events as the C call takes them: n_event, Q (column-major, or None: all linear), a, b,
+        t_lo, t_hi."""
+        n, m, N = self.n, self.m, self.N
+        dense = [e.dense(n, m, N) for e in events]
+        E = len(dense)
+        quad = any(q[0] is not None for q in dense)
+        Q = nv.f64(np.stack([(np.zeros((n + m, n + m)) if q[0] is None else q[0]).T for q in dense])) if quad and E else None   # column-major
+        a = nv.f64(np.stack([q[1] for q in dense])) if E else None
+        b = nv.f64(np.array([q[2] for q in dense])) if E else None
+        lo = np.ascontiguousarray([q[3] for q in dense], dtype=np.int32) if E else None
+        hi = np.ascontiguousarray([q[4] for q in dense], dtype=np.int32) if E else None
+        return E, Q, a, b, lo, hi
+
+    @staticmethod
+    def _events_part(row_slots, rows, ev, step, sl):
+        """The rows sl of an events call as a dict: the row keys (row_slots), the RAT_EV_* arrays, event_flag and, with step, step."""
+        r = {k: rows[sl, i].copy() for i, k in enumerate(row_slots)}
+        r["flag"] = r["flag"].astype(np.int64)
+        r.update({k: ev[sl, :, i].copy() for i, k in enumerate(nv.EV_SLOTS) if k != "flag"})
+        r["event_flag"] = ev[sl, :, nv.EV_SLOTS.index("flag")].astype(np.int64)
+        if step is not None:
+            r["step"] = step[sl].copy()
+        return r
+
     def policy_events(self, events, kl_bounds=(), thetas=(), want_steps=False, want_margins=False):
         """How often the policy violates safety events (rat_policy_events): per event (halfspace, ball, quadratic_event; 1 to 16) and per
         row -- the worst-case distribution of each KL radius, the tilt of each theta; theta = 0 is the nominal distribution -- the
@@ -535,17 +560,10 @@ class Context:
         prob, prob_se, margin_mean, margin_max, first_mean, n_viol, prob_robust, event_flag, and with want_steps step (R, n_event + 1, N+1):
         the probability of a violation at each step.  margins[i] (want_margins) is the margin of every rollout for event i, NaN for a
         DomainError rollout: a sample to hand to policy_tail_risk(costs=) or policy_worst_case(costs=)."""
-        events = list(events)
         d = nv.f64(np.atleast_1d(np.asarray(kl_bounds, dtype=np.float64))).ravel()
         th = nv.f64(np.atleast_1d(np.asarray(thetas, dtype=np.float64))).ravel()
-        n, m, N, R, E = self.n, self.m, self.N, d.size + th.size, len(events)
-        dense = [e.dense(n, m, N) for e in events]
-        quad = any(q[0] is not None for q in dense)
-        Q = nv.f64(np.stack([(np.zeros((n + m, n + m)) if q[0] is None else q[0]).T for q in dense])) if quad and E else None   # column-major
-        a = nv.f64(np.stack([q[1] for q in dense])) if E else None
-        b = nv.f64(np.array([q[2] for q in dense])) if E else None
-        lo = np.ascontiguousarray([q[3] for q in dense], dtype=np.int32) if E else None
-        hi = np.ascontiguousarray([q[4] for q in dense], dtype=np.int32) if E else None
+        E, Q, a, b, lo, hi = self._events_dense(events)
+        N, R = self.N, d.size + th.size
         rows, ev = np.zeros((R, nv.WC_NSTAT)), np.zeros((R, E + 1, nv.EV_NSTAT))
         step = np.zeros((R, E + 1, N + 1)) if want_steps else None
         margins = np.zeros((max(E, 1), max(int(self.debug_get("mc_cost_K")), 1))) if want_margins else None
@@ -554,13 +572,7 @@ class Context:
                                             nv.P(step), nv.P(margins)))
 
         def part(sl):
-            r = {k: rows[sl, i].copy() for i, k in enumerate(nv.WC_SLOTS)}
-            r["flag"] = r["flag"].astype(np.int64)
-            r.update({k: ev[sl, :, i].copy() for i, k in enumerate(nv.EV_SLOTS) if k != "flag"})
-            r["event_flag"] = ev[sl, :, nv.EV_SLOTS.index("flag")].astype(np.int64)
-            if step is not None:
-                r["step"] = step[sl].copy()
-            return r
+            return self._events_part(nv.WC_SLOTS, rows, ev, step, sl)
         return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)), margins=margins)
 
     def policy_events_user(self, n_event, kl_bounds=(), thetas=(), want_steps=False, want_margins=False):
@@ -580,14 +592,39 @@ class Context:
                                                  nv.P(margins)))
 
         def part(sl):
-            r = {k: rows[sl, i].copy() for i, k in enumerate(nv.WC_SLOTS)}
-            r["flag"] = r["flag"].astype(np.int64)
-            r.update({k: ev[sl, :, i].copy() for i, k in enumerate(nv.EV_SLOTS) if k != "flag"})
-            r["event_flag"] = ev[sl, :, nv.EV_SLOTS.index("flag")].astype(np.int64)
-            if step is not None:
-                r["step"] = step[sl].copy()
-            return r
+            return self._events_part(nv.WC_SLOTS, rows, ev, step, sl)
         return dict(bounds=part(slice(0, d.size)), thetas=part(slice(d.size, R)), margins=margins)
+
+    def policy_tail_events(self, events, alphas, want_steps=False, want_margins=False):
+        """Safety events under the CVaR adversary (rat_policy_tail_events): policy_events with one row per level alpha in [0, 1) (1 to 16
+        levels; alpha = 0 is the nominal distribution) -- among the worst (1 - alpha) share of the rollouts, the tail distribution of
+        policy_tail_risk, how often each event is violated, where in the horizon and by how much.  Replays the last policy_evaluate /
+        policy_evaluate_noise of this context.  Returns {"levels": part, "margins": (n_event, K) or None}; the part carries
+        policy_tail_risk's row keys (alpha, var, cvar, ..., flag) and policy_events' arrays (R, n_event + 1) -- the last column is "any" --
+        and, with want_steps, step (R, n_event + 1, N+1).  prob_robust is min(1, (n_viol / N_OK) / (tail_n / N_OK)): the largest
+        probability of the event under any p with dp/dq <= N_OK / tail_n; event_flag is the level's flag."""
+        al, rows = self._tail_rows(alphas)
+        E, Q, a, b, lo, hi = self._events_dense(events)
+        N, R = self.N, al.size
+        ev = np.zeros((R, E + 1, nv.EV_NSTAT))
+        step = np.zeros((R, E + 1, N + 1)) if want_steps else None
+        margins = np.zeros((max(E, 1), max(int(self.debug_get("mc_cost_K")), 1))) if want_margins else None
+        nv.check(nv.lib().rat_policy_tail_events(self.h, C.c_int32(E), nv.P(Q), nv.P(a), nv.P(b), nv.PI(lo), nv.PI(hi), nv.P(al) if al.size else None,
+                                                 C.c_int32(al.size), nv.P(rows), nv.P(ev), nv.P(step), nv.P(margins)))
+        return dict(levels=self._events_part(nv.TR_SLOTS, rows, ev, step, slice(0, R)), margins=margins)
+
+    def policy_tail_events_user(self, n_event, alphas, want_steps=False, want_margins=False):
+        """policy_tail_events for the events the source problem's own rat_user_event writes (rat_policy_tail_events_user): n_event as
+        policy_events_user takes it; returns policy_tail_events' dict."""
+        al, rows = self._tail_rows(alphas)
+        N, R, E = self.N, al.size, int(n_event)
+        Ea = min(max(E, 1), 16)                                       # (the arrays of a call that the library refuses)
+        ev = np.zeros((R, Ea + 1, nv.EV_NSTAT))
+        step = np.zeros((R, Ea + 1, N + 1)) if want_steps else None
+        margins = np.zeros((Ea, max(int(self.debug_get("mc_cost_K")), 1))) if want_margins else None
+        nv.check(nv.lib().rat_policy_tail_events_user(self.h, C.c_int32(E), nv.P(al) if al.size else None, C.c_int32(al.size), nv.P(rows),
+                                                      nv.P(ev), nv.P(step), nv.P(margins)))
+        return dict(levels=self._events_part(nv.TR_SLOTS, rows, ev, step, slice(0, R)), margins=margins)
 
     def policy_rare_event(self, x_nom, l, L, event, K, seed=0, shift=None, n_iter=8, rho=0.1, want_margins=False, want_logw=False):
         """The probability of a rare safety event under the policy (x_nom, l, L) -- as policy_evaluate takes it -- by adaptive importance
