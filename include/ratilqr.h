@@ -759,7 +759,78 @@ rat_rc rat_policy_rare_event_params(rat_handle h, const double *x_nom, const dou
  * RAT_ERR_UNSUPPORTED for param_normals > 12. */
 rat_rc rat_rare_event_params_check(const char *source, int32_t n, int32_t m, int32_t n_params, int32_t normals, int32_t uniforms,
                                    int32_t param_normals, int32_t param_uniforms, int32_t n_event);
-/* approximate_model(problem, u_array, x_array)                 ileqg.jl:258-322
+
+/* ---- which uncertainty drives the cost: Sobol indices of a policy ----------------------------------------------------------------
+ * How much of Var J of a source model's Monte-Carlo cost comes from which of its independent random inputs: the first-order index
+ * S_i = Var(E[J | group i]) / Var J and the total index T_i = E[Var(J | everything but group i)] / Var J of up to sixteen groups of
+ * draws, by pick-freeze sampling on the device generator.  T_i - S_i is what group i contributes through interactions alone.
+ *
+ * Groups.  The caller partitions the declared draws into d = n_groups groups, 1 <= d <= 16.  A group is four 64-bit masks over draw
+ * indices, groups[4 i .. 4 i + 3] (RAT_SB_G_*): bit j of the parameter-normal / parameter-uniform word is the j-th rng.normal() /
+ * rng.uniform() of rat_user_params, bit j of the step-normal / step-uniform word the j-th rng.normal() / rng.uniform() of rat_user_noise
+ * at EVERY step.  Groups are disjoint; a draw in no group belongs
+ * to "the rest", which is never frozen: its share shows as 1 - sum S.  A group with four empty masks is allowed (S = T = 0 exactly).
+ *
+ * Rollouts.  Base sample g = 0 .. K - 1 gets d + 2 rollouts of the policy (x_nom, l, L), each rat_policy_evaluate_noise's rollout
+ * (the same feedback law, cost order, DomainError rule, rat_user_policy, parameters drawn in front of step 0):
+ *   Y_A[g]   every draw from the generator under seed_a
+ *   Y_B[g]   every draw under seed_b
+ *   Y_i[g]   the draws of group i under seed_b, all others under seed_a          (Saltelli's AB_i)
+ * Draw i taken from a stream is bit for bit the draw i the plain generator yields under that stream's seed for (g, step, i) -- the
+ * Box-Muller pairing of normals 2q and 2q + 1 included: where the two lie in different streams each comes from its own stream's block
+ * q.  So Y_A is rat_policy_evaluate_noise's cost_out under seed_a bit for bit, Y_B that under seed_b, and no Y depends on K.
+ *
+ * Estimator.  A base sample is OK when none of its d + 2 costs is NaN.  Over the N_OK OK samples, with mu the mean of Y_A and Y_B pooled,
+ * y' = y - mu and s_g = (y'_A^2 + y'_B^2) / 2:
+ *   V   = mean(s)
+ *   S_i = mean(y'_B (y_i - y_A)) / V                (Saltelli et al. 2010, centred)
+ *   T_i = mean((y_A - y_i)^2) / (2 V)               (Jansen 1999)
+ * Standard errors by the ratio linearisation: with a_g the numerator's term (y'_B (y_i - y_A), or (y_A - y_i)^2 / 2), R the ratio and
+ * e_g = a_g - R s_g (mean zero by construction), SE = sqrt(sum e^2 / (N_OK - 1) / N_OK) / V.  VAR_SE = sd(s) / sqrt(N_OK), sd unbiased.
+ * Sums run in a fixed tree: two calls with the same arguments return the same bits, however K was cut into launches.
+ *   index_out    [n_groups][RAT_SB_NINDEX] row-major: S, S_SE, T, T_SE
+ *   summary_out  [RAT_SB_NSTAT]
+ *   y_out        [(n_groups + 2)][K] row-major (rows A, B, then the groups in order), or NULL: the costs stay on the device
+ * RAT_SB_FLAG holds the overdraw bits of the rollouts (1, 2: a step's normals / uniforms; 4, 8: the hook's) -- with one set the call
+ * returns RAT_ERR_ARG naming the limits, as rat_policy_evaluate_noise does, after writing the summary -- and RAT_SB_DEGENERATE where
+ * V == 0, V is not finite or N_OK < 2: every index and standard error is NaN then.
+ * Parameter sampling (rat_policy_params_sampling) may be on or off; off, the parameter masks must be zero.  The call leaves the
+ * handle's recorded evaluation (its costs, its replay record) as it found it.  One device.
+ * RAT_ERR_ARG: null x_nom / l / groups / index_out / summary_out; n_groups outside 1 .. 16; K < 2; (n_groups + 2) K above 2^28 (Y is 8
+ * bytes per rollout on the device); seed_a == seed_b; negative draw counts; a mask bit at or beyond its declared count (parameter masks
+ * with sampling off included); overlapping groups; a source that does not compile; an overdraw.  RAT_ERR_UNSUPPORTED: a problem that is
+ * not a source model, or a source without rat_user_noise; injected parameter streams on the handle (the call is defined on the
+ * generator, as rat_policy_rare_event_params is); a declared draw count above 64 (the width of a mask); n > 12 or m > 4. */
+#define RAT_SB_G_PARAM_NORMALS  0   /* the words of a group, groups[4 i + word] */
+#define RAT_SB_G_PARAM_UNIFORMS 1
+#define RAT_SB_G_STEP_NORMALS   2
+#define RAT_SB_G_STEP_UNIFORMS  3
+#define RAT_SB_NGROUPWORD       4
+#define RAT_SB_S        0
+#define RAT_SB_S_SE     1
+#define RAT_SB_T        2
+#define RAT_SB_T_SE     3
+#define RAT_SB_NINDEX   4
+#define RAT_SB_N_OK     0   /* base samples none of whose d + 2 rollouts hit a DomainError, as a double */
+#define RAT_SB_MEAN     1   /* mu */
+#define RAT_SB_VAR      2   /* V */
+#define RAT_SB_VAR_SE   3
+#define RAT_SB_FLAG     4   /* overdraw bits | RAT_SB_DEGENERATE, as a double */
+#define RAT_SB_N_DROPPED 5  /* K - N_OK */
+#define RAT_SB_NSTAT    8   /* slots 6, 7 reserved, written as 0 */
+#define RAT_SB_DEGENERATE 16
+rat_rc rat_policy_sobol(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
+                        int32_t normals_per_step, int32_t uniforms_per_step,
+                        const uint64_t *groups, int32_t n_groups, uint64_t seed_a, uint64_t seed_b,
+                        double *index_out, double *summary_out, double *y_out);
+/* Compile only, for gfx950 (no device needed), the kernel of rat_policy_sobol; n_params == 0: with parameter sampling off
+ * (param_normals, param_uniforms must be 0 then), else with sampling on for n_params parameters.  rat_user_noise_check's codes with
+ * RAT_ERR_UNSUPPORTED for a source without RAT_USER_NOISE and for a draw count above 64; rat_user_params_check's for the parameter
+ * counts (a source without RAT_USER_PARAMS: RAT_ERR_ARG). */
+rat_rc rat_policy_sobol_check(const char *source, int32_t n, int32_t m, int32_t n_params, int32_t normals, int32_t uniforms,
+                              int32_t param_normals, int32_t param_uniforms);
+
+/* approximate_model(problem, u_array, x_array)                ileqg.jl:258-322
  * -> q[N+1], qv[n*(N+1)], Q[n*n*(N+1)], r[m*N], R[m*m*N], P[m*n*N], A[n*n*N], B[n*m*N], W[n*n*N] */
 rat_rc rat_approximate_model(rat_handle h, const double *u, const double *x,
                              double *q, double *qv, double *Q, double *r, double *R, double *P,

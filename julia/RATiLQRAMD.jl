@@ -858,6 +858,59 @@ rare_event_params_check(source::AbstractString, n::Integer, m::Integer, n_params
     check(ccall((:rat_rare_event_params_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32), source, n, m, n_params,
                 normals_per_step, uniforms_per_step, param_normals, param_uniforms, n_event))
 
+"""
+SobolGroup(; param_normals, param_uniforms, step_normals, step_uniforms, name): one group of random inputs of policy_sobol -- the 0-based
+draw indices it holds (the i-th rng.normal() / rng.uniform() of rat_user_params; of rat_user_noise at every step), kept as the four 64-bit
+masks of the C ABI in the order of RAT_SB_G_*.
+"""
+struct SobolGroup
+    words::NTuple{4,UInt64}
+    name::Union{Nothing,String}
+end
+function sobol_mask(indices)
+    mask = UInt64(0)
+    for i in indices
+        0 <= i < 64 || throw(ArgumentError("SobolGroup: draw index $i is outside 0:63"))
+        mask |= UInt64(1) << i
+    end
+    mask
+end
+SobolGroup(; param_normals=(), param_uniforms=(), step_normals=(), step_uniforms=(), name=nothing) =
+    SobolGroup((sobol_mask(param_normals), sobol_mask(param_uniforms), sobol_mask(step_normals), sobol_mask(step_uniforms)), name)
+
+"""
+policy_sobol(s, problem, x_nom, l_array, L_array, noise, groups; K, seed_a, seed_b, want_costs): which uncertainty drives the cost
+(rat_policy_sobol) -- the first-order and total Sobol indices of the Monte-Carlo cost of the policy for up to sixteen disjoint groups of
+draws, from K base samples of d + 2 pick-freeze rollouts each on the device generator (stream A under seed_a, stream B under seed_b).
+Parameter sampling of the solver's handle may be on (the device generator) or off.  Returns a named tuple: S, S_se, T, T_se (vectors over
+the groups), names, n_ok, mean, var, var_se, flag, and with want_costs y (K x (d + 2): columns A, B, then the groups; nothing otherwise).
+"""
+function policy_sobol(s::ILEQGSolver, problem::DeviceSourceProblem, x_nom, l_array::Vector{Vector{Float64}},
+                      L_array::Union{Nothing,Vector{Matrix{Float64}}}, noise::UserNoise, groups::Vector{SobolGroup};
+                      K::Integer=65536, seed_a::Integer=1, seed_b::Integer=2, want_costs::Bool=false)
+    (noise.zn === nothing && noise.zu === nothing) || throw(ArgumentError("policy_sobol draws from the device generator only"))
+    h = bind!(s.h, problem)
+    d = length(groups)
+    words = UInt64[g.words[k] for k in 1:4, g in groups]              # column-major 4 x d: group i's words are contiguous
+    xn = x_nom isa Vector{Float64} ? x_nom : flat(x_nom)
+    l = flat(l_array)
+    L = L_array === nothing ? C_NULL : flat(L_array)
+    index = zeros(4, max(d, 1)); summary = zeros(8)
+    y = want_costs ? Matrix{Float64}(undef, K, d + 2) : nothing
+    check(ccall((:rat_policy_sobol, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Ptr{UInt64}, Int32, UInt64, UInt64, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}),
+                h.ptr, xn, l, L, K, noise.normals_per_step, noise.uniforms_per_step, words, d, UInt64(seed_a), UInt64(seed_b), index, summary,
+                want_costs ? y : C_NULL))
+    (S=index[1, 1:d], S_se=index[2, 1:d], T=index[3, 1:d], T_se=index[4, 1:d], names=[g.name for g in groups], n_ok=Int(summary[1]),
+     mean=summary[2], var=summary[3], var_se=summary[4], flag=Int(summary[5]), y=y)
+end
+"policy_sobol_check(source, n, m; n_params, normals_per_step, uniforms_per_step, param_normals, param_uniforms): compile the kernel of policy_sobol only (rat_policy_sobol_check)"
+policy_sobol_check(source::AbstractString, n::Integer, m::Integer; n_params::Integer=0, normals_per_step::Integer=0, uniforms_per_step::Integer=0,
+                   param_normals::Integer=0, param_uniforms::Integer=0) =
+    check(ccall((:rat_policy_sobol_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32, Int32, Int32, Int32), source, n, m, n_params,
+                normals_per_step, uniforms_per_step, param_normals, param_uniforms))
+
 "integrate_cost(problem, x_array, u_array) -- ileqg.jl:115-124"
 function integrate_cost(s::ILEQGSolver, problem::DeviceRiskSensitiveProblem, x_array, u_array)
     h = bind!(s.h, problem); c = Ref(0.0)
@@ -1700,7 +1753,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, policy_tail_events, policy_tail_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, rare_event_probability_params, rare_event_params_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, policy_tail_events, policy_tail_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, rare_event_probability_params, rare_event_params_check, SobolGroup, policy_sobol, policy_sobol_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

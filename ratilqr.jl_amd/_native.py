@@ -15,6 +15,7 @@ SO_PATH = os.environ.get("RATILQR_SO", os.path.join(_HERE, "csrc", "libratilqr_h
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+_up = C.POINTER(C.c_uint64)
 
 RC_NAMES = {0: "RAT_OK", 1: "RAT_ERR_ARG", 2: "RAT_ERR_UNSUPPORTED", 3: "RAT_ERR_HIP", 4: "RAT_ERR_NO_PROBLEM",
             5: "RAT_ERR_STREAM_DRY", 6: "RAT_ERR_DIVERGED"}
@@ -105,6 +106,7 @@ EXPORTS = [
     "rat_policy_params_sampling", "rat_user_params_check", "rat_policy_params_sample",
     "rat_policy_rare_event_params", "rat_rare_event_params_check",
     "rat_policy_tail_events", "rat_policy_tail_events_user",
+    "rat_policy_sobol", "rat_policy_sobol_check",
 ]
 MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 WC_SLOTS = ("theta", "kl", "bound", "bound_se", "tilt_mean", "tilt_var", "ess", "flag")      # RAT_WC_* slots of the header, in order
@@ -115,6 +117,9 @@ EV_SLOTS = ("prob", "prob_se", "margin_mean", "margin_max", "first_mean", "n_vio
 EV_NSTAT, EV_MAX = 8, 16
 RE_SLOTS = ("prob", "prob_se", "ess", "n_viol", "n_ok", "n_domain", "logw_max", "logw_min", "flag", "n_iter", "level")   # RAT_RE_* slots of the header, in order
 RE_NSTAT, RE_NTRACE, RE_OK, RE_NOT_REACHED, RE_EMPTY, RE_NONFINITE = 12, 4, 0, 1, 2, 3
+SB_S, SB_S_SE, SB_T, SB_T_SE, SB_NINDEX = 0, 1, 2, 3, 4                                      # RAT_SB_* of the header: an index row ...
+SB_N_OK, SB_MEAN, SB_VAR, SB_VAR_SE, SB_FLAG, SB_N_DROPPED, SB_NSTAT = 0, 1, 2, 3, 4, 5, 8  # ... the summary ...
+SB_NGROUPWORD, SB_MAX_GROUPS, SB_DEGENERATE = 4, 16, 16                                      # ... a group's words, the cap, the flag bit
 
 _lib = None
 
@@ -184,6 +189,9 @@ def lib():
                                                       _dp, _dp, C.c_double, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.c_int32, C.c_double,
                                                       _dp, _dp, _dp, _dp, _dp, _dp, _dp]
         _lib.rat_rare_event_params_check.argtypes = [C.c_char_p] + [C.c_int32] * 8
+        _lib.rat_policy_sobol.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_int32, _up, C.c_int32, C.c_uint64, C.c_uint64,
+                                          _dp, _dp, _dp]
+        _lib.rat_policy_sobol_check.argtypes = [C.c_char_p] + [C.c_int32] * 7
     return _lib
 
 
@@ -275,6 +283,14 @@ def rare_event_params_check(source, n, m, n_params, normals_per_step=1, uniforms
     what the source does not define, or naming the limit on the counts (param_normals in 1 .. 12)."""
     check(lib().rat_rare_event_params_check(str(source).encode(), int(n), int(m), int(n_params), int(normals_per_step), int(uniforms_per_step),
                                             int(param_normals), int(param_uniforms), int(n_event)))
+
+
+def policy_sobol_check(source, n, m, n_params=0, normals_per_step=0, uniforms_per_step=0, param_normals=0, param_uniforms=0):
+    """rat_policy_sobol_check: compile the rollout kernel of rat_policy_sobol only (gfx950, no device needed), with parameter sampling
+    off (n_params=0) or on; raises RatError with the compiler's log, saying what the source does not define, or naming the limit on
+    the counts (at most 64 each)."""
+    check(lib().rat_policy_sobol_check(str(source).encode(), int(n), int(m), int(n_params), int(normals_per_step), int(uniforms_per_step),
+                                       int(param_normals), int(param_uniforms)))
 
 
 def pets_set_source(h, prob):

@@ -264,6 +264,11 @@ struct rat_handle_s {
     int *d_re_dom = nullptr; size_t cap_re_dom = 0;          // [K] DomainError flags
     double *d_re_part = nullptr; size_t cap_re_part = 0;     // [N * 12 + 3][RE_SLOTS] partials of the elite sums
     double *d_re_red = nullptr;                              // [RE_SCRATCH]
+    // the Sobol indices (rat_policy_sobol, policy_mc.hip): buffers of its own for the same reason; grown on demand
+    double *d_sb_in = nullptr; size_t cap_sb_in = 0;         // x_nom | l | L
+    double *d_sb_y = nullptr; size_t cap_sb_y = 0;           // [n_groups + 2][K] costs of the pick-freeze rollouts
+    int *d_sb_ok = nullptr; size_t cap_sb_ok = 0;            // [K] base samples without a DomainError in any of their rollouts
+    double *d_sb_red = nullptr;                              // [SB_SCRATCH]
 };
 
 extern "C" int32_t rat_version(void) { return RAT_VERSION; }
@@ -456,6 +461,7 @@ extern "C" void rat_destroy(rat_handle h) {
     for (double *q : {h->d_wp_q, h->d_wp_part, h->d_wp_out}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_ev_out, (void *)h->d_ev_part, (void *)h->d_ev_margin, (void *)h->d_ev_tau, (void *)h->d_ev_mask}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_re_in, (void *)h->d_re_margin, (void *)h->d_re_logw, (void *)h->d_re_dom, (void *)h->d_re_part, (void *)h->d_re_red}) if (q) (void)hipFree(q);
+    for (void *q : {(void *)h->d_sb_in, (void *)h->d_sb_y, (void *)h->d_sb_ok, (void *)h->d_sb_red}) if (q) (void)hipFree(q);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
     if (h->h_pcost) (void)hipHostFree(h->h_pcost);
@@ -920,10 +926,11 @@ static rat_rc src_kernel(rat_handle h, SrcKind kind, SrcShape shape, const char 
     return RAT_OK;
 }
 
-// a source kernel's launch: one wavefront per `per_block` of `count`, *args its one argument record
-static hipError_t launch_src(hipFunction_t fn, int64_t count, int per_block, hipStream_t s, void *args) {
+// a source kernel's launch: one wavefront per `per_block` of `count` (times grid_y: rat_src_sobol_rollout's variants), *args its one
+// argument record
+static hipError_t launch_src(hipFunction_t fn, int64_t count, int per_block, hipStream_t s, void *args, unsigned grid_y = 1) {
     void *a[] = {args};
-    return hipModuleLaunchKernel(fn, (unsigned)((count + per_block - 1) / per_block), 1, 1, 64, 1, 1, 0, s, a, nullptr);
+    return hipModuleLaunchKernel(fn, (unsigned)((count + per_block - 1) / per_block), grid_y, 1, 64, 1, 1, 0, s, a, nullptr);
 }
 
 // The pinned overdraw flag of a kernel that draws (bit 0 normals, bit 1 uniforms; set with a plain store, read after a host wait):
@@ -3439,6 +3446,113 @@ extern "C" rat_rc rat_policy_rare_event_params(rat_handle h, const double *x_nom
                             shift_in, n_iter, rho, stats, shift_out, trace_out, margin_out, logw_out, &par);
     return rare_src_run(h, F, who, x_nom, l, L, K, normals_per_step, uniforms_per_step, seed, 0, 0, Q, a, b, t_lo, t_hi, shift_in, n_iter, rho,
                         stats, shift_out, trace_out, margin_out, logw_out, &par);
+}
+
+// ---- which uncertainty drives the cost: first-order and total Sobol indices (rat_policy_sobol; include/ratilqr.h) -------------------------
+// what the numbers alone decide: the draw counts against the width of a mask, the groups against the counts and against each other
+static_assert(SB_MAX_GROUPS == SOBOL_MAX_GROUPS, "policy_mc.h reduces as many groups as source_args.h rolls out");
+static_assert(SB_NSTAT == RAT_SB_NSTAT && SB_FLAG_DEGENERATE == RAT_SB_DEGENERATE, "policy_mc.h writes the header's summary");
+static rat_rc sobol_counts_ok(const std::string &F, int npn, int npu, int ppn, int ppu) {
+    if (npn > 64 || npu > 64 || ppn > 64 || ppu > 64)
+        return fail(RAT_ERR_UNSUPPORTED, F + "a declared draw count is above 64 (a group names draws by the bits of a 64-bit mask)");
+    return RAT_OK;
+}
+static rat_rc sobol_groups_ok(const std::string &F, const uint64_t *groups, int d, int npn, int npu, int ppn, int ppu, bool sampling) {
+    auto beyond = [](uint64_t mask, int count) { return count < 64 && (mask >> count) != 0; };
+    uint64_t seen[4] = {0, 0, 0, 0};
+    for (int i = 0; i < d; ++i) {
+        const uint64_t *mk = groups + (size_t)RAT_SB_NGROUPWORD * i;
+        const int cnt[4] = {ppn, ppu, npn, npu};                      // (RAT_SB_G_*: the order of a group's words)
+        if (!sampling && (mk[0] || mk[1]))
+            return fail(RAT_ERR_ARG, F + "group " + std::to_string(i) + " names parameter draws, but parameter sampling is off (rat_policy_params_sampling)");
+        for (int k = 0; k < 4; ++k) {
+            if (beyond(mk[k], cnt[k]))
+                return fail(RAT_ERR_ARG, F + "group " + std::to_string(i) + " names a draw at or beyond the declared count (" + std::to_string(cnt[k]) + ")");
+            if (mk[k] & seen[k]) return fail(RAT_ERR_ARG, F + "group " + std::to_string(i) + " overlaps an earlier group: groups must be disjoint");
+            seen[k] |= mk[k];
+        }
+    }
+    return RAT_OK;
+}
+// a compile that failed on the header's own refusal of a source without the sampler is RAT_ERR_UNSUPPORTED, like a problem that is no source
+static rat_rc sobol_compile_rc(rat_rc rc) {
+    return (rc == RAT_ERR_ARG && g_err.find("does not define RAT_USER_NOISE") != std::string::npos) ? RAT_ERR_UNSUPPORTED : rc;
+}
+
+extern "C" rat_rc rat_policy_sobol_check(const char *source, int32_t n, int32_t m, int32_t n_params, int32_t normals, int32_t uniforms,
+                                         int32_t param_normals, int32_t param_uniforms) {
+    const std::string F = "rat_policy_sobol_check: ";
+    if (!source) return fail(RAT_ERR_ARG, "null");
+    rat_rc rc;
+    if ((rc = src_args_ok("rat_policy_sobol_check", SRC_SOBOL, n, m, normals, uniforms, 0))) return rc;
+    if (n_params < 0) return fail(RAT_ERR_ARG, F + "n_params must not be negative");
+    if (n_params == 0 && (param_normals != 0 || param_uniforms != 0))
+        return fail(RAT_ERR_ARG, F + "n_params is 0 (parameter sampling off): param_normals, param_uniforms must be 0");
+    if (n_params > 0 && (rc = params_args_ok(F, n_params, param_normals, param_uniforms))) return rc;
+    if ((rc = sobol_counts_ok(F, normals, uniforms, param_normals, param_uniforms))) return rc;
+    return sobol_compile_rc(src_check("rat_policy_sobol_check", SRC_SOBOL, source, n, m, normals, uniforms, 0, n_params, param_normals, param_uniforms));
+}
+
+// The d + 2 pick-freeze rollouts of every base sample in one launch of rat_src_sobol_rollout (source_sobol.h: the variant is blockIdx.y; the
+// generator counts base samples globally and nothing is staged, so the launch is not cut), then the reduction of launch_policy_sobol.  The
+// policy goes through pack_policy like every analysis, into buffers of the call's own: the recorded evaluation stays as it was.
+extern "C" rat_rc rat_policy_sobol(rat_handle h, const double *x_nom, const double *l, const double *L, int64_t K,
+                                   int32_t normals_per_step, int32_t uniforms_per_step,
+                                   const uint64_t *groups, int32_t n_groups, uint64_t seed_a, uint64_t seed_b,
+                                   double *index_out, double *summary_out, double *y_out) {
+    const std::string F = "rat_policy_sobol: ";
+    if (!h || !x_nom || !l || !groups || !index_out || !summary_out) return fail(RAT_ERR_ARG, F + "null handle / x_nom / l / groups / index_out / summary_out");
+    if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
+    if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
+        return fail(RAT_ERR_UNSUPPORTED, F + "the handle's problem is not a source model (only a source can define rat_user_noise)");
+    const int d = n_groups, nvar = n_groups + 2, npn = normals_per_step, npu = uniforms_per_step;
+    if (d < 1 || d > SOBOL_MAX_GROUPS) return fail(RAT_ERR_ARG, F + "n_groups must be in 1 .. 16");
+    if (K < 2) return fail(RAT_ERR_ARG, F + "K must be at least 2");
+    if ((int64_t)nvar * K > ((int64_t)1 << 28))
+        return fail(RAT_ERR_ARG, F + "(n_groups + 2) K must be at most 2^28 (the costs stay on the device, 8 bytes per rollout)");
+    if (seed_a == seed_b) return fail(RAT_ERR_ARG, F + "seed_a and seed_b must differ (the two streams must be independent)");
+    rat_rc rc;
+    if ((rc = src_args_ok("rat_policy_sobol", SRC_SOBOL, h->n, h->m, npn, npu, 0))) return rc;
+    if (h->ps_on && (h->ps_K > 0 || h->d_ps_zn || h->d_ps_zu))
+        return fail(RAT_ERR_UNSUPPORTED, F + "the handle holds injected parameter draws: the two streams are defined on the generator");
+    const int ppn = h->ps_on ? h->ps_pn : 0, ppu = h->ps_on ? h->ps_pu : 0;
+    if ((rc = sobol_counts_ok(F, npn, npu, ppn, ppu))) return rc;
+    if ((rc = sobol_groups_ok(F, groups, d, npn, npu, ppn, ppu, h->ps_on))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    hipFunction_t kernel = nullptr;
+    int *d_over = nullptr;
+    if ((rc = src_kernel(h, SRC_SOBOL, SrcShape{npn, npu, 0}, "rat_policy_sobol", &kernel))) return sobol_compile_rc(rc);
+    if ((rc = overdraw_flag(&h->h_un_over, F, &d_over))) return rc;
+    PolicyPack pk;                                                // (W is not read: the pack starts at x_nom)
+    if ((rc = pack_policy(h, x_nom, l, L, false, &pk))) return rc;
+    size_t cap_red = h->d_sb_red ? SB_SCRATCH : 0;
+    if ((rc = grow(&h->d_sb_in, &h->cap_sb_in, pk.data.size()))) return rc;
+    if ((rc = grow(&h->d_sb_y, &h->cap_sb_y, (size_t)nvar * K))) return rc;
+    if ((rc = grow(&h->d_sb_ok, &h->cap_sb_ok, (size_t)K))) return rc;
+    if ((rc = grow(&h->d_sb_red, &cap_red, (size_t)SB_SCRATCH))) return rc;
+    HIPCHK(hipMemcpy(h->d_sb_in, pk.data.data(), pk.data.size() * 8, hipMemcpyHostToDevice));
+    const PolicyDev dev = policy_dev(h->d_sb_in, pk.o_x, pk.o_l, pk.o_L, L != nullptr);
+    SrcSobolArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xnom = dev.x; a.l = dev.l; a.L = dev.L; a.K = (long)K; a.j0 = 0; a.N = h->N; a.tpw = h->src_mc_tpw;
+    a.seed_a = seed_a; a.seed_b = seed_b; a.y = h->d_sb_y; a.ldy = (long)K; a.p = h->d_src_p; a.overdraw = d_over;
+    for (int k = 0; k < 4; ++k) a.pick[1][k] = ~0ull;             // (row 0, A: no bit; row 1, B: every bit)
+    for (int i = 0; i < d; ++i)
+        for (int k = 0; k < 4; ++k) a.pick[2 + i][k] = groups[(size_t)RAT_SB_NGROUPWORD * i + k];
+    HIPCHK(launch_src(kernel, K, a.tpw, h->stream, &a, (unsigned)nvar));
+    SbArgs sa;
+    sa.y = h->d_sb_y; sa.ldy = (long)K; sa.K = (long)K; sa.d = d; sa.ok = h->d_sb_ok; sa.scratch = h->d_sb_red;
+    launch_policy_sobol(sa, h->stream);
+    HIPCHK(hipGetLastError());
+    double out[SB_NSTAT + SB_MAX_GROUPS * 4];
+    HIPCHK(hipMemcpyAsync(out, h->d_sb_red + SB_O_OUT, sizeof(out), hipMemcpyDeviceToHost, h->stream));
+    if (y_out) HIPCHK(hipMemcpyAsync(y_out, h->d_sb_y, (size_t)nvar * K * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int over = *(volatile int *)h->h_un_over;               // after the wait: a step, or rat_user_params, that drew more than was declared
+    for (int i = 0; i < RAT_SB_NSTAT; ++i) summary_out[i] = out[i];
+    summary_out[RAT_SB_FLAG] = (double)((int)out[RAT_SB_FLAG] | over);
+    for (int i = 0; i < d * RAT_SB_NINDEX; ++i) index_out[i] = out[SB_NSTAT + i];
+    return over == 0 ? RAT_OK : overdraw_fail(h, F, over, npn, npu);
 }
 
 static rat_rc linearize_slot0(rat_handle h, const double *u, const double *x, std::vector<double> *tiles, int32_t *domain_fail) {

@@ -296,3 +296,29 @@ void launch_ev_final(const EvArgs &a, hipStream_t s);
 // FLAG the level's RAT_TR_FLAG and PROB_ROBUST = min(1, (N_VIOL / N_OK) / (TAIL_N / N_OK)) formed in place (never below PROB: where every
 // violator lies in the tail the two are the same number, sum y A / sum y and the quotient of the counts, and their roundings may differ
 // in the last bit; PROB is returned then).
+
+// ---- rat_policy_sobol: first-order and total Sobol indices of the cost from pick-freeze rollouts (policy_mc.hip) ------------------------------
+// Y [d + 2][ldy]: rows A, B and the d groups' AB_i, written by rat_src_sobol_rollout (source_sobol.h).  A base sample is OK when none of
+// its d + 2 costs is NaN.  The partials are [2 + 8 d][MC_BLOCKS] doubles, 0.27 MB at d = 16: far below the 64 MiB the other analyses cap
+// theirs at, so the call has no cap of that kind; what grows with K is Y itself, which the host bounds (driver.cpp).
+#define SB_MAX_GROUPS 16
+#define SB_NSUM 8             /* sums per group of sb_pass2: s, s^2, ns, ns^2, ns s, nt, nt^2, nt s */
+#define SB_NSTAT 8            /* RAT_SB_NSTAT of the header */
+#define SB_FLAG_DEGENERATE 16 /* RAT_SB_DEGENERATE of the header */
+// scratch, in doubles: part1 [2][B] | part2 [16][8][B] | summary [8] | rows [16][4]
+#define SB_O_P1 0
+#define SB_O_P2 (2 * MC_BLOCKS)
+#define SB_O_OUT (SB_O_P2 + SB_MAX_GROUPS * SB_NSUM * MC_BLOCKS)
+#define SB_O_ROWS (SB_O_OUT + SB_NSTAT)
+#define SB_SCRATCH (SB_O_ROWS + SB_MAX_GROUPS * 4)
+
+struct SbArgs {
+    const double *y;          // [d + 2][ldy] costs, NaN for a DomainError rollout
+    long ldy;
+    long K;                   // base samples
+    int d;                    // groups, 1 .. SB_MAX_GROUPS
+    int *ok;                  // [K] sb_pass1 writes 1 where the base sample is OK
+    double *scratch;          // [SB_SCRATCH]
+};
+// enqueues sb_pass1, sb_pass2 and sb_final on s; the summary is a.scratch + SB_O_OUT, the rows [d][4] a.scratch + SB_O_ROWS
+void launch_policy_sobol(const SbArgs &a, hipStream_t s);

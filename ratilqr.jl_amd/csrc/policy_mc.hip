@@ -1499,7 +1499,98 @@ __global__ __launch_bounds__(MC_THREADS) void tle_final(EvArgs a) {
     }
 }
 
+// ---- rat_policy_sobol: first-order and total Sobol indices from the pick-freeze costs Y [d + 2][K] ------------------------------------------
+// Rows A, B, then the d groups' AB_i (rat_src_sobol_rollout, source_sobol.h).  Three launches, every sum in mc_pass1's order (lane g of the
+// MC_BLOCKS x MC_THREADS grid sums base samples g, g + T, ... in order, the LDS tree, the second level at the head of the next launch):
+//   sb_pass1   ok[k] = no row of base sample k is NaN; N_OK and sum (y_A + y_B) over the OK samples                   -> part1 [2][B]
+//   sb_pass2   mu from part1; per group (blockIdx.y), with a' = y_A - mu, b' = y_B - mu, D = y_i - y_A, s = (a'^2 + b'^2) / 2,
+//              ns = b' D, nt = D D:  sum s, s^2, ns, ns^2, ns s, nt, nt^2, nt s                                      -> part2 [d][8][B]
+//   sb_final   V = sum s / N_OK; S = sum ns / sum s, T = sum nt / (2 sum s); the standard errors from the ratio linearisation:
+//              the residuals e = ns - S s (or nt / 2 - T s) have mean zero by construction, so var(e) = sum e^2 / (N_OK - 1) with
+//              sum e^2 = sum ns^2 - 2 S sum ns s + S^2 sum s^2 expanded, and SE = sqrt(var(e) / N_OK) / V.
+// Centring about the pooled mean matters: the uncentred numerator mean(y_B (y_i - y_A)) carries mu (y_i - y_A), whose mean is zero but
+// whose spread is mu^2 T -- it would dominate the standard error wherever |mu| is large against sd(J).  D is formed from the costs
+// themselves, not from the centred values: a group with empty masks has y_i == y_A bit for bit and gets S = T = 0 exactly.
+__global__ __launch_bounds__(MC_THREADS) void sb_pass1(SbArgs a) {
+    __shared__ double sh[MC_THREADS];
+    const long T = (long)MC_BLOCKS * MC_THREADS;
+    double cnt = 0.0, sum = 0.0;
+    for (long k = (long)blockIdx.x * MC_THREADS + threadIdx.x; k < a.K; k += T) {
+        bool ok = true;
+        for (int v = 0; v < a.d + 2; ++v) ok = ok && !mc_nan(a.y[(long)v * a.ldy + k]);
+        a.ok[k] = ok ? 1 : 0;                                         // (each base sample belongs to one lane)
+        if (ok) { cnt += 1.0; sum += a.y[k] + a.y[a.ldy + k]; }
+    }
+    cnt = block_tree<0>(cnt, sh);
+    sum = block_tree<0>(sum, sh);
+    if (threadIdx.x == 0) { a.scratch[SB_O_P1 + blockIdx.x] = cnt; a.scratch[SB_O_P1 + MC_BLOCKS + blockIdx.x] = sum; }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void sb_pass2(SbArgs a) {
+    __shared__ double sh[SB_NSUM * MC_THREADS];
+    const double n_ok = block_tree<0>(a.scratch[SB_O_P1 + threadIdx.x], sh);
+    const double mu = block_tree<0>(a.scratch[SB_O_P1 + MC_BLOCKS + threadIdx.x], sh) / (2.0 * n_ok);
+    const int i = blockIdx.y;
+    const double *ya = a.y, *yb = a.y + a.ldy, *yi = a.y + (long)(2 + i) * a.ldy;
+    double v[SB_NSUM];
+#pragma unroll
+    for (int q = 0; q < SB_NSUM; ++q) v[q] = 0.0;
+    const long T = (long)MC_BLOCKS * MC_THREADS;
+    for (long k = (long)blockIdx.x * MC_THREADS + threadIdx.x; k < a.K; k += T) {
+        if (!a.ok[k]) continue;
+        const double A = ya[k], ap = A - mu, bp = yb[k] - mu, D = yi[k] - A;
+        const double s = 0.5 * (ap * ap + bp * bp), ns = bp * D, nt = D * D;
+        v[0] += s; v[1] += s * s;
+        v[2] += ns; v[3] += ns * ns; v[4] += ns * s;
+        v[5] += nt; v[6] += nt * nt; v[7] += nt * s;
+    }
+    block_tree_n<SB_NSUM>(v, sh);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < SB_NSUM; ++q) a.scratch[SB_O_P2 + ((size_t)i * SB_NSUM + q) * MC_BLOCKS + blockIdx.x] = v[q];
+    }
+}
+
+__global__ __launch_bounds__(MC_THREADS) void sb_final(SbArgs a) {
+    __shared__ double sh[SB_NSUM * MC_THREADS];
+    const int tid = threadIdx.x;
+    const double nan = __builtin_nan("");
+    const double n = block_tree<0>(a.scratch[SB_O_P1 + tid], sh);
+    const double sum = block_tree<0>(a.scratch[SB_O_P1 + MC_BLOCKS + tid], sh);
+    double *out = a.scratch + SB_O_OUT, *rows = a.scratch + SB_O_ROWS;
+    bool good = false;
+    for (int i = 0; i < a.d; ++i) {
+        double v[SB_NSUM];
+#pragma unroll
+        for (int q = 0; q < SB_NSUM; ++q) v[q] = a.scratch[SB_O_P2 + ((size_t)i * SB_NSUM + q) * MC_BLOCKS + tid];
+        block_tree_n<SB_NSUM>(v, sh);
+        const double V = v[0] / n;
+        good = n >= 2.0 && V > 0.0 && V < __builtin_inf();
+        if (tid != 0) continue;
+        if (i == 0) {                                                 // (sum s and sum s^2 are the same bits in every group's partials)
+            double vs = (v[1] - v[0] * v[0] / n) / (n - 1.0);
+            if (vs < 0.0) vs = 0.0;
+            out[0] = n; out[1] = n > 0.0 ? sum / (2.0 * n) : nan; out[2] = n > 0.0 ? V : nan; out[3] = n >= 2.0 ? sqrt(vs / n) : nan;
+            out[4] = good ? 0.0 : (double)SB_FLAG_DEGENERATE; out[5] = (double)a.K - n; out[6] = 0.0; out[7] = 0.0;
+        }
+        const double S = v[2] / v[0], Tt = v[5] / (2.0 * v[0]);
+        double es = v[3] - 2.0 * S * v[4] + S * S * v[1], et = 0.25 * v[6] - Tt * v[7] + Tt * Tt * v[1];
+        if (es < 0.0) es = 0.0;
+        if (et < 0.0) et = 0.0;
+        rows[i * 4 + 0] = good ? S : nan;
+        rows[i * 4 + 1] = good ? sqrt(es / (n - 1.0) / n) / V : nan;
+        rows[i * 4 + 2] = good ? Tt : nan;
+        rows[i * 4 + 3] = good ? sqrt(et / (n - 1.0) / n) / V : nan;
+    }
+}
+
 }  // namespace
+
+void launch_policy_sobol(const SbArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(sb_pass1, dim3(MC_BLOCKS), dim3(MC_THREADS), 0, s, a);
+    hipLaunchKernelGGL(sb_pass2, dim3(MC_BLOCKS, (unsigned)a.d), dim3(MC_THREADS), 0, s, a);
+    hipLaunchKernelGGL(sb_final, dim3(1), dim3(MC_THREADS), 0, s, a);
+}
 
 void launch_wct_centre(const double *x, const double *u, int n, int m, int N, double *centre, hipStream_t s) {
     hipLaunchKernelGGL(wct_centre, dim3((unsigned)(((N + 1) * 16 + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, s, x, u, n, m, N, centre);

@@ -14,12 +14,27 @@
 // proposal, z = shift[i] + xi with xi the draw above, and the log-likelihood ratio of the draw, -s z + s^2 / 2, is added to logw at the
 // draw, in draw order -- a sequential likelihood ratio, valid when the number of draws depends on earlier draws.  Uniforms are not
 // shifted.  Without the macro RAT_RNG_NORMAL is the identity and the struct has no further member.
+//
+// RAT_RNG_PICK (the command line of source_sobol.h's module alone, rat_policy_sobol): every generator draw comes from one of two streams,
+// the one above under key (k0, k1) or the same counters under a second key (kb0, kb1).  Bit i of pick_n / pick_u says that normal /
+// uniform i of every step is the second stream's; the draw is bit for bit what the plain generator yields under that stream's seed for
+// (g, t, i), the pairing included: normal 2q is z0 and normal 2q + 1 is z1 of block q of its OWN stream.  The spare of a block serves
+// draw 2q + 1 only where draws 2q and 2q + 1 have the same key; otherwise draw 2q + 1 runs block q of its own stream and takes the second
+// output.  Keys and masks are the same for a whole wavefront and a draw's index is a constant once the user's loops are unrolled, so the
+// choice is a scalar select.  Without the macro the header preprocesses to what it was.  Not combined with RAT_RNG_SHIFT.
 #pragma once
 #include "rat_normal.h"
 #include "rat_philox.h"
 
 #if !defined(RAT_PETS_NORMALS) || !defined(RAT_PETS_UNIFORMS)
 #error "RAT_PETS_NORMALS and RAT_PETS_UNIFORMS must be defined"
+#endif
+
+#if defined(RAT_RNG_PICK) && defined(RAT_RNG_SHIFT)
+#error "RAT_RNG_PICK is not combined with RAT_RNG_SHIFT"
+#endif
+#if defined(RAT_RNG_PICK) && (RAT_PETS_NORMALS > 64 || RAT_PETS_UNIFORMS > 64)
+#error "rat_policy_sobol masks at most 64 normals and 64 uniforms per step"
 #endif
 
 #ifdef RAT_RNG_SHIFT
@@ -34,6 +49,10 @@ struct rat_rng {
     unsigned g0, g1, t, k0, k1;   // generator: counter words of this (trajectory, step), key
     int in, iu, over;
     double spare_n, spare_u;      // the second output of the last generator block
+#ifdef RAT_RNG_PICK
+    unsigned kb0, kb1;            // the second stream's key
+    unsigned long long pick_n, pick_u;   // bit i: normal / uniform i of a step is the second stream's
+#endif
 #ifdef RAT_RNG_SHIFT
     const double *shift;          // the step's shift row [RAT_PETS_NORMALS]: one address for the whole wavefront
     double logw;
@@ -49,21 +68,43 @@ struct rat_rng {
         const int i = in++;
         if (i >= RAT_PETS_NORMALS) { over |= 1; return __builtin_nan(""); }
         if (!gen) return zn[i];
+#ifdef RAT_RNG_PICK
+        const bool b = (pick_n >> i) & 1;
+        if ((i & 1) && b == (bool)((pick_n >> (i - 1)) & 1)) return spare_n;
+        unsigned r[4];
+        philox4x32_10(g0, g1, t, (unsigned)(i >> 1), b ? kb0 : k0, b ? kb1 : k1, r);
+        double z0, z1;
+        ratn_box_muller(u01(r[0], r[1]), u01(r[2], r[3]), &z0, &z1);
+        if (i & 1) return z1;                                         // (its neighbour came from the other stream)
+        spare_n = z1;
+        return z0;
+#else
         if (i & 1) return RAT_RNG_NORMAL(i, spare_n);
         unsigned r[4];
         philox4x32_10(g0, g1, t, (unsigned)(i >> 1), k0, k1, r);
         double z0;
         ratn_box_muller(u01(r[0], r[1]), u01(r[2], r[3]), &z0, &spare_n);
         return RAT_RNG_NORMAL(i, z0);
+#endif
     }
     __device__ __forceinline__ double uniform() {
         const int i = iu++;
         if (i >= RAT_PETS_UNIFORMS) { over |= 2; return __builtin_nan(""); }
         if (!gen) return zu[i];
+#ifdef RAT_RNG_PICK
+        const bool b = (pick_u >> i) & 1;
+        if ((i & 1) && b == (bool)((pick_u >> (i - 1)) & 1)) return spare_u;
+        unsigned r[4];
+        philox4x32_10(g0, g1, t, 0x80000000u | (unsigned)(i >> 1), b ? kb0 : k0, b ? kb1 : k1, r);
+        if (i & 1) return u01(r[2], r[3]);
+        spare_u = u01(r[2], r[3]);
+        return u01(r[0], r[1]);
+#else
         if (i & 1) return spare_u;
         unsigned r[4];
         philox4x32_10(g0, g1, t, 0x80000000u | (unsigned)(i >> 1), k0, k1, r);
         spare_u = u01(r[2], r[3]);
         return u01(r[0], r[1]);
+#endif
     }
 };

@@ -134,3 +134,23 @@ struct SrcParamsArgs {
     double *q_out;            // [K][RAT_N_PARAMS]
     int *overdraw;            // set (plain store) when the hook draws more than was declared: 4 normals, 8 uniforms
 };
+
+// rat_src_sobol_rollout (source_sobol.h): rat_src_user_noisy_rollout's rollout for every (base sample, variant) of rat_policy_sobol, the
+// generator only; variant blockIdx.y draws what its masks name from the stream of seed_b and everything else from the stream of seed_a
+#define SOBOL_MAX_GROUPS 16
+#define SOBOL_MAX_VAR (SOBOL_MAX_GROUPS + 2)   /* A (no bit set), B (every bit set), then the groups */
+struct SrcSobolArgs {
+    const double *xnom;       // [(N+1)][12] nominal states (open loop: only row 0 is read)
+    const double *l;          // [N][4]
+    const double *L;          // [N][4][12] or null (open loop)
+    long K;                   // base samples of this launch
+    long j0;                  // global index of this launch's first base sample (the generator's counter)
+    int N;
+    int tpw;                  // rollouts per wavefront (lanes 0 .. tpw-1 of each 64-lane workgroup work)
+    unsigned long long seed_a, seed_b;
+    double *y;                // row v of the costs at y + v ldy, [K] each; NaN where the rollout hit a DomainError
+    long ldy;
+    const double *p;          // the model's parameters
+    int *overdraw;            // set (plain store) as rat_src_user_noisy_rollout sets it: 1, 2 a step's normals / uniforms, 4, 8 the hook's
+    unsigned long long pick[SOBOL_MAX_VAR][4];   // per variant: parameter normals, parameter uniforms, step normals, step uniforms
+};

@@ -81,6 +81,7 @@ static const SrcKindRow k_kinds[SRC_NKIND] = {
     /* SRC_EVENTS     */ {"source_events.h",     "rat_src_user_events",        nullptr,             false,    false, true,  false, true},
     /* SRC_RARE_USER  */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  true,  true,  true},
     /* SRC_PARAMS     */ {"source_params.h",     "rat_src_params_sample",      nullptr,             false,    false, false, false, true},
+    /* SRC_SOBOL      */ {"source_sobol.h",      "rat_src_sobol_rollout",      nullptr,             false,    true,  false, false, true},
 };
 
 const SrcKindRow &src_kind(SrcKind kind) { return k_kinds[kind]; }
@@ -132,6 +133,7 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
     }
     if (pshift) opts.push_back("-DRAT_PARAM_SHIFT=1");
     if (kind == SRC_PARAMS) opts.push_back("-DRAT_PARAMS_SAMPLE_KERNEL=1");
+    if (kind == SRC_SOBOL) opts.push_back("-DRAT_RNG_PICK=1");
     const hiprtcResult rc = g_rtc.compile(prog, (int)opts.size(), opts.data());
     size_t ls = 0;
     std::string lg;

@@ -18,6 +18,7 @@ enum SrcKind {
     SRC_EVENTS,          // the user's rat_user_event on replayed trajectories (rat_policy_events_user)
     SRC_RARE_USER,       // SRC_RARE with entry `event` of rat_user_event for the margin (rat_policy_rare_event_user)
     SRC_PARAMS,          // the user's rat_user_params alone (rat_policy_params_sample)
+    SRC_SOBOL,           // SRC_USER_NOISE's rollout with every draw picked from one of two streams (rat_policy_sobol)
     SRC_NKIND
 };
 // One row per kind: what its translation unit is made of and what the module exports.  Every kind is the user's text behind
@@ -25,7 +26,8 @@ enum SrcKind {
 // -DRAT_M=m -DRAT_PETS_NORMALS=npn -DRAT_PETS_UNIFORMS=npu (0 where the kind takes no draws).  A kind that takes parameter draws gets
 // -DRAT_USER_PARAMS_ON=1 -DRAT_N_PARAMS=npar -DRAT_PARAM_NORMALS=ppn -DRAT_PARAM_UNIFORMS=ppu as well when the shape has npar > 0
 // (parameter sampling is on, rat_policy_params_sampling); with npar == 0 its command line is what it was without the feature.  The two
-// rng_shift kinds get -DRAT_PARAM_SHIFT=1 besides when the shape has pshift (rat_policy_rare_event_params: source_params.h).
+// rng_shift kinds get -DRAT_PARAM_SHIFT=1 besides when the shape has pshift (rat_policy_rare_event_params: source_params.h).  SRC_SOBOL
+// alone gets -DRAT_RNG_PICK=1 (rat_rng.h, source_params.h: a second key and the masks that pick a draw's stream).
 struct SrcKindRow {
     const char *header;          // embedded header with the kind's kernels
     const char *entry, *entry2;  // kernels the module exports (entry2: NULL but for SRC_MODEL's linearisation)

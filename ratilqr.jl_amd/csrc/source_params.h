@@ -21,8 +21,21 @@
 // -s z + s^2 / 2 is added to the rollout's logw at the draw, in draw order, in rat_rng.h's form; a hook that draws fewer normals than it
 // declared adds fewer terms.  The shift row [RAT_PARAM_NORMALS] is one address for the whole wavefront.  Uniforms are not shifted.
 // Without the macro RAT_PARAM_NORMAL is the identity, the struct has no further member and the functions no further argument.
+//
+// RAT_RNG_PICK (source_sobol.h's module alone, rat_policy_sobol; rat_rng.h has the rule): the generator's parameter draws come from two
+// streams, `seed` and a second seed, chosen per draw index by two masks (bit i: parameter normal / uniform i is the second stream's), each
+// draw bit for bit the plain generator's under its stream's seed, the spare of a block reused only between neighbours of one key.  The
+// functions take the second seed and the masks behind `over`.  Without the macro the header preprocesses to what it was.
 #pragma once
 #include "source_step.h"
+
+#ifdef RAT_RNG_PICK               // (with sampling off too: the rollout's draw() keeps one signature)
+#define RAT_PARAM_PICK_ARGS , unsigned long long seed_b, unsigned long long pick_pn, unsigned long long pick_pu
+#define RAT_PARAM_PICK_PASS , seed_b, pick_pn, pick_pu
+#else
+#define RAT_PARAM_PICK_ARGS
+#define RAT_PARAM_PICK_PASS
+#endif
 
 #ifdef RAT_USER_PARAMS_ON
 #include "rat_normal.h"
@@ -45,6 +58,13 @@
 #error "rat_policy_params_sample draws from N(0, 1): it is not compiled with RAT_PARAM_SHIFT"
 #endif
 
+#if defined(RAT_RNG_PICK) && (defined(RAT_PARAM_SHIFT) || defined(RAT_PARAMS_SAMPLE_KERNEL))
+#error "RAT_RNG_PICK is source_sobol.h's: not combined with RAT_PARAM_SHIFT or the kernel of rat_policy_params_sample"
+#endif
+#if defined(RAT_RNG_PICK) && (RAT_PARAM_NORMALS > 64 || RAT_PARAM_UNIFORMS > 64)
+#error "rat_policy_sobol masks at most 64 parameter normals and 64 parameter uniforms"
+#endif
+
 #ifdef RAT_PARAM_SHIFT
 #define RAT_PARAM_NORMAL(i, xi) proposal(i, xi)
 #define RAT_PARAM_SHIFT_ARGS , const double *pshift, double &logw
@@ -63,6 +83,10 @@ struct rat_param_rng {
     unsigned g0, g1, k0, k1;      // generator: the rollout's counter words, key
     int in, iu, over;
     double spare_n, spare_u;      // the second output of the last generator block
+#ifdef RAT_RNG_PICK
+    unsigned kb0, kb1;            // the second stream's key
+    unsigned long long pick_n, pick_u;   // bit i: parameter normal / uniform i is the second stream's
+#endif
 #ifdef RAT_PARAM_SHIFT
     const double *shift;          // the parameter shift row [RAT_PARAM_NORMALS]: one address for the whole wavefront
     double logw;
@@ -78,22 +102,44 @@ struct rat_param_rng {
         const int i = in++;
         if (i >= RAT_PARAM_NORMALS) { over |= 1; return __builtin_nan(""); }
         if (!gen) return RAT_PARAM_NORMAL(i, zn[i]);
+#ifdef RAT_RNG_PICK
+        const bool b = (pick_n >> i) & 1;
+        if ((i & 1) && b == (bool)((pick_n >> (i - 1)) & 1)) return spare_n;
+        unsigned r[4];
+        philox4x32_10(g0, g1, 0xFFFFFFFFu, (unsigned)(i >> 1), b ? kb0 : k0, b ? kb1 : k1, r);
+        double z0, z1;
+        ratn_box_muller(u01(r[0], r[1]), u01(r[2], r[3]), &z0, &z1);
+        if (i & 1) return z1;                                         // (its neighbour came from the other stream)
+        spare_n = z1;
+        return z0;
+#else
         if (i & 1) return RAT_PARAM_NORMAL(i, spare_n);
         unsigned r[4];
         philox4x32_10(g0, g1, 0xFFFFFFFFu, (unsigned)(i >> 1), k0, k1, r);
         double z0;
         ratn_box_muller(u01(r[0], r[1]), u01(r[2], r[3]), &z0, &spare_n);
         return RAT_PARAM_NORMAL(i, z0);
+#endif
     }
     __device__ __forceinline__ double uniform() {
         const int i = iu++;
         if (i >= RAT_PARAM_UNIFORMS) { over |= 2; return __builtin_nan(""); }
         if (!gen) return zu[i];
+#ifdef RAT_RNG_PICK
+        const bool b = (pick_u >> i) & 1;
+        if ((i & 1) && b == (bool)((pick_u >> (i - 1)) & 1)) return spare_u;
+        unsigned r[4];
+        philox4x32_10(g0, g1, 0xFFFFFFFFu, 0x80000000u | (unsigned)(i >> 1), b ? kb0 : k0, b ? kb1 : k1, r);
+        if (i & 1) return u01(r[2], r[3]);
+        spare_u = u01(r[2], r[3]);
+        return u01(r[0], r[1]);
+#else
         if (i & 1) return spare_u;
         unsigned r[4];
         philox4x32_10(g0, g1, 0xFFFFFFFFu, 0x80000000u | (unsigned)(i >> 1), k0, k1, r);
         spare_u = u01(r[2], r[3]);
         return u01(r[0], r[1]);
+#endif
     }
 };
 
@@ -103,7 +149,7 @@ struct rat_param_rng {
 // none: the rollout's DomainError (the caller sets dom).  A hook that leaves q alone changes no bit.
 // Under RAT_PARAM_SHIFT: pshift is the shift row of the parameter normals, logw leaves holding the parameter part of the likelihood ratio.
 __device__ __forceinline__ bool rat_src_params(long g, unsigned long long seed, const double *zpn, const double *zpu, const double *p,
-                                               double (&q)[RAT_N_PARAMS], int &over RAT_PARAM_SHIFT_ARGS) {
+                                               double (&q)[RAT_N_PARAMS], int &over RAT_PARAM_SHIFT_ARGS RAT_PARAM_PICK_ARGS) {
     rat_param_rng rng;
     rng.gen = (zpn == nullptr && zpu == nullptr);
     rng.zn = (rng.gen || RAT_PARAM_NORMALS == 0) ? nullptr : zpn + g * (long)RAT_PARAM_NORMALS;
@@ -113,6 +159,9 @@ __device__ __forceinline__ bool rat_src_params(long g, unsigned long long seed, 
     rng.in = 0; rng.iu = 0; rng.over = 0; rng.spare_n = 0.0; rng.spare_u = 0.0;
 #ifdef RAT_PARAM_SHIFT
     rng.shift = pshift; rng.logw = 0.0;
+#endif
+#ifdef RAT_RNG_PICK
+    rng.kb0 = (unsigned)seed_b; rng.kb1 = (unsigned)(seed_b >> 32); rng.pick_n = pick_pn; rng.pick_u = pick_pu;
 #endif
     bool inok = true;
 #pragma unroll
@@ -155,12 +204,12 @@ struct src_rollout_params {
     // rat_src_params: true for the DomainError of a NaN parameter; the hook's overdraw bits go to `over` (and under RAT_PARAM_SHIFT the
     // parameter part of the rollout's likelihood ratio to `logw`)
     __device__ __forceinline__ bool draw(long g, unsigned long long seed, const double *zpn, const double *zpu, const double *p,
-                                         int &over RAT_PARAM_SHIFT_ARGS) {
-        return rat_src_params(g, seed, zpn, zpu, p, q, over RAT_PARAM_SHIFT_PASS);
+                                         int &over RAT_PARAM_SHIFT_ARGS RAT_PARAM_PICK_ARGS) {
+        return rat_src_params(g, seed, zpn, zpu, p, q, over RAT_PARAM_SHIFT_PASS RAT_PARAM_PICK_PASS);
     }
     __device__ __forceinline__ const double *of(const double *) const { return q; }
 #else
-    __device__ __forceinline__ bool draw(long, unsigned long long, const double *, const double *, const double *, int &) { return false; }
+    __device__ __forceinline__ bool draw(long, unsigned long long, const double *, const double *, const double *, int & RAT_PARAM_PICK_ARGS) { return false; }
     __device__ __forceinline__ const double *of(const double *p) const { return p; }
 #endif
 };

@@ -226,6 +226,9 @@ class GenericContext(il.Context):
     def policy_rare_event_params(self, *a, **k):
         self._carrier_only("policy_rare_event_params")
 
+    def policy_sobol(self, *a, **k):
+        self._carrier_only("policy_sobol")
+
     def policy_tail_events(self, *a, **k):
         self._carrier_only("policy_tail_events")
 

@@ -48,6 +48,44 @@ class ParamSampling:
         self.zpu = None if zpu is None else nv.f64(zpu)
 
 
+class SobolGroup:
+    """One group of random inputs of Context.policy_sobol (rat_policy_sobol): the draw indices it holds -- param_normals /
+    param_uniforms: the i-th rng.normal() / rng.uniform() of the source's rat_user_params; step_normals / step_uniforms: the i-th
+    rng.normal() / rng.uniform() of rat_user_noise at every step -- as four 64-bit masks (`words`, in the order of the C ABI's
+    RAT_SB_G_*).  Indices are 0 .. 63; groups of one call must be disjoint (check_groups)."""
+
+    def __init__(self, param_normals=(), param_uniforms=(), step_normals=(), step_uniforms=(), name=None):
+        self.name = name
+        self.words = tuple(self._mask(ix, what) for ix, what in ((param_normals, "param_normals"), (param_uniforms, "param_uniforms"),
+                                                                  (step_normals, "step_normals"), (step_uniforms, "step_uniforms")))
+
+    @staticmethod
+    def _mask(indices, what):
+        mask = 0
+        for i in np.atleast_1d(np.asarray(indices, dtype=np.int64)).ravel():
+            if not 0 <= int(i) < 64:
+                raise ValueError(f"SobolGroup: {what} index {int(i)} is outside 0 .. 63")
+            mask |= 1 << int(i)
+        return mask
+
+    @staticmethod
+    def check_groups(groups, normals_per_step, uniforms_per_step, param_normals=0, param_uniforms=0):
+        """What rat_policy_sobol asks of the groups, on the host: 1 .. 16 of them, no index at or beyond its declared count, no draw in
+        two groups.  Raises ValueError naming the group."""
+        groups = list(groups)
+        if not 1 <= len(groups) <= nv.SB_MAX_GROUPS:
+            raise ValueError("policy_sobol takes 1 .. 16 groups")
+        counts, seen = (param_normals, param_uniforms, normals_per_step, uniforms_per_step), [0, 0, 0, 0]
+        for gi, g in enumerate(groups):
+            for k in range(4):
+                if g.words[k] >> int(counts[k]):
+                    raise ValueError(f"policy_sobol: group {gi} names a draw at or beyond the declared count ({int(counts[k])})")
+                if g.words[k] & seen[k]:
+                    raise ValueError(f"policy_sobol: group {gi} overlaps an earlier group: groups must be disjoint")
+                seen[k] |= g.words[k]
+        return np.array([g.words for g in groups], dtype=np.uint64)
+
+
 def explained_share(cov_q, cov_qJ, tilt_var):
     """The linear share of the cost's variance that each parameter explains under a row's distribution, from the outputs of
     Context.policy_worst_case_params: cov_qJ[i]^2 / (cov_q[i, i] tilt_var) -- the squared correlation of q_i with J.  cov_q (R, P, P),
@@ -174,10 +212,11 @@ class Context:
                               self.device, C.byref(self.h)))
         self._fin = weakref.finalize(self, L.rat_destroy, self.h)
         self._param_normals = 0                                       # param_normals of the handle's parameter sampling (0: off)
+        self._param_uniforms = 0
         self._keep = self._upload(problem) if problem is not None else None
 
     def _upload(self, problem):
-        self._param_normals = 0                                       # (rat_problem_set_source switches parameter sampling off)
+        self._param_normals = self._param_uniforms = 0                # (rat_problem_set_source switches parameter sampling off)
         if getattr(problem, "model", 0) == MODEL_SOURCE:            # user-written f, c, h: compiled at run time (rat_problem_set_source)
             keep = nv.set_source(self.h, problem)
             self.params = keep["params"].copy()                       # what this handle's kernels read (set_params changes it)
@@ -210,7 +249,7 @@ class Context:
         behind policy_evaluate_noise call the source's rat_user_params once per rollout.  Injected streams are copied by the call."""
         if ps is None:
             nv.check(nv.lib().rat_policy_params_sampling(self.h, C.c_int32(0), C.c_int32(0), None, None, C.c_int64(0)))
-            self._param_normals = 0
+            self._param_normals = self._param_uniforms = 0
             return
         if not isinstance(ps, ParamSampling):
             raise TypeError("set_param_sampling needs a ParamSampling or None")
@@ -223,7 +262,7 @@ class Context:
                     raise ValueError("zpn and zpu hold different numbers of rollouts")
                 K = z.size // per
         nv.check(nv.lib().rat_policy_params_sampling(self.h, C.c_int32(pn), C.c_int32(pu), nv.P(ps.zpn), nv.P(ps.zpu), C.c_int64(K)))
-        self._param_normals = pn
+        self._param_normals, self._param_uniforms = pn, pu
 
     def sample_params(self, K, seed=0):
         """The parameters rat_user_params draws for rollouts 0 .. K - 1 under `seed` (or the injected draws): (K, n_params), row j behind
@@ -772,6 +811,31 @@ class Context:
         for k in ("n_viol", "n_ok", "n_domain", "flag", "n_iter"):
             r[k] = int(r[k])
         return RareEventResult(shift=s_out, trace=trace, margins=margins, logw=logw, param_shift=ps_out[:pn], param_trace=ptrace, **r)
+
+    def policy_sobol(self, x_nom, l, L=None, noise=None, groups=(), K=None, seed_a=1, seed_b=2, want_costs=False):
+        """Which uncertainty drives the cost (rat_policy_sobol): the first-order and total Sobol indices of the Monte-Carlo cost of the
+        policy (x_nom, l, L) for the groups of draws `groups` (SobolGroup), from K base samples of d + 2 pick-freeze rollouts each on the
+        device generator -- stream A under seed_a, stream B under seed_b.  noise: a UserNoise without injected streams (its seed is not
+        read).  Parameter sampling may be on (the device generator) or off.  Returns a dict: S, S_se, T, T_se (arrays over the groups),
+        names, n_ok, mean, var, var_se, flag, and with want_costs y (d + 2, K): rows A, B, then the groups (None otherwise)."""
+        if not isinstance(noise, UserNoise):
+            raise TypeError("policy_sobol needs noise=UserNoise(...)")
+        if noise.zn is not None or noise.zu is not None:
+            raise ValueError("policy_sobol draws from the device generator only: no injected streams")
+        if K is None:
+            raise ValueError("policy_sobol needs K=")
+        groups = list(groups)
+        words = SobolGroup.check_groups(groups, noise.normals_per_step, noise.uniforms_per_step, self._param_normals, self._param_uniforms)
+        K, d = int(K), len(groups)
+        index, summary = np.zeros((d, nv.SB_NINDEX)), np.zeros(nv.SB_NSTAT)
+        y = np.zeros((d + 2, max(K, 1))) if want_costs else None
+        nv.check(nv.lib().rat_policy_sobol(self.h, nv.P(nv.f64(x_nom)), nv.P(nv.f64(l)), nv.P(nv.cm3(L)) if L is not None else None,
+                                           C.c_int64(K), C.c_int32(noise.normals_per_step), C.c_int32(noise.uniforms_per_step),
+                                           words.ctypes.data_as(nv._up), C.c_int32(d), C.c_uint64(int(seed_a)), C.c_uint64(int(seed_b)),
+                                           nv.P(index), nv.P(summary), nv.P(y)))
+        return dict(S=index[:, nv.SB_S].copy(), S_se=index[:, nv.SB_S_SE].copy(), T=index[:, nv.SB_T].copy(), T_se=index[:, nv.SB_T_SE].copy(),
+                    names=[g.name for g in groups], n_ok=int(summary[nv.SB_N_OK]), mean=float(summary[nv.SB_MEAN]),
+                    var=float(summary[nv.SB_VAR]), var_se=float(summary[nv.SB_VAR_SE]), flag=int(summary[nv.SB_FLAG]), y=y)
 
     def integrate_cost(self, x, u):
         out = C.c_double()
