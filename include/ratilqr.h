@@ -522,6 +522,52 @@ rat_rc rat_policy_tail_disturbance(rat_handle h, const double *alpha, int32_t n_
                                    double *cov_w_out, double *cov_wz_out);
 rat_rc rat_policy_tail_params(rat_handle h, const double *alpha, int32_t n_alpha, double *rows_out, double *mean_q_out,
                               double *cov_q_out, double *cov_qJ_out);
+/* Which way to move the policy: the gradient, with respect to the feed-forward terms l and the gains L, of what the Monte-Carlo calls
+ * measure on a source model -- the mean cost (theta = 0, alpha = 0), the entropic risk (1 / theta) log mean exp(theta J) of a theta row,
+ * sup { E_p[J] : KL(p || q) <= d } of a kl_bound row (envelope theorem: the tilt at theta*, theta* itself is not differentiated) and
+ * CVaR_alpha of a level -- by adjoint replay on the device.  The calls take no policy and no noise: they REPLAY the last
+ * rat_policy_evaluate_noise exactly as rat_policy_worst_case_trajectory / rat_policy_tail_trajectory do (the same chunks and seeds, the
+ * same bit-for-bit check against the stored costs) and sweep every replayed rollout k backwards, the recorded disturbances w_t held fixed:
+ *   lambda_N = h_x(x_N)
+ *   g_t      = c_z(t, x_t, u_t) + f_z(x_t, u_t)' lambda_{t+1},   z = (x, u),   t = N - 1 .. 0
+ *   gu_t     = the u part of g_t                                   (dJ_k / du_t with the loop closed downstream)
+ *   lambda_t = (x part of g_t) + L_t' gu_t                          (open loop, L == NULL: the x part alone)
+ *   dJ_k / dl_t = gu_t,     dJ_k / dL_t = gu_t (x_t - x_nom_t)'
+ * with f_z, c_z, h_x by rat_ad.h's forward mode on the user's rat_user_f / rat_user_c / rat_user_h (f_z from rat_user_f_jacobian where
+ * the source defines RAT_USER_F_JACOBIAN).  With y_k the weight of rollout k in a row -- the tilted weights of a theta row, those at
+ * theta* of a kl_bound row, the tail distribution of a level, bit for bit the rows' own --
+ *   grad_l[t] = sum y_k gu_t^k / sum y_k,      grad_L[t] = sum y_k gu_t^k (x_t^k - x_nom_t)' / sum y_k.
+ * What this is and is not:
+ *   - A saturated row (RAT_WC_SATURATED, RAT_TR_SATURATED: all weight on the rollouts that attain Jmax) is a SUBGRADIENT of its functional.
+ *   - A sampler that reads x or u is differentiated with w FROZEN: rat_user_noise takes double, not T, so the dependence of w_t on
+ *     (x_t, u_t) is not seen.  The gradient is exact only for samplers that ignore their state arguments.
+ *   - x_nom is not differentiated: it is the point the law is written about, not a decision variable.
+ *   rows_out       as rat_policy_worst_case_trajectory's / rat_policy_tail_trajectory's, bit for bit
+ *   grad_l_out     [rows][N][m]: one copy per row in the layout rat_policy_evaluate_noise takes l in
+ *   grad_L_out     [rows][N][m n] (column-major m x n per step, the layout it takes L in), or NULL; written as zeros after an open-loop
+ *                  evaluation
+ *   grad_l_se_out  [rows][N][m] or NULL: the self-normalised standard error sqrt(sum p_k^2 (gu - mean)^2), p_k = y_k / sum y, formed
+ *                  from the uncentred sums sum y gu, sum y^2 gu, sum y^2 gu^2, sum y^2 and clamped at 0 -- whether an entry of grad_l
+ *                  stands out of its own sampling error
+ *   n_nonfinite_out  or NULL: rollouts that have a cost but a NaN or Inf somewhere in their sensitivities (h_x or a component of some
+ *                  g_t: AD at sqrt(0), say).  They are left out of every gradient sum and of the denominator the gradient is divided
+ *                  by; the rows themselves still count them.  The call returns RAT_OK.
+ * A DomainError rollout carries no weight.  RAT_WC_EMPTY / RAT_WC_NONFINITE rows (and the tail's) are NaN in every gradient output and the
+ * call returns RAT_OK.  Fixed summation order, no floating-point atomics: the same call returns the same bits, and a row's bits do not
+ * depend on the other rows of the call.
+ * Served: source models after rat_policy_evaluate_noise with zn == zu == NULL -- what the trajectory calls serve for sources.
+ * RAT_ERR_UNSUPPORTED, each message naming its reason: the LQ / power-law families and general sizes (write the model as source); a source
+ * that defines RAT_USER_POLICY (the hook is not templated, so the law is not differentiable by rat_ad.h); parameter sampling switched
+ * on (rat_policy_params_sampling); rows x N above 3360 (64 MiB of partial sums).  Row validation, "no evaluation yet" and the replay
+ * guard are the trajectory calls', with their codes. */
+rat_rc rat_policy_gradient(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                           double *rows_out, double *grad_l_out, double *grad_L_out, double *grad_l_se_out, int64_t *n_nonfinite_out);
+rat_rc rat_policy_tail_gradient(rat_handle h, const double *alpha, int32_t n_alpha,
+                                double *rows_out, double *grad_l_out, double *grad_L_out, double *grad_l_se_out, int64_t *n_nonfinite_out);
+/* Compile only, for gfx950 (no device needed), the adjoint kernel of the two calls above.  rat_user_noise_check's codes (a source that
+ * does not compile, or one without RAT_USER_NOISE: RAT_ERR_ARG with the compiler's log), and RAT_ERR_UNSUPPORTED for a source that defines
+ * RAT_USER_POLICY. */
+rat_rc rat_policy_gradient_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms);
 /* Safety events of a policy: how often it hits an obstacle, leaves the lane or saturates an actuator -- under the nominal distribution q (a
  * theta = 0 row) and under the worst-case distribution p* ~ exp(theta* J) q of each kl_bound (and the tilt of each given theta), formed on
  * the device.  An event is a quadratic function of z_t = (x_t, u_t) in R^d, d = n + m, u_N = 0, watched over a window of steps:

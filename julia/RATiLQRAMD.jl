@@ -573,6 +573,47 @@ function policy_tail_trajectory(s::ILEQGSolver; alphas=Float64[])
 end
 
 """
+policy_gradient(s; kl_bounds, thetas): which way to move the policy (rat_policy_gradient).  The gradient with respect to l and L of the
+mean cost (θ = 0), of the entropic risk of each θ and of the KL-robust bound of each radius (at its θ*), by adjoint replay of the last
+evaluate_policy under the source's own noise on this solver's handle.  Returns (bounds, thetas): each a named tuple of
+policy_worst_case's row vectors and, with R rows, grad_l (m, N, R), grad_L (m, n, N, R) (zeros after an open-loop evaluation), grad_l_se
+(m, N, R) and n_nonfinite.  The disturbances are held fixed, x_nom is not differentiated, a saturated row is a subgradient.
+"""
+function policy_gradient(s::ILEQGSolver; kl_bounds=Float64[], thetas=Float64[])
+    h = s.h
+    n, m, N = dims(h.problem)
+    d = collect(Float64, kl_bounds); th = collect(Float64, thetas)
+    nb, nt = length(d), length(th); R = nb + nt
+    rows = zeros(8, R); gl = zeros(m, N, R); gL = zeros(m, n, N, R); se = zeros(m, N, R); nf = Ref{Int64}(0)
+    check(ccall((:rat_policy_gradient, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, nb > 0 ? d : C_NULL, nb, nt > 0 ? th : C_NULL, nt, rows, gl, gL, se, nf))
+    part(r) = (theta=rows[1, r], kl=rows[2, r], bound=rows[3, r], bound_se=rows[4, r], tilt_mean=rows[5, r], tilt_var=rows[6, r],
+               ess=rows[7, r], flag=Int.(rows[8, r]), grad_l=gl[:, :, r], grad_L=gL[:, :, :, r], grad_l_se=se[:, :, r], n_nonfinite=nf[])
+    (bounds=part(1:nb), thetas=part(nb+1:R))
+end
+
+"""
+policy_tail_gradient(s; alphas): the gradient of CVaR_α with respect to l and L per level (rat_policy_tail_gradient): policy_gradient
+under the tail distribution of policy_tail_risk (α = 0 is the mean).  Returns a named tuple of policy_tail_risk's row vectors and
+grad_l (m, N, R), grad_L (m, n, N, R), grad_l_se (m, N, R), n_nonfinite.
+"""
+function policy_tail_gradient(s::ILEQGSolver; alphas=Float64[])
+    h = s.h
+    n, m, N = dims(h.problem)
+    al = collect(Float64, alphas); R = length(al)
+    rows = zeros(8, R); gl = zeros(m, N, R); gL = zeros(m, n, N, R); se = zeros(m, N, R); nf = Ref{Int64}(0)
+    check(ccall((:rat_policy_tail_gradient, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, R > 0 ? al : C_NULL, R, rows, gl, gL, se, nf))
+    merge(tail_rows(rows, 1:R), (grad_l=gl, grad_L=gL, grad_l_se=se, n_nonfinite=nf[]))
+end
+
+"policy_gradient_check(source, n, m; normals_per_step, uniforms_per_step): compile the adjoint kernel of policy_gradient only (rat_policy_gradient_check)"
+policy_gradient_check(source::AbstractString, n::Integer, m::Integer; normals_per_step::Integer=0, uniforms_per_step::Integer=0) =
+    check(ccall((:rat_policy_gradient_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32), source, n, m, normals_per_step, uniforms_per_step))
+
+"""
 policy_tail_disturbance(s; alphas, cross): what the noise of the tail looks like (rat_policy_tail_disturbance):
 policy_worst_case_disturbance's moments over the worst (1 − α) share of the rollouts per level.  Returns a named tuple of
 policy_tail_risk's row vectors and, with R levels, mean_w (n, N, R), cov_w (n, n, N, R) and, with cross, cov_wx (n, n, N, R) and cov_wu
@@ -1753,7 +1794,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, policy_tail_events, policy_tail_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, rare_event_probability_params, rare_event_params_check, SobolGroup, policy_sobol, policy_sobol_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_gradient, policy_tail_gradient, policy_gradient_check, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, policy_tail_events, policy_tail_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, rare_event_probability_params, rare_event_params_check, SobolGroup, policy_sobol, policy_sobol_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

@@ -107,6 +107,7 @@ EXPORTS = [
     "rat_policy_rare_event_params", "rat_rare_event_params_check",
     "rat_policy_tail_events", "rat_policy_tail_events_user",
     "rat_policy_sobol", "rat_policy_sobol_check",
+    "rat_policy_gradient", "rat_policy_tail_gradient", "rat_policy_gradient_check",
 ]
 MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 WC_SLOTS = ("theta", "kl", "bound", "bound_se", "tilt_mean", "tilt_var", "ess", "flag")      # RAT_WC_* slots of the header, in order
@@ -192,6 +193,9 @@ def lib():
         _lib.rat_policy_sobol.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_int32, _up, C.c_int32, C.c_uint64, C.c_uint64,
                                           _dp, _dp, _dp]
         _lib.rat_policy_sobol_check.argtypes = [C.c_char_p] + [C.c_int32] * 7
+        _lib.rat_policy_gradient.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]
+        _lib.rat_policy_tail_gradient.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]
+        _lib.rat_policy_gradient_check.argtypes = [C.c_char_p] + [C.c_int32] * 4
     return _lib
 
 
@@ -291,6 +295,12 @@ def policy_sobol_check(source, n, m, n_params=0, normals_per_step=0, uniforms_pe
     the counts (at most 64 each)."""
     check(lib().rat_policy_sobol_check(str(source).encode(), int(n), int(m), int(n_params), int(normals_per_step), int(uniforms_per_step),
                                        int(param_normals), int(param_uniforms)))
+
+
+def policy_gradient_check(source, n, m, normals_per_step=0, uniforms_per_step=0):
+    """rat_policy_gradient_check: compile the adjoint kernel of rat_policy_gradient / rat_policy_tail_gradient only (gfx950, no device
+    needed); raises RatError with the compiler's log, or saying that the source defines RAT_USER_POLICY (RAT_ERR_UNSUPPORTED)."""
+    check(lib().rat_policy_gradient_check(str(source).encode(), int(n), int(m), int(normals_per_step), int(uniforms_per_step)))
 
 
 def pets_set_source(h, prob):

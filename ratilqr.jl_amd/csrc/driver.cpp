@@ -269,6 +269,12 @@ struct rat_handle_s {
     double *d_sb_y = nullptr; size_t cap_sb_y = 0;           // [n_groups + 2][K] costs of the pick-freeze rollouts
     int *d_sb_ok = nullptr; size_t cap_sb_ok = 0;            // [K] base samples without a DomainError in any of their rollouts
     double *d_sb_red = nullptr;                              // [SB_SCRATCH]
+    // the policy gradient (rat_policy_gradient / rat_policy_tail_gradient, source_adjoint.h and policy_mc.hip) rides on the replay, with
+    // the SRC_ADJOINT kernel forming each chunk's adjoints; only those calls allocate these
+    double *d_pg_gu = nullptr; size_t cap_pg_gu = 0;         // [chunk][N][4] dJ_k / du_t staging
+    int *d_pg_bad = nullptr; size_t cap_pg_bad = 0;          // [chunk] rollouts with a cost but non-finite sensitivities
+    double *d_pg_part = nullptr; size_t cap_pg_part = 0;     // [rows][N][WT_SLOTS][PG_PART] partials
+    double *d_pg_out = nullptr; size_t cap_pg_out = 0;       // grad_l | grad_L | grad_l_se | S0, sum y^2 per row | mismatch count | non-finite count
 };
 
 extern "C" int32_t rat_version(void) { return RAT_VERSION; }
@@ -462,6 +468,7 @@ extern "C" void rat_destroy(rat_handle h) {
     for (void *q : {(void *)h->d_ev_out, (void *)h->d_ev_part, (void *)h->d_ev_margin, (void *)h->d_ev_tau, (void *)h->d_ev_mask}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_re_in, (void *)h->d_re_margin, (void *)h->d_re_logw, (void *)h->d_re_dom, (void *)h->d_re_part, (void *)h->d_re_red}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_sb_in, (void *)h->d_sb_y, (void *)h->d_sb_ok, (void *)h->d_sb_red}) if (q) (void)hipFree(q);
+    for (void *q : {(void *)h->d_pg_gu, (void *)h->d_pg_bad, (void *)h->d_pg_part, (void *)h->d_pg_out}) if (q) (void)hipFree(q);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
     if (h->h_pcost) (void)hipHostFree(h->h_pcost);
@@ -2959,6 +2966,104 @@ extern "C" rat_rc rat_policy_tail_params(rat_handle h, const double *alpha, int3
     if ((rc = replay_params_ready(h, F))) return rc;
     if ((rc = replay_validate_handle(h, F, "rat_policy_tail_risk"))) return rc;
     return replay_params(h, F, "rat_policy_tail_params", replay_tail(alpha, n_alpha), rows_out, mean_q_out, cov_q_out, cov_qJ_out);
+}
+
+// ---- which way to move the policy: rat_policy_gradient and rat_policy_tail_gradient -----------------------------------------------------------
+// The gradient of a row's functional (the mean, the entropic risk, the KL-robust bound at theta*, CVaR) with respect to l and L, by
+// adjoint replay: the trajectory call's replay; behind each chunk rat_src_adjoint (source_adjoint.h, a hiprtc module of its own that the
+// first gradient call compiles) sweeps every rollout backwards into d_pg_gu, then pg_moments of policy_mc.hip; one enqueue chain, one host
+// wait.
+// a compile that failed on the header's own refusal of a source with rat_user_policy is RAT_ERR_UNSUPPORTED
+static rat_rc gradient_compile_rc(rat_rc rc) {
+    return (rc == RAT_ERR_ARG && g_err.find("the source defines RAT_USER_POLICY") != std::string::npos) ? RAT_ERR_UNSUPPORTED : rc;
+}
+
+extern "C" rat_rc rat_policy_gradient_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms) {
+    return gradient_compile_rc(src_check("rat_policy_gradient_check", SRC_ADJOINT, source, n, m, normals, uniforms));
+}
+
+// what either gradient call refuses before the row arguments are looked at
+static rat_rc gradient_ready(rat_handle h, const std::string &F) {
+    if (!h) return fail(RAT_ERR_ARG, F + "null handle");
+    if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
+    if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
+        return fail(RAT_ERR_UNSUPPORTED, F + "the gradient differentiates the user's f, c and h with rat_ad.h, which the LQ / power-law families and "
+                                         "general sizes do not go through: write the model as source (rat_problem_set_source) and evaluate "
+                                         "with rat_policy_evaluate_noise");
+    if (h->ps_on)
+        return fail(RAT_ERR_UNSUPPORTED, F + "parameter sampling is on (rat_policy_params_sampling): the adjoint of rollouts that draw parameters "
+                                         "of their own is not built; switch sampling off and evaluate again");
+    return RAT_OK;
+}
+
+// (rs.tail(): rat_policy_tail_gradient, as replay_trajectory serves rat_policy_tail_trajectory; fn: the call's name)
+static rat_rc replay_gradient(rat_handle h, const std::string &F, const char *fn, const ReplaySpec &rs, double *rows_out, double *grad_l_out,
+                              double *grad_L_out, double *grad_l_se_out, int64_t *n_nonfinite_out) {
+    rat_rc rc;
+    const rat_handle_s::McReplay rec = h->mc_rec;
+    const int n = h->n, m = h->m, N = h->N, nrows = rs.nrows();
+    if ((long)nrows * N > PG_MAX_ROWSTEPS)
+        return fail(RAT_ERR_UNSUPPORTED, F + "rows x N = " + std::to_string((long)nrows * N) + " is above " +
+                                         std::to_string(PG_MAX_ROWSTEPS) + " (64 MiB of partial sums): ask for fewer rows per call");
+    HIPCHK(hipSetDevice(h->device));
+    hipFunction_t kadj = nullptr;
+    if ((rc = src_kernel(h, SRC_ADJOINT, SrcShape{rec.npn, rec.npu, 0}, fn, &kadj))) return gradient_compile_rc(rc);
+    const int64_t chunk = mc_chunk(rec.K);
+    const size_t nrs = (size_t)nrows * N;                             // (rows x steps)
+    const size_t o_gl = 0, o_gL = o_gl + nrs * m, o_se = o_gL + nrs * m * n, o_ess = o_se + nrs * m, o_cnt = o_ess + 2 * (size_t)nrows,
+                 o_nf = o_cnt + 1, n_out = o_nf + 1, n_part = nrs * WT_SLOTS * PG_PART;
+    if ((rc = grow(&h->d_pg_part, &h->cap_pg_part, n_part))) return rc;
+    if ((rc = grow(&h->d_pg_out, &h->cap_pg_out, n_out))) return rc;
+    if ((rc = grow(&h->d_pg_gu, &h->cap_pg_gu, (size_t)chunk * N * 4))) return rc;
+    if ((rc = grow(&h->d_pg_bad, &h->cap_pg_bad, (size_t)chunk))) return rc;
+    HIPCHK(hipMemsetAsync(h->d_pg_part, 0, n_part * 8, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_pg_out + o_nf, 0, 8, h->stream));
+    PgArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.gu = h->d_pg_gu; pa.bad = h->d_pg_bad; pa.xnom = rec.has_L ? h->d_mc_in + rec.o_x : nullptr; pa.part = h->d_pg_part;
+    pa.grad_l = h->d_pg_out + o_gl; pa.grad_L = h->d_pg_out + o_gL; pa.grad_l_se = h->d_pg_out + o_se; pa.ess = h->d_pg_out + o_ess;
+    if ((rc = replay_chunks(h, rs, reinterpret_cast<int *>(h->d_pg_out + o_cnt), pa.t,
+                            [&](const WtArgs &c, ReplayChunk ch) -> rat_rc {
+                                SrcAdjointArgs sa;                    // the chunk's adjoints, behind its rollouts
+                                sa.xs = c.xs; sa.us = c.us; sa.N = N; sa.kc = (long)ch.kc; sa.cost = c.cost_re;
+                                sa.L = rec.has_L ? h->d_mc_in + rec.o_L : nullptr; sa.p = h->d_src_p;
+                                sa.gu = h->d_pg_gu; sa.bad = h->d_pg_bad; sa.n_bad = reinterpret_cast<int *>(h->d_pg_out + o_nf);
+                                HIPCHK(launch_src(kadj, ch.kc, 4, h->stream, &sa));
+                                launch_pg_chunk(pa, ch.live, h->stream);
+                                return RAT_OK;
+                            })))
+        return rc;
+    launch_pg_final(pa, h->stream);
+    double nf_slot = 0.0;                                             // (the count is an int in a slot of the doubles)
+    if ((rc = replay_finish(h, F, rs.tail(), nrows, h->d_pg_out, o_ess, 2, o_cnt,
+                            {{grad_l_out, o_gl, nrs * m}, {grad_L_out, o_gL, nrs * m * n}, {grad_l_se_out, o_se, nrs * m}, {&nf_slot, o_nf, 1}},
+                            rows_out)))
+        return rc;
+    int nf = 0;
+    memcpy(&nf, &nf_slot, sizeof(int));
+    if (n_nonfinite_out) *n_nonfinite_out = nf;
+    return RAT_OK;
+}
+
+extern "C" rat_rc rat_policy_gradient(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                      double *rows_out, double *grad_l_out, double *grad_L_out, double *grad_l_se_out, int64_t *n_nonfinite_out) {
+    const std::string F = "rat_policy_gradient: ";
+    rat_rc rc;
+    if ((rc = gradient_ready(h, F))) return rc;
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && grad_l_out))) return rc;
+    return replay_gradient(h, F, "rat_policy_gradient", replay_kl(kl_bound, n_bound, theta, n_theta), rows_out, grad_l_out, grad_L_out,
+                           grad_l_se_out, n_nonfinite_out);
+}
+
+extern "C" rat_rc rat_policy_tail_gradient(rat_handle h, const double *alpha, int32_t n_alpha, double *rows_out, double *grad_l_out,
+                                           double *grad_L_out, double *grad_l_se_out, int64_t *n_nonfinite_out) {
+    const std::string F = "rat_policy_tail_gradient: ";
+    rat_rc rc;
+    if ((rc = replay_validate_alpha(F, alpha, n_alpha, rows_out && grad_l_out))) return rc;
+    if ((rc = gradient_ready(h, F))) return rc;
+    if ((rc = replay_validate_handle(h, F, "rat_policy_tail_risk"))) return rc;
+    return replay_gradient(h, F, "rat_policy_tail_gradient", replay_tail(alpha, n_alpha), rows_out, grad_l_out, grad_L_out, grad_l_se_out,
+                           n_nonfinite_out);
 }
 
 // p' log(p' / p) + (1 - p') log((1 - p') / (1 - p)) for p <= p' < 1, 0 < p < 1, both logarithms through log1p of the difference: near

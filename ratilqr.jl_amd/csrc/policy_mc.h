@@ -231,6 +231,40 @@ void launch_tlt_levels(const TrArgs &a, double *wc, hipStream_t s);
 void launch_tlt_weights(const WtArgs &a, unsigned *live, hipStream_t s);
 // ... then, behind it, the chunk's sums into the partials: launch_wct_chunk / launch_wcd_chunk / launch_wcp_chunk with live
 
+// ---- rat_policy_gradient / rat_policy_tail_gradient: the gradient of a row's functional with respect to the policy (policy_mc.hip) ---------
+// The trajectory call's replay; behind each chunk rat_src_adjoint (source_adjoint.h, kind SRC_ADJOINT) writes gu_t = dJ_k / du_t of every
+// rollout (staged [kc][N][4]) and its flag bad [kc] (a cost, but a NaN or Inf in the sensitivities), and pg_moments adds, per step t < N and
+// row: one tile sum y G Dx' -- G = gu_t in lanes 12 .. 15, Dx = x_t - x_nom_t in lanes 0 .. 11 (zeros open loop), so rows 12 .. 15,
+// columns 0 .. 11 of the tile are dJ / dL_t -- the per-lane sums sum y G, sum y^2 G, sum y^2 G^2, and per rollout lane sum y and sum y^2
+// over the rollouts whose sensitivities are finite.  A flagged rollout is selected out of all of these (both operands of the product
+// included), never multiplied; the skeleton's own S0 and sum y^2 still count it.  pg_moments keeps wct_moments' schedule (WT_SLOTS,
+// WT_WAVES, WT_ROWS; dense, or the tail calls' liveness schedule); pg_final sums the slots in index order.
+#define PG_PART 312           /* doubles per partial: sum y G Dx' [16][16] | sum y G [16] | sum y^2 G [16] | sum y^2 G^2 [16] | S0 | sum y^2 | the two over finite rollouts | padding */
+#define PG_O_V1 256
+#define PG_O_V2 272
+#define PG_O_V3 288
+#define PG_O_S0 304
+#define PG_O_SY2 305
+#define PG_O_SF 306
+#define PG_O_SF2 307
+#define PG_MAX_ROWSTEPS 3360  /* rows x N at most: the partials [rows][N][WT_SLOTS][PG_PART] stay below 64 MiB (31.9 MB: 32 rows, N = 50) */
+
+struct PgArgs {
+    WtArgs t;                 // the replay's fields as wct_weights fills them (xs, ldx, kc, cost, y, ldy, nrows, wc, n, m, N); centre, part, mean, cov, ess are not read
+    const double *gu;         // [kc][N][4] the staged adjoints of the chunk
+    const int *bad;           // [kc] the chunk's non-finite flags
+    const double *xnom;       // [N+1][12] the pack's nominal states, or null (open loop: no dJ / dL)
+    double *part;             // [nrows][N][WT_SLOTS][PG_PART]
+    // pg_final only
+    double *grad_l;           // [nrows][N][m]
+    double *grad_L;           // [nrows][N][m n] column-major m x n per step (zeros open loop)
+    double *grad_l_se;        // [nrows][N][m]
+    double *ess;              // [nrows][2]: S0 and sum y^2 of step 0
+};
+// one chunk, behind launch_wct_weights / launch_tlt_weights and the chunk's adjoints: the chunk's sums into the partials
+void launch_pg_chunk(const PgArgs &a, const unsigned *live, hipStream_t s);
+void launch_pg_final(const PgArgs &a, hipStream_t s);
+
 // ---- rat_policy_events: how often a policy violates quadratic constraints, under q and under every row's tilt (policy_mc.hip) ---------------
 // An event is g(t, z) = z' Q z + a' z + b of z = (x_t, u_t) in the 12 + 4 tile, watched over the steps t_lo .. t_hi.  Behind each replayed
 // chunk (after wct_weights) ev_eval forms, per rollout and event, the margin M = max g over the window, the first step tau with g > 0 and

@@ -1067,6 +1067,74 @@ __global__ __launch_bounds__(MC_THREADS) void wcd_final(WdArgs a) {
     if (t == 0 && e == 0) { a.ess[2 * r] = s0; a.ess[2 * r + 1] = S[WD_O_SY2]; }
 }
 
+// ---- rat_policy_gradient / rat_policy_tail_gradient: G = gu_t in lanes 12 .. 15, Dx = x_t - x_nom_t in lanes 0 .. 11, one product ----------
+// Per group, step and row one MFMA A = y G, B = Dx: C[12 + j][i] = sum y gu_j Dx_i = dJ / dL_t(j, i) before the division.  A lane holds
+// one of the two operands and an exact zero for the other, so the rest of the tile is zeros.  sum y G, sum y^2 G and sum y^2 G^2 ride
+// along in the lanes, sum y and sum y^2 over the rollouts with finite sensitivities in the rollout lanes.  A rollout flagged in bad is
+// selected out at the load -- of G, of Dx and of the two scalar sums -- so a NaN or Inf of its adjoint reaches nothing.
+struct GradientMoments {
+    static constexpr int TILES = 1, VECS = 3, SCALARS = 4;
+    static __device__ __forceinline__ constexpr int o_tile(int) { return 0; }
+    static __device__ __forceinline__ constexpr int o_vec(int b) { return b == 0 ? PG_O_V1 : b == 1 ? PG_O_V2 : PG_O_V3; }
+    static __device__ __forceinline__ constexpr int o_scalar(int s) { return s == 0 ? PG_O_S0 : s == 1 ? PG_O_SY2 : s == 2 ? PG_O_SF : PG_O_SF2; }
+    static __device__ __forceinline__ int batch() { return blockIdx.z; }
+    struct Dev { double G, Dx; bool fin; };
+    const PgArgs &a;
+    const int t, i;
+    const bool compg, compx;
+    const double c;
+    __device__ __forceinline__ GradientMoments(const PgArgs &a_)
+        : a(a_), t(blockIdx.y), i(threadIdx.x & 15),
+          compg(i >= 12 && i - 12 < a_.t.m),                          // (padding lanes stay zero; t < N throughout)
+          compx(a_.xnom != nullptr && i < a_.t.n),
+          c(compx ? a_.xnom[t * 12 + i] : 0.0) {}
+    __device__ __forceinline__ double *part(int row, int slot) const { return a.part + (((size_t)row * a.t.N + t) * WT_SLOTS + slot) * PG_PART; }
+    __device__ __forceinline__ Dev load(long q, bool ok, double) const {
+        const int N = a.t.N;
+        const bool fin = ok && a.bad[q] == 0;
+        double G = 0.0, Dx = 0.0;
+        if (fin && compg) G = a.gu[(q * N + t) * 4 + (i - 12)];
+        if (fin && compx) Dx = a.t.xs[(q * (N + 1) + t) * a.t.ldx + i] - c;
+        return Dev{G, Dx, fin};
+    }
+    __device__ __forceinline__ void row(wt_d4 (&C)[TILES], double (&v)[VECS], double (&s)[SCALARS], double y, bool has, const Dev &d) const {
+        const double Dxr = has ? d.Dx : 0.0, yg = has ? y * d.G : 0.0, yf = d.fin ? y : 0.0;
+        C[0] = wt_mfma(yg, Dxr, C[0]);
+        v[0] += yg;
+        v[1] += y * yg;
+        v[2] += yg * yg;
+        s[2] += yf;
+        s[3] += yf * yf;
+    }
+};
+
+__global__ __launch_bounds__(WT_WAVES * 64) void pg_moments(PgArgs a) { moments_body<GradientMoments, false>(GradientMoments(a), a.t, nullptr); }
+__global__ __launch_bounds__(WT_WAVES * 64) void tlg_moments(PgArgs a, const unsigned *live) { moments_body<GradientMoments, true>(GradientMoments(a), a.t, live); }
+
+// grad_l = sum y gu / sum y and grad_L = sum y gu Dx' / sum y over the rollouts with finite sensitivities; the self-normalised standard
+// error sqrt(sum p^2 (gu - mean)^2), p = y / sum y, from the uncentred sums, clamped at 0.  A dead row (an empty or non-finite sample) is
+// NaN, as in wct_final; a row none of whose rollouts has finite sensitivities is 0 / 0.
+__global__ __launch_bounds__(MC_THREADS) void pg_final(PgArgs a) {
+    __shared__ double S[PG_PART];
+    const int t = blockIdx.x, r = blockIdx.y, e = threadIdx.x, N = a.t.N, n = a.t.n, m = a.t.m;
+    slot_sum<PG_PART>(a.part + ((size_t)r * N + t) * WT_SLOTS * PG_PART, S);
+    const double nan = __builtin_nan("");
+    const bool dead = row_dead(a.t.wc, r);
+    const double sf = S[PG_O_SF], sf2 = S[PG_O_SF2];
+    const size_t o = (size_t)r * N + t;
+    if (e < m * n) {                                                  // column-major m x n: entry (j, i) at j + m i
+        const int j = e % m, ii = e / m;
+        a.grad_L[o * m * n + e] = !a.xnom ? 0.0 : dead ? nan : S[(12 + j) * 16 + ii] / sf;   // (open loop: zeros)
+    }
+    if (e < m) {
+        const double mean = S[PG_O_V1 + 12 + e] / sf;
+        const double var = ((S[PG_O_V3 + 12 + e] - 2.0 * mean * S[PG_O_V2 + 12 + e]) + mean * mean * sf2) / (sf * sf);
+        a.grad_l[o * m + e] = dead ? nan : mean;
+        a.grad_l_se[o * m + e] = dead ? nan : (var > 0.0 ? sqrt(var) : (var != var ? nan : 0.0));
+    }
+    if (t == 0 && e == 0) { a.ess[2 * r] = S[PG_O_S0]; a.ess[2 * r + 1] = S[PG_O_SY2]; }
+}
+
 // ---- rat_policy_worst_case_params: one step, Dq = q - c_q in up to two tiles of sixteen parameters per lane ----------------------------------
 // Lane (i, kk) holds Dq_i (tile 0) and Dq_{16 + i} (tile 1, TWO) of rollout 4 g + kk.  Per group and row A0 = y Dq(tile 0), B0 = Dq(tile 0)
 // give block (0,0) of sum y Dq Dq'; with TWO, A0 and B1 give block (0,1) and A1, B1 block (1,1); block (1,0) is (0,1)' and is never
@@ -1631,6 +1699,15 @@ void launch_wcd_chunk(const WdArgs &a, const unsigned *live, hipStream_t s) {
 
 void launch_wcd_final(const WdArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(wcd_final, dim3((unsigned)a.t.N, (unsigned)a.t.nrows), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_pg_chunk(const PgArgs &a, const unsigned *live, hipStream_t s) {
+    if (a.t.kc <= 0 || a.t.nrows <= 0 || a.t.N <= 0) return;
+    launch_moments(pg_moments, tlg_moments, dim3(WT_SLOTS, (unsigned)a.t.N, (unsigned)((a.t.nrows + WT_ROWS - 1) / WT_ROWS)), a, live, s);
+}
+
+void launch_pg_final(const PgArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(pg_final, dim3((unsigned)a.t.N, (unsigned)a.t.nrows), dim3(MC_THREADS), 0, s, a);
 }
 
 void launch_wcp_centre(const WpArgs &a, hipStream_t s) {

@@ -154,3 +154,17 @@ struct SrcSobolArgs {
     int *overdraw;            // set (plain store) as rat_src_user_noisy_rollout sets it: 1, 2 a step's normals / uniforms, 4, 8 the hook's
     unsigned long long pick[SOBOL_MAX_VAR][4];   // per variant: parameter normals, parameter uniforms, step normals, step uniforms
 };
+
+// rat_src_adjoint (source_adjoint.h): the adjoint sweep of every rollout of one replayed chunk (rat_policy_gradient /
+// rat_policy_tail_gradient), a team of sixteen lanes per rollout, four rollouts per wavefront
+struct SrcAdjointArgs {
+    const double *xs, *us;    // staged trajectories of the chunk: [kc][N+1][RAT_N], [kc][N][RAT_M] dense
+    int N;
+    long kc;                  // rollouts of the chunk
+    const double *cost;       // [kc] the costs the replay formed (NaN: DomainError, the rollout is passed over)
+    const double *L;          // [N][4][12] or null (open loop)
+    const double *p;          // the model's parameters
+    double *gu;               // [kc][N][4] dJ_k / du_t with the loop closed downstream, zero padded; untouched for a rollout without a cost
+    int *bad;                 // [kc] 1: the rollout has a cost but a NaN or Inf in its sensitivities; untouched for a rollout without a cost
+    int *n_bad;               // the number of those rollouts, added to (an integer atomic: a count has no order)
+};

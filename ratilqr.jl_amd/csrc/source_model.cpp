@@ -82,6 +82,7 @@ static const SrcKindRow k_kinds[SRC_NKIND] = {
     /* SRC_RARE_USER  */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  true,  true,  true},
     /* SRC_PARAMS     */ {"source_params.h",     "rat_src_params_sample",      nullptr,             false,    false, false, false, true},
     /* SRC_SOBOL      */ {"source_sobol.h",      "rat_src_sobol_rollout",      nullptr,             false,    true,  false, false, true},
+    /* SRC_ADJOINT    */ {"source_adjoint.h",    "rat_src_adjoint",            nullptr,             false,    true,  false, false, false},
 };
 
 const SrcKindRow &src_kind(SrcKind kind) { return k_kinds[kind]; }

@@ -19,6 +19,7 @@ enum SrcKind {
     SRC_RARE_USER,       // SRC_RARE with entry `event` of rat_user_event for the margin (rat_policy_rare_event_user)
     SRC_PARAMS,          // the user's rat_user_params alone (rat_policy_params_sample)
     SRC_SOBOL,           // SRC_USER_NOISE's rollout with every draw picked from one of two streams (rat_policy_sobol)
+    SRC_ADJOINT,         // the adjoint sweep on replayed trajectories (rat_policy_gradient, rat_policy_tail_gradient)
     SRC_NKIND
 };
 // One row per kind: what its translation unit is made of and what the module exports.  Every kind is the user's text behind

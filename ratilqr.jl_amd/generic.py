@@ -229,6 +229,12 @@ class GenericContext(il.Context):
     def policy_sobol(self, *a, **k):
         self._carrier_only("policy_sobol")
 
+    def policy_gradient(self, *a, **k):
+        self._carrier_only("policy_gradient")
+
+    def policy_tail_gradient(self, *a, **k):
+        self._carrier_only("policy_tail_gradient")
+
     def policy_tail_events(self, *a, **k):
         self._carrier_only("policy_tail_events")
 

@@ -358,6 +358,7 @@ class Context:
                                                     C.c_uint64(noise.seed), nv.P(th) if th.size else None, C.c_int32(th.size), nv.P(stats),
                                                     nv.P(risk) if th.size else None, nv.P(se) if th.size else None, nv.P(costs), nv.P(x),
                                                     nv.P(u)))
+        self._noise_open_loop = L is None                             # (policy_gradient returns grad_L None for it)
         return dict(n_ok=int(stats[nv.MC_N_OK]), n_domain=int(stats[nv.MC_N_DOMAIN]), mean=float(stats[nv.MC_MEAN]),
                     var=float(stats[nv.MC_VAR]), min=float(stats[nv.MC_MIN]), max=float(stats[nv.MC_MAX]),
                     se_mean=float(stats[nv.MC_SE_MEAN]), risk=risk, risk_se=se, costs=costs, x=x, u=u)
@@ -535,6 +536,47 @@ class Context:
         nv.check(nv.lib().rat_policy_tail_trajectory(self.h, nv.P(al) if al.size else None, C.c_int32(al.size), nv.P(rows), nv.P(mean), nv.P(cov)))
         r = self._tail_part(rows)
         r.update(self._unpack_trajectory(mean, cov))
+        return r
+
+    def _gradient_out(self, R):
+        n, m, N = self.n, self.m, self.N
+        return np.zeros((R, N, m)), np.zeros((R, N, n, m)), np.zeros((R, N, m)), C.c_int64(0)
+
+    def _gradient_part(self, gl, gL, se, nf):
+        open_loop = getattr(self, "_noise_open_loop", False)
+        return dict(grad_l=gl, grad_L=None if open_loop else gL.transpose(0, 1, 3, 2).copy(), grad_l_se=se, n_nonfinite=int(nf.value))
+
+    def policy_gradient(self, kl_bounds=(), thetas=()):
+        """Which way to move the policy (rat_policy_gradient): the gradient with respect to l and L of the mean cost (theta = 0), of the
+        entropic risk of each theta and of the KL-robust bound of each radius (at its theta*, envelope theorem), by adjoint replay of the
+        last policy_evaluate_noise of this context on the device (source problems, device generator, the affine law).  Returns
+        {"bounds": part, "thetas": part}; a part carries policy_worst_case's row keys and, with R rows, grad_l (R, N, m), grad_L
+        (R, N, m, n) (None after an open-loop evaluation), grad_l_se (R, N, m), the self-normalised standard error of grad_l, and
+        n_nonfinite, the rollouts left out because their sensitivities hold a NaN or Inf.  The disturbances are held fixed (a sampler that
+        reads x or u is not differentiated through), x_nom is not differentiated, a saturated row is a subgradient."""
+        d = nv.f64(np.atleast_1d(np.asarray(kl_bounds, dtype=np.float64))).ravel()
+        th = nv.f64(np.atleast_1d(np.asarray(thetas, dtype=np.float64))).ravel()
+        R = d.size + th.size
+        rows = np.zeros((R, nv.WC_NSTAT))
+        gl, gL, se, nf = self._gradient_out(R)
+        nv.check(nv.lib().rat_policy_gradient(self.h, nv.P(d) if d.size else None, C.c_int32(d.size), nv.P(th) if th.size else None,
+                                              C.c_int32(th.size), nv.P(rows), nv.P(gl), nv.P(gL), nv.P(se), C.byref(nf)))
+        full = self._gradient_part(gl, gL, se, nf)
+
+        def moments(sl, r):
+            return {k: (v[sl].copy() if isinstance(v, np.ndarray) else v) for k, v in full.items()}
+        return self._wc_parts(rows, d.size, moments)
+
+    def policy_tail_gradient(self, alphas):
+        """The gradient of CVaR_alpha with respect to l and L per level (rat_policy_tail_gradient): policy_gradient under the tail
+        distribution of policy_tail_risk (alpha = 0 is the mean).  Returns one dict: policy_tail_risk's row keys and grad_l, grad_L,
+        grad_l_se, n_nonfinite as policy_gradient's parts carry them."""
+        al, rows = self._tail_rows(alphas)
+        gl, gL, se, nf = self._gradient_out(al.size)
+        nv.check(nv.lib().rat_policy_tail_gradient(self.h, nv.P(al) if al.size else None, C.c_int32(al.size), nv.P(rows), nv.P(gl), nv.P(gL),
+                                                   nv.P(se), C.byref(nf)))
+        r = self._tail_part(rows)
+        r.update(self._gradient_part(gl, gL, se, nf))
         return r
 
     def policy_tail_disturbance(self, alphas, cross=True):
