@@ -568,6 +568,48 @@ rat_rc rat_policy_tail_gradient(rat_handle h, const double *alpha, int32_t n_alp
  * does not compile, or one without RAT_USER_NOISE: RAT_ERR_ARG with the compiler's log), and RAT_ERR_UNSUPPORTED for a source that defines
  * RAT_USER_POLICY. */
 rat_rc rat_policy_gradient_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms);
+/* How a risk reacts to the model: the gradient of the same functionals -- the mean cost, the entropic risk of a theta row, the KL-robust
+ * bound of a kl_bound row (at theta*, envelope theorem), CVaR_alpha of a level -- with respect to the model's parameters p and to the
+ * initial state x_0, by the same adjoint replay.  The source opts in: it defines RAT_USER_PARAMS_AD and templates rat_user_f, rat_user_c
+ * and rat_user_h on a second type for the parameters,
+ *   template <class T, class P> __device__ void rat_user_f(const T *x, const T *u, T *xn, const P *p);
+ *   template <class T, class P> __device__ T    rat_user_c(int k, const T *x, const T *u, const P *p);
+ *   template <class T, class P> __device__ T    rat_user_h(const T *x, const P *p);
+ * (rat_user_noise, rat_user_policy, rat_user_params, rat_user_event and rat_user_f_jacobian keep const double *p).  Every other kernel
+ * calls the three with p as double, so P deduces to double and such a source serves every other call unchanged.  Per replayed rollout k,
+ * with lambda and g_t as rat_policy_gradient has them:
+ *   gp       = h_p(x_N) + sum_t ( c_p(t, x_t, u_t) + f_p(x_t, u_t)' lambda_{t+1} )      (dJ_k / dp)
+ *   lambda_0 = (x part of g_0) + L_0' gu_0                                               (dJ_k / dx_0; open loop: the x part alone)
+ *   grad_p = sum y_k gp^k / sum y_k,      grad_x0 = sum y_k lambda_0^k / sum y_k
+ * with f_p, c_p, h_p by rat_ad.h's forward mode with p seeded (f_p always from rat_user_f, also where RAT_USER_F_JACOBIAN serves f_x, f_u).
+ * What this is and is not:
+ *   - The noise and the controller are FROZEN: the recorded w_t are held fixed, so a rat_user_noise that scales with a parameter is not
+ *     differentiated through, and the law u = l + L (x - x_nom) is a constant -- x_nom and (l, L) do not move with p or x_0.
+ *   - grad_x0 answers "the law stays centred on x_nom_0, the true initial state is off by delta": with the loop closed the feedback reacts
+ *     to the error; open loop it is the plain shift of x_0.
+ *   - theta* of a kl_bound row is not differentiated (envelope theorem); a saturated row is a SUBGRADIENT.
+ *   - With parameter sampling on (rat_policy_params_sampling) every rollout is differentiated at its own drawn q: grad_p is the
+ *     derivative with respect to a common additive shift of every rollout's drawn parameters, the local counterpart of cov_qJ of
+ *     rat_policy_worst_case_params.  rat_user_params itself is not differentiated.
+ *   rows_out        as rat_policy_worst_case_trajectory's / rat_policy_tail_trajectory's, bit for bit
+ *   grad_p_out      [rows][n_params], or NULL if grad_x0_out is not
+ *   grad_x0_out     [rows][n], or NULL if grad_p_out is not
+ *   grad_p_se_out, grad_x0_se_out   the same shapes or NULL: the self-normalised standard errors, formed as rat_policy_gradient's grad_l_se
+ *   n_nonfinite_out  or NULL: rollouts that have a cost but a NaN or Inf in h_x, some g_t, h_p or some parameter term; they are left out
+ *                   of every sum and of the denominator; the rows still count them.  The call returns RAT_OK.
+ * Dead rows are NaN; fixed summation order, no floating-point atomics; the replay guard, "no evaluation yet" and the row validation are
+ * rat_policy_gradient's.  RAT_ERR_UNSUPPORTED, each message naming its reason: the LQ / power-law families and general sizes; a source
+ * without RAT_USER_PARAMS_AD; a source that defines RAT_USER_POLICY; n_params above 32; n_params == 0 together with grad_p_out != NULL.
+ * RAT_ERR_ARG with the compiler's log: a source that defines RAT_USER_PARAMS_AD but whose functions do not take const P *.
+ * rat_policy_gradient and rat_policy_tail_gradient are unchanged, their refusal of parameter sampling included. */
+rat_rc rat_policy_param_gradient(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                 double *rows_out, double *grad_p_out, double *grad_p_se_out, double *grad_x0_out, double *grad_x0_se_out,
+                                 int64_t *n_nonfinite_out);
+rat_rc rat_policy_tail_param_gradient(rat_handle h, const double *alpha, int32_t n_alpha, double *rows_out, double *grad_p_out,
+                                      double *grad_p_se_out, double *grad_x0_out, double *grad_x0_se_out, int64_t *n_nonfinite_out);
+/* Compile only, for gfx950 (no device needed), the adjoint kernel of the two calls above for n_params parameters (0 .. 32), sampling off.
+ * rat_policy_gradient_check's codes; RAT_ERR_UNSUPPORTED also for a source without RAT_USER_PARAMS_AD and for n_params above 32. */
+rat_rc rat_policy_param_gradient_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms, int32_t n_params);
 /* Safety events of a policy: how often it hits an obstacle, leaves the lane or saturates an actuator -- under the nominal distribution q (a
  * theta = 0 row) and under the worst-case distribution p* ~ exp(theta* J) q of each kl_bound (and the tilt of each given theta), formed on
  * the device.  An event is a quadratic function of z_t = (x_t, u_t) in R^d, d = n + m, u_N = 0, watched over a window of steps:

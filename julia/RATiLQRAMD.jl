@@ -614,6 +614,51 @@ policy_gradient_check(source::AbstractString, n::Integer, m::Integer; normals_pe
     check(ccall((:rat_policy_gradient_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32), source, n, m, normals_per_step, uniforms_per_step))
 
 """
+policy_param_gradient(s; kl_bounds, thetas): how a risk reacts to the model (rat_policy_param_gradient).  The gradient with respect to the
+source problem's parameters p and to the initial state x_0 of the mean cost (θ = 0), of the entropic risk of each θ and of the KL-robust
+bound of each radius (at its θ*), by adjoint replay of the last evaluate_policy under the source's own noise on this solver's handle.  The
+source defines RAT_USER_PARAMS_AD: rat_user_f, rat_user_c, rat_user_h templated on the parameters' type.  Returns (bounds, thetas): each
+a named tuple of policy_worst_case's row vectors and, with R rows and P = length(problem.params), grad_p and grad_p_se (P, R), grad_x0 and
+grad_x0_se (n, R), n_nonfinite.  Noise and controller are frozen, θ* is not differentiated, and with parameter sampling on every rollout is
+differentiated at its own drawn q.
+"""
+function policy_param_gradient(s::ILEQGSolver; kl_bounds=Float64[], thetas=Float64[])
+    h = s.h
+    n, m, N = dims(h.problem)
+    P = hasproperty(h.problem, :params) ? length(h.problem.params) : 0
+    d = collect(Float64, kl_bounds); th = collect(Float64, thetas)
+    nb, nt = length(d), length(th); R = nb + nt
+    rows = zeros(8, R); gp = zeros(P, R); gps = zeros(P, R); gx = zeros(n, R); gxs = zeros(n, R); nf = Ref{Int64}(0)
+    check(ccall((:rat_policy_param_gradient, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, nb > 0 ? d : C_NULL, nb, nt > 0 ? th : C_NULL, nt, rows, P > 0 ? gp : C_NULL, P > 0 ? gps : C_NULL, gx, gxs, nf))
+    part(r) = (theta=rows[1, r], kl=rows[2, r], bound=rows[3, r], bound_se=rows[4, r], tilt_mean=rows[5, r], tilt_var=rows[6, r],
+               ess=rows[7, r], flag=Int.(rows[8, r]), grad_p=gp[:, r], grad_p_se=gps[:, r], grad_x0=gx[:, r], grad_x0_se=gxs[:, r], n_nonfinite=nf[])
+    (bounds=part(1:nb), thetas=part(nb+1:R))
+end
+
+"""
+policy_tail_param_gradient(s; alphas): the gradient of CVaR_α with respect to p and x_0 per level (rat_policy_tail_param_gradient):
+policy_param_gradient under the tail distribution of policy_tail_risk (α = 0 is the mean).  Returns a named tuple of policy_tail_risk's row
+vectors and grad_p, grad_p_se (P, R), grad_x0, grad_x0_se (n, R), n_nonfinite.
+"""
+function policy_tail_param_gradient(s::ILEQGSolver; alphas=Float64[])
+    h = s.h
+    n, m, N = dims(h.problem)
+    P = hasproperty(h.problem, :params) ? length(h.problem.params) : 0
+    al = collect(Float64, alphas); R = length(al)
+    rows = zeros(8, R); gp = zeros(P, R); gps = zeros(P, R); gx = zeros(n, R); gxs = zeros(n, R); nf = Ref{Int64}(0)
+    check(ccall((:rat_policy_tail_param_gradient, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, R > 0 ? al : C_NULL, R, rows, P > 0 ? gp : C_NULL, P > 0 ? gps : C_NULL, gx, gxs, nf))
+    merge(tail_rows(rows, 1:R), (grad_p=gp, grad_p_se=gps, grad_x0=gx, grad_x0_se=gxs, n_nonfinite=nf[]))
+end
+
+"policy_param_gradient_check(source, n, m; normals_per_step, uniforms_per_step, n_params): compile the adjoint kernel of policy_param_gradient only (rat_policy_param_gradient_check)"
+policy_param_gradient_check(source::AbstractString, n::Integer, m::Integer; normals_per_step::Integer=0, uniforms_per_step::Integer=0, n_params::Integer=0) =
+    check(ccall((:rat_policy_param_gradient_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32, Int32), source, n, m, normals_per_step, uniforms_per_step, n_params))
+
+"""
 policy_tail_disturbance(s; alphas, cross): what the noise of the tail looks like (rat_policy_tail_disturbance):
 policy_worst_case_disturbance's moments over the worst (1 − α) share of the rollouts per level.  Returns a named tuple of
 policy_tail_risk's row vectors and, with R levels, mean_w (n, N, R), cov_w (n, n, N, R) and, with cross, cov_wx (n, n, N, R) and cov_wu
@@ -1794,7 +1839,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_gradient, policy_tail_gradient, policy_gradient_check, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, policy_tail_events, policy_tail_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, rare_event_probability_params, rare_event_params_check, SobolGroup, policy_sobol, policy_sobol_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_gradient, policy_tail_gradient, policy_gradient_check, policy_param_gradient, policy_tail_param_gradient, policy_param_gradient_check, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, policy_tail_events, policy_tail_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, rare_event_probability_params, rare_event_params_check, SobolGroup, policy_sobol, policy_sobol_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

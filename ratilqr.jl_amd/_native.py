@@ -108,6 +108,7 @@ EXPORTS = [
     "rat_policy_tail_events", "rat_policy_tail_events_user",
     "rat_policy_sobol", "rat_policy_sobol_check",
     "rat_policy_gradient", "rat_policy_tail_gradient", "rat_policy_gradient_check",
+    "rat_policy_param_gradient", "rat_policy_tail_param_gradient", "rat_policy_param_gradient_check",
 ]
 MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 WC_SLOTS = ("theta", "kl", "bound", "bound_se", "tilt_mean", "tilt_var", "ess", "flag")      # RAT_WC_* slots of the header, in order
@@ -196,6 +197,9 @@ def lib():
         _lib.rat_policy_gradient.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]
         _lib.rat_policy_tail_gradient.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]
         _lib.rat_policy_gradient_check.argtypes = [C.c_char_p] + [C.c_int32] * 4
+        _lib.rat_policy_param_gradient.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]
+        _lib.rat_policy_tail_param_gradient.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]
+        _lib.rat_policy_param_gradient_check.argtypes = [C.c_char_p] + [C.c_int32] * 5
     return _lib
 
 
@@ -301,6 +305,13 @@ def policy_gradient_check(source, n, m, normals_per_step=0, uniforms_per_step=0)
     """rat_policy_gradient_check: compile the adjoint kernel of rat_policy_gradient / rat_policy_tail_gradient only (gfx950, no device
     needed); raises RatError with the compiler's log, or saying that the source defines RAT_USER_POLICY (RAT_ERR_UNSUPPORTED)."""
     check(lib().rat_policy_gradient_check(str(source).encode(), int(n), int(m), int(normals_per_step), int(uniforms_per_step)))
+
+
+def policy_param_gradient_check(source, n, m, normals_per_step=0, uniforms_per_step=0, n_params=0):
+    """rat_policy_param_gradient_check: compile the adjoint kernel of rat_policy_param_gradient / rat_policy_tail_param_gradient only
+    (gfx950, no device needed) for n_params parameters; raises RatError with the compiler's log, or saying that the source lacks
+    RAT_USER_PARAMS_AD, defines RAT_USER_POLICY or has more than 32 parameters (RAT_ERR_UNSUPPORTED)."""
+    check(lib().rat_policy_param_gradient_check(str(source).encode(), int(n), int(m), int(normals_per_step), int(uniforms_per_step), int(n_params)))
 
 
 def pets_set_source(h, prob):

@@ -42,7 +42,7 @@ void rat_set_error(const char *msg) { g_err = msg; }          // (multi.cpp repo
 
 struct EvRec { hipEvent_t a, b; int kind; int64_t ntraj; };
 // a lazily compiled source kernel of the handle and the shape its module was compiled for (fn == NULL: empty)
-struct SrcSlot { hipModule_t mod = nullptr; hipFunction_t fn = nullptr; int npn = 0, npu = 0, nev = 0, npar = 0, ppn = 0, ppu = 0, pshift = 0; };
+struct SrcSlot { hipModule_t mod = nullptr; hipFunction_t fn = nullptr; int npn = 0, npu = 0, nev = 0, npar = 0, ppn = 0, ppu = 0, pshift = 0, nap = 0; };
 
 struct rat_handle_s {
     int device = 0;
@@ -275,6 +275,12 @@ struct rat_handle_s {
     int *d_pg_bad = nullptr; size_t cap_pg_bad = 0;          // [chunk] rollouts with a cost but non-finite sensitivities
     double *d_pg_part = nullptr; size_t cap_pg_part = 0;     // [rows][N][WT_SLOTS][PG_PART] partials
     double *d_pg_out = nullptr; size_t cap_pg_out = 0;       // grad_l | grad_L | grad_l_se | S0, sum y^2 per row | mismatch count | non-finite count
+    // the parameter gradient (rat_policy_param_gradient / rat_policy_tail_param_gradient, source_adjoint_params.h and policy_mc.hip), the
+    // same ride with the SRC_ADJOINT_P kernel; d_pg_bad serves both
+    double *d_ppg_gp = nullptr; size_t cap_ppg_gp = 0;       // [chunk][32] dJ_k / dp staging
+    double *d_ppg_l0 = nullptr; size_t cap_ppg_l0 = 0;       // [chunk][12] dJ_k / dx_0 staging
+    double *d_ppg_part = nullptr; size_t cap_ppg_part = 0;   // [rows][WT_SLOTS][PPG_PART] partials
+    double *d_ppg_out = nullptr; size_t cap_ppg_out = 0;     // grad_p | grad_p_se | grad_x0 | grad_x0_se | S0, sum y^2 per row | mismatch count | non-finite count
 };
 
 extern "C" int32_t rat_version(void) { return RAT_VERSION; }
@@ -469,6 +475,7 @@ extern "C" void rat_destroy(rat_handle h) {
     for (void *q : {(void *)h->d_re_in, (void *)h->d_re_margin, (void *)h->d_re_logw, (void *)h->d_re_dom, (void *)h->d_re_part, (void *)h->d_re_red}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_sb_in, (void *)h->d_sb_y, (void *)h->d_sb_ok, (void *)h->d_sb_red}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_pg_gu, (void *)h->d_pg_bad, (void *)h->d_pg_part, (void *)h->d_pg_out}) if (q) (void)hipFree(q);
+    for (void *q : {(void *)h->d_ppg_gp, (void *)h->d_ppg_l0, (void *)h->d_ppg_part, (void *)h->d_ppg_out}) if (q) (void)hipFree(q);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
     if (h->h_pcost) (void)hipHostFree(h->h_pcost);
@@ -867,12 +874,12 @@ static rat_rc src_args_ok(const char *who, SrcKind kind, int n, int m, int npn, 
 // the rat_*_check entry points: whether `source` would be accepted as `kind`, compiled for gfx950 without a device
 // (npar > 0: with parameter sampling on for npar parameters, ppn normals and ppu uniforms per rollout -- what params_args_ok accepted)
 static rat_rc src_check(const char *who, SrcKind kind, const char *source, int n, int m, int npn = 0, int npu = 0, int nev = 0, int npar = 0,
-                        int ppn = 0, int ppu = 0, int pshift = 0) {
+                        int ppn = 0, int ppu = 0, int pshift = 0, int nap = 0) {
     if (!source) return fail(RAT_ERR_ARG, "null");
     rat_rc rc = src_args_ok(who, kind, n, m, npn, npu, nev);
     if (rc) return rc;
     std::string log;
-    if ((rc = src_compile(kind, source, n, m, SrcShape{npn, npu, nev, npar, ppn, ppu, pshift}, "gfx950", nullptr, &log))) return fail(rc, log);
+    if ((rc = src_compile(kind, source, n, m, SrcShape{npn, npu, nev, npar, ppn, ppu, pshift, nap}, "gfx950", nullptr, &log))) return fail(rc, log);
     return RAT_OK;
 }
 
@@ -914,13 +921,14 @@ static rat_rc src_kernel(rat_handle h, SrcKind kind, SrcShape shape, const char 
     SrcSlot &s = h->src_slot[kind];
     const bool ps = src_kind(kind).param_draws && h->ps_on;
     shape.npar = ps ? (int)h->src_np : 0; shape.ppn = ps ? h->ps_pn : 0; shape.ppu = ps ? h->ps_pu : 0;
+    shape.nap = src_kind(kind).params_ad ? (int)h->src_np : 0;
     if (!s.fn || s.npn != shape.npn || s.npu != shape.npu || s.nev != shape.nev || s.npar != shape.npar || s.ppn != shape.ppn ||
-        s.ppu != shape.ppu || s.pshift != shape.pshift) {
+        s.ppu != shape.ppu || s.pshift != shape.pshift || s.nap != shape.nap) {
         std::shared_ptr<const std::vector<char>> code;
         std::string log;
         rat_rc rc;
         if ((rc = src_compile(kind, h->src_text.c_str(), h->n, h->m, shape, h->src_arch_name, &code, &log))) return fail(rc, log);
-        SrcSlot fresh{nullptr, nullptr, shape.npn, shape.npu, shape.nev, shape.npar, shape.ppn, shape.ppu, shape.pshift};
+        SrcSlot fresh{nullptr, nullptr, shape.npn, shape.npu, shape.nev, shape.npar, shape.ppn, shape.ppu, shape.pshift, shape.nap};
         if ((rc = load_module_function(code, src_kind(kind).entry, who, &fresh.mod, &fresh.fn))) return rc;
         if (s.mod) {
             HIPCHK(hipStreamSynchronize(h->stream));
@@ -3064,6 +3072,118 @@ extern "C" rat_rc rat_policy_tail_gradient(rat_handle h, const double *alpha, in
     if ((rc = replay_validate_handle(h, F, "rat_policy_tail_risk"))) return rc;
     return replay_gradient(h, F, "rat_policy_tail_gradient", replay_tail(alpha, n_alpha), rows_out, grad_l_out, grad_L_out, grad_l_se_out,
                            n_nonfinite_out);
+}
+
+// ---- how a risk reacts to the model: rat_policy_param_gradient and rat_policy_tail_param_gradient ---------------------------------------------
+// The gradient of a row's functional with respect to the model's parameters p and the initial state x_0, by the same adjoint replay:
+// behind each chunk rat_src_adjoint_p (source_adjoint_params.h, a hiprtc module of its own that the first call compiles for the
+// problem's parameter count) sweeps every rollout backwards into d_ppg_gp and d_ppg_l0, then ppg_moments of policy_mc.hip; one enqueue
+// chain, one host wait.
+// a compile that failed on one of the header's own refusals (rat_user_policy, no RAT_USER_PARAMS_AD) is RAT_ERR_UNSUPPORTED
+static rat_rc param_gradient_compile_rc(rat_rc rc) {
+    if (rc == RAT_ERR_ARG && g_err.find("the source does not define RAT_USER_PARAMS_AD") != std::string::npos) return RAT_ERR_UNSUPPORTED;
+    return gradient_compile_rc(rc);
+}
+
+static rat_rc param_gradient_count_ok(const std::string &F, int64_t n_params) {
+    if (n_params < 0) return fail(RAT_ERR_ARG, F + "n_params must not be negative");
+    if (n_params > 32)
+        return fail(RAT_ERR_UNSUPPORTED, F + "n_params = " + std::to_string(n_params) + " is above 32 (a team of sixteen lanes seeds two tiles of sixteen directions)");
+    return RAT_OK;
+}
+
+extern "C" rat_rc rat_policy_param_gradient_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms, int32_t n_params) {
+    rat_rc rc;
+    if ((rc = param_gradient_count_ok("rat_policy_param_gradient_check: ", n_params))) return rc;
+    return param_gradient_compile_rc(src_check("rat_policy_param_gradient_check", SRC_ADJOINT_P, source, n, m, normals, uniforms, 0, 0, 0, 0, 0, n_params));
+}
+
+// what either call refuses before the row arguments are looked at
+static rat_rc param_gradient_ready(rat_handle h, const std::string &F, const double *grad_p_out) {
+    if (!h) return fail(RAT_ERR_ARG, F + "null handle");
+    if (!h->have_problem) return fail(RAT_ERR_NO_PROBLEM, "rat_problem_set was not called");
+    if (h->wide || h->pb.model != RAT_MODEL_SOURCE)
+        return fail(RAT_ERR_UNSUPPORTED, F + "the gradient differentiates the user's f, c and h with rat_ad.h, which the LQ / power-law families and "
+                                         "general sizes do not go through: write the model as source (rat_problem_set_source) and evaluate "
+                                         "with rat_policy_evaluate_noise");
+    rat_rc rc;
+    if ((rc = param_gradient_count_ok(F, h->src_np))) return rc;
+    if (h->src_np == 0 && grad_p_out)
+        return fail(RAT_ERR_UNSUPPORTED, F + "the problem has no parameters (n_params = 0): there is no grad_p; pass grad_p_out = NULL for grad_x0 alone");
+    return RAT_OK;
+}
+
+// (rs.tail(): rat_policy_tail_param_gradient, as replay_trajectory serves rat_policy_tail_trajectory; fn: the call's name)
+static rat_rc replay_param_gradient(rat_handle h, const std::string &F, const char *fn, const ReplaySpec &rs, double *rows_out, double *grad_p_out,
+                                    double *grad_p_se_out, double *grad_x0_out, double *grad_x0_se_out, int64_t *n_nonfinite_out) {
+    rat_rc rc;
+    const rat_handle_s::McReplay rec = h->mc_rec;
+    const int n = h->n, N = h->N, nrows = rs.nrows(), P = (int)h->src_np;
+    HIPCHK(hipSetDevice(h->device));
+    hipFunction_t kadj = nullptr;
+    if ((rc = src_kernel(h, SRC_ADJOINT_P, SrcShape{rec.npn, rec.npu, 0}, fn, &kadj))) return param_gradient_compile_rc(rc);
+    const int64_t chunk = mc_chunk(rec.K);
+    const size_t o_gp = 0, o_gps = o_gp + (size_t)nrows * P, o_gx = o_gps + (size_t)nrows * P, o_gxs = o_gx + (size_t)nrows * n,
+                 o_ess = o_gxs + (size_t)nrows * n, o_cnt = o_ess + 2 * (size_t)nrows, o_nf = o_cnt + 1, n_out = o_nf + 1,
+                 n_part = (size_t)nrows * WT_SLOTS * PPG_PART;
+    if ((rc = grow(&h->d_ppg_part, &h->cap_ppg_part, n_part))) return rc;
+    if ((rc = grow(&h->d_ppg_out, &h->cap_ppg_out, n_out))) return rc;
+    if ((rc = grow(&h->d_ppg_gp, &h->cap_ppg_gp, (size_t)chunk * 32))) return rc;
+    if ((rc = grow(&h->d_ppg_l0, &h->cap_ppg_l0, (size_t)chunk * 12))) return rc;
+    if ((rc = grow(&h->d_pg_bad, &h->cap_pg_bad, (size_t)chunk))) return rc;
+    HIPCHK(hipMemsetAsync(h->d_ppg_part, 0, n_part * 8, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_ppg_out + o_nf, 0, 8, h->stream));
+    PpgArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.gp = h->d_ppg_gp; pa.lam0 = h->d_ppg_l0; pa.bad = h->d_pg_bad; pa.P = P; pa.part = h->d_ppg_part;
+    pa.grad_p = h->d_ppg_out + o_gp; pa.grad_p_se = h->d_ppg_out + o_gps; pa.grad_x0 = h->d_ppg_out + o_gx; pa.grad_x0_se = h->d_ppg_out + o_gxs;
+    pa.ess = h->d_ppg_out + o_ess;
+    if ((rc = replay_chunks(h, rs, reinterpret_cast<int *>(h->d_ppg_out + o_cnt), pa.t,
+                            [&](const WtArgs &c, ReplayChunk ch) -> rat_rc {
+                                SrcAdjointPArgs sa;                   // the chunk's adjoints, behind its rollouts
+                                sa.xs = c.xs; sa.us = c.us; sa.N = N; sa.kc = (long)ch.kc; sa.cost = c.cost_re;
+                                sa.L = rec.has_L ? h->d_mc_in + rec.o_L : nullptr; sa.p = h->d_src_p;
+                                sa.j0 = (long)ch.k0; sa.seed = rec.seed; sa.zpn = h->d_ps_zn; sa.zpu = h->d_ps_zu;
+                                sa.gp = h->d_ppg_gp; sa.lam0 = h->d_ppg_l0; sa.bad = h->d_pg_bad;
+                                sa.n_bad = reinterpret_cast<int *>(h->d_ppg_out + o_nf);
+                                HIPCHK(launch_src(kadj, ch.kc, 4, h->stream, &sa));
+                                launch_ppg_chunk(pa, ch.live, h->stream);
+                                return RAT_OK;
+                            })))
+        return rc;
+    launch_ppg_final(pa, h->stream);
+    double nf_slot = 0.0;                                             // (the count is an int in a slot of the doubles)
+    if ((rc = replay_finish(h, F, rs.tail(), nrows, h->d_ppg_out, o_ess, 2, o_cnt,
+                            {{grad_p_out, o_gp, (size_t)nrows * P}, {grad_p_se_out, o_gps, (size_t)nrows * P}, {grad_x0_out, o_gx, (size_t)nrows * n},
+                             {grad_x0_se_out, o_gxs, (size_t)nrows * n}, {&nf_slot, o_nf, 1}},
+                            rows_out)))
+        return rc;
+    int nf = 0;
+    memcpy(&nf, &nf_slot, sizeof(int));
+    if (n_nonfinite_out) *n_nonfinite_out = nf;
+    return RAT_OK;
+}
+
+extern "C" rat_rc rat_policy_param_gradient(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
+                                            double *rows_out, double *grad_p_out, double *grad_p_se_out, double *grad_x0_out,
+                                            double *grad_x0_se_out, int64_t *n_nonfinite_out) {
+    const std::string F = "rat_policy_param_gradient: ";
+    rat_rc rc;
+    if ((rc = param_gradient_ready(h, F, grad_p_out))) return rc;
+    if ((rc = replay_validate(h, F, kl_bound, n_bound, theta, n_theta, rows_out && (grad_p_out || grad_x0_out)))) return rc;
+    return replay_param_gradient(h, F, "rat_policy_param_gradient", replay_kl(kl_bound, n_bound, theta, n_theta), rows_out, grad_p_out,
+                                 grad_p_se_out, grad_x0_out, grad_x0_se_out, n_nonfinite_out);
+}
+
+extern "C" rat_rc rat_policy_tail_param_gradient(rat_handle h, const double *alpha, int32_t n_alpha, double *rows_out, double *grad_p_out,
+                                                 double *grad_p_se_out, double *grad_x0_out, double *grad_x0_se_out, int64_t *n_nonfinite_out) {
+    const std::string F = "rat_policy_tail_param_gradient: ";
+    rat_rc rc;
+    if ((rc = replay_validate_alpha(F, alpha, n_alpha, rows_out && (grad_p_out || grad_x0_out)))) return rc;
+    if ((rc = param_gradient_ready(h, F, grad_p_out))) return rc;
+    if ((rc = replay_validate_handle(h, F, "rat_policy_tail_risk"))) return rc;
+    return replay_param_gradient(h, F, "rat_policy_tail_param_gradient", replay_tail(alpha, n_alpha), rows_out, grad_p_out, grad_p_se_out,
+                                 grad_x0_out, grad_x0_se_out, n_nonfinite_out);
 }
 
 // p' log(p' / p) + (1 - p') log((1 - p') / (1 - p)) for p <= p' < 1, 0 < p < 1, both logarithms through log1p of the difference: near

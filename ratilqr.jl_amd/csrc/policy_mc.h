@@ -265,6 +265,37 @@ struct PgArgs {
 void launch_pg_chunk(const PgArgs &a, const unsigned *live, hipStream_t s);
 void launch_pg_final(const PgArgs &a, hipStream_t s);
 
+// ---- rat_policy_param_gradient / rat_policy_tail_param_gradient: the gradient of a row's functional with respect to the model's parameters
+// and the initial state (policy_mc.hip) ---------------------------------------------------------------------------------------------------
+// The trajectory call's replay; behind each chunk rat_src_adjoint_p (source_adjoint_params.h, kind SRC_ADJOINT_P) writes per rollout
+// gp = dJ_k / dp ([kc][32], zero padded), lam0 = dJ_k / dx_0 ([kc][12], zero padded) and its flag bad [kc], and ppg_moments adds, per row,
+// the per-lane sums sum y v, sum y^2 v, sum y^2 v^2 of the three components a lane holds -- gp_i, gp_{16 + i} (TWO: more than sixteen
+// parameters) and lam0_i -- and per rollout lane sum y and sum y^2 over the rollouts whose sensitivities are finite.  A flagged rollout
+// is selected out at the load; the skeleton's own S0 and sum y^2 still count it.  A payload of moments_body without a C tile (no product
+// of two deviations is asked for): wcp_moments' one-step schedule (WT_SLOTS, WT_WAVES, WT_ROWS; dense, or the tail calls' liveness
+// schedule); ppg_final sums the slots in index order.
+#define PPG_PART 152          /* doubles per partial: 9 vectors [16] (component c, sum k at (3 c + k) * 16) | S0 | sum y^2 | the two over finite rollouts | padding */
+#define PPG_O_S0 144
+#define PPG_O_SY2 145
+#define PPG_O_SF 146
+#define PPG_O_SF2 147
+
+struct PpgArgs {
+    WtArgs t;                 // the replay's fields as wct_weights fills them (kc, cost, y, ldy, nrows, wc, n); the rest is not read
+    const double *gp;         // [kc][32] the staged parameter sensitivities of the chunk
+    const double *lam0;       // [kc][12] the staged initial-state sensitivities
+    const int *bad;           // [kc] the chunk's non-finite flags
+    int P;                    // parameters, 0 .. 32
+    double *part;             // [nrows][WT_SLOTS][PPG_PART]
+    // ppg_final only
+    double *grad_p, *grad_p_se;     // [nrows][P]
+    double *grad_x0, *grad_x0_se;   // [nrows][n]
+    double *ess;              // [nrows][2]: S0 and sum y^2
+};
+// one chunk, behind launch_wct_weights / launch_tlt_weights and the chunk's adjoints: the chunk's sums into the partials
+void launch_ppg_chunk(const PpgArgs &a, const unsigned *live, hipStream_t s);
+void launch_ppg_final(const PpgArgs &a, hipStream_t s);
+
 // ---- rat_policy_events: how often a policy violates quadratic constraints, under q and under every row's tilt (policy_mc.hip) ---------------
 // An event is g(t, z) = z' Q z + a' z + b of z = (x_t, u_t) in the 12 + 4 tile, watched over the steps t_lo .. t_hi.  Behind each replayed
 // chunk (after wct_weights) ev_eval forms, per rollout and event, the margin M = max g over the window, the first step tau with g > 0 and

@@ -1135,6 +1135,78 @@ __global__ __launch_bounds__(MC_THREADS) void pg_final(PgArgs a) {
     if (t == 0 && e == 0) { a.ess[2 * r] = S[PG_O_S0]; a.ess[2 * r + 1] = S[PG_O_SY2]; }
 }
 
+// ---- rat_policy_param_gradient / rat_policy_tail_param_gradient: per lane gp_i, gp_{16 + i} (TWO) and lam0_i, no product -------------------
+// A payload without a C tile: what is asked for is first and second moments of each component alone, which ride in the lanes as
+// GradientMoments' vectors do.  Component c of a lane puts sum y v, sum y^2 v, sum y^2 v^2 in vectors 3 c .. 3 c + 2; c = 0: gp_i,
+// c = 1: lam0_i, c = 2 (TWO): gp_{16 + i}.  A rollout flagged in bad is selected out at the load -- of all three and of the two scalar
+// sums -- so a NaN or Inf of its adjoint reaches nothing.
+template <bool TWO>
+struct ParamGradientMoments {
+    static constexpr int NC = TWO ? 3 : 2;
+    static constexpr int TILES = 0, VECS = 3 * NC, SCALARS = 4;
+    static __device__ __forceinline__ constexpr int o_tile(int) { return 0; }
+    static __device__ __forceinline__ constexpr int o_vec(int b) { return b * 16; }
+    static __device__ __forceinline__ constexpr int o_scalar(int s) { return PPG_O_S0 + s; }   // S0, sum y^2, and the two over finite rollouts
+    static __device__ __forceinline__ int batch() { return blockIdx.y; }
+    struct Dev { double V[NC]; bool fin; };
+    const PpgArgs &a;
+    const int i;
+    const bool comp0, compx, comp1;
+    __device__ __forceinline__ ParamGradientMoments(const PpgArgs &a_)
+        : a(a_), i(threadIdx.x & 15), comp0(i < a_.P), compx(i < a_.t.n && i < 12), comp1(TWO && 16 + i < a_.P) {}   // (padding lanes stay zero)
+    __device__ __forceinline__ double *part(int row, int slot) const { return a.part + ((size_t)row * WT_SLOTS + slot) * PPG_PART; }
+    __device__ __forceinline__ Dev load(long q, bool ok, double) const {
+        Dev d;
+        d.fin = ok && a.bad[q] == 0;
+        d.V[0] = (d.fin && comp0) ? a.gp[q * 32 + i] : 0.0;
+        d.V[1] = (d.fin && compx) ? a.lam0[q * 12 + i] : 0.0;
+        if constexpr (TWO) d.V[2] = (d.fin && comp1) ? a.gp[q * 32 + 16 + i] : 0.0;
+        return d;
+    }
+    template <class Tiles>
+    __device__ __forceinline__ void row(Tiles &, double (&v)[VECS], double (&s)[SCALARS], double y, bool has, const Dev &d) const {
+        const double yf = d.fin ? y : 0.0;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const double yv = has ? y * d.V[c] : 0.0;
+            v[3 * c] += yv;
+            v[3 * c + 1] += y * yv;
+            v[3 * c + 2] += yv * yv;
+        }
+        s[2] += yf;
+        s[3] += yf * yf;
+    }
+};
+
+template <bool TWO>
+__global__ __launch_bounds__(WT_WAVES * 64) void ppg_moments(PpgArgs a) { moments_body<ParamGradientMoments<TWO>, false>(ParamGradientMoments<TWO>(a), a.t, nullptr); }
+template <bool TWO>
+__global__ __launch_bounds__(WT_WAVES * 64) void tlpg_moments(PpgArgs a, const unsigned *live) { moments_body<ParamGradientMoments<TWO>, true>(ParamGradientMoments<TWO>(a), a.t, live); }
+
+// grad_p = sum y gp / sum y and grad_x0 = sum y lam0 / sum y over the rollouts with finite sensitivities, each with its self-normalised
+// standard error exactly as pg_final forms grad_l's: uncentred sums, clamped at 0, NaN for a dead row
+__global__ __launch_bounds__(MC_THREADS) void ppg_final(PpgArgs a) {
+    __shared__ double S[PPG_PART];
+    const int r = blockIdx.x, e = threadIdx.x, n = a.t.n, P = a.P;
+    slot_sum<PPG_PART>(a.part + (size_t)r * WT_SLOTS * PPG_PART, S);
+    const double nan = __builtin_nan("");
+    const bool dead = row_dead(a.t.wc, r);
+    const double sf = S[PPG_O_SF], sf2 = S[PPG_O_SF2];
+    if (e < P + n) {
+        const bool isp = e < P;
+        const int c = isp ? (e < 16 ? 0 : 2) : 1, i = isp ? (e & 15) : e - P;
+        const double s1 = S[(3 * c) * 16 + i], s2 = S[(3 * c + 1) * 16 + i], s3 = S[(3 * c + 2) * 16 + i];
+        const double mean = s1 / sf;
+        const double var = ((s3 - 2.0 * mean * s2) + mean * mean * sf2) / (sf * sf);
+        const double se = var > 0.0 ? sqrt(var) : (var != var ? nan : 0.0);
+        double *g = isp ? a.grad_p + (size_t)r * P + e : a.grad_x0 + (size_t)r * n + i;
+        double *gs = isp ? a.grad_p_se + (size_t)r * P + e : a.grad_x0_se + (size_t)r * n + i;
+        *g = dead ? nan : mean;
+        *gs = dead ? nan : se;
+    }
+    if (e == 0) { a.ess[2 * r] = S[PPG_O_S0]; a.ess[2 * r + 1] = S[PPG_O_SY2]; }
+}
+
 // ---- rat_policy_worst_case_params: one step, Dq = q - c_q in up to two tiles of sixteen parameters per lane ----------------------------------
 // Lane (i, kk) holds Dq_i (tile 0) and Dq_{16 + i} (tile 1, TWO) of rollout 4 g + kk.  Per group and row A0 = y Dq(tile 0), B0 = Dq(tile 0)
 // give block (0,0) of sum y Dq Dq'; with TWO, A0 and B1 give block (0,1) and A1, B1 block (1,1); block (1,0) is (0,1)' and is never
@@ -1708,6 +1780,17 @@ void launch_pg_chunk(const PgArgs &a, const unsigned *live, hipStream_t s) {
 
 void launch_pg_final(const PgArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(pg_final, dim3((unsigned)a.t.N, (unsigned)a.t.nrows), dim3(MC_THREADS), 0, s, a);
+}
+
+void launch_ppg_chunk(const PpgArgs &a, const unsigned *live, hipStream_t s) {
+    if (a.t.kc <= 0 || a.t.nrows <= 0) return;
+    const dim3 grid(WT_SLOTS, (unsigned)((a.t.nrows + WT_ROWS - 1) / WT_ROWS));
+    if (a.P > 16) launch_moments(ppg_moments<true>, tlpg_moments<true>, grid, a, live, s);
+    else launch_moments(ppg_moments<false>, tlpg_moments<false>, grid, a, live, s);
+}
+
+void launch_ppg_final(const PpgArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(ppg_final, dim3((unsigned)a.t.nrows), dim3(MC_THREADS), 0, s, a);
 }
 
 void launch_wcp_centre(const WpArgs &a, hipStream_t s) {

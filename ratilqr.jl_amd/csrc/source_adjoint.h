@@ -25,6 +25,7 @@
 #pragma once
 #include "rat_ad.h"
 #include "source_step.h"
+#include "source_adjoint_lanes.h"
 
 #ifndef RAT_USER_NOISE
 #error "the source does not define RAT_USER_NOISE: rat_policy_gradient replays rat_policy_evaluate_noise, which needs '#define RAT_USER_NOISE' and rat_user_noise(k, x, u, rng, w, p)"
@@ -33,17 +34,6 @@
 #error "the source defines RAT_USER_POLICY: rat_user_policy is not templated, so the control law is not differentiable by rat_ad.h (rat_policy_gradient serves the affine law alone)"
 #endif
 
-// the value lane `src` of the wavefront holds (no <hip/hip_runtime.h> under hiprtc): both halves through ds_bpermute
-__device__ __forceinline__ double adj_from(double v, int src) {
-    int w[2];
-    __builtin_memcpy(w, &v, 8);
-    w[0] = __builtin_amdgcn_ds_bpermute(src << 2, w[0]);
-    w[1] = __builtin_amdgcn_ds_bpermute(src << 2, w[1]);
-    double r;
-    __builtin_memcpy(&r, w, 8);
-    return r;
-}
-__device__ __forceinline__ bool adj_finite(double v) { return __builtin_fabs(v) < __builtin_inf(); }
 
 extern "C" __global__ __launch_bounds__(64) void rat_src_adjoint(SrcAdjointArgs a) {
 #ifdef RAT_USER_F_JACOBIAN

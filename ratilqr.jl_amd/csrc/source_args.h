@@ -168,3 +168,21 @@ struct SrcAdjointArgs {
     int *bad;                 // [kc] 1: the rollout has a cost but a NaN or Inf in its sensitivities; untouched for a rollout without a cost
     int *n_bad;               // the number of those rollouts, added to (an integer atomic: a count has no order)
 };
+
+// rat_src_adjoint_p (source_adjoint_params.h): rat_src_adjoint's sweep with the parameter pass and lambda_0 (rat_policy_param_gradient /
+// rat_policy_tail_param_gradient), the same team of sixteen lanes per rollout
+struct SrcAdjointPArgs {
+    const double *xs, *us;    // staged trajectories of the chunk: [kc][N+1][RAT_N], [kc][N][RAT_M] dense
+    int N;
+    long kc;                  // rollouts of the chunk
+    const double *cost;       // [kc] the costs the replay formed (NaN: DomainError, the rollout is passed over)
+    const double *L;          // [N][4][12] or null (open loop)
+    const double *p;          // the model's parameters
+    long j0;                  // global index of the chunk's first rollout (parameter sampling: the rollout's own q)
+    unsigned long long seed;  // the replayed evaluation's seed
+    const double *zpn, *zpu;  // the handle's injected parameter streams (whole, indexed by the global rollout), or both null: the generator
+    double *gp;               // [kc][32] dJ_k / dp, zero padded; untouched for a rollout without a cost
+    double *lam0;             // [kc][12] dJ_k / dx_0 with the loop closed, zero padded; untouched for a rollout without a cost
+    int *bad;                 // [kc] 1: the rollout has a cost but a NaN or Inf in its sensitivities; untouched for a rollout without a cost
+    int *n_bad;               // the number of those rollouts, added to (an integer atomic: a count has no order)
+};

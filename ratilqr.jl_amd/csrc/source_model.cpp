@@ -33,8 +33,8 @@ std::mutex g_mu;
 Rtc g_rtc;
 // key: (source, n, m, SrcKind, normals per step, uniforms per step, events of rat_user_event (0 where the kind takes none), parameters
 // drawn per rollout (0: sampling off) with their normals and uniforms, whether the parameter normals are shifted (0 where the kind has
-// no shifted proposal), architecture)
-std::map<std::tuple<std::string, int, int, int, int, int, int, int, int, int, int, std::string>, std::shared_ptr<const std::vector<char>>> g_cache;
+// no shifted proposal), the parameter count of a params_ad kind (0 elsewhere), architecture)
+std::map<std::tuple<std::string, int, int, int, int, int, int, int, int, int, int, int, std::string>, std::shared_ptr<const std::vector<char>>> g_cache;
 
 bool rtc_load(std::string *why) {           // (g_mu held)
     if (!g_rtc.tried) {
@@ -71,18 +71,19 @@ std::string src_arch(const char *gcn_arch_name) {
     return out.empty() ? std::string("gfx950") : out;
 }
 
-// indexed by SrcKind:  header                 entry                         entry2               rng_shift draws events rare_user_event param_draws
+// indexed by SrcKind:  header                 entry                         entry2               rng_shift draws events rare_user_event param_draws params_ad
 static const SrcKindRow k_kinds[SRC_NKIND] = {
-    /* SRC_MODEL      */ {"source_kernels.h",    "rat_src_rollout",            "rat_src_linearize", false,    false, false, false, false},
-    /* SRC_PETS       */ {"source_pets.h",       "rat_src_pets_rollout",       nullptr,             false,    true,  false, false, false},
-    /* SRC_NOISY      */ {"source_noisy.h",      "rat_src_noisy_rollout",      nullptr,             false,    false, false, false, false},
-    /* SRC_USER_NOISE */ {"source_user_noise.h", "rat_src_user_noisy_rollout", nullptr,             false,    true,  false, false, true},
-    /* SRC_RARE       */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  false, false, true},
-    /* SRC_EVENTS     */ {"source_events.h",     "rat_src_user_events",        nullptr,             false,    false, true,  false, true},
-    /* SRC_RARE_USER  */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  true,  true,  true},
-    /* SRC_PARAMS     */ {"source_params.h",     "rat_src_params_sample",      nullptr,             false,    false, false, false, true},
-    /* SRC_SOBOL      */ {"source_sobol.h",      "rat_src_sobol_rollout",      nullptr,             false,    true,  false, false, true},
-    /* SRC_ADJOINT    */ {"source_adjoint.h",    "rat_src_adjoint",            nullptr,             false,    true,  false, false, false},
+    /* SRC_MODEL      */ {"source_kernels.h",    "rat_src_rollout",            "rat_src_linearize", false,    false, false, false, false, false},
+    /* SRC_PETS       */ {"source_pets.h",       "rat_src_pets_rollout",       nullptr,             false,    true,  false, false, false, false},
+    /* SRC_NOISY      */ {"source_noisy.h",      "rat_src_noisy_rollout",      nullptr,             false,    false, false, false, false, false},
+    /* SRC_USER_NOISE */ {"source_user_noise.h", "rat_src_user_noisy_rollout", nullptr,             false,    true,  false, false, true,  false},
+    /* SRC_RARE       */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  false, false, true,  false},
+    /* SRC_EVENTS     */ {"source_events.h",     "rat_src_user_events",        nullptr,             false,    false, true,  false, true,  false},
+    /* SRC_RARE_USER  */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  true,  true,  true,  false},
+    /* SRC_PARAMS     */ {"source_params.h",     "rat_src_params_sample",      nullptr,             false,    false, false, false, true,  false},
+    /* SRC_SOBOL      */ {"source_sobol.h",      "rat_src_sobol_rollout",      nullptr,             false,    true,  false, false, true,  false},
+    /* SRC_ADJOINT    */ {"source_adjoint.h",    "rat_src_adjoint",            nullptr,             false,    true,  false, false, false, false},
+    /* SRC_ADJOINT_P  */ {"source_adjoint_params.h", "rat_src_adjoint_p",   nullptr,             false,    true,  false, false, true,  true},
 };
 
 const SrcKindRow &src_kind(SrcKind kind) { return k_kinds[kind]; }
@@ -92,7 +93,7 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
     const SrcKindRow &row = k_kinds[kind];
     const int npn = row.draws ? shape.npn : 0, npu = row.draws ? shape.npu : 0, nev = row.events ? shape.nev : 0;
     const int npar = row.param_draws ? shape.npar : 0, ppn = npar > 0 ? shape.ppn : 0, ppu = npar > 0 ? shape.ppu : 0;
-    const int pshift = row.rng_shift ? shape.pshift : 0;
+    const int pshift = row.rng_shift ? shape.pshift : 0, nap = row.params_ad ? shape.nap : 0;
     const auto t0 = std::chrono::steady_clock::now();
     auto done = [&](rat_rc rc) {
         if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -100,7 +101,7 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
     };
     std::lock_guard<std::mutex> lk(g_mu);
     if (cached) *cached = false;
-    const auto key = std::make_tuple(std::string(source), n, m, (int)kind, npn, npu, nev, npar, ppn, ppu, pshift, arch);
+    const auto key = std::make_tuple(std::string(source), n, m, (int)kind, npn, npu, nev, npar, ppn, ppu, pshift, nap, arch);
     auto it = g_cache.find(key);
     if (it != g_cache.end()) {
         if (code) *code = it->second;
@@ -132,6 +133,8 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
         opts.push_back("-DRAT_USER_PARAMS_ON=1");
         opts.push_back(dnp.c_str()); opts.push_back(dppn.c_str()); opts.push_back(dppu.c_str());
     }
+    const std::string dnap = "-DRAT_N_PARAMS=" + std::to_string(nap);
+    if (row.params_ad && npar == 0) opts.push_back(dnap.c_str());     // (with sampling on npar == nap is already there)
     if (pshift) opts.push_back("-DRAT_PARAM_SHIFT=1");
     if (kind == SRC_PARAMS) opts.push_back("-DRAT_PARAMS_SAMPLE_KERNEL=1");
     if (kind == SRC_SOBOL) opts.push_back("-DRAT_RNG_PICK=1");

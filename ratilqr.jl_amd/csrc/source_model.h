@@ -20,6 +20,7 @@ enum SrcKind {
     SRC_PARAMS,          // the user's rat_user_params alone (rat_policy_params_sample)
     SRC_SOBOL,           // SRC_USER_NOISE's rollout with every draw picked from one of two streams (rat_policy_sobol)
     SRC_ADJOINT,         // the adjoint sweep on replayed trajectories (rat_policy_gradient, rat_policy_tail_gradient)
+    SRC_ADJOINT_P,       // that sweep with the parameter pass and lambda_0 (rat_policy_param_gradient, rat_policy_tail_param_gradient)
     SRC_NKIND
 };
 // One row per kind: what its translation unit is made of and what the module exports.  Every kind is the user's text behind
@@ -28,7 +29,8 @@ enum SrcKind {
 // -DRAT_USER_PARAMS_ON=1 -DRAT_N_PARAMS=npar -DRAT_PARAM_NORMALS=ppn -DRAT_PARAM_UNIFORMS=ppu as well when the shape has npar > 0
 // (parameter sampling is on, rat_policy_params_sampling); with npar == 0 its command line is what it was without the feature.  The two
 // rng_shift kinds get -DRAT_PARAM_SHIFT=1 besides when the shape has pshift (rat_policy_rare_event_params: source_params.h).  SRC_SOBOL
-// alone gets -DRAT_RNG_PICK=1 (rat_rng.h, source_params.h: a second key and the masks that pick a draw's stream).
+// alone gets -DRAT_RNG_PICK=1 (rat_rng.h, source_params.h: a second key and the masks that pick a draw's stream).  A params_ad kind gets
+// -DRAT_N_PARAMS=nap, the problem's parameter count, whether or not sampling is on (with sampling on npar == nap).
 struct SrcKindRow {
     const char *header;          // embedded header with the kind's kernels
     const char *entry, *entry2;  // kernels the module exports (entry2: NULL but for SRC_MODEL's linearisation)
@@ -37,6 +39,7 @@ struct SrcKindRow {
     bool events;                 // takes nev: -DRAT_N_EVENT=nev (the source must define RAT_USER_EVENT)
     bool rare_user_event;        // -DRAT_RARE_USER_EVENT=1
     bool param_draws;            // takes npar, ppn, ppu: the kernels that call rat_user_params once per rollout (source_params.h)
+    bool params_ad;              // takes nap: the kernel seeds rat_dual[RAT_N_PARAMS] (the source must define RAT_USER_PARAMS_AD)
 };
 const SrcKindRow &src_kind(SrcKind kind);
 struct SrcShape {                                        // (fields a kind does not take are read as 0)
@@ -44,6 +47,7 @@ struct SrcShape {                                        // (fields a kind does 
     int npar = 0, ppn = 0, ppu = 0;                      // parameter sampling: RAT_N_PARAMS (0: off), parameter normals / uniforms per rollout
     int pshift = 0;                                      // 1: -DRAT_PARAM_SHIFT=1, the parameter normals are shifted too (rat_policy_rare_event_params);
                                                          // read by the rng_shift kinds alone (SRC_RARE, SRC_RARE_USER), which need npar > 0 with it
+    int nap = 0;                                         // the problem's parameter count, read by the params_ad kind alone (SRC_ADJOINT_P)
 };
 
 // Compiles `source` as `kind`.  RAT_OK: *code holds the code object (shared with the cache, which keys on source, n, m, kind, shape and

@@ -235,6 +235,12 @@ class GenericContext(il.Context):
     def policy_tail_gradient(self, *a, **k):
         self._carrier_only("policy_tail_gradient")
 
+    def policy_param_gradient(self, *a, **k):
+        self._carrier_only("policy_param_gradient")
+
+    def policy_tail_param_gradient(self, *a, **k):
+        self._carrier_only("policy_tail_param_gradient")
+
     def policy_tail_events(self, *a, **k):
         self._carrier_only("policy_tail_events")
 

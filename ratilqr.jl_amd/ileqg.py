@@ -579,6 +579,48 @@ class Context:
         r.update(self._gradient_part(gl, gL, se, nf))
         return r
 
+    def _param_gradient_out(self, R):
+        P = getattr(self, "params", np.zeros(0)).size
+        return np.zeros((R, P)), np.zeros((R, P)), np.zeros((R, self.n)), np.zeros((R, self.n)), C.c_int64(0)
+
+    def policy_param_gradient(self, kl_bounds=(), thetas=()):
+        """How a risk reacts to the model (rat_policy_param_gradient): the gradient with respect to the source problem's parameters p and
+        to the initial state x_0 of the mean cost (theta = 0), of the entropic risk of each theta and of the KL-robust bound of each
+        radius (at its theta*), by adjoint replay of the last policy_evaluate_noise of this context on the device.  The source defines
+        RAT_USER_PARAMS_AD (rat_user_f, rat_user_c, rat_user_h templated on the parameters' type).  Returns {"bounds": part, "thetas":
+        part}; a part carries policy_worst_case's row keys and, with R rows, grad_p and grad_p_se (R, n_params), grad_x0 and grad_x0_se
+        (R, n), and n_nonfinite.  Noise and controller are frozen (a sampler that scales with a parameter is not differentiated through;
+        x_nom and the law are constants), theta* is not differentiated, and with parameter sampling on every rollout is differentiated at
+        its own drawn q."""
+        d = nv.f64(np.atleast_1d(np.asarray(kl_bounds, dtype=np.float64))).ravel()
+        th = nv.f64(np.atleast_1d(np.asarray(thetas, dtype=np.float64))).ravel()
+        R = d.size + th.size
+        rows = np.zeros((R, nv.WC_NSTAT))
+        gp, gps, gx, gxs, nf = self._param_gradient_out(R)
+        has_p = gp.shape[1] > 0                                       # (no parameters: grad_x0 alone)
+        nv.check(nv.lib().rat_policy_param_gradient(self.h, nv.P(d) if d.size else None, C.c_int32(d.size), nv.P(th) if th.size else None,
+                                                    C.c_int32(th.size), nv.P(rows), nv.P(gp) if has_p else None,
+                                                    nv.P(gps) if has_p else None, nv.P(gx), nv.P(gxs), C.byref(nf)))
+        full = dict(grad_p=gp, grad_p_se=gps, grad_x0=gx, grad_x0_se=gxs, n_nonfinite=int(nf.value))
+
+        def moments(sl, r):
+            return {k: (v[sl].copy() if isinstance(v, np.ndarray) else v) for k, v in full.items()}
+        return self._wc_parts(rows, d.size, moments)
+
+    def policy_tail_param_gradient(self, alphas):
+        """The gradient of CVaR_alpha with respect to p and x_0 per level (rat_policy_tail_param_gradient): policy_param_gradient under the
+        tail distribution of policy_tail_risk (alpha = 0 is the mean).  Returns one dict: policy_tail_risk's row keys and grad_p,
+        grad_p_se, grad_x0, grad_x0_se, n_nonfinite as policy_param_gradient's parts carry them."""
+        al, rows = self._tail_rows(alphas)
+        gp, gps, gx, gxs, nf = self._param_gradient_out(al.size)
+        has_p = gp.shape[1] > 0
+        nv.check(nv.lib().rat_policy_tail_param_gradient(self.h, nv.P(al) if al.size else None, C.c_int32(al.size), nv.P(rows),
+                                                         nv.P(gp) if has_p else None, nv.P(gps) if has_p else None, nv.P(gx), nv.P(gxs),
+                                                         C.byref(nf)))
+        r = self._tail_part(rows)
+        r.update(dict(grad_p=gp, grad_p_se=gps, grad_x0=gx, grad_x0_se=gxs, n_nonfinite=int(nf.value)))
+        return r
+
     def policy_tail_disturbance(self, alphas, cross=True):
         """What the noise of the tail looks like (rat_policy_tail_disturbance): policy_worst_case_disturbance's moments over the worst
         (1 - alpha) share of the rollouts per level.  Returns one dict: policy_tail_risk's row keys and, with R levels, mean_w (R, N, n),
