@@ -11,7 +11,19 @@ Held: rows A and B bit for bit against rat_policy_evaluate_noise under seed_a / 
 bit for bit row A with S = T = 0 exactly; an all-draws group's row bit for bit row B; every row against the model to 1e-12 relative (what
 tests/test_gpu_user_params.py holds under the generator); indices, standard errors and summary against the model's math.fsum estimator
 on the device's own rows to 1e-9 absolute (the project's parity bound; the indices are O(1)); a shorter call returns the leading columns
-bit for bit; the closed forms of tests/test_cpu_sobol.py within 4 reported standard errors; every refusal of the header with its code."""
+bit for bit; the closed forms of tests/test_cpu_sobol.py within 4 reported standard errors; every refusal of the header with its code.
+
+Beyond those sizes (sections 9 .. 11; the bounds are the same 1e-12, 1e-9 and 4 standard errors):
+  9   the wide closed form of tests/sobol_model.py -- 64 draws of each of the four kinds, 32 parameters, N = 2 -- at K = 2^14 with the
+      sixteen groups of sobol_model.wide_groups(): bits 31, 32 and 63 of every word alone, Box-Muller block 16 of the step and of the
+      parameter normals cut in two, one mask with bits in both halves, the empty group at index 15 (variant 17); one group of all 256
+      bits; a 40-draw instantiation that refuses bit 40 and serves bit 39.  tests/test_cpu_sobol.py shows that each wrong reading of one of
+      those bits gives the model another row, at least 4e-2 of the row's largest entry away.
+  10  K = 65536 + 5, past the stride 256 x 256 of the reduction grid: the additive closed form, its calls at 65535 and 65536, and the
+      pendulum's "nan" hook with dropped base samples and survivors on both sides of 65536 (the model: sobol_model.pend_costs).
+  11  the "nan" hook at K = 64 with thresholds that leave 0, 1 and 2 base samples; the additive form about a mean of 10^4 standard
+      deviations (sobol_model.OFFSET_SOURCE), where test_cpu_sobol.large_mean_figures shows that an uncentred estimator is 8e+1 away from
+      fsum in S_se and a centred float64 one agrees with it."""
 import ctypes as C
 
 import numpy as np
@@ -327,3 +339,231 @@ def test_the_recorded_evaluation_survives_the_call():
             return np.array_equal(a, b, equal_nan=True)
         return a == b or (a != a and b != b)
     assert same(before_w, after_w) and same(before_t, after_t)
+
+
+# ---- 9. masks past bit 31: sixteen groups over all four words at 64 draws each ------------------------------------------------------------------
+WIDE_K = 1 << 14
+_WIDE = {}
+
+
+def wide_context(nd=sm.WIDE_D):
+    if nd not in _WIDE:
+        _WIDE[nd] = rat.Context(sm.wide_problem(nd))
+        _WIDE[nd].set_param_sampling(rat.ParamSampling(nd, nd))
+    return _WIDE[nd]
+
+
+def wide_run():
+    """the shared call of the wide closed form: the sixteen groups of sobol_model.wide_groups(), all rows (computed once, left unchanged)"""
+    if "run" not in _WIDE:
+        x, l, L = sm.wide_policy()
+        r = wide_context().policy_sobol(x, l, L, noise=rat.UserNoise(64, 64), groups=sm.wide_groups(), K=WIDE_K, seed_a=SEED0, seed_b=SEED0 + 1,
+                                        want_costs=True)
+        r["y"].setflags(write=False)
+        _WIDE["run"] = (r, sm.wide_model(WIDE_K, SEED0, SEED0 + 1))
+    return _WIDE["run"]
+
+
+def test_wide_rows_a_and_b_are_the_evaluations_with_every_bit_of_row_b_live():
+    r, _ = wide_run()
+    x, l, L = sm.wide_policy()
+    for row, seed in ((0, SEED0), (1, SEED0 + 1)):
+        e = wide_context().policy_evaluate_noise(x, l, L, noise=rat.UserNoise(64, 64, seed=seed), K=WIDE_K, want_costs=True)
+        assert np.array_equal(r["y"][row], e["costs"]), row
+    assert not np.array_equal(r["y"][0], r["y"][1])
+
+
+def test_wide_sixteen_groups_over_both_halves_of_all_four_words():
+    r, model = wide_run()
+    groups = sm.wide_groups()
+    var, exact = sm.wide_exact(groups)
+    scale = float(np.abs(model).max())
+    err = np.abs(r["y"] - model).max(axis=1) / scale
+    print(f"wide: rows against the model, the largest {err.max():.2e} of max |model| = {scale:.1f} (row {int(err.argmax())}); per row {np.array2string(err, precision=1)}")
+    assert r["y"].shape == model.shape == (18, WIDE_K) and err.max() <= 1e-12
+    assert np.array_equal(r["y"][17], r["y"][0])                      # the empty group, index 15: row A bit for bit
+    for key in ("S", "S_se", "T", "T_se"):
+        assert r[key][15] == 0.0, key
+    for i in range(17):                                               # A, B and the fifteen groups that hold a draw: seventeen different rows
+        for j in range(i):
+            assert not np.array_equal(r["y"][i], r["y"][j]), (i, j)
+    against_estimator(r, "wide")
+    assert r["names"] == [g.name for g in groups] and r["names"][0] == "pn31" and r["names"][15] == "empty"
+    assert r["n_ok"] == WIDE_K and r["flag"] == 0 and abs(r["var"] - var) <= 4.0 * r["var_se"]
+    worst = 0.0
+    for key in ("S", "T"):
+        for i in range(15):
+            dev = abs(r[key][i] - exact[i]) / r[key + "_se"][i]
+            worst = max(worst, dev)
+            print(f"wide: {key}[{i}] {groups[i].name} {r[key][i]:+.5f} +- {r[key + '_se'][i]:.5f} (exact {exact[i]:.5f}): {dev:.2f} sigma")
+            assert dev <= 4.0, (key, i)
+    print(f"wide: Var {r['var']:.3f} +- {r['var_se']:.3f} (exact {var}); the largest deviation {worst:.2f} sigma")
+
+
+def test_wide_one_group_of_all_two_hundred_and_fifty_six_bits_is_row_b():
+    base, _ = wide_run()
+    x, l, L = sm.wide_policy()
+    full = G(*[range(64)] * 4, name="all")
+    assert full.words == (sm.ALL,) * 4
+    r = wide_context().policy_sobol(x, l, L, noise=rat.UserNoise(64, 64), groups=[full], K=WIDE_K, seed_a=SEED0, seed_b=SEED0 + 1, want_costs=True)
+    assert np.array_equal(r["y"][0], base["y"][0]) and np.array_equal(r["y"][1], base["y"][1]) and np.array_equal(r["y"][2], r["y"][1])
+    against_estimator(r, "wide, one group of everything")
+    for key in ("S", "T"):                                            # everything frozen at once: both estimate 1
+        dev = abs(r[key][0] - 1.0) / r[key + "_se"][0]
+        print(f"wide, one group of everything: {key} {r[key][0]:.5f} +- {r[key + '_se'][0]:.5f}: {dev:.2f} sigma from 1")
+        assert dev <= 4.0 and r[key + "_se"][0] > 0.0
+    assert r["flag"] == 0 and r["names"] == ["all"]
+
+
+def test_a_count_of_forty_refuses_bit_forty_and_serves_bit_thirty_nine():
+    from types import SimpleNamespace
+    K, N = 256, sm.WIDE_N
+    ctx = wide_context(40)
+    c = SimpleNamespace(args=lambda closed: (np.zeros((N + 1, 1)), np.zeros((N, 1)), np.zeros((N, 1, 1))), K=K, npn=40, npu=40)
+    for k in range(4):
+        word = lambda b: tuple((1 << b) if j == k else 0 for j in range(4))
+        with pytest.raises(rat.RatError, match="RAT_ERR_ARG.*group 0 names a draw at or beyond the declared count \\(40\\)"):
+            raw(ctx, c, [word(40)], seeds=(SEED0, SEED0 + 1))
+        with pytest.raises(rat.RatError, match="RAT_ERR_ARG.*group 1 names a draw at or beyond the declared count \\(40\\)"):
+            raw(ctx, c, [word(39), word(63)], seeds=(SEED0, SEED0 + 1))
+        rc, index, summary = raw(ctx, c, [word(39)], seeds=(SEED0, SEED0 + 1))
+        assert rc == 0 and int(summary[nv.SB_FLAG]) == 0 and int(summary[nv.SB_N_OK]) == K and index[0, nv.SB_T] > 0.0, k
+    groups = [G(param_normals=(39,)), G(param_uniforms=(39,)), G(step_normals=(39,)), G(step_uniforms=(39,))]
+    x, l, L = sm.wide_policy()
+    r = ctx.policy_sobol(x, l, L, noise=rat.UserNoise(40, 40), groups=groups, K=K, seed_a=SEED0, seed_b=SEED0 + 1, want_costs=True)
+    model = sm.wide_costs(groups, K, SEED0, SEED0 + 1, nd=40)
+    err = float(np.abs(r["y"] - model).max() / np.abs(model).max())
+    print(f"wide at 40 draws: rows against the model {err:.2e}")
+    assert err <= 1e-12 and np.unique(r["y"], axis=0).shape[0] == 6
+    index = raw(ctx, c, [g.words for g in groups], seeds=(SEED0, SEED0 + 1))[1]      # (L = 0 under raw(): the same controls, the same bits)
+    assert np.array_equal(index, np.stack([r[k] for k in ("S", "S_se", "T", "T_se")], axis=1))
+    against_estimator(r, "wide at 40 draws")
+
+
+# ---- 10. K across the stride of the reduction grid (256 blocks of 256 lanes) ----------------------------------------------------------------------
+LONG_K = 65536 + 5
+_LONG = {}
+
+
+def long_run():
+    """the additive closed form at K = 65536 + 5: lanes 0 .. 4 of the first block of sb_pass1 / sb_pass2 take a second trip"""
+    if not _LONG:
+        ctx = rat.Context(sm.closed_problem("additive"))
+        ctx.set_param_sampling(rat.ParamSampling(2, 0))
+        x, l, L = sm.closed_policy()
+        call = lambda K: ctx.policy_sobol(x, l, L, noise=rat.UserNoise(1, 0), groups=sm.closed_groups(), K=K, seed_a=SEED0, seed_b=SEED0 + 1,
+                                          want_costs=True)
+        model = sm.closed_costs("additive", LONG_K, SEED0, SEED0 + 1)
+        r = call(LONG_K)
+        for v in (r["y"], model):
+            v.setflags(write=False)
+        _LONG.update(ctx=ctx, call=call, r=r, model=model)
+    return _LONG
+
+
+def test_the_additive_form_across_the_reduction_grid():
+    run = long_run()
+    r, model, m = run["r"], run["model"], sm.CLOSED["additive"]
+    err = float(np.abs(r["y"] - model).max())
+    print(f"additive at K = {LONG_K}: rows against the model {err:.2e}, in the second trip {float(np.abs(r['y'][:, 65536:] - model[:, 65536:]).max()):.2e}")
+    assert r["y"].shape == (5, LONG_K) and err <= 1e-12 * float(np.abs(model).max())
+    x, l, L = sm.closed_policy()
+    for row, seed in ((0, SEED0), (1, SEED0 + 1)):
+        e = run["ctx"].policy_evaluate_noise(x, l, L, noise=rat.UserNoise(1, 0, seed=seed), K=LONG_K, want_costs=True)
+        assert np.array_equal(r["y"][row], e["costs"]), row
+    against_estimator(r, f"additive at K = {LONG_K}")
+    assert r["n_ok"] == LONG_K and r["flag"] == 0 and abs(r["var"] - m["var"]) <= 4.0 * r["var_se"]
+    for key in ("S", "T"):
+        for i in range(3):
+            dev = abs(r[key][i] - m[key][i]) / r[key + "_se"][i]
+            print(f"additive at K = {LONG_K}: {key}[{i}] {r[key][i]:+.5f} +- {r[key + '_se'][i]:.5f} (exact {m[key][i]}): {dev:.2f} sigma")
+            assert dev <= 4.0
+
+
+@pytest.mark.parametrize("K", [65535, 65536])
+def test_a_call_that_ends_at_the_stride_returns_the_leading_columns(K):
+    run = long_run()
+    short = run["call"](K)
+    assert np.array_equal(short["y"], run["r"]["y"][:, :K]) and short["n_ok"] == K
+    against_estimator(short, f"additive at K = {K}")
+
+
+def test_dropped_base_samples_on_both_sides_of_the_stride():
+    c = pm.case("pend")
+    groups = split_groups(c)
+    m = sm.nan_thresholds(c, LONG_K, SEED_A, SEED_B)
+    tail = np.sort(m[65536:])
+    p = c.p.copy()
+    p[c.idx["pnan"]] = 0.5 * (tail[3] + tail[4])                      # four of the five base samples of the second trip survive, one drops
+    model = sm.pend_costs(c, "nan", groups, LONG_K, SEED_A, SEED_B, p=p)
+    bad = np.isnan(model).any(axis=0)
+    print(f"nan hook at K = {LONG_K}: threshold {p[c.idx['pnan']]:.4f}, dropped {int(bad.sum())}, of them at or beyond 65536: {int(bad[65536:].sum())}")
+    assert bad[65536:].sum() == 1 and (~bad[65536:]).sum() == 4 and bad[:65536].any() and (~bad[:65536]).any()
+    assert np.array_equal(bad, m > p[c.idx["pnan"]])
+    ctx = context("pend", "nan")
+    ctx.set_params(p)
+    ctx.set_param_sampling(c.sampling(injected=False))
+    r = ctx.policy_sobol(*c.args(True), noise=c.user_noise(), groups=groups, K=LONG_K, seed_a=SEED_A, seed_b=SEED_B, want_costs=True)
+    assert np.array_equal(np.isnan(r["y"]), np.isnan(model))
+    assert r["n_ok"] == LONG_K - bad.sum() and r["flag"] == 0
+    err = float(np.nanmax(np.abs(r["y"] / model - 1)))
+    print(f"nan hook at K = {LONG_K}: rows against the model {err:.2e}")
+    assert err <= 1e-12
+    against_estimator(r, f"nan hook at K = {LONG_K}")
+
+
+# ---- 11. few survivors, and a mean that is large against the spread -----------------------------------------------------------------------------
+@pytest.mark.parametrize("n_left", [0, 1, 2])
+def test_few_survivors(n_left):
+    c = pm.case("pend")
+    groups = split_groups(c)
+    ms = np.sort(sm.nan_thresholds(c, 64, SEED_A, SEED_B))
+    p = c.p.copy()
+    p[c.idx["pnan"]] = ms[0] - 0.5 if n_left == 0 else 0.5 * (ms[n_left - 1] + ms[n_left])
+    model = sm.case_costs(c, "nan", True, groups, 64, SEED_A, SEED_B, p=p)
+    alive = ~np.isnan(model).any(axis=0)
+    ref = sm.estimator(model)
+    assert alive.sum() == n_left and ref["n_ok"] == n_left and np.array_equal(alive, sm.nan_thresholds(c, 64, SEED_A, SEED_B) <= p[c.idx["pnan"]])
+    assert not np.isnan(model[:, alive]).any()                        # the survivors are whole in all five rows
+    ctx = context("pend", "nan")
+    ctx.set_params(p)
+    ctx.set_param_sampling(c.sampling(injected=False))
+    r = ctx.policy_sobol(*c.args(True), noise=c.user_noise(), groups=groups, K=64, seed_a=SEED_A, seed_b=SEED_B, want_costs=True)   # rc: RAT_OK
+    assert np.array_equal(np.isnan(r["y"]), np.isnan(model)) and r["n_ok"] == n_left
+    if n_left == 2:
+        assert r["flag"] == 0
+        against_estimator(r, "two survivors")
+        return
+    assert r["flag"] == nv.SB_DEGENERATE and ref["flag"] == sm.DEGENERATE and np.isnan(r["var_se"])
+    for key in ("S", "S_se", "T", "T_se"):
+        assert np.isnan(r[key]).all(), key
+    if n_left == 0:
+        assert np.isnan(r["mean"]) and np.isnan(r["var"])
+    else:
+        print(f"one survivor: mean {r['mean']:.6g} against fsum {abs(r['mean'] - ref['mean']):.2e}, var {r['var']:.6g} against fsum {abs(r['var'] - ref['var']):.2e}")
+        assert np.isfinite(r["mean"]) and np.isfinite(r["var"]) and r["var"] > 0.0
+        assert abs(r["mean"] - ref["mean"]) <= 1e-9 * max(1.0, abs(ref["mean"])) and abs(r["var"] - ref["var"]) <= 1e-9 * max(1.0, abs(ref["var"]))
+
+
+def test_a_mean_ten_thousand_spreads_away():
+    from test_cpu_sobol import OFFSET, large_mean_figures
+    uncentred, centred, Y = large_mean_figures()                      # on the model's rows, before the device is touched
+    assert uncentred > 1e-6 and centred <= 1e-10
+    ctx = rat.Context(sm.offset_problem())
+    ctx.set_param_sampling(rat.ParamSampling(2, 0))
+    x, l, L = sm.closed_policy()
+    kw = dict(noise=rat.UserNoise(1, 0), groups=sm.closed_groups(), K=sm.CLOSED_K, seed_a=SEED0, seed_b=SEED0 + 1, want_costs=True)
+    ctx.set_params([0.0, 0.0, OFFSET])
+    r = ctx.policy_sobol(x, l, L, **kw)
+    err = float(np.abs(r["y"] - Y).max())
+    print(f"offset {OFFSET}: rows against the model {err:.2e}; mean {r['mean']:.4f}, sd {np.sqrt(r['var']):.4f}, |mean| / sd {abs(r['mean']) / np.sqrt(r['var']):.1f}")
+    assert err <= 1e-12 * float(np.abs(Y).max()) and 0.9e4 <= abs(r["mean"]) / np.sqrt(r["var"]) <= 1.1e4
+    against_estimator(r, f"offset {OFFSET}")
+    ctx.set_params([0.0, 0.0, 0.0])
+    r0 = ctx.policy_sobol(x, l, L, **kw)
+    Y0 = sm.closed_costs("additive", sm.CLOSED_K, SEED0, SEED0 + 1)
+    assert float(np.abs(r0["y"] - Y0).max()) <= 1e-12 * float(np.abs(Y0).max())
+    for key in ("S", "T"):
+        gap = float(np.abs(r[key] - r0[key]).max())
+        print(f"offset {OFFSET}: {key} {np.round(r[key], 5)} against offset 0 {gap:.2e}")
+        assert gap <= 1e-9, key
