@@ -568,6 +568,52 @@ rat_rc rat_policy_tail_gradient(rat_handle h, const double *alpha, int32_t n_alp
  * does not compile, or one without RAT_USER_NOISE: RAT_ERR_ARG with the compiler's log), and RAT_ERR_UNSUPPORTED for a source that defines
  * RAT_USER_POLICY. */
 rat_rc rat_policy_gradient_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms);
+/* Which way to move the policy so that a safety event becomes less likely: the gradient, with respect to l and L, of the tail mean of an
+ * event's margin.  Events are rat_policy_events' quadratic events -- g_i(t, z) = z' Q_i z + a_i' z + b_i of z = (x_t, u_t), the same
+ * layouts, the same validation and codes, Q used as given (not symmetrised) or NULL -- and M_ik = max over the window of g_i(t, z_t) is
+ * the margin of rollout k, as margin_out has it.  CVaR_alpha(M_i) <= 0 implies P(M_i > 0) <= 1 - alpha, and unlike the indicator it is
+ * differentiable almost everywhere: this call is the constraint's gradient beside rat_policy_tail_gradient's, the objective's.
+ *   n_event  1 .. 4 (above: RAT_ERR_UNSUPPORTED; the joint sweep below keeps one adjoint per event in registers).  "any" is not served.
+ *   alpha    1 .. 16 levels, validated as rat_policy_tail_risk validates them; alpha = 0 is the mean margin.
+ * Rows are event-major, row r = i * n_alpha + j.  The sample of event i is its margins over the replayed rollouts (NaN for a DomainError
+ * rollout) and row (i, j) is the tail distribution of that sample at alpha_j exactly as rat_policy_tail_risk forms it:
+ *   rows_out  [n_event * n_alpha][RAT_TR_NSTAT]: bit for bit rat_policy_tail_risk(cost = row i of rat_policy_events' margin_out).
+ * Per replayed rollout k and event i, the recorded disturbances w_t held fixed as in rat_policy_gradient:
+ *   t*       = the first step of the window that attains M_ik (only a strictly greater g replaces the running margin; a NaN g is passed
+ *              over).  It is recorded by the margin pass itself, not recomputed by the sweep.
+ *   at t*      g_z = (Q_i + Q_i') z + a_i with z = (x_t*, u_t*), u_N = 0;  t* < N: gu_t* = its u part, lambda_t* = its x part + L_t*' gu_t*;
+ *              t* = N: lambda_N = its x part (there is no u_N)
+ *   t > t*     gu_t = 0 exactly
+ *   t < t*     g_t = f_z(x_t, u_t)' lambda_{t+1} (no c_z, no h_x);  gu_t = its u part;  lambda_t = its x part + L_t' gu_t (open loop: the
+ *              x part alone)
+ *   dM_ik / dl_t = gu_t,     dM_ik / dL_t = gu_t (x_t - x_nom_t)'
+ * and with y_k the tail weights of the row, self-normalised, grad_l[t] = sum y_k gu_t^k / sum y_k, grad_L[t] likewise:
+ *   grad_l_out     [rows][N][m]
+ *   grad_L_out     [rows][N][m n] (column-major m x n per step), or NULL; zeros after an open-loop evaluation
+ *   grad_l_se_out  [rows][N][m] or NULL: rat_policy_gradient's self-normalised standard error
+ *   n_nonfinite_out  [n_event] or NULL: per event, the rollouts that have a cost but a NaN or Inf in that event's sensitivities (g_z at t*
+ *                  or a component of some g_t below it); they are left out of the event's gradient sums and of their denominator, the
+ *                  rows still count them.  The call returns RAT_OK.
+ * A rollout whose margin is NaN carries no weight.  Dead rows (an empty or non-finite sample) are NaN in every gradient output and the call
+ * returns RAT_OK.  Fixed summation order, no floating-point atomics: the same call returns the same bits, and a row's bits depend neither
+ * on the other levels nor on the other events of the call.
+ * What this is and is not:
+ *   - A gradient almost everywhere; a SUBGRADIENT where the arg-max step ties (the first one is taken), where the tail's membership ties
+ *     (rollouts on the quantile share its weight) and on a saturated row (RAT_TR_SATURATED).
+ *   - w is FROZEN: a sampler that reads x or u is not differentiated through (rat_user_noise takes double, not T).
+ *   - x_nom is not a decision variable and is not differentiated.
+ *   - The value at risk is not differentiated: this is the usual CVaR gradient, the tail mean of the per-rollout gradients.
+ * The call REPLAYS the last rat_policy_evaluate_noise twice in one enqueue chain -- once for the margins, once for the adjoints -- in
+ * buffers of its own: the handle's recorded evaluation and its stored costs are left as they were, and every other replay call works
+ * after it.  Served and refused exactly as rat_policy_gradient is: source models after rat_policy_evaluate_noise with zn == zu == NULL;
+ * RAT_ERR_UNSUPPORTED for the families, general sizes, a source that defines RAT_USER_POLICY, parameter sampling switched on, and
+ * rows x N above 3360 (64 MiB of partial sums); the same "no evaluation yet" and replay guard. */
+rat_rc rat_policy_margin_gradient(rat_handle h, int32_t n_event, const double *Q, const double *a, const double *b,
+                                  const int32_t *t_lo, const int32_t *t_hi, const double *alpha, int32_t n_alpha,
+                                  double *rows_out, double *grad_l_out, double *grad_L_out, double *grad_l_se_out,
+                                  int64_t *n_nonfinite_out);
+/* Compile only, for gfx950 (no device needed), the adjoint kernel of the call above for four events.  rat_policy_gradient_check's codes. */
+rat_rc rat_policy_margin_gradient_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms);
 /* How a risk reacts to the model: the gradient of the same functionals -- the mean cost, the entropic risk of a theta row, the KL-robust
  * bound of a kl_bound row (at theta*, envelope theorem), CVaR_alpha of a level -- with respect to the model's parameters p and to the
  * initial state x_0, by the same adjoint replay.  The source opts in: it defines RAT_USER_PARAMS_AD and templates rat_user_f, rat_user_c

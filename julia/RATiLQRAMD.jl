@@ -767,6 +767,32 @@ function policy_tail_events(s::ILEQGSolver, Q::Union{Nothing,Array{Float64,3}}, 
 end
 
 """
+policy_margin_gradient(s, Q, a, b, t_lo, t_hi; alphas): which way to move the policy to clear a safety event
+(rat_policy_margin_gradient).  policy_events' events (1 to 4) and levels α ∈ [0, 1) (1 to 16): per event and level the gradient with
+respect to l and L of the tail mean of the event's margin -- α = 0: the mean margin; otherwise CVaR_α(M), whose being ≤ 0 implies
+P(M > 0) ≤ 1 − α -- by adjoint replay of the last evaluate_policy under the source's own noise on this solver's handle.  Rows are
+event-major (level fastest).  Returns (rows, grad_l, grad_L, grad_l_se, n_nonfinite): rows (8, R, E) as policy_tail_risk's on each
+event's margins, grad_l (m, N, R, E), grad_L (m, n, N, R, E) (zeros after an open-loop evaluation), grad_l_se (m, N, R, E), n_nonfinite
+(E).  The disturbances are held fixed, x_nom and the value at risk are not differentiated; ties and saturated levels give a subgradient.
+"""
+function policy_margin_gradient(s::ILEQGSolver, Q::Union{Nothing,Array{Float64,3}}, a::Matrix{Float64}, b::Vector{Float64},
+                                t_lo::Vector{Int32}, t_hi::Vector{Int32}; alphas=Float64[])
+    h = s.h
+    n, m, N = dims(h.problem)
+    al = collect(Float64, alphas); R = length(al); E = length(b); Ea = clamp(E, 1, 4)
+    rows = zeros(8, R, Ea); gl = zeros(m, N, R, Ea); gL = zeros(m, n, N, R, Ea); se = zeros(m, N, R, Ea); nf = zeros(Int64, max(E, 1))
+    check(ccall((:rat_policy_margin_gradient, LIB), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int32,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                h.ptr, E, Q === nothing ? C_NULL : Q, a, b, t_lo, t_hi, R > 0 ? al : C_NULL, R, rows, gl, gL, se, nf))
+    (rows=rows, grad_l=gl, grad_L=gL, grad_l_se=se, n_nonfinite=nf)
+end
+
+"policy_margin_gradient_check(source, n, m; normals_per_step, uniforms_per_step): compile the adjoint kernel of policy_margin_gradient only (rat_policy_margin_gradient_check)"
+policy_margin_gradient_check(source::AbstractString, n::Integer, m::Integer; normals_per_step::Integer=0, uniforms_per_step::Integer=0) =
+    check(ccall((:rat_policy_margin_gradient_check, LIB), Int32, (Cstring, Int32, Int32, Int32, Int32), source, n, m, normals_per_step, uniforms_per_step))
+
+"""
 policy_tail_events_user(s, n_event; alphas, want_steps, want_margins): policy_tail_events for the events the source problem's own
 rat_user_event writes (rat_policy_tail_events_user); n_event as policy_events_user takes it.  Returns policy_tail_events' named tuple.
 """
@@ -1839,7 +1865,7 @@ end
 
 export OptimalControlProblem, LQRiskSensitiveProblem, PowerLawRiskSensitiveProblem, LQGenerativeProblem, DeviceSourceProblem, set_params!, source_check, UserNoise, user_noise_check,
        DeviceGenerativeSourceProblem, pets_source_check,
-       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_gradient, policy_tail_gradient, policy_gradient_check, policy_param_gradient, policy_tail_param_gradient, policy_param_gradient_check, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, policy_tail_events, policy_tail_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, rare_event_probability_params, rare_event_params_check, SobolGroup, policy_sobol, policy_sobol_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
+       simulate_dynamics, simulate_dynamics_noisy, evaluate_policy, policy_worst_case, policy_worst_case_trajectory, policy_worst_case_disturbance, policy_worst_case_params, policy_tail_risk, policy_tail_trajectory, policy_tail_disturbance, policy_tail_params, policy_gradient, policy_tail_gradient, policy_gradient_check, policy_margin_gradient, policy_margin_gradient_check, policy_param_gradient, policy_tail_param_gradient, policy_param_gradient_check, policy_events, kl_event_bound, rare_event_probability, rare_event_probability_noise, rare_event_noise_check, policy_events_user, policy_tail_events, policy_tail_events_user, user_event_check, user_policy_check, ParamSampling, set_param_sampling!, sample_params, user_params_check, rare_event_probability_user, rare_event_user_check, rare_event_probability_params, rare_event_params_check, SobolGroup, policy_sobol, policy_sobol_check, integrate_cost, ILEQGSolver, initialize!, ApproximationResult, approximate_model,
        DynamicProgrammingResult, solve_approximate_dp!, solve_approximate_dp, increase_μ_and_Δ!, decrease_μ_and_Δ!, line_search!, step!, solve!,
        solve_batch, solve_approximate_dp_batch!, solve_approximate_dp_batch, solve_closure_batch, closure_device, CrossEntropyBilevelOptimizationSolver, compute_value_worker, compute_cost, compute_cost_serial, get_positive_samples,
        set_initial!, compute_cost_dev!, NelderMeadBilevelOptimizationSolver, compute_cost_worker, CrossEntropyDirectOptimizationSolver,

@@ -12,7 +12,7 @@ from .problems import (  # noqa: F401
     DeviceGenerativeSourceProblem,
     synthetic_lq_problem,
 )
-from ._native import RatError, SO_PATH, user_event_check, rare_event_user_check, user_policy_check, user_params_check, rare_event_params_check, policy_sobol_check, policy_gradient_check, policy_param_gradient_check  # noqa: F401,E402
+from ._native import RatError, SO_PATH, user_event_check, rare_event_user_check, user_policy_check, user_params_check, rare_event_params_check, policy_sobol_check, policy_gradient_check, policy_param_gradient_check, policy_margin_gradient_check  # noqa: F401,E402
 from . import _native as native  # noqa: F401,E402
 from .ileqg import (  # noqa: F401,E402
     Context,

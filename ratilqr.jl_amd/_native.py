@@ -109,6 +109,7 @@ EXPORTS = [
     "rat_policy_sobol", "rat_policy_sobol_check",
     "rat_policy_gradient", "rat_policy_tail_gradient", "rat_policy_gradient_check",
     "rat_policy_param_gradient", "rat_policy_tail_param_gradient", "rat_policy_param_gradient_check",
+    "rat_policy_margin_gradient", "rat_policy_margin_gradient_check",
 ]
 MC_N_OK, MC_N_DOMAIN, MC_MEAN, MC_VAR, MC_MIN, MC_MAX, MC_SE_MEAN, MC_NSTAT = 0, 1, 2, 3, 4, 5, 6, 8      # RAT_MC_* of the header
 WC_SLOTS = ("theta", "kl", "bound", "bound_se", "tilt_mean", "tilt_var", "ess", "flag")      # RAT_WC_* slots of the header, in order
@@ -197,6 +198,8 @@ def lib():
         _lib.rat_policy_gradient.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]
         _lib.rat_policy_tail_gradient.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]
         _lib.rat_policy_gradient_check.argtypes = [C.c_char_p] + [C.c_int32] * 4
+        _lib.rat_policy_margin_gradient.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _ip, _dp, C.c_int32, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]
+        _lib.rat_policy_margin_gradient_check.argtypes = [C.c_char_p] + [C.c_int32] * 4
         _lib.rat_policy_param_gradient.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]
         _lib.rat_policy_tail_param_gradient.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]
         _lib.rat_policy_param_gradient_check.argtypes = [C.c_char_p] + [C.c_int32] * 5
@@ -299,6 +302,12 @@ def policy_sobol_check(source, n, m, n_params=0, normals_per_step=0, uniforms_pe
     the counts (at most 64 each)."""
     check(lib().rat_policy_sobol_check(str(source).encode(), int(n), int(m), int(n_params), int(normals_per_step), int(uniforms_per_step),
                                        int(param_normals), int(param_uniforms)))
+
+
+def policy_margin_gradient_check(source, n, m, normals_per_step=0, uniforms_per_step=0):
+    """rat_policy_margin_gradient_check: compile the adjoint kernel of rat_policy_margin_gradient only (gfx950, four events, no device
+    needed); raises RatError with the compiler's log, RAT_ERR_UNSUPPORTED for a source that defines RAT_USER_POLICY."""
+    check(lib().rat_policy_margin_gradient_check(str(source).encode(), int(n), int(m), int(normals_per_step), int(uniforms_per_step)))
 
 
 def policy_gradient_check(source, n, m, normals_per_step=0, uniforms_per_step=0):

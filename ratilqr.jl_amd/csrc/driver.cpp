@@ -281,6 +281,19 @@ struct rat_handle_s {
     double *d_ppg_l0 = nullptr; size_t cap_ppg_l0 = 0;       // [chunk][12] dJ_k / dx_0 staging
     double *d_ppg_part = nullptr; size_t cap_ppg_part = 0;   // [rows][WT_SLOTS][PPG_PART] partials
     double *d_ppg_out = nullptr; size_t cap_ppg_out = 0;     // grad_p | grad_p_se | grad_x0 | grad_x0_se | S0, sum y^2 per row | mismatch count | non-finite count
+    // the safety-margin gradient (rat_policy_margin_gradient, source_margin_adjoint.h and policy_mc.hip): two replays in one call, the
+    // margins of every event kept whole between them; buffers of its own but for the replay's staging -- the stored costs, d_tr_red and
+    // d_tl_live are not written
+    double *d_mg_margin = nullptr; size_t cap_mg_margin = 0; // [n_event][K] margins (the samples the levels are selected on)
+    int *d_mg_tstar = nullptr; size_t cap_mg_tstar = 0;      // [n_event][K] arg-max steps
+    double *d_mg_tr = nullptr; size_t cap_mg_tr = 0;         // [n_event][TR_SCRATCH] the tail chain's scratch per event (its rows inside)
+    double *d_mg_wc = nullptr; size_t cap_mg_wc = 0;         // [n_event][WC_SCRATCH] tlt_levels' output per event
+    double *d_mg_y = nullptr; size_t cap_mg_y = 0;           // [n_event][n_alpha][chunk] weights
+    unsigned *d_mg_live = nullptr; size_t cap_mg_live = 0;   // [n_event][chunk / 4] liveness words
+    double *d_mg_gu = nullptr; size_t cap_mg_gu = 0;         // [chunk][n_event][N][4] dM_ik / du_t staging
+    int *d_mg_bad = nullptr; size_t cap_mg_bad = 0;          // [n_event][chunk] non-finite flags
+    double *d_mg_part = nullptr; size_t cap_mg_part = 0;     // [rows][N][WT_SLOTS][PG_PART] partials
+    double *d_mg_out = nullptr; size_t cap_mg_out = 0;       // events' tile | grad_l | grad_L | grad_l_se | S0, sum y^2 per row | mismatch counts [2] | non-finite counts [4]
 };
 
 extern "C" int32_t rat_version(void) { return RAT_VERSION; }
@@ -476,6 +489,8 @@ extern "C" void rat_destroy(rat_handle h) {
     for (void *q : {(void *)h->d_sb_in, (void *)h->d_sb_y, (void *)h->d_sb_ok, (void *)h->d_sb_red}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_pg_gu, (void *)h->d_pg_bad, (void *)h->d_pg_part, (void *)h->d_pg_out}) if (q) (void)hipFree(q);
     for (void *q : {(void *)h->d_ppg_gp, (void *)h->d_ppg_l0, (void *)h->d_ppg_part, (void *)h->d_ppg_out}) if (q) (void)hipFree(q);
+    for (void *q : {(void *)h->d_mg_margin, (void *)h->d_mg_tstar, (void *)h->d_mg_tr, (void *)h->d_mg_wc, (void *)h->d_mg_y, (void *)h->d_mg_live,
+                    (void *)h->d_mg_gu, (void *)h->d_mg_bad, (void *)h->d_mg_part, (void *)h->d_mg_out}) if (q) (void)hipFree(q);
     if (h->h_un_over) (void)hipHostFree(h->h_un_over);
     if (h->h_pzc) (void)hipHostFree(h->h_pzc);
     if (h->h_pcost) (void)hipHostFree(h->h_pcost);
@@ -863,6 +878,7 @@ static rat_rc src_args_ok(const char *who, SrcKind kind, int n, int m, int npn, 
     const bool big = !src_sizes_ok(n, m);
     if (n < 1 || m < 1) return fail(RAT_ERR_ARG, F + "n, m must be positive");
     if (row.events && (nev < 1 || nev > EV_MAX)) return fail(RAT_ERR_ARG, F + "n_event must be in 1 .. 16");
+    if (row.margins && (nev < 1 || nev > SRC_MARGIN_MAX)) return fail(RAT_ERR_ARG, F + "n_event must be in 1 .. 4");
     if (row.draws && !(row.events && big) && (npn < 0 || npu < 0))
         return fail(RAT_ERR_ARG, F + "normals_per_step, uniforms_per_step must not be negative");
     if (big) return fail(RAT_ERR_UNSUPPORTED, F + "source models are compiled for n <= 12, m <= 4");
@@ -2589,11 +2605,14 @@ static rat_rc replay_validate_handle(rat_handle h, const std::string &F, const c
 
 // The rows of a replay, by their source: KL radii and thetas (rat_policy_worst_case's chain: the worst-case calls and the events) or CVaR
 // levels (rat_policy_tail_risk's chain: the tail calls, n_alpha > 0 and no kl_bound or theta then)
+// A replay without rows (replay_none: rat_policy_margin_gradient, whose rows come from samples of its own): no chain on the stored costs
+// and no weights; the caller's kernels behind each chunk form the weights and hold the replay's costs against the stored ones
 struct ReplaySpec {
     const double *kl_bound; int32_t n_bound; const double *theta; int32_t n_theta; const double *alpha; int32_t n_alpha;
     bool tail() const { return n_alpha > 0; }
     int nrows() const { return tail() ? n_alpha : n_bound + n_theta; }
 };
+static ReplaySpec replay_none() { return ReplaySpec{nullptr, 0, nullptr, 0, nullptr, 0}; }
 static ReplaySpec replay_kl(const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta) {
     return ReplaySpec{kl_bound, n_bound, theta, n_theta, nullptr, 0};
 }
@@ -2695,7 +2714,7 @@ static rat_rc replay_chunks(rat_handle h, const ReplaySpec &rs, int *d_mismatch,
         for (int i = 0; i < rs.n_alpha; ++i) tr.alpha[i] = rs.alpha[i];
         launch_policy_tr(tr, h->stream);
         launch_tlt_levels(tr, h->d_wc_red, h->stream);
-    } else {
+    } else if (nrows > 0) {
         // theta*, Jmax and the rows, on the stored costs
         WcArgs wa;
         memset(&wa, 0, sizeof(wa));
@@ -3028,7 +3047,7 @@ static rat_rc replay_gradient(rat_handle h, const std::string &F, const char *fn
     HIPCHK(hipMemsetAsync(h->d_pg_out + o_nf, 0, 8, h->stream));
     PgArgs pa;
     memset(&pa, 0, sizeof(pa));
-    pa.gu = h->d_pg_gu; pa.bad = h->d_pg_bad; pa.xnom = rec.has_L ? h->d_mc_in + rec.o_x : nullptr; pa.part = h->d_pg_part;
+    pa.gu = h->d_pg_gu; pa.ldg = (long)N * 4; pa.bad = h->d_pg_bad; pa.xnom = rec.has_L ? h->d_mc_in + rec.o_x : nullptr; pa.part = h->d_pg_part;
     pa.grad_l = h->d_pg_out + o_gl; pa.grad_L = h->d_pg_out + o_gL; pa.grad_l_se = h->d_pg_out + o_se; pa.ess = h->d_pg_out + o_ess;
     if ((rc = replay_chunks(h, rs, reinterpret_cast<int *>(h->d_pg_out + o_cnt), pa.t,
                             [&](const WtArgs &c, ReplayChunk ch) -> rat_rc {
@@ -3295,11 +3314,9 @@ static rat_rc events_run(rat_handle h, const std::string &F, int n_event, const 
     return RAT_OK;
 }
 
-// Quadratic events: ev_eval.  Behind the call's own validation of its rows and of the handle (rs: the rows, KL or tail)
-static rat_rc events_quad(rat_handle h, const std::string &F, int32_t n_event, const double *Q, const double *a, const double *b,
-                          const int32_t *t_lo, const int32_t *t_hi, const ReplaySpec &rs,
-                          double *rows_out, double *event_out, double *step_out, double *margin_out) {
-    if (n_event < 1 || n_event > EV_MAX) return fail(RAT_ERR_ARG, F + "n_event must be in 1 .. 16");
+// What a call with quadratic events checks of them (n_event in range already) and their tile, the head of d_ev_out as ev_eval reads it
+static rat_rc events_tile(rat_handle h, const std::string &F, int32_t n_event, const double *Q, const double *a, const double *b,
+                          const int32_t *t_lo, const int32_t *t_hi, std::vector<double> *tile) {
     if (!a || !b || !t_lo || !t_hi) return fail(RAT_ERR_ARG, F + "null a / b / t_lo / t_hi");
     const int n = h->n, m = h->m, N = h->N, d = n + m;
     for (int e = 0; e < n_event; ++e) {
@@ -3311,7 +3328,8 @@ static rat_rc events_quad(rat_handle h, const std::string &F, int32_t n_event, c
         if (!fin) return fail(RAT_ERR_ARG, F + "event " + std::to_string(e) + ": Q, a and b must be finite");
     }
     // the events in the 12 + 4 tile: Q as the MFMA's A operand reads it (entry (k, i) at k * 16 + i), a, b, the windows
-    std::vector<double> in(EV_O_EV, 0.0);
+    std::vector<double> &in = *tile;
+    in.assign(EV_O_EV, 0.0);
     auto tix = [n](int i) { return i < n ? i : 12 + i - n; };
     for (int e = 0; e < n_event; ++e) {
         for (int i = 0; i < d; ++i) {
@@ -3322,6 +3340,17 @@ static rat_rc events_quad(rat_handle h, const std::string &F, int32_t n_event, c
         int32_t w[2] = {t_lo[e], t_hi[e]};
         memcpy(&in[EV_O_WIN + e], w, sizeof(w));
     }
+    return RAT_OK;
+}
+
+// Quadratic events: ev_eval.  Behind the call's own validation of its rows and of the handle (rs: the rows, KL or tail)
+static rat_rc events_quad(rat_handle h, const std::string &F, int32_t n_event, const double *Q, const double *a, const double *b,
+                          const int32_t *t_lo, const int32_t *t_hi, const ReplaySpec &rs,
+                          double *rows_out, double *event_out, double *step_out, double *margin_out) {
+    if (n_event < 1 || n_event > EV_MAX) return fail(RAT_ERR_ARG, F + "n_event must be in 1 .. 16");
+    std::vector<double> in;
+    rat_rc rc;
+    if ((rc = events_tile(h, F, n_event, Q, a, b, t_lo, t_hi, &in))) return rc;
     return events_run(h, F, n_event, &in, Q != nullptr, [h](const EvArgs &ea, int64_t) -> rat_rc { launch_ev_chunk(ea, h->stream); return RAT_OK; },
                       rs, rows_out, event_out, step_out, margin_out);
 }
@@ -3346,6 +3375,144 @@ extern "C" rat_rc rat_policy_tail_events(rat_handle h, int32_t n_event, const do
     if ((rc = replay_validate_alpha(F, alpha, n_alpha, rows_out && event_out))) return rc;
     if ((rc = replay_validate_handle(h, F, "rat_policy_tail_risk"))) return rc;
     return events_quad(h, F, n_event, Q, a, b, t_lo, t_hi, replay_tail(alpha, n_alpha), rows_out, event_out, step_out, margin_out);
+}
+
+// ---- which way to move the policy to clear an event: rat_policy_margin_gradient ---------------------------------------------------------
+// The gradient with respect to l and L of the tail distribution's mean of an event's margin (alpha = 0: the mean margin; otherwise
+// CVaR_alpha(M_i), the relaxation of the chance constraint P(M_i > 0) <= 1 - alpha), for up to SRC_MARGIN_MAX events at once.  Two
+// replays in one enqueue chain:
+//   pass A  the rollouts chunk by chunk with ev_eval's arg-max sibling behind each: the margins [n_event][K] and the steps that attain
+//           them, whole, in buffers of this call (the handle's costs are read, never written);
+//   select  per event rat_policy_tail_risk's chain on its margins and tlt_levels behind it, each into a scratch of its own;
+//   pass B  the rollouts again; behind each chunk tlt_weights per event (the weights from the event's margins, the replay check on the
+//           costs), rat_src_margin_adjoint once for all events, tlg_moments per event on its slice of gu and its liveness words;
+// then pg_final per event, the copies and the call's one wait for results.
+extern "C" rat_rc rat_policy_margin_gradient_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms) {
+    return gradient_compile_rc(src_check("rat_policy_margin_gradient_check", SRC_MARGIN_ADJOINT, source, n, m, normals, uniforms, SRC_MARGIN_MAX));
+}
+
+extern "C" rat_rc rat_policy_margin_gradient(rat_handle h, int32_t n_event, const double *Q, const double *a, const double *b,
+                                             const int32_t *t_lo, const int32_t *t_hi, const double *alpha, int32_t n_alpha,
+                                             double *rows_out, double *grad_l_out, double *grad_L_out, double *grad_l_se_out,
+                                             int64_t *n_nonfinite_out) {
+    const std::string F = "rat_policy_margin_gradient: ";
+    const char *fn = "rat_policy_margin_gradient";
+    rat_rc rc;
+    if ((rc = replay_validate_alpha(F, alpha, n_alpha, rows_out && grad_l_out))) return rc;
+    if ((rc = gradient_ready(h, F))) return rc;
+    if ((rc = replay_validate_handle(h, F, "rat_policy_tail_risk"))) return rc;
+    if (n_event < 1) return fail(RAT_ERR_ARG, F + "n_event must be at least 1");
+    if (n_event > SRC_MARGIN_MAX)
+        return fail(RAT_ERR_UNSUPPORTED, F + "n_event = " + std::to_string(n_event) + " is above " + std::to_string(SRC_MARGIN_MAX) +
+                                         " (the joint sweep keeps one lambda per event in registers): ask for the events in several calls");
+    std::vector<double> tile;
+    if ((rc = events_tile(h, F, n_event, Q, a, b, t_lo, t_hi, &tile))) return rc;
+    const rat_handle_s::McReplay rec = h->mc_rec;
+    const int n = h->n, m = h->m, N = h->N, E = n_event, A = n_alpha, R = E * A;
+    if ((long)R * N > PG_MAX_ROWSTEPS)
+        return fail(RAT_ERR_UNSUPPORTED, F + "rows x N = " + std::to_string((long)R * N) + " is above " + std::to_string(PG_MAX_ROWSTEPS) +
+                                         " (64 MiB of partial sums): ask for fewer events or levels per call");
+    HIPCHK(hipSetDevice(h->device));
+    hipFunction_t kadj = nullptr;
+    if ((rc = src_kernel(h, SRC_MARGIN_ADJOINT, SrcShape{rec.npn, rec.npu, E}, fn, &kadj))) return gradient_compile_rc(rc);
+    const int64_t K = rec.K, chunk = mc_chunk(K);
+    const size_t nrs = (size_t)R * N, ars = (size_t)A * N, nlive = (size_t)((chunk + 3) / 4);
+    const size_t o_gl = EV_O_EV, o_gL = o_gl + nrs * m, o_se = o_gL + nrs * m * n, o_ess = o_se + nrs * m, o_cnt = o_ess + 2 * (size_t)R,
+                 o_nf = o_cnt + 1, n_out = o_nf + (SRC_MARGIN_MAX + 1) / 2, n_part = nrs * WT_SLOTS * PG_PART;
+    if ((rc = grow(&h->d_mg_out, &h->cap_mg_out, n_out))) return rc;
+    if ((rc = grow(&h->d_mg_part, &h->cap_mg_part, n_part))) return rc;
+    if ((rc = grow(&h->d_mg_margin, &h->cap_mg_margin, (size_t)E * K))) return rc;
+    if ((rc = grow(&h->d_mg_tstar, &h->cap_mg_tstar, (size_t)E * K))) return rc;
+    if ((rc = grow(&h->d_mg_tr, &h->cap_mg_tr, (size_t)E * TR_SCRATCH))) return rc;
+    if ((rc = grow(&h->d_mg_wc, &h->cap_mg_wc, (size_t)E * WC_SCRATCH))) return rc;
+    if ((rc = grow(&h->d_mg_y, &h->cap_mg_y, (size_t)R * chunk))) return rc;
+    if ((rc = grow(&h->d_mg_live, &h->cap_mg_live, (size_t)E * nlive))) return rc;
+    if ((rc = grow(&h->d_mg_gu, &h->cap_mg_gu, (size_t)chunk * E * N * 4))) return rc;
+    if ((rc = grow(&h->d_mg_bad, &h->cap_mg_bad, (size_t)E * chunk))) return rc;
+    HIPCHK(hipMemcpyAsync(h->d_mg_out, tile.data(), EV_O_EV * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));                          // (the tile is pageable: the copy is complete here)
+    HIPCHK(hipMemsetAsync(h->d_mg_part, 0, n_part * 8, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_mg_out + o_nf, 0, (size_t)((SRC_MARGIN_MAX + 1) / 2) * 8, h->stream));
+    int *const d_cnt = reinterpret_cast<int *>(h->d_mg_out + o_cnt), *const d_nf = reinterpret_cast<int *>(h->d_mg_out + o_nf);
+    // pass A: the margins and the steps that attain them
+    EvArgs ea;
+    memset(&ea, 0, sizeof(ea));
+    ea.n_event = E; ea.quad = Q ? 1 : 0; ea.Qt = h->d_mg_out; ea.at = h->d_mg_out + EV_O_A; ea.b = h->d_mg_out + EV_O_B;
+    ea.win = reinterpret_cast<const int *>(h->d_mg_out + EV_O_WIN);
+    WtArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    if ((rc = replay_chunks(h, replay_none(), d_cnt, ta,
+                            [&](const WtArgs &c, ReplayChunk ch) -> rat_rc {
+                                ea.xs = c.xs; ea.us = c.us; ea.ldx = c.ldx; ea.ldu = c.ldu; ea.n = c.n; ea.m = c.m; ea.N = c.N; ea.kc = c.kc; ea.cost = c.cost;
+                                ea.ldy = (long)K; ea.margin = h->d_mg_margin + ch.k0; ea.tstar = h->d_mg_tstar + ch.k0;
+                                launch_ev_argmax(ea, h->stream);
+                                return RAT_OK;
+                            })))
+        return rc;
+    // the levels of every event, on its margins
+    TrArgs tr[SRC_MARGIN_MAX];
+    for (int e = 0; e < E; ++e) {
+        memset(&tr[e], 0, sizeof(TrArgs));
+        tr[e].cost = h->d_mg_margin + (size_t)e * K; tr[e].K = (long)K; tr[e].n_alpha = A; tr[e].scratch = h->d_mg_tr + (size_t)e * TR_SCRATCH;
+        for (int i = 0; i < A; ++i) tr[e].alpha[i] = alpha[i];
+        launch_policy_tr(tr[e], h->stream);
+        launch_tlt_levels(tr[e], h->d_mg_wc + (size_t)e * WC_SCRATCH, h->stream);
+    }
+    // pass B: the adjoints of every event and their sums
+    PgArgs pa[SRC_MARGIN_MAX];
+    for (int e = 0; e < E; ++e) {
+        memset(&pa[e], 0, sizeof(PgArgs));
+        pa[e].gu = h->d_mg_gu + (size_t)e * N * 4; pa[e].ldg = (long)E * N * 4; pa[e].bad = h->d_mg_bad + (size_t)e * chunk;
+        pa[e].xnom = rec.has_L ? h->d_mc_in + rec.o_x : nullptr; pa[e].part = h->d_mg_part + (size_t)e * ars * WT_SLOTS * PG_PART;
+        pa[e].grad_l = h->d_mg_out + o_gl + (size_t)e * ars * m; pa[e].grad_L = h->d_mg_out + o_gL + (size_t)e * ars * m * n;
+        pa[e].grad_l_se = h->d_mg_out + o_se + (size_t)e * ars * m; pa[e].ess = h->d_mg_out + o_ess + 2 * (size_t)e * A;
+    }
+    if ((rc = replay_chunks(h, replay_none(), d_cnt, ta,
+                            [&](const WtArgs &c, ReplayChunk ch) -> rat_rc {
+                                for (int e = 0; e < E; ++e) {         // the event's weights; the replay check rides on the first
+                                    WtArgs &w = pa[e].t;
+                                    w = c;
+                                    w.nrows = A; w.sample = h->d_mg_margin + (size_t)e * K + ch.k0; w.wc = h->d_mg_wc + (size_t)e * WC_SCRATCH;
+                                    w.y = h->d_mg_y + (size_t)e * A * chunk; w.ldy = (long)chunk;
+                                    if (e > 0) { w.cost_re = c.cost; w.dom_re = nullptr; }
+                                    launch_tlt_weights(w, h->d_mg_live + (size_t)e * nlive, h->stream);
+                                }
+                                SrcMarginArgs sa;
+                                sa.xs = c.xs; sa.us = c.us; sa.N = N; sa.kc = (long)ch.kc; sa.cost = c.cost_re;
+                                sa.L = rec.has_L ? h->d_mc_in + rec.o_L : nullptr; sa.p = h->d_src_p;
+                                sa.quad = Q ? 1 : 0; sa.Qt = h->d_mg_out; sa.at = h->d_mg_out + EV_O_A;
+                                sa.tstar = h->d_mg_tstar + ch.k0; sa.ldt = (long)K;
+                                sa.gu = h->d_mg_gu; sa.bad = h->d_mg_bad; sa.ldb = (long)chunk; sa.n_bad = d_nf;
+                                HIPCHK(launch_src(kadj, ch.kc, 4, h->stream, &sa));
+                                for (int e = 0; e < E; ++e)
+                                    launch_pg_chunk(pa[e], h->tail_dense ? nullptr : h->d_mg_live + (size_t)e * nlive, h->stream);
+                                return RAT_OK;
+                            })))
+        return rc;
+    for (int e = 0; e < E; ++e) launch_pg_final(pa[e], h->stream);
+    HIPCHK(hipGetLastError());
+    double rows[SRC_MARGIN_MAX * TR_MAX_ALPHA * TR_NSTAT], ess[SRC_MARGIN_MAX * TR_MAX_ALPHA * 2];
+    int bad = 0, nf[SRC_MARGIN_MAX] = {0, 0, 0, 0};
+    for (int e = 0; e < E; ++e)
+        HIPCHK(hipMemcpyAsync(rows + (size_t)e * A * TR_NSTAT, h->d_mg_tr + (size_t)e * TR_SCRATCH + TR_O_ROWS, (size_t)A * TR_NSTAT * 8,
+                              hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(ess, h->d_mg_out + o_ess, (size_t)R * 2 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&bad, d_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(nf, d_nf, sizeof(int) * E, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(grad_l_out, h->d_mg_out + o_gl, nrs * m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (grad_L_out) HIPCHK(hipMemcpyAsync(grad_L_out, h->d_mg_out + o_gL, nrs * m * n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (grad_l_se_out) HIPCHK(hipMemcpyAsync(grad_l_se_out, h->d_mg_out + o_se, nrs * m * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = replay_mismatch(F, bad, K))) return rc;
+    for (int r = 0; r < R; ++r) {                                     // (replay_finish's second route to the effective sample size)
+        const double e_row = rows[r * TR_NSTAT + RAT_TR_ESS], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
+        if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
+            return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
+                                     " is not the row's " + std::to_string(e_row));
+    }
+    if (n_nonfinite_out) for (int e = 0; e < E; ++e) n_nonfinite_out[e] = nf[e];
+    for (int i = 0; i < R * TR_NSTAT; ++i) rows_out[i] = rows[i];
+    return RAT_OK;
 }
 
 extern "C" rat_rc rat_user_event_check(const char *source, int32_t n, int32_t m, int32_t n_event) {

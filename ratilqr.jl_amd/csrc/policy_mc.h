@@ -133,6 +133,9 @@ struct WtArgs {
     double *mean;             // [nrows][N+1][n+m]
     double *cov;              // [nrows][N+1][(n+m)^2] column-major
     double *ess;              // [nrows][2]: S0 and sum y^2 of step 0
+    // tlt_weights only
+    const double *sample;     // [kc] what the levels were selected on where that is not the costs (rat_policy_margin_gradient: an event's
+                              // margins; NaN carries no weight), or null: cost.  The replay check is on cost either way
 };
 // c[t] = (x[t][0..n), u[t][0..m)) in the 12 + 4 tile, zero padded, zero where the source is not finite; x [N+1][12], u [N][4]
 void launch_wct_centre(const double *x, const double *u, int n, int m, int N, double *centre, hipStream_t s);
@@ -251,7 +254,8 @@ void launch_tlt_weights(const WtArgs &a, unsigned *live, hipStream_t s);
 
 struct PgArgs {
     WtArgs t;                 // the replay's fields as wct_weights fills them (xs, ldx, kc, cost, y, ldy, nrows, wc, n, m, N); centre, part, mean, cov, ess are not read
-    const double *gu;         // [kc][N][4] the staged adjoints of the chunk
+    const double *gu;         // the staged adjoints of the chunk: gu_t of rollout q at gu + q ldg + 4 t
+    long ldg;                 // doubles between rollouts: 4 N ([kc][N][4]), or more where the adjoint kernel interleaves several sweeps
     const int *bad;           // [kc] the chunk's non-finite flags
     const double *xnom;       // [N+1][12] the pack's nominal states, or null (open loop: no dJ / dL)
     double *part;             // [nrows][N][WT_SLOTS][PG_PART]
@@ -340,6 +344,8 @@ struct EvArgs {
     // rat_policy_tail_events only (null otherwise)
     const unsigned *live;     // the chunk's liveness words (launch_tlt_weights): launch_ev_sums enqueues tle_sums in place of ev_sums
     const double *tr;         // launch_policy_tr's rows [nrows][TR_NSTAT]: launch_ev_final enqueues tle_final in place of ev_final
+    // launch_ev_argmax only (null otherwise)
+    int *tstar;               // [n_event][ldy] the first step of the window that attains the margin, -1 where the margin is NaN
 };
 // one chunk, behind launch_wct_weights: the events of the staged trajectories, then the chunk's sums into the partials
 void launch_ev_chunk(const EvArgs &a, hipStream_t s);
@@ -347,6 +353,11 @@ void launch_ev_chunk(const EvArgs &a, hipStream_t s);
 // (rat_policy_events_user: rat_src_user_events of source_events.h); xs, us, Qt, at, b, win are not read
 void launch_ev_sums(const EvArgs &a, hipStream_t s);
 void launch_ev_final(const EvArgs &a, hipStream_t s);
+// ev_eval's sibling for rat_policy_margin_gradient: the same kernel text, so the same g and the same margins bit for bit, which also keeps
+// the step at which the running margin was last replaced -- only a strictly greater g replaces it, so that is the FIRST step attaining the
+// maximum -- and writes margin [n_event][ldy] and tstar alone (no "any" row, no tau, no mask, no sums behind it); cost, xs, us, Qt, at, b,
+// win as launch_ev_chunk reads them
+void launch_ev_argmax(const EvArgs &a, hipStream_t s);
 
 // ---- rat_policy_tail_events / _user: the same event sums under the CVaR adversary, one row per level (policy_mc.hip) ----------------------------
 // The rows, the weights y (1 above the level's quantile, y_eq on it, 0 below and for a DomainError rollout; ev_final's ratios divide the

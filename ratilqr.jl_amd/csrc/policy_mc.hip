@@ -919,11 +919,12 @@ __global__ __launch_bounds__(MC_THREADS) void tlt_weights(WtArgs a, unsigned *lv
         const bool in = q < a.kc;                                     // (the K tail: no cost, no weight, no bit)
         const double J = in ? a.cost[q] : __builtin_nan("");
         if (in) bad += replay_same(a, q, J) ? 0 : 1;
+        const double S = (a.sample && in) ? a.sample[q] : J;          // (the sample the levels were selected on: the costs, or an event's margins)
         unsigned bits = 0u;
         for (int r = 0; r < a.nrows; ++r) {
             const double v = a.wc[WC_O_INFO + 2 * r], st = a.wc[WC_O_INFO + 2 * r + 1], ye = a.wc[TL_O_YEQ + r];
             double y = 0.0;                                           // (a DomainError rollout, an empty or non-finite sample: no weight)
-            if (!mc_nan(J) && st == WC_ST_SEARCH) y = (J > v) ? 1.0 : (J == v) ? ye : 0.0;
+            if (!mc_nan(S) && st == WC_ST_SEARCH) y = (S > v) ? 1.0 : (S == v) ? ye : 0.0;
             if (in) a.y[(long)r * a.ldy + q] = y;
             bits |= (y != 0.0) ? (1u << r) : 0u;
         }
@@ -1093,7 +1094,7 @@ struct GradientMoments {
         const int N = a.t.N;
         const bool fin = ok && a.bad[q] == 0;
         double G = 0.0, Dx = 0.0;
-        if (fin && compg) G = a.gu[(q * N + t) * 4 + (i - 12)];
+        if (fin && compg) G = a.gu[q * a.ldg + t * 4 + (i - 12)];
         if (fin && compx) Dx = a.t.xs[(q * (N + 1) + t) * a.t.ldx + i] - c;
         return Dev{G, Dx, fin};
     }
@@ -1308,7 +1309,8 @@ __global__ __launch_bounds__(MC_THREADS) void wcp_final(WpArgs a) {
 // into the slot's partial, chunk after chunk in stream order; ev_final sums the slots in index order.  A workgroup (slot, y, row batch)
 // sums either one step's indicators of every event, or one event's per-rollout terms.  No floating-point atomics, and the counts are
 // sums of ones in double: exact, so no atomics there either.
-template <bool QUAD>
+// ARGMAX (launch_ev_argmax, rat_policy_margin_gradient): the same text, and the step at which the running margin was last replaced.
+template <bool QUAD, bool ARGMAX = false>
 __global__ __launch_bounds__(MC_THREADS) void ev_eval(EvArgs a) {
     __shared__ double s_q[QUAD ? EV_MAX * 256 : 1];
     __shared__ double s_a[EV_MAX * 16], s_b[EV_MAX];
@@ -1327,9 +1329,9 @@ __global__ __launch_bounds__(MC_THREADS) void ev_eval(EvArgs a) {
         const bool ok = live && !mc_nan(a.cost[live ? q : 0]);        // selected, not multiplied: the trajectory may hold NaN
         const double *xq = a.xs + q * (N + 1) * a.ldx, *uq = a.us + q * N * a.ldu;
         double M[EV_MAX];
-        int tau[EV_MAX];
+        int tau[EV_MAX], ts[ARGMAX ? EV_MAX : 1];
 #pragma unroll
-        for (int e = 0; e < EV_MAX; ++e) { M[e] = nan; tau[e] = -1; }
+        for (int e = 0; e < EV_MAX; ++e) { M[e] = nan; tau[e] = -1; if (ARGMAX) ts[e] = -1; }
         for (int t = 0; t <= N; ++t) {
             double zv[4];
 #pragma unroll
@@ -1352,7 +1354,10 @@ __global__ __launch_bounds__(MC_THREADS) void ev_eval(EvArgs a) {
                     p += __shfl_xor(p, 32);
                     const double gv = p + s_b[e];
                     if (t >= s_lo[e] && t <= s_hi[e]) {
-                        if (gv > M[e] || mc_nan(M[e])) M[e] = gv;     // (a NaN g never replaces a number)
+                        if (gv > M[e] || mc_nan(M[e])) {              // (a NaN g never replaces a number)
+                            M[e] = gv;
+                            if (ARGMAX && !mc_nan(gv)) ts[e] = t;
+                        }
                         if (gv > 0.0) {
                             bits |= 1u << e;
                             if (tau[e] < 0) tau[e] = t;
@@ -1362,6 +1367,18 @@ __global__ __launch_bounds__(MC_THREADS) void ev_eval(EvArgs a) {
             }
             if (bits) bits |= 1u << ne;
             if (a.mask && kq == 0 && live) a.mask[(long)t * a.ldy + q] = ok ? bits : 0u;
+        }
+        if (ARGMAX) {
+            if (kq == 0 && live) {
+#pragma unroll
+                for (int e = 0; e < EV_MAX; ++e) {
+                    if (e < ne) {
+                        a.margin[(long)e * a.ldy + q] = ok ? M[e] : nan;
+                        a.tstar[(long)e * a.ldy + q] = ok ? ts[e] : -1;
+                    }
+                }
+            }
+            continue;
         }
         if (kq == 0 && live) {
             double Ma = nan;
@@ -1830,6 +1847,14 @@ void launch_ev_chunk(const EvArgs &a, hipStream_t s) {
     if (a.quad) hipLaunchKernelGGL(ev_eval<true>, ge, dim3(MC_THREADS), 0, s, a);
     else hipLaunchKernelGGL(ev_eval<false>, ge, dim3(MC_THREADS), 0, s, a);
     launch_ev_sums(a, s);
+}
+
+void launch_ev_argmax(const EvArgs &a, hipStream_t s) {
+    if (a.kc <= 0 || a.n_event <= 0) return;
+    const long nb = (((a.kc + 15) >> 4) + 3) >> 2;
+    const dim3 ge((unsigned)(nb < 1024 ? nb : 1024));
+    if (a.quad) hipLaunchKernelGGL((ev_eval<true, true>), ge, dim3(MC_THREADS), 0, s, a);
+    else hipLaunchKernelGGL((ev_eval<false, true>), ge, dim3(MC_THREADS), 0, s, a);
 }
 
 void launch_ev_sums(const EvArgs &a, hipStream_t s) {

@@ -186,3 +186,24 @@ struct SrcAdjointPArgs {
     int *bad;                 // [kc] 1: the rollout has a cost but a NaN or Inf in its sensitivities; untouched for a rollout without a cost
     int *n_bad;               // the number of those rollouts, added to (an integer atomic: a count has no order)
 };
+
+// rat_src_margin_adjoint (source_margin_adjoint.h): rat_src_adjoint's team sweeping the margins of RAT_N_MARGIN quadratic events jointly
+// (rat_policy_margin_gradient); the seed of event i is g_z at the step t* that the margin pass recorded, not the cost
+#define SRC_MARGIN_MAX 4      /* events a call sweeps: four lambdas of twelve doubles beside the dual evaluation of f stay in registers */
+struct SrcMarginArgs {
+    const double *xs, *us;    // staged trajectories of the chunk: [kc][N+1][RAT_N], [kc][N][RAT_M] dense
+    int N;
+    long kc;                  // rollouts of the chunk
+    const double *cost;       // [kc] the costs the replay formed (NaN: DomainError, the rollout is passed over)
+    const double *L;          // [N][4][12] or null (open loop)
+    const double *p;          // the model's parameters
+    int quad;                 // 0: every event is linear (g_z = a): Qt is not read
+    const double *Qt;         // [RAT_N_MARGIN][16][16] in the tile as ev_eval reads it: entry (k, i) at k * 16 + i is Q's row i, column k
+    const double *at;         // [RAT_N_MARGIN][16] in the tile
+    const int *tstar;         // [RAT_N_MARGIN][ldt] the chunk's arg-max steps (launch_ev_argmax), -1: the margin is NaN
+    long ldt;
+    double *gu;               // [kc][RAT_N_MARGIN][N][4] dM_ik / du_t with the loop closed downstream, zero padded; untouched for a rollout without a cost
+    int *bad;                 // [RAT_N_MARGIN][ldb] 1: the rollout has a cost but a NaN or Inf in the event's sensitivities; untouched for a rollout without a cost
+    long ldb;
+    int *n_bad;               // [RAT_N_MARGIN] the number of those rollouts per event, added to (an integer atomic: a count has no order)
+};

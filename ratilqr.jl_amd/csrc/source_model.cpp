@@ -71,19 +71,20 @@ std::string src_arch(const char *gcn_arch_name) {
     return out.empty() ? std::string("gfx950") : out;
 }
 
-// indexed by SrcKind:  header                 entry                         entry2               rng_shift draws events rare_user_event param_draws params_ad
+// indexed by SrcKind:  header                 entry                         entry2               rng_shift draws events rare_user_event param_draws params_ad margins
 static const SrcKindRow k_kinds[SRC_NKIND] = {
-    /* SRC_MODEL      */ {"source_kernels.h",    "rat_src_rollout",            "rat_src_linearize", false,    false, false, false, false, false},
-    /* SRC_PETS       */ {"source_pets.h",       "rat_src_pets_rollout",       nullptr,             false,    true,  false, false, false, false},
-    /* SRC_NOISY      */ {"source_noisy.h",      "rat_src_noisy_rollout",      nullptr,             false,    false, false, false, false, false},
-    /* SRC_USER_NOISE */ {"source_user_noise.h", "rat_src_user_noisy_rollout", nullptr,             false,    true,  false, false, true,  false},
-    /* SRC_RARE       */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  false, false, true,  false},
-    /* SRC_EVENTS     */ {"source_events.h",     "rat_src_user_events",        nullptr,             false,    false, true,  false, true,  false},
-    /* SRC_RARE_USER  */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  true,  true,  true,  false},
-    /* SRC_PARAMS     */ {"source_params.h",     "rat_src_params_sample",      nullptr,             false,    false, false, false, true,  false},
-    /* SRC_SOBOL      */ {"source_sobol.h",      "rat_src_sobol_rollout",      nullptr,             false,    true,  false, false, true,  false},
-    /* SRC_ADJOINT    */ {"source_adjoint.h",    "rat_src_adjoint",            nullptr,             false,    true,  false, false, false, false},
-    /* SRC_ADJOINT_P  */ {"source_adjoint_params.h", "rat_src_adjoint_p",   nullptr,             false,    true,  false, false, true,  true},
+    /* SRC_MODEL      */ {"source_kernels.h",    "rat_src_rollout",            "rat_src_linearize", false,    false, false, false, false, false, false},
+    /* SRC_PETS       */ {"source_pets.h",       "rat_src_pets_rollout",       nullptr,             false,    true,  false, false, false, false, false},
+    /* SRC_NOISY      */ {"source_noisy.h",      "rat_src_noisy_rollout",      nullptr,             false,    false, false, false, false, false, false},
+    /* SRC_USER_NOISE */ {"source_user_noise.h", "rat_src_user_noisy_rollout", nullptr,             false,    true,  false, false, true,  false, false},
+    /* SRC_RARE       */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  false, false, true,  false, false},
+    /* SRC_EVENTS     */ {"source_events.h",     "rat_src_user_events",        nullptr,             false,    false, true,  false, true,  false, false},
+    /* SRC_RARE_USER  */ {"source_rare.h",       "rat_src_rare_rollout",       nullptr,             true,     true,  true,  true,  true,  false, false},
+    /* SRC_PARAMS     */ {"source_params.h",     "rat_src_params_sample",      nullptr,             false,    false, false, false, true,  false, false},
+    /* SRC_SOBOL      */ {"source_sobol.h",      "rat_src_sobol_rollout",      nullptr,             false,    true,  false, false, true,  false, false},
+    /* SRC_ADJOINT    */ {"source_adjoint.h",    "rat_src_adjoint",            nullptr,             false,    true,  false, false, false, false, false},
+    /* SRC_ADJOINT_P  */ {"source_adjoint_params.h", "rat_src_adjoint_p",   nullptr,             false,    true,  false, false, true,  true, false},
+    /* SRC_MARGIN_ADJOINT */ {"source_margin_adjoint.h", "rat_src_margin_adjoint", nullptr,      false,    true,  false, false, false, false, true},
 };
 
 const SrcKindRow &src_kind(SrcKind kind) { return k_kinds[kind]; }
@@ -91,7 +92,7 @@ const SrcKindRow &src_kind(SrcKind kind) { return k_kinds[kind]; }
 rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShape &shape, const std::string &arch,
                    std::shared_ptr<const std::vector<char>> *code, std::string *log, double *ms, bool *cached) {
     const SrcKindRow &row = k_kinds[kind];
-    const int npn = row.draws ? shape.npn : 0, npu = row.draws ? shape.npu : 0, nev = row.events ? shape.nev : 0;
+    const int npn = row.draws ? shape.npn : 0, npu = row.draws ? shape.npu : 0, nev = (row.events || row.margins) ? shape.nev : 0;
     const int npar = row.param_draws ? shape.npar : 0, ppn = npar > 0 ? shape.ppn : 0, ppu = npar > 0 ? shape.ppu : 0;
     const int pshift = row.rng_shift ? shape.pshift : 0, nap = row.params_ad ? shape.nap : 0;
     const auto t0 = std::chrono::steady_clock::now();
@@ -126,6 +127,8 @@ rat_rc src_compile(SrcKind kind, const char *source, int n, int m, const SrcShap
     const std::string dne = "-DRAT_N_EVENT=" + std::to_string(nev);
     std::vector<const char *> opts = {"-O3", "-std=c++17", dn.c_str(), dm.c_str(), oa.c_str(), dpn.c_str(), dpu.c_str()};
     if (row.events) opts.push_back(dne.c_str());
+    const std::string dnm = "-DRAT_N_MARGIN=" + std::to_string(nev);
+    if (row.margins) opts.push_back(dnm.c_str());
     if (row.rare_user_event) opts.push_back("-DRAT_RARE_USER_EVENT=1");
     const std::string dnp = "-DRAT_N_PARAMS=" + std::to_string(npar), dppn = "-DRAT_PARAM_NORMALS=" + std::to_string(ppn),
                       dppu = "-DRAT_PARAM_UNIFORMS=" + std::to_string(ppu);

@@ -21,6 +21,7 @@ enum SrcKind {
     SRC_SOBOL,           // SRC_USER_NOISE's rollout with every draw picked from one of two streams (rat_policy_sobol)
     SRC_ADJOINT,         // the adjoint sweep on replayed trajectories (rat_policy_gradient, rat_policy_tail_gradient)
     SRC_ADJOINT_P,       // that sweep with the parameter pass and lambda_0 (rat_policy_param_gradient, rat_policy_tail_param_gradient)
+    SRC_MARGIN_ADJOINT,  // the adjoint sweep seeded by quadratic events' margins, the events of a call jointly (rat_policy_margin_gradient)
     SRC_NKIND
 };
 // One row per kind: what its translation unit is made of and what the module exports.  Every kind is the user's text behind
@@ -30,7 +31,8 @@ enum SrcKind {
 // (parameter sampling is on, rat_policy_params_sampling); with npar == 0 its command line is what it was without the feature.  The two
 // rng_shift kinds get -DRAT_PARAM_SHIFT=1 besides when the shape has pshift (rat_policy_rare_event_params: source_params.h).  SRC_SOBOL
 // alone gets -DRAT_RNG_PICK=1 (rat_rng.h, source_params.h: a second key and the masks that pick a draw's stream).  A params_ad kind gets
-// -DRAT_N_PARAMS=nap, the problem's parameter count, whether or not sampling is on (with sampling on npar == nap).
+// -DRAT_N_PARAMS=nap, the problem's parameter count, whether or not sampling is on (with sampling on npar == nap).  A margins kind gets
+// -DRAT_N_MARGIN=nev: the quadratic events its kernel sweeps jointly (they are data, not source: nothing is asked of the user's text).
 struct SrcKindRow {
     const char *header;          // embedded header with the kind's kernels
     const char *entry, *entry2;  // kernels the module exports (entry2: NULL but for SRC_MODEL's linearisation)
@@ -40,6 +42,7 @@ struct SrcKindRow {
     bool rare_user_event;        // -DRAT_RARE_USER_EVENT=1
     bool param_draws;            // takes npar, ppn, ppu: the kernels that call rat_user_params once per rollout (source_params.h)
     bool params_ad;              // takes nap: the kernel seeds rat_dual[RAT_N_PARAMS] (the source must define RAT_USER_PARAMS_AD)
+    bool margins;                // takes nev as -DRAT_N_MARGIN=nev
 };
 const SrcKindRow &src_kind(SrcKind kind);
 struct SrcShape {                                        // (fields a kind does not take are read as 0)

@@ -235,6 +235,9 @@ class GenericContext(il.Context):
     def policy_tail_gradient(self, *a, **k):
         self._carrier_only("policy_tail_gradient")
 
+    def policy_margin_gradient(self, *a, **k):
+        self._carrier_only("policy_margin_gradient")
+
     def policy_param_gradient(self, *a, **k):
         self._carrier_only("policy_param_gradient")
 

@@ -579,6 +579,32 @@ class Context:
         r.update(self._gradient_part(gl, gL, se, nf))
         return r
 
+    def policy_margin_gradient(self, events, alphas):
+        """Which way to move the policy to clear a safety event (rat_policy_margin_gradient): for each of 1 to 4 events (halfspace, ball,
+        quadratic_event) and each level alpha in [0, 1) (1 to 16), the gradient with respect to l and L of the tail mean of the event's
+        margin M = max over its window of g -- alpha = 0: the mean margin; otherwise CVaR_alpha(M), whose being <= 0 implies
+        P(M > 0) <= 1 - alpha -- by adjoint replay of the last policy_evaluate_noise of this context (source problems, device generator,
+        the affine law).  Returns a list with one dict per event: policy_tail_risk's row keys on that event's margins (bit for bit
+        policy_tail_risk(costs=margins[i])) and grad_l (R, N, m), grad_L (R, N, m, n) (None after an open-loop evaluation), grad_l_se,
+        n_nonfinite as policy_tail_gradient carries them.  The disturbances are held fixed, x_nom and the value at risk are not
+        differentiated; a tie of the arg-max step or of the tail's membership, and a saturated level, give a subgradient."""
+        al, _ = self._tail_rows(alphas)
+        E, Q, a, b, lo, hi = self._events_dense(events)
+        A, Ea = al.size, min(max(E, 1), 4)                            # (the arrays of a call that the library refuses)
+        rows = np.zeros((Ea * max(A, 1), nv.TR_NSTAT))
+        gl, gL, se, _ = self._gradient_out(Ea * max(A, 1))
+        nf = np.zeros(max(E, 1), dtype=np.int64)
+        nv.check(nv.lib().rat_policy_margin_gradient(self.h, C.c_int32(E), nv.P(Q), nv.P(a), nv.P(b), nv.PI(lo), nv.PI(hi),
+                                                     nv.P(al) if A else None, C.c_int32(A), nv.P(rows), nv.P(gl), nv.P(gL), nv.P(se),
+                                                     nf.ctypes.data_as(C.POINTER(C.c_int64))))
+        out = []
+        for i in range(E):
+            sl = slice(i * A, (i + 1) * A)
+            r = self._tail_part(rows[sl])
+            r.update(self._gradient_part(gl[sl].copy(), gL[sl], se[sl].copy(), C.c_int64(int(nf[i]))))
+            out.append(r)
+        return out
+
     def _param_gradient_out(self, R):
         P = getattr(self, "params", np.zeros(0)).size
         return np.zeros((R, P)), np.zeros((R, P)), np.zeros((R, self.n)), np.zeros((R, self.n)), C.c_int64(0)
