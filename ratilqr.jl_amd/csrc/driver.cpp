@@ -2752,30 +2752,37 @@ static rat_rc replay_mismatch(const std::string &F, int bad, int64_t K) {
 }
 
 // Where a replay's rows lie on the device and which slot holds their effective sample size: rat_policy_worst_case's, or (the tail
-// calls) rat_policy_tail_risk's
-struct ReplayRows { const double *d_rows; int nstat, ess; };
-static ReplayRows replay_rows(rat_handle h, bool tail) {
+// calls) rat_policy_tail_risk's; `blocks` blocks of `per` rows each, `stride` doubles apart (the margin gradient: a scratch per event)
+struct ReplayRows { const double *d_rows; int nstat, ess, per, blocks; size_t stride; };
+static ReplayRows replay_rows(rat_handle h, bool tail, int nrows) {
     static_assert(TR_MAX_ALPHA * TR_NSTAT <= WC_MAX_ROWS * WC_NSTAT, "the callers' row buffers hold either kind");
-    if (tail) return ReplayRows{h->d_tr_red + TR_O_ROWS, TR_NSTAT, RAT_TR_ESS};
-    return ReplayRows{h->d_wc_red + WC_O_ROWS, WC_NSTAT, RAT_WC_ESS};
+    if (tail) return ReplayRows{h->d_tr_red + TR_O_ROWS, TR_NSTAT, RAT_TR_ESS, nrows, 1, 0};
+    return ReplayRows{h->d_wc_red + WC_O_ROWS, WC_NSTAT, RAT_WC_ESS, nrows, 1, 0};
 }
 
 // The end of a moment replay, behind its *_final kernel: the rows, the moment kernel's (S0, sum y^2) per row (d_out + o_ess, ess_stride
 // doubles a row), the mismatch count (d_out + o_cnt) and the call's outputs (copies; a null destination is skipped) to the host, the
 // call's one host wait, the replay guard, and the rows' effective sample size against the moment kernel's own S0^2 / sum y^2: two routes
 // to one number (the rows' sums are centred, these are not: 1e-6 relative is far above what either loses and far below any error of the
-// weights).  rows_out is written last: a refused call leaves it alone.
+// weights).  rows_out is written last: a refused call leaves it alone, and so it leaves n_nonfinite_out (the gradients: nf_count ints at
+// d_out + o_nf, the rollouts left out for their sensitivities, widened into it behind both checks; a null destination is skipped).
 struct ReplayCopy { double *dst; size_t off, count; };
-static rat_rc replay_finish(rat_handle h, const std::string &F, bool tail, int nrows, const double *d_out, size_t o_ess, int ess_stride, size_t o_cnt,
-                            std::initializer_list<ReplayCopy> copies, double *rows_out) {
+static rat_rc replay_finish(rat_handle h, const std::string &F, const ReplayRows &rr, const double *d_out, size_t o_ess, int ess_stride, size_t o_cnt,
+                            std::initializer_list<ReplayCopy> copies, double *rows_out, size_t o_nf = 0, int nf_count = 0,
+                            int64_t *n_nonfinite_out = nullptr) {
     rat_rc rc;
     HIPCHK(hipGetLastError());
-    const ReplayRows rr = replay_rows(h, tail);
-    double rows[WC_MAX_ROWS * WC_NSTAT], ess[WC_MAX_ROWS * 4];
-    int bad = 0;
-    HIPCHK(hipMemcpyAsync(rows, rr.d_rows, (size_t)nrows * rr.nstat * 8, hipMemcpyDeviceToHost, h->stream));
+    const int nrows = rr.per * rr.blocks;
+    static_assert(WC_MAX_ROWS * WC_NSTAT <= SRC_MARGIN_MAX * TR_MAX_ALPHA * TR_NSTAT && SRC_MARGIN_MAX * TR_MAX_ALPHA * 2 <= WC_MAX_ROWS * 4,
+                  "the margin gradient's rows are the most, the parameter moments' sums the widest");
+    double rows[SRC_MARGIN_MAX * TR_MAX_ALPHA * TR_NSTAT], ess[WC_MAX_ROWS * 4];
+    int bad = 0, nf[SRC_MARGIN_MAX] = {0, 0, 0, 0};
+    for (int b = 0; b < rr.blocks; ++b)
+        HIPCHK(hipMemcpyAsync(rows + (size_t)b * rr.per * rr.nstat, rr.d_rows + b * rr.stride, (size_t)rr.per * rr.nstat * 8, hipMemcpyDeviceToHost,
+                              h->stream));
     HIPCHK(hipMemcpyAsync(ess, d_out + o_ess, (size_t)nrows * ess_stride * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(&bad, d_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (n_nonfinite_out) HIPCHK(hipMemcpyAsync(nf, d_out + o_nf, sizeof(int) * nf_count, hipMemcpyDeviceToHost, h->stream));
     for (const ReplayCopy &c : copies)
         if (c.dst) HIPCHK(hipMemcpyAsync(c.dst, d_out + c.off, c.count * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2787,6 +2794,7 @@ static rat_rc replay_finish(rat_handle h, const std::string &F, bool tail, int n
             return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
                                      " is not the row's " + std::to_string(e_row));
     }
+    for (int e = 0; n_nonfinite_out && e < nf_count; ++e) n_nonfinite_out[e] = nf[e];
     for (int i = 0; i < nrows * rr.nstat; ++i) rows_out[i] = rows[i];
     return RAT_OK;
 }
@@ -2835,7 +2843,7 @@ static rat_rc replay_trajectory(rat_handle h, const std::string &F, const Replay
                             [&](const WtArgs &c, ReplayChunk ch) -> rat_rc { launch_wct_chunk(c, ch.live, h->stream); return RAT_OK; })))
         return rc;
     launch_wct_final(ta, h->stream);
-    return replay_finish(h, F, rs.tail(), nrows, h->d_wt_out, o_ess, 2, o_cnt,
+    return replay_finish(h, F, replay_rows(h, rs.tail(), nrows), h->d_wt_out, o_ess, 2, o_cnt,
                          {{mean_out, o_mean, (size_t)nrows * (N + 1) * d}, {cov_out, o_cov, (size_t)nrows * (N + 1) * d * d}}, rows_out);
 }
 
@@ -2895,7 +2903,7 @@ static rat_rc replay_disturbance(rat_handle h, const std::string &F, const Repla
                             }, h->d_mc_wo)))
         return rc;
     launch_wcd_final(da, h->stream);
-    return replay_finish(h, F, rs.tail(), nrows, h->d_wd_out, o_ess, 2, o_cnt,
+    return replay_finish(h, F, replay_rows(h, rs.tail(), nrows), h->d_wd_out, o_ess, 2, o_cnt,
                          {{mean_w_out, o_mean, nrs * n}, {cov_w_out, o_cov, nrs * n * n}, {cov_wz_out, o_wz, nrs * n * d}}, rows_out);
 }
 
@@ -2969,7 +2977,7 @@ static rat_rc replay_params(rat_handle h, const std::string &F, const char *fn, 
                             })))
         return rc;
     launch_wcp_final(pa, h->stream);
-    return replay_finish(h, F, rs.tail(), nrows, h->d_wp_out, o_ess, 4, o_cnt,
+    return replay_finish(h, F, replay_rows(h, rs.tail(), nrows), h->d_wp_out, o_ess, 4, o_cnt,
                          {{mean_q_out, o_mean, (size_t)nrows * P}, {cov_q_out, o_cov, (size_t)nrows * P * P}, {cov_qJ_out, o_qJ, (size_t)nrows * P}},
                          rows_out);
 }
@@ -3003,6 +3011,12 @@ extern "C" rat_rc rat_policy_tail_params(rat_handle h, const double *alpha, int3
 // a compile that failed on the header's own refusal of a source with rat_user_policy is RAT_ERR_UNSUPPORTED
 static rat_rc gradient_compile_rc(rat_rc rc) {
     return (rc == RAT_ERR_ARG && g_err.find("the source defines RAT_USER_POLICY") != std::string::npos) ? RAT_ERR_UNSUPPORTED : rc;
+}
+
+// the head of an adjoint kernel's arguments: the replayed chunk as replay_chunks staged it, the gains and the parameters
+static void adjoint_head(SrcAdjointHead &sa, const WtArgs &c, ReplayChunk ch, const rat_handle_s::McReplay &rec, rat_handle h) {
+    sa.xs = c.xs; sa.us = c.us; sa.N = c.N; sa.kc = (long)ch.kc; sa.cost = c.cost_re;
+    sa.L = rec.has_L ? h->d_mc_in + rec.o_L : nullptr; sa.p = h->d_src_p;
 }
 
 extern "C" rat_rc rat_policy_gradient_check(const char *source, int32_t n, int32_t m, int32_t normals, int32_t uniforms) {
@@ -3052,8 +3066,7 @@ static rat_rc replay_gradient(rat_handle h, const std::string &F, const char *fn
     if ((rc = replay_chunks(h, rs, reinterpret_cast<int *>(h->d_pg_out + o_cnt), pa.t,
                             [&](const WtArgs &c, ReplayChunk ch) -> rat_rc {
                                 SrcAdjointArgs sa;                    // the chunk's adjoints, behind its rollouts
-                                sa.xs = c.xs; sa.us = c.us; sa.N = N; sa.kc = (long)ch.kc; sa.cost = c.cost_re;
-                                sa.L = rec.has_L ? h->d_mc_in + rec.o_L : nullptr; sa.p = h->d_src_p;
+                                adjoint_head(sa, c, ch, rec, h);
                                 sa.gu = h->d_pg_gu; sa.bad = h->d_pg_bad; sa.n_bad = reinterpret_cast<int *>(h->d_pg_out + o_nf);
                                 HIPCHK(launch_src(kadj, ch.kc, 4, h->stream, &sa));
                                 launch_pg_chunk(pa, ch.live, h->stream);
@@ -3061,15 +3074,9 @@ static rat_rc replay_gradient(rat_handle h, const std::string &F, const char *fn
                             })))
         return rc;
     launch_pg_final(pa, h->stream);
-    double nf_slot = 0.0;                                             // (the count is an int in a slot of the doubles)
-    if ((rc = replay_finish(h, F, rs.tail(), nrows, h->d_pg_out, o_ess, 2, o_cnt,
-                            {{grad_l_out, o_gl, nrs * m}, {grad_L_out, o_gL, nrs * m * n}, {grad_l_se_out, o_se, nrs * m}, {&nf_slot, o_nf, 1}},
-                            rows_out)))
-        return rc;
-    int nf = 0;
-    memcpy(&nf, &nf_slot, sizeof(int));
-    if (n_nonfinite_out) *n_nonfinite_out = nf;
-    return RAT_OK;
+    return replay_finish(h, F, replay_rows(h, rs.tail(), nrows), h->d_pg_out, o_ess, 2, o_cnt,
+                         {{grad_l_out, o_gl, nrs * m}, {grad_L_out, o_gL, nrs * m * n}, {grad_l_se_out, o_se, nrs * m}}, rows_out, o_nf, 1,
+                         n_nonfinite_out);
 }
 
 extern "C" rat_rc rat_policy_gradient(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
@@ -3137,7 +3144,7 @@ static rat_rc replay_param_gradient(rat_handle h, const std::string &F, const ch
                                     double *grad_p_se_out, double *grad_x0_out, double *grad_x0_se_out, int64_t *n_nonfinite_out) {
     rat_rc rc;
     const rat_handle_s::McReplay rec = h->mc_rec;
-    const int n = h->n, N = h->N, nrows = rs.nrows(), P = (int)h->src_np;
+    const int n = h->n, nrows = rs.nrows(), P = (int)h->src_np;
     HIPCHK(hipSetDevice(h->device));
     hipFunction_t kadj = nullptr;
     if ((rc = src_kernel(h, SRC_ADJOINT_P, SrcShape{rec.npn, rec.npu, 0}, fn, &kadj))) return param_gradient_compile_rc(rc);
@@ -3160,8 +3167,7 @@ static rat_rc replay_param_gradient(rat_handle h, const std::string &F, const ch
     if ((rc = replay_chunks(h, rs, reinterpret_cast<int *>(h->d_ppg_out + o_cnt), pa.t,
                             [&](const WtArgs &c, ReplayChunk ch) -> rat_rc {
                                 SrcAdjointPArgs sa;                   // the chunk's adjoints, behind its rollouts
-                                sa.xs = c.xs; sa.us = c.us; sa.N = N; sa.kc = (long)ch.kc; sa.cost = c.cost_re;
-                                sa.L = rec.has_L ? h->d_mc_in + rec.o_L : nullptr; sa.p = h->d_src_p;
+                                adjoint_head(sa, c, ch, rec, h);
                                 sa.j0 = (long)ch.k0; sa.seed = rec.seed; sa.zpn = h->d_ps_zn; sa.zpu = h->d_ps_zu;
                                 sa.gp = h->d_ppg_gp; sa.lam0 = h->d_ppg_l0; sa.bad = h->d_pg_bad;
                                 sa.n_bad = reinterpret_cast<int *>(h->d_ppg_out + o_nf);
@@ -3171,16 +3177,10 @@ static rat_rc replay_param_gradient(rat_handle h, const std::string &F, const ch
                             })))
         return rc;
     launch_ppg_final(pa, h->stream);
-    double nf_slot = 0.0;                                             // (the count is an int in a slot of the doubles)
-    if ((rc = replay_finish(h, F, rs.tail(), nrows, h->d_ppg_out, o_ess, 2, o_cnt,
-                            {{grad_p_out, o_gp, (size_t)nrows * P}, {grad_p_se_out, o_gps, (size_t)nrows * P}, {grad_x0_out, o_gx, (size_t)nrows * n},
-                             {grad_x0_se_out, o_gxs, (size_t)nrows * n}, {&nf_slot, o_nf, 1}},
-                            rows_out)))
-        return rc;
-    int nf = 0;
-    memcpy(&nf, &nf_slot, sizeof(int));
-    if (n_nonfinite_out) *n_nonfinite_out = nf;
-    return RAT_OK;
+    return replay_finish(h, F, replay_rows(h, rs.tail(), nrows), h->d_ppg_out, o_ess, 2, o_cnt,
+                         {{grad_p_out, o_gp, (size_t)nrows * P}, {grad_p_se_out, o_gps, (size_t)nrows * P}, {grad_x0_out, o_gx, (size_t)nrows * n},
+                          {grad_x0_se_out, o_gxs, (size_t)nrows * n}},
+                         rows_out, o_nf, 1, n_nonfinite_out);
 }
 
 extern "C" rat_rc rat_policy_param_gradient(rat_handle h, const double *kl_bound, int32_t n_bound, const double *theta, int32_t n_theta,
@@ -3278,7 +3278,7 @@ static rat_rc events_run(rat_handle h, const std::string &F, int n_event, const 
                             [&](const WtArgs &c, ReplayChunk ch) -> rat_rc {
                                 ea.xs = c.xs; ea.us = c.us; ea.ldx = c.ldx; ea.ldu = c.ldu; ea.n = c.n; ea.m = c.m; ea.N = c.N; ea.kc = c.kc; ea.cost = c.cost;
                                 ea.ldy = c.ldy; ea.nrows = c.nrows; ea.y = c.y; ea.wc = c.wc; ea.first = ch.k0 == 0;
-                                ea.live = ch.live; ea.tr = tail ? replay_rows(h, true).d_rows : nullptr;
+                                ea.live = ch.live; ea.tr = tail ? replay_rows(h, true, nrows).d_rows : nullptr;
                                 rat_rc rce;
                                 if ((rce = eval(ea, ch.k0))) return rce;
                                 if (margin_out)                       // the chunk's margins, event by event, to their place among the K
@@ -3292,7 +3292,7 @@ static rat_rc events_run(rat_handle h, const std::string &F, int n_event, const 
     double rows[WC_MAX_ROWS * WC_NSTAT];
     int bad = 0;
     std::vector<double> ev((size_t)nrows * ne1 * EV_NSTAT);
-    const ReplayRows rr = replay_rows(h, tail);
+    const ReplayRows rr = replay_rows(h, tail, nrows);
     HIPCHK(hipMemcpyAsync(rows, rr.d_rows, (size_t)nrows * rr.nstat * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(&bad, h->d_ev_out + o_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(ev.data(), h->d_ev_out + o_ev, ev.size() * 8, hipMemcpyDeviceToHost, h->stream));
@@ -3478,8 +3478,7 @@ extern "C" rat_rc rat_policy_margin_gradient(rat_handle h, int32_t n_event, cons
                                     launch_tlt_weights(w, h->d_mg_live + (size_t)e * nlive, h->stream);
                                 }
                                 SrcMarginArgs sa;
-                                sa.xs = c.xs; sa.us = c.us; sa.N = N; sa.kc = (long)ch.kc; sa.cost = c.cost_re;
-                                sa.L = rec.has_L ? h->d_mc_in + rec.o_L : nullptr; sa.p = h->d_src_p;
+                                adjoint_head(sa, c, ch, rec, h);
                                 sa.quad = Q ? 1 : 0; sa.Qt = h->d_mg_out; sa.at = h->d_mg_out + EV_O_A;
                                 sa.tstar = h->d_mg_tstar + ch.k0; sa.ldt = (long)K;
                                 sa.gu = h->d_mg_gu; sa.bad = h->d_mg_bad; sa.ldb = (long)chunk; sa.n_bad = d_nf;
@@ -3490,29 +3489,9 @@ extern "C" rat_rc rat_policy_margin_gradient(rat_handle h, int32_t n_event, cons
                             })))
         return rc;
     for (int e = 0; e < E; ++e) launch_pg_final(pa[e], h->stream);
-    HIPCHK(hipGetLastError());
-    double rows[SRC_MARGIN_MAX * TR_MAX_ALPHA * TR_NSTAT], ess[SRC_MARGIN_MAX * TR_MAX_ALPHA * 2];
-    int bad = 0, nf[SRC_MARGIN_MAX] = {0, 0, 0, 0};
-    for (int e = 0; e < E; ++e)
-        HIPCHK(hipMemcpyAsync(rows + (size_t)e * A * TR_NSTAT, h->d_mg_tr + (size_t)e * TR_SCRATCH + TR_O_ROWS, (size_t)A * TR_NSTAT * 8,
-                              hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(ess, h->d_mg_out + o_ess, (size_t)R * 2 * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(&bad, d_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(nf, d_nf, sizeof(int) * E, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(grad_l_out, h->d_mg_out + o_gl, nrs * m * 8, hipMemcpyDeviceToHost, h->stream));
-    if (grad_L_out) HIPCHK(hipMemcpyAsync(grad_L_out, h->d_mg_out + o_gL, nrs * m * n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (grad_l_se_out) HIPCHK(hipMemcpyAsync(grad_l_se_out, h->d_mg_out + o_se, nrs * m * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if ((rc = replay_mismatch(F, bad, K))) return rc;
-    for (int r = 0; r < R; ++r) {                                     // (replay_finish's second route to the effective sample size)
-        const double e_row = rows[r * TR_NSTAT + RAT_TR_ESS], e_mom = ess[2 * r] * ess[2 * r] / ess[2 * r + 1];
-        if (std::isfinite(e_row) && !(std::fabs(e_mom - e_row) <= 1e-6 * e_row))
-            return fail(RAT_ERR_HIP, F + "row " + std::to_string(r) + ": the moment kernel's effective sample size " + std::to_string(e_mom) +
-                                     " is not the row's " + std::to_string(e_row));
-    }
-    if (n_nonfinite_out) for (int e = 0; e < E; ++e) n_nonfinite_out[e] = nf[e];
-    for (int i = 0; i < R * TR_NSTAT; ++i) rows_out[i] = rows[i];
-    return RAT_OK;
+    return replay_finish(h, F, ReplayRows{h->d_mg_tr + TR_O_ROWS, TR_NSTAT, RAT_TR_ESS, A, E, TR_SCRATCH}, h->d_mg_out, o_ess, 2, o_cnt,
+                         {{grad_l_out, o_gl, nrs * m}, {grad_L_out, o_gL, nrs * m * n}, {grad_l_se_out, o_se, nrs * m}}, rows_out, o_nf, E,
+                         n_nonfinite_out);
 }
 
 extern "C" rat_rc rat_user_event_check(const char *source, int32_t n, int32_t m, int32_t n_event) {

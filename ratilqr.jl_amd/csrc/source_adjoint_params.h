@@ -9,25 +9,20 @@
 //   lambda_t = (x part of g_t) + L_t' gu_t                      (open loop, L == NULL: the x part alone)
 //   dJ_k / dp = gp,   dJ_k / dx_0 = lambda_0
 //
-// The lambda recursion is rat_src_adjoint's (source_adjoint.h), the same operations in the same order on the same team of sixteen lanes
-// per rollout; gu is not stored.  The parameter pass rides on it: lane i evaluates c and f once more at (x_t, u_t) as duals of zero
-// tangent with p as rat_dual[RAT_N_PARAMS] seeded in direction i (and, with more than sixteen parameters, again in direction 16 + i);
-// c's partial and, behind it, the lane's column of f_p dotted with lambda_{t+1} (j = 0 .. n - 1 in order, fused multiply-adds) is the
-// step's term, added to the lane's gp.  No cross-lane traffic; a lane with no parameter evaluates nothing and holds an exact zero.  With
-// RAT_USER_F_JACOBIAN the hook serves f_x, f_u as in the sibling; f_p always comes from AD of rat_user_f.
+// The lambda recursion is rat_src_adjoint's (source_adjoint.h) on the team of source_adjoint_lanes.h; gu is not stored.  The parameter
+// pass rides on it: lane i evaluates c and f once more at (x_t, u_t) as duals of zero tangent with p as rat_dual[RAT_N_PARAMS] seeded in
+// direction i (and, with more than sixteen parameters, again in direction 16 + i); c's partial and, behind it, the lane's column of f_p
+// dotted with lambda_{t+1} (j = 0 .. n - 1 in order, fused multiply-adds) is the step's term, added to the lane's gp.  No cross-lane
+// traffic; a lane with no parameter evaluates nothing and holds an exact zero.  With RAT_USER_F_JACOBIAN the hook serves f_x, f_u; f_p
+// always comes from AD of rat_user_f.
 //
 // With parameter sampling on (RAT_USER_PARAMS_ON) every lane forms the rollout's own q again from the replayed seed and the global
 // rollout index, as rat_src_user_events does, and everything above is evaluated at q: the derivative is with respect to a common
 // additive shift of the drawn parameters.  rat_user_params itself is not differentiated.
 //
 // A rollout without a cost (NaN: DomainError) is passed over by predicate.  A rollout with a cost but a NaN or Inf in h_x, any g_t, h_p or
-// any parameter term is flagged in bad and counted; what it stores is selected out downstream, never multiplied.  Every lane of the
-// wavefront runs every step: there is no early return.
+// any parameter term is flagged in bad and counted; what it stores is selected out downstream, never multiplied.
 #pragma once
-#include "rat_ad.h"
-#include "source_step.h"
-#include "source_params.h"
-#include "source_adjoint_lanes.h"
 
 #ifndef RAT_USER_NOISE
 #error "the source does not define RAT_USER_NOISE: rat_policy_param_gradient replays rat_policy_evaluate_noise, which needs '#define RAT_USER_NOISE' and rat_user_noise(k, x, u, rng, w, p)"
@@ -41,6 +36,8 @@
 #if !defined(RAT_N_PARAMS) || RAT_N_PARAMS < 0 || RAT_N_PARAMS > 32
 #error "rat_policy_param_gradient is compiled for 0 .. 32 parameters (RAT_N_PARAMS)"
 #endif
+#include "source_adjoint_lanes.h"
+#include "source_params.h"
 
 #define ADJP_TILES ((RAT_N_PARAMS + 15) / 16)                         /* parameter tiles of sixteen directions: 0, 1 or 2 */
 
@@ -54,64 +51,38 @@ __device__ __forceinline__ void adjp_seed(const double *p, int dir, rat_dual (&p
 
 extern "C" __global__ __launch_bounds__(64) void rat_src_adjoint_p(SrcAdjointPArgs a) {
 #ifdef RAT_USER_F_JACOBIAN
-    __shared__ double s_col[4][(RAT_N + RAT_M) * RAT_N];              // per team: column z of [f_x | f_u] at z * RAT_N
+    __shared__ double s_col[4][ADJ_COLUMNS];
+#else
+    double (*const s_col)[ADJ_COLUMNS] = nullptr;
 #endif
-    const int lane = threadIdx.x, i = lane & 15, kk = lane >> 4, team = lane & 48;
-    const long q = (long)blockIdx.x * 4 + kk;
-    const int N = a.N;
-    const bool ok = q < a.kc && !src_nan(a.cost[q < a.kc ? q : 0]);
-    const bool isx = i < 12;
-    const bool act = ok && (isx ? (i < RAT_N) : (i - 12 < RAT_M));    // (a dead lane, the K tail, a rollout without a cost: exact zeros)
-    const int zi = isx ? i : RAT_N + (i - 12);                        // the lane's direction in z = (x, u)
-    const double *__restrict__ xq = a.xs + q * (long)(N + 1) * RAT_N;
-    const double *__restrict__ uq = a.us + q * (long)N * RAT_M;
+    const AdjTeam T(a);
+    const int N = a.N, i = T.i;
+    const bool ok = T.ok;
+    const double *__restrict__ xq = T.xq, *__restrict__ uq = T.uq;
     // the rollout's parameters: the problem's, or with sampling on its own q (an overdraw or a NaN there was the rollout kernel's to
     // report: the stored cost is NaN)
     src_rollout_params own;
     int pover = 0;
-    if (ok) (void)own.draw(q + a.j0, a.seed, a.zpn, a.zpu, a.p, pover);
+    if (ok) (void)own.draw(T.q + a.j0, a.seed, a.zpn, a.zpu, a.p, pover);
     const double *p = own.of(a.p);
     double lam[RAT_N], gp[2] = {0.0, 0.0}, l0 = 0.0;
     bool bad = false;
-    {                                                                 // lambda_N = h_x(x_N)
-        double g = 0.0;
-        if (act && isx) {
-            rat_dual xd[RAT_N];
-#pragma unroll
-            for (int j = 0; j < RAT_N; ++j) xd[j] = rat_dual(xq[(long)N * RAT_N + j], j == zi ? 1.0 : 0.0);
-            g = rat_user_h<rat_dual>(xd, p).d;
-            bad = bad || !adj_finite(g);
-        }
 #if RAT_N_PARAMS > 0
 #pragma unroll
-        for (int b = 0; b < ADJP_TILES; ++b) {                        // gp = h_p(x_N), direction 16 b + i
-            if (ok && 16 * b + i < RAT_N_PARAMS) {
-                rat_dual xd[RAT_N], pd[RAT_N_PARAMS];
+    for (int b = 0; b < ADJP_TILES; ++b) {                            // gp = h_p(x_N), direction 16 b + i (ahead of lambda_N: fewer live registers)
+        if (ok && 16 * b + i < RAT_N_PARAMS) {
+            rat_dual xd[RAT_N], pd[RAT_N_PARAMS];
 #pragma unroll
-                for (int j = 0; j < RAT_N; ++j) xd[j] = rat_dual(xq[(long)N * RAT_N + j], 0.0);
-                adjp_seed(p, 16 * b + i, pd);
-                gp[b] = rat_user_h<rat_dual>(xd, pd).d;
-                bad = bad || !adj_finite(gp[b]);
-            }
+            for (int j = 0; j < RAT_N; ++j) xd[j] = rat_dual(xq[(long)N * RAT_N + j], 0.0);
+            adjp_seed(p, 16 * b + i, pd);
+            gp[b] = rat_user_h<rat_dual>(xd, pd).d;
+            bad = bad || !adj_finite(gp[b]);
         }
-#endif
-#pragma unroll
-        for (int j = 0; j < RAT_N; ++j) lam[j] = adj_from(g, team + j);
     }
-    for (int t = N - 1; t >= 0; --t) {
-#ifdef RAT_USER_F_JACOBIAN
-        if (ok && i == 0) {                                           // f_returns_jacobian (ileqg.jl:302-311): A, B column-major
-            double x[RAT_N], u[RAT_M], xn[RAT_N], A[RAT_N * RAT_N], B[RAT_N * RAT_M];
-#pragma unroll
-            for (int j = 0; j < RAT_N; ++j) x[j] = xq[(long)t * RAT_N + j];
-#pragma unroll
-            for (int j = 0; j < RAT_M; ++j) u[j] = uq[(long)t * RAT_M + j];
-            rat_user_f_jacobian(x, u, xn, A, B, p);
-            for (int e = 0; e < RAT_N * RAT_N; ++e) s_col[kk][e] = A[e];
-            for (int e = 0; e < RAT_N * RAT_M; ++e) s_col[kk][RAT_N * RAT_N + e] = B[e];
-        }
-        __syncthreads();
 #endif
+    adj_terminal(T, N, p, lam, bad);
+    for (int t = N - 1; t >= 0; --t) {
+        adj_jacobian(T, t, p, true, s_col[T.kk]);
 #if RAT_N_PARAMS > 0
 #pragma unroll
         for (int b = 0; b < ADJP_TILES; ++b) {                        // the parameter pass: c_p + f_p' lambda_{t+1}, direction 16 b + i
@@ -132,52 +103,23 @@ extern "C" __global__ __launch_bounds__(64) void rat_src_adjoint_p(SrcAdjointPAr
         }
 #endif
         double g = 0.0;
-        if (act) {
+        if (T.act) {
             rat_dual xd[RAT_N], ud[RAT_M];
-#pragma unroll
-            for (int j = 0; j < RAT_N; ++j) xd[j] = rat_dual(xq[(long)t * RAT_N + j], j == zi ? 1.0 : 0.0);
-#pragma unroll
-            for (int j = 0; j < RAT_M; ++j) ud[j] = rat_dual(uq[(long)t * RAT_M + j], RAT_N + j == zi ? 1.0 : 0.0);
+            double col[RAT_N];
+            adj_seed(T, t, xd, ud);
             g = rat_user_c<rat_dual>(t, xd, ud, p).d;                 // c_z, component zi
-#ifdef RAT_USER_F_JACOBIAN
+            adj_column(T, xd, ud, p, s_col[T.kk], col);
 #pragma unroll
-            for (int j = 0; j < RAT_N; ++j) g = __builtin_fma(s_col[kk][zi * RAT_N + j], lam[j], g);
-#else
-            rat_dual xn[RAT_N];
-            rat_user_f<rat_dual>(xd, ud, xn, p);                      // column zi of [f_x | f_u]
-#pragma unroll
-            for (int j = 0; j < RAT_N; ++j) g = __builtin_fma(xn[j].d, lam[j], g);
-#endif
+            for (int j = 0; j < RAT_N; ++j) g = __builtin_fma(col[j], lam[j], g);
             bad = bad || !adj_finite(g);
         }
-#ifdef RAT_USER_F_JACOBIAN
-        __syncthreads();                                              // (the columns are read: the next step may write)
-#endif
-        double gu[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) gu[j] = adj_from(g, team + 12 + j);
-        double ln = 0.0;
-        if (act && isx) {                                             // lambda_t, component i
-            ln = g;
-            if (a.L) {
-#pragma unroll
-                for (int j = 0; j < RAT_M; ++j) ln = __builtin_fma(a.L[(long)t * LSTR + j * 12 + i], gu[j], ln);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < RAT_N; ++j) lam[j] = adj_from(ln, team + j);
-        l0 = ln;                                                      // (after step 0: lambda_0, component i; zero in a padding lane)
+        adj_columns_read();
+        l0 = adj_close(T, t, g, a.L, lam);                            // (after step 0: lambda_0, component i; zero in a padding lane)
     }
-    int b = bad ? 1 : 0;
-#pragma unroll
-    for (int s = 1; s < 16; s <<= 1) b |= __builtin_amdgcn_ds_bpermute((lane ^ s) << 2, b);
     if (ok) {
-        a.gp[q * 32 + i] = gp[0];
-        a.gp[q * 32 + 16 + i] = gp[1];
-        if (isx) a.lam0[q * 12 + i] = l0;
-        if (i == 0) {
-            a.bad[q] = b;
-            if (b) (void)__hip_atomic_fetch_add(a.n_bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        a.gp[T.q * 32 + i] = gp[0];
+        a.gp[T.q * 32 + 16 + i] = gp[1];
+        if (T.isx) a.lam0[T.q * 12 + i] = l0;
     }
+    adj_flag(T, bad, a.bad, T.q, a.n_bad);
 }

@@ -155,48 +155,39 @@ struct SrcSobolArgs {
     unsigned long long pick[SOBOL_MAX_VAR][4];   // per variant: parameter normals, parameter uniforms, step normals, step uniforms
 };
 
-// rat_src_adjoint (source_adjoint.h): the adjoint sweep of every rollout of one replayed chunk (rat_policy_gradient /
-// rat_policy_tail_gradient), a team of sixteen lanes per rollout, four rollouts per wavefront
-struct SrcAdjointArgs {
+// The head of the adjoint kernels' argument blocks (source_adjoint_lanes.h builds its team from it; adjoint_head of driver.cpp fills it):
+// one replayed chunk, a team of sixteen lanes per rollout, four rollouts per wavefront
+struct SrcAdjointHead {
     const double *xs, *us;    // staged trajectories of the chunk: [kc][N+1][RAT_N], [kc][N][RAT_M] dense
     int N;
     long kc;                  // rollouts of the chunk
     const double *cost;       // [kc] the costs the replay formed (NaN: DomainError, the rollout is passed over)
     const double *L;          // [N][4][12] or null (open loop)
     const double *p;          // the model's parameters
+};
+
+// rat_src_adjoint (source_adjoint.h): the adjoint sweep of every rollout of the chunk (rat_policy_gradient / rat_policy_tail_gradient)
+struct SrcAdjointArgs : SrcAdjointHead {
     double *gu;               // [kc][N][4] dJ_k / du_t with the loop closed downstream, zero padded; untouched for a rollout without a cost
     int *bad;                 // [kc] 1: the rollout has a cost but a NaN or Inf in its sensitivities; untouched for a rollout without a cost
     int *n_bad;               // the number of those rollouts, added to (an integer atomic: a count has no order)
 };
 
 // rat_src_adjoint_p (source_adjoint_params.h): rat_src_adjoint's sweep with the parameter pass and lambda_0 (rat_policy_param_gradient /
-// rat_policy_tail_param_gradient), the same team of sixteen lanes per rollout
-struct SrcAdjointPArgs {
-    const double *xs, *us;    // staged trajectories of the chunk: [kc][N+1][RAT_N], [kc][N][RAT_M] dense
-    int N;
-    long kc;                  // rollouts of the chunk
-    const double *cost;       // [kc] the costs the replay formed (NaN: DomainError, the rollout is passed over)
-    const double *L;          // [N][4][12] or null (open loop)
-    const double *p;          // the model's parameters
+// rat_policy_tail_param_gradient)
+struct SrcAdjointPArgs : SrcAdjointHead {
     long j0;                  // global index of the chunk's first rollout (parameter sampling: the rollout's own q)
     unsigned long long seed;  // the replayed evaluation's seed
     const double *zpn, *zpu;  // the handle's injected parameter streams (whole, indexed by the global rollout), or both null: the generator
     double *gp;               // [kc][32] dJ_k / dp, zero padded; untouched for a rollout without a cost
     double *lam0;             // [kc][12] dJ_k / dx_0 with the loop closed, zero padded; untouched for a rollout without a cost
-    int *bad;                 // [kc] 1: the rollout has a cost but a NaN or Inf in its sensitivities; untouched for a rollout without a cost
-    int *n_bad;               // the number of those rollouts, added to (an integer atomic: a count has no order)
+    int *bad, *n_bad;         // as SrcAdjointArgs'
 };
 
-// rat_src_margin_adjoint (source_margin_adjoint.h): rat_src_adjoint's team sweeping the margins of RAT_N_MARGIN quadratic events jointly
+// rat_src_margin_adjoint (source_margin_adjoint.h): the team sweeping the margins of RAT_N_MARGIN quadratic events jointly
 // (rat_policy_margin_gradient); the seed of event i is g_z at the step t* that the margin pass recorded, not the cost
 #define SRC_MARGIN_MAX 4      /* events a call sweeps: four lambdas of twelve doubles beside the dual evaluation of f stay in registers */
-struct SrcMarginArgs {
-    const double *xs, *us;    // staged trajectories of the chunk: [kc][N+1][RAT_N], [kc][N][RAT_M] dense
-    int N;
-    long kc;                  // rollouts of the chunk
-    const double *cost;       // [kc] the costs the replay formed (NaN: DomainError, the rollout is passed over)
-    const double *L;          // [N][4][12] or null (open loop)
-    const double *p;          // the model's parameters
+struct SrcMarginArgs : SrcAdjointHead {
     int quad;                 // 0: every event is linear (g_z = a): Qt is not read
     const double *Qt;         // [RAT_N_MARGIN][16][16] in the tile as ev_eval reads it: entry (k, i) at k * 16 + i is Q's row i, column k
     const double *at;         // [RAT_N_MARGIN][16] in the tile

@@ -11,13 +11,11 @@
 //   t > t*     gu_t = 0, exactly
 //   t < t*     g_t = f_z(x_t, u_t)' lambda_{t+1};   gu_t = its u part;   lambda_t = its x part + L_t' gu_t   (open loop: the x part alone)
 //
-// rat_src_adjoint's team (source_adjoint.h): sixteen lanes per rollout, four rollouts per wavefront, lane i direction i of the padded
-// 12 + 4 tile, lambda replicated in the registers of the team -- here one lambda per event.  The events are swept JOINTLY: per step one
-// rat_dual evaluation of rat_user_f (or one rat_user_f_jacobian by lane 0 of the team, the columns through LDS), and the lane's column of
-// f_z is dotted with each event's lambda (j = 0 .. n - 1 in order, fused multiply-adds from 0).  An event whose t* lies below the step
-// contributes exact zeros by SELECTION, not through 0 * f_z (which is NaN where f_z is not finite) and not by a branch around the
-// exchanges: those are wavefront-wide, every lane of the wavefront runs every step, there is no early return.  What a team may skip is
-// the evaluation of f at the steps t >= max_i t*, where no event of the rollout reads it: that holds no exchange.
+// The team of source_adjoint_lanes.h, with one lambda per event.  The events are swept JOINTLY: per step one column of f_z per lane, dotted
+// with each event's lambda (j = 0 .. n - 1 in order, fused multiply-adds from 0), and one close per event.  An event whose t* lies below
+// the step contributes exact zeros by SELECTION, not through 0 * f_z (which is NaN where f_z is not finite) and not by a branch around
+// the exchanges.  What a team may skip is the evaluation of f at the steps t >= max_i t*, where no event of the rollout reads it: that
+// holds no exchange.
 // g_z at t* costs sixteen exchanges of z within the team and sixteen fused multiply-adds against the lane's row of Q_i + Q_i', which the
 // workgroup forms once in LDS from the tile the events call uploads (entry (k, i) at k * 16 + i: Q_i's row i, column k); no AD, no MFMA.
 //
@@ -26,9 +24,6 @@
 // g_t below) is flagged in bad[i] and counted in n_bad[i]; its gu is stored as it came out and is selected out downstream, never
 // multiplied.  An event's sweep reads nothing of another event's but the shared f_z: its bits do not depend on the other events.
 #pragma once
-#include "rat_ad.h"
-#include "source_step.h"
-#include "source_adjoint_lanes.h"
 
 #ifndef RAT_USER_NOISE
 #error "the source does not define RAT_USER_NOISE: rat_policy_margin_gradient replays rat_policy_evaluate_noise, which needs '#define RAT_USER_NOISE' and rat_user_noise(k, x, u, rng, w, p)"
@@ -39,123 +34,75 @@
 #if RAT_N_MARGIN < 1 || RAT_N_MARGIN > SRC_MARGIN_MAX
 #error "RAT_N_MARGIN must be in 1 .. 4"
 #endif
+#include "source_adjoint_lanes.h"
 
 extern "C" __global__ __launch_bounds__(64) void rat_src_margin_adjoint(SrcMarginArgs a) {
     constexpr int E = RAT_N_MARGIN;
     __shared__ double s_S[E * 256];                                   // Q_e + Q_e' in the tile: entry (i, k) at e * 256 + k * 16 + i
     __shared__ double s_a[E * 16];
 #ifdef RAT_USER_F_JACOBIAN
-    __shared__ double s_col[4][(RAT_N + RAT_M) * RAT_N];              // per team: column z of [f_x | f_u] at z * RAT_N
+    __shared__ double s_col[4][ADJ_COLUMNS];
+#else
+    double (*const s_col)[ADJ_COLUMNS] = nullptr;
 #endif
-    const int lane = threadIdx.x, i = lane & 15, kk = lane >> 4, team = lane & 48;
-    const long q = (long)blockIdx.x * 4 + kk;
-    const int N = a.N;
+    const AdjTeam T(a);
+    const int N = a.N, i = T.i;
     if (a.quad) {
-        for (int e = lane; e < E * 256; e += 64) {
+        for (int e = T.lane; e < E * 256; e += 64) {
             const int ev = e >> 8, k = (e >> 4) & 15, r = e & 15;
             s_S[e] = a.Qt[ev * 256 + k * 16 + r] + a.Qt[ev * 256 + r * 16 + k];
         }
     }
-    for (int e = lane; e < E * 16; e += 64) s_a[e] = a.at[e];
+    for (int e = T.lane; e < E * 16; e += 64) s_a[e] = a.at[e];
     __syncthreads();
-    const bool ok = q < a.kc && !src_nan(a.cost[q < a.kc ? q : 0]);
-    const bool isx = i < 12;
-    const bool act = ok && (isx ? (i < RAT_N) : (i - 12 < RAT_M));    // (a dead lane, the K tail, a rollout without a cost: exact zeros)
-    const int zi = isx ? i : RAT_N + (i - 12);                        // the lane's direction in z = (x, u)
-    const double *__restrict__ xq = a.xs + q * (long)(N + 1) * RAT_N;
-    const double *__restrict__ uq = a.us + q * (long)N * RAT_M;
     int ts[E], tmax = -1;
     double sd[E], lam[E][RAT_N];
     bool bad[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) {                                     // g_z at t*, component i, and lambda_N
-        ts[e] = ok ? a.tstar[(long)e * a.ldt + q] : -1;
+        ts[e] = T.ok ? a.tstar[(long)e * a.ldt + T.q] : -1;
         if (ts[e] < 0 || ts[e] > N) ts[e] = -1;                       // (nothing outside 0 .. N is ever an index)
         tmax = ts[e] > tmax ? ts[e] : tmax;
         double z = 0.0;
-        if (act && ts[e] >= 0) {
-            if (isx) z = xq[(long)ts[e] * RAT_N + i];
-            else if (ts[e] < N) z = uq[(long)ts[e] * RAT_M + (i - 12)];
+        if (T.act && ts[e] >= 0) {
+            if (T.isx) z = T.xq[(long)ts[e] * RAT_N + i];
+            else if (ts[e] < N) z = T.uq[(long)ts[e] * RAT_M + (i - 12)];
         }
         double g = s_a[e * 16 + i];
         if (a.quad) {
 #pragma unroll
-            for (int k = 0; k < 16; ++k) g = __builtin_fma(s_S[e * 256 + k * 16 + i], adj_from(z, team + k), g);
+            for (int k = 0; k < 16; ++k) g = __builtin_fma(s_S[e * 256 + k * 16 + i], adj_from(z, T.team + k), g);
         }
-        const bool seeded = act && ts[e] >= 0 && (isx || ts[e] < N);  // (u_N = 0 is no variable: t* = N has no u part)
+        const bool seeded = T.act && ts[e] >= 0 && (T.isx || ts[e] < N);   // (u_N = 0 is no variable: t* = N has no u part)
         sd[e] = seeded ? g : 0.0;
         bad[e] = seeded && !adj_finite(g);
-        const double l0 = (ts[e] == N && isx) ? sd[e] : 0.0;
+        const double l0 = (ts[e] == N && T.isx) ? sd[e] : 0.0;
 #pragma unroll
-        for (int j = 0; j < RAT_N; ++j) lam[e][j] = adj_from(l0, team + j);
+        for (int j = 0; j < RAT_N; ++j) lam[e][j] = adj_from(l0, T.team + j);
     }
     for (int t = N - 1; t >= 0; --t) {
         const bool need = t < tmax;                                   // (uniform over the team: some event of the rollout reads f_z here)
-#ifdef RAT_USER_F_JACOBIAN
-        if (ok && need && i == 0) {                                   // f_returns_jacobian (ileqg.jl:302-311): A, B column-major
-            double x[RAT_N], u[RAT_M], xn[RAT_N], A[RAT_N * RAT_N], B[RAT_N * RAT_M];
-#pragma unroll
-            for (int j = 0; j < RAT_N; ++j) x[j] = xq[(long)t * RAT_N + j];
-#pragma unroll
-            for (int j = 0; j < RAT_M; ++j) u[j] = uq[(long)t * RAT_M + j];
-            rat_user_f_jacobian(x, u, xn, A, B, a.p);
-            for (int e = 0; e < RAT_N * RAT_N; ++e) s_col[kk][e] = A[e];
-            for (int e = 0; e < RAT_N * RAT_M; ++e) s_col[kk][RAT_N * RAT_N + e] = B[e];
-        }
-        __syncthreads();
-#endif
+        adj_jacobian(T, t, a.p, need, s_col[T.kk]);
         double col[RAT_N];                                            // column zi of [f_x | f_u]
 #pragma unroll
         for (int j = 0; j < RAT_N; ++j) col[j] = 0.0;
-        if (act && need) {
-#ifdef RAT_USER_F_JACOBIAN
-#pragma unroll
-            for (int j = 0; j < RAT_N; ++j) col[j] = s_col[kk][zi * RAT_N + j];
-#else
-            rat_dual xd[RAT_N], ud[RAT_M], xn[RAT_N];
-#pragma unroll
-            for (int j = 0; j < RAT_N; ++j) xd[j] = rat_dual(xq[(long)t * RAT_N + j], j == zi ? 1.0 : 0.0);
-#pragma unroll
-            for (int j = 0; j < RAT_M; ++j) ud[j] = rat_dual(uq[(long)t * RAT_M + j], RAT_N + j == zi ? 1.0 : 0.0);
-            rat_user_f<rat_dual>(xd, ud, xn, a.p);
-#pragma unroll
-            for (int j = 0; j < RAT_N; ++j) col[j] = xn[j].d;
-#endif
+        if (T.act && need) {
+            rat_dual xd[RAT_N], ud[RAT_M];
+            adj_seed(T, t, xd, ud);
+            adj_column(T, xd, ud, a.p, s_col[T.kk], col);
         }
-#ifdef RAT_USER_F_JACOBIAN
-        __syncthreads();                                              // (the columns are read: the next step may write)
-#endif
+        adj_columns_read();
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             double dot = 0.0;
 #pragma unroll
             for (int j = 0; j < RAT_N; ++j) dot = __builtin_fma(col[j], lam[e][j], dot);
-            const double g = !act ? 0.0 : (t < ts[e]) ? dot : (t == ts[e]) ? sd[e] : 0.0;   // selected: above t* exact zeros
+            const double g = !T.act ? 0.0 : (t < ts[e]) ? dot : (t == ts[e]) ? sd[e] : 0.0;   // selected: above t* exact zeros
             bad[e] = bad[e] || !adj_finite(g);
-            double gu[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) gu[j] = adj_from(g, team + 12 + j);
-            double ln = 0.0;
-            if (act && isx) {                                         // lambda_t, component i
-                ln = g;
-                if (a.L) {
-#pragma unroll
-                    for (int j = 0; j < RAT_M; ++j) ln = __builtin_fma(a.L[(long)t * LSTR + j * 12 + i], gu[j], ln);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < RAT_N; ++j) lam[e][j] = adj_from(ln, team + j);
-            if (ok && !isx) a.gu[((q * E + e) * N + t) * 4 + (i - 12)] = g;   // (zero in a padding lane)
+            (void)adj_close(T, t, g, a.L, lam[e]);
+            if (T.ok && !T.isx) a.gu[((T.q * E + e) * N + t) * 4 + (i - 12)] = g;   // (zero in a padding lane)
         }
     }
 #pragma unroll
-    for (int e = 0; e < E; ++e) {
-        int b = bad[e] ? 1 : 0;
-#pragma unroll
-        for (int s = 1; s < 16; s <<= 1) b |= __builtin_amdgcn_ds_bpermute((lane ^ s) << 2, b);
-        if (ok && i == 0) {
-            a.bad[(long)e * a.ldb + q] = b;
-            if (b) (void)__hip_atomic_fetch_add(a.n_bad + e, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    for (int e = 0; e < E; ++e) adj_flag(T, bad[e], a.bad, (long)e * a.ldb + T.q, a.n_bad + e);
 }
