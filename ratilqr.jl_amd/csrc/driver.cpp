@@ -3314,6 +3314,16 @@ static rat_rc events_run(rat_handle h, const std::string &F, int n_event, const 
     return RAT_OK;
 }
 
+// One event in the 12 + 4 tile: component i of (x, u) sits at i for a state and at 12 + i - n for a control.  Q (column-major over (x, u),
+// or null) goes to tq as the MFMA's A operand reads it (entry (k, i) at k * 16 + i), a to ta
+static void event_tile_put(int n, int d, const double *Q, const double *a, double *tq, double *ta) {
+    auto tix = [n](int i) { return i < n ? i : 12 + i - n; };
+    for (int i = 0; i < d; ++i) {
+        ta[tix(i)] = a[i];
+        if (Q) for (int k = 0; k < d; ++k) tq[tix(k) * 16 + tix(i)] = Q[i + (size_t)d * k];
+    }
+}
+
 // What a call with quadratic events checks of them (n_event in range already) and their tile, the head of d_ev_out as ev_eval reads it
 static rat_rc events_tile(rat_handle h, const std::string &F, int32_t n_event, const double *Q, const double *a, const double *b,
                           const int32_t *t_lo, const int32_t *t_hi, std::vector<double> *tile) {
@@ -3327,15 +3337,11 @@ static rat_rc events_tile(rat_handle h, const std::string &F, int32_t n_event, c
         if (Q) for (int i = 0; i < d * d; ++i) fin = fin && std::isfinite(Q[(size_t)e * d * d + i]);
         if (!fin) return fail(RAT_ERR_ARG, F + "event " + std::to_string(e) + ": Q, a and b must be finite");
     }
-    // the events in the 12 + 4 tile: Q as the MFMA's A operand reads it (entry (k, i) at k * 16 + i), a, b, the windows
+    // the events in the 12 + 4 tile (event_tile_put), b, the windows
     std::vector<double> &in = *tile;
     in.assign(EV_O_EV, 0.0);
-    auto tix = [n](int i) { return i < n ? i : 12 + i - n; };
     for (int e = 0; e < n_event; ++e) {
-        for (int i = 0; i < d; ++i) {
-            in[EV_O_A + e * 16 + tix(i)] = a[e * d + i];
-            if (Q) for (int k = 0; k < d; ++k) in[(size_t)e * 256 + tix(k) * 16 + tix(i)] = Q[(size_t)e * d * d + i + (size_t)d * k];
-        }
+        event_tile_put(n, d, Q ? Q + (size_t)e * d * d : nullptr, a + e * d, &in[(size_t)e * 256], &in[EV_O_A + e * 16]);
         in[EV_O_B + e] = b[e];
         int32_t w[2] = {t_lo[e], t_hi[e]};
         memcpy(&in[EV_O_WIN + e], w, sizeof(w));
@@ -3603,11 +3609,7 @@ static rat_rc re_run(rat_handle h, const std::string &F, const ReKernels &kn, co
     std::vector<double> &pack = pk.data;
     const size_t o_q = pack.size(), o_a = o_q + 256, o_s = o_a + 16;
     pack.resize(o_s + (size_t)(N + 1) * 12, 0.0);                     // (row N: the parameter shift, read with pn > 0 alone)
-    auto tix = [n](int i) { return i < n ? i : 12 + i - n; };
-    for (int i = 0; i < d; ++i) {
-        pack[o_a + tix(i)] = a[i];
-        if (Q) for (int k = 0; k < d; ++k) pack[o_q + tix(k) * 16 + tix(i)] = Q[i + (size_t)d * k];
-    }
+    event_tile_put(n, d, Q, a, &pack[o_q], &pack[o_a]);
     if (shift_in) for (int t = 0; t < N; ++t) for (int i = 0; i < nc; ++i) pack[o_s + (size_t)t * 12 + i] = shift_in[(size_t)t * nc + i];
     if (par && par->pshift_in) for (int i = 0; i < pn; ++i) pack[o_s + (size_t)N * 12 + i] = par->pshift_in[i];
     size_t cap_red = h->d_re_red ? RE_SCRATCH : 0;

@@ -1398,13 +1398,21 @@ __global__ __launch_bounds__(MC_THREADS) void ev_eval(EvArgs a) {
     }
 }
 
-__global__ __launch_bounds__(MC_THREADS) void ev_sums(EvArgs a) {
+// ev_sums_body: the sums of one chunk, once for the KL rows (ev_sums) and the tail rows (tle_sums).  TAIL reads the liveness word of the
+// rollout's group of four first (tlt_weights wrote it: bit r says some y of level r in the group is not zero), a load of one word per four
+// lanes.  What it passes over would have added 0 (y == 0, or no indicator bit), which changes no bit of a sum that started at +0 and holds
+// no negative term; y != 0 means the rollout has a cost, so the steps' workgroups do not read the costs at all.  Everything else -- the lane
+// that takes a rollout, the order it takes them in, the trees, the partials -- is written once: alpha = 0 is the theta = 0 row and the
+// switch tail_dense gives the same bits because there is no second copy to keep in step.
+template <bool TAIL>
+__device__ __forceinline__ void ev_sums_body(const EvArgs &a) {
     __shared__ double sh[(EV_MAX + 1) * MC_THREADS];
     const int slot = blockIdx.x, by = blockIdx.y, r0 = blockIdx.z * EV_ROWS, tid = threadIdx.x;
     const int nr = (a.nrows - r0 < EV_ROWS) ? a.nrows - r0 : EV_ROWS;
     const int nsteps = a.mask ? a.N + 1 : 0, ny = nsteps + a.n_event + 1;
     double *p = a.part + (((size_t)blockIdx.z * ny + by) * EV_SLOTS + slot) * EV_PART;
     const long T = (long)EV_SLOTS * MC_THREADS;
+    const unsigned rows = (1u << nr) - 1u;                            // the rows of this workgroup, as bits of a word shifted by r0 (uniform over the workgroup)
     if (by < nsteps) {                                                // one step: sum y [g_e(t) > 0] per row and event
         double acc[EV_ROWS][EV_MAX + 1];
 #pragma unroll
@@ -1412,141 +1420,21 @@ __global__ __launch_bounds__(MC_THREADS) void ev_sums(EvArgs a) {
 #pragma unroll
             for (int e = 0; e <= EV_MAX; ++e) acc[r][e] = 0.0;
         for (long q = (long)slot * MC_THREADS + tid; q < a.kc; q += T) {
-            const bool ok = !mc_nan(a.cost[q]);
-            const unsigned bits = ok ? a.mask[(long)by * a.ldy + q] : 0u;
-#pragma unroll
-            for (int r = 0; r < EV_ROWS; ++r) {
-                if (r < nr) {                                         // (uniform over the workgroup)
-                    const double y = ok ? a.y[(long)(r0 + r) * a.ldy + q] : 0.0;
-#pragma unroll
-                    for (int e = 0; e <= EV_MAX; ++e) acc[r][e] += ((bits >> e) & 1u) ? y : 0.0;
-                }
+            unsigned on = rows, bits;
+            bool ok = true;
+            if (TAIL) {
+                on = (a.live[q >> 2] >> r0) & rows;
+                if (on == 0u) continue;                               // no weight in any row of the workgroup: nothing is loaded
+                bits = a.mask[(long)by * a.ldy + q];
+                if (bits == 0u) continue;                             // no event at this step: no weight is loaded
+            } else {
+                ok = !mc_nan(a.cost[q]);
+                bits = ok ? a.mask[(long)by * a.ldy + q] : 0u;
             }
-        }
-#pragma unroll
-        for (int r = 0; r < EV_ROWS; ++r) {
-            if (r < nr) {
-                block_tree_n<EV_MAX + 1>(acc[r], sh);
-                if (tid == 0) {
-#pragma unroll
-                    for (int e = 0; e <= EV_MAX; ++e) p[r * (EV_MAX + 1) + e] = a.first ? acc[r][e] : p[r * (EV_MAX + 1) + e] + acc[r][e];
-                }
-            }
-        }
-        return;
-    }
-    const int e = by - nsteps;                                        // one event: the per-rollout terms per row, the counts, the largest margin
-    double s[EV_ROWS][EV_NSUM], cnt[2] = {0.0, 0.0}, mx = -__builtin_inf();
-#pragma unroll
-    for (int r = 0; r < EV_ROWS; ++r)
-#pragma unroll
-        for (int i = 0; i < EV_NSUM; ++i) s[r][i] = 0.0;
-    for (long q = (long)slot * MC_THREADS + tid; q < a.kc; q += T) {
-        const bool ok = !mc_nan(a.cost[q]);
-        const double Mv = a.margin[(long)e * a.ldy + q];
-        const int tv = a.tau[(long)e * a.ldy + q];
-        const bool A = ok && tv >= 0;
-        cnt[0] += A ? 1.0 : 0.0;
-        cnt[1] += ok ? 1.0 : 0.0;
-        if (ok && Mv > mx) mx = Mv;
-#pragma unroll
-        for (int r = 0; r < EV_ROWS; ++r) {
-            if (r < nr) {
-                const double y = ok ? a.y[(long)(r0 + r) * a.ldy + q] : 0.0, y2 = y * y;
-                s[r][0] += y;
-                s[r][1] += A ? y : 0.0;
-                s[r][2] += A ? y2 : 0.0;
-                s[r][3] += A ? 0.0 : y2;
-                s[r][4] += ok ? y * Mv : 0.0;
-                s[r][5] += A ? y * (double)tv : 0.0;
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < EV_ROWS; ++r) {
-        if (r < nr) {
-            block_tree_n<EV_NSUM>(s[r], sh);
-            if (tid == 0) {
-#pragma unroll
-                for (int i = 0; i < EV_NSUM; ++i) p[r * EV_NSUM + i] = a.first ? s[r][i] : p[r * EV_NSUM + i] + s[r][i];
-            }
-        }
-    }
-    block_tree_n<2>(cnt, sh);
-    mx = block_tree<2>(mx, sh);
-    if (tid == 0) {
-        p[EV_O_NVIOL] = a.first ? cnt[0] : p[EV_O_NVIOL] + cnt[0];
-        p[EV_O_NOK] = a.first ? cnt[1] : p[EV_O_NOK] + cnt[1];
-        p[EV_O_MMAX] = (a.first || mx > p[EV_O_MMAX]) ? mx : p[EV_O_MMAX];
-    }
-}
-
-__global__ __launch_bounds__(MC_THREADS) void ev_final(EvArgs a) {
-    __shared__ double S[EV_NSUM + 3];
-    const int e = blockIdx.x, r = blockIdx.y, z = r / EV_ROWS, rr = r % EV_ROWS, tid = threadIdx.x;
-    const int nsteps = a.mask ? a.N + 1 : 0, ne1 = a.n_event + 1, ny = nsteps + ne1;
-    const double *pe = a.part + ((size_t)z * ny + nsteps + e) * EV_SLOTS * EV_PART;
-    if (tid < EV_NSUM + 3) {
-        const int i = (tid < EV_NSUM) ? rr * EV_NSUM + tid : EV_O_NVIOL + (tid - EV_NSUM);
-        double v = pe[i];
-        for (int sl = 1; sl < EV_SLOTS; ++sl) {
-            const double x = pe[sl * EV_PART + i];
-            v = (i == EV_O_MMAX) ? (x > v ? x : v) : v + x;
-        }
-        S[tid] = v;
-    }
-    __syncthreads();
-    const double st = a.wc[WC_O_INFO + 2 * r + 1], nan = __builtin_nan("");
-    const bool dead = (st == WC_ST_EMPTY || st == WC_ST_NONFINITE);
-    const double sy = S[0];
-    if (tid == 0) {
-        double *o = a.event_out + ((size_t)r * ne1 + e) * EV_NSTAT;
-        const double pr = S[1] / sy, se2 = (1.0 - pr) * (1.0 - pr) * S[2] + pr * pr * S[3];
-        o[0] = dead ? nan : pr;
-        o[1] = dead ? nan : sqrt(se2) / sy;
-        o[2] = dead ? nan : S[4] / sy;
-        o[3] = dead ? nan : S[EV_NSUM + 2];
-        o[4] = dead ? nan : S[5] / S[1];                              // (NaN when no weighted rollout violates: 0 / 0)
-        o[5] = dead ? nan : S[EV_NSUM];
-        o[6] = dead ? nan : S[EV_NSUM + 1];                           // N_OK: the host forms PROB_ROBUST from it
-        o[7] = (st == WC_ST_SAT) ? 1.0 : (st == WC_ST_EMPTY) ? 2.0 : (st == WC_ST_NONFINITE) ? 3.0 : 0.0;
-    }
-    for (int t = tid; t < nsteps; t += MC_THREADS) {
-        const double *ps = a.part + ((size_t)z * ny + t) * EV_SLOTS * EV_PART + rr * (EV_MAX + 1) + e;
-        double v = 0.0;
-        for (int sl = 0; sl < EV_SLOTS; ++sl) v += ps[sl * EV_PART];
-        a.step_out[((size_t)r * ne1 + e) * nsteps + t] = dead ? nan : v / sy;
-    }
-}
-
-// ---- rat_policy_tail_events: the event sums under tail rows, where one rollout in a hundred carries weight ----------------------------------
-// tle_sums is ev_sums -- the same lane takes the same rollouts in the same order, the same trees, the same partials -- with the liveness
-// word of the rollout's group of four (tlt_weights wrote it: bit r says some y of level r in the group is not zero) read first: a load of
-// one word per four lanes.  What is passed over would have added 0 (y == 0, or no indicator bit), which changes no bit of a sum that
-// started at +0 and holds no negative term; y != 0 means the rollout has a cost, so the steps' workgroups do not read the costs at all.
-__global__ __launch_bounds__(MC_THREADS) void tle_sums(EvArgs a) {
-    __shared__ double sh[(EV_MAX + 1) * MC_THREADS];
-    const int slot = blockIdx.x, by = blockIdx.y, r0 = blockIdx.z * EV_ROWS, tid = threadIdx.x;
-    const int nr = (a.nrows - r0 < EV_ROWS) ? a.nrows - r0 : EV_ROWS;
-    const int nsteps = a.mask ? a.N + 1 : 0, ny = nsteps + a.n_event + 1;
-    double *p = a.part + (((size_t)blockIdx.z * ny + by) * EV_SLOTS + slot) * EV_PART;
-    const long T = (long)EV_SLOTS * MC_THREADS;
-    const unsigned rows = (1u << nr) - 1u;                            // the levels of this workgroup, as bits of a word shifted by r0
-    if (by < nsteps) {                                                // one step: sum y [g_e(t) > 0] per row and event
-        double acc[EV_ROWS][EV_MAX + 1];
-#pragma unroll
-        for (int r = 0; r < EV_ROWS; ++r)
-#pragma unroll
-            for (int e = 0; e <= EV_MAX; ++e) acc[r][e] = 0.0;
-        for (long q = (long)slot * MC_THREADS + tid; q < a.kc; q += T) {
-            const unsigned on = (a.live[q >> 2] >> r0) & rows;
-            if (on == 0u) continue;                                   // no weight in any row of the workgroup: nothing is loaded
-            const unsigned bits = a.mask[(long)by * a.ldy + q];
-            if (bits == 0u) continue;                                 // no event at this step: no weight is loaded
 #pragma unroll
             for (int r = 0; r < EV_ROWS; ++r) {
                 if ((on >> r) & 1u) {
-                    const double y = a.y[(long)(r0 + r) * a.ldy + q];
+                    const double y = ok ? a.y[(long)(r0 + r) * a.ldy + q] : 0.0;
 #pragma unroll
                     for (int e = 0; e <= EV_MAX; ++e) acc[r][e] += ((bits >> e) & 1u) ? y : 0.0;
                 }
@@ -1578,17 +1466,21 @@ __global__ __launch_bounds__(MC_THREADS) void tle_sums(EvArgs a) {
         cnt[0] += A ? 1.0 : 0.0;
         cnt[1] += ok ? 1.0 : 0.0;
         if (ok && Mv > mx) mx = Mv;
-        const unsigned on = (a.live[q >> 2] >> r0) & rows;
-        if (on == 0u) continue;
+        unsigned on = rows;
+        if (TAIL) {
+            on = (a.live[q >> 2] >> r0) & rows;
+            if (on == 0u) continue;
+        }
 #pragma unroll
         for (int r = 0; r < EV_ROWS; ++r) {
             if ((on >> r) & 1u) {
-                const double y = a.y[(long)(r0 + r) * a.ldy + q], y2 = y * y;
+                const double y = (TAIL || ok) ? a.y[(long)(r0 + r) * a.ldy + q] : 0.0, y2 = y * y;
                 s[r][0] += y;
                 s[r][1] += A ? y : 0.0;
                 s[r][2] += A ? y2 : 0.0;
                 s[r][3] += A ? 0.0 : y2;
-                s[r][4] += (y != 0.0) ? y * Mv : 0.0;                 // (selected, not multiplied: a rollout without weight may hold a NaN margin)
+                if (TAIL) s[r][4] += (y != 0.0) ? y * Mv : 0.0;       // (selected, not multiplied: a rollout without weight may hold a NaN margin)
+                else s[r][4] += ok ? y * Mv : 0.0;
                 s[r][5] += A ? y * (double)tv : 0.0;
             }
         }
@@ -1612,9 +1504,16 @@ __global__ __launch_bounds__(MC_THREADS) void tle_sums(EvArgs a) {
     }
 }
 
-// ev_final on a tail row: the same sums in the same order; FLAG is the level's RAT_TR_FLAG, and PROB_ROBUST is the CVaR adversary aimed at
-// the event -- the largest probability of the event under any p with dp/dq <= N_OK / TAIL_N -- formed here from the counts and the row.
-__global__ __launch_bounds__(MC_THREADS) void tle_final(EvArgs a) {
+__global__ __launch_bounds__(MC_THREADS) void ev_sums(EvArgs a) { ev_sums_body<false>(a); }
+// (rat_policy_tail_events: the event sums under tail rows, where one rollout in a hundred carries weight)
+__global__ __launch_bounds__(MC_THREADS) void tle_sums(EvArgs a) { ev_sums_body<true>(a); }
+
+// ev_final_body: the slots of one (event, row) summed in index order, then the statistics.  A KL row (ev_final) takes its state from the
+// row's word of a.wc and leaves N_OK in slot 6 for the host's rat_kl_event_bound; a tail row (tle_final) takes RAT_TR_FLAG of its level,
+// and its PROB_ROBUST is the CVaR adversary aimed at the event -- the largest probability of the event under any p with
+// dp/dq <= N_OK / TAIL_N -- formed here from the counts and the row.
+template <bool TAIL>
+__device__ __forceinline__ void ev_final_body(const EvArgs &a) {
     __shared__ double S[EV_NSUM + 3];
     const int e = blockIdx.x, r = blockIdx.y, z = r / EV_ROWS, rr = r % EV_ROWS, tid = threadIdx.x;
     const int nsteps = a.mask ? a.N + 1 : 0, ne1 = a.n_event + 1, ny = nsteps + ne1;
@@ -1629,23 +1528,37 @@ __global__ __launch_bounds__(MC_THREADS) void tle_final(EvArgs a) {
         S[tid] = v;
     }
     __syncthreads();
-    const double flag = a.tr[r * TR_NSTAT + 7], tail = a.tr[r * TR_NSTAT + 4], nan = __builtin_nan("");
-    const bool dead = (flag == 2.0 || flag == 3.0);                   // RAT_TR_EMPTY, RAT_TR_NONFINITE
+    const double nan = __builtin_nan("");
+    double flag;
+    bool dead;
+    if (TAIL) {
+        flag = a.tr[r * TR_NSTAT + 7];
+        dead = (flag == 2.0 || flag == 3.0);                          // RAT_TR_EMPTY, RAT_TR_NONFINITE
+    } else {
+        const double st = a.wc[WC_O_INFO + 2 * r + 1];
+        dead = (st == WC_ST_EMPTY || st == WC_ST_NONFINITE);
+        flag = (st == WC_ST_SAT) ? 1.0 : (st == WC_ST_EMPTY) ? 2.0 : (st == WC_ST_NONFINITE) ? 3.0 : 0.0;
+    }
     const double sy = S[0];
     if (tid == 0) {
         double *o = a.event_out + ((size_t)r * ne1 + e) * EV_NSTAT;
         const double pr = S[1] / sy, se2 = (1.0 - pr) * (1.0 - pr) * S[2] + pr * pr * S[3];
         const double nv = S[EV_NSUM], nok = S[EV_NSUM + 1];
-        double rob = (nv / nok) / (tail / nok);
-        rob = rob < 1.0 ? rob : 1.0;
-        if (rob < pr) rob = pr;                                       // (every violator in the tail: the two are one number, and rounding must not part them)
         o[0] = dead ? nan : pr;
         o[1] = dead ? nan : sqrt(se2) / sy;
         o[2] = dead ? nan : S[4] / sy;
         o[3] = dead ? nan : S[EV_NSUM + 2];
         o[4] = dead ? nan : S[5] / S[1];                              // (NaN when no weighted rollout violates: 0 / 0)
         o[5] = dead ? nan : nv;
-        o[6] = dead ? nan : rob;
+        if (TAIL) {
+            const double tail = a.tr[r * TR_NSTAT + 4];
+            double rob = (nv / nok) / (tail / nok);
+            rob = rob < 1.0 ? rob : 1.0;
+            if (rob < pr) rob = pr;                                   // (every violator in the tail: the two are one number, and rounding must not part them)
+            o[6] = dead ? nan : rob;
+        } else {
+            o[6] = dead ? nan : nok;                                  // N_OK: the host forms PROB_ROBUST from it
+        }
         o[7] = flag;
     }
     for (int t = tid; t < nsteps; t += MC_THREADS) {
@@ -1655,6 +1568,9 @@ __global__ __launch_bounds__(MC_THREADS) void tle_final(EvArgs a) {
         a.step_out[((size_t)r * ne1 + e) * nsteps + t] = dead ? nan : v / sy;
     }
 }
+
+__global__ __launch_bounds__(MC_THREADS) void ev_final(EvArgs a) { ev_final_body<false>(a); }
+__global__ __launch_bounds__(MC_THREADS) void tle_final(EvArgs a) { ev_final_body<true>(a); }
 
 // ---- rat_policy_sobol: first-order and total Sobol indices from the pick-freeze costs Y [d + 2][K] ------------------------------------------
 // Rows A, B, then the d groups' AB_i (rat_src_sobol_rollout, source_sobol.h).  Three launches, every sum in mc_pass1's order (lane g of the
